@@ -91,6 +91,33 @@ def perturbed_inputs(S, model, count, first_seed):
     return out
 
 
+DUMP_BYTES = 60 * 10**6   # --dump-outputs writes at most this many bytes of values (64 MB with room for the .npy headers)
+
+
+def dump_problems(g_off, jac_off, budget=DUMP_BYTES):
+    """The problems whose outputs --dump-outputs writes, in batch order: all of them when their g and Jacobian values fit in
+    `budget` bytes, else a fixed, seeded sample of whole problems that does (the same for every run of the same batch)."""
+    sizes = 8 * (np.diff(g_off) + np.diff(jac_off))
+    if sizes.sum() <= budget:
+        return np.arange(len(sizes))
+    order = np.random.default_rng(0).permutation(len(sizes))
+    return np.sort(order[np.cumsum(sizes[order]) <= budget])
+
+
+def dump_outputs(out_dir, g, jac, g_off, jac_off):
+    """What the last timed step left in the output buffers, as out_dir/g.npy and out_dir/jac.npy (float64): the constraint values
+    and the Jacobian values of the problems dump_problems picks, their segments back to back."""
+    import torch
+
+    os.makedirs(out_dir, exist_ok=True)
+    picked = dump_problems(g_off, jac_off)
+    whole = len(picked) == len(g_off) - 1
+    for name, buf, off in (("g", g, g_off), ("jac", jac, jac_off)):
+        vals = buf[:int(off[-1])] if whole else torch.cat([buf[int(off[p]):int(off[p + 1])] for p in picked])
+        np.save(os.path.join(out_dir, name + ".npy"), vals.cpu().numpy())
+    return picked
+
+
 def _cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -147,12 +174,18 @@ def cpu_baseline(sched, params, x, terrain, budget_s=3.0):
     instance per hardware thread, all running at once (the oracle is not re-entrant, like the reference)."""
     import statistics
     import subprocess
+    import tempfile
     import threading
 
     from oracle import binding as ob
 
-    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "native"])
-    ob.use_library(os.path.join(ROOT, "oracle", "_build", "libtowr_oracle_native.so"))
+    # built into a directory of this run, not into the checkout (which whoever benchmarks it may not be able to write);
+    # the loaded library outlives the directory
+    with tempfile.TemporaryDirectory(prefix="towr_oracle_native_") as tmp:
+        native = os.path.join(tmp, "libtowr_oracle_native.so")
+        subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "native", "NATIVE=" + native])
+        ob.use_library(native)
+        ob.lib()
 
     def make():
         return ob.OracleProblem("anymal", terrain, sched.durations(), sched.contact(), dt_dynamic=params.dt_dynamic,
@@ -608,12 +641,17 @@ def main():
     ap.add_argument("--placement-tries", type=int, default=12,
                     help="allocate the output buffers this many times at different places of device memory and keep the fastest "
                          "(untimed probe steps, before the W warm-up steps; 1: as the allocator hands them out)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/g.npy and DIR/jac.npy (float64; rank 0's "
+                         "problems, a fixed seeded sample of whole problems when they exceed %d MB)" % (DUMP_BYTES // 10**6))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-scale-c5", action="store_true", help="skip the strong-scaling C5 leg of the default run")
     ap.add_argument("--no-values-c3", action="store_true", help="skip the values-only leg of the default run")
     ap.add_argument("--no-timings-c3", action="store_true",
                     help="skip the optimised-timings and the whole-default-list legs of the default run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -747,6 +785,8 @@ def main():
 
     # sanity: the outputs are finite (no work skipped / no garbage)
     assert bool(torch.isfinite(g).all()) and bool(torch.isfinite(jac).all())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, g, jac, batch.g_off, batch.jac_off)
 
     if rank == 0:
         callbacks = n_all * args.steps
