@@ -3,13 +3,18 @@
 // Built by `make -C oracle asan` with -fsanitize=address,undefined and run by tests/test_sanitizers.py: walks
 // robots x gait combos x constraint-set masks (incl. optimised timings and baseMotion) through
 //   twr::Structure::Build / InitialGuess / VariableBounds   (towr_amd/csrc/structure.cc)
+//   twr::ShareLayoutTables / PlanBatch (what twr_batch_create uploads; structure.cc)
 //   orc_create / orc_eval / orc_bounds / orc_sample_trajectory (oracle/towr_oracle.cc)
 // and cross-checks sizes and the CSR pattern of the two, so that every table write and every row of the
 // pattern builders executes under the sanitizers.
+#include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
+#include <memory>
 #include <vector>
 
 #include "../towr_amd/csrc/structure.h"
@@ -100,30 +105,39 @@ static void one_case(int robot, int terrain, int combo, double T, int sets, doub
   orc_destroy(P);
 }
 
-// twr::ShareLayoutTables (what twr_batch_create merges): T-siblings of a sweep at K = 200 share selector / polynomial-layout /
+// a structure as the sweeps of BASELINE build them: K time nodes of dynamic / range of motion
+static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 200,
+                            std::shared_ptr<const twr::TerrainGrid> grid = nullptr) {
+  twr::Structure S;
+  twr::ModelPreset(robot, terrain, &S.model);
+  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
+  twr_params& p = S.params;
+  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
+  p.duration_base_poly = 0.1;
+  p.polys_per_swing = 2;
+  p.polys_per_stance_force = 3;
+  p.constraint_sets = sets;
+  p.reserved_ = 0;
+  p.dt_base_motion = 0.025;
+  p.base_z_init = -S.model.nominal_stance[0][2];
+  S.grid = grid;
+  S.Build();
+  return S;
+}
+
+// the candidates of a sweep at K = 200 (hyq on the slope): T-siblings, swing-scale siblings and one other gait
+static std::vector<twr::Structure> sweep_structures() {
+  std::vector<twr::Structure> ss;
+  for (int i = 0; i < 11; ++i)
+    ss.push_back(build(2, 4, i == 10 ? 3 : 1, i < 8 ? 1.2 + 0.2 * i : 2.0, 27, i < 8 ? 0.80 : 0.80 + 0.016 * (i - 7)));
+  return ss;
+}
+
+// twr::ShareLayoutTables (what twr::PlanBatch merges): T-siblings of a sweep at K = 200 share selector / polynomial-layout /
 // tile tables, every reference points at bytes identical to the structure's own table, owners own themselves, and the
 // byte counts add up.
 static void sharing_case() {
-  twr_model m;
-  twr::ModelPreset(2, 4, &m);
-  std::vector<twr::Structure> ss(11);
-  for (int i = 0; i < 11; ++i) {
-    const double T = i < 8 ? 1.2 + 0.2 * i : 2.0;
-    const double scale = i < 8 ? 0.80 : 0.80 + 0.016 * (i - 7);
-    twr::GaitCombo(m.n_ee, i == 10 ? 3 : 1, T, scale, &ss[i].schedule);
-    twr_params p;
-    p.dt_dynamic = p.dt_rom = T / (200 - 1.5);
-    p.duration_base_poly = 0.1;
-    p.polys_per_swing = 2;
-    p.polys_per_stance_force = 3;
-    p.constraint_sets = 27;
-    p.reserved_ = 0;
-    p.dt_base_motion = 0.025;
-    p.base_z_init = -m.nominal_stance[0][2];
-    ss[i].model = m;
-    ss[i].params = p;
-    ss[i].Build();
-  }
+  const std::vector<twr::Structure> ss = sweep_structures();
   std::vector<const twr::Structure*> sp;
   for (const auto& s : ss) sp.push_back(&s);
   sp.push_back(&ss[3]);   // the same structure twice: shares everything with its first occurrence
@@ -168,9 +182,213 @@ static void policy_case() {
   CHECK(!twr::StreamNonTemporal(256, 256, 256 * per, twr::MemorySideCacheBytes("gfx950", 4 << 20)), "policy: MI355X as measured");
 }
 
+// a copy of list `a` with every non-zero address field (byte offsets `addr`) moved by `delta` must be `b`, byte for byte
+template <class W>
+static void check_moved(const char* what, const std::vector<W>& a, const std::vector<W>& b, std::initializer_list<size_t> addr,
+                        uint64_t delta) {
+  CHECK(a.size() == b.size(), "plan: %s has %zu vs %zu items", what, a.size(), b.size());
+  for (size_t i = 0; i < a.size() && i < b.size(); ++i) {
+    char want[sizeof(W)];
+    std::memcpy(want, &a[i], sizeof(W));
+    for (size_t off : addr) {
+      uint64_t v;
+      std::memcpy(&v, want + off, 8);
+      if (v) v += delta;
+      std::memcpy(want + off, &v, 8);
+    }
+    if (std::memcmp(want, &b[i], sizeof(W)) != 0) {
+      CHECK(false, "plan: %s[%zu] differs (blob delta %llu)", what, i, (unsigned long long)delta);
+      return;
+    }
+  }
+}
+
+
+// twr::PlanBatch (what twr_batch_create uploads besides the tables), on fake blob addresses: every row of dynamic,
+// rangeofmotion-* and the chunked node families is written by exactly one work item at the g / Jacobian offsets of the
+// CSR pattern, every list keeps each problem's items in order, the XCD order, whole flat groups of one problem, every
+// address inside the blob it belongs to, and a plan that depends on nothing but its inputs (twice the same bytes; moving
+// the blobs moves the addresses and nothing else).
+static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop) {
+  const int n_cu = 256, chunk = 32, P = (int)sop.size();
+  const std::vector<size_t> off = twr::BlobOffsets(sp);
+  std::vector<uint64_t> at(sp.size());
+  for (size_t i = 0; i < sp.size(); ++i) {
+    CHECK(off[i] % 256 == 0 && off[i + 1] >= off[i] + sp[i]->blob.size(), "%s: blob %zu placed at %zu", name, i, off[i]);
+    at[i] = 0x7f0000000000ull + off[i];
+  }
+  twr::BatchPlan B = twr::PlanBatch(sp, sop, at, n_cu, (int64_t)256 << 20, chunk);
+  const twr::BatchPlan::Lists& L = B.lists;
+  auto in_blob = [&](uint64_t a, int si) { return a >= at[si] && a < at[si] + sp[si]->blob.size(); };
+  auto in_any = [&](uint64_t a) {
+    for (size_t i = 0; i < sp.size(); ++i)
+      if (in_blob(a, (int)i)) return true;
+    return false;
+  };
+  auto problem_of = [&](int64_t g) { return (int)(std::upper_bound(B.g_off.begin(), B.g_off.end(), g) - B.g_off.begin()) - 1; };
+  CHECK((int)B.x_off.size() == P + 1 && (int)L.node.size() == P + 1 && L.node[P].blob == 0 && L.node[P].g_off == B.g_off[P] &&
+            L.node[P].j_off == B.j_off[P] && L.node[P].x_off == B.x_off[P], "%s: offsets / node end entry", name);
+  // rows written by the item lists: hits[p][row]
+  std::vector<std::vector<int>> hits(P);
+  for (int p = 0; p < P; ++p) {
+    const twr::Structure& S = *sp[sop[p]];
+    CHECK(B.x_off[p + 1] - B.x_off[p] == S.n_vars && B.g_off[p + 1] - B.g_off[p] == S.n_rows && B.j_off[p + 1] - B.j_off[p] == S.nnz,
+          "%s: offsets of problem %d", name, p);
+    CHECK(L.node[p].blob == at[sop[p]] && B.blob_of_problem[p] == at[sop[p]] && L.node[p].g_off == B.g_off[p], "%s: node item %d", name, p);
+    hits[p].assign(S.n_rows, 0);
+  }
+  int bad = 0;
+  auto rows = [&](const char* what, int64_t x_off, int64_t g_off, int64_t j_off, int n_rows, uint64_t own_addr) {
+    const int p = problem_of(g_off);
+    if (p < 0 || p >= P) {
+      CHECK(false, "%s: %s item outside every problem", name, what);
+      return;
+    }
+    const twr::Structure& S = *sp[sop[p]];
+    const int r0 = (int)(g_off - B.g_off[p]);
+    const bool ok = x_off == B.x_off[p] && r0 + n_rows <= S.n_rows && j_off - B.j_off[p] == S.row_ptr[r0] &&
+                    (!own_addr || in_blob(own_addr, sop[p]));
+    if (!ok && bad++ < 5) CHECK(false, "%s: %s item of problem %d at row %d", name, what, p, r0);
+    for (int r = r0; r < std::min(r0 + n_rows, S.n_rows); ++r) hits[p][r]++;
+  };
+  for (const auto& w : L.dyn) {
+    rows("dyn", w.x_off, w.g_off, w.j_off, 6 * w.cnt, w.nodes_t);
+    for (uint64_t a : {w.nodes_l, w.sel, w.tile, w.poly_l, w.map, w.hdr}) CHECK(in_any(a), "%s: dyn layout address", name);
+    CHECK(in_blob(w.poly_t, sop[problem_of(w.g_off)]), "%s: dyn poly_t", name);
+  }
+  for (const auto& w : L.rom) {
+    rows("rom", w.x_off, w.g_off, w.j_off, 3 * w.cnt, w.nodes);
+    CHECK(in_blob(w.segs, sop[problem_of(w.g_off)]), "%s: rom segs", name);
+  }
+  for (const auto& w : L.pdyn) {
+    rows("pdyn", w.x_off, w.g_off, w.j_off, 6 * w.cnt, w.shared);
+    for (uint64_t a : {w.hdr, w.mput, w.fput, w.ee}) CHECK(in_blob(a, sop[problem_of(w.g_off)]), "%s: pdyn address", name);
+    CHECK(w.loc < B.records_bytes, "%s: pdyn scratch", name);
+  }
+  for (const auto& w : L.prom) {
+    rows("prom", w.x_off, w.g_off, w.j_off, 3 * w.cnt, 0);
+    CHECK(w.recs + sizeof(twr::RomRec) * w.cnt <= B.records_bytes, "%s: prom scratch", name);
+  }
+  for (const auto& w : L.ploc) {
+    CHECK(in_any(w.blob) && w.recs <= B.records_bytes && w.dyn_loc <= B.records_bytes && (w.recs || w.dyn_loc), "%s: ploc item", name);
+  }
+  const int fam_rows[4] = {1, 5, 1, 4};
+  for (int f = 0; f < 4; ++f)
+    for (const auto& w : L.fam[f]) {
+      rows("fam", w.x_off, w.g_off, w.j_off, fam_rows[f] * w.cnt, w.table);
+      CHECK(w.blob == B.blob_of_problem[problem_of(w.g_off)] && w.cnt <= (f == 1 ? chunk : 64), "%s: fam %d item", name, f);
+    }
+  // exactly once: every row of dynamic / rangeofmotion-*, and the node families when there are chunk lists
+  bool chunked = false;
+  for (int f = 0; f < 4; ++f) chunked = chunked || !L.fam[f].empty();
+  for (int p = 0; p < P; ++p) {
+    const twr::Structure& S = *sp[sop[p]];
+    const twr::DevStruct* H = reinterpret_cast<const twr::DevStruct*>(S.blob.data());
+    std::vector<std::pair<int, int>> want;   // [first, end) row ranges
+    for (const twr::SetInfo& cs : S.con_sets)
+      if (cs.name == "dynamic" || cs.name.rfind("rangeofmotion-", 0) == 0) want.push_back({cs.offset, cs.offset + cs.size});
+    if (chunked) {
+      want.push_back({H->row_terrain, H->row_terrain + H->n_terrain_rows});
+      want.push_back({H->row_force, H->row_force + 5 * H->n_force_nodes});
+      want.push_back({H->row_acc, H->row_acc + 6 * H->n_junctions});
+      want.push_back({H->row_swing, H->row_swing + 4 * H->n_swing_nodes});
+    }
+    std::vector<char> covered(S.n_rows, 0);
+    for (const auto& w : want)
+      for (int r = w.first; r < w.second; ++r) covered[r] = 1;
+    for (int r = 0; r < S.n_rows; ++r)
+      if (hits[p][r] != covered[r] && bad++ < 5) CHECK(false, "%s: problem %d row %d written %d times", name, p, r, hits[p][r]);
+  }
+  // each problem's items in their order (rows ascending); equal item counts: position j holds a problem = j mod 8
+  auto order = [&](const char* what, const std::vector<int64_t>& g) {
+    std::vector<int64_t> last(P, -1);
+    std::vector<int> count(P, 0);
+    for (int64_t x : g) {
+      const int p = problem_of(x);
+      CHECK(x > last[p], "%s: %s items of problem %d out of order", name, what, p);
+      last[p] = x;
+      count[p]++;
+    }
+    if (std::count(count.begin(), count.end(), count[0]) == P)
+      for (size_t j = 0; j < (size_t)(P / 8 * 8) * count[0]; ++j)
+        CHECK(problem_of(g[j]) % 8 == (int)(j % 8), "%s: %s position %zu on the wrong XCD", name, what, j);
+  };
+  std::vector<int64_t> gd, gr, gp;
+  for (const auto& w : L.dyn) gd.push_back(w.g_off);
+  for (const auto& w : L.rom) gr.push_back(w.g_off);
+  for (const auto& w : L.pdyn) gp.push_back(w.g_off);
+  order("dyn", gd);
+  order("rom", gr);
+  order("pdyn", gp);
+  // flat: whole groups of four of one problem each, nothing when a problem has optimised timings
+  bool timings = false;
+  for (int si : sop) timings = timings || sp[si]->timings;
+  CHECK(L.flat.size() % 4 == 0 && (!timings || L.flat.empty()), "%s: flat list of %zu items", name, L.flat.size());
+  for (size_t i = 0; i < L.flat.size(); ++i) {
+    const auto& w = L.flat[i];
+    CHECK(w.x_off == L.flat[i & ~(size_t)3].x_off && w.n_x == L.flat[i & ~(size_t)3].n_x, "%s: flat group %zu of two problems", name, i / 4);
+    if (w.cnt) CHECK(in_any(w.nodes) && in_any(w.polys), "%s: flat addresses", name);
+  }
+  // the same inputs plan the same bytes; moved blobs move every address and nothing else; the scratch placed
+  const uint64_t delta = 0x12345600;
+  std::vector<uint64_t> moved(at);
+  for (auto& a : moved) a += delta;
+  for (uint64_t d : {(uint64_t)0, delta}) {
+    const twr::BatchPlan C = twr::PlanBatch(sp, sop, d ? moved : at, n_cu, (int64_t)256 << 20, chunk);
+    const twr::BatchPlan::Lists& M = C.lists;
+    check_moved("dyn", L.dyn, M.dyn, {offsetof(twr::DynWork, nodes_t), offsetof(twr::DynWork, nodes_l), offsetof(twr::DynWork, sel),
+                                      offsetof(twr::DynWork, tile), offsetof(twr::DynWork, poly_t), offsetof(twr::DynWork, poly_l),
+                                      offsetof(twr::DynWork, map), offsetof(twr::DynWork, hdr)}, d);
+    check_moved("rom", L.rom, M.rom, {offsetof(twr::RomWork, nodes), offsetof(twr::RomWork, segs)}, d);
+    check_moved("node", L.node, M.node, {offsetof(twr::NodeWork, blob)}, d);
+    check_moved("flat", L.flat, M.flat, {offsetof(twr::FlatWork, nodes), offsetof(twr::FlatWork, polys)}, d);
+    for (int f = 0; f < 4; ++f) check_moved("fam", L.fam[f], M.fam[f], {offsetof(twr::FamWork, blob), offsetof(twr::FamWork, table)}, d);
+    check_moved("pdyn", L.pdyn, M.pdyn, {offsetof(twr::PDynWork, hdr), offsetof(twr::PDynWork, shared), offsetof(twr::PDynWork, mput),
+                                         offsetof(twr::PDynWork, fput), offsetof(twr::PDynWork, ee)}, d);
+    check_moved("ploc", L.ploc, M.ploc, {offsetof(twr::LocWork, blob)}, d);
+    check_moved("prom", L.prom, M.prom, {}, d);
+    check_moved("blob_of_problem", B.blob_of_problem, C.blob_of_problem, {0}, d);
+    CHECK(C.x_off == B.x_off && C.j_off == B.j_off && C.t_total == B.t_total && C.sample_ok == B.sample_ok &&
+              C.records_bytes == B.records_bytes && C.stream_nt == B.stream_nt && C.dyn_map_chunks == B.dyn_map_chunks &&
+              C.node_families == B.node_families && C.rom_max_vals == B.rom_max_vals && C.flat_max_x == B.flat_max_x &&
+              C.pdyn_img_cap == B.pdyn_img_cap && C.prom_img_cap == B.prom_img_cap && C.dyn_layout_bytes == B.dyn_layout_bytes,
+          "%s: plan scalars differ", name);
+  }
+  const uint64_t base = 0x7e0000000000ull;
+  B.PlaceRecords(base);
+  for (const auto& w : L.ploc)
+    CHECK((!w.recs || (w.recs >= base && w.recs < base + B.records_bytes)) && (!w.dyn_loc || (w.dyn_loc >= base && w.dyn_loc < base + B.records_bytes)),
+          "%s: placed LocWork", name);
+  for (const auto& w : L.prom) CHECK(w.recs >= base && w.recs < base + B.records_bytes, "%s: placed RomPhaseWork", name);
+  for (const auto& w : L.pdyn) CHECK(w.loc >= base && w.loc < base + B.records_bytes, "%s: placed PDynWork", name);
+  std::printf("plan %-9s %5d problems: dyn %zu rom %zu flat %zu fam %zu/%zu/%zu/%zu pdyn %zu ploc %zu prom %zu\n", name, P, L.dyn.size(),
+              L.rom.size(), L.flat.size(), L.fam[0].size(), L.fam[1].size(), L.fam[2].size(), L.fam[3].size(), L.pdyn.size(),
+              L.ploc.size(), L.prom.size());
+}
+
+static void plan_cases() {
+  const twr::Structure c3 = build(3, 0, 1, 2.0, 63), c3_timings = build(3, 0, 1, 2.0, 127), c3_hot = build(3, 0, 1, 2.0, 27);
+  plan_case("C3x2048", {&c3}, std::vector<int32_t>(2048, 0));   // 8 problems per CU: chunk lists
+  plan_case("C3x200", {&c3}, std::vector<int32_t>(200, 0));
+  plan_case("single", {&c3_hot}, {0});
+  std::vector<twr::Structure> ss = sweep_structures();
+  std::vector<const twr::Structure*> sp;
+  for (const auto& s : ss) sp.push_back(&s);
+  plan_case("ragged", sp, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 3, 5, 5, 0});
+  const twr::Structure gap_timings = build(3, 3, 2, 1.8, 127, 0.9), stairs_all = build(3, 2, 0, 2.4, 255, 1.1);
+  plan_case("mixed", {&c3, &gap_timings, &stairs_all, &c3_timings, &c3_hot}, {0, 1, 2, 1, 3, 2, 2, 1, 0, 1, 4, 4, 1, 2, 2, 3, 1, 0, 2, 1, 4});
+  auto grid = std::make_shared<twr::TerrainGrid>();
+  grid->rows = 40;
+  grid->cols = 60;
+  for (int i = 0; i < grid->rows * grid->cols; ++i) grid->heights.push_back(0.05 * ((i * 7919) % 13) / 13.0);
+  const twr::Structure g1 = build(3, 7, 1, 2.0, 63, 1.0, 200, grid), g2 = build(3, 7, 0, 2.4, 27, 1.0, 120, grid);
+  plan_case("grid", {&g1, &g2}, {0, 1, 1, 0, 0, 1, 0});
+}
+
 int main() {
   sharing_case();
   policy_case();
+  plan_cases();
   int cases = 0;
   const int masks[] = {27, 63, 127, 255, 2, 8 | 64, 1 | 16};
   for (int robot = 0; robot < 5; ++robot) {

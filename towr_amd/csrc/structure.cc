@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <limits>
 #include <map>
@@ -1519,14 +1520,15 @@ void Structure::InitialGuess(const double* lin0, const double* ang0, const doubl
 
 // ------------------------------------------------------------------ trajectory sampling
 // fpowr::GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53): `while (t <= T + 1e-5) { ...; t += dt; }`
-int Structure::SampleCount(double dt) const {
+int SampleCount(double t_total, double dt) {
   if (!(dt > 0)) throw std::runtime_error("dt must be positive");
-  const double Tt = std::accumulate(base.durations.begin(), base.durations.end(), 0.0);
   int n = 0;
-  for (double t = 0.0; t <= Tt + 1e-5; t += dt) {
+  for (double t = 0.0; t <= t_total + 1e-5; t += dt)
     if (++n > 10000000) throw std::runtime_error("too many samples");
-  }
   return n;
+}
+int Structure::SampleCount(double dt) const {
+  return twr::SampleCount(std::accumulate(base.durations.begin(), base.durations.end(), 0.0), dt);
 }
 
 // ------------------------------------------------------------------ variable bounds
@@ -1780,6 +1782,349 @@ LayoutShare ShareLayoutTables(const std::vector<const Structure*>& structs) {
     }
   }
   return out;
+}
+
+
+std::vector<size_t> BlobOffsets(const std::vector<const Structure*>& structs) {
+  std::vector<size_t> off(structs.size() + 1, 0);
+  for (size_t i = 0; i < structs.size(); ++i) off[i + 1] = off[i] + (structs[i]->blob.size() + 255) / 256 * 256;
+  return off;
+}
+
+namespace {
+// XCD-aware order.  Workgroups are dealt round-robin over the 8 XCDs and the persistent grids are multiples of 8, so list
+// position j runs on XCD j % 8 (eval_fused_kernel's slice mapping relies on it, kernels.hip).  Interleaving the problems in
+// groups of 8 puts all items of one problem on ONE XCD (same L2): its x is fetched from HBM once per kernel instead of once
+// per XCD.  (Speed only; ragged item counts merely loosen the alignment.)  first: first item of every problem (+ end).
+template <class W>
+void Interleave(std::vector<W>& items, const std::vector<int>& first) {
+  const std::vector<W> src = items;
+  const int n = (int)first.size() - 1;
+  size_t out = 0;
+  for (int p0 = 0; p0 < n; p0 += 8) {
+    const int np = std::min(8, n - p0);
+    for (int s = 0;; ++s) {
+      bool any = false;
+      for (int k = 0; k < np; ++k)
+        if (first[p0 + k] + s < first[p0 + k + 1]) {
+          items[out++] = src[first[p0 + k] + s];
+          any = true;
+        }
+      if (!any) break;
+    }
+  }
+}
+}  // namespace
+
+void BatchPlan::PlaceRecords(uint64_t base) {
+  for (auto& lw : lists.ploc) {
+    if (lw.recs) lw.recs += base - 1;
+    if (lw.dyn_loc) lw.dyn_loc += base - 1;
+  }
+  for (auto& rw : lists.prom) rw.recs += base;
+  for (auto& pw : lists.pdyn) pw.loc += base;
+}
+
+BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem,
+                    const std::vector<uint64_t>& blob_at, int n_cu, int64_t cache_bytes, int force_chunk) {
+  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
+  BatchPlan b;
+  BatchPlan::Lists& L = b.lists;
+  // Layout tables of dyn_kernel (device_tables.h) are stored once per distinct CONTENT: a structure whose table is
+  // byte-identical to one of an earlier structure of the batch reads that one (its own copy stays in the arena, unread).
+  // Candidates of a sweep that differ in the total time only share all of them, and an evaluation then reads 24 B per
+  // time node + 16 B per polynomial of such a candidate instead of ~35 KB.  The model constants (DevStruct header) are
+  // taken from the first structure of the batch that has the same ones.
+  std::vector<std::unordered_map<uint32_t, uint64_t>> layout_at(n_structs);   // [structure][blob offset of the table] -> device address
+  std::vector<uint64_t> model_hdr(n_structs);
+  const LayoutShare share = ShareLayoutTables(structs);
+  b.dyn_layout_bytes = share.bytes_built;
+  b.dyn_layout_distinct_bytes = share.bytes_distinct;
+  for (int i = 0; i < n_structs; ++i) {
+    const auto& tabs = structs[i]->dyn_layout_tables;
+    for (size_t t = 0; t < tabs.size(); ++t) layout_at[i][tabs[t].off] = blob_at[share.of[i][t].owner] + share.of[i][t].off;
+    const DevStruct* H = reinterpret_cast<const DevStruct*>(structs[i]->blob.data());
+    model_hdr[i] = blob_at[i];
+    for (int q = 0; q < i; ++q) {
+      const DevStruct* Q = reinterpret_cast<const DevStruct*>(structs[q]->blob.data());
+      if (model_hdr[q] == blob_at[q] && Q->mass == H->mass && Q->gravity == H->gravity && std::memcmp(Q->Ib, H->Ib, sizeof(H->Ib)) == 0) {
+        model_hdr[i] = model_hdr[q];
+        break;
+      }
+    }
+    if (structs[i]->dyn_staged_max > 128) b.dyn_map_chunks = 4;
+  }
+  b.x_off.assign(n_problems + 1, 0);
+  b.g_off.assign(n_problems + 1, 0);
+  b.j_off.assign(n_problems + 1, 0);
+  std::vector<int> flat_group_p;             // the problem of every group of four flat items
+  bool flat_ok = true;
+  std::vector<int> dyn_first, rom_first, pdyn_first;   // first work item of every problem (+ end; pdyn: optimised timings only)
+  // (families that are switched off -- twr_params.constraint_sets -- simply have no work items; problems with
+  // optimised timings get PDynWork / LocWork / RomPhaseWork items instead of DynWork / RomWork)
+  for (int p = 0; p < n_problems; ++p) {
+    const int si = struct_of_problem[p];
+    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
+    const Structure& S = *structs[si];
+    const DevStruct* H = reinterpret_cast<const DevStruct*>(S.blob.data());
+    const uint64_t blob = blob_at[si];
+    const SampleTables* st = reinterpret_cast<const SampleTables*>(S.blob.data() + H->o_sample);
+    b.blob_of_problem.push_back(blob);
+    b.t_total.push_back(st->t_total);
+    b.sample_ok.push_back(st->n_base >= 0);
+    b.x_off[p + 1] = b.x_off[p] + S.n_vars;
+    b.g_off[p + 1] = b.g_off[p] + S.n_rows;
+    b.j_off[p + 1] = b.j_off[p] + S.nnz;
+    dyn_first.push_back((int)L.dyn.size());
+    rom_first.push_back((int)L.rom.size());
+    const SetInfo* dsp = S.FindSet("dynamic");
+    const SetInfo ds = dsp ? *dsp : SetInfo();
+    for (const auto& sl : S.dyn_slices) {   // fixed timings only (empty otherwise)
+      DynWork w;
+      std::memset(&w, 0, sizeof(w));
+      const auto& lay = layout_at[si];
+      w.nodes_t = blob + S.off_dyn_nodes_t + sizeof(DynNodeT) * (size_t)sl.k0;
+      w.nodes_l = lay.at(S.off_dyn_nodes_l) + sizeof(DynNodeL) * (size_t)sl.k0;
+      w.sel = lay.at(S.off_dyn_sel) + sizeof(DynSel) * (size_t)sl.k0 * 4;
+      w.tile = lay.at(S.off_dyn_tile);   // (records are addressed through DynSel::tile)
+      w.poly_t = blob + S.off_dyn_poly_t + sizeof(DynPolyT) * (size_t)sl.poly0;
+      w.poly_l = lay.at(S.off_dyn_poly_l) + sizeof(DynPolyL) * (size_t)sl.poly0;
+      w.map = lay.at(b.dyn_map_chunks == 2 ? sl.map2 : sl.map);
+      w.hdr = model_hdr[si];
+      w.x_off = b.x_off[p];
+      w.g_off = b.g_off[p] + ds.offset + 6 * sl.k0;
+      w.j_off = b.j_off[p] + S.row_ptr[ds.offset + 6 * sl.k0];
+      w.cnt = sl.cnt;
+      w.nvals = sl.nvals;
+      L.dyn.push_back(w);
+    }
+    for (int e = 0; e < (int)S.rom_slices.size(); ++e) {   // fixed timings only (empty otherwise)
+      if (S.rom_slices[e].empty()) continue;
+      const SetInfo& rs = *S.FindSet("rangeofmotion-" + std::to_string(e));
+      for (const auto& sl : S.rom_slices[e]) {
+        RomWork w;
+        std::memset(&w, 0, sizeof(w));
+        w.nodes = blob + S.off_rom_nodes + sizeof(RomNode) * (size_t)sl.k0;
+        w.segs = blob + sl.segs;
+        w.x_off = b.x_off[p];
+        w.g_off = b.g_off[p] + rs.offset + 3 * sl.k0;
+        w.j_off = b.j_off[p] + S.row_ptr[rs.offset + 3 * sl.k0];
+        w.off_lin = S.off_base_lin;
+        w.off_ang = S.off_base_ang;
+        w.cnt = sl.cnt;
+        w.nvals = sl.nvals;
+        w.ee = e;
+        b.rom_max_vals = std::max(b.rom_max_vals, w.nvals);
+        L.rom.push_back(w);
+      }
+    }
+    if (S.timings) {
+      const int Kd = (int)S.grid_dyn.size();
+      const size_t loc_off = b.records_bytes;   // DynLoc[4 * Kd] of this problem, then its RomRec arrays
+      const PhaseTables& pt = S.phase_tables;
+      if (dsp) {
+        // dyn_phase_kernel: a pass = the time nodes whose expanded rows fit the LDS image (four at sixteen lanes each,
+        // fewer when a node has more than 5120 values: the image then takes the whole 160 KB of a CU)
+        b.records_bytes += sizeof(DynLoc) * 4 * (size_t)Kd;
+        const int nv = pt.node_vals;
+        const int run = std::max(1, std::min(4, (160 * 128) / nv));
+        b.pdyn_img_cap = std::max(b.pdyn_img_cap, run * nv);
+        pdyn_first.push_back((int)L.pdyn.size());
+        for (int k0 = 0; k0 < Kd; k0 += run) {
+          PDynWork pw;
+          std::memset(&pw, 0, sizeof(pw));
+          pw.hdr = blob;
+          pw.loc = loc_off + sizeof(DynLoc) * (size_t)k0;
+          pw.loc_stride = (int32_t)(sizeof(DynLoc) * (size_t)Kd);
+          pw.shared = blob + pt.o_dyn_shared + sizeof(DynShared) * (size_t)k0;
+          pw.mput = blob + pt.o_mput;
+          pw.fput = blob + pt.o_fput;
+          pw.ee = blob + H->o_phase + offsetof(PhaseTables, ee);
+          pw.x_off = b.x_off[p];
+          pw.g_off = b.g_off[p] + dsp->offset + 6 * k0;
+          pw.j_off = b.j_off[p] + dsp->nnz_offset + (int64_t)k0 * nv;
+          pw.cnt = std::min(run, Kd - k0);
+          pw.node_vals = nv;
+          pw.off_lin = S.off_base_lin;
+          pw.off_ang = S.off_base_ang;
+          pw.n_ee = S.n_ee;
+          pw.n_mput = pt.n_mput;
+          pw.n_fput = pt.n_fput;
+          for (int q = 0; q < 5; ++q) pw.row_off[q] = pt.dyn_row_off[q];
+          L.pdyn.push_back(pw);
+        }
+      }
+      for (int e = 0; e < S.n_ee; ++e) {
+        const SetInfo* rs = S.FindSet("rangeofmotion-" + std::to_string(e));
+        if (!rs && !dsp) continue;
+        LocWork lw;
+        std::memset(&lw, 0, sizeof(lw));
+        lw.blob = blob;
+        lw.recs = rs ? b.records_bytes + 1 : 0;   // (+1: see BatchPlan::records_bytes)
+        lw.dyn_loc = dsp ? loc_off + sizeof(DynLoc) * (size_t)Kd * (size_t)e + 1 : 0;
+        lw.x_off = b.x_off[p];
+        lw.ee = e;
+        L.ploc.push_back(lw);
+        if (!rs) continue;
+        const int K = (int)S.grid_rom.size(), nv = pt.rom_node_vals[e];
+        const int run_max = std::max(1, std::min(16, (160 * 128) / nv));   // time nodes per pass (four lanes each)
+        const int n_pass = (K + run_max - 1) / run_max;
+        const int run = (K + n_pass - 1) / n_pass;                  // balanced: no short tail pass (it pays the full copy-out)
+        b.prom_img_cap = std::max(b.prom_img_cap, run * nv);
+        for (int k0 = 0; k0 < K; k0 += run) {
+          RomPhaseWork rw;
+          rw.recs = b.records_bytes + sizeof(RomRec) * (size_t)k0;
+          rw.x_off = b.x_off[p];
+          rw.g_off = b.g_off[p] + rs->offset + 3 * k0;
+          rw.j_off = b.j_off[p] + rs->nnz_offset + (int64_t)k0 * nv;
+          rw.off_lin = S.off_base_lin;
+          rw.off_ang = S.off_base_ang;
+          rw.cnt = std::min(run, K - k0);
+          rw.msize = pt.msize[e];
+          rw.ns = S.schedule.n_phases[e] - 1;
+          rw.node_vals = nv;
+          L.prom.push_back(rw);
+        }
+        b.records_bytes += sizeof(RomRec) * (size_t)K;
+      }
+    }
+    // values-only work items (device_tables.h FlatWork): 64 time nodes of the dynamic / range-of-motion grid each
+    if (S.timings) flat_ok = false;
+    if (S.off_flat_polys) {
+      auto items = [&](uint32_t off_nodes, const std::vector<Structure::FlatItem>& list, bool dynamic) {
+        for (const auto& it : list) {
+          FlatWork fw;
+          std::memset(&fw, 0, sizeof(fw));
+          fw.nodes = blob + off_nodes + sizeof(FlatNode) * (size_t)it.k0;
+          fw.polys = blob + S.off_flat_polys;
+          fw.x_off = b.x_off[p];
+          fw.g_off = b.g_off[p];
+          fw.k0 = it.k0;
+          fw.cnt = it.cnt;
+          fw.start[0] = it.start[0];
+          fw.start[1] = it.start[1];
+          fw.count = it.count;
+          fw.n_x = S.n_vars;
+          fw.n_ee = S.n_ee;
+          fw.off_lin = S.off_base_lin;
+          fw.off_ang = S.off_base_ang;
+          for (int e = 0; e < kMaxEE; ++e) fw.row_rom[e] = S.flat_row_rom[e];
+          fw.dynamic = dynamic ? 1 : 0;
+          fw.gather = it.gather ? 1 : 0;
+          if (dynamic) {
+            fw.row_dyn = S.flat_row_dyn;
+            fw.with_rom = S.flat_with_rom ? 1 : 0;
+            fw.mass = H->mass;
+            fw.gravity = H->gravity;
+            for (int i = 0; i < 6; ++i) fw.Ib[i] = H->Ib[i];
+          }
+          L.flat.push_back(fw);
+        }
+      };
+      b.flat_max_x = std::max(b.flat_max_x, S.n_vars);
+      items(S.off_flat_dyn, S.flat_items_dyn, true);
+      items(S.off_flat_rom, S.flat_items_rom, false);
+      while (L.flat.size() % 4 != 0) {   // whole groups: empty items that still carry the problem's x (the group copies it
+        FlatWork fw;                     // to LDS with all its threads)
+        std::memset(&fw, 0, sizeof(fw));
+        fw.x_off = b.x_off[p];
+        fw.n_x = S.n_vars;
+        L.flat.push_back(fw);
+      }
+      flat_group_p.resize(L.flat.size() / 4, p);
+    } else if (S.FindSet("rangeofmotion-0") || dsp) {
+      flat_ok = false;
+    }
+    NodeWork nw;
+    nw.blob = blob;
+    nw.x_off = b.x_off[p];
+    nw.g_off = b.g_off[p];
+    nw.j_off = b.j_off[p];
+    L.node.push_back(nw);
+  }
+  // one entry past the end carries the totals: a kernel reads a problem's row count as work[p + 1].g_off - work[p].g_off
+  // from the work list alone (score_kernel requests g before the structure's header has arrived)
+  L.node.push_back(NodeWork{0, b.x_off[n_problems], b.g_off[n_problems], b.j_off[n_problems]});
+  dyn_first.push_back((int)L.dyn.size());
+  rom_first.push_back((int)L.rom.size());
+  pdyn_first.push_back((int)L.pdyn.size());
+  Interleave(L.dyn, dyn_first);
+  Interleave(L.rom, rom_first);
+  Interleave(L.pdyn, pdyn_first);
+  // Store policy of the copy-out (kernels.hip copy_out_fixed): non-temporal when the batch is SWEEP-LIKE -- fewer than four
+  // problems per structure on average, so every evaluation re-reads tables (and x) that only that problem uses -- AND one
+  // evaluation writes more than the device's memory-side cache holds (256 MB on an MI355X; by architecture name, structure.h), so that plain stores would flush those
+  // tables out of it between two evaluations.  Measured (one box, no per-kernel events): the C5 sweep at 512 /
+  // 1024 candidates 116-118 / 223-224 -> 99 / 209-211 us per step; at 256 candidates (220 MB of output, absorbed by the
+  // Infinity Cache as it is) 52 -> 55 us, and 8192 problems of ONE structure lose 15 % in rom_kernel -- hence the two conditions.
+  std::vector<char> used(n_structs, 0);
+  int n_used = 0;
+  for (int si : struct_of_problem)
+    if (!used[si]) {
+      used[si] = 1;
+      ++n_used;
+    }
+  b.stream_nt = StreamNonTemporal(n_used, n_problems, 8 * (b.g_off[n_problems] + b.j_off[n_problems]), cache_bytes);
+  b.node_families = 2;
+  for (const Structure* S : structs)
+    if (S->params.constraint_sets & ~(TWR_SET_TERRAIN | TWR_SET_DYNAMIC | TWR_SET_ROM | TWR_SET_FORCE)) b.node_families = 4;
+  if (!flat_ok) {
+    L.flat.clear();
+  } else {
+    // One problem, one XCD: workgroup r of the launch runs on XCD r modulo 8 and takes group r.  The groups of problem p go to
+    // workgroups = p modulo 8: its x comes from HBM once and from that XCD's L2 for its other groups.
+    std::vector<size_t> queue[8];   // queue c: the groups that go to the list positions = c modulo 8
+    for (size_t i = 0; i < flat_group_p.size(); ++i) queue[flat_group_p[i] % 8].push_back(i);
+    std::vector<FlatWork> out;
+    out.reserve(L.flat.size());
+    auto emit = [&](size_t group) { out.insert(out.end(), L.flat.begin() + 4 * group, L.flat.begin() + 4 * group + 4); };
+    size_t depth = 0, k = 0;
+    for (const auto& q : queue) depth = std::max(depth, q.size());
+    for (; k < depth; ++k) {   // whole rounds of eight; a round in which a queue has run dry ends the interleaving
+      bool whole = true;
+      for (const auto& q : queue) whole = whole && k < q.size();
+      if (!whole) break;
+      for (const auto& q : queue) emit(q[k]);
+    }
+    for (const auto& q : queue)
+      for (size_t i = k; i < q.size(); ++i) emit(q[i]);
+    L.flat.swap(out);
+  }
+  // Large batches whose node-based sets are terrain / force / splineacc / swing only: per-family chunk lists for the
+  // persistent node_chunk_kernel (baseMotion and totalduration rows, and small batches -- where the fused launch or the
+  // one-workgroup-per-problem kernel is as good -- stay with node_kernel).
+  // (hot-path batches -- terrain and force rows only -- are faster on node_kernel2: 0.041 vs 0.047 ms per 8192 C3 problems)
+  // (from eight problems per CU on -- 2048 on the 256 CUs of an MI355X, where the cut-over was measured: below that the
+  // one-workgroup-per-problem kernel has enough waves in flight and no persistent loop to fill)
+  bool eligible = n_problems >= 8 * n_cu && b.node_families == 4;
+  for (const Structure* S : structs)
+    if (S->params.constraint_sets & (TWR_SET_BASE_ROM | TWR_SET_TOTAL_TIME)) eligible = false;
+  for (int p = 0; p < n_problems && eligible; ++p) {
+    const DevStruct* H = reinterpret_cast<const DevStruct*>(structs[struct_of_problem[p]]->blob.data());
+    auto add = [&](int f, int count, uint32_t table_off, size_t rec_bytes, int row0, int rows_per, int nnz0, int vals_per) {
+      const int chunk = f == 1 ? force_chunk : 64;
+      for (int i0 = 0; i0 < count; i0 += chunk) {
+        FamWork w;
+        std::memset(&w, 0, sizeof(w));
+        w.blob = b.blob_of_problem[p];
+        w.table = w.blob + table_off + (f == 2 ? 0 : rec_bytes * (size_t)i0);
+        w.x_off = b.x_off[p];
+        w.g_off = b.g_off[p] + row0 + (int64_t)rows_per * i0;
+        w.j_off = b.j_off[p] + nnz0 + (int64_t)vals_per * i0;
+        w.cnt = std::min(chunk, count - i0);
+        w.i0 = f == 2 ? i0 : 0;
+        w.aux0 = 3 * H->n_junctions;
+        w.aux1 = H->off_base_ang;
+        w.inv_t_swing = H->inv_t_swing;
+        L.fam[f].push_back(w);
+      }
+    };
+    add(0, H->n_terrain_rows, H->o_terrain_rows, sizeof(TerrainRow), H->row_terrain, 1, H->nnz_terrain, 3);
+    add(1, H->n_force_nodes, H->o_force_nodes, sizeof(ForceNode), H->row_force, 5, H->nnz_force, 25);
+    add(2, 6 * H->n_junctions, H->o_acc, sizeof(AccJunction), H->row_acc, 1, H->nnz_acc, 6);
+    add(3, H->n_swing_nodes, H->o_swing_nodes, sizeof(SwingNode), H->row_swing, 4, H->nnz_swing, 12);
+  }
+  return b;
 }
 
 }  // namespace twr

@@ -100,7 +100,7 @@ struct Structure {
   std::vector<std::vector<RomSlice>> rom_slices;   // [ee]
   uint32_t off_rom_nodes = 0;
   // values-only evaluation of dynamic / rangeofmotion-*, one lane per time node (device_tables.h FlatNode / FlatPoly /
-  // FlatWork): blob offsets (0 = none) and the items of a problem of this structure (twr_batch_create adds the problem's
+  // FlatWork): blob offsets (0 = none) and the items of a problem of this structure (PlanBatch adds the problem's
   // addresses)
   struct FlatItem {
     int k0 = 0, cnt = 0;                 // time nodes [k0, k0 + cnt) of the grid
@@ -117,7 +117,7 @@ struct Structure {
   void BuildSizes();       // variables, time tables and CSR pattern only (n_vars / n_rows / nnz): no device tables
   void InitialGuess(const double* lin0, const double* ang0, const double* lin1, const double* ang1,
                     const double* ee0, double* x) const;
-  int SampleCount(double dt) const;  // fpowr GetTrajectory: samples while t <= T + 1e-5, t accumulated
+  int SampleCount(double dt) const;  // twr::SampleCount of the base spline's total time
   void VariableBounds(const double* init_base, const double* final_base, const double* ee0, double* lower,
                       double* upper) const;
 
@@ -131,7 +131,7 @@ struct Structure {
 // gait tables
 // Layout tables of dyn_kernel stored once per distinct CONTENT (device_tables.h): for every structure and every entry of its
 // dyn_layout_tables, which structure's copy a batch reads -- the first one of the list with the same bytes (itself if none).
-// Host logic only (no device): twr_batch_create turns {owner, offset} into device addresses.
+// Host logic only (no device): PlanBatch turns {owner, offset} into device addresses.
 struct LayoutShare {
   struct Ref {
     int owner;          // index into the structure list
@@ -160,6 +160,44 @@ inline bool StreamNonTemporal(int structures_used, int n_problems, int64_t outpu
                               int64_t memory_side_cache_bytes = kInfinityCacheBytes) {
   return (int64_t)structures_used * 4 > n_problems && output_bytes_per_evaluation > memory_side_cache_bytes;
 }
+// Everything twr_batch_create uploads besides the structures' tables, planned on the host (no HIP): the offsets of every
+// problem, every work list in launch order and the batch's policy decisions.  blob[i] is the device address of structure i's
+// blob (BlobOffsets: one arena, every blob on a 256-byte line); the device enters as its CU count, its memory-side cache and
+// the chunk length of node_chunk_kernel's force family (kernels.hip kForceChunk).
+struct BatchPlan {
+  std::vector<int64_t> x_off, g_off, j_off;   // n_problems + 1
+  // what twr_batch_sample needs of every problem (the structures need not outlive the batch)
+  std::vector<uint64_t> blob_of_problem;      // device blob address
+  std::vector<double> t_total;                // Spline::GetTotalTime of base-lin
+  std::vector<char> sample_ok;                // polynomial counts fit the sampling kernel's LDS tables
+  struct Lists {
+    std::vector<DynWork> dyn;                 // fixed timings; every slice of one problem on one XCD (Interleave)
+    std::vector<RomWork> rom;                 // (same)
+    std::vector<NodeWork> node;               // one per problem + one past the end that carries the totals
+    std::vector<FlatWork> flat;               // groups of four per problem; empty when a problem cannot take the values-only path
+    std::vector<FamWork> fam[4];              // chunk lists of node_chunk_kernel (large batches only)
+    std::vector<PDynWork> pdyn;               // optimised timings (XCD order as dyn)
+    std::vector<LocWork> ploc;
+    std::vector<RomPhaseWork> prom;
+  } lists;
+  // Scratch for the x-dependent DynLoc / RomRec records of the optimised-timings problems.  The lists hold byte offsets into it
+  // until PlaceRecords(scratch address) turns them into addresses; LocWork::recs / dyn_loc store offset + 1 meanwhile, since
+  // 0 there means "no such array".
+  size_t records_bytes = 0;
+  void PlaceRecords(uint64_t base);
+  int rom_max_vals = 0;        // Jacobian values of the largest rom slice (picks the copy-out length)
+  int flat_max_x = 0;          // variables of the largest problem of the values-only path (the LDS a wave stages x in)
+  int dyn_map_chunks = 2;      // 2: every dyn slice of the batch stages <= 128 doubles of x (256-byte staging maps), else 4
+  int node_families = 4;       // 2 when no problem has more than terrain-* / force-* work for the node kernel
+  int pdyn_img_cap = 0, prom_img_cap = 0;   // doubles of the LDS images of dyn_phase_kernel / rom_phase_kernel (largest pass)
+  bool stream_nt = false;      // non-temporal copy-out stores (StreamNonTemporal)
+  int64_t dyn_layout_bytes = 0, dyn_layout_distinct_bytes = 0;   // dyn_kernel's layout tables: as built / after sharing
+};
+std::vector<size_t> BlobOffsets(const std::vector<const Structure*>& structs);   // n + 1 arena offsets
+BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem,
+                    const std::vector<uint64_t>& blob, int n_cu, int64_t cache_bytes, int force_chunk);
+// fpowr GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53): samples while t <= t_total + 1e-5, t accumulated
+int SampleCount(double t_total, double dt);
 void GaitCombo(int n_ee, int combo, double t_total, double swing_scale, twr_schedule* out);
 void ModelPreset(int robot, int terrain, twr_model* out);
 double TerrainHeightHost(const twr_model& m, const TerrainGrid* grid, double x, double y);
