@@ -382,9 +382,12 @@ int twr_batch_eval_host(twr_batch* b, const double* h_x, double* h_g, double* h_
 int twr_batch_host_buffers(twr_batch* b, double** h_x, double** h_g, double** h_jac);
 
 /* Tuning knobs.  The DEFAULT build reads nothing from the environment: the values below are compiled in.  A build with
- * -DTWR_TUNING_KNOBS (make -C towr_amd/csrc TUNING=1) reads them once per process, for A/B measurements (scripts/ab.py,
- * DESIGN.md section 6); they never change results, only how the work is spread over the device:
+ * -DTWR_TUNING_KNOBS (make -C towr_amd/csrc TUNING=1) reads them, for A/B measurements (scripts/ab.py):
+ * TWR_STREAM_NT when a batch is created, TWR_HOST_ZERO_COPY[_X] once per process, the launch knobs (the BPC, FUSED knobs) on
+ * every twr_batch_eval, so that an experiment may change them between evaluations of one process.  They never change
+ * results, only how the work is spread over the device:
  *   TWR_DYN_BPC, TWR_ROM_BPC        persistent workgroups per CU of dyn_kernel / rom_kernel (8 / 4: their LDS images fill a CU)
+ *   TWR_NODE_BPC                    persistent waves per CU of node_chunk_kernel, all families together (16)
  *   TWR_PDYN_BPC, TWR_PROM_BPC      the same for dyn_phase_kernel / rom_phase_kernel (default: what their LDS images allow,
  *                                   at most 4 / 8)
  *   TWR_FUSED_MAX_ROM               rom slices up to which one fused launch replaces the three kernels (default: 20 rounds

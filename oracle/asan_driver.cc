@@ -4,6 +4,7 @@
 // robots x gait combos x constraint-set masks (incl. optimised timings and baseMotion) through
 //   twr::Structure::Build / InitialGuess / VariableBounds   (towr_amd/csrc/structure.cc)
 //   twr::ShareLayoutTables / PlanBatch (what twr_batch_create uploads; structure.cc)
+//   twr::PlanEval (the launches of one twr_batch_eval; structure.cc)
 //   orc_create / orc_eval / orc_bounds / orc_sample_trajectory (oracle/towr_oracle.cc)
 // and cross-checks sizes and the CSR pattern of the two, so that every table write and every row of the
 // pattern builders executes under the sanitizers.
@@ -15,6 +16,7 @@
 #include <cstring>
 #include <initializer_list>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "../towr_amd/csrc/structure.h"
@@ -204,6 +206,264 @@ static void check_moved(const char* what, const std::vector<W>& a, const std::ve
 }
 
 
+// twr::PlanEval (the launches of one evaluation).  A plan as text, one token per step: "e<i>" for an event, else the kernel
+// and its instantiation (n = NIT, x = XC / NX, store variant), grid x block, dynamic LDS when there is any, then the role
+// grids (fused, chunks) or groups / node families (values).
+static const char* const kKernelName[] = {"e", "dyn", "rom", "fused", "ploc", "pdyn", "prom", "node", "node2", "chunk", "values"};
+static const char* const kStoreName[] = {"G", "J", "GJ", "J+NT", "GJ+NT"};
+static std::string describe(const twr::EvalPlan& plan, bool full = true) {
+  std::string out;
+  char buf[160];
+  for (int i = 0; i < plan.n; ++i) {
+    const twr::LaunchStep& p = plan.step[i];
+    if (p.kernel == twr::Launch::kEvent) {
+      std::snprintf(buf, sizeof buf, "%se%d", i ? " " : "", p.arg[0]);
+    } else if (!full) {
+      std::snprintf(buf, sizeof buf, "%s%s", i ? " " : "", kKernelName[(int)p.kernel]);
+    } else {
+      int n = std::snprintf(buf, sizeof buf, "%s%s", i ? " " : "", kKernelName[(int)p.kernel]);
+      if (p.nit || p.kernel == twr::Launch::kDynPhase || p.kernel == twr::Launch::kRomPhase) n += std::snprintf(buf + n, sizeof buf - n, " n%d", p.nit);
+      if (p.xc) n += std::snprintf(buf + n, sizeof buf - n, " x%d", p.xc);
+      n += std::snprintf(buf + n, sizeof buf - n, " %s %dx%d", kStoreName[p.store], p.grid, p.block);
+      if (p.lds) n += std::snprintf(buf + n, sizeof buf - n, " lds%d", p.lds);
+      if (p.kernel == twr::Launch::kFused) n += std::snprintf(buf + n, sizeof buf - n, " [%d %d]", p.arg[0], p.arg[1]);
+      if (p.kernel == twr::Launch::kChunk) n += std::snprintf(buf + n, sizeof buf - n, " [%d %d %d %d]", p.arg[0], p.arg[1], p.arg[2], p.arg[3]);
+      if (p.kernel == twr::Launch::kValues) std::snprintf(buf + n, sizeof buf - n, " [%d %d %d]", p.arg[0], p.arg[1], p.arg[2]);
+    }
+    out += buf;
+    if (full && p.kernel != twr::Launch::kEvent) out += ";";
+  }
+  return out;
+}
+static void expect_plan(const char* what, const twr::EvalShape& s, const char* want) {
+  const std::string got = describe(twr::PlanEval(s));
+  CHECK(got == want, "eval plan %s:\n  got  %s\n  want %s", what, got.c_str(), want);
+}
+template <size_t N>
+static bool listed(const int (&keys)[N], int v) {
+  return std::find(keys, keys + N, v) != keys + N;
+}
+
+// Both sides of every threshold of PlanEval on synthetic shapes of a 256-CU device (rom residency 4 x 256 = 1024 slices);
+// the expected plans are worked out by hand from the rules, not by the planner's formulas.
+static twr::EvalShape shape(int dyn, int rom, int node, int flags = 3) {
+  twr::EvalShape s;
+  s.n_cu = 256;
+  s.dyn = dyn, s.rom = rom, s.node = node, s.flags = flags;
+  s.rom_max_vals = 4000;   // copy-out 32 -> NIT 34 for rom and fused
+  return s;
+}
+static void eval_threshold_cases() {
+  // fused up to 20 rounds of rom residency; the split of the residency at 8 n_rom = 34 cap (5/8 for rom, then 4/8)
+  expect_plan("fused at 20 rounds", shape(4000, 20480, 300), "fused n34 x2 GJ 1624x128 [512 512];");
+  expect_plan("separate past 20 rounds", shape(4000, 20481, 300), "dyn x2 GJ 2048x64; rom n34 GJ 1024x64; node GJ 300x256;");
+  expect_plan("split 5/8 at 34/8 rounds", shape(4096, 4352, 300), "fused n34 x2 GJ 1624x128 [640 384];");
+  expect_plan("split 4/8 past 34/8 rounds", shape(4096, 4353, 300), "fused n34 x2 GJ 1624x128 [512 512];");
+  expect_plan("roles that fit stay whole", shape(200, 300, 300), "fused n34 x2 GJ 996x128 [300 96];");
+  expect_plan("g_dyn below 8", shape(13, 100, 10), "fused n34 x2 GJ 127x128 [100 7];");
+  expect_plan("g_dyn at 8", shape(16, 100, 10), "fused n34 x2 GJ 128x128 [100 8];");
+  expect_plan("g_dyn rounded to 8", shape(19, 100, 10), "fused n34 x2 GJ 128x128 [100 8];");
+  // copy-out lengths: rom 26 / 30 / 34 / 38, fused 34 / 38 (whole store instructions of 128 doubles past a parity pair and one)
+  const int rom_nit[][2] = {{3325, 26}, {3326, 30}, {3837, 30}, {3838, 34}, {4349, 34}, {4350, 38}, {twr::kRomStage, 38}};
+  for (const auto& c : rom_nit) {
+    twr::EvalShape s = shape(0, 1000, 0);
+    s.rom_max_vals = c[0];
+    const std::string want = "rom n" + std::to_string(c[1]) + " GJ 1000x64;";
+    expect_plan(("rom copy-out of " + std::to_string(c[0])).c_str(), s, want.c_str());
+  }
+  twr::EvalShape f = shape(100, 100, 0);
+  f.rom_max_vals = 4349;
+  expect_plan("fused copy-out 34", f, "fused n34 x2 GJ 148x128 [100 48];");
+  f.rom_max_vals = 4350;
+  f.dyn_map_chunks = 4;
+  expect_plan("fused copy-out 38", f, "fused n38 x4 GJ 148x128 [100 48];");
+  // phase kernels: copy-out length and residency from the LDS image (dyn_phase_kernel at most 4 per CU, rom_phase_kernel 8)
+  const int pdyn[][2] = {{1000, 0}, {5120, 0}, {5121, 0}, {8200, 0}};
+  const char* const pdyn_want[] = {"pdyn n40 GJ 1024x64 lds8000;", "pdyn n40 GJ 1024x64 lds40960;", "pdyn n0 GJ 768x64 lds40976;",
+                                   "pdyn n0 GJ 512x64 lds65600;"};
+  for (int i = 0; i < 4; ++i) {
+    twr::EvalShape s = shape(0, 0, 0);
+    s.pdyn = 2000, s.pdyn_img_cap = pdyn[i][0];
+    expect_plan(("pdyn image " + std::to_string(pdyn[i][0])).c_str(), s, pdyn_want[i]);
+  }
+  const int prom[] = {100, 3072, 3073, 4096, 4097, 5120, 5121, 8193};
+  const char* const prom_want[] = {"prom n24 GJ 2048x64 lds800;",    "prom n24 GJ 1536x64 lds24576;", "prom n32 GJ 1536x64 lds24592;",
+                                   "prom n32 GJ 1280x64 lds32768;",  "prom n40 GJ 1024x64 lds32784;", "prom n40 GJ 1024x64 lds40960;",
+                                   "prom n0 GJ 768x64 lds40976;",    "prom n0 GJ 512x64 lds65552;"};
+  for (int i = 0; i < 8; ++i) {
+    twr::EvalShape s = shape(0, 0, 0);
+    s.prom = 3000, s.prom_img_cap = prom[i];
+    expect_plan(("prom image " + std::to_string(prom[i])).c_str(), s, prom_want[i]);
+  }
+  // values only: NX 3 / 5 / 8 for up to 3 / 5 / 8 x 256 variables; the node families ride along without events and chunks
+  const int flat_x[] = {768, 769, 1280, 1281};
+  const char* const flat_want[] = {"values x3 G 200x256 lds24592 [100 4 6160];", "values x5 G 200x256 lds24608 [100 4 6176];",
+                                   "values x5 G 200x256 lds28688 [100 4 10256];", "values x8 G 200x256 lds28704 [100 4 10272];"};
+  for (int i = 0; i < 4; ++i) {
+    twr::EvalShape s = shape(1600, 1600, 100, 1);
+    s.flat = 400, s.flat_max_x = flat_x[i];
+    expect_plan(("values of " + std::to_string(flat_x[i]) + " variables").c_str(), s, flat_want[i]);
+  }
+  twr::EvalShape v = shape(1600, 1600, 100, 1);
+  v.flat = 400, v.flat_max_x = 768, v.events = true;
+  expect_plan("values with events", v, "e0 values x3 G 100x256 lds24592 [100 0 6160]; e1 e2 node G 100x256; e3");
+  v.events = false, v.fam[1] = 100, v.fam[3] = 50;
+  expect_plan("values with chunk lists", v, "values x3 G 100x256 lds24592 [100 0 6160]; chunk G 150x64 [0 100 0 50];");
+  v.fam[1] = 0, v.fam[3] = 0, v.flags = 3;
+  expect_plan("values and Jacobian", v, "fused n34 x2 GJ 1224x128 [640 384];");
+  // chunk shares: one that rounds to 0 gets one block, none gets more than its chunks
+  twr::EvalShape c = shape(0, 0, 2048);
+  c.fam[0] = 100000, c.fam[1] = 1, c.fam[3] = 5000;
+  expect_plan("chunk shares rounding to 0", c, "chunk GJ 4096x64 [3900 1 0 195];");
+  c.fam[0] = 10, c.fam[1] = 20, c.fam[2] = 30, c.fam[3] = 40;
+  expect_plan("chunk shares past the chunks", c, "chunk GJ 100x64 [10 20 30 40];");
+  twr::EvalShape n2 = shape(0, 0, 300, 2);
+  n2.node_families = 2;
+  expect_plan("two node families", n2, "node2 J 300x128;");
+  // every list with events, non-temporal stores (Jacobian only: the values-only store variant stays G)
+  twr::EvalShape all = shape(100, 100, 10, 2);
+  all.ploc = 4, all.pdyn = 50, all.prom = 60, all.pdyn_img_cap = 1000, all.prom_img_cap = 1000, all.dyn_map_chunks = 4;
+  all.stream_nt = true, all.events = true;
+  expect_plan("all lists, events", all, "e0 dyn x4 J+NT 100x64; ploc J 4x256; pdyn n40 J 50x64 lds8000; e1 prom n24 J 60x64 lds8000; "
+              "rom n34 J+NT 100x64; e2 node J 10x256; e3");
+  twr::EvalShape g = shape(100, 100, 10, 1);
+  g.stream_nt = true;
+  expect_plan("values with non-temporal stores", g, "fused n34 x2 G 168x128 [100 48];");
+  g.flags = 3;
+  expect_plan("both with non-temporal stores", g, "fused n34 x2 GJ+NT 168x128 [100 48];");
+
+  // tuning knobs: split 8 = unsplit, explicit role grids clamped to the work, the residency counts
+  twr::EvalShape k = shape(4096, 4352, 300);
+  k.tuning.fused_split = 8;
+  expect_plan("knob: split 8", k, "fused n34 x2 GJ 2648x128 [1024 1024];");
+  k.tuning.fused_split = 6;
+  expect_plan("knob: split 6", k, "fused n34 x2 GJ 1624x128 [768 256];");
+  k = shape(4000, 3000, 0);
+  k.tuning.fused_grom = 5000, k.tuning.fused_gdyn = 5000;
+  expect_plan("knob: role grids clamped", k, "fused n34 x2 GJ 5000x128 [3000 2000];");
+  k.tuning.fused_grom = 100, k.tuning.fused_gdyn = 13;
+  expect_plan("knob: role grids", k, "fused n34 x2 GJ 108x128 [100 8];");
+  k = shape(4000, 25000, 0);
+  k.tuning.fused_max_rom = 30000;
+  expect_plan("knob: fused up to more", k, "fused n34 x2 GJ 1024x128 [512 512];");
+  k = shape(4000, 101, 0);
+  k.tuning.fused_max_rom = 100;
+  expect_plan("knob: fused up to less", k, "dyn x2 GJ 2048x64; rom n34 GJ 101x64;");
+  k = shape(4000, 30000, 0);
+  k.tuning.dyn_bpc = 4, k.tuning.rom_bpc = 2;
+  expect_plan("knob: dyn / rom residency", k, "dyn x2 GJ 1024x64; rom n34 GJ 512x64;");
+  k = shape(0, 0, 100);
+  k.fam[0] = 1000, k.fam[1] = 1000, k.tuning.node_bpc = 1;
+  expect_plan("knob: chunk residency", k, "chunk GJ 256x64 [128 128 0 0];");
+  k = shape(0, 0, 0);
+  k.pdyn = 2000, k.prom = 2000, k.pdyn_img_cap = 1000, k.prom_img_cap = 1000, k.tuning.pdyn_bpc = 2, k.tuning.prom_bpc = 3;
+  expect_plan("knob: phase residency", k, "pdyn n40 GJ 512x64 lds8000; prom n24 GJ 768x64 lds8000;");
+}
+
+// Invariants of the plans of a PlanBatch result, for V, J and VJ with and without events: every list is launched exactly once
+// (dyn and rom rows by their own kernels, the fused launch or the values-only launch; the node families by the node kernels,
+// the chunk kernel, the fused launch's node role or the values-only launch), grids inside 1..items, copy-outs covering the
+// largest slice, LDS within a CU, instantiations that exist, non-temporal stores only with the Jacobian, events in place.
+static void eval_invariants(const char* name, const twr::BatchPlan& B, int n_cu) {
+  const twr::BatchPlan::Lists& L = B.lists;
+  for (int flags : {1, 2, 3})
+    for (bool events : {false, true}) {
+      twr::EvalShape s;
+      s.n_cu = n_cu;
+      s.dyn = (int)L.dyn.size(); s.rom = (int)L.rom.size(); s.node = (int)L.node.size() - 1; s.flat = (int)L.flat.size();
+      s.pdyn = (int)L.pdyn.size(); s.ploc = (int)L.ploc.size(); s.prom = (int)L.prom.size();
+      for (int f = 0; f < 4; ++f) s.fam[f] = (int)L.fam[f].size();
+      s.rom_max_vals = B.rom_max_vals; s.flat_max_x = B.flat_max_x; s.dyn_map_chunks = B.dyn_map_chunks; s.node_families = B.node_families;
+      s.pdyn_img_cap = B.pdyn_img_cap; s.prom_img_cap = B.prom_img_cap; s.stream_nt = B.stream_nt;
+      s.flags = flags;
+      s.events = events;
+      const twr::EvalPlan plan = twr::PlanEval(s);
+      const std::string text = describe(plan);
+      const char* what = text.c_str();
+      int dyn = 0, rom = 0, node = 0, pdyn = 0, ploc = 0, prom = 0, launches = 0, chunks = 0;
+      for (int f = 0; f < 4; ++f) chunks += s.fam[f];
+      for (int i = 0; i < plan.n; ++i) {
+        const twr::LaunchStep& p = plan.step[i];
+        if (p.kernel == twr::Launch::kEvent) continue;
+        ++launches;
+        int items = 0;
+        bool key = true;
+        const bool has_store = p.kernel != twr::Launch::kLocate && p.kernel != twr::Launch::kNode && p.kernel != twr::Launch::kNode2 &&
+                               p.kernel != twr::Launch::kValues;
+        switch (p.kernel) {
+          case twr::Launch::kDyn: ++dyn; items = s.dyn; key = listed(twr::kDynXc, p.xc) && listed(twr::kStoresNT, p.store); break;
+          case twr::Launch::kRom: ++rom; items = s.rom; key = listed(twr::kRomNits, p.nit) && listed(twr::kStoresNT, p.store); break;
+          case twr::Launch::kFused:
+            ++dyn, ++rom, ++node;
+            items = s.rom + (s.dyn + 1) / 2 + 2 * s.node;
+            key = listed(twr::kFusedNits, p.nit) && listed(twr::kDynXc, p.xc) && listed(twr::kStoresNT, p.store);
+            CHECK(p.arg[0] >= 1 && p.arg[0] <= s.rom && p.arg[1] >= 1 && p.arg[1] <= (s.dyn + 1) / 2 && p.grid == p.arg[0] + p.arg[1] + 2 * s.node,
+                  "%s: fused role grids in %s", name, what);
+            break;
+          case twr::Launch::kLocate: ++ploc; items = s.ploc; break;
+          case twr::Launch::kDynPhase: ++pdyn; items = s.pdyn; key = listed(twr::kDynPhaseNits, p.nit) && listed(twr::kStores, p.store); break;
+          case twr::Launch::kRomPhase: ++prom; items = s.prom; key = listed(twr::kRomPhaseNits, p.nit) && listed(twr::kStores, p.store); break;
+          case twr::Launch::kNode: case twr::Launch::kNode2: ++node; items = s.node; break;
+          case twr::Launch::kChunk:
+            ++node;
+            items = chunks;
+            key = listed(twr::kStores, p.store);
+            for (int f = 0; f < 4; ++f)
+              CHECK(s.fam[f] ? p.arg[f] >= 1 && p.arg[f] <= s.fam[f] : p.arg[f] == 0, "%s: chunk grid of family %d in %s", name, f, what);
+            CHECK(p.grid == p.arg[0] + p.arg[1] + p.arg[2] + p.arg[3], "%s: chunk grid in %s", name, what);
+            break;
+          case twr::Launch::kValues:
+            ++dyn, ++rom, node += p.arg[1] > 0;
+            items = s.flat / 4 + (p.arg[1] > 0 ? s.node : 0);
+            key = listed(twr::kValuesNx, p.xc) && p.xc * 64 * twr::kFlatGroup >= s.flat_max_x;
+            CHECK(p.arg[0] == s.flat / 4 && (p.arg[1] == 0 || p.arg[1] == s.node_families), "%s: values groups in %s", name, what);
+            break;
+          case twr::Launch::kEvent: break;
+        }
+        CHECK(p.grid >= 1 && p.grid <= items, "%s: grid %d of %d items in %s", name, p.grid, items, what);
+        CHECK(key, "%s: an instantiation that does not exist in %s", name, what);
+        CHECK(p.lds >= 0 && p.lds <= 160 * 1024, "%s: LDS in %s", name, what);
+        if (has_store)
+          CHECK(twr::StoreG(p.store) == (bool)(flags & 1) && twr::StoreJ(p.store) == (bool)(flags & 2) &&
+                    (!twr::StoreNT(p.store) || s.stream_nt),
+                "%s: store variant in %s", name, what);
+        if (p.kernel == twr::Launch::kRom || p.kernel == twr::Launch::kFused)
+          CHECK(p.nit * 128 >= s.rom_max_vals + 3, "%s: rom copy-out of %d in %s", name, s.rom_max_vals, what);
+        if (p.kernel == twr::Launch::kDynPhase || p.kernel == twr::Launch::kRomPhase) {
+          const int img = p.kernel == twr::Launch::kDynPhase ? s.pdyn_img_cap : s.prom_img_cap;
+          CHECK(p.nit == 0 || p.nit * 128 >= img, "%s: phase copy-out of %d in %s", name, img, what);
+          CHECK(p.lds >= 8 * img, "%s: phase image in %s", name, what);
+        }
+      }
+      const bool values = (flags == 1) && s.flat > 0 && s.pdyn + s.ploc + s.prom == 0;
+      CHECK(dyn == (s.dyn > 0 || values) && rom == (s.rom > 0 || values) && node == (s.node > 0) && pdyn == (s.pdyn > 0) &&
+                ploc == (s.ploc > 0) && prom == (s.prom > 0),
+            "%s: flags %d events %d: a list launched twice or not at all: %s", name, flags, events, what);
+      // events: ev0 | launch | ev1 ev2 | nodes | ev3 (values only), ev0 | dyn ploc pdyn | ev1 | prom rom | ev2 | nodes | ev3
+      std::vector<std::string> tok;
+      const std::string seq = describe(plan, false);
+      for (size_t a = 0, b; a < seq.size(); a = b + 1) {
+        b = seq.find(' ', a);
+        if (b == std::string::npos) b = seq.size();
+        tok.push_back(seq.substr(a, b - a));
+      }
+      const char* const between[3] = {values ? " values " : " dyn ploc pdyn ", values ? " " : " prom rom ", " node node2 chunk "};
+      int ev = 0;
+      for (size_t t = 0; t < tok.size(); ++t) {
+        if (tok[t][0] == 'e' && tok[t].size() == 2) {
+          CHECK(events && tok[t][1] == '0' + ev && (ev > 0 || t == 0), "%s: events at %s", name, seq.c_str());
+          ++ev;
+        } else if (events) {
+          CHECK(ev >= 1 && ev <= 3 && std::string(between[ev - 1]).find(" " + tok[t] + " ") != std::string::npos, "%s: events at %s", name,
+                seq.c_str());
+        }
+      }
+      CHECK(ev == (events ? 4 : 0) && (!events || tok.back() == "e3"), "%s: events at %s", name, seq.c_str());
+      if (values && events) CHECK(seq.compare(0, 15, "e0 values e1 e2") == 0, "%s: events at %s", name, seq.c_str());
+      if (seq.find("fused") != std::string::npos) CHECK(!events && launches == 1, "%s: the fused launch is not alone: %s", name, seq.c_str());
+    }
+}
+
 // twr::PlanBatch (what twr_batch_create uploads besides the tables), on fake blob addresses: every row of dynamic,
 // rangeofmotion-* and the chunked node families is written by exactly one work item at the g / Jacobian offsets of the
 // CSR pattern, every list keeps each problem's items in order, the XCD order, whole flat groups of one problem, every
@@ -361,6 +621,7 @@ static void plan_case(const char* name, const std::vector<const twr::Structure*>
           "%s: placed LocWork", name);
   for (const auto& w : L.prom) CHECK(w.recs >= base && w.recs < base + B.records_bytes, "%s: placed RomPhaseWork", name);
   for (const auto& w : L.pdyn) CHECK(w.loc >= base && w.loc < base + B.records_bytes, "%s: placed PDynWork", name);
+  eval_invariants(name, B, n_cu);
   std::printf("plan %-9s %5d problems: dyn %zu rom %zu flat %zu fam %zu/%zu/%zu/%zu pdyn %zu ploc %zu prom %zu\n", name, P, L.dyn.size(),
               L.rom.size(), L.flat.size(), L.fam[0].size(), L.fam[1].size(), L.fam[2].size(), L.fam[3].size(), L.pdyn.size(),
               L.ploc.size(), L.prom.size());
@@ -388,6 +649,7 @@ static void plan_cases() {
 int main() {
   sharing_case();
   policy_case();
+  eval_threshold_cases();
   plan_cases();
   int cases = 0;
   const int masks[] = {27, 63, 127, 255, 2, 8 | 64, 1 | 16};

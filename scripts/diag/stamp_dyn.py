@@ -37,10 +37,10 @@ rep("    w2 = w3;\n  }\n  copy_out(pdst, pg, wp.nvals, wp.cnt);                 
     "    w2 = w3;\n    acc[7] += 1;\n  }\n"
     "  if (lane == 0 && i_first < 1024 && WANT_G && WANT_J)\n    for (int q = 0; q < 8; ++q) g_dyn_stamps[i_first * 8 + q] = acc[q];\n"
     "  copy_out(pdst, pg, wp.nvals, wp.cnt);                 // last slice of this workgroup")
-rep("int dyn_dump_doubles() { return kDynImage + 2 + 96; }",
-    "int dyn_dump_doubles() { return kDynImage + 2 + 96; }\n"
+rep("#endif  // !TWR_TU_ROM\n\n}  // namespace twr",
     "extern \"C\" int twr_debug_dyn_stamps(unsigned long long* out, int n) {\n"
-    "  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dyn_stamps), sizeof(unsigned long long) * (size_t)n);\n}")
+    "  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_dyn_stamps), sizeof(unsigned long long) * (size_t)n);\n}\n"
+    "#endif  // !TWR_TU_ROM\n\n}  // namespace twr")
 tmp = os.path.join(SRC, "_kernels_dynstamps.hip")
 open(tmp, "w").write(s)
 hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -30,10 +30,10 @@ rep("    fam_store<FAM, WANT_G, WANT_J>(w0, g, jac, stage, gst, par, lane);\n", 
 rep("    w1 = w2; in1 = in2;\n    w2 = w3;\n  }",
     "    w1 = w2; in1 = in2;\n    w2 = w3;\n    NSTAMP(3)\n    acc[7] += 1;\n  }\n"
     "  if (lane == 0 && i_first < 256 && WANT_G && WANT_J)\n    for (int q = 0; q < 8; ++q) g_node_stamps[(FAM * 256 + i_first) * 8 + q] = acc[q];")
-rep("int dyn_dump_doubles() { return kDynImage + 2 + 96; }",
-    "int dyn_dump_doubles() { return kDynImage + 2 + 96; }\n"
+rep("#endif  // !TWR_TU_ROM\n\n}  // namespace twr",
     "extern \"C\" int twr_debug_node_stamps(unsigned long long* out, int n) {\n"
-    "  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_node_stamps), sizeof(unsigned long long) * (size_t)n);\n}")
+    "  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_node_stamps), sizeof(unsigned long long) * (size_t)n);\n}\n"
+    "#endif  // !TWR_TU_ROM\n\n}  // namespace twr")
 tmp = os.path.join(SRC, "_kernels_nodestamps.hip")
 open(tmp, "w").write(s)
 hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

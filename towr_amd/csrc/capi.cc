@@ -15,31 +15,7 @@
 #include <utility>
 #include <vector>
 
-#include "structure.h"
-
-namespace twr {
-hipError_t launch_eval(int n_ee, int n_cu, const DynWork* dyn, int n_dyn, int dyn_map_chunks, const RomWork* rom, int n_rom, int rom_max_vals,
-                       const NodeWork* node, int n_node, int node_families, const FamWork* const fam[4], const int n_fam[4],
-                       const PDynWork* pdyn, int n_pdyn, int pdyn_img_cap,
-                       const LocWork* ploc, int n_ploc, const RomPhaseWork* prom, int n_prom, int prom_img_cap, const double* x,
-                       double* g, double* jac, double* dump, int flags, bool stream_nt, const FlatWork* flat, int n_flat, int flat_max_x,
-                       hipStream_t stream, hipEvent_t* ev);
-int dyn_dump_doubles();
-int node_force_chunk();
-hipError_t prepare_phase_kernels(int pdyn_img_cap, int prom_img_cap);
-hipError_t launch_check(int n_problems, const int64_t* g_off, const int64_t* j_off, const double* g, const double* jac,
-                        int32_t* status, int flags, hipStream_t stream);
-hipError_t launch_score(const NodeWork* work, int n_problems, const double* g, double* scores, hipStream_t stream);
-int best_max_blocks();
-hipError_t launch_best(const double* scores, int n, unsigned families, double* partial, unsigned* counter, double* best, double index_offset,
-                       hipStream_t stream);
-hipError_t launch_contact_plan(const NodeWork* work, int n_problems, const double* x, double* out, int32_t* counts, double dt,
-                               double time_horizon, int n_samples_max, int max_steps, hipStream_t stream);
-hipError_t launch_planes(const double* plan, const int32_t* counts, const double* poly_xy, const int32_t* poly_start, int n_polys,
-                         int n_problems, int max_steps, int n_ee, int32_t* plane_index, hipStream_t stream);
-hipError_t launch_sample(const SampleWork* work, int n_work, const double* x, double* out, double dt, const double* times,
-                         hipStream_t stream);
-}  // namespace twr
+#include "launch.h"
 
 struct twr_structure {
   twr::Structure s;
@@ -557,7 +533,7 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
     b->n_cu = prop.multiProcessorCount;
     // (a compute partition -- CPX -- shows up as a device with a fraction of the chip's CUs: its share of the cache follows)
     b->plan = twr::PlanBatch(sp, std::vector<int32_t>(struct_of_problem, struct_of_problem + n_problems), blob_at, b->n_cu,
-                             twr::MemorySideCacheBytes(prop.gcnArchName, prop.l2CacheSize, 1), twr::node_force_chunk());
+                             twr::MemorySideCacheBytes(prop.gcnArchName, prop.l2CacheSize, 1), twr::kForceChunk);
 #ifdef TWR_TUNING_KNOBS   // (include/towr_amd.h, "Tuning knobs")
     if (const char* e = getenv("TWR_STREAM_NT")) b->plan.stream_nt = atoi(e) != 0;
 #endif
@@ -571,7 +547,7 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
       if (!L.fam[f].empty()) b->fam[f] = upload(L.fam[f]);
     b->goff = upload(b->plan.g_off);
     b->joff = upload(b->plan.j_off);
-    b->dump = dev_zeros<double>(twr::dyn_dump_doubles());
+    b->dump = dev_zeros<double>(twr::kDynDump);
     b->best = dev_zeros<double>(2 * (size_t)twr::best_max_blocks() + 1);
     b->status = dev_zeros<int32_t>(n_problems);
     if (!L.ploc.empty()) {
@@ -618,6 +594,28 @@ int twr_batch_layout(const twr_batch* b, int64_t* x_off, int64_t* g_off, int64_t
   return TWR_OK;
 }
 
+// Tuning knobs of the launches (include/towr_amd.h): a TUNING=1 build reads them on every evaluation; the default build reads
+// nothing and keeps the defaults of twr::LaunchTuning.
+static twr::LaunchTuning tuning_knobs() {
+  twr::LaunchTuning t;
+#ifdef TWR_TUNING_KNOBS
+  const auto knob = [](const char* name, int& v) {
+    const char* e = getenv(name);
+    if (e && atoi(e) > 0) v = atoi(e);
+  };
+  knob("TWR_DYN_BPC", t.dyn_bpc);
+  knob("TWR_ROM_BPC", t.rom_bpc);
+  knob("TWR_NODE_BPC", t.node_bpc);
+  knob("TWR_PDYN_BPC", t.pdyn_bpc);
+  knob("TWR_PROM_BPC", t.prom_bpc);
+  knob("TWR_FUSED_MAX_ROM", t.fused_max_rom);
+  knob("TWR_FUSED_SPLIT", t.fused_split);
+  knob("TWR_FUSED_GROM", t.fused_grom);
+  knob("TWR_FUSED_GDYN", t.fused_gdyn);
+#endif
+  return t;
+}
+
 int twr_batch_eval(twr_batch* b, const double* d_x, double* d_g, double* d_jac, int flags, void* hip_stream) {
   if (!b || !d_x) return fail(TWR_ERR_INVALID, "null argument");
   if ((flags & TWR_EVAL_BOTH) == 0) return fail(TWR_ERR_INVALID, "flags select nothing");
@@ -631,11 +629,19 @@ int twr_batch_eval(twr_batch* b, const double* d_x, double* d_g, double* d_jac, 
   if (b->prof_count < b->prof_capacity) ev = b->prof_events.ev.data() + 4 * b->prof_count++;
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   const twr::BatchPlan& P = b->plan;
-  const twr::FamWork* const fam[4] = {b->fam[0].d.get(), b->fam[1].d.get(), b->fam[2].d.get(), b->fam[3].d.get()};
-  const int n_fam[4] = {b->fam[0].n, b->fam[1].n, b->fam[2].n, b->fam[3].n};
-  hipError_t e = twr::launch_eval(b->n_ee, b->n_cu, b->dyn.d.get(), b->dyn.n, P.dyn_map_chunks, b->rom.d.get(), b->rom.n, P.rom_max_vals, b->node.d.get(), b->node.n, P.node_families, fam, n_fam,
-                                  b->pdyn.d.get(), b->pdyn.n, P.pdyn_img_cap, b->ploc.d.get(), b->ploc.n, b->prom.d.get(), b->prom.n,
-                                  P.prom_img_cap, d_x, d_g, d_jac, b->dump.get(), flags & TWR_EVAL_BOTH, P.stream_nt, b->flat.d.get(), b->flat.n, P.flat_max_x, stream, ev);
+  twr::EvalShape s;
+  s.n_cu = b->n_cu;
+  s.dyn = b->dyn.n; s.rom = b->rom.n; s.node = b->node.n; s.flat = b->flat.n; s.pdyn = b->pdyn.n; s.ploc = b->ploc.n; s.prom = b->prom.n;
+  for (int f = 0; f < 4; ++f) s.fam[f] = b->fam[f].n;
+  s.rom_max_vals = P.rom_max_vals; s.flat_max_x = P.flat_max_x; s.dyn_map_chunks = P.dyn_map_chunks; s.node_families = P.node_families;
+  s.pdyn_img_cap = P.pdyn_img_cap; s.prom_img_cap = P.prom_img_cap; s.stream_nt = P.stream_nt;
+  s.flags = flags & TWR_EVAL_BOTH;
+  s.events = ev != nullptr;
+  s.tuning = tuning_knobs();
+  const twr::EvalBuffers buf{b->dyn.d.get(), b->rom.d.get(), b->node.d.get(), b->flat.d.get(),
+                             {b->fam[0].d.get(), b->fam[1].d.get(), b->fam[2].d.get(), b->fam[3].d.get()},
+                             b->pdyn.d.get(), b->ploc.d.get(), b->prom.d.get(), d_x, d_g, d_jac, b->dump.get()};
+  hipError_t e = twr::launch_eval(s, buf, stream, ev);
   if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   if (flags & TWR_EVAL_CHECK) {
     e = twr::launch_check(b->n_problems, b->goff.d.get(), b->joff.d.get(), d_g, d_jac, b->status.get(), flags & TWR_EVAL_BOTH, stream);

@@ -528,4 +528,15 @@ struct RomPhaseWork {     // one pass: cnt <= 16 time nodes of one (problem, ee)
 };
 static_assert(sizeof(RomPhaseWork) == 56, "RomPhaseWork layout");
 
+// Launch geometry the host planner (structure.h PlanEval) shares with the kernels.
+constexpr int kRomNitMax = (kRomStage + 2 + 127) / 128;   // 38: rom_kernel's copy-out of a whole image (store instructions)
+constexpr int kDynDump = kDynImage + 2 + 96;              // doubles of dyn_kernel's dump (its first, empty copy-out per workgroup)
+constexpr int kForceChunk = 32;                           // force nodes per chunk of node_chunk_kernel (25 values each)
+constexpr int kLocateThreads = 256;                       // phase_locate_kernel: one thread per time node
+constexpr int kFlatGroup = 4;                             // eval_values_kernel: items (= waves) per workgroup
+constexpr int kFlatWaveLds = kFlatPolyLds + 192 * 8;      // bytes of a wave's own region: polynomial windows, constraint values
+// eval_values_kernel's dynamic LDS: [ zero pair | x ] [ per wave: kFlatWaveLds ]
+inline int flat_x_bytes(int max_n_x) { return 8 * (2 + ((max_n_x + 1) & ~1)); }
+inline int flat_lds_bytes(int max_n_x) { return flat_x_bytes(max_n_x) + kFlatGroup * kFlatWaveLds; }
+
 }  // namespace twr

@@ -26,12 +26,11 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
-#include <stdlib.h>
 
 #include <tuple>
 #include <utility>
 
-#include "device_tables.h"
+#include "launch.h"
 
 namespace twr {
 
@@ -95,6 +94,19 @@ static inline hipError_t twr_launch(void (*kern)(P...), dim3 grid, dim3 block, s
   return twr_launch_impl(reinterpret_cast<const void*>(kern), grid, block, lds, stream, vals, std::index_sequence_for<P...>{});
 }
 static inline hipError_t twr_first(hipError_t a, hipError_t b) { return a != hipSuccess ? a : b; }
+// The instantiation a planned launch names (structure.h: the key lists kStoresNT ... kValuesNx): pick<L>(v, f) returns
+// f(std::integral_constant<int, v>) if v is an entry of the list L, else a null kernel.  Every templated kernel has one
+// lookup built from these, the one place its instantiations are listed.
+template <const auto& L, class F, size_t... I>
+static inline auto pick(int v, F f, std::index_sequence<I...>) {
+  decltype(f(std::integral_constant<int, L[0]>{})) r = nullptr;
+  (void)(... || (L[I] == v && (r = f(std::integral_constant<int, L[I]>{}), true)));
+  return r;
+}
+template <const auto& L, class F>
+static inline auto pick(int v, F f) {
+  return pick<L>(v, f, std::make_index_sequence<sizeof(L) / sizeof(L[0])>{});
+}
 
 // ---------------------------------------------------------------- cubic Hermite weights
 // d{pos,vel,acc}/d{p0,v0,p1,v1} of CubicHermitePolynomial (src/polynomial.cc:140-234); iT = 1/T comes
@@ -1184,10 +1196,7 @@ constexpr int kDynValuesLds = 96 + 2 + kDynXsCap;
 // rom_kernel is compiled in its own translation unit (rom_tu.hip) with a different instruction scheduling
 // strategy: it is store bound and gains 4-5 % from clause-oriented scheduling, the VALU-bound kernels lose.
 constexpr int kRomLds = kRomStage + 2 + 64 + 192;   // doubles: image, per-lane trash slots, g
-// NIT = store instructions of the copy-out: the launcher picks the smallest instantiation that covers the largest slice
-// of the batch.  The stores past the end of a slice are re-stores of its last pair -- no HBM traffic, but requests all
-// the same: C3's balanced 50-node slices need 34, and 34 instead of 38 is worth 4 % of the kernel (A/B on one box: 0.925
-// -> 0.883 ms together with the balanced slices; five 40-node slices with 27 stores each: 0.965 ms -- large slices win).
+// NIT = store instructions of the copy-out (structure.cc PlanEval picks it).
 // (The hand-scheduled form of dyn_phase_kernel -- asm loads into AGPRs, one counted wait behind the copy-out -- was built
 // for this loop too and is SLOWER here, 0.98 vs 0.90 ms on one box: the compiler's clause-oriented schedule of the 28
 // loads with scalar bases and immediate offsets beats 28 separate asm loads with per-lane 64-bit addresses.)
@@ -1229,7 +1238,8 @@ TWR_DEV void rom_body(const RomWork* __restrict__ work, int n_work, const double
   }
 }
 
-constexpr int kRomNitMax = (kRomStage + 2 + 127) / 128;   // 38
+using RomFn = void (*)(const RomWork*, int, const double*, double*, double*);
+RomFn rom_kernel_fn(const LaunchStep& p);   // rom_kernel's lookup, compiled in the rom unit
 #ifdef TWR_TU_ROM
 template <int NIT, bool WANT_G, bool WANT_J, bool NT>
 __global__ __launch_bounds__(64, 1) void rom_kernel(const RomWork* __restrict__ work, int n_work, const double* __restrict__ x,
@@ -1237,29 +1247,12 @@ __global__ __launch_bounds__(64, 1) void rom_kernel(const RomWork* __restrict__ 
   __shared__ __attribute__((aligned(16))) double stage[kRomLds];
   rom_body<NIT, WANT_G, WANT_J, NT>(work, n_work, x, g, jac, stage, threadIdx.x, blockIdx.x, gridDim.x);
 }
-
-// max_vals: Jacobian values of the largest slice of the batch
-hipError_t launch_rom_kernel(int grid, hipStream_t stream, const RomWork* rom, int n_rom, int max_vals, const double* x, double* g,
-                             double* jac, int flags, bool nt) {
-  const bool wg = flags & 1, wj = flags & 2;
-  const int need = (max_vals + 1 + 2 + 127) / 128;   // (+ parity shift, rounded up to whole store instructions)
-#define TWR_ROM_LAUNCH(NIT)                                                                                                  \
-  {                                                                                                                          \
-    if (wg && wj && nt) return twr_launch(rom_kernel<NIT, true, true, true>, dim3(grid), dim3(64), 0, stream, rom, n_rom, x, g, jac);    \
-    if (wg && wj) return twr_launch(rom_kernel<NIT, true, true, false>, dim3(grid), dim3(64), 0, stream, rom, n_rom, x, g, jac);         \
-    if (wj && nt) return twr_launch(rom_kernel<NIT, false, true, true>, dim3(grid), dim3(64), 0, stream, rom, n_rom, x, g, jac);         \
-    if (wj) return twr_launch(rom_kernel<NIT, false, true, false>, dim3(grid), dim3(64), 0, stream, rom, n_rom, x, g, jac);              \
-    return twr_launch(rom_kernel<NIT, true, false, false>, dim3(grid), dim3(64), 0, stream, rom, n_rom, x, g, jac);                      \
-  }
-  if (need <= 26) TWR_ROM_LAUNCH(26)
-  if (need <= 30) TWR_ROM_LAUNCH(30)
-  if (need <= 34) TWR_ROM_LAUNCH(34)
-  TWR_ROM_LAUNCH(kRomNitMax)
-#undef TWR_ROM_LAUNCH
+RomFn rom_kernel_fn(const LaunchStep& p) {
+  return pick<kRomNits>(p.nit, [&](auto nit) {
+    return pick<kStoresNT>(p.store, [&](auto st) -> RomFn { return rom_kernel<nit, StoreG(st), StoreJ(st), StoreNT(st)>; });
+  });
 }
 #else   // !TWR_TU_ROM
-hipError_t launch_rom_kernel(int grid, hipStream_t stream, const RomWork* rom, int n_rom, int max_vals, const double* x, double* g,
-                             double* jac, int flags, bool nt);
 
 // all terrain-ee-motion_e (terrain_constraint.cc:57-108), force-ee-force_e, splineacc-base-* and
 // swing-ee-motion_e sets of one problem.  One workgroup of four waves per problem, one wave per family
@@ -1615,7 +1608,6 @@ TWR_DEV void fam_body(const FamWork* __restrict__ work, int n_work, const double
   }
 }
 // blocks [0, g0) walk the terrain chunks, the next g1 the force chunks, then splineacc, then swing (any count may be 0)
-constexpr int kForceChunk = 32;                                   // force nodes per chunk (25 values each)
 constexpr int kStageChunk = kForceChunk * 25 + 2;                // >= 64 x 12 + 2 (swing), 64 x 6 + 2, 64 x 3 + 2
 constexpr int kStageChunkG = 64 * 4;                             // constraint values of a chunk: <= 64 x 4 (swing), 32 x 5 (force)
 static_assert(kStageChunk >= kStageSwing && kStageChunk >= kStageAcc && kStageChunk >= kStageTerrain, "chunk image");
@@ -1748,7 +1740,6 @@ TWR_DEV void flat_stage_polys(const FlatIn& in, char* lds, int lane) {
 }
 // x of a problem by the 256 threads of a group, NX doubles per thread (the launcher picks the smallest instantiation that
 // covers the largest problem)
-constexpr int kFlatGroup = 4;   // items (= waves) per workgroup
 template <int NX>
 TWR_DEV void flat_load_x(const double* __restrict__ xp, int n_x, int tid, double xr[NX]) {
 #pragma unroll
@@ -1970,10 +1961,7 @@ TWR_DEV void flat_dyn_math(const FlatRec& w, const FlatNodeR& n, double* __restr
 // i, the work record read by one vector load and v_readlane so that no scalar load sat in the loop -- was built, is parity-
 // green and is NOT faster: 0.084-0.092 / 0.067-0.072 ms against 0.068-0.073 / 0.066 ms per 8192 C3 problems as single-wave
 // workgroups, at three waves per SIMD instead of four because of the prefetch registers)
-constexpr int kFlatWaveLds = kFlatPolyLds + 192 * 8;   // bytes of a wave's own region
 static_assert(kFlatWaveLds >= kDynValuesLds * 8, "node_body stages its constraint values in a wave's region");
-inline size_t flat_x_bytes(int max_n_x) { return sizeof(double) * (size_t)(2 + ((max_n_x + 1) & ~1)); }
-inline size_t flat_lds_bytes(int max_n_x) { return flat_x_bytes(max_n_x) + (size_t)kFlatGroup * kFlatWaveLds; }
 template <int NX>
 __global__ __launch_bounds__(64 * kFlatGroup, 4) void eval_values_kernel(const FlatWork* __restrict__ flat, int n_groups, int x_bytes, const NodeWork* __restrict__ node,
                                                                          int node_families, const double* __restrict__ x, double* __restrict__ g) {
@@ -2580,7 +2568,6 @@ __global__ __launch_bounds__(64, 1) void dyn_phase_kernel(const PDynWork* __rest
 // DynLoc / RomRec records in the batch's scratch buffer.  256 threads, one per time node: a lookup is a chain of ~60
 // dependent LDS reads (the reference's sequential accumulation, kept bit for bit), so the kernel lives on waves in flight
 // (one wave per workgroup, four time nodes per lane: 0.094 ms per 2048 C3 problems; this form: see DESIGN 6.0).
-constexpr int kLocateThreads = 256;
 __global__ __launch_bounds__(kLocateThreads) void phase_locate_kernel(const LocWork* __restrict__ work, const double* __restrict__ x) {
   __shared__ double s_ph[TWR_MAX_PHASES_DEV], s_md[kMaxPhasePolys], s_fd[kMaxPhasePolys];
   // the records of one block of time nodes are staged in LDS and leave as one contiguous, fully coalesced stream
@@ -3435,224 +3422,74 @@ hipError_t launch_check(int n_problems, const int64_t* g_off, const int64_t* j_o
   return twr_launch(check_kernel, dim3(n_problems * kCheckParts), dim3(256), 0, stream, g_off, j_off, g, jac, status, flags);
 }
 
-// host-side launcher (called from capi.cc): three launches on one stream.  The dyn/rom grids are
-// persistent: as many workgroups as are resident at once.  Residency is LDS bound; the occupancy API
-// over-reports it for the dynamic kernel (measured: 7 x 22.5 KB resident, an 8th starts a second
-// round), so the per-CU counts are fixed here and can be overridden for experiments.
-// (Running dyn and rom concurrently on two streams was measured and is slower than back to back.)
-// Tuning knobs (include/towr_amd.h, "Tuning knobs"): read from the environment ONLY in builds with -DTWR_TUNING_KNOBS
-// (make TUNING=1; what scripts/ab.py and the A/B notes of DESIGN 6 use); the default build has the measured optima compiled in.
-static int env_int(const char* name, int dflt) {
-#ifdef TWR_TUNING_KNOBS
-  const char* e = getenv(name);
-  if (!e) return dflt;
-  int v = atoi(e);
-  return v > 0 ? v : dflt;
-#else
-  (void)name;
-  return dflt;
-#endif
+// The instantiation lookups of the kernels launched by launch_eval (rom_kernel's: rom_kernel_fn).
+using DynFn = void (*)(const DynWork*, int, const double*, double*, double*, double*);
+using FusedFn = void (*)(const RomWork*, int, int, const DynWork*, int, int, const NodeWork*, const double*, double*, double*, double*);
+using PDynFn = void (*)(const PDynWork*, int, const double*, double*, double*);
+using PRomFn = void (*)(const RomPhaseWork*, int, const double*, double*, double*);
+using ChunkFn = void (*)(const FamWork*, int, int, const FamWork*, int, int, const FamWork*, int, int, const FamWork*, int, int,
+                         const double*, double*, double*);
+using ValuesFn = void (*)(const FlatWork*, int, int, const NodeWork*, int, const double*, double*);
+static ChunkFn node_chunk_kernel_fn(const LaunchStep& p) {
+  return pick<kStores>(p.store, [&](auto st) -> ChunkFn { return node_chunk_kernel<StoreG(st), StoreJ(st)>; });
 }
-static int n_chunks_of(const int n_fam[4]) { return n_fam[0] + n_fam[1] + n_fam[2] + n_fam[3]; }
-hipError_t launch_eval(int n_ee, int n_cu, const DynWork* dyn, int n_dyn, int dyn_map_chunks /* 2 or 4 */, const RomWork* rom, int n_rom,
-                       int rom_max_vals, const NodeWork* node, int n_node, int node_families /* 2: terrain + force only; 4 */,
-                       const FamWork* const fam[4], const int n_fam[4] /* chunk lists of node_chunk_kernel; all 0: none */,
-                       const PDynWork* pdyn, int n_pdyn, int pdyn_img_cap, const LocWork* ploc, int n_ploc, const RomPhaseWork* prom, int n_prom, int prom_img_cap, const double* x,
-                       double* g, double* jac, double* dump /* kDynDump doubles */, int flags, bool stream_nt /* non-temporal copy-out of
-                       dyn / rom (copy_out_fixed) */, const FlatWork* flat /* values-only work items in groups of four; nullptr: none */, int n_flat, int flat_max_x /* variables of the largest problem */, hipStream_t stream, hipEvent_t* ev /* 4 events or nullptr */) {
-#ifdef TWR_TUNING_KNOBS   // (read on every launch: an experiment can change them between evaluations of one process)
-  const int dyn_bpc = env_int("TWR_DYN_BPC", 8), rom_bpc = env_int("TWR_ROM_BPC", 4);
-#else
-  static const int dyn_bpc = env_int("TWR_DYN_BPC", 8), rom_bpc = env_int("TWR_ROM_BPC", 4);
-#endif
-  dim3 block(64);
+static ValuesFn eval_values_kernel_fn(const LaunchStep& p) {
+  return pick<kValuesNx>(p.xc, [&](auto nx) -> ValuesFn { return eval_values_kernel<nx>; });
+}
+static FusedFn fused_kernel_fn(const LaunchStep& p) {
+  return pick<kDynXc>(p.xc, [&](auto xc) {
+    return pick<kFusedNits>(p.nit, [&](auto nit) {
+      return pick<kStoresNT>(p.store, [&](auto st) -> FusedFn { return eval_fused_kernel<nit, StoreG(st), StoreJ(st), xc, StoreNT(st)>; });
+    });
+  });
+}
+static DynFn dyn_kernel_fn(const LaunchStep& p) {
+  return pick<kDynXc>(p.xc, [&](auto xc) {
+    return pick<kStoresNT>(p.store, [&](auto st) -> DynFn { return dyn_kernel<StoreG(st), StoreJ(st), xc, StoreNT(st)>; });
+  });
+}
+static PDynFn dyn_phase_kernel_fn(const LaunchStep& p) {
+  return pick<kDynPhaseNits>(p.nit, [&](auto nit) {
+    return pick<kStores>(p.store, [&](auto st) -> PDynFn { return dyn_phase_kernel<nit, StoreG(st), StoreJ(st)>; });
+  });
+}
+static PRomFn rom_phase_kernel_fn(const LaunchStep& p) {
+  return pick<kRomPhaseNits>(p.nit, [&](auto nit) {
+    return pick<kStores>(p.store, [&](auto st) -> PRomFn { return rom_phase_kernel<nit, StoreG(st), StoreJ(st)>; });
+  });
+}
+
+// Host side of one evaluation: the launches structure.cc PlanEval plans (policy, thresholds and the measurements behind
+// them are there), issued in order on one stream.  Every launch is issued; the first error is returned.
+hipError_t launch_eval(const EvalShape& s, const EvalBuffers& b, hipStream_t stream, hipEvent_t* ev) {
+  const EvalPlan plan = PlanEval(s);
   hipError_t st = hipSuccess;
-  if (n_ee < 1 || n_ee > 4) return hipErrorInvalidValue;
-  // The fused launch is used while the rom role needs at most TEN rounds of its residency (rom_bpc workgroups per CU x
-  // n_cu; round-3 re-tune on one box, ragged sweep, fused vs three launches: 320 / 400 / 512 candidates 75 / 98 / 126 vs
-  // 83 / 104 / 128 us per step, 768 / 1024: 187 / 250 vs 183 / 235; round 4: 512 candidates 115 vs 124, 768 / 1024 equal).
-  // Ten, not eight: the 512 candidates of a two-GPU shard of the C5 sweep are ~8500 rom slices (the enumeration is ragged:
-  // 16.6 slices per candidate), 8.3 rounds on the 256 CUs of an MI355X.  The thresholds are in units of the device's
-  // residency, not constants of one chip.
-  auto launch_nodes = [&]() {   // the node-based sets (terrain-*, force-*, splineacc-*, swing-*, ...): last launch of every path
-    const int n_chunks = n_fam[0] + n_fam[1] + n_fam[2] + n_fam[3];
-    if (n_chunks > 0) {
-      // persistent waves per CU for ALL families together, shared out by their chunk counts (by count, not by bytes: an iteration
-      // costs about the same whatever the family -- weighting the force chunks 1.5 x ... 3 x was 4-15 % slower)
-      static const int node_bpc = env_int("TWR_NODE_BPC", 16);
-      const int res = node_bpc * n_cu;
-      int gf[4];
-      for (int f = 0; f < 4; ++f) {
-        gf[f] = n_fam[f] == 0 ? 0 : (int)((long long)res * n_fam[f] / n_chunks);
-        if (n_fam[f] > 0 && gf[f] < 1) gf[f] = 1;
-        if (gf[f] > n_fam[f]) gf[f] = n_fam[f];
-      }
-  #define TWR_CHUNK_LAUNCH(WG, WJ)                                                                                                              \
-    st = twr_first(st, twr_launch(node_chunk_kernel<WG, WJ>, dim3(gf[0] + gf[1] + gf[2] + gf[3]), dim3(64), 0, stream, fam[0], n_fam[0], gf[0],   \
-                                  fam[1], n_fam[1], gf[1], fam[2], n_fam[2], gf[2], fam[3], n_fam[3], gf[3], x, g, jac))
-      if ((flags & 3) == 3) TWR_CHUNK_LAUNCH(true, true);
-      else if (flags & 2) TWR_CHUNK_LAUNCH(false, true);
-      else TWR_CHUNK_LAUNCH(true, false);
-  #undef TWR_CHUNK_LAUNCH
-    } else if (n_node > 0 && node_families == 2)
-      st = twr_first(st, twr_launch(node_kernel2, dim3(n_node), dim3(128), 0, stream, node, x, g, jac, flags));
-    else if (n_node > 0)
-      st = twr_first(st, twr_launch(node_kernel, dim3(n_node), dim3(256), 0, stream, node, x, g, jac, flags));
-  };
-  const int cap = rom_bpc * n_cu;
-  // Values only (no Jacobian), every problem with fixed timings and at most kFlatXCap variables: "dynamic" and "rangeofmotion-*"
-  // with one lane per time node (flat items), the node-based sets -- one launch (eval_values_kernel); with per-kernel events three.
-  if (!(flags & 2) && (flags & 1) && flat && n_flat > 0 && n_pdyn == 0 && n_prom == 0 && n_ploc == 0) {
-    const int nf = !ev && n_chunks_of(n_fam) == 0 ? node_families : 0;   // (large batches: the chunk kernel takes the node sets; with
-                                                                          // per-kernel events they are a launch of their own)
-    const size_t lds = flat_lds_bytes(flat_max_x);
-    const int x_bytes = (int)flat_x_bytes(flat_max_x);
-    const int nx = (flat_max_x + 64 * kFlatGroup - 1) / (64 * kFlatGroup);
-    const int n_groups = n_flat / kFlatGroup;
-    const dim3 vgrid(n_groups + (nf > 0 ? n_node : 0)), vblock(64 * kFlatGroup);
-    if (ev) (void)hipEventRecord(ev[0], stream);
-    if (nx <= 3) st = twr_first(st, twr_launch(eval_values_kernel<3>, vgrid, vblock, lds, stream, flat, n_groups, x_bytes, node, nf, x, g));
-    else if (nx <= 5) st = twr_first(st, twr_launch(eval_values_kernel<5>, vgrid, vblock, lds, stream, flat, n_groups, x_bytes, node, nf, x, g));
-    else st = twr_first(st, twr_launch(eval_values_kernel<8>, vgrid, vblock, lds, stream, flat, n_groups, x_bytes, node, nf, x, g));
-    static_assert(kFlatXCap <= 8 * 64 * kFlatGroup, "largest instantiation of the values-only kernel");
-    if (ev) {   // (the two flat families are one launch: the second interval is empty)
-      (void)hipEventRecord(ev[1], stream);
-      (void)hipEventRecord(ev[2], stream);
+  for (int i = 0; i < plan.n; ++i) {
+    const LaunchStep& p = plan.step[i];
+    const dim3 grid(p.grid), block(p.block);
+    const int* a = p.arg;
+    switch (p.kernel) {
+      case Launch::kEvent: (void)hipEventRecord(ev[a[0]], stream); break;
+      case Launch::kDyn: st = twr_first(st, twr_launch(dyn_kernel_fn(p), grid, block, p.lds, stream, b.dyn, s.dyn, b.x, b.g, b.jac, b.dump)); break;
+      case Launch::kRom: st = twr_first(st, twr_launch(rom_kernel_fn(p), grid, block, p.lds, stream, b.rom, s.rom, b.x, b.g, b.jac)); break;
+      case Launch::kFused:
+        st = twr_first(st, twr_launch(fused_kernel_fn(p), grid, block, p.lds, stream, b.rom, s.rom, a[0], b.dyn, s.dyn, a[1], b.node, b.x, b.g,
+                                      b.jac, b.dump));
+        break;
+      case Launch::kLocate: st = twr_first(st, twr_launch(phase_locate_kernel, grid, block, p.lds, stream, b.ploc, b.x)); break;
+      case Launch::kDynPhase: st = twr_first(st, twr_launch(dyn_phase_kernel_fn(p), grid, block, p.lds, stream, b.pdyn, s.pdyn, b.x, b.g, b.jac)); break;
+      case Launch::kRomPhase: st = twr_first(st, twr_launch(rom_phase_kernel_fn(p), grid, block, p.lds, stream, b.prom, s.prom, b.x, b.g, b.jac)); break;
+      case Launch::kNode: st = twr_first(st, twr_launch(node_kernel, grid, block, p.lds, stream, b.node, b.x, b.g, b.jac, s.flags)); break;
+      case Launch::kNode2: st = twr_first(st, twr_launch(node_kernel2, grid, block, p.lds, stream, b.node, b.x, b.g, b.jac, s.flags)); break;
+      case Launch::kChunk:
+        st = twr_first(st, twr_launch(node_chunk_kernel_fn(p), grid, block, p.lds, stream, b.fam[0], s.fam[0], a[0], b.fam[1], s.fam[1], a[1],
+                                      b.fam[2], s.fam[2], a[2], b.fam[3], s.fam[3], a[3], b.x, b.g, b.jac));
+        break;
+      case Launch::kValues:
+        st = twr_first(st, twr_launch(eval_values_kernel_fn(p), grid, block, p.lds, stream, b.flat, a[0], a[2], b.node, a[1], b.x, b.g));
+        break;
     }
-    if (nf == 0) launch_nodes();
-    if (ev) (void)hipEventRecord(ev[3], stream);
-    return st;
   }
-  // With non-temporal stores (sweep-like batches) the fused launch stays ahead for longer -- 768 / 896 / 1024 candidates of the
-  // C5 sweep (12.7 / 14.9 / 17 thousand rom slices): 160-165 / 179 / 210 us as three launches, 148 / 166 / 202 us fused -- twenty
-  // rounds there (the enumeration ends at 1040 candidates; nothing larger was measured).
-  // (round 5, with the roles always co-resident: batches that share one structure, plain stores, 640 / 1024 / 2048 problems
-  // 129.5 / 193.5 / 365 us as three launches, 120 / 188 / 376 us fused -- twenty rounds for both store policies)
-  const int fused_max = env_int("TWR_FUSED_MAX_ROM", 20 * cap);
-  if (!ev && n_pdyn == 0 && n_prom == 0 && n_rom > 0 && n_dyn > 0 && n_rom <= fused_max) {
-    int g_rom = n_rom < cap ? n_rom : cap, g_dyn = (n_dyn + 1) / 2 < cap ? (n_dyn + 1) / 2 : cap;
-    // When the two persistent roles do not fit the CUs together, the blocks of the later role only start as the earlier
-    // ones retire, i.e. the roles run one after the other.  For up to 2560 rom slices (160 quadruped candidates of
-    // K = 200) it pays to give each role half of the residency instead, so that the latency-bound dyn waves and the
-    // store-bound rom waves overlap from the start (64 / 128 / 160 candidates: 18.7 / 30.1 / 35.2 -> 17.5 / 27.8 /
-    // 31.6 us per step; from 200 candidates on the extra rounds cost more than the overlap gains).
-    // TWR_FUSED_SPLIT = eighths of the residency given to rom (experiments; 8 = never split).
-    static const int split_env = env_int("TWR_FUSED_SPLIT", 0);
-    // (round 3: five eighths for rom up to 3200 slices -- 128 / 160 / 200 candidates 27.5 / 33.5 / 40.5 us against 27.7 / 33.9 /
-    // 44.0 us with the round-2 rule "half each up to 2560"; from 256 candidates on unsplit was as good or better THEN.)
-    // Round 5, re-measured with the round-4 kernels (split tables, nt stores; scripts/r05_split_exp.sh, one box, ragged
-    // sweep, us per step unsplit -> split): 256 candidates 53.8 -> 47.2 (five eighths; 48.6 at four), 320: 69.3 -> 62.5 (four),
-    // 384: 81.7 -> 74.5, 512: 100.9 -> 92.6, 768: 155.8 -> 145.9, 1024: 206.0 -> 194.1; six eighths loses everywhere.  The two
-    // roles are ALWAYS co-resident now: the latency-bound dyn waves fill the holes of the store-bound rom stream.
-    const int split = split_env > 0 ? split_env : (8 * n_rom <= 34 * cap ? 5 : 4);   // (4352 slices on 256 CUs)
-    if (split < 8 && g_rom + g_dyn > cap) {
-      const int r = cap * split / 8, d = cap - r;
-      if (g_rom > r) g_rom = r;
-      if (g_dyn > d) g_dyn = d;
-    }
-    {   // experiments (make TUNING=1): explicit grids of the two roles
-      static const int e_rom = env_int("TWR_FUSED_GROM", 0), e_dyn = env_int("TWR_FUSED_GDYN", 0);
-      if (e_rom > 0) g_rom = e_rom < n_rom ? e_rom : n_rom;
-      if (e_dyn > 0) g_dyn = e_dyn < (n_dyn + 1) / 2 ? e_dyn : (n_dyn + 1) / 2;
-    }
-    if (g_dyn >= 8) g_dyn &= ~7;   // (the XCD-aware slice mapping of the dyn role, eval_fused_kernel)
-    const dim3 fgrid(g_rom + g_dyn + 2 * n_node);
-    const int need = (rom_max_vals + 1 + 2 + 127) / 128;   // copy-out length of the rom role (see launch_rom_kernel)
-#define TWR_FUSED_ARGS fgrid, dim3(128), 0, stream, rom, n_rom, g_rom, dyn, n_dyn, g_dyn, node, x, g, jac, dump
-#define TWR_FUSED_LAUNCH(NIT, XC)                                                                              \
-  {                                                                                                            \
-    if ((flags & 3) == 3 && stream_nt) return twr_launch(eval_fused_kernel<NIT, true, true, XC, true>, TWR_FUSED_ARGS);    \
-    if ((flags & 3) == 3) return twr_launch(eval_fused_kernel<NIT, true, true, XC, false>, TWR_FUSED_ARGS);                \
-    if ((flags & 2) && stream_nt) return twr_launch(eval_fused_kernel<NIT, false, true, XC, true>, TWR_FUSED_ARGS);        \
-    if (flags & 2) return twr_launch(eval_fused_kernel<NIT, false, true, XC, false>, TWR_FUSED_ARGS);                      \
-    return twr_launch(eval_fused_kernel<NIT, true, false, XC, false>, TWR_FUSED_ARGS);                                     \
-  }
-    if (dyn_map_chunks == 2) {
-      if (need <= 34) TWR_FUSED_LAUNCH(34, 2)
-      TWR_FUSED_LAUNCH(kRomNitMax, 2)
-    }
-    if (need <= 34) TWR_FUSED_LAUNCH(34, 4)
-    TWR_FUSED_LAUNCH(kRomNitMax, 4)
-#undef TWR_FUSED_LAUNCH
-#undef TWR_FUSED_ARGS
-  }
-  if (ev) (void)hipEventRecord(ev[0], stream);
-  if (n_dyn > 0) {
-    const int res = dyn_bpc * n_cu;
-    dim3 grid(n_dyn < res ? n_dyn : res);
-#define TWR_DYN_ARGS grid, block, 0, stream, dyn, n_dyn, x, g, jac, dump
-#define TWR_DYN_LAUNCH(XC)                                                                                                   \
-  {                                                                                                                           \
-    if ((flags & 3) == 3 && stream_nt) st = twr_first(st, twr_launch(dyn_kernel<true, true, XC, true>, TWR_DYN_ARGS));        \
-    else if ((flags & 3) == 3) st = twr_first(st, twr_launch(dyn_kernel<true, true, XC, false>, TWR_DYN_ARGS));               \
-    else if ((flags & 2) && stream_nt) st = twr_first(st, twr_launch(dyn_kernel<false, true, XC, true>, TWR_DYN_ARGS));       \
-    else if (flags & 2) st = twr_first(st, twr_launch(dyn_kernel<false, true, XC, false>, TWR_DYN_ARGS));                     \
-    else st = twr_first(st, twr_launch(dyn_kernel<true, false, XC, false>, TWR_DYN_ARGS));                                    \
-  }
-    if (dyn_map_chunks == 2) TWR_DYN_LAUNCH(2) else TWR_DYN_LAUNCH(4)
-#undef TWR_DYN_LAUNCH
-#undef TWR_DYN_ARGS
-  }
-  // optimised-timings problems: the pre-pass (segment lookup -> records), then the persistent kernels
-  if (n_ploc > 0) st = twr_first(st, twr_launch(phase_locate_kernel, dim3(n_ploc), dim3(kLocateThreads), 0, stream, ploc, x));
-  if (n_pdyn > 0) {
-    // LDS per workgroup: the image of one pass; residency follows from it
-    const size_t lds = sizeof(double) * (size_t)((pdyn_img_cap + 1) & ~1);
-    static const int pdyn_bpc_env = env_int("TWR_PDYN_BPC", 0);
-    int bpc = (int)((size_t)(160 * 1024) / lds);
-    if (bpc > 4) bpc = 4;   // one wave per SIMD (the kernel uses the AGPR half of the register file as well)
-    if (bpc < 1) bpc = 1;
-    if (pdyn_bpc_env > 0) bpc = pdyn_bpc_env;
-    const int res = bpc * n_cu;
-    dim3 grid(n_pdyn < res ? n_pdyn : res);
-    const bool wg = flags & 1, wj = flags & 2;
-#define TWR_PDYN_LAUNCH(NIT, WG, WJ) st = twr_first(st, twr_launch(dyn_phase_kernel<NIT, WG, WJ>, grid, block, lds, stream, pdyn, n_pdyn, x, g, jac))
-    if (pdyn_img_cap <= 40 * 128) {
-      if (wg && wj) TWR_PDYN_LAUNCH(40, true, true);
-      else if (wj) TWR_PDYN_LAUNCH(40, false, true);
-      else TWR_PDYN_LAUNCH(40, true, false);
-    } else {
-      if (wg && wj) TWR_PDYN_LAUNCH(0, true, true);
-      else if (wj) TWR_PDYN_LAUNCH(0, false, true);
-      else TWR_PDYN_LAUNCH(0, true, false);
-    }
-#undef TWR_PDYN_LAUNCH
-  }
-  if (ev) (void)hipEventRecord(ev[1], stream);
-  if (n_prom > 0) {
-    const size_t lds = sizeof(double) * (size_t)((prom_img_cap + 1) & ~1);
-    static const int prom_bpc_env = env_int("TWR_PROM_BPC", 0);
-    int bpc = (int)((size_t)(160 * 1024) / lds);
-    if (bpc > 8) bpc = 8;
-    if (bpc < 1) bpc = 1;
-    if (prom_bpc_env > 0) bpc = prom_bpc_env;
-    const int res = bpc * n_cu;
-    dim3 grid(n_prom < res ? n_prom : res);
-    const bool wg = flags & 1, wj = flags & 2;
-#define TWR_PROM_LAUNCH(NIT, WG, WJ) st = twr_first(st, twr_launch(rom_phase_kernel<NIT, WG, WJ>, grid, block, lds, stream, prom, n_prom, x, g, jac))
-#define TWR_PROM_FLAGS(NIT)                           \
-  {                                                   \
-    if (wg && wj) TWR_PROM_LAUNCH(NIT, true, true);   \
-    else if (wj) TWR_PROM_LAUNCH(NIT, false, true);   \
-    else TWR_PROM_LAUNCH(NIT, true, false);           \
-  }
-    if (prom_img_cap <= 24 * 128) TWR_PROM_FLAGS(24)
-    else if (prom_img_cap <= 32 * 128) TWR_PROM_FLAGS(32)
-    else if (prom_img_cap <= 40 * 128) TWR_PROM_FLAGS(40)
-    else {
-      TWR_PROM_FLAGS(0)
-    }
-#undef TWR_PROM_FLAGS
-#undef TWR_PROM_LAUNCH
-  }
-  if (n_rom > 0) {
-    const int res = rom_bpc * n_cu;
-    dim3 grid(n_rom < res ? n_rom : res);
-    st = twr_first(st, launch_rom_kernel((int)grid.x, stream, rom, n_rom, rom_max_vals, x, g, jac, flags, stream_nt));
-  }
-  if (ev) (void)hipEventRecord(ev[2], stream);
-  launch_nodes();
-  if (ev) (void)hipEventRecord(ev[3], stream);
   return st;
 }
 
@@ -3660,23 +3497,16 @@ hipError_t launch_eval(int n_ee, int n_cu, const DynWork* dyn, int n_dyn, int dy
 // is created (on its device, always to the whole 160 KB of a CU), not at launch: an evaluation must stay capturable
 // in a hipGraph.
 hipError_t prepare_phase_kernels(int pdyn_img_cap, int prom_img_cap) {
-  const int whole = 160 * 1024;
   hipError_t st = hipSuccess;
-  auto raise = [&](const void* fn) { st = twr_first(st, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, whole)); };
-  if ((size_t)pdyn_img_cap * sizeof(double) > 64 * 1024) {
-    raise(reinterpret_cast<const void*>(dyn_phase_kernel<0, true, true>));
-    raise(reinterpret_cast<const void*>(dyn_phase_kernel<0, false, true>));
-    raise(reinterpret_cast<const void*>(dyn_phase_kernel<0, true, false>));
-  }
-  if ((size_t)prom_img_cap * sizeof(double) > 64 * 1024) {
-    raise(reinterpret_cast<const void*>(rom_phase_kernel<0, true, true>));
-    raise(reinterpret_cast<const void*>(rom_phase_kernel<0, false, true>));
-    raise(reinterpret_cast<const void*>(rom_phase_kernel<0, true, false>));
+  auto raise = [&](const void* fn) { st = twr_first(st, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); };
+  LaunchStep p;   // (nit 0: the run-time length)
+  for (int store : kStores) {
+    p.store = store;
+    if (pdyn_img_cap * sizeof(double) > 64 * 1024) raise(reinterpret_cast<const void*>(dyn_phase_kernel_fn(p)));
+    if (prom_img_cap * sizeof(double) > 64 * 1024) raise(reinterpret_cast<const void*>(rom_phase_kernel_fn(p)));
   }
   return st;
 }
-int dyn_dump_doubles() { return kDynImage + 2 + 96; }
-int node_force_chunk() { return kForceChunk; }
 #endif  // !TWR_TU_ROM
 
 }  // namespace twr

@@ -1,0 +1,39 @@
+// Host launchers of the kernels (kernels.hip, rom_tu.hip), called by the C ABI (capi.cc).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "structure.h"
+
+namespace twr {
+
+struct EvalBuffers {   // device memory of one evaluation: the batch's work lists and the caller's x / g / jac
+  const DynWork* dyn;
+  const RomWork* rom;
+  const NodeWork* node;
+  const FlatWork* flat;
+  const FamWork* fam[4];
+  const PDynWork* pdyn;
+  const LocWork* ploc;
+  const RomPhaseWork* prom;
+  const double* x;
+  double* g;
+  double* jac;
+  double* dump;   // kDynDump doubles
+};
+// Issues the launches PlanEval plans for `shape` (ev: four events when shape.events); returns the first error.
+hipError_t launch_eval(const EvalShape& shape, const EvalBuffers& buf, hipStream_t stream, hipEvent_t* ev);
+hipError_t prepare_phase_kernels(int pdyn_img_cap, int prom_img_cap);
+hipError_t launch_check(int n_problems, const int64_t* g_off, const int64_t* j_off, const double* g, const double* jac,
+                        int32_t* status, int flags, hipStream_t stream);
+hipError_t launch_score(const NodeWork* work, int n_problems, const double* g, double* scores, hipStream_t stream);
+int best_max_blocks();
+hipError_t launch_best(const double* scores, int n, unsigned families, double* partial, unsigned* counter, double* best, double index_offset,
+                       hipStream_t stream);
+hipError_t launch_contact_plan(const NodeWork* work, int n_problems, const double* x, double* out, int32_t* counts, double dt,
+                               double time_horizon, int n_samples_max, int max_steps, hipStream_t stream);
+hipError_t launch_planes(const double* plan, const int32_t* counts, const double* poly_xy, const int32_t* poly_start, int n_polys,
+                         int n_problems, int max_steps, int n_ee, int32_t* plane_index, hipStream_t stream);
+hipError_t launch_sample(const SampleWork* work, int n_work, const double* x, double* out, double dt, const double* times,
+                         hipStream_t stream);
+
+}  // namespace twr

@@ -163,7 +163,7 @@ inline bool StreamNonTemporal(int structures_used, int n_problems, int64_t outpu
 // Everything twr_batch_create uploads besides the structures' tables, planned on the host (no HIP): the offsets of every
 // problem, every work list in launch order and the batch's policy decisions.  blob[i] is the device address of structure i's
 // blob (BlobOffsets: one arena, every blob on a 256-byte line); the device enters as its CU count, its memory-side cache and
-// the chunk length of node_chunk_kernel's force family (kernels.hip kForceChunk).
+// the chunk length of node_chunk_kernel's force family (device_tables.h kForceChunk).
 struct BatchPlan {
   std::vector<int64_t> x_off, g_off, j_off;   // n_problems + 1
   // what twr_batch_sample needs of every problem (the structures need not outlive the batch)
@@ -196,6 +196,58 @@ struct BatchPlan {
 std::vector<size_t> BlobOffsets(const std::vector<const Structure*>& structs);   // n + 1 arena offsets
 BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem,
                     const std::vector<uint64_t>& blob, int n_cu, int64_t cache_bytes, int force_chunk);
+
+// The launches of one evaluation (twr_batch_eval), planned on the host (no HIP) from the batch's list counts and policy:
+// which kernels, which instantiation of each, their grids and LDS, and where the four profiling events go.
+// Tuning knobs (include/towr_amd.h): 0 leaves the decision to the rules of PlanEval.
+struct LaunchTuning {
+  int dyn_bpc = 8, rom_bpc = 4;   // TWR_DYN_BPC, TWR_ROM_BPC: persistent workgroups per CU
+  int node_bpc = 16;              // TWR_NODE_BPC: node_chunk_kernel's waves per CU, all families together
+  int pdyn_bpc = 0, prom_bpc = 0; // TWR_PDYN_BPC, TWR_PROM_BPC
+  int fused_max_rom = 0;          // TWR_FUSED_MAX_ROM
+  int fused_split = 0;            // TWR_FUSED_SPLIT
+  int fused_grom = 0, fused_gdyn = 0;   // TWR_FUSED_GROM, TWR_FUSED_GDYN
+};
+struct EvalShape {
+  int n_cu = 0;
+  int dyn = 0, rom = 0, node = 0, flat = 0, fam[4] = {0, 0, 0, 0}, pdyn = 0, ploc = 0, prom = 0;   // work items per list
+  // what PlanBatch decided for the batch (BatchPlan)
+  int rom_max_vals = 0, flat_max_x = 0, dyn_map_chunks = 2, node_families = 4, pdyn_img_cap = 0, prom_img_cap = 0;
+  bool stream_nt = false;
+  int flags = 0;                  // TWR_EVAL_VALUES | TWR_EVAL_JACOBIAN
+  bool events = false;            // per-kernel profiling events are recorded
+  LaunchTuning tuning;
+};
+enum class Launch { kEvent, kDyn, kRom, kFused, kLocate, kDynPhase, kRomPhase, kNode, kNode2, kChunk, kValues };
+// Outputs a launch writes: constraint values (G), Jacobian (J), and non-temporal copy-out stores (NT, only with J).
+enum StoreVariant { kStoreG, kStoreJ, kStoreGJ, kStoreJNT, kStoreGJNT };
+constexpr bool StoreG(int s) { return s == kStoreG || s == kStoreGJ || s == kStoreGJNT; }
+constexpr bool StoreJ(int s) { return s != kStoreG; }
+constexpr bool StoreNT(int s) { return s == kStoreJNT || s == kStoreGJNT; }
+// The instantiations that exist: the key lists of the kernels' lookups (kernels.hip, rom_tu.hip), in the order the code
+// objects lay them out.  NIT = store instructions of a copy-out (0: run-time length), XC = 64-entry chunks of dyn_kernel's
+// staging maps, NX = doubles of x per thread of eval_values_kernel.
+constexpr int kStoresNT[] = {kStoreGJNT, kStoreGJ, kStoreJNT, kStoreJ, kStoreG};   // dyn, rom, fused
+constexpr int kStores[] = {kStoreGJ, kStoreJ, kStoreG};                            // phase kernels, chunks
+constexpr int kDynXc[] = {2, 4};                                                   // dyn, fused
+constexpr int kRomNits[] = {26, 30, 34, kRomNitMax};
+constexpr int kFusedNits[] = {34, kRomNitMax};
+constexpr int kDynPhaseNits[] = {40, 0};
+constexpr int kRomPhaseNits[] = {24, 32, 40, 0};
+constexpr int kValuesNx[] = {3, 5, 8};
+struct LaunchStep {
+  Launch kernel = Launch::kEvent;
+  int store = kStoreG, nit = 0, xc = 0;   // instantiation (xc: NX of eval_values_kernel)
+  int grid = 0, block = 0, lds = 0;       // lds: dynamic LDS bytes
+  // kEvent: the event; kFused: rom and dyn blocks; kChunk: blocks per family; kValues: groups, node families, x bytes
+  int arg[4] = {0, 0, 0, 0};
+};
+struct EvalPlan {
+  static constexpr int kMaxSteps = 10;
+  int n = 0;
+  LaunchStep step[kMaxSteps];
+};
+EvalPlan PlanEval(const EvalShape& shape);
 // fpowr GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53): samples while t <= t_total + 1e-5, t accumulated
 int SampleCount(double t_total, double dt);
 void GaitCombo(int n_ee, int combo, double t_total, double swing_scale, twr_schedule* out);
