@@ -276,7 +276,8 @@ int twr_batch_layout(const twr_batch* b, int64_t* x_off, int64_t* g_off, int64_t
  * (Values only: a batch in which EVERY problem has fixed timings and at most 2046 variables takes the lane-per-time-node
  * kernel, see twr_structure_values_items; one problem that cannot keeps the whole batch on the values-only instantiation of
  * the Jacobian kernels.  The two agree to rounding, so the shards of one sweep -- which all take the same path -- compare
- * bit for bit, a batch of another composition to rounding.) */
+ * bit for bit, a batch of another composition to rounding.)  twr_batch_eval_scores without g: inf-norms bit-identical to
+ * twr_batch_score over this path's g, 1-norms to rounding (<= 1e-12 relative), see there. */
 int twr_batch_eval(twr_batch* b, const double* d_x, double* d_g, double* d_jac, int flags, void* hip_stream);
 /* Failure detection (the reference only has Release-mode-silent asserts, spline.cc:52,65): after an evaluation with
  * TWR_EVAL_CHECK, h_status[p] has bit 0 set if a constraint value of problem p is NaN/Inf and bit 1 if a Jacobian
@@ -331,6 +332,32 @@ int twr_batch_best(twr_batch* b, const double* d_scores, int32_t n_candidates, u
  * 128 bytes per candidate.  Asynchronous on hip_stream, capturable; shares the scratch of twr_batch_best. */
 int twr_batch_score_best(twr_batch* b, const double* d_g, double* d_scores /* 16 * n_problems */, uint32_t families,
                          int64_t index_offset, double* d_best /* 2 */, void* hip_stream);
+/* A planner step without g: the values-only evaluation reduced to twr_batch_score's table as it is computed.
+ * twr_batch_scores_without_g: 1 if the batch scores without g -- every problem takes the values-only path (fixed timings,
+ * at most 2046 variables; see twr_batch_eval) --, 0 if the scoring calls need d_g.
+ * twr_batch_eval_scores: d_scores[16 p + 2 f] = inf-norm, [16 p + 2 f + 1] = 1-norm of the bound violation of family f,
+ * exactly twr_batch_score's table (bounds of ConstraintSet::GetBounds, twr_structure_bounds; the constraint files
+ * twr_batch_score cites): 0 for families the structure does not build, NaN if a constraint value of the family is NaN,
+ * all zeros for a structure without rows.
+ *   - scores without g (twr_batch_scores_without_g == 1): d_g may be NULL; if it is not, it is left untouched -- no g is
+ *     written anywhere.  Two launches: the values-only kernel's scoring instantiation (every wave reduces its rows to a
+ *     partial record in a scratch slab of the batch) and a fold of each problem's records in a fixed order.
+ *   - otherwise (optimised timings, a batch mixing them with fixed timings, problems of more than 2046 variables): exactly
+ *     twr_batch_eval(TWR_EVAL_VALUES) into d_g followed by twr_batch_score, bit for bit; d_g NULL is TWR_ERR_INVALID.
+ * twr_batch_eval_score_best: the same, then this shard's decision as twr_batch_score_best (families mask, index_offset,
+ * d_best = {index_offset + index, total}); it shares twr_batch_best's scratch.
+ * Both are asynchronous and stream-ordered on hip_stream, capturable in a hipGraph, and count as an evaluation of the batch
+ * (at most one in flight, see twr_batch_eval; _score_best: one call per batch in flight, as twr_batch_best).  Device scope
+ * and errors as twr_batch_eval.  They record no per-kernel profiling events (twr_batch_profile_begin).
+ * REPRODUCIBILITY (without g): a given x gives bit-identical scores wherever the problem sits in the batch and on every call.
+ * The inf-norms are bit-identical to twr_batch_score over a TWR_EVAL_VALUES g of the same batch (same arithmetic, same
+ * bounds); the 1-norms are summed in the scoring kernel's own fixed order (per lane, a fixed xor tree over the wave, then
+ * the problem's partial records in planned order) and agree with twr_batch_score to rounding (<= 1e-12 relative). */
+int twr_batch_scores_without_g(const twr_batch* b);
+int twr_batch_eval_scores(twr_batch* b, const double* d_x, double* d_g /* may be NULL without g */, double* d_scores /* 16 * n_problems */,
+                          void* hip_stream);
+int twr_batch_eval_score_best(twr_batch* b, const double* d_x, double* d_g, double* d_scores /* 16 * n_problems */, uint32_t families,
+                              int64_t index_offset, double* d_best /* 2 */, void* hip_stream);
 /* fpowr::ExtractFootstepPlan (fpowr/include/fpowr/footstep_plan_extractor.h:69-133) for every problem of the batch,
  * up to the nearest-plane lookup (twr_batch_contact_planes below): the solution x sampled every dt
  * (GetTrajectory, :19-53), a footstep state at the first sample and wherever HasEndEffectorContactChanged (:55-67)

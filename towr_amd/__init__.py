@@ -144,6 +144,10 @@ def lib():
         L.twr_batch_score.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.twr_batch_best.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_void_p]
         L.twr_batch_score_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p]
+        L.twr_batch_scores_without_g.argtypes = [C.c_void_p]
+        L.twr_batch_eval_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_batch_eval_score_best.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p,
+                                                C.c_void_p]
         L.twr_structure_contact_steps_max.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         L.twr_structure_values_items.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
         L.twr_planes_create.argtypes = [_dp, _dp, C.POINTER(C.c_int32), C.c_int32, C.c_int, C.POINTER(C.c_void_p)]
@@ -484,6 +488,26 @@ class Batch:
             mask |= 1 << int(f)
         _check(lib().twr_batch_score_best(self._h, C.c_void_p(d_g), C.c_void_p(d_scores), mask, int(index_offset), C.c_void_p(d_best),
                                           C.c_void_p(stream)))
+
+    @property
+    def scores_without_g(self):
+        """True when eval_scores_device / eval_score_best_device write no g (twr_batch_scores_without_g): every problem takes
+        the values-only path.  Otherwise they need d_g and are eval_device(EVAL_VALUES) + score_device."""
+        return bool(lib().twr_batch_scores_without_g(self._h))
+
+    def eval_scores_device(self, d_x, d_scores, d_g=0, stream=0):
+        """twr_batch_eval_scores: the score table of score_device straight from x (device pointers); d_g may be 0 when
+        scores_without_g, and is left untouched then."""
+        _check(lib().twr_batch_eval_scores(self._h, C.c_void_p(d_x), C.c_void_p(d_g), C.c_void_p(d_scores), C.c_void_p(stream)))
+
+    def eval_score_best_device(self, d_x, d_scores, d_best, families=(0, 1, 3, 4), index_offset=0, d_g=0, stream=0):
+        """twr_batch_eval_score_best: eval_scores_device + this batch's decision as score_best_device (d_best = [index_offset +
+        index, total])."""
+        mask = 0
+        for f in families:
+            mask |= 1 << int(f)
+        _check(lib().twr_batch_eval_score_best(self._h, C.c_void_p(d_x), C.c_void_p(d_g), C.c_void_p(d_scores), mask, int(index_offset),
+                                               C.c_void_p(d_best), C.c_void_p(stream)))
 
     def best_device(self, d_scores, n_candidates, d_best, families=(0, 1, 3, 4), stream=0):
         """twr_batch_best: device arg-min of the summed inf-norm violations of `families` (indices into FAMILIES) over a

@@ -105,6 +105,9 @@ struct twr_batch {
   DevPtr<int32_t> status;                    // per-problem non-finite flags of the last checked evaluation
   DevPtr<double> dump;                       // where dyn_kernel's first (empty) copy-out of every workgroup goes
   DevPtr<double> best;                       // twr_batch_best: per-block results (2 doubles each) + the block counter behind them
+  DevList<uint64_t> score_blob;              // twr_batch_eval_scores without g (plan.score_fused): BatchPlan::Lists score_*
+  DevList<int32_t> score_first, score_slot;
+  DevPtr<double> score_slab;                 // the scoring launch's partial records (kScorePartial doubles each)
   DevList<twr::SampleWork> swork;            // work list of the last twr_batch_sample call (cached per dt / stride)
   double swork_dt = 0.0;
   int64_t swork_stride = -1;
@@ -549,6 +552,12 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
     b->joff = upload(b->plan.j_off);
     b->dump = dev_zeros<double>(twr::kDynDump);
     b->best = dev_zeros<double>(2 * (size_t)twr::best_max_blocks() + 1);
+    if (b->plan.score_fused) {
+      if (!L.score_blob.empty()) b->score_blob = upload(L.score_blob);
+      b->score_first = upload(L.score_first);
+      b->score_slot = upload(L.score_slot);
+      b->score_slab = dev_alloc<double>(sizeof(double) * twr::kScorePartial * (size_t)b->plan.score_slab);
+    }
     b->status = dev_zeros<int32_t>(n_problems);
     if (!L.ploc.empty()) {
       b->precs = dev_alloc<void>(b->plan.records_bytes);
@@ -920,6 +929,56 @@ int twr_batch_score_best(twr_batch* b, const double* d_g, double* d_scores, uint
     e = twr::launch_best(d_scores, b->n_problems, families, b->best.get(), counter, d_best, (double)index_offset, static_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   return TWR_OK;
+}
+
+int twr_batch_scores_without_g(const twr_batch* b) { return b && b->plan.score_fused ? 1 : 0; }
+
+namespace {
+// twr_batch_eval_scores / twr_batch_eval_score_best: the launches PlanEval plans for a scoring request (kEvalScores)
+int eval_scores(twr_batch* b, const double* d_x, double* d_g, double* d_scores, bool best, uint32_t families, int64_t index_offset,
+                double* d_best, void* hip_stream) {
+  if (!b || !d_x || !d_scores || (best && !d_best)) return fail(TWR_ERR_INVALID, "null argument");
+  if (best && (!(families & 0xffu) || (families & ~0xffu))) return fail(TWR_ERR_INVALID, "families must be a non-empty mask of the eight TWR_SET_* bits");
+  if (!b->plan.score_fused && !d_g)
+    return fail(TWR_ERR_INVALID, "this batch scores through g (twr_batch_scores_without_g == 0): d_g is required");
+  DeviceScope on(b->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  const twr::BatchPlan& P = b->plan;
+  twr::EvalShape s;
+  s.n_cu = b->n_cu;
+  s.dyn = b->dyn.n; s.rom = b->rom.n; s.node = b->node.n; s.flat = b->flat.n; s.pdyn = b->pdyn.n; s.ploc = b->ploc.n; s.prom = b->prom.n;
+  for (int f = 0; f < 4; ++f) s.fam[f] = b->fam[f].n;
+  s.rom_max_vals = P.rom_max_vals; s.flat_max_x = P.flat_max_x; s.dyn_map_chunks = P.dyn_map_chunks; s.node_families = P.node_families;
+  s.pdyn_img_cap = P.pdyn_img_cap; s.prom_img_cap = P.prom_img_cap; s.stream_nt = P.stream_nt;
+  s.flags = twr::kEvalScores | (best ? twr::kEvalBest : 0);
+  s.score_fused = P.score_fused;
+  s.tuning = tuning_knobs();
+  twr::EvalBuffers buf{b->dyn.d.get(), b->rom.d.get(), b->node.d.get(), b->flat.d.get(),
+                       {b->fam[0].d.get(), b->fam[1].d.get(), b->fam[2].d.get(), b->fam[3].d.get()},
+                       b->pdyn.d.get(), b->ploc.d.get(), b->prom.d.get(), d_x, P.score_fused ? nullptr : d_g, nullptr, b->dump.get()};
+  buf.score_blob = b->score_blob.d.get();
+  buf.score_first = b->score_first.d.get();
+  buf.score_slot = b->score_slot.d.get();
+  buf.slab = b->score_slab.get();
+  buf.scores = d_scores;
+  buf.families = families;
+  buf.index_offset = (double)index_offset;
+  buf.best_partial = b->best.get();
+  buf.best_counter = reinterpret_cast<unsigned*>(b->best.get() + 2 * (size_t)twr::best_max_blocks());
+  buf.best = d_best;
+  hipError_t e = twr::launch_eval(s, buf, static_cast<hipStream_t>(hip_stream), nullptr);
+  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return TWR_OK;
+}
+}  // namespace
+
+int twr_batch_eval_scores(twr_batch* b, const double* d_x, double* d_g, double* d_scores, void* hip_stream) {
+  return eval_scores(b, d_x, d_g, d_scores, false, 0, 0, nullptr, hip_stream);
+}
+
+int twr_batch_eval_score_best(twr_batch* b, const double* d_x, double* d_g, double* d_scores, uint32_t families, int64_t index_offset,
+                              double* d_best, void* hip_stream) {
+  return eval_scores(b, d_x, d_g, d_scores, true, families, index_offset, d_best, hip_stream);
 }
 
 int twr_batch_best(twr_batch* b, const double* d_scores, int32_t n_candidates, uint32_t families, double* d_best, void* hip_stream) {

@@ -538,5 +538,7 @@ constexpr int kFlatWaveLds = kFlatPolyLds + 192 * 8;      // bytes of a wave's o
 // eval_values_kernel's dynamic LDS: [ zero pair | x ] [ per wave: kFlatWaveLds ]
 inline int flat_x_bytes(int max_n_x) { return 8 * (2 + ((max_n_x + 1) & ~1)); }
 inline int flat_lds_bytes(int max_n_x) { return flat_x_bytes(max_n_x) + kFlatGroup * kFlatWaveLds; }
+constexpr int kScorePartial = 16;                         // eval_scores_kernel: doubles of a wave's partial record (as a score row)
+constexpr int kFoldThreads = 16;                          // score_fold_kernel: threads per problem (one per column of its row)
 
 }  // namespace twr

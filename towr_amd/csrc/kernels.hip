@@ -1257,11 +1257,65 @@ RomFn rom_kernel_fn(const LaunchStep& p) {
 // all terrain-ee-motion_e (terrain_constraint.cc:57-108), force-ee-force_e, splineacc-base-* and
 // swing-ee-motion_e sets of one problem.  One workgroup of four waves per problem, one wave per family
 // (each with its own LDS image, no barriers), 64 spline nodes / rows at a time.
+// NaN-propagating max of two violations (score_kernel, eval_scores_kernel): a NaN operand wins
+TWR_DEV double nan_max(double a, double b) { return (a != a || b != b) ? (a != a ? a : b) : fmax(a, b); }
+// Candidate scoring without g (eval_scores_kernel): where the values-only kernel stores a constraint value, the scoring
+// instantiation turns it into the row's bound violation max(lower - g, g - upper, 0) -- bounds from the structure's score
+// record at kScoreOff (the row's 16-bit meta word, its (lower, upper) pair in the 2-KB head), exactly as score_kernel --
+// and adds it to the lane's running (max, sum) of the row's family F (the TWR_SET_* bit; every call site knows its family).
+// flush() reduces the lanes over a fixed xor tree and writes the wave's partial record: kScorePartial doubles laid out as a
+// score row, 2 F = max, 2 F + 1 = sum.
+enum ScoreFamily { kFamTerrain = 0, kFamDyn = 1, kFamAcc = 2, kFamRom = 3, kFamForce = 4, kFamSwing = 5, kFamTotal = 6, kFamBaseMotion = 7 };
+struct ScoreAcc {
+  const uint16_t* meta;
+  const double* pairs;
+  double m[8], s[8];
+  TWR_DEV explicit ScoreAcc(uint64_t blob)
+      : meta(reinterpret_cast<const uint16_t*>(blob + kScoreOff + kScoreHeadBytes)),
+        pairs(reinterpret_cast<const double*>(blob + kScoreOff + sizeof(ScoreTables))) {
+#pragma unroll
+    for (int f = 0; f < 8; ++f) m[f] = s[f] = 0.0;
+  }
+  template <int F>
+  TWR_DEV void put(int row, double val) {   // row: the problem's row index
+    const int q = (int)(meta[row] & 0xFFFu);
+    const double lo = pairs[2 * q], up = pairs[2 * q + 1];
+    double viol = fmax(fmax(lo - val, val - up), 0.0);
+    if (val != val) viol = val;
+    m[F] = nan_max(m[F], viol);
+    s[F] += viol;
+  }
+  // the n values of rows row0 .. row0 + n - 1, staged in LDS at gs[0 .. n) (n <= 64 NIT)
+  template <int F, int NIT>
+  TWR_DEV void rows(const double* gs, int row0, int n, int lane) {
+#pragma unroll
+    for (int t = 0; t < NIT; ++t)
+      if (lane + 64 * t < n) put<F>(row0 + lane + 64 * t, gs[lane + 64 * t]);
+  }
+  template <int FA, int FB>   // the families the wave has met (FB = FA: one)
+  TWR_DEV void flush(double* __restrict__ rec, int lane) {
+    double r[4] = {m[FA], s[FA], m[FB], s[FB]};
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1)
+#pragma unroll
+      for (int k = 0; k < (FA == FB ? 2 : 4); ++k) {
+        const double v = __shfl_xor(r[k], o);
+        r[k] = (k & 1) ? r[k] + v : nan_max(r[k], v);
+      }
+    if (lane < kScorePartial) {
+      const int f = lane >> 1;
+      const double v = f == FA ? r[lane & 1] : f == FB ? r[2 + (lane & 1)] : 0.0;
+      rec[lane] = v;
+    }
+  }
+};
 constexpr int kStageTerrain = 64 * 3 + 2, kStageForce = 64 * 25 + 2, kStageAcc = 64 * 6 + 2, kStageSwing = 64 * 12 + 2;
 constexpr int kNodeStageOff[4] = {0, kStageTerrain, kStageTerrain + kStageForce, kStageTerrain + kStageForce + kStageAcc};
 // one family (wave-uniform 0..3) of one problem; `stage`: the family's LDS image (kStage<Family> doubles)
+// (SCORE: the values go to sc instead of g -- eval_scores_kernel, flags = values only)
+template <bool SCORE = false>
 TWR_DEV void node_body(const NodeWork& w, const double* __restrict__ x, double* __restrict__ g, double* __restrict__ jac,
-                       int flags, double* stage, int family, int lane) {
+                       int flags, double* stage, int family, int lane, ScoreAcc* sc = nullptr) {
   const char* blob = reinterpret_cast<const char*>(w.blob);
   const DevStruct* S = reinterpret_cast<const DevStruct*>(blob);
   const double* xp = x + w.x_off;
@@ -1278,7 +1332,8 @@ TWR_DEV void node_body(const NodeWork& w, const double* __restrict__ x, double* 
       if (lane < cnt) {
         const double px = xp[tr.idx], py = xp[tr.idx + tr.stride], pz = xp[tr.idx + 2 * tr.stride];
         const Terr t = terrain_eval(S, S->terrain_id, S->flat_height, px, py);
-        if (want_g) gp[S->row_terrain + r0 + lane] = pz - t.h;
+        if constexpr (SCORE) sc->put<kFamTerrain>(S->row_terrain + r0 + lane, pz - t.h);
+        else if (want_g) gp[S->row_terrain + r0 + lane] = pz - t.h;
         if (want_j) {
           stage[par + 3 * lane + 0] = -t.hx;
           stage[par + 3 * lane + 1] = -t.hy;
@@ -1299,7 +1354,16 @@ TWR_DEV void node_body(const NodeWork& w, const double* __restrict__ x, double* 
       const int cnt = min(64, nn - i0);
       double* dst = jp + S->nnz_force + 25 * i0;
       const int par = (int)((reinterpret_cast<uintptr_t>(dst) >> 3) & 1);
-      if (lane < cnt) force_item(S, fn, xp, gp + S->row_force + 5 * (i0 + lane), stage + par + 25 * lane, want_g, want_j);
+      if constexpr (SCORE) {
+        if (lane < cnt) {
+          double g5[5];
+          force_item(S, fn, xp, g5, nullptr, true, false);
+#pragma unroll
+          for (int r = 0; r < 5; ++r) sc->put<kFamForce>(S->row_force + 5 * (i0 + lane) + r, g5[r]);
+        }
+      } else if (lane < cnt) {
+        force_item(S, fn, xp, gp + S->row_force + 5 * (i0 + lane), stage + par + 25 * lane, want_g, want_j);
+      }
       if (want_j) copy_out(dst, stage, 25 * cnt, par, lane);
     };
     const ForceNode fn0 = tbl<ForceNode>(blob, kNodeHeadForceOff)[lane];   // (fixed offset, see the terrain family)
@@ -1331,7 +1395,8 @@ TWR_DEV void node_body(const NodeWork& w, const double* __restrict__ x, double* 
           v += a.c[i] * xb[3 * i];
           if (want_j) stage[par + 6 * lane + i] = a.c[i];
         }
-        if (want_g) gp[S->row_acc + r] = v;
+        if constexpr (SCORE) sc->put<kFamAcc>(S->row_acc + r, v);
+        else if (want_g) gp[S->row_acc + r] = v;
       }
       if (want_j) copy_out(dst, stage, 6 * cnt, par, lane);
     }
@@ -1351,7 +1416,10 @@ TWR_DEV void node_body(const NodeWork& w, const double* __restrict__ x, double* 
         const double* xl = xp + n.q6;
 #pragma unroll
         for (int d = 0; d < 3; ++d) {
-          if (want_g) {
+          if constexpr (SCORE) {
+            sc->put<kFamBaseMotion>(S->row_bm + 6 * (k0 + lane) + d, wP[0] * xa[d] + wP[1] * xa[3 + d] + wP[2] * xa[6 + d] + wP[3] * xa[9 + d]);
+            sc->put<kFamBaseMotion>(S->row_bm + 6 * (k0 + lane) + 3 + d, wP[0] * xl[d] + wP[1] * xl[3 + d] + wP[2] * xl[6 + d] + wP[3] * xl[9 + d]);
+          } else if (want_g) {
             double* g6 = gp + S->row_bm + 6 * (k0 + lane);
             g6[d] = wP[0] * xa[d] + wP[1] * xa[3 + d] + wP[2] * xa[6 + d] + wP[3] * xa[9 + d];
             g6[3 + d] = wP[0] * xl[d] + wP[1] * xl[3 + d] + wP[2] * xl[6 + d] + wP[3] * xl[9 + d];
@@ -1385,7 +1453,10 @@ TWR_DEV void node_body(const NodeWork& w, const double* __restrict__ x, double* 
           const double prev = xp[pi[dim]], next = xp[ni[dim]];
           const double pos = xp[sn.cur + 2 * dim], vel = xp[sn.cur + 2 * dim + 1];
           const double distance = next - prev;
-          if (want_g) {
+          if constexpr (SCORE) {
+            sc->put<kFamSwing>(S->row_swing + 4 * (i0 + lane) + 2 * dim, pos - (prev + 0.5 * distance));
+            sc->put<kFamSwing>(S->row_swing + 4 * (i0 + lane) + 2 * dim + 1, vel - distance * it);
+          } else if (want_g) {
             double* g4 = gp + S->row_swing + 4 * (i0 + lane);
             g4[2 * dim] = pos - (prev + 0.5 * distance);
             g4[2 * dim + 1] = vel - distance * it;
@@ -1411,7 +1482,8 @@ TWR_DEV void node_body(const NodeWork& w, const double* __restrict__ x, double* 
           sum += xp[PT->off_sched[lane] + i];
           if (want_j) jp[PT->nnz_total + voff + i] = 1.0;
         }
-        if (want_g) gp[PT->row_total + lane] = sum;
+        if constexpr (SCORE) sc->put<kFamTotal>(PT->row_total + lane, sum);
+        else if (want_g) gp[PT->row_total + lane] = sum;
       }
     }
   }
@@ -1789,8 +1861,9 @@ TWR_DEV void flat_point(const char* __restrict__ xs, const FlatPolyR& r, double 
 }
 // Same formula as rom_item (RangeOfMotionConstraint::UpdateConstraintAtInstance, range_of_motion_constraint.cc:58-69).
 // `lds`: the wave's polynomial windows; `xs`: the group's copy of x (zero pair first); `gs`: 192 doubles of the wave's own
-template <bool GATHER>
-TWR_DEV void flat_rom_math(const FlatRec& w, const FlatNodeR& n, double* __restrict__ g, const char* lds, const char* xs, double* gs, int lane) {
+template <bool GATHER, bool SCORE = false>
+TWR_DEV void flat_rom_math(const FlatRec& w, const FlatNodeR& n, double* __restrict__ g, const char* lds, const char* xs, double* gs, int lane,
+                           ScoreAcc* sc = nullptr) {
   const double* xv = reinterpret_cast<const double*>(xs) + 2;
   double* gp = g + (int64_t)w.u64(kFwG);
   const int n_ee = w.i32(kFwNee);
@@ -1822,17 +1895,22 @@ TWR_DEV void flat_rom_math(const FlatRec& w, const FlatNodeR& n, double* __restr
       gs[3 * lane + 1] = gv[1];
       gs[3 * lane + 2] = gv[2];
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      double* go = gp + w.i32(kFwRowRom + ee) + 3 * w.i32(kFwK0);
-      const int last_g = 3 * w.i32(kFwCnt) - 1;
+      if constexpr (SCORE) {
+        sc->rows<kFamRom, 3>(gs, w.i32(kFwRowRom + ee) + 3 * w.i32(kFwK0), 3 * w.i32(kFwCnt), lane);
+      } else {
+        double* go = gp + w.i32(kFwRowRom + ee) + 3 * w.i32(kFwK0);
+        const int last_g = 3 * w.i32(kFwCnt) - 1;
 #pragma unroll
-      for (int t = 0; t < 3; ++t) go[min(lane + 64 * t, last_g)] = gs[min(lane + 64 * t, last_g)];
+        for (int t = 0; t < 3; ++t) go[min(lane + 64 * t, last_g)] = gs[min(lane + 64 * t, last_g)];
+      }
     }
 }
 // DynamicConstraint::UpdateConstraintAtInstance (dynamic_constraint.cc:59-77) with SingleRigidBodyDynamics::GetDynamicViolation
 // (single_rigid_body_dynamics.cc:76-101) and the EulerConverter quantities (euler_converter.cc:58-83,133-166,207-221) of one time
 // node on ONE lane -- the statements of dyn2_front / dyn2_back without the quad.
-template <bool GATHER>
-TWR_DEV void flat_dyn_math(const FlatRec& w, const FlatNodeR& n, double* __restrict__ g, const char* lds, const char* xs, double* gs_rom, int lane) {
+template <bool GATHER, bool SCORE = false>
+TWR_DEV void flat_dyn_math(const FlatRec& w, const FlatNodeR& n, double* __restrict__ g, const char* lds, const char* xs, double* gs_rom, int lane,
+                           ScoreAcc* sc = nullptr) {
   const double* xv = reinterpret_cast<const double*>(xs) + 2;
   const int n_ee = w.i32(kFwNee);
   const double* bl = xv + w.i32(kFwOffLin) + n.q6;   // base splines: the twelve node values of the active polynomial
@@ -1878,9 +1956,13 @@ TWR_DEV void flat_dyn_math(const FlatRec& w, const FlatNodeR& n, double* __restr
           gs_rom[3 * lane + 1] = gv[1];
           gs_rom[3 * lane + 2] = gv[2];
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-          double* go = gp + w.i32(kFwRowRom + ee) + 3 * w.i32(kFwK0);
+          if constexpr (SCORE) {
+            sc->rows<kFamRom, 3>(gs_rom, w.i32(kFwRowRom + ee) + 3 * w.i32(kFwK0), last_rom + 1, lane);
+          } else {
+            double* go = gp + w.i32(kFwRowRom + ee) + 3 * w.i32(kFwK0);
 #pragma unroll
-          for (int t = 0; t < 3; ++t) go[min(lane + 64 * t, last_rom)] = gs_rom[min(lane + 64 * t, last_rom)];
+            for (int t = 0; t < 3; ++t) go[min(lane + 64 * t, last_rom)] = gs_rom[min(lane + 64 * t, last_rom)];
+          }
         }
       }
   }
@@ -1941,7 +2023,9 @@ TWR_DEV void flat_dyn_math(const FlatRec& w, const FlatNodeR& n, double* __restr
   gs[4] = m * cdd[1] - F[1];
   gs[5] = m * cdd[2] - F[2] + m * w.f64(kFwGravity);
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  {
+  if constexpr (SCORE) {
+    sc->rows<kFamDyn, 6>(reinterpret_cast<const double*>(lds), w.i32(kFwRowDyn) + 6 * w.i32(kFwK0), 6 * w.i32(kFwCnt), lane);
+  } else {
     const double* gl = reinterpret_cast<const double*>(lds);
     double* go = gp + w.i32(kFwRowDyn) + 6 * w.i32(kFwK0);
     const int last_g = 6 * w.i32(kFwCnt) - 1;
@@ -1997,6 +2081,85 @@ __global__ __launch_bounds__(64 * kFlatGroup, 4) void eval_values_kernel(const F
     if (dynamic) flat_dyn_math<false>(w, flat_node(in), g, mine, xs, gs, lane);
     else flat_rom_math<false>(w, flat_node(in), g, mine, xs, gs, lane);
   }
+}
+
+// twr_batch_eval_scores: the same launch in its scoring instantiation.  Every value is reduced where eval_values_kernel stores
+// it (ScoreAcc: same device functions, same arithmetic, the values go to the wave's running violations instead of g), and
+// every wave with work writes ONE partial record, wave w of workgroup b at slab + kScorePartial (4 b + w).  The node-based
+// sets are always taken by the launch's own node waves (one workgroup per problem, node_families waves), at every batch size:
+// node_chunk_kernel writes g.  score_fold_kernel then folds each problem's records in the order structure.cc planned.
+// group_blob[b]: the blob of group b's problem (FlatWork carries no blob; the score record sits at its kScoreOff).
+template <int NX>
+__global__ __launch_bounds__(64 * kFlatGroup, 4) void eval_scores_kernel(const FlatWork* __restrict__ flat, const uint64_t* __restrict__ group_blob,
+                                                                         int n_groups, int x_bytes, const NodeWork* __restrict__ node,
+                                                                         int node_families, const double* __restrict__ x, double* __restrict__ slab) {
+  extern __shared__ __attribute__((aligned(16))) double flat_stage[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  char* xs = reinterpret_cast<char*>(flat_stage);
+  char* mine = xs + x_bytes + wave * kFlatWaveLds;
+  int b = blockIdx.x;
+  double* rec = slab + kScorePartial * ((int64_t)kFlatGroup * b + wave);
+  if (b >= n_groups) {
+    if (wave < node_families) {   // (one call site per CONSTANT family, as node_kernel: the record names its families)
+      const NodeWork w = node[b - n_groups];
+      ScoreAcc sc(w.blob);
+      double* st = reinterpret_cast<double*>(mine);
+      if (wave == 0) {
+        node_body<true>(w, x, nullptr, nullptr, 1, st, 0, lane, &sc);
+        sc.flush<kFamTerrain, kFamTerrain>(rec, lane);
+      } else if (wave == 1) {
+        node_body<true>(w, x, nullptr, nullptr, 1, st, 1, lane, &sc);
+        sc.flush<kFamForce, kFamForce>(rec, lane);
+      } else if (wave == 2) {
+        node_body<true>(w, x, nullptr, nullptr, 1, st, 2, lane, &sc);
+        sc.flush<kFamAcc, kFamBaseMotion>(rec, lane);
+      } else {
+        node_body<true>(w, x, nullptr, nullptr, 1, st, 3, lane, &sc);
+        sc.flush<kFamSwing, kFamTotal>(rec, lane);
+      }
+    }
+    return;
+  }
+  FlatRec w;
+  w.p = cptr<uint32_t>(reinterpret_cast<uint64_t>(flat + (kFlatGroup * b + wave)));
+  const int cnt = w.i32(kFwCnt);
+  ScoreAcc sc(group_blob[b]);
+  FlatIn in;
+  double xr[NX];
+  const bool gather = w.i32(kFwGather) != 0;
+  if (cnt > 0) flat_load(w, lane, in);
+  if (cnt > 0 && !gather) flat_load_polys(w, lane, in);
+  flat_load_x<NX>(x + (int64_t)w.u64(kFwX), w.i32(kFwNx), tid, xr);
+  flat_stage_x<NX>(xr, w.i32(kFwNx), reinterpret_cast<double*>(xs), tid);
+  if (cnt > 0 && !gather) flat_stage_polys(in, mine, lane);
+  __syncthreads();
+  if (cnt <= 0) return;   // (an empty item has no partial record: structure.cc leaves it out of the fold)
+  double* gs = reinterpret_cast<double*>(mine + kFlatPolyLds);
+  if (w.i32(kFwDynamic) != 0) {
+    if (gather) flat_dyn_math<true, true>(w, flat_node(in), nullptr, mine, xs, gs, lane, &sc);
+    else flat_dyn_math<false, true>(w, flat_node(in), nullptr, mine, xs, gs, lane, &sc);
+    sc.flush<kFamDyn, kFamRom>(rec, lane);
+  } else {
+    if (gather) flat_rom_math<true, true>(w, flat_node(in), nullptr, mine, xs, gs, lane, &sc);
+    else flat_rom_math<false, true>(w, flat_node(in), nullptr, mine, xs, gs, lane, &sc);
+    sc.flush<kFamRom, kFamRom>(rec, lane);
+  }
+}
+// The fold: kFoldThreads threads per problem, thread j of problem p folds column j of its partial records
+// slot[first[p] .. first[p + 1]) in that order (max for even columns, sum for odd ones) into scores[16 p + j].  A family
+// the structure does not build has no rows, so no record names it: it scores 0, as in score_kernel (ScoreTables::
+// slot_of_family < 0).  A problem without records (no rows) scores zeros.
+__global__ __launch_bounds__(256) void score_fold_kernel(const int32_t* __restrict__ first, const int32_t* __restrict__ slot,
+                                                         const double* __restrict__ slab, int n_problems, double* __restrict__ scores) {
+  const int t = blockIdx.x * 256 + threadIdx.x, p = t / kFoldThreads, j = t % kFoldThreads;
+  if (p >= n_problems) return;
+  const int k0 = first[p], k1 = first[p + 1];
+  double acc = 0.0;
+  for (int k = k0; k < k1; ++k) {
+    const double o = slab[kScorePartial * (int64_t)slot[k] + j];
+    acc = (j & 1) ? acc + o : nan_max(acc, o);
+  }
+  scores[kScorePartial * (int64_t)p + j] = acc;
 }
 
 // ---------------------------------------------------------------- optimised timings (PhaseSpline) kernels
@@ -3053,7 +3216,6 @@ hipError_t launch_sample(const SampleWork* work, int n_work, const double* x, do
 // the pair table) -> LDS -- the record sits at a fixed offset of the blob (kScoreOff), no field of the header is needed.  The slot of a thread's rows never falls, so it keeps one
 // running (max, sum) pair and hands it to its LDS cell when the slot moves on.  Round 4's kernel fetched a cold candidate's
 // fields one s_load at a time and 16 bytes of bounds per row: 25 us for 128 candidates, 43 us for 1024.
-TWR_DEV double nan_max(double a, double b) { return (a != a || b != b) ? (a != a ? a : b) : fmax(a, b); }
 __device__ __forceinline__ void best_of(double& v, int& i, double ov, int oi) {
   if (ov < v || (ov == v && oi < i)) {
     v = ov;
@@ -3436,6 +3598,10 @@ static ChunkFn node_chunk_kernel_fn(const LaunchStep& p) {
 static ValuesFn eval_values_kernel_fn(const LaunchStep& p) {
   return pick<kValuesNx>(p.xc, [&](auto nx) -> ValuesFn { return eval_values_kernel<nx>; });
 }
+using ScoresFn = void (*)(const FlatWork*, const uint64_t*, int, int, const NodeWork*, int, const double*, double*);
+static ScoresFn eval_scores_kernel_fn(const LaunchStep& p) {
+  return pick<kValuesNx>(p.xc, [&](auto nx) -> ScoresFn { return eval_scores_kernel<nx>; });
+}
 static FusedFn fused_kernel_fn(const LaunchStep& p) {
   return pick<kDynXc>(p.xc, [&](auto xc) {
     return pick<kFusedNits>(p.nit, [&](auto nit) {
@@ -3463,6 +3629,7 @@ static PRomFn rom_phase_kernel_fn(const LaunchStep& p) {
 // them are there), issued in order on one stream.  Every launch is issued; the first error is returned.
 hipError_t launch_eval(const EvalShape& s, const EvalBuffers& b, hipStream_t stream, hipEvent_t* ev) {
   const EvalPlan plan = PlanEval(s);
+  const int plan_flags = (s.flags & kEvalScores) ? 1 : s.flags & 3;   // what the node kernels write (a scoring request's fallback: g)
   hipError_t st = hipSuccess;
   for (int i = 0; i < plan.n; ++i) {
     const LaunchStep& p = plan.step[i];
@@ -3479,14 +3646,23 @@ hipError_t launch_eval(const EvalShape& s, const EvalBuffers& b, hipStream_t str
       case Launch::kLocate: st = twr_first(st, twr_launch(phase_locate_kernel, grid, block, p.lds, stream, b.ploc, b.x)); break;
       case Launch::kDynPhase: st = twr_first(st, twr_launch(dyn_phase_kernel_fn(p), grid, block, p.lds, stream, b.pdyn, s.pdyn, b.x, b.g, b.jac)); break;
       case Launch::kRomPhase: st = twr_first(st, twr_launch(rom_phase_kernel_fn(p), grid, block, p.lds, stream, b.prom, s.prom, b.x, b.g, b.jac)); break;
-      case Launch::kNode: st = twr_first(st, twr_launch(node_kernel, grid, block, p.lds, stream, b.node, b.x, b.g, b.jac, s.flags)); break;
-      case Launch::kNode2: st = twr_first(st, twr_launch(node_kernel2, grid, block, p.lds, stream, b.node, b.x, b.g, b.jac, s.flags)); break;
+      case Launch::kNode: st = twr_first(st, twr_launch(node_kernel, grid, block, p.lds, stream, b.node, b.x, b.g, b.jac, plan_flags)); break;
+      case Launch::kNode2: st = twr_first(st, twr_launch(node_kernel2, grid, block, p.lds, stream, b.node, b.x, b.g, b.jac, plan_flags)); break;
       case Launch::kChunk:
         st = twr_first(st, twr_launch(node_chunk_kernel_fn(p), grid, block, p.lds, stream, b.fam[0], s.fam[0], a[0], b.fam[1], s.fam[1], a[1],
                                       b.fam[2], s.fam[2], a[2], b.fam[3], s.fam[3], a[3], b.x, b.g, b.jac));
         break;
       case Launch::kValues:
         st = twr_first(st, twr_launch(eval_values_kernel_fn(p), grid, block, p.lds, stream, b.flat, a[0], a[2], b.node, a[1], b.x, b.g));
+        break;
+      case Launch::kScores:
+        st = twr_first(st, twr_launch(eval_scores_kernel_fn(p), grid, block, p.lds, stream, b.flat, b.score_blob, a[0], a[2], b.node, a[1], b.x,
+                                      b.slab));
+        break;
+      case Launch::kFold: st = twr_first(st, twr_launch(score_fold_kernel, grid, block, p.lds, stream, b.score_first, b.score_slot, b.slab, a[0], b.scores)); break;
+      case Launch::kScoreG: st = twr_first(st, launch_score(b.node, a[0], b.g, b.scores, stream)); break;
+      case Launch::kBest:
+        st = twr_first(st, launch_best(b.scores, a[0], b.families, b.best_partial, b.best_counter, b.best, b.index_offset, stream));
         break;
     }
   }

@@ -19,6 +19,18 @@ struct EvalBuffers {   // device memory of one evaluation: the batch's work list
   double* g;
   double* jac;
   double* dump;   // kDynDump doubles
+  // candidate scoring (EvalShape::flags kEvalScores / kEvalBest): the batch's scoring lists and slab, the caller's score table,
+  // and twr_batch_best's arguments and scratch
+  const uint64_t* score_blob;
+  const int32_t* score_first;
+  const int32_t* score_slot;
+  double* slab;
+  double* scores;
+  unsigned families;
+  double index_offset;
+  double* best_partial;
+  unsigned* best_counter;
+  double* best;
 };
 // Issues the launches PlanEval plans for `shape` (ev: four events when shape.events); returns the first error.
 hipError_t launch_eval(const EvalShape& shape, const EvalBuffers& buf, hipStream_t stream, hipEvent_t* ev);

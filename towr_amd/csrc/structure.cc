@@ -2077,7 +2077,12 @@ BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vec
     for (size_t i = 0; i < flat_group_p.size(); ++i) queue[flat_group_p[i] % 8].push_back(i);
     std::vector<FlatWork> out;
     out.reserve(L.flat.size());
-    auto emit = [&](size_t group) { out.insert(out.end(), L.flat.begin() + 4 * group, L.flat.begin() + 4 * group + 4); };
+    std::vector<size_t> order;      // the groups in list order
+    order.reserve(flat_group_p.size());
+    auto emit = [&](size_t group) {
+      out.insert(out.end(), L.flat.begin() + 4 * group, L.flat.begin() + 4 * group + 4);
+      order.push_back(group);
+    };
     size_t depth = 0, k = 0;
     for (const auto& q : queue) depth = std::max(depth, q.size());
     for (; k < depth; ++k) {   // whole rounds of eight; a round in which a queue has run dry ends the interleaving
@@ -2088,6 +2093,24 @@ BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vec
     }
     for (const auto& q : queue)
       for (size_t i = k; i < q.size(); ++i) emit(q[i]);
+    // candidate scoring without g: where every group went, then per problem its partial records in a fixed order (its groups
+    // in the order the structure lists its items, so the fold's sums do not depend on where the problem sits in the batch)
+    std::vector<int32_t> pos(flat_group_p.size());
+    for (size_t i = 0; i < order.size(); ++i) pos[order[i]] = (int32_t)i;
+    const int32_t n_groups = (int32_t)flat_group_p.size();
+    L.score_blob.resize(order.size());
+    for (size_t i = 0; i < order.size(); ++i) L.score_blob[i] = b.blob_of_problem[flat_group_p[order[i]]];
+    L.score_first.assign(1, 0);
+    size_t i = 0;
+    for (int p = 0; p < n_problems; ++p) {
+      for (; i < flat_group_p.size() && flat_group_p[i] == p; ++i)
+        for (int w = 0; w < kFlatGroup; ++w)
+          if (L.flat[kFlatGroup * i + w].cnt > 0) L.score_slot.push_back(kFlatGroup * pos[i] + w);   // (L.flat: still in list order)
+      for (int w = 0; w < b.node_families; ++w) L.score_slot.push_back(kFlatGroup * (n_groups + p) + w);
+      L.score_first.push_back((int32_t)L.score_slot.size());
+    }
+    b.score_fused = true;
+    b.score_slab = (int64_t)kFlatGroup * (n_groups + n_problems);
     L.flat.swap(out);
   }
   // Large batches whose node-based sets are terrain / force / splineacc / swing only: per-family chunk lists for the
@@ -2169,6 +2192,33 @@ EvalPlan PlanEval(const EvalShape& s) {
       add(s.node_families == 2 ? Launch::kNode2 : Launch::kNode, store, 0, 0, s.node, s.node, s.node_families == 2 ? 128 : 256);
     }
   };
+  // Candidate scores (twr_batch_eval_scores): with score_fused the values-only launch in its scoring instantiation
+  // (eval_scores_kernel: every wave reduces its rows to a partial record, the node-based sets always by the launch's own
+  // node waves -- node_chunk_kernel writes g) and the fold of the partial records into the score rows; otherwise exactly
+  // twr_batch_eval(TWR_EVAL_VALUES) and twr_batch_score.  Then twr_batch_best's launch if asked for.  No per-kernel events.
+  if (s.flags & kEvalScores) {
+    if (s.score_fused) {
+      const int nx = (s.flat_max_x + 64 * kFlatGroup - 1) / (64 * kFlatGroup);
+      const int n_groups = s.flat / kFlatGroup, items = n_groups + s.node;
+      LaunchStep& p = add(Launch::kScores, kStoreG, 0, nx <= 3 ? 3 : nx <= 5 ? 5 : 8, items, items, 64 * kFlatGroup, flat_lds_bytes(s.flat_max_x));
+      p.arg[0] = n_groups;
+      p.arg[1] = s.node_families;
+      p.arg[2] = flat_x_bytes(s.flat_max_x);
+      const int fold = (kFoldThreads * s.node + 255) / 256;
+      add(Launch::kFold, kStoreG, 0, 0, fold, fold, 256).arg[0] = s.node;
+    } else {
+      EvalShape v = s;
+      v.flags = 1;   // TWR_EVAL_VALUES
+      v.events = false;
+      plan = PlanEval(v);
+      add(Launch::kScoreG, kStoreG, 0, 0, s.node, s.node, 256).arg[0] = s.node;
+    }
+    if (s.flags & kEvalBest) {   // (launch_best's grid: four candidates per thread, at most 256 workgroups)
+      const int blocks = std::max(1, std::min((s.node + 1023) / 1024, 256));
+      add(Launch::kBest, kStoreG, 0, 0, blocks, blocks, 256).arg[0] = s.node;
+    }
+    return plan;
+  }
   // Values only (no Jacobian), every problem with fixed timings and at most kFlatXCap variables: "dynamic" and "rangeofmotion-*"
   // with one lane per time node (flat items), the node-based sets -- one launch (eval_values_kernel); with per-kernel events three.
   if (wg && !wj && s.flat > 0 && s.pdyn == 0 && s.prom == 0 && s.ploc == 0) {

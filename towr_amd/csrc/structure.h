@@ -179,6 +179,13 @@ struct BatchPlan {
     std::vector<PDynWork> pdyn;               // optimised timings (XCD order as dyn)
     std::vector<LocWork> ploc;
     std::vector<RomPhaseWork> prom;
+    // candidate scoring without g (score_fused only; device_tables.h kScorePartial).  The scoring launch runs the flat groups
+    // in the order of `flat`, then one workgroup per problem for the node-based sets; wave w of workgroup b writes partial
+    // record 4 b + w of the slab.  Per problem, the fold reads score_slot[score_first[p] .. score_first[p + 1]) in that order:
+    // its flat items in the order the structure lists them (empty items left out), then its node waves.
+    std::vector<uint64_t> score_blob;         // per flat group: the blob of its problem (the score record, kScoreOff)
+    std::vector<int32_t> score_first;         // n_problems + 1
+    std::vector<int32_t> score_slot;
   } lists;
   // Scratch for the x-dependent DynLoc / RomRec records of the optimised-timings problems.  The lists hold byte offsets into it
   // until PlaceRecords(scratch address) turns them into addresses; LocWork::recs / dyn_loc store offset + 1 meanwhile, since
@@ -191,6 +198,8 @@ struct BatchPlan {
   int node_families = 4;       // 2 when no problem has more than terrain-* / force-* work for the node kernel
   int pdyn_img_cap = 0, prom_img_cap = 0;   // doubles of the LDS images of dyn_phase_kernel / rom_phase_kernel (largest pass)
   bool stream_nt = false;      // non-temporal copy-out stores (StreamNonTemporal)
+  bool score_fused = false;    // every problem takes the values-only path: twr_batch_eval_scores writes no g
+  int64_t score_slab = 0;      // partial records of the scoring launch (kScorePartial doubles each)
   int64_t dyn_layout_bytes = 0, dyn_layout_distinct_bytes = 0;   // dyn_kernel's layout tables: as built / after sharing
 };
 std::vector<size_t> BlobOffsets(const std::vector<const Structure*>& structs);   // n + 1 arena offsets
@@ -214,11 +223,16 @@ struct EvalShape {
   // what PlanBatch decided for the batch (BatchPlan)
   int rom_max_vals = 0, flat_max_x = 0, dyn_map_chunks = 2, node_families = 4, pdyn_img_cap = 0, prom_img_cap = 0;
   bool stream_nt = false;
-  int flags = 0;                  // TWR_EVAL_VALUES | TWR_EVAL_JACOBIAN
+  int flags = 0;                  // TWR_EVAL_VALUES | TWR_EVAL_JACOBIAN, or kEvalScores (| kEvalBest)
   bool events = false;            // per-kernel profiling events are recorded
+  bool score_fused = false;       // BatchPlan::score_fused
   LaunchTuning tuning;
 };
-enum class Launch { kEvent, kDyn, kRom, kFused, kLocate, kDynPhase, kRomPhase, kNode, kNode2, kChunk, kValues };
+// Internal requests of EvalShape::flags (not TWR_EVAL_* values): the score table of twr_batch_score (kEvalScores), then the
+// arg-min of twr_batch_best over it (kEvalBest).  Fused (score_fused): the scoring launch and the fold; otherwise the
+// values-only evaluation into g and score_kernel.  Neither records per-kernel events.
+constexpr int kEvalScores = 1 << 8, kEvalBest = 1 << 9;
+enum class Launch { kEvent, kDyn, kRom, kFused, kLocate, kDynPhase, kRomPhase, kNode, kNode2, kChunk, kValues, kScores, kFold, kScoreG, kBest };
 // Outputs a launch writes: constraint values (G), Jacobian (J), and non-temporal copy-out stores (NT, only with J).
 enum StoreVariant { kStoreG, kStoreJ, kStoreGJ, kStoreJNT, kStoreGJNT };
 constexpr bool StoreG(int s) { return s == kStoreG || s == kStoreGJ || s == kStoreGJNT; }
@@ -239,7 +253,8 @@ struct LaunchStep {
   Launch kernel = Launch::kEvent;
   int store = kStoreG, nit = 0, xc = 0;   // instantiation (xc: NX of eval_values_kernel)
   int grid = 0, block = 0, lds = 0;       // lds: dynamic LDS bytes
-  // kEvent: the event; kFused: rom and dyn blocks; kChunk: blocks per family; kValues: groups, node families, x bytes
+  // kEvent: the event; kFused: rom and dyn blocks; kChunk: blocks per family; kValues, kScores: groups, node families, x bytes;
+  // kFold, kScoreG, kBest: problems
   int arg[4] = {0, 0, 0, 0};
 };
 struct EvalPlan {
