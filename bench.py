@@ -11,7 +11,10 @@ flat terrain, K_dyn=K_rom=200, `--batch` problems per GPU that share the structu
 (BASELINE.md section 4 perturbation).  Candidates shard across ranks with no data-path collective
 (weak scaling: per-GPU batch fixed); the only collective is one broadcast of the POD model blob.
 
-Prints ONE JSON line on rank 0, with the `roofline` and `cpu_baseline` objects of the contract.
+Prints ONE JSON line on rank 0, with the `roofline` object of the contract.  A plain run does only what that line needs:
+set-up, output placement, the W warm-up steps, the K timed steps and, with --dump-outputs, the dump.  `--full` adds what
+takes runs of its own: two repeats of the timed region, the `cpu_baseline` object and, for the default C3 workload, the
+`values_c3`, `timings_c3`, `all_sets_c3` and `scale_c5` legs (the --no-* options leave single ones out).
 """
 import argparse
 import json
@@ -644,11 +647,14 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one computed as DIR/g.npy and DIR/jac.npy (float64; rank 0's "
                          "problems, a fixed seeded sample of whole problems when they exceed %d MB)" % (DUMP_BYTES // 10**6))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-scale-c5", action="store_true", help="skip the strong-scaling C5 leg of the default run")
-    ap.add_argument("--no-values-c3", action="store_true", help="skip the values-only leg of the default run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: repeat its timed region twice, time the CPU baseline and, for the default C3 "
+                         "workload, run the values-only, optimised-timings, whole-default-list and strong-scaling C5 legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline of a --full run")
+    ap.add_argument("--no-scale-c5", action="store_true", help="skip the strong-scaling C5 leg of a --full run")
+    ap.add_argument("--no-values-c3", action="store_true", help="skip the values-only leg of a --full run")
     ap.add_argument("--no-timings-c3", action="store_true",
-                    help="skip the optimised-timings and the whole-default-list legs of the default run")
+                    help="skip the optimised-timings and the whole-default-list legs of a --full run")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -753,26 +759,27 @@ def main():
     elapsed = time.perf_counter() - t0
     kern_ms, n_prof = batch.profile_end()
     assert n_prof == args.steps
-    # measurement hygiene: the same timed region twice more (same K steps, same per-kernel events, barriers on both
-    # sides).  The headline stays the FIRST region (the contract's K steps); the repeats show its run-to-run spread.
+    # measurement hygiene (--full): the same timed region twice more (same K steps, same per-kernel events, barriers on
+    # both sides).  The headline stays the FIRST region (the contract's K steps); the repeats show its run-to-run spread.
     repeats = [elapsed]
-    for _ in range(2):
-        batch.profile_begin(args.steps)
-        torch.cuda.synchronize()
+    if args.full:
+        for _ in range(2):
+            batch.profile_begin(args.steps)
+            torch.cuda.synchronize()
+            if dist_on(world):
+                dist.barrier()
+            t_r = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            if dist_on(world):
+                dist.barrier()
+            repeats.append(time.perf_counter() - t_r)
+            batch.profile_end()
         if dist_on(world):
-            dist.barrier()
-        t_r = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        if dist_on(world):
-            dist.barrier()
-        repeats.append(time.perf_counter() - t_r)
-        batch.profile_end()
-    if dist_on(world):
-        t_rep = torch.tensor(repeats, dtype=torch.float64, device=dev if backend == "nccl" else None)
-        dist.all_reduce(t_rep, op=dist.ReduceOp.MAX)
-        repeats = [float(v) for v in t_rep]
+            t_rep = torch.tensor(repeats, dtype=torch.float64, device=dev if backend == "nccl" else None)
+            dist.all_reduce(t_rep, op=dist.ReduceOp.MAX)
+            repeats = [float(v) for v in t_rep]
 
     per_rank_ms = [elapsed / args.steps * 1e3]
     if dist_on(world):
@@ -815,8 +822,6 @@ def main():
             "warmup": args.warmup,
             "device_warmup_s": warm_s,   # plain HBM writes before the W warm-up steps (idle power state), not steps of the path
             "ms_per_step": elapsed / args.steps * 1e3,
-            # the timed region three times in this process (max over ranks each); [0] is the headline's region
-            "ms_per_step_repeats": [r_ / args.steps * 1e3 for r_ in repeats],
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,
@@ -834,11 +839,14 @@ def main():
                                   "kernel_ms": {names[k]: v for k, v in kern_ms.items()},
                                   "algorithmic_bytes_per_step": alg_bytes}},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            # the timed region three times in this process (max over ranks each); [0] is the headline's region
+            out["ms_per_step_repeats"] = [r_ / args.steps * 1e3 for r_ in repeats]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(sched, params, x_host[:S.n], terrain)
-    # north_star's strong-scaling claim rides on the same command: 1024 sweep candidates over all ranks
+    # north_star's strong-scaling claim rides on the same command with --full: 1024 sweep candidates over all ranks
     c5 = t3 = None
-    default_run = args.workload == "c3" and args.sets == "hot"
+    default_run = args.full and args.workload == "c3" and args.sets == "hot"
     if default_run and not (args.no_scale_c5 and args.no_timings_c3 and args.no_values_c3):
         del x, g, jac, batch
     a3 = v3 = None

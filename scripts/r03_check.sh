@@ -2,10 +2,10 @@
 # full GPU test tier + the default bench (summary of the legs on stdout)
 export TMPDIR=/tmp
 bash scripts/gpu_tests.sh 900 > /dev/null; tail -2 gpurun_out/gpu_tests.log
-python3 bench.py --steps ${1:-30} --warmup 5 ${2:---no-cpu-baseline} > gpurun_out/bench_check.json 2> gpurun_out/bench_check.err || tail -5 gpurun_out/bench_check.err
+python3 bench.py --steps ${1:-30} --warmup 5 --full ${2:---no-cpu-baseline} > $TMPDIR/bench_check.json 2> $TMPDIR/bench_check.err || tail -5 $TMPDIR/bench_check.err
 python3 - <<'PY'
-import json
-d = json.loads(open("gpurun_out/bench_check.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ["TMPDIR"], "bench_check.json")).read().strip().splitlines()[-1])
 r = d["roofline"]
 print(round(d["value"]), {k.split("::")[1]: round(v, 4) for k, v in r["path"]["kernel_ms"].items()}, "dominant", round(r["frac"], 3), "path", round(r["path"]["frac"], 3), "traffic", r["traffic"])
 for leg in ("timings_c3", "all_sets_c3"):

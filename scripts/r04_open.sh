@@ -10,7 +10,7 @@ B="--steps 30 --warmup 5 --no-cpu-baseline --no-scale-c5 --no-timings-c3"
 timeout -k 10 200 python3 bench.py $B --workload sweep --batch 1024 > $OUT/sweep1024.json 2> $OUT/sweep1024.err || exit 1
 timeout -k 10 200 python3 scripts/small_batches.py 128 256 512 1024 > $OUT/small_batches.txt 2>&1 || exit 1
 cat $OUT/small_batches.txt
-timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
+timeout -k 10 300 python3 bench.py --steps 20 --warmup 3 --full > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
 python3 - <<'PY'
 import json
 for f in ("sweep1024", "bench_default"):

@@ -1145,15 +1145,15 @@ def test_eval_is_graph_capturable_and_stream_ordered():
 
 
 def test_bench_prints_one_contract_line():
-    """`python bench.py` as the driver runs it (N = 1; fewer steps): exactly one JSON line on stdout with the contract's keys,
-    the `roofline` and `cpu_baseline` objects and the extra legs of the default run."""
+    """`python bench.py --full` (N = 1; fewer steps): exactly one JSON line on stdout with the contract's keys, the `roofline`
+    and `cpu_baseline` objects and the extra legs of the default workload."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1"], capture_output=True,
-                       text=True, timeout=600, cwd=root)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--full"],
+                       capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -1175,3 +1175,32 @@ def test_bench_prints_one_contract_line():
     for leg in ("timings_c3", "all_sets_c3", "scale_c5"):
         assert d[leg]["value"] > 0 and d[leg]["unit"] == "callbacks/s", leg
     assert d["scale_c5"]["candidates"] == 1024 and d["scale_c5"]["world_size"] == 1
+
+
+def test_plain_bench_run_prints_the_headline_only():
+    """`python bench.py` without --full: the same contract line, without the repeats, the CPU baseline and the extra legs, and at
+    most 30 s of the run's wall time outside its warm-up and timed steps."""
+    import json
+    import subprocess
+    import sys
+    import time
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=600, cwd=root)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
+                "dtype", "data", "config", "roofline"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True
+    assert d["unit"] == "callbacks/s" and d["dtype"] == "f64"
+    assert abs(d["value"] - d["config"]["problems_per_gpu"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert 0.2 < d["roofline"]["frac"] < 1.0
+    for key in ("ms_per_step_repeats", "cpu_baseline", "values_c3", "timings_c3", "all_sets_c3", "scale_c5"):
+        assert key not in d, key
+    assert wall - (3 + 1) * d["ms_per_step"] * 1e-3 < 30.0, wall
