@@ -10,6 +10,7 @@
 #include <map>
 #include <numeric>
 #include <stdexcept>
+#include <tuple>
 #include <unordered_map>
 
 namespace twr {
@@ -114,6 +115,16 @@ SplineLayout PhaseBasedLayout(const double* phase_durations, int n_phases, bool 
   s.var_offset = var_offset;
   s.var_size = idx - var_offset;
   return s;
+}
+
+// the dimension of every variable of a phase-based set, by index relative to the set's first (-1: none)
+std::vector<int> DimOf(const SplineLayout& s) {
+  std::vector<int> dim_of(s.var_size, -1);
+  for (int n = 0; n < s.n_nodes; ++n)
+    for (int dv = 0; dv < 2; ++dv)
+      for (int d = 0; d < 3; ++d)
+        if (s.at(n, dv, d) >= 0) dim_of[s.at(n, dv, d) - s.var_offset] = d;
+  return dim_of;
 }
 
 PolyDesc MakeEePoly(const SplineLayout& s, int q) {
@@ -358,11 +369,7 @@ void Structure::BuildPattern() {
   };
   auto set_cols = [&](const SplineLayout& s, int want_dim, bool equal, std::vector<int32_t>& out) {
     // all variables of a phase-based set whose dim ==/!= want_dim, ascending
-    std::vector<int> dim_of(s.var_size, -1);
-    for (int n = 0; n < s.n_nodes; ++n)
-      for (int dv = 0; dv < 2; ++dv)
-        for (int d = 0; d < 3; ++d)
-          if (s.at(n, dv, d) >= 0) dim_of[s.at(n, dv, d) - s.var_offset] = d;
+    const std::vector<int> dim_of = DimOf(s);
     for (int i = 0; i < s.var_size; ++i)
       if ((dim_of[i] == want_dim) == equal) out.push_back(s.var_offset + i);
   };
@@ -515,860 +522,848 @@ void Structure::BuildPattern() {
 }
 
 // ------------------------------------------------------------------ device blob
-void Structure::PackBlob() {
-  DevStruct h;
-  std::memset(&h, 0, sizeof(h));
-  std::vector<char> body;
-  auto put_aligned = [&](const void* src, size_t bytes, size_t align) -> uint32_t {   // (a blob starts on a 256-byte line)
-    size_t off = (sizeof(DevStruct) + body.size() + align - 1) / align * align;
-    body.resize(off - sizeof(DevStruct) + bytes);
-    if (bytes) std::memcpy(body.data() + off - sizeof(DevStruct), src, bytes);
+namespace {
+
+// The blob's alignment rules (device_tables.h): the DevStruct header, then the tables on 16-byte boundaries and the layout
+// tables of dyn_kernel on 64-byte lines (a blob starts on a 256-byte line); the whole is a multiple of 16 bytes.
+class BlobWriter {
+ public:
+  // the layout tables are recorded in `layout`: a batch stores byte-identical ones once
+  explicit BlobWriter(std::vector<Structure::TableRef>& layout) : blob_(sizeof(DevStruct)), layout_(layout) { layout_.clear(); }
+  uint32_t Put(const void* src, size_t bytes, size_t align = 16) {
+    const size_t off = (blob_.size() + align - 1) / align * align;
+    blob_.resize(off + bytes);
+    if (bytes) std::memcpy(blob_.data() + off, src, bytes);
     return (uint32_t)off;
-  };
-  auto put = [&](const void* src, size_t bytes) -> uint32_t { return put_aligned(src, bytes, 16); };
-  // a layout table of dyn_kernel (device_tables.h): a batch stores byte-identical ones once
-  dyn_layout_tables.clear();
-  auto put_layout = [&](const void* src, size_t bytes) -> uint32_t {
-    const uint32_t off = put_aligned(src, bytes, 64);
-    dyn_layout_tables.push_back({off, (uint32_t)bytes});
-    return off;
-  };
-  h.n_ee = n_ee;
-  h.terrain_id = model.terrain_id;
-  std::vector<TerrainRow> all_rows;
-  std::vector<ForceNode> all_nodes;
-  std::vector<SwingNode> all_swing;
-  auto family = [&](const std::string& prefix, int rows_per_item, auto& per_ee, auto& all, int32_t& row0, int32_t& nnz0) {
-    // the per-ee sets of one family are adjacent in g / jac: one flat list
-    for (int e = 0; e < n_ee; ++e) {
-      const SetInfo* si = FindSet(prefix + std::to_string(e));
-      if (!si) return;
-      if (e == 0) { row0 = si->offset; nnz0 = si->nnz_offset; }
-      if (si->offset != row0 + rows_per_item * (int)all.size()) throw std::runtime_error(prefix + " sets not adjacent");
-      all.insert(all.end(), per_ee[e].begin(), per_ee[e].end());
-    }
-  };
-  family("terrain-ee-motion_", 1, terrain_rows, all_rows, h.row_terrain, h.nnz_terrain);
-  family("force-ee-force_", 5, force_nodes, all_nodes, h.row_force, h.nnz_force);
-  family("swing-ee-motion_", 4, swing_nodes, all_swing, h.row_swing, h.nnz_swing);
-  h.n_terrain_rows = (int)all_rows.size();
-  h.n_force_nodes = (int)all_nodes.size();
-  h.n_swing_nodes = (int)all_swing.size();
-  h.off_base_ang = off_base_ang;
-  h.inv_t_swing = 1.0 / 0.3;  // t_swing_avg_, swing_constraint.h:68
-  if (const SetInfo* si = FindSet("splineacc-base-lin")) {
-    const SetInfo* sa = FindSet("splineacc-base-ang");
-    if (!sa || sa->offset != si->offset + si->size || off_base_lin != 0) throw std::runtime_error("splineacc sets not adjacent");
-    h.row_acc = si->offset;
-    h.nnz_acc = si->nnz_offset;
-    h.n_junctions = (int)acc_junctions.size();
   }
-  const SetInfo* dyn_set = FindSet("dynamic");
-  const int row_dyn = dyn_set ? dyn_set->offset : 0, nnz_dyn = dyn_set ? dyn_set->nnz_offset : 0;
-  int row_rom[kMaxEE] = {0, 0, 0, 0}, nnz_rom[kMaxEE] = {0, 0, 0, 0};
-  const bool have_rom = FindSet("rangeofmotion-0") != nullptr;
-  for (int e = 0; e < n_ee && have_rom; ++e) {
-    const SetInfo* si = FindSet("rangeofmotion-" + std::to_string(e));
-    row_rom[e] = si->offset;
-    nnz_rom[e] = si->nnz_offset;
+  template <class T>
+  uint32_t Put(const std::vector<T>& v, size_t align = 16) { return Put(v.data(), v.size() * sizeof(T), align); }
+  template <class T>
+  uint32_t PutLayout(const std::vector<T>& v) {
+    layout_.push_back({Put(v, 64), (uint32_t)(v.size() * sizeof(T))});
+    return layout_.back().off;
   }
-  {  // the node head (device_tables.h): first 64 terrain rows, first 64 force nodes, at fixed offsets behind the header
-    std::vector<char> head(kNodeHeadBytes, 0);
-    if (!all_rows.empty()) std::memcpy(head.data(), all_rows.data(), std::min<size_t>(64, all_rows.size()) * sizeof(TerrainRow));
-    if (!all_nodes.empty())
-      std::memcpy(head.data() + 64 * sizeof(TerrainRow), all_nodes.data(), std::min<size_t>(64, all_nodes.size()) * sizeof(ForceNode));
-    if (put(head.data(), head.size()) != kNodeHeadTerrainOff) throw std::runtime_error("node head is not the first table of the blob");
+  std::vector<char> Finish(const DevStruct& h) {
+    std::memcpy(blob_.data(), &h, sizeof(h));
+    blob_.resize((blob_.size() + 15) / 16 * 16);
+    return std::move(blob_);
   }
-  {  // candidate scoring: family and bounds of every row (device_tables.h, ScoreTables)
-    if (con_sets.size() > (size_t)kMaxConSets) throw std::runtime_error("too many constraint sets");
-    std::vector<double> pairs;
-    std::map<std::pair<uint64_t, uint64_t>, int> pair_index;   // distinct (lower, upper), by bit pattern
-    std::vector<uint16_t> meta((size_t)n_rows, 0);
-    int slot_of[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, n_slots = 0;
-    // (sets in row order: the slots are handed out in the order the families first appear along the rows)
-    std::vector<size_t> by_row(con_sets.size());
-    std::iota(by_row.begin(), by_row.end(), (size_t)0);
-    std::sort(by_row.begin(), by_row.end(), [&](size_t a, size_t b) { return con_sets[a].offset < con_sets[b].offset; });
-    for (size_t i : by_row) {
-      const std::string& nm = con_sets[i].name;
-      auto starts = [&](const char* p) { return nm.rfind(p, 0) == 0; };
-      const int fam = starts("terrain-") ? 0 : starts("dynamic") ? 1 : starts("splineacc-") ? 2 : starts("rangeofmotion-") ? 3
-                    : starts("force-") ? 4 : starts("swing-") ? 5 : starts("totalduration-") ? 6 : starts("baseMotion") ? 7 : -1;
-      if (fam < 0) throw std::runtime_error("constraint set of an unknown family");
-      if (con_sets[i].size > 0 && slot_of[fam] < 0) slot_of[fam] = n_slots++;
-      if (con_sets[i].size > 0 && slot_of[fam] != n_slots - 1) throw std::runtime_error("the sets of a constraint family are not adjacent in g");
-      for (int r = con_sets[i].offset; r < con_sets[i].offset + con_sets[i].size; ++r) {
-        uint64_t kl, ku;
-        std::memcpy(&kl, &lower[r], 8);
-        std::memcpy(&ku, &upper[r], 8);
-        auto it = pair_index.find({kl, ku});
-        if (it == pair_index.end()) {
-          it = pair_index.emplace(std::make_pair(kl, ku), (int)(pairs.size() / 2)).first;
-          pairs.push_back(lower[r]);
-          pairs.push_back(upper[r]);
-        }
-        if (it->second >= kScoreMaxPairs) throw std::runtime_error("more than 127 distinct constraint bounds in one structure");
-        meta[r] = (uint16_t)(slot_of[fam] << 12 | it->second);
+
+ private:
+  std::vector<char> blob_;
+  std::vector<Structure::TableRef>& layout_;
+};
+
+// the base-spline point of a time node: local time in the active polynomial, 1 / its duration, and 6 * its index (the offset
+// of its first node in base-lin / base-ang); the records assign it to their named fields with std::tie
+std::tuple<double, double, int32_t> BaseAt(const SplineLayout& base, const TimeNode& n) {
+  return std::make_tuple(n.t_local, 1.0 / base.durations[n.poly], 6 * n.poly);
+}
+
+// start time of every polynomial: the running sum Spline::GetSegmentID compares t against (spline.cc:52-57)
+std::vector<double> StartTimes(const std::vector<double>& durations) {
+  std::vector<double> t0(durations.size() + 1, 0.0);
+  for (size_t q = 0; q < durations.size(); ++q) t0[q + 1] = t0[q] + durations[q];
+  return t0;
+}
+
+// the ee-motion polynomial of a range-of-motion record (RomRec, RomSeg): 1 / duration, first x index, meta and the 48-bit
+// slot word (12 x 4 bit: the slot of candidate c, 0xF = absent)
+template <class R>
+void SetRomPoly(R& r, const PolyDesc& p) {
+  r.iTm = p.iT;
+  r.xbase = p.xbase;
+  r.meta = p.meta;
+  uint64_t slots = 0;
+  for (int c = 0; c < 12; ++c) slots |= (uint64_t)(p.cand[c] & 0xF) << (4 * c);
+  r.slots[0] = (uint32_t)slots;
+  r.slots[1] = (uint32_t)(slots >> 32);
+}
+
+// Cuts the time nodes [0, K) into consecutive runs from the left, each as long as fits(k0, k1) allows for the run [k0, k1):
+// (first node, count) per run, or none when a single time node does not fit.
+template <class Fits>
+std::vector<std::pair<int, int>> CutRuns(int K, const Fits& fits) {
+  std::vector<std::pair<int, int>> runs;
+  for (int k0 = 0; k0 < K;) {
+    int k1 = k0;
+    while (k1 < K && fits(k0, k1 + 1)) ++k1;
+    if (k1 == k0) return {};
+    runs.push_back({k0, k1 - k0});
+    k0 = k1;
+  }
+  return runs;
+}
+
+// the per-ee sets of one family are adjacent in g / jac: one flat list
+template <class T>
+std::vector<T> FlatFamily(const Structure& S, const std::string& prefix, int rows_per_item, const std::vector<std::vector<T>>& per_ee,
+                          int32_t& row0, int32_t& nnz0, int32_t& count) {
+  std::vector<T> all;
+  for (int e = 0; e < S.n_ee; ++e) {
+    const SetInfo* si = S.FindSet(prefix + std::to_string(e));
+    if (!si) break;
+    if (e == 0) { row0 = si->offset; nnz0 = si->nnz_offset; }
+    if (si->offset != row0 + rows_per_item * (int)all.size()) throw std::runtime_error(prefix + " sets not adjacent");
+    all.insert(all.end(), per_ee[e].begin(), per_ee[e].end());
+  }
+  count = (int32_t)all.size();
+  return all;
+}
+
+// the node head (device_tables.h): first 64 terrain rows, first 64 force nodes, at fixed offsets behind the header
+void PutNodeHead(BlobWriter& w, const std::vector<TerrainRow>& rows, const std::vector<ForceNode>& forces) {
+  std::vector<char> head(kNodeHeadBytes, 0);
+  if (!rows.empty()) std::memcpy(head.data(), rows.data(), std::min<size_t>(64, rows.size()) * sizeof(TerrainRow));
+  if (!forces.empty())
+    std::memcpy(head.data() + 64 * sizeof(TerrainRow), forces.data(), std::min<size_t>(64, forces.size()) * sizeof(ForceNode));
+  if (w.Put(head.data(), head.size()) != kNodeHeadTerrainOff) throw std::runtime_error("node head is not the first table of the blob");
+}
+
+// optimised timings: the polynomial table of one ee spline (device_tables.h PhasePoly)
+std::vector<PhasePoly> PhasePolyTable(const SplineLayout& sl, const std::vector<PolyDesc>& pd) {
+  std::vector<PhasePoly> out(pd.size());
+  const std::vector<int> dim_of = DimOf(sl);
+  int in_phase = 0;
+  for (size_t q = 0; q < pd.size(); ++q) {
+    PhasePoly& pp = out[q];
+    in_phase = (q > 0 && sl.poly_phase[q] == sl.poly_phase[q - 1]) ? in_phase + 1 : 0;
+    int n_in = 0;
+    for (size_t q2 = 0; q2 < pd.size(); ++q2) n_in += sl.poly_phase[q2] == sl.poly_phase[q];
+    pp.phase = sl.poly_phase[q];
+    pp.n_in_phase = n_in;
+    pp.poly_in_phase = in_phase;
+    pp.xbase = pd[q].xbase;
+    pp.meta = pd[q].meta;
+    std::memcpy(pp.cand, pd[q].cand, sizeof(pp.cand));
+    const int before = (pd[q].meta & 0xF) ? pd[q].xbase - sl.var_offset : 0;
+    for (int i = 0; i < before; ++i) {
+      for (int r = 0; r < 3; ++r) {
+        if (dim_of[i] != r) pp.base_ne[r]++;
+        if (dim_of[i] == r) pp.base_eq[r]++;
       }
     }
-    ScoreTables sc;
-    std::memset(&sc, 0, sizeof(sc));
-    sc.n_rows = n_rows;
-    sc.n_pairs = (int)(pairs.size() / 2);
-    for (int f = 0; f < 8; ++f) sc.slot_of_family[f] = (int8_t)slot_of[f];
-    // [ ScoreTables | pairs | zero padding to kScoreHeadBytes ][ meta words ] at a FIXED offset behind the node head: score_kernel
-    // asks for all of it without having seen a single field of the header
-    if (sizeof(sc) + pairs.size() * sizeof(double) > (size_t)kScoreHeadBytes) throw std::runtime_error("score record head overflows");
-    std::vector<char> rec(kScoreHeadBytes + (meta.size() * sizeof(uint16_t) + 15) / 16 * 16, 0);
-    std::memcpy(rec.data(), &sc, sizeof(sc));
-    std::memcpy(rec.data() + sizeof(sc), pairs.data(), pairs.size() * sizeof(double));
-    if (!meta.empty()) std::memcpy(rec.data() + kScoreHeadBytes, meta.data(), meta.size() * sizeof(uint16_t));
-    h.o_score = put(rec.data(), rec.size());
-    if (h.o_score != kScoreOff) throw std::runtime_error("score record is not at its fixed offset");
+    pp.base_all = (uint16_t)before;
   }
-  h.o_force_nodes = put(all_nodes.data(), all_nodes.size() * sizeof(ForceNode));
-  h.o_terrain_rows = put(all_rows.data(), all_rows.size() * sizeof(TerrainRow));
-  h.o_acc = put(acc_junctions.data(), acc_junctions.size() * sizeof(AccJunction));
-  if (const SetInfo* si = FindSet("baseMotion")) {
-    std::vector<BaseNode> bn(grid_bm.size());
-    for (size_t k = 0; k < grid_bm.size(); ++k) {
-      bn[k].t = bm_base[k].t_local;
-      bn[k].iT = 1.0 / base.durations[bm_base[k].poly];
-      bn[k].q6 = 6 * bm_base[k].poly;
-      bn[k].pad = 0;
+  return out;
+}
+
+// the dynamic row, relative to a time node's first, of value i of a candidate of dimension d: the two angular rows, then the
+// linear row (ee-force)
+int CandRow(int d, int i) { return i < 2 ? (d + 1 + i) % 3 : 3 + d; }
+
+// optimised timings: where the W values of each candidate of one ee polynomial go inside a time node's expanded dynamic
+// rows (PhasePutM, PhasePutF); `trash` for absent candidates, unused entries and dummy records (p = nullptr)
+template <int W, class Put, class Pos>
+Put PhasePutOf(const PolyDesc* p, uint16_t trash, const Pos& pos) {
+  Put r;
+  for (auto& row : r.off)
+    for (uint16_t& v : row) v = trash;
+  for (int c = 0; c < 12 && p; ++c) {
+    if (p->cand[c] == 0xFFFF) continue;
+    const int j = c / 3, d = c % 3, col = p->xbase + (p->cand[c] & 0xF);
+    for (int i = 0; i < W; ++i) r.off[j][W * d + i] = (uint16_t)(8 * pos(CandRow(d, i), col));
+  }
+  return r;
+}
+
+// dyn_kernel's tables of the dynamic set, fixed timings (device_tables.h)
+struct DynTables {
+  int row = 0;                                 // first row of the set
+  std::vector<DynPolyT> polys_t;
+  std::vector<DynPolyL> polys;
+  std::vector<std::vector<int>> rec_of[2];     // [kind][ee][q] -> record index (kind 0: ee-motion, 1: ee-force)
+  std::vector<DynNodeT> nodes_t;
+  std::vector<DynNodeL> nodes;
+  std::vector<DynSel> sel;
+  std::vector<DynTile> tiles;                  // four per (slice, polynomial combination)
+};
+
+// position in col_idx of column `col` of CSR row `row` (exact) or of the first column after it
+int ColumnPos(const Structure& S, int row, int col, bool exact) {
+  const int32_t* b = S.col_idx.data() + S.row_ptr[row];
+  const int32_t* e = S.col_idx.data() + S.row_ptr[row + 1];
+  const int32_t* it = std::lower_bound(b, e, col);
+  if (exact && (it == e || *it != col)) throw std::runtime_error("dynamic pattern lacks an expected column");
+  return (int)(it - S.col_idx.data());
+}
+
+// candidate scoring: family and bounds of every row (device_tables.h, ScoreTables)
+void PutScoreRecord(const Structure& S, BlobWriter& w, DevStruct& h) {
+  if (S.con_sets.size() > (size_t)kMaxConSets) throw std::runtime_error("too many constraint sets");
+  std::vector<double> pairs;
+  std::map<std::pair<uint64_t, uint64_t>, int> pair_index;   // distinct (lower, upper), by bit pattern
+  std::vector<uint16_t> meta((size_t)S.n_rows, 0);
+  int slot_of[8] = {-1, -1, -1, -1, -1, -1, -1, -1}, n_slots = 0;
+  // (sets in row order: the slots are handed out in the order the families first appear along the rows)
+  std::vector<size_t> by_row(S.con_sets.size());
+  std::iota(by_row.begin(), by_row.end(), (size_t)0);
+  std::sort(by_row.begin(), by_row.end(), [&](size_t a, size_t b) { return S.con_sets[a].offset < S.con_sets[b].offset; });
+  for (size_t i : by_row) {
+    const std::string& nm = S.con_sets[i].name;
+    auto starts = [&](const char* p) { return nm.rfind(p, 0) == 0; };
+    const int fam = starts("terrain-") ? 0 : starts("dynamic") ? 1 : starts("splineacc-") ? 2 : starts("rangeofmotion-") ? 3
+                  : starts("force-") ? 4 : starts("swing-") ? 5 : starts("totalduration-") ? 6 : starts("baseMotion") ? 7 : -1;
+    if (fam < 0) throw std::runtime_error("constraint set of an unknown family");
+    if (S.con_sets[i].size > 0 && slot_of[fam] < 0) slot_of[fam] = n_slots++;
+    if (S.con_sets[i].size > 0 && slot_of[fam] != n_slots - 1) throw std::runtime_error("the sets of a constraint family are not adjacent in g");
+    for (int r = S.con_sets[i].offset; r < S.con_sets[i].offset + S.con_sets[i].size; ++r) {
+      uint64_t kl, ku;
+      std::memcpy(&kl, &S.lower[r], 8);
+      std::memcpy(&ku, &S.upper[r], 8);
+      auto it = pair_index.find({kl, ku});
+      if (it == pair_index.end()) {
+        it = pair_index.emplace(std::make_pair(kl, ku), (int)(pairs.size() / 2)).first;
+        pairs.push_back(S.lower[r]);
+        pairs.push_back(S.upper[r]);
+      }
+      if (it->second >= kScoreMaxPairs) throw std::runtime_error("more than 127 distinct constraint bounds in one structure");
+      meta[r] = (uint16_t)(slot_of[fam] << 12 | it->second);
     }
+  }
+  ScoreTables sc;
+  std::memset(&sc, 0, sizeof(sc));
+  sc.n_rows = S.n_rows;
+  sc.n_pairs = (int)(pairs.size() / 2);
+  for (int f = 0; f < 8; ++f) sc.slot_of_family[f] = (int8_t)slot_of[f];
+  // [ ScoreTables | pairs | zero padding to kScoreHeadBytes ][ meta words ] at a FIXED offset behind the node head: score_kernel
+  // asks for all of it without having seen a single field of the header
+  if (sizeof(sc) + pairs.size() * sizeof(double) > (size_t)kScoreHeadBytes) throw std::runtime_error("score record head overflows");
+  std::vector<char> rec(kScoreHeadBytes + (meta.size() * sizeof(uint16_t) + 15) / 16 * 16, 0);
+  std::memcpy(rec.data(), &sc, sizeof(sc));
+  if (!pairs.empty()) std::memcpy(rec.data() + sizeof(sc), pairs.data(), pairs.size() * sizeof(double));
+  if (!meta.empty()) std::memcpy(rec.data() + kScoreHeadBytes, meta.data(), meta.size() * sizeof(uint16_t));
+  h.o_score = w.Put(rec.data(), rec.size());
+  if (h.o_score != kScoreOff) throw std::runtime_error("score record is not at its fixed offset");
+}
+
+// the node families: force, terrain, splineacc, baseMotion, swing
+void PutNodeFamilies(const Structure& S, BlobWriter& w, DevStruct& h, const std::vector<TerrainRow>& rows, const std::vector<ForceNode>& forces,
+                                const std::vector<SwingNode>& swings) {
+  if (const SetInfo* si = S.FindSet("splineacc-base-lin")) {
+    const SetInfo* sa = S.FindSet("splineacc-base-ang");
+    if (!sa || sa->offset != si->offset + si->size || S.off_base_lin != 0) throw std::runtime_error("splineacc sets not adjacent");
+    h.row_acc = si->offset;
+    h.nnz_acc = si->nnz_offset;
+    h.n_junctions = (int)S.acc_junctions.size();
+  }
+  h.o_force_nodes = w.Put(forces);
+  h.o_terrain_rows = w.Put(rows);
+  h.o_acc = w.Put(S.acc_junctions);
+  if (const SetInfo* si = S.FindSet("baseMotion")) {
+    std::vector<BaseNode> bn(S.grid_bm.size());
+    for (size_t k = 0; k < S.grid_bm.size(); ++k) std::tie(bn[k].t, bn[k].iT, bn[k].q6) = BaseAt(S.base, S.bm_base[k]);
     h.row_bm = si->offset;
     h.nnz_bm = si->nnz_offset;
     h.n_bm_nodes = (int)bn.size();
-    h.o_bm = put(bn.data(), bn.size() * sizeof(BaseNode));
+    h.o_bm = w.Put(bn);
   }
-  h.o_swing_nodes = put(all_swing.data(), all_swing.size() * sizeof(SwingNode));
-  // --- dynamic, optimised timings: the base-spline part of the per-node record (the rest depends on x)
-  if (dyn_set && timings) {
-    std::vector<DynShared> sh(grid_dyn.size());
-    for (size_t k = 0; k < grid_dyn.size(); ++k) {
-      std::memset(&sh[k], 0, sizeof(DynShared));
-      sh[k].tb = dyn_base[k].t_local;
-      sh[k].iTb = 1.0 / base.durations[dyn_base[k].poly];
-      sh[k].q6 = 6 * dyn_base[k].poly;
-      sh[k].voff = row_ptr[row_dyn + 6 * k] - nnz_dyn;
-    }
-    off_dyn_shared = put(sh.data(), sh.size() * sizeof(DynShared));
-  }
-  // --- dynamic, fixed timings: slices, staging maps and per-lane records with every index resolved to an LDS
-  // byte offset (device_tables.h).  The put offsets are read off the CSR pattern itself, so kernel and
-  // pattern cannot disagree.
-  if (dyn_set && !timings) {
-    const int K = (int)grid_dyn.size();
-    auto poly_range = [&](const std::vector<PolyDesc>& pd, int qa, int qb, int& lo, int& hi) {
-      lo = 1 << 30;
-      hi = -1;
-      for (int q = qa; q <= qb; ++q) {
-        const int ns = (int)(pd[q].meta & 0xF);
-        if (!ns) continue;
-        lo = std::min(lo, pd[q].xbase);
-        hi = std::max(hi, pd[q].xbase + ns);
-      }
-      if (hi < 0) lo = hi = 0;
-    };
-    auto stage_count = [&](int k0, int k1) {  // doubles of x the nodes [k0, k1) read
-      int n = 2 * 6 * (dyn_base[k1 - 1].poly - dyn_base[k0].poly + 2);
-      for (int e = 0; e < n_ee; ++e) {
-        int lo, hi;
-        poly_range(mpoly[e], dyn_motion[e][k0].poly, dyn_motion[e][k1 - 1].poly, lo, hi);
-        n += hi - lo;
-        poly_range(fpoly[e], dyn_force[e][k0].poly, dyn_force[e][k1 - 1].poly, lo, hi);
-        n += hi - lo;
-      }
-      return n;
-    };
-    auto nvals_of = [&](int k0, int k1) { return row_ptr[row_dyn + 6 * k1] - row_ptr[row_dyn + 6 * k0]; };
-    // --- DynPolyT / DynPolyL: one record pair per polynomial of every ee spline, ordered by start time, so that the records a slice
-    // (a short time window) reads sit next to each other and an 8-bit index relative to the slice's first record
-    // reaches all of them
-    struct PolyRef {
-      double t0;
-      int e, kind, q;   // kind 0: ee-motion, 1: ee-force
-    };
-    std::vector<PolyRef> order;
-    for (int e = 0; e < n_ee; ++e)
-      for (int kind = 0; kind < 2; ++kind) {
-        const std::vector<double>& dur = kind == 0 ? motion[e].durations : force[e].durations;
-        double t0 = 0.0;   // the running sum Spline::GetSegmentID compares t against (spline.cc:52-57)
-        for (size_t q = 0; q < dur.size(); ++q) {
-          order.push_back({t0, e, kind, (int)q});
-          t0 += dur[q];
-        }
-      }
-    std::stable_sort(order.begin(), order.end(), [](const PolyRef& a, const PolyRef& b) { return a.t0 < b.t0; });
-    std::vector<std::vector<int>> rec_of[2];   // [kind][ee][q] -> record index
+  h.o_swing_nodes = w.Put(swings);
+}
+
+// --- DynPolyT / DynPolyL: one record pair per polynomial of every ee spline, ordered by start time, so that the records a slice
+// (a short time window) reads sit next to each other and an 8-bit index relative to the slice's first record
+// reaches all of them
+void DynPolyRecords(const Structure& S, DynTables& t) {
+  struct PolyRef {
+    double t0;
+    int e, kind, q;   // kind 0: ee-motion, 1: ee-force
+  };
+  std::vector<PolyRef> order;
+  for (auto& r : t.rec_of) r.resize(S.n_ee);
+  for (int e = 0; e < S.n_ee; ++e)
     for (int kind = 0; kind < 2; ++kind) {
-      rec_of[kind].resize(n_ee);
-      for (int e = 0; e < n_ee; ++e) rec_of[kind][e].resize(kind == 0 ? mpoly[e].size() : fpoly[e].size());
+      const std::vector<double> t0 = StartTimes(kind == 0 ? S.motion[e].durations : S.force[e].durations);
+      for (size_t q = 0; q + 1 < t0.size(); ++q) order.push_back({t0[q], e, kind, (int)q});
+      t.rec_of[kind][e].resize(t0.size() - 1);
     }
-    std::vector<DynPolyT> polys_t(order.size());
-    std::vector<DynPolyL> polys(order.size());
-    for (size_t i = 0; i < order.size(); ++i) {
-      const PolyRef& pr = order[i];
-      rec_of[pr.kind][pr.e][pr.q] = (int)i;
-      const PolyDesc& pd = pr.kind == 0 ? mpoly[pr.e][pr.q] : fpoly[pr.e][pr.q];
-      polys_t[i].t0 = pr.t0;
-      polys_t[i].iT = pd.iT;
-      DynPolyL& P = polys[i];
-      std::memset(&P, 0, sizeof(P));
-      int dim_of_slot[12] = {0}, slot_of[12];
+  std::stable_sort(order.begin(), order.end(), [](const PolyRef& a, const PolyRef& b) { return a.t0 < b.t0; });
+  t.polys_t.resize(order.size());
+  t.polys.resize(order.size());
+  for (size_t i = 0; i < order.size(); ++i) {
+    const PolyRef& pr = order[i];
+    t.rec_of[pr.kind][pr.e][pr.q] = (int)i;
+    const PolyDesc& pd = pr.kind == 0 ? S.mpoly[pr.e][pr.q] : S.fpoly[pr.e][pr.q];
+    t.polys_t[i].t0 = pr.t0;
+    t.polys_t[i].iT = pd.iT;
+    DynPolyL& P = t.polys[i];
+    int slot_of[12];
+    for (int c = 0; c < 12; ++c) {
+      slot_of[c] = pd.cand[c] == 0xFFFF ? -1 : (pd.cand[c] & 0xF);
+      if (slot_of[c] >= 0) {
+        P.rel[c] = (uint8_t)slot_of[c];
+        P.pres[c] = 0xFF;
+      }
+    }
+    // 8 * the position of candidate src's slot among the slots of its two angular rows / its linear row: the ranks MakeEePoly
+    // stored in PolyDesc::cand, valid here because every src below has the dimension of the candidate c it stands in for
+    auto code = [&](int src, int r) { return (uint8_t)(8 * ((pd.cand[src] >> (4 + 4 * r)) & 0xF)); };
+    if (pr.kind == 0) {
+      if ((pd.meta >> 16) & 1) P.flags |= 1;
+      for (int d = 0; d < 3; ++d)
+        if (slot_of[d] < 0) throw std::runtime_error("ee-motion node position that is not a variable");
       for (int c = 0; c < 12; ++c) {
-        slot_of[c] = pd.cand[c] == 0xFFFF ? -1 : (pd.cand[c] & 0xF);
-        if (slot_of[c] >= 0) {
-          P.rel[c] = (uint8_t)slot_of[c];
-          P.pres[c] = 0xFF;
-          dim_of_slot[slot_of[c]] = c % 3;
-        }
+        const int src = slot_of[c] >= 0 ? c : c % 3;   // not a variable: p0's slots (stored last by the kernel)
+        for (int r = 0; r < 2; ++r) P.code[2 * c + r] = code(src, r);
       }
-      const int nslots = pd.meta & 0xF;
-      auto rank = [&](int slot, int row_dim, bool equal) {   // position of the slot among the slots a row holds
-        int r = 0;
-        for (int s2 = 0; s2 < slot; ++s2) r += (dim_of_slot[s2] == row_dim) == equal;
-        return r;
-      };
-      if (pr.kind == 0) {
-        if ((pd.meta >> 16) & 1) P.flags |= 1;
-        for (int d = 0; d < 3; ++d)
-          if (slot_of[d] < 0) throw std::runtime_error("ee-motion node position that is not a variable");
-        for (int c = 0; c < 12; ++c) {
-          const int d = c % 3, src = slot_of[c] >= 0 ? c : d;   // not a variable: p0's slots (stored last by the kernel)
-          P.code[2 * c + 0] = (uint8_t)(8 * rank(slot_of[src], (d + 1) % 3, false));
-          P.code[2 * c + 1] = (uint8_t)(8 * rank(slot_of[src], (d + 2) % 3, false));
-        }
-      } else {
-        bool present[4];
-        for (int j = 0; j < 4; ++j) {
-          present[j] = slot_of[3 * j] >= 0;
-          for (int d = 1; d < 3; ++d)
-            if ((slot_of[3 * j + d] >= 0) != present[j]) throw std::runtime_error("ee-force node value that is a variable in some dimensions only");
-        }
-        if (present[0] != present[1] || present[2] != present[3]) throw std::runtime_error("ee-force node with a constant position or velocity only");
-        if (!present[0]) P.flags |= 2;
-        if (!present[2]) P.flags |= 4;
-        for (int c = 0; c < 12; ++c) {
-          const int d = c % 3, j = c / 3;
-          if (nslots == 0) continue;                      // no variables at all: codes 0, the tile starts point at trash
-          const int src = present[j] ? c : (j ^ 2) * 3 + d;   // constant node: the other node's value of the same kind
-          if (slot_of[src] < 0) throw std::runtime_error("ee-force polynomial layout not understood");
-          P.code[3 * c + 0] = (uint8_t)(8 * rank(slot_of[src], (d + 1) % 3, false));
-          P.code[3 * c + 1] = (uint8_t)(8 * rank(slot_of[src], (d + 2) % 3, false));
-          P.code[3 * c + 2] = (uint8_t)(8 * rank(slot_of[src], d, true));
-        }
-      }
+      continue;
     }
-    auto rec_span_ok = [&](int k0, int k1) {   // the 8-bit record indices of a slice (255 = dummy)
-      int lo = 1 << 30, hi = -1;
-      for (int e = 0; e < n_ee; ++e)
-        for (int k : {k0, k1 - 1}) {
-          lo = std::min({lo, rec_of[0][e][dyn_motion[e][k0].poly], rec_of[1][e][dyn_force[e][k0].poly]});
-          hi = std::max({hi, rec_of[0][e][dyn_motion[e][k].poly], rec_of[1][e][dyn_force[e][k].poly]});
+    bool present[4];
+    for (int j = 0; j < 4; ++j) {
+      present[j] = slot_of[3 * j] >= 0;
+      for (int d = 1; d < 3; ++d)
+        if ((slot_of[3 * j + d] >= 0) != present[j]) throw std::runtime_error("ee-force node value that is a variable in some dimensions only");
+    }
+    if (present[0] != present[1] || present[2] != present[3]) throw std::runtime_error("ee-force node with a constant position or velocity only");
+    if (!present[0]) P.flags |= 2;
+    if (!present[2]) P.flags |= 4;
+    for (int c = 0; c < 12; ++c) {
+      const int d = c % 3, j = c / 3;
+      if ((pd.meta & 0xF) == 0) continue;             // no variables at all: codes 0, the tile starts point at trash
+      const int src = present[j] ? c : (j ^ 2) * 3 + d;   // constant node: the other node's value of the same kind
+      if (slot_of[src] < 0) throw std::runtime_error("ee-force polynomial layout not understood");
+      for (int r = 0; r < 3; ++r) P.code[3 * c + r] = code(src, r);
+    }
+  }
+}
+
+// the per-node records of one dynamic slice and the tile records of its polynomial combinations (shift: PutDynTables' stage)
+void DynSliceNodes(const Structure& S, DynTables& t, const Structure::DynSlice& sl, const int (&shift)[2][kMaxEE]) {
+  const int qmin = S.dyn_base[sl.k0].poly, nbase = 6 * (S.dyn_base[sl.k0 + sl.cnt - 1].poly - qmin + 2);   // base-lin doubles staged
+  std::vector<int> combo_key;   // active polynomial ids of the last combination: a new slice has its own staging layout, its
+                                // first node opens a new combination
+  for (int k = sl.k0; k < sl.k0 + sl.cnt; ++k) {
+    const int row0 = t.row + 6 * k, v0 = S.row_ptr[row0];
+    DynNodeL& N = t.nodes[k];
+    t.nodes_t[k].t = S.grid_dyn[k];
+    std::tie(t.nodes_t[k].tb, t.nodes_t[k].iTb, std::ignore) = BaseAt(S.base, S.dyn_base[k]);
+    N.sb_lin = (uint16_t)(8 * (2 + 6 * (S.dyn_base[k].poly - qmin)));
+    N.sb_ang = (uint16_t)(8 * (2 + nbase + 6 * (S.dyn_base[k].poly - qmin)));
+    const int node_rel = v0 - S.row_ptr[t.row + 6 * sl.k0];
+    N.nb = (uint16_t)(8 * node_rel);
+    N.rs1 = (uint16_t)(8 * (S.row_ptr[row0 + 1] - v0));
+    N.rs2 = (uint16_t)(8 * (S.row_ptr[row0 + 2] - v0));
+    for (int d = 0; d < 3; ++d) N.rl[d] = (uint16_t)(8 * (S.row_ptr[row0 + 3 + d] - v0));
+    // where a tile starts in a row, relative to the node's first value: the position of the polynomial's first
+    // variable in the CSR row (read off the pattern itself, so kernel and pattern cannot disagree)
+    auto pos = [&](int row, int col, bool exact) { return ColumnPos(S, row0 + row, col, exact) - v0; };
+    // the tile starts depend on the node only through the active polynomials: one record set per combination
+    std::vector<int> key;
+    for (int e = 0; e < S.n_ee; ++e) {
+      key.push_back(S.dyn_motion[e][k].poly);
+      key.push_back(S.dyn_force[e][k].poly);
+    }
+    const bool new_combo = key != combo_key;
+    if (new_combo) {
+      combo_key = key;
+      t.tiles.resize(t.tiles.size() + 4);
+    }
+    const size_t tile0 = t.tiles.size() - 4;
+    if (tile0 + 3 > 0xFFFF) throw std::runtime_error("too many polynomial combinations for 16-bit tile indices");
+    for (int role = 0; role < 4; ++role) {
+      DynSel& Sx = t.sel[(size_t)k * 4 + role];
+      DynTile T = {};
+      Sx.tile = (uint16_t)(tile0 + role);
+      Sx.dm = Sx.df = (uint8_t)kDynPolyDummy;
+      // trash: base-lin entry `role` of every row (the rows' first four entries are base-lin values, which the same
+      // wave writes after the tiles); the dummy record's codes are 0
+      const int row_start[6] = {0, N.rs1, N.rs2, N.rl[0], N.rl[1], N.rl[2]};
+      for (int r = 0; r < 3; ++r) T.base_m[r] = (uint16_t)(row_start[r] + 8 * role);
+      for (int r = 0; r < 6; ++r) T.base_f[r] = (uint16_t)(row_start[r] + 8 * role);
+      if (role < S.n_ee) {
+        const int e = role;
+        const int qm = S.dyn_motion[e][k].poly, qf = S.dyn_force[e][k].poly;
+        const PolyDesc& mp = S.mpoly[e][qm];
+        const PolyDesc& fp = S.fpoly[e][qf];
+        const int rm = t.rec_of[0][e][qm], rf = t.rec_of[1][e][qf];
+        Sx.dm = (uint8_t)(rm - sl.poly0);
+        Sx.df = (uint8_t)(rf - sl.poly0);
+        if (rm - sl.poly0 >= kDynPolyDummy || rf - sl.poly0 >= kDynPolyDummy || rm < sl.poly0 || rf < sl.poly0)
+          throw std::runtime_error("polynomial record index does not fit the slice");
+        T.s_m = (uint8_t)(shift[0][e] + mp.xbase);
+        if ((mp.meta & 0xF) == 0) throw std::runtime_error("ee-motion polynomial without variables");
+        for (int r = 0; r < 3; ++r) T.base_m[r] = (uint16_t)(8 * pos(r, mp.xbase, false));
+        if ((fp.meta & 0xF) != 0) {
+          T.s_f = (uint8_t)(shift[1][e] + fp.xbase);
+          for (int r = 0; r < 6; ++r) T.base_f[r] = (uint16_t)(8 * pos(r, fp.xbase, false));
         }
-      return hi - lo < kDynPolyDummy;
-    };
-    std::vector<DynNodeT> nodes_t(K);
-    std::vector<DynNodeL> nodes(K);
-    std::vector<DynSel> sel((size_t)K * 4);
-    std::vector<DynTile> tiles;   // four per (slice, polynomial combination)
-    std::vector<int> combo_key;   // active polynomial ids of the last combination
-    dyn_slices.clear();
-    dyn_staged_max = 0;
-    // Slices that stage at most 128 doubles of x read the 256-byte form of their staging map and gather x with two loads per
-    // lane instead of four (dyn_body XC = 2) -- if EVERY slice of a batch does.  Fine discretisations do anyway (a 12..15-node
-    // slice of a K = 200 problem stages 90-130); where the general capacity would let a few slices stage a little more, they
-    // are cut at 128 instead, as long as that costs at most one more slice per eight.
-    auto count_slices = [&](int cap) {
-      int n = 0;
-      for (int k0 = 0; k0 < K; ++n) {
-        int k1 = k0;
-        while (k1 < K && k1 - k0 < kDynNodes && nvals_of(k0, k1 + 1) <= kDynImage && stage_count(k0, k1 + 1) <= cap && rec_span_ok(k0, k1 + 1)) ++k1;
-        if (k1 == k0) return 1 << 30;
-        k0 = k1;
+        // self-check of the decomposition  offset = tile start + 8 * rank  against the pattern, value by value (once per
+        // polynomial combination: the nodes of a combination share their tile records, asserted below)
+        auto check = [&](const PolyDesc& p, const uint16_t* tile, const DynPolyL& P, int W, const char* what) {
+          for (int c = 0; c < 12 && new_combo; ++c)
+            for (int i = 0; i < W && p.cand[c] != 0xFFFF; ++i) {
+              const int row = CandRow(c % 3, i);
+              if (tile[row] + P.code[W * c + i] != 8 * pos(row, p.xbase + (p.cand[c] & 0xF), true)) throw std::runtime_error(what);
+            }
+        };
+        check(mp, T.base_m, t.polys[rm], 2, "ee-motion tile offsets disagree with the CSR pattern");
+        check(fp, T.base_f, t.polys[rf], 3, "ee-force tile offsets disagree with the CSR pattern");
       }
+      if (!new_combo && std::memcmp(&t.tiles[tile0 + role], &T, sizeof(T)) != 0)
+        throw std::runtime_error("tile starts differ inside one polynomial combination");
+      t.tiles[tile0 + role] = T;
+    }
+  }
+}
+
+// --- dynamic, fixed timings: slices, staging maps and per-lane records with every index resolved to an LDS
+// byte offset (device_tables.h).  The put offsets are read off the CSR pattern itself, so kernel and
+// pattern cannot disagree.
+void PutDynTables(Structure& S, BlobWriter& w) {
+  const SetInfo* dyn = S.FindSet("dynamic");
+  if (!dyn) return;
+  const int K = (int)S.grid_dyn.size();
+  DynTables t;
+  t.row = dyn->offset;
+  DynPolyRecords(S, t);
+  // the doubles of x the nodes [k0, k1) read, in staging order (xs index 2 + entry): the nodes of their base-lin, then base-ang
+  // polynomials, then the variables of each ee's active motion (kind 0) and force (kind 1) polynomials.  With `xidx`: the
+  // x index of every entry, and shift[kind][e] such that x index i of that ee range is staged at xs index i + shift
+  auto stage = [&](int k0, int k1, std::vector<int>* xidx, int (*shift)[kMaxEE]) {
+    const int qmin = S.dyn_base[k0].poly, nbase = 6 * (S.dyn_base[k1 - 1].poly - qmin + 2);
+    for (int i = 0; xidx && i < nbase; ++i) xidx->push_back(S.off_base_lin + 6 * qmin + i);
+    for (int i = 0; xidx && i < nbase; ++i) xidx->push_back(S.off_base_ang + 6 * qmin + i);
+    int n = 2 * nbase;
+    for (int e = 0; e < S.n_ee; ++e)
+      for (int kind = 0; kind < 2; ++kind) {
+        const std::vector<PolyDesc>& pd = kind == 0 ? S.mpoly[e] : S.fpoly[e];
+        const std::vector<TimeNode>& at = kind == 0 ? S.dyn_motion[e] : S.dyn_force[e];
+        int lo = 1 << 30, hi = -1;
+        for (int q = at[k0].poly; q <= at[k1 - 1].poly; ++q) {
+          const int ns = (int)(pd[q].meta & 0xF);
+          if (!ns) continue;
+          lo = std::min(lo, pd[q].xbase);
+          hi = std::max(hi, pd[q].xbase + ns);
+        }
+        if (hi < 0) lo = hi = 0;
+        if (xidx) shift[kind][e] = 2 + n - lo;
+        for (int i = lo; xidx && i < hi; ++i) xidx->push_back(i);
+        n += hi - lo;
+      }
+    return n;
+  };
+  auto nvals_of = [&](int k0, int k1) { return S.row_ptr[t.row + 6 * k1] - S.row_ptr[t.row + 6 * k0]; };
+  auto first_rec = [&](int k) {   // the first polynomial record time node k reads
+    int lo = 1 << 30;
+    for (int e = 0; e < S.n_ee; ++e) lo = std::min({lo, t.rec_of[0][e][S.dyn_motion[e][k].poly], t.rec_of[1][e][S.dyn_force[e][k].poly]});
+    return lo;
+  };
+  auto rec_span_ok = [&](int k0, int k1) {   // the 8-bit record indices of a slice (255 = dummy)
+    int hi = -1;
+    for (int e = 0; e < S.n_ee; ++e)
+      for (int k : {k0, k1 - 1}) hi = std::max({hi, t.rec_of[0][e][S.dyn_motion[e][k].poly], t.rec_of[1][e][S.dyn_force[e][k].poly]});
+    return hi - first_rec(k0) < kDynPolyDummy;
+  };
+  t.nodes_t.resize(K);
+  t.nodes.resize(K);
+  t.sel.resize((size_t)K * 4);
+  S.dyn_slices.clear();
+  S.dyn_staged_max = 0;
+  // Slices that stage at most 128 doubles of x read the 256-byte form of their staging map and gather x with two loads per
+  // lane instead of four (dyn_body XC = 2) -- if EVERY slice of a batch does.  Fine discretisations do anyway (a 12..15-node
+  // slice of a K = 200 problem stages 90-130); where the general capacity would let a few slices stage a little more, they
+  // are cut at 128 instead, as long as that costs at most one more slice per eight.
+  auto cut = [&](int cap) {
+    return CutRuns(K, [&](int k0, int k1) {
+      return k1 - k0 <= kDynNodes && nvals_of(k0, k1) <= kDynImage && stage(k0, k1, nullptr, nullptr) <= cap && rec_span_ok(k0, k1);
+    });
+  };
+  const auto general = cut(kDynXsCap), small = cut(std::min(kDynXsCap, 128));
+  const int n_general = general.empty() ? 1 << 30 : (int)general.size(), n_small = small.empty() ? 1 << 30 : (int)small.size();
+  const auto& runs = n_small <= n_general + (n_general + 7) / 8 ? small : general;
+  if (runs.empty()) throw std::runtime_error("one time node of the dynamic set exceeds the LDS staging capacity");
+  for (const auto& run : runs) {
+    const int k0 = run.first, k1 = run.first + run.second;
+    if (nvals_of(k0, k1) < 16) throw std::runtime_error("a time-node run with fewer than 16 Jacobian values cannot be staged");
+    // staging layout of the slice
+    std::vector<int> xidx;
+    int shift[2][kMaxEE];
+    stage(k0, k1, &xidx, shift);
+    if ((int)xidx.size() > kDynXsCap) throw std::runtime_error("staging count inconsistent");
+    for (int x : xidx)
+      if (x < 0 || x > 0xFFFF) throw std::runtime_error("x index does not fit the staging map");
+    auto staging_map = [&](int chunks) {   // lane l holds entries l, 64 + l, ...; unused entries stage x[0] (harmless)
+      std::vector<uint16_t> map(64 * chunks, 0);
+      for (size_t e = 0; e < xidx.size(); ++e) map[(e % 64) * chunks + e / 64] = (uint16_t)xidx[e];
+      return map;
+    };
+    Structure::DynSlice sl;
+    sl.k0 = k0;
+    sl.cnt = k1 - k0;
+    sl.nvals = nvals_of(k0, k1);
+    sl.map = w.PutLayout(staging_map(4));
+    sl.map2 = sl.map;
+    S.dyn_staged_max = std::max(S.dyn_staged_max, (int)xidx.size());
+    if (xidx.size() <= 128) sl.map2 = w.PutLayout(staging_map(2));   // the 256-byte form (what a batch of such slices reads)
+    sl.poly0 = first_rec(k0);
+    S.dyn_slices.push_back(sl);
+    DynSliceNodes(S, t, sl, shift);
+  }
+  // times first, then the layout tables (twr_batch_create stores byte-identical layout tables of a batch once)
+  S.off_dyn_nodes_t = w.Put(t.nodes_t);
+  S.off_dyn_poly_t = w.Put(t.polys_t);
+  S.off_dyn_nodes_l = w.PutLayout(t.nodes);
+  S.off_dyn_sel = w.PutLayout(t.sel);
+  S.off_dyn_tile = w.PutLayout(t.tiles);
+  S.off_dyn_poly_l = w.PutLayout(t.polys);
+}
+
+// --- rangeofmotion-<ee>, fixed timings: per-node records shared by all ee, slices, per-(slice, polynomial) segments
+void PutRomTables(Structure& S, BlobWriter& w) {
+  if (!S.FindSet("rangeofmotion-0")) return;
+  const int K = (int)S.grid_rom.size();
+  std::vector<RomNode> nodes(K);
+  for (int k = 0; k < K; ++k) {
+    nodes[k].t = S.grid_rom[k];
+    std::tie(nodes[k].tb, nodes[k].iTb, nodes[k].q6) = BaseAt(S.base, S.rom_base[k]);
+  }
+  for (int e = 0; e < S.n_ee; ++e) {
+    const int row0 = S.FindSet("rangeofmotion-" + std::to_string(e))->offset;
+    auto vals = [&](int k0, int k1) { return S.row_ptr[row0 + 3 * k1] - S.row_ptr[row0 + 3 * k0]; };
+    auto segs = [&](int k0, int k1) {   // polynomials of the ee spline active in nodes [k0, k1)
+      int n = 1;
+      for (int k = k0 + 1; k < k1; ++k) n += S.rom_motion[e][k].poly != S.rom_motion[e][k - 1].poly;
       return n;
     };
-    const int n_general = count_slices(kDynXsCap), n_small = count_slices(std::min(kDynXsCap, 128));
-    const int xs_cap = n_small <= n_general + (n_general + 7) / 8 ? std::min(kDynXsCap, 128) : kDynXsCap;
-    for (int k0 = 0; k0 < K;) {
-      int k1 = k0;
-      while (k1 < K && k1 - k0 < kDynNodes && nvals_of(k0, k1 + 1) <= kDynImage && stage_count(k0, k1 + 1) <= xs_cap &&
-             rec_span_ok(k0, k1 + 1))
-        ++k1;
-      if (k1 == k0) throw std::runtime_error("one time node of the dynamic set exceeds the LDS staging capacity");
-      if (nvals_of(k0, k1) < 16) throw std::runtime_error("a time-node run with fewer than 16 Jacobian values cannot be staged");
-      // staging layout of the slice: xs index 2 + e
-      std::vector<uint16_t> map(256, 0);   // lane-transposed below; unused entries stage x[0] (harmless)
-      std::vector<int> xidx;               // x index of staging entry e
-      const int qmin = dyn_base[k0].poly, nbase = 6 * (dyn_base[k1 - 1].poly - qmin + 2);
-      for (int i = 0; i < nbase; ++i) xidx.push_back(off_base_lin + 6 * qmin + i);
-      for (int i = 0; i < nbase; ++i) xidx.push_back(off_base_ang + 6 * qmin + i);
-      int mlo[kMaxEE], mst[kMaxEE], flo[kMaxEE], fst[kMaxEE];   // first x index / staging entry of every ee range
-      for (int e = 0; e < n_ee; ++e) {
-        int hi;
-        poly_range(mpoly[e], dyn_motion[e][k0].poly, dyn_motion[e][k1 - 1].poly, mlo[e], hi);
-        mst[e] = (int)xidx.size();
-        for (int i = mlo[e]; i < hi; ++i) xidx.push_back(i);
-        poly_range(fpoly[e], dyn_force[e][k0].poly, dyn_force[e][k1 - 1].poly, flo[e], hi);
-        fst[e] = (int)xidx.size();
-        for (int i = flo[e]; i < hi; ++i) xidx.push_back(i);
+    // Balanced runs: the fewest runs that respect the limits (<= 64 time nodes = lanes, the LDS image, kRomMaxSeg
+    // polynomials), of (nearly) equal length -- K = 200 gives 4 x 50 rather than 64 + 64 + 64 + 8: the kernel has a
+    // compile-time number of copy-out stores and pays the full count for a short tail run too.
+    auto cut = [&](int limit) {
+      return CutRuns(K, [&](int k0, int k1) { return k1 - k0 <= limit && vals(k0, k1) <= kRomStage && segs(k0, k1) <= kRomMaxSeg; });
+    };
+    std::vector<std::pair<int, int>> best = cut(64);
+    if (best.empty()) throw std::runtime_error("one time node exceeds the LDS staging capacity");
+    for (int limit = (K + (int)best.size() - 1) / (int)best.size(); limit < 64; ++limit) {
+      auto runs = cut(limit);   // the smallest run length that still needs no more runs
+      if (runs.size() == best.size()) {
+        best = std::move(runs);
+        break;
       }
-      if ((int)xidx.size() > kDynXsCap) throw std::runtime_error("staging count inconsistent");
-      for (size_t e = 0; e < xidx.size(); ++e) {
-        if (xidx[e] < 0 || xidx[e] > 0xFFFF) throw std::runtime_error("x index does not fit the staging map");
-        map[(e % 64) * 4 + e / 64] = (uint16_t)xidx[e];
-      }
-      DynSlice sl;
-      sl.k0 = k0;
-      sl.cnt = k1 - k0;
-      sl.nvals = nvals_of(k0, k1);
-      sl.map = put_layout(map.data(), map.size() * sizeof(uint16_t));
-      sl.map2 = sl.map;
-      dyn_staged_max = std::max(dyn_staged_max, (int)xidx.size());
-      if (xidx.size() <= 128) {   // the 256-byte form: lane l holds entries l and 64 + l (what a batch of such slices reads)
-        std::vector<uint16_t> m2(128, 0);
-        for (size_t e = 0; e < xidx.size(); ++e) m2[(e % 64) * 2 + e / 64] = (uint16_t)xidx[e];
-        sl.map2 = put_layout(m2.data(), m2.size() * sizeof(uint16_t));
-      }
-      sl.poly0 = 1 << 30;
-      for (int e = 0; e < n_ee; ++e)
-        sl.poly0 = std::min({sl.poly0, rec_of[0][e][dyn_motion[e][k0].poly], rec_of[1][e][dyn_force[e][k0].poly]});
-      dyn_slices.push_back(sl);
-      combo_key.clear();   // a new slice has its own staging layout: its first node opens a new combination
-      for (int k = k0; k < k1; ++k) {
-        const int row0 = row_dyn + 6 * k, v0 = row_ptr[row0];
-        DynNodeL& N = nodes[k];
-        std::memset(&N, 0, sizeof(N));
-        nodes_t[k].t = grid_dyn[k];
-        nodes_t[k].tb = dyn_base[k].t_local;
-        nodes_t[k].iTb = 1.0 / base.durations[dyn_base[k].poly];
-        N.sb_lin = (uint16_t)(8 * (2 + 6 * (dyn_base[k].poly - qmin)));
-        N.sb_ang = (uint16_t)(8 * (2 + nbase + 6 * (dyn_base[k].poly - qmin)));
-        const int node_rel = v0 - row_ptr[row_dyn + 6 * k0];
-        N.nb = (uint16_t)(8 * node_rel);
-        N.rs1 = (uint16_t)(8 * (row_ptr[row0 + 1] - v0));
-        N.rs2 = (uint16_t)(8 * (row_ptr[row0 + 2] - v0));
-        for (int d = 0; d < 3; ++d) N.rl[d] = (uint16_t)(8 * (row_ptr[row0 + 3 + d] - v0));
-        // where a tile starts in a row, relative to the node's first value: the position of the polynomial's first
-        // variable in the CSR row (read off the pattern itself, so kernel and pattern cannot disagree)
-        auto tile_start = [&](int row, int col) -> int {
-          const int32_t* b = col_idx.data() + row_ptr[row0 + row];
-          const int32_t* e2 = col_idx.data() + row_ptr[row0 + row + 1];
-          return (int)(std::lower_bound(b, e2, col) - col_idx.data()) - v0;
-        };
-        auto find = [&](int row, int col) -> int {  // position of `col` in row `row`, relative to the node's first value
-          const int32_t* b = col_idx.data() + row_ptr[row0 + row];
-          const int32_t* e2 = col_idx.data() + row_ptr[row0 + row + 1];
-          const int32_t* it = std::lower_bound(b, e2, col);
-          if (it == e2 || *it != col) throw std::runtime_error("dynamic pattern lacks an expected column");
-          return (int)(it - col_idx.data()) - v0;
-        };
-        // the tile starts depend on the node only through the active polynomials: one record set per combination
-        std::vector<int> key;
-        for (int e = 0; e < n_ee; ++e) {
-          key.push_back(dyn_motion[e][k].poly);
-          key.push_back(dyn_force[e][k].poly);
-        }
-        const bool new_combo = key != combo_key;
-        if (new_combo) {
-          combo_key = key;
-          tiles.resize(tiles.size() + 4);
-        }
-        const size_t tile0 = tiles.size() - 4;
-        if (tile0 + 3 > 0xFFFF) throw std::runtime_error("too many polynomial combinations for 16-bit tile indices");
-        for (int role = 0; role < 4; ++role) {
-          DynSel& Sx = sel[(size_t)k * 4 + role];
-          DynTile T;
-          std::memset(&T, 0, sizeof(T));
-          Sx.tile = (uint16_t)(tile0 + role);
-          Sx.dm = Sx.df = (uint8_t)kDynPolyDummy;
-          // trash: base-lin entry `role` of every row (the rows' first four entries are base-lin values, which the same
-          // wave writes after the tiles); the dummy record's codes are 0
-          const int row_start[6] = {0, N.rs1, N.rs2, N.rl[0], N.rl[1], N.rl[2]};
-          for (int r = 0; r < 3; ++r) T.base_m[r] = (uint16_t)(row_start[r] + 8 * role);
-          for (int r = 0; r < 6; ++r) T.base_f[r] = (uint16_t)(row_start[r] + 8 * role);
-          if (role < n_ee) {
-            const int e = role;
-            const int qm = dyn_motion[e][k].poly, qf = dyn_force[e][k].poly;
-            const PolyDesc& mp = mpoly[e][qm];
-            const PolyDesc& fp = fpoly[e][qf];
-            Sx.dm = (uint8_t)(rec_of[0][e][qm] - sl.poly0);
-            Sx.df = (uint8_t)(rec_of[1][e][qf] - sl.poly0);
-            if (rec_of[0][e][qm] - sl.poly0 >= kDynPolyDummy || rec_of[1][e][qf] - sl.poly0 >= kDynPolyDummy || rec_of[0][e][qm] < sl.poly0 ||
-                rec_of[1][e][qf] < sl.poly0)
-              throw std::runtime_error("polynomial record index does not fit the slice");
-            T.s_m = (uint8_t)(2 + mst[e] + mp.xbase - mlo[e]);
-            if ((mp.meta & 0xF) == 0) throw std::runtime_error("ee-motion polynomial without variables");
-            for (int r = 0; r < 3; ++r) T.base_m[r] = (uint16_t)(8 * tile_start(r, mp.xbase));
-            if ((fp.meta & 0xF) != 0) {
-              T.s_f = (uint8_t)(2 + fst[e] + fp.xbase - flo[e]);
-              for (int r = 0; r < 6; ++r) T.base_f[r] = (uint16_t)(8 * tile_start(r, fp.xbase));
-            }
-            // self-check of the decomposition  offset = tile start + 8 * rank  against the pattern, value by value (once per
-            // polynomial combination: the nodes of a combination share their tile records, asserted below)
-            const DynPolyL& PM = polys[rec_of[0][e][qm]];
-            const DynPolyL& PF = polys[rec_of[1][e][qf]];
-            for (int c = 0; c < 12 && new_combo; ++c) {
-              const int d = c % 3, r1 = (d + 1) % 3, r2 = (d + 2) % 3;
-              if (mp.cand[c] != 0xFFFF) {
-                const int col = mp.xbase + (mp.cand[c] & 0xF);
-                if (T.base_m[r1] + PM.code[2 * c] != 8 * find(r1, col) || T.base_m[r2] + PM.code[2 * c + 1] != 8 * find(r2, col))
-                  throw std::runtime_error("ee-motion tile offsets disagree with the CSR pattern");
-              }
-              if (fp.cand[c] != 0xFFFF) {
-                const int col = fp.xbase + (fp.cand[c] & 0xF);
-                if (T.base_f[r1] + PF.code[3 * c] != 8 * find(r1, col) || T.base_f[r2] + PF.code[3 * c + 1] != 8 * find(r2, col) ||
-                    T.base_f[3 + d] + PF.code[3 * c + 2] != 8 * find(3 + d, col))
-                  throw std::runtime_error("ee-force tile offsets disagree with the CSR pattern");
-              }
-            }
-          }
-          if (!new_combo && std::memcmp(&tiles[tile0 + role], &T, sizeof(T)) != 0)
-            throw std::runtime_error("tile starts differ inside one polynomial combination");
-          tiles[tile0 + role] = T;
-        }
-      }
-      k0 = k1;
     }
-    // times first, then the layout tables (twr_batch_create stores byte-identical layout tables of a batch once)
-    off_dyn_nodes_t = put(nodes_t.data(), nodes_t.size() * sizeof(DynNodeT));
-    off_dyn_poly_t = put(polys_t.data(), polys_t.size() * sizeof(DynPolyT));
-    off_dyn_nodes_l = put_layout(nodes.data(), nodes.size() * sizeof(DynNodeL));
-    off_dyn_sel = put_layout(sel.data(), sel.size() * sizeof(DynSel));
-    off_dyn_tile = put_layout(tiles.data(), tiles.size() * sizeof(DynTile));
-    off_dyn_poly_l = put_layout(polys.data(), polys.size() * sizeof(DynPolyL));
-  }
-  // --- rangeofmotion-<ee>, optimised timings: per-node record templates (the pre-pass fills in the x-dependent part)
-  for (int e = 0; e < n_ee && have_rom && timings; ++e) {
-    std::vector<RomRec> rc(grid_rom.size());
-    for (size_t k = 0; k < grid_rom.size(); ++k) {
-      RomRec& R = rc[k];
-      std::memset(&R, 0, sizeof(R));
-      const PolyDesc& mp = mpoly[e][rom_motion[e][k].poly];
-      R.tb = rom_base[k].t_local;
-      R.iTb = 1.0 / base.durations[rom_base[k].poly];
-      R.tm = rom_motion[e][k].t_local;
-      R.iTm = mp.iT;
-      R.q6 = 6 * rom_base[k].poly;
-      R.xbase = mp.xbase;
-      R.voff = row_ptr[row_rom[e] + 3 * k] - nnz_rom[e];
-      R.meta = mp.meta;
-      uint64_t slots = 0;
-      for (int c = 0; c < 12; ++c) slots |= (uint64_t)(mp.cand[c] & 0xF) << (4 * c);
-      R.slots[0] = (uint32_t)slots;
-      R.slots[1] = (uint32_t)(slots >> 32);
-    }
-    off_rom_recs[e] = put(rc.data(), rc.size() * sizeof(RomRec));
-  }
-  // --- rangeofmotion-<ee>, fixed timings: per-node records shared by all ee, slices, per-(slice, polynomial) segments
-  rom_slices.assign(n_ee, {});
-  if (have_rom && !timings) {
-    const int K = (int)grid_rom.size();
-    std::vector<RomNode> nodes(K);
-    for (int k = 0; k < K; ++k) {
-      std::memset(&nodes[k], 0, sizeof(RomNode));
-      nodes[k].t = grid_rom[k];
-      nodes[k].tb = rom_base[k].t_local;
-      nodes[k].iTb = 1.0 / base.durations[rom_base[k].poly];
-      nodes[k].q6 = 6 * rom_base[k].poly;
-    }
-    for (int e = 0; e < n_ee; ++e) {
-      const int row0 = row_rom[e];
-      auto vals = [&](int k0, int k1) { return row_ptr[row0 + 3 * k1] - row_ptr[row0 + 3 * k0]; };
-      auto segs = [&](int k0, int k1) {   // polynomials of the ee spline active in nodes [k0, k1)
-        int n = 1;
-        for (int k = k0 + 1; k < k1; ++k) n += rom_motion[e][k].poly != rom_motion[e][k - 1].poly;
-        return n;
-      };
-      // Balanced runs: the fewest runs that respect the limits (<= 64 time nodes = lanes, the LDS image, kRomMaxSeg
-      // polynomials), of (nearly) equal length -- K = 200 gives 4 x 50 rather than 64 + 64 + 64 + 8: the kernel has a
-      // compile-time number of copy-out stores and pays the full count for a short tail run too.
-      auto greedy = [&](int limit, std::vector<std::pair<int, int>>& out) {
-        out.clear();
-        for (int k0 = 0; k0 < K;) {
-          int k1 = k0;
-          while (k1 < K && k1 - k0 < limit && vals(k0, k1 + 1) <= kRomStage && segs(k0, k1 + 1) <= kRomMaxSeg) ++k1;
-          if (k1 == k0) throw std::runtime_error("one time node exceeds the LDS staging capacity");
-          out.push_back({k0, k1 - k0});
-          k0 = k1;
-        }
-      };
-      std::vector<std::pair<int, int>> runs, best;
-      greedy(64, best);
-      for (int limit = (K + (int)best.size() - 1) / (int)best.size(); limit < 64; ++limit) {
-        greedy(limit, runs);   // the smallest run length that still needs no more runs
-        if (runs.size() == best.size()) {
-          best = runs;
-          break;
-        }
-      }
-      // t0 of every polynomial: the running sum Spline::GetSegmentID compares t against (spline.cc:52-57)
-      std::vector<double> t0(motion[e].durations.size() + 1, 0.0);
-      for (size_t q = 0; q < motion[e].durations.size(); ++q) t0[q + 1] = t0[q] + motion[e].durations[q];
-      for (const auto& r : best) {
-        RomSlice sl;
-        sl.k0 = r.first;
-        sl.cnt = r.second;
-        sl.nvals = vals(r.first, r.first + r.second);
-        // copy_out_fixed clamps its tail iterations to the last complete pair of the slice: a slice must hold one
-        if (sl.nvals < 4) throw std::runtime_error("a time-node run with fewer than 4 Jacobian values cannot be staged");
-        std::memset(sl.first, 255, sizeof(sl.first));
-        std::vector<RomSeg> sg;
-        for (int k = sl.k0; k < sl.k0 + sl.cnt; ++k) {
-          const int q = rom_motion[e][k].poly;
-          if (k > sl.k0 && q == rom_motion[e][k - 1].poly) continue;
-          const PolyDesc& mp = mpoly[e][q];
-          RomSeg S;
-          std::memset(&S, 0, sizeof(S));
-          S.t0 = t0[q];
-          S.iTm = mp.iT;
-          uint64_t slots = 0;
-          for (int c = 0; c < 12; ++c) slots |= (uint64_t)(mp.cand[c] & 0xF) << (4 * c);
-          S.slots[0] = (uint32_t)slots;
-          S.slots[1] = (uint32_t)(slots >> 32);
-          S.xbase = mp.xbase;
-          S.meta = mp.meta;
-          S.voff0 = row_ptr[row0 + 3 * k] - row_ptr[row0 + 3 * sl.k0];
-          S.kfirst = k - sl.k0;
-          S.node_vals = row_ptr[row0 + 3 * (k + 1)] - row_ptr[row0 + 3 * k];
-          if (S.node_vals != 68 + 3 * (int)(mp.meta & 0xF)) throw std::runtime_error("rangeofmotion row lengths inconsistent");
+    const std::vector<double> t0 = StartTimes(S.motion[e].durations);
+    for (const auto& r : best) {
+      Structure::RomSlice sl;
+      sl.k0 = r.first;
+      sl.cnt = r.second;
+      sl.nvals = vals(r.first, r.first + r.second);
+      // copy_out_fixed clamps its tail iterations to the last complete pair of the slice: a slice must hold one
+      if (sl.nvals < 4) throw std::runtime_error("a time-node run with fewer than 4 Jacobian values cannot be staged");
+      std::memset(sl.first, 255, sizeof(sl.first));
+      std::vector<RomSeg> sg;
+      for (int k = sl.k0; k < sl.k0 + sl.cnt; ++k) {
+        const int q = S.rom_motion[e][k].poly;
+        if (k == sl.k0 || q != S.rom_motion[e][k - 1].poly) {
+          const PolyDesc& mp = S.mpoly[e][q];
+          RomSeg seg = {};
+          seg.t0 = t0[q];
+          SetRomPoly(seg, mp);
+          seg.voff0 = vals(sl.k0, k);
+          seg.kfirst = k - sl.k0;
+          seg.node_vals = vals(k, k + 1);
+          if (seg.node_vals != 68 + 3 * (int)(mp.meta & 0xF)) throw std::runtime_error("rangeofmotion row lengths inconsistent");
           sl.first[sg.size()] = (uint8_t)(k - sl.k0);
-          sg.push_back(S);
+          sg.push_back(seg);
         }
-        // every node of a segment has the same row lengths: voff = voff0 + (k - kfirst) * node_vals (checked)
-        for (int k = sl.k0; k < sl.k0 + sl.cnt; ++k) {
-          size_t si = 0;
-          while (si + 1 < sg.size() && k - sl.k0 >= (int)sl.first[si + 1]) ++si;
-          if (row_ptr[row0 + 3 * k] - row_ptr[row0 + 3 * sl.k0] != sg[si].voff0 + (k - sl.k0 - sg[si].kfirst) * sg[si].node_vals)
-            throw std::runtime_error("rangeofmotion segment layout inconsistent");
-        }
-        for (int k = sl.k0; k < sl.k0 + sl.cnt; ++k) {   // which segment of this ee's slice node k reads: three bits per ee
-          uint32_t si = 0;
-          while (si + 1 < sg.size() && k - sl.k0 >= (int)sl.first[si + 1]) ++si;
-          nodes[k].seg |= si << (3 * e);
-        }
-        sl.segs = put(sg.data(), sg.size() * sizeof(RomSeg));
-        rom_slices[e].push_back(sl);
+        // every node of a segment has the same row lengths: voff = voff0 + (k - kfirst) * node_vals (checked); which segment of
+        // this ee's slice node k reads: three bits per ee
+        const RomSeg& last = sg.back();
+        if (vals(sl.k0, k) != last.voff0 + (k - sl.k0 - last.kfirst) * last.node_vals) throw std::runtime_error("rangeofmotion segment layout inconsistent");
+        nodes[k].seg |= (uint32_t)(sg.size() - 1) << (3 * e);
       }
+      sl.segs = w.Put(sg);
+      S.rom_slices[e].push_back(sl);
     }
-    off_rom_nodes = put(nodes.data(), nodes.size() * sizeof(RomNode));   // (after the loop: it fills RomNode::seg)
   }
-  // --- optimised timings: polynomial tables, set-wide counts, global grid times
-  if (timings) {
-    PhaseTables& pt = phase_tables;
-    std::memset(&pt, 0, sizeof(pt));
-    auto dim_table = [&](const SplineLayout& sl) {
-      std::vector<int> dim_of(sl.var_size, -1);
-      for (int n = 0; n < sl.n_nodes; ++n)
-        for (int dv = 0; dv < 2; ++dv)
-          for (int d = 0; d < 3; ++d)
-            if (sl.at(n, dv, d) >= 0) dim_of[sl.at(n, dv, d) - sl.var_offset] = d;
-      return dim_of;
-    };
-    auto poly_table = [&](const SplineLayout& sl, const std::vector<PolyDesc>& pd, int n_changing) {
-      std::vector<PhasePoly> out(pd.size());
-      std::vector<int> dim_of = dim_table(sl);
-      int in_phase = 0;
-      for (size_t q = 0; q < pd.size(); ++q) {
-        PhasePoly& pp = out[q];
-        std::memset(&pp, 0, sizeof(pp));
-        in_phase = (q > 0 && sl.poly_phase[q] == sl.poly_phase[q - 1]) ? in_phase + 1 : 0;
-        int n_in = 0;
-        for (size_t q2 = 0; q2 < pd.size(); ++q2) n_in += sl.poly_phase[q2] == sl.poly_phase[q];
-        (void)n_changing;
-        pp.phase = sl.poly_phase[q];
-        pp.n_in_phase = n_in;
-        pp.poly_in_phase = in_phase;
-        pp.xbase = pd[q].xbase;
-        pp.meta = pd[q].meta;
-        std::memcpy(pp.cand, pd[q].cand, sizeof(pp.cand));
-        const int before = (pd[q].meta & 0xF) ? pd[q].xbase - sl.var_offset : 0;
-        for (int i = 0; i < before; ++i) {
-          for (int r = 0; r < 3; ++r) {
-            if (dim_of[i] != r) pp.base_ne[r]++;
-            if (dim_of[i] == r) pp.base_eq[r]++;
-          }
-        }
-        pp.base_all = (uint16_t)before;
-      }
-      return out;
-    };
-    for (int e = 0; e < n_ee; ++e) {
-      pt.off_sched[e] = off_schedule[e];
-      pt.n_phases[e] = schedule.n_phases[e];
-      pt.t_total[e] = std::accumulate(schedule.phase_durations[e], schedule.phase_durations[e] + schedule.n_phases[e], 0.0);
-      auto mp = poly_table(motion[e], mpoly[e], params.polys_per_swing);
-      auto fp = poly_table(force[e], fpoly[e], params.polys_per_stance_force);
-      pt.n_mpoly[e] = (int)mp.size();
-      pt.n_fpoly[e] = (int)fp.size();
-      pt.o_mpoly[e] = put(mp.data(), mp.size() * sizeof(PhasePoly));
-      pt.o_fpoly[e] = put(fp.data(), fp.size() * sizeof(PhasePoly));
-      std::vector<int> dm = dim_table(motion[e]), df = dim_table(force[e]);
-      for (int r = 0; r < 3; ++r) {
-        for (int v : dm) pt.mne[e][r] += v != r;
-        for (int v : df) { pt.fne[e][r] += v != r; pt.feq[e][r] += v == r; }
-      }
-      pt.msize[e] = motion[e].var_size;
+  S.off_rom_nodes = w.Put(nodes);   // (after the loop: it fills RomNode::seg)
+}
+
+// --- optimised timings: per-node record templates, polynomial tables, set-wide counts, global grid times
+uint32_t PutPhaseTables(Structure& S, BlobWriter& w) {
+  const SetInfo* dyn = S.FindSet("dynamic");
+  const SetInfo* rom[kMaxEE] = {nullptr, nullptr, nullptr, nullptr};
+  for (int e = 0; e < S.n_ee; ++e) rom[e] = S.FindSet("rangeofmotion-" + std::to_string(e));
+  const bool have_rom = rom[0] != nullptr;
+  if (dyn) {   // dynamic: the base-spline part of the per-node record (the rest depends on x)
+    std::vector<DynShared> sh(S.grid_dyn.size());
+    for (size_t k = 0; k < S.grid_dyn.size(); ++k) {
+      std::tie(sh[k].tb, sh[k].iTb, sh[k].q6) = BaseAt(S.base, S.dyn_base[k]);
+      sh[k].voff = S.row_ptr[dyn->offset + 6 * k] - dyn->nnz_offset;
     }
-    int sched_total = 0;
-    for (int e = 0; e < n_ee; ++e) sched_total += schedule.n_phases[e] - 1;
+    S.off_dyn_shared = w.Put(sh);
+  }
+  // rangeofmotion-<ee>: the record templates (the pre-pass fills in the x-dependent part)
+  for (int e = 0; e < S.n_ee && have_rom; ++e) {
+    std::vector<RomRec> rc(S.grid_rom.size());
+    for (size_t k = 0; k < S.grid_rom.size(); ++k) {
+      RomRec& R = rc[k];
+      const PolyDesc& mp = S.mpoly[e][S.rom_motion[e][k].poly];
+      std::tie(R.tb, R.iTb, R.q6) = BaseAt(S.base, S.rom_base[k]);
+      R.tm = S.rom_motion[e][k].t_local;
+      R.voff = S.row_ptr[rom[e]->offset + 3 * k] - rom[e]->nnz_offset;
+      SetRomPoly(R, mp);
+    }
+    S.off_rom_recs[e] = w.Put(rc);
+  }
+  PhaseTables& pt = S.phase_tables;
+  std::memset(&pt, 0, sizeof(pt));
+  for (int e = 0; e < S.n_ee; ++e) {
+    pt.off_sched[e] = S.off_schedule[e];
+    pt.n_phases[e] = S.schedule.n_phases[e];
+    pt.t_total[e] = std::accumulate(S.schedule.phase_durations[e], S.schedule.phase_durations[e] + S.schedule.n_phases[e], 0.0);
+    const auto mp = PhasePolyTable(S.motion[e], S.mpoly[e]), fp = PhasePolyTable(S.force[e], S.fpoly[e]);
+    pt.n_mpoly[e] = (int)mp.size();
+    pt.n_fpoly[e] = (int)fp.size();
+    pt.o_mpoly[e] = w.Put(mp);
+    pt.o_fpoly[e] = w.Put(fp);
+    const std::vector<int> dm = DimOf(S.motion[e]), df = DimOf(S.force[e]);
     for (int r = 0; r < 3; ++r) {
-      pt.len_ang[r] = 20 + sched_total;
-      pt.len_lin[r] = 4 + sched_total;
-      for (int e = 0; e < n_ee; ++e) {
-        pt.len_ang[r] += pt.mne[e][r] + pt.fne[e][r];
-        pt.len_lin[r] += pt.feq[e][r];
-      }
-      pt.node_vals += pt.len_ang[r] + pt.len_lin[r];
+      for (int v : dm) pt.mne[e][r] += v != r;
+      for (int v : df) { pt.fne[e][r] += v != r; pt.feq[e][r] += v == r; }
     }
-    for (int e = 0; e < n_ee; ++e) {
+    pt.msize[e] = S.motion[e].var_size;
+  }
+  int sched_total = 0;
+  for (int e = 0; e < S.n_ee; ++e) sched_total += S.schedule.n_phases[e] - 1;
+  for (int r = 0; r < 3; ++r) {
+    pt.len_ang[r] = 20 + sched_total;
+    pt.len_lin[r] = 4 + sched_total;
+    for (int e = 0; e < S.n_ee; ++e) {
+      pt.len_ang[r] += pt.mne[e][r] + pt.fne[e][r];
+      pt.len_lin[r] += pt.feq[e][r];
+    }
+    pt.node_vals += pt.len_ang[r] + pt.len_lin[r];
+  }
+  for (int e = 0; e < S.n_ee; ++e) {
+    for (int r = 0; r < 3; ++r) {
+      pt.rom_len[e][r] = 12 + (r == 0 ? 8 : 12) + pt.msize[e] + S.schedule.n_phases[e] - 1;
+      pt.rom_node_vals[e] += pt.rom_len[e][r];
+    }
+    if (have_rom) {
+      pt.row_rom[e] = rom[e]->offset;
+      pt.nnz_rom[e] = rom[e]->nnz_offset;
+    }
+    // rom_phase_kernel assembles whole expanded time nodes in LDS: one node must fit the 160 KB of a CU
+    // (the dynamic set has the matching guard below; without it the batch is created and every evaluation fails to launch)
+    if (have_rom && pt.rom_node_vals[e] > 160 * 128)
+      throw std::runtime_error("optimised timings: a time node of rangeofmotion-" + std::to_string(e) + " has more than 20480 Jacobian values");
+  }
+  pt.o_tdyn = w.Put(S.grid_dyn);
+  pt.o_trom = w.Put(S.grid_rom);
+  pt.k_dyn = dyn ? (int)S.grid_dyn.size() : 0;
+  pt.k_rom = have_rom ? (int)S.grid_rom.size() : 0;
+  pt.row_dyn = dyn ? dyn->offset : 0;
+  pt.nnz_dyn = dyn ? dyn->nnz_offset : 0;
+  pt.off_lin = S.off_base_lin;
+  pt.off_ang = S.off_base_ang;
+  pt.o_dyn_shared = S.off_dyn_shared;
+  for (int e = 0; e < S.n_ee; ++e) {
+    pt.o_rom_recs[e] = S.off_rom_recs[e];
+    if (pt.n_mpoly[e] > kMaxPhasePolys || pt.n_fpoly[e] > kMaxPhasePolys) throw std::runtime_error("too many polynomials per ee spline for optimised timings");
+  }
+  if (const SetInfo* si = S.FindSet("totalduration-0")) {
+    pt.row_total = si->offset;
+    pt.nnz_total = si->nnz_offset;
+  }
+  // dynamic: byte offset of every ee value inside a time node's expanded rows, read off the CSR pattern of time
+  // node 0 (the rows hold all variables of every ee set, so the ee part of the layout is the same at every node)
+  if (dyn) {
+    if (pt.node_vals > 8191) throw std::runtime_error("optimised timings: a time node of the dynamic set has more than 8191 Jacobian values");
+    const int v0 = S.row_ptr[dyn->offset];
+    auto find = [&](int row, int col) { return ColumnPos(S, dyn->offset + row, col, true) - v0; };
+    std::vector<PhasePutM> pm_all;
+    std::vector<PhasePutF> pf_all;
+    for (int e = 0; e < S.n_ee; ++e) {
+      const uint16_t trash = (uint16_t)(8 * (8 + e));   // base-ang entry of row AX, rewritten after the tiles
+      pt.mput_base[e] = (int)pm_all.size();
+      pt.fput_base[e] = (int)pf_all.size();
+      for (const PolyDesc& p : S.mpoly[e]) pm_all.push_back(PhasePutOf<2, PhasePutM>(&p, trash, find));
+      for (const PolyDesc& p : S.fpoly[e]) pf_all.push_back(PhasePutOf<3, PhasePutF>(&p, trash, find));
+      pt.ee[e].ns = S.schedule.n_phases[e] - 1;
       for (int r = 0; r < 3; ++r) {
-        pt.rom_len[e][r] = 12 + (r == 0 ? 8 : 12) + pt.msize[e] + schedule.n_phases[e] - 1;
-        pt.rom_node_vals[e] += pt.rom_len[e][r];
+        pt.ee[e].dur_ang[r] = 8 * find(r, S.off_schedule[e]);
+        pt.ee[e].dur_lin[r] = 8 * find(3 + r, S.off_schedule[e]);
       }
-      pt.row_rom[e] = row_rom[e];
-      pt.nnz_rom[e] = nnz_rom[e];
-      // rom_phase_kernel assembles whole expanded time nodes in LDS: one node must fit the 160 KB of a CU
-      // (the dynamic set has the matching guard below; without it the batch is created and every evaluation fails to launch)
-      if (have_rom && pt.rom_node_vals[e] > 160 * 128)
-        throw std::runtime_error("optimised timings: a time node of rangeofmotion-" + std::to_string(e) + " has more than 20480 Jacobian values");
     }
-    pt.o_tdyn = put(grid_dyn.data(), grid_dyn.size() * sizeof(double));
-    pt.o_trom = put(grid_rom.data(), grid_rom.size() * sizeof(double));
-    pt.k_dyn = dyn_set ? (int)grid_dyn.size() : 0;
-    pt.k_rom = have_rom ? (int)grid_rom.size() : 0;
-    pt.row_dyn = row_dyn;
-    pt.nnz_dyn = nnz_dyn;
-    pt.off_lin = off_base_lin;
-    pt.off_ang = off_base_ang;
-    pt.o_dyn_shared = off_dyn_shared;
-    for (int e = 0; e < n_ee; ++e) {
-      pt.o_rom_recs[e] = off_rom_recs[e];
-      if (pt.n_mpoly[e] > kMaxPhasePolys || pt.n_fpoly[e] > kMaxPhasePolys) throw std::runtime_error("too many polynomials per ee spline for optimised timings");
+    pt.n_mput = (int)pm_all.size();
+    pt.n_fput = (int)pf_all.size();
+    for (int e = 0; e < kMaxEE; ++e) {   // dummy records
+      pm_all.push_back(PhasePutOf<2, PhasePutM>(nullptr, (uint16_t)(8 * (8 + e)), find));
+      pf_all.push_back(PhasePutOf<3, PhasePutF>(nullptr, (uint16_t)(8 * (8 + e)), find));
     }
-    if (const SetInfo* si = FindSet("totalduration-0")) {
-      pt.row_total = si->offset;
-      pt.nnz_total = si->nnz_offset;
-    }
-    // dynamic: byte offset of every ee value inside a time node's expanded rows, read off the CSR pattern of time
-    // node 0 (the rows hold all variables of every ee set, so the ee part of the layout is the same at every node)
-    if (dyn_set) {
-      if (pt.node_vals > 8191) throw std::runtime_error("optimised timings: a time node of the dynamic set has more than 8191 Jacobian values");
-      const int v0 = row_ptr[row_dyn];
-      auto find = [&](int row, int col) -> int {
-        const int32_t* b = col_idx.data() + row_ptr[row_dyn + row];
-        const int32_t* e2 = col_idx.data() + row_ptr[row_dyn + row + 1];
-        const int32_t* it = std::lower_bound(b, e2, col);
-        if (it == e2 || *it != col) throw std::runtime_error("dynamic pattern lacks an expected column");
-        return (int)(it - col_idx.data()) - v0;
-      };
-      std::vector<PhasePutM> pm_all;
-      std::vector<PhasePutF> pf_all;
-      for (int e = 0; e < n_ee; ++e) {
-        const uint16_t trash = (uint16_t)(8 * (8 + e));   // base-ang entry of row AX, rewritten after the tiles
-        std::vector<PhasePutM> pm(mpoly[e].size());
-        std::vector<PhasePutF> pf(fpoly[e].size());
-        for (size_t q = 0; q < mpoly[e].size(); ++q) {
-          std::memset(&pm[q], 0, sizeof(PhasePutM));
-          for (int c = 0; c < 12; ++c) {
-            const int j = c / 3, d = c % 3, r1 = (d + 1) % 3, r2 = (d + 2) % 3;
-            pm[q].off[j][2 * d] = pm[q].off[j][2 * d + 1] = trash;
-            if (mpoly[e][q].cand[c] == 0xFFFF) continue;
-            const int col = mpoly[e][q].xbase + (mpoly[e][q].cand[c] & 0xF);
-            pm[q].off[j][2 * d] = (uint16_t)(8 * find(r1, col));
-            pm[q].off[j][2 * d + 1] = (uint16_t)(8 * find(r2, col));
-          }
-          for (int j = 0; j < 4; ++j) pm[q].off[j][6] = pm[q].off[j][7] = trash;
-        }
-        for (size_t q = 0; q < fpoly[e].size(); ++q) {
-          std::memset(&pf[q], 0, sizeof(PhasePutF));
-          for (int c = 0; c < 12; ++c) {
-            const int j = c / 3, d = c % 3, r1 = (d + 1) % 3, r2 = (d + 2) % 3;
-            pf[q].off[j][3 * d] = pf[q].off[j][3 * d + 1] = pf[q].off[j][3 * d + 2] = trash;
-            if (fpoly[e][q].cand[c] == 0xFFFF) continue;
-            const int col = fpoly[e][q].xbase + (fpoly[e][q].cand[c] & 0xF);
-            pf[q].off[j][3 * d] = (uint16_t)(8 * find(r1, col));
-            pf[q].off[j][3 * d + 1] = (uint16_t)(8 * find(r2, col));
-            pf[q].off[j][3 * d + 2] = (uint16_t)(8 * find(3 + d, col));
-          }
-          for (int j = 0; j < 4; ++j) pf[q].off[j][9] = pf[q].off[j][10] = pf[q].off[j][11] = trash;
-        }
-        pt.mput_base[e] = (int)pm_all.size();
-        pt.fput_base[e] = (int)pf_all.size();
-        pm_all.insert(pm_all.end(), pm.begin(), pm.end());
-        pf_all.insert(pf_all.end(), pf.begin(), pf.end());
-        pt.ee[e].ns = schedule.n_phases[e] - 1;
-        for (int r = 0; r < 3; ++r) {
-          pt.ee[e].dur_ang[r] = 8 * find(r, off_schedule[e]);
-          pt.ee[e].dur_lin[r] = 8 * find(3 + r, off_schedule[e]);
-        }
-      }
-      pt.n_mput = (int)pm_all.size();
-      pt.n_fput = (int)pf_all.size();
-      for (int e = 0; e < kMaxEE; ++e) {   // dummy records
-        PhasePutM dm;
-        PhasePutF df;
-        for (int j = 0; j < 4; ++j) {
-          for (int q = 0; q < 8; ++q) dm.off[j][q] = (uint16_t)(8 * (8 + e));
-          for (int q = 0; q < 12; ++q) df.off[j][q] = (uint16_t)(8 * (8 + e));
-        }
-        pm_all.push_back(dm);
-        pf_all.push_back(df);
-      }
-      pt.o_mput = put(pm_all.data(), pm_all.size() * sizeof(PhasePutM));
-      pt.o_fput = put(pf_all.data(), pf_all.size() * sizeof(PhasePutF));
-      for (int r = 1; r < 6; ++r) pt.dyn_row_off[r - 1] = 8u * (uint32_t)(row_ptr[row_dyn + r] - v0);
-      if (params.polys_per_swing > 15 || params.polys_per_stance_force > 15)
-        throw std::runtime_error("optimised timings: at most 15 polynomials per phase");
-    }
-    // the pattern builder and these closed forms must agree
-    if (dyn_set && dyn_set->nnz != pt.node_vals * (int)grid_dyn.size()) throw std::runtime_error("dynamic row lengths inconsistent");
-    for (int e = 0; e < n_ee && have_rom; ++e)
-      if (FindSet("rangeofmotion-" + std::to_string(e))->nnz != pt.rom_node_vals[e] * (int)grid_rom.size())
-        throw std::runtime_error("rangeofmotion row lengths inconsistent");
-    h.timings = 1;
-    h.o_phase = put(&pt, sizeof(pt));
+    pt.o_mput = w.Put(pm_all);
+    pt.o_fput = w.Put(pf_all);
+    for (int r = 1; r < 6; ++r) pt.dyn_row_off[r - 1] = 8u * (uint32_t)(S.row_ptr[dyn->offset + r] - v0);
+    if (S.params.polys_per_swing > 15 || S.params.polys_per_stance_force > 15)
+      throw std::runtime_error("optimised timings: at most 15 polynomials per phase");
   }
-  if (model.terrain_id == TWR_TERRAIN_CSV_GRID || model.terrain_id == TWR_TERRAIN_GRID_MAP) {
-    if (!grid) throw std::runtime_error("gridded terrains need twr_structure_create_with_grid");
-    if (grid->grid_map != (model.terrain_id == TWR_TERRAIN_GRID_MAP))
+  // the pattern builder and these closed forms must agree
+  if (dyn && dyn->nnz != pt.node_vals * (int)S.grid_dyn.size()) throw std::runtime_error("dynamic row lengths inconsistent");
+  for (int e = 0; e < S.n_ee && have_rom; ++e)
+    if (rom[e]->nnz != pt.rom_node_vals[e] * (int)S.grid_rom.size())
+      throw std::runtime_error("rangeofmotion row lengths inconsistent");
+  return w.Put(&pt, sizeof(pt));
+}
+
+// trajectory sampling tables
+uint32_t PutSampleTables(const Structure& S, BlobWriter& w) {
+  SampleTables st;
+  std::memset(&st, 0, sizeof(st));
+  st.n_base = (int)S.base.durations.size();
+  st.o_bdur = w.Put(S.base.durations);
+  st.off_lin = S.off_base_lin;
+  st.off_ang = S.off_base_ang;
+  st.t_total = std::accumulate(S.base.durations.begin(), S.base.durations.end(), 0.0);  // spline.cc:118-123
+  for (int e = 0; e < S.n_ee; ++e) {
+    st.n_phases[e] = S.schedule.n_phases[e];
+    st.contact0[e] = S.schedule.in_contact_at_start[e] != 0;
+    st.n_mpoly[e] = (int)S.mpoly[e].size();
+    st.n_fpoly[e] = (int)S.fpoly[e].size();
+    st.o_phdur[e] = w.Put(S.schedule.phase_durations[e], S.schedule.n_phases[e] * sizeof(double));
+    st.o_mdur[e] = w.Put(S.motion[e].durations);
+    st.o_fdur[e] = w.Put(S.force[e].durations);
+    st.o_mdesc[e] = w.Put(S.mpoly[e]);
+    st.o_fdesc[e] = w.Put(S.fpoly[e]);
+    if (st.n_mpoly[e] > kMaxPhasePolys || st.n_fpoly[e] > kMaxPhasePolys) st.n_base = -1;  // sampling unsupported
+  }
+  if (st.n_base > 2 * kMaxPhasePolys) st.n_base = -1;
+  return w.Put(&st, sizeof(st));
+}
+
+// values-only evaluation of dynamic / rangeofmotion-* with one lane per time node (device_tables.h FlatNode): fixed
+// timings only -- with optimised timings the active polynomials depend on x and the phase kernels keep that path
+void PutFlatTables(Structure& S, BlobWriter& w, DevStruct& h) {
+  const SetInfo* dyn = S.FindSet("dynamic");
+  const bool have_rom = S.FindSet("rangeofmotion-0") != nullptr;
+  S.flat_items_rom.clear();
+  S.flat_items_dyn.clear();
+  S.flat_with_rom = false;
+  size_t n_flat_polys = 0;
+  for (int e = 0; e < S.n_ee; ++e) n_flat_polys += S.mpoly[e].size() + S.fpoly[e].size();
+  // x is staged in LDS (16-bit byte offsets); window starts are 16-bit indices
+  if (S.timings || S.n_vars > kFlatXCap || n_flat_polys >= 65536 || !(have_rom || dyn)) return;
+  S.flat_row_dyn = dyn ? dyn->offset : 0;
+  std::vector<FlatPoly> fp;
+  int first[2 * kMaxEE] = {0};   // spline s = 2 e (ee-motion_e), 2 e + 1 (ee-force_e): its first record in fp
+  auto flat_polys = [&](int s, const std::vector<PolyDesc>& polys, const std::vector<double>& durations) {
+    first[s] = (int)fp.size();
+    const std::vector<double> t0 = StartTimes(durations);
+    for (size_t q = 0; q < polys.size(); ++q) {
+      FlatPoly r = {};
+      r.t0 = t0[q];
+      r.iT = polys[q].iT;
+      const bool shared = (polys[q].meta >> 16) & 1;
+      for (int c = 0; c < 12; ++c) {
+        const int src = shared && c >= 6 && c < 9 ? c - 6 : c;   // stance: p1 is the same variable as p0
+        const int sl = polys[q].cand[src] & 0xF;
+        r.off[c] = (uint16_t)(sl != 0xF ? 8 * (2 + polys[q].xbase + sl) : 0);
+      }
+      fp.push_back(r);
+    }
+  };
+  for (int e = 0; e < S.n_ee; ++e) {
+    if (have_rom) S.flat_row_rom[e] = S.FindSet("rangeofmotion-" + std::to_string(e))->offset;
+    flat_polys(2 * e, S.mpoly[e], S.motion[e].durations);
+    flat_polys(2 * e + 1, S.fpoly[e], S.force[e].durations);
+  }
+  S.off_flat_polys = h.o_flat = w.Put(fp);
+  // items: <= 64 consecutive time nodes whose active polynomials span <= kFlatWindow per spline.  On a COARSE grid (towr's
+  // defaults: 0.1 / 0.08 s against polynomials of that length) the time nodes hardly share polynomials and the windows would
+  // cut items of a few time nodes: such a grid is cut at 64 time nodes alone and its lanes fetch their own records
+  // (FlatWork::gather; the indices stay relative to the item's first polynomials, 8 bits)
+  auto flat_items = [&](const std::vector<double>& grid, const std::vector<TimeNode>& at_base, const std::vector<std::vector<TimeNode>>& at_motion,
+                        const std::vector<std::vector<TimeNode>>* at_force, std::vector<Structure::FlatItem>& items) {
+    auto poly_at = [&](int s, size_t k) { return (s & 1) ? (*at_force)[s >> 1][k].poly : at_motion[s >> 1][k].poly; };
+    const int step = at_force ? 1 : 2;   // range of motion: the ee-motion splines only
+    auto cut = [&](int window) {
+      return CutRuns((int)grid.size(), [&](int k0, int k1) {
+        if (k1 - k0 > 64) return false;
+        for (int s = 0; s < 2 * S.n_ee; s += step)
+          if (poly_at(s, k1 - 1) - poly_at(s, k0) >= window) return false;
+        return true;
+      });
+    };
+    std::vector<std::pair<int, int>> runs = cut(kFlatWindow);
+    // (an item costs about the same whatever it holds, fetching the records per lane a quarter more: the windows stay while
+    // they cut at most a quarter more items than 64 time nodes each would)
+    const bool gather = 4 * runs.size() > 5 * ((grid.size() + 63) / 64);
+    if (gather) runs = cut(256);
+    std::vector<FlatNode> fn(grid.size());
+    items.clear();
+    for (const auto& r : runs) {
+      const int k0 = r.first, k1 = r.first + r.second;
+      Structure::FlatItem it;
+      it.k0 = k0;
+      it.cnt = r.second;
+      it.gather = gather;
+      for (int k = k0; k < k1; ++k) {
+        fn[k].t = grid[k];
+        std::tie(fn[k].tb, fn[k].iTb, fn[k].q6) = BaseAt(S.base, at_base[k]);
+      }
+      for (int s = 0; s < 2 * S.n_ee; s += step) {
+        const int lo = poly_at(s, k0), hi = poly_at(s, k1 - 1);
+        it.start[s >> 2] |= (uint64_t)(first[s] + lo) << (16 * (s & 3));
+        it.count |= (uint64_t)(hi - lo + 1) << (8 * s);
+        for (int k = k0; k < k1; ++k) ((s & 1) ? fn[k].qf[s >> 1] : fn[k].qm[s >> 1]) = (uint8_t)(poly_at(s, k) - lo);
+      }
+      items.push_back(it);
+    }
+    return w.Put(fn);
+  };
+  // coinciding grids (the BASELINE configurations choose one dt for both; towr's defaults are 0.1 / 0.08 s): the "dynamic"
+  // items evaluate the range-of-motion rows of their time nodes as well -- same base point, rotation and ee positions
+  S.flat_with_rom = have_rom && dyn && S.grid_rom == S.grid_dyn;
+  if (have_rom && !S.flat_with_rom) S.off_flat_rom = flat_items(S.grid_rom, S.rom_base, S.rom_motion, nullptr, S.flat_items_rom);
+  if (dyn) S.off_flat_dyn = flat_items(S.grid_dyn, S.dyn_base, S.dyn_motion, &S.dyn_force, S.flat_items_dyn);
+}
+
+// the header's grid fields and model constants
+void SetHeader(const Structure& S, DevStruct& h) {
+  if (S.model.terrain_id == TWR_TERRAIN_CSV_GRID || S.model.terrain_id == TWR_TERRAIN_GRID_MAP) {
+    if (!S.grid) throw std::runtime_error("gridded terrains need twr_structure_create_with_grid");
+    if (S.grid->grid_map != (S.model.terrain_id == TWR_TERRAIN_GRID_MAP))
       throw std::runtime_error("the grid handle is of the other kind (CSV heights vs grid_map elevation layer)");
-    h.grid_rows = grid->rows;
-    h.grid_cols = grid->cols;
-    h.grid_res = grid->res;
-    h.grid_eps = grid->eps;
-    h.grid_px = grid->pos_x;
-    h.grid_py = grid->pos_y;
+    h.grid_rows = S.grid->rows;
+    h.grid_cols = S.grid->cols;
+    h.grid_res = S.grid->res;
+    h.grid_eps = S.grid->eps;
+    h.grid_px = S.grid->pos_x;
+    h.grid_py = S.grid->pos_y;
   }
-  {  // trajectory sampling tables
-    SampleTables st;
-    std::memset(&st, 0, sizeof(st));
-    st.n_base = (int)base.durations.size();
-    st.o_bdur = put(base.durations.data(), base.durations.size() * sizeof(double));
-    st.off_lin = off_base_lin;
-    st.off_ang = off_base_ang;
-    st.t_total = std::accumulate(base.durations.begin(), base.durations.end(), 0.0);  // spline.cc:118-123
-    for (int e = 0; e < n_ee; ++e) {
-      st.n_phases[e] = schedule.n_phases[e];
-      st.contact0[e] = schedule.in_contact_at_start[e] != 0;
-      st.n_mpoly[e] = (int)mpoly[e].size();
-      st.n_fpoly[e] = (int)fpoly[e].size();
-      st.o_phdur[e] = put(schedule.phase_durations[e], schedule.n_phases[e] * sizeof(double));
-      st.o_mdur[e] = put(motion[e].durations.data(), motion[e].durations.size() * sizeof(double));
-      st.o_fdur[e] = put(force[e].durations.data(), force[e].durations.size() * sizeof(double));
-      st.o_mdesc[e] = put(mpoly[e].data(), mpoly[e].size() * sizeof(PolyDesc));
-      st.o_fdesc[e] = put(fpoly[e].data(), fpoly[e].size() * sizeof(PolyDesc));
-      if (st.n_mpoly[e] > kMaxPhasePolys || st.n_fpoly[e] > kMaxPhasePolys) st.n_base = -1;  // sampling unsupported
-    }
-    if (st.n_base > 2 * kMaxPhasePolys) st.n_base = -1;
-    h.o_sample = put(&st, sizeof(st));
-    // values-only evaluation of dynamic / rangeofmotion-* with one lane per time node (device_tables.h FlatNode): fixed
-    // timings only -- with optimised timings the active polynomials depend on x and the phase kernels keep that path
-    const bool rom_set = FindSet("rangeofmotion-0") != nullptr;
-    const SetInfo* dyn_set = FindSet("dynamic");
-    flat_items_rom.clear();
-    flat_items_dyn.clear();
-    flat_with_rom = false;
-    size_t n_flat_polys = 0;
-    for (int e = 0; e < n_ee; ++e) n_flat_polys += mpoly[e].size() + fpoly[e].size();
-    // x is staged in LDS (16-bit byte offsets); window starts are 16-bit indices
-    if (!timings && n_vars <= kFlatXCap && n_flat_polys < 65536 && (rom_set || dyn_set)) {
-      flat_row_dyn = dyn_set ? dyn_set->offset : 0;
-      std::vector<FlatPoly> fp;
-      int first[2 * kMaxEE] = {0};   // spline s = 2 e (ee-motion_e), 2 e + 1 (ee-force_e): its first record in fp
-      auto flat_polys = [&](const std::vector<PolyDesc>& polys, const std::vector<double>& durations) {
-        double t0 = 0.0;   // the running sum Spline::GetSegmentID compares t against (spline.cc:52-57)
-        for (size_t q = 0; q < polys.size(); ++q) {
-          FlatPoly r;
-          std::memset(&r, 0, sizeof(r));
-          r.t0 = t0;
-          r.iT = polys[q].iT;
-          t0 += durations[q];
-          const bool shared = (polys[q].meta >> 16) & 1;
-          for (int c = 0; c < 12; ++c) {
-            const int src = shared && c >= 6 && c < 9 ? c - 6 : c;   // stance: p1 is the same variable as p0
-            const int sl = polys[q].cand[src] & 0xF;
-            r.off[c] = (uint16_t)(sl != 0xF ? 8 * (2 + polys[q].xbase + sl) : 0);
-          }
-          fp.push_back(r);
-        }
-      };
-      for (int e = 0; e < n_ee; ++e) {
-        if (rom_set) flat_row_rom[e] = FindSet("rangeofmotion-" + std::to_string(e))->offset;
-        first[2 * e] = (int)fp.size();
-        flat_polys(mpoly[e], motion[e].durations);
-        first[2 * e + 1] = (int)fp.size();
-        flat_polys(fpoly[e], force[e].durations);
-      }
-      off_flat_polys = h.o_flat = put(fp.data(), fp.size() * sizeof(FlatPoly));
-      // items: <= 64 consecutive time nodes whose active polynomials span <= kFlatWindow per spline.  On a COARSE grid (towr's
-      // defaults: 0.1 / 0.08 s against polynomials of that length) the time nodes hardly share polynomials and the windows would
-      // cut items of a few time nodes: such a grid is cut at 64 time nodes alone and its lanes fetch their own records
-      // (FlatWork::gather; the indices stay relative to the item's first polynomials, 8 bits)
-      auto flat_items = [&](const std::vector<double>& grid, const std::vector<TimeNode>& at_base, const std::vector<std::vector<TimeNode>>& at_motion,
-                            const std::vector<std::vector<TimeNode>>* at_force, std::vector<FlatItem>& items) {
-        std::vector<FlatNode> fn(grid.size());
-        auto poly_at = [&](int s, size_t k) { return (s & 1) ? (*at_force)[s >> 1][k].poly : at_motion[s >> 1][k].poly; };
-        const int step = at_force ? 1 : 2;   // range of motion: the ee-motion splines only
-        auto cut = [&](int window, bool gather) {
-          items.clear();
-          size_t k0 = 0;
-          while (k0 < grid.size()) {
-            size_t k1 = k0 + 1;
-            auto fits = [&](size_t k) {
-              for (int s = 0; s < 2 * n_ee; s += step)
-                if (poly_at(s, k) - poly_at(s, k0) >= window) return false;
-              return true;
-            };
-            while (k1 < grid.size() && k1 - k0 < 64 && fits(k1)) ++k1;
-            FlatItem it;
-            it.k0 = (int)k0;
-            it.cnt = (int)(k1 - k0);
-            it.gather = gather;
-            for (int s = 0; s < 2 * n_ee; s += step) {
-              const int lo = poly_at(s, k0), hi = poly_at(s, k1 - 1);
-              it.start[s >> 2] |= (uint64_t)(first[s] + lo) << (16 * (s & 3));
-              it.count |= (uint64_t)(hi - lo + 1) << (8 * s);
-            }
-            items.push_back(it);
-            for (size_t k = k0; k < k1; ++k) {
-              std::memset(&fn[k], 0, sizeof(FlatNode));
-              fn[k].t = grid[k];
-              fn[k].tb = at_base[k].t_local;
-              fn[k].iTb = 1.0 / base.durations[at_base[k].poly];
-              fn[k].q6 = 6 * at_base[k].poly;
-              for (int e = 0; e < n_ee; ++e) {
-                fn[k].qm[e] = (uint8_t)(at_motion[e][k].poly - at_motion[e][k0].poly);
-                if (at_force) fn[k].qf[e] = (uint8_t)((*at_force)[e][k].poly - (*at_force)[e][k0].poly);
-              }
-            }
-            k0 = k1;
-          }
-        };
-        cut(kFlatWindow, false);
-        // (an item costs about the same whatever it holds, fetching the records per lane a quarter more: the windows stay while
-        // they cut at most a quarter more items than 64 time nodes each would)
-        if (4 * items.size() > 5 * ((grid.size() + 63) / 64)) cut(256, true);
-        return put(fn.data(), fn.size() * sizeof(FlatNode));
-      };
-      // coinciding grids (the BASELINE configurations choose one dt for both; towr's defaults are 0.1 / 0.08 s): the "dynamic"
-      // items evaluate the range-of-motion rows of their time nodes as well -- same base point, rotation and ee positions
-      flat_with_rom = rom_set && dyn_set && grid_rom == grid_dyn;
-      if (rom_set && !flat_with_rom) off_flat_rom = flat_items(grid_rom, rom_base, rom_motion, nullptr, flat_items_rom);
-      if (dyn_set) off_flat_dyn = flat_items(grid_dyn, dyn_base, dyn_motion, &dyn_force, flat_items_dyn);
-    }
-  }
-  h.mass = model.mass; h.gravity = model.gravity; h.mu = model.friction; h.flat_height = model.flat_height;
+  h.n_ee = S.n_ee;
+  h.terrain_id = S.model.terrain_id;
+  h.off_base_ang = S.off_base_ang;
+  h.inv_t_swing = 1.0 / 0.3;  // t_swing_avg_, swing_constraint.h:68
+  h.mass = S.model.mass; h.gravity = S.model.gravity; h.mu = S.model.friction; h.flat_height = S.model.flat_height;
   // BuildInertiaTensor (single_rigid_body_dynamics.cc:36-44): off-diagonals are the negated products of inertia
-  const double* I = model.inertia;  // Ixx,Iyy,Izz,Ixy,Ixz,Iyz
+  const double* I = S.model.inertia;  // Ixx,Iyy,Izz,Ixy,Ixz,Iyz
   h.Ib[0] = I[0]; h.Ib[1] = -I[3]; h.Ib[2] = -I[4]; h.Ib[3] = I[1]; h.Ib[4] = -I[5]; h.Ib[5] = I[2];
-  blob.resize(sizeof(DevStruct) + body.size());
-  std::memcpy(blob.data(), &h, sizeof(h));
-  if (!body.empty()) std::memcpy(blob.data() + sizeof(DevStruct), body.data(), body.size());
-  blob.resize((blob.size() + 15) / 16 * 16);
+}
+
+}  // namespace
+
+// one builder per table group, called in the order the blob holds them
+void Structure::PackBlob() {
+  DevStruct h;
+  std::memset(&h, 0, sizeof(h));
+  BlobWriter w(dyn_layout_tables);
+  const auto rows = FlatFamily(*this, "terrain-ee-motion_", 1, terrain_rows, h.row_terrain, h.nnz_terrain, h.n_terrain_rows);
+  const auto forces = FlatFamily(*this, "force-ee-force_", 5, force_nodes, h.row_force, h.nnz_force, h.n_force_nodes);
+  const auto swings = FlatFamily(*this, "swing-ee-motion_", 4, swing_nodes, h.row_swing, h.nnz_swing, h.n_swing_nodes);
+  PutNodeHead(w, rows, forces);
+  PutScoreRecord(*this, w, h);
+  PutNodeFamilies(*this, w, h, rows, forces, swings);
+  rom_slices.assign(n_ee, {});
+  if (timings) {
+    h.timings = 1;
+    h.o_phase = PutPhaseTables(*this, w);
+  } else {
+    PutDynTables(*this, w);
+    PutRomTables(*this, w);
+  }
+  h.o_sample = PutSampleTables(*this, w);
+  PutFlatTables(*this, w, h);
+  SetHeader(*this, h);
+  blob = w.Finish(h);
 }
 
 const SetInfo* Structure::FindSet(const std::string& name) const {
@@ -1783,7 +1778,6 @@ LayoutShare ShareLayoutTables(const std::vector<const Structure*>& structs) {
   }
   return out;
 }
-
 
 std::vector<size_t> BlobOffsets(const std::vector<const Structure*>& structs) {
   std::vector<size_t> off(structs.size() + 1, 0);
