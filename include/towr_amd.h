@@ -408,6 +408,40 @@ int twr_batch_eval_host(twr_batch* b, const double* h_x, double* h_g, double* h_
  * followed by two copies: and gather x from them: 34 instead of 53 us for one quadruped problem (TWR_HOST_ZERO_COPY=0 switches it off). */
 int twr_batch_host_buffers(twr_batch* b, double** h_x, double** h_g, double** h_jac);
 
+/* Products with the Jacobian values of a batch, on the device (new; what every gradient-based use of a Jacobian needs):
+ *   twr_jac_mul:  y[g_off[p] + r] = sum_k J_p[r][k] v[x_off[p] + k]    -- the directional derivative J v: Ipopt's first-order
+ *                 derivative test (towr/test/hopper_example.cc:86), a Gauss-Newton / CG step
+ *   twr_jac_tmul: z[x_off[p] + k] = sum_r J_p[r][k] w[g_off[p] + r]    -- J^T w: the gradient of SoftConstraint,
+ *                 jac.transpose() * W * (g - b) (towr/src/soft_constraint.cc:61-66), of 1/2 |viol|^2 with w = viol, the
+ *                 J^T lambda term of a KKT check
+ * J_p = d_jac + jac_off[p]: the CSR values of problem p as twr_batch_eval writes them (TWR_EVAL_JACOBIAN or TWR_EVAL_BOTH, any
+ * store policy, any launch path: the layout is the same).  A handle of its own: twr_jac_ops_create takes the same arguments as
+ * twr_batch_create and its x / g / jac layout is exactly that batch's (twr_jac_ops_layout == twr_batch_layout); a batch that
+ * never asks for products allocates nothing for them.  The handle owns the device copies of what it reads (the patterns,
+ * byte-identical ones stored once, column indices in 16 bits, and its work lists), so it may outlive the batch and the
+ * structures.  Both products are asynchronous and stream-ordered on hip_stream and capturable in a hipGraph; device scope,
+ * error codes and the sticky HIP error as twr_batch_eval; NULL buffers are TWR_ERR_INVALID, and so are buffers that are not
+ * 8-byte aligned.  At most ONE product per handle in flight (J^T w keeps its partials in the handle's slab); handles on
+ * different streams are independent.  Outputs must not overlap inputs.
+ * Summation order is a function of the problem's structure alone (structure.h, twr::PlanJacOps): a problem's y and z have the
+ * same bits wherever it sits in whatever batch, on every call, stream and device, and a NaN / Inf in one problem's J, v or w
+ * reaches that problem's outputs only.  A structure without rows: J v writes nothing, J^T w writes zeros; a column without
+ * entries gets an exact 0. */
+typedef struct twr_jac_ops twr_jac_ops;
+int twr_jac_ops_create(const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem, int n_problems, int device,
+                       twr_jac_ops** out);
+void twr_jac_ops_destroy(twr_jac_ops* ops);
+int twr_jac_ops_layout(const twr_jac_ops* ops, int64_t* x_off, int64_t* g_off, int64_t* jac_off);
+/* resident: device bytes the handle holds (tables, work lists, slab); distinct_patterns: the patterns its tables hold once each */
+int twr_jac_ops_bytes(const twr_jac_ops* ops, int64_t* resident, int32_t* distinct_patterns);
+int twr_jac_mul(twr_jac_ops* ops, const double* d_jac, const double* d_v, double* d_y, void* hip_stream);
+int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_z, void* hip_stream);
+/* Host introspection: the CSC view of the CSR pattern -- col_ptr[n_vars + 1], and per entry row_idx[nnz] (ascending within a
+ * column) and csr_pos[nnz], its position in the CSR value array (CSC values = csr_values[csr_pos]).  Any pointer may be NULL.
+ * TWR_ERR_INVALID if a row's column indices do not ascend strictly (they always do for the patterns the factory builds; the
+ * products rely on it). */
+int twr_structure_transpose(const twr_structure* s, int32_t* col_ptr, int32_t* row_idx, int32_t* csr_pos);
+
 /* Tuning knobs.  The DEFAULT build reads nothing from the environment: the values below are compiled in.  A build with
  * -DTWR_TUNING_KNOBS (make -C towr_amd/csrc TUNING=1) reads them, for A/B measurements (scripts/ab.py):
  * TWR_STREAM_NT when a batch is created, TWR_HOST_ZERO_COPY[_X] once per process, the launch knobs (the BPC, FUSED knobs) on

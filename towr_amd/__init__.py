@@ -160,6 +160,15 @@ def lib():
         L.twr_batch_host_buffers.argtypes = [C.c_void_p, C.POINTER(_dp), C.POINTER(_dp), C.POINTER(_dp)]
         L.twr_batch_profile_begin.argtypes = [C.c_void_p, C.c_int]
         L.twr_batch_profile_end.argtypes = [C.c_void_p, _dp, C.POINTER(C.c_int)]
+        L.twr_structure_transpose.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_ops_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
+                                         C.POINTER(C.c_void_p)]
+        L.twr_jac_ops_destroy.argtypes = [C.c_void_p]
+        L.twr_jac_ops_destroy.restype = None
+        L.twr_jac_ops_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        L.twr_jac_ops_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        L.twr_jac_mul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_tmul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -374,6 +383,15 @@ class Structure:
         rows = [tuple(int(v) for v in r) for r in items]
         return {"dynamic": rows[:nd.value], "rom": rows[nd.value:], "dynamic_takes_rom": bool(both.value)}
 
+    def transpose(self):
+        """twr_structure_transpose: the CSC view of the CSR pattern as numpy (col_ptr[n + 1], row_idx[nnz], csr_pos[nnz]); rows
+        ascend within a column, and the CSC values of CSR values v are v[csr_pos]."""
+        cp = np.zeros(self.n + 1, dtype=np.int32)
+        ri = np.zeros(self.nnz, dtype=np.int32)
+        cs = np.zeros(self.nnz, dtype=np.int32)
+        _check(lib().twr_structure_transpose(self._h, cp.ctypes.data, ri.ctypes.data, cs.ctypes.data))
+        return cp, ri, cs
+
     def sample_count(self, dt=0.01):
         """Records fpowr::GetTrajectory produces for this structure at step dt."""
         n = C.c_int32()
@@ -548,3 +566,48 @@ class Batch:
         j = np.zeros(self.jac_off[-1])
         _check(lib().twr_batch_eval_host(self._h, _d(x), _d(g), _d(j), flags))
         return g, j
+
+
+class JacOps:
+    """Products with the Jacobian values of Batch(structures, struct_of_problem) on the device (twr_jac_ops_*), in that batch's
+    x / g / jac layout: mul_device y = J v (v in the x layout, y in the g layout), tmul_device z = J^T w (w in the g layout,
+    z in the x layout)."""
+
+    def __init__(self, structures, struct_of_problem=None, device=0):
+        if struct_of_problem is None:
+            struct_of_problem = list(range(len(structures)))
+        self.structures = list(structures)
+        self.struct_of_problem = np.ascontiguousarray(struct_of_problem, dtype=np.int32)
+        hs = (C.c_void_p * len(structures))(*[s._h for s in structures])
+        self._h = C.c_void_p()
+        _check(lib().twr_jac_ops_create(hs, len(structures), self.struct_of_problem.ctypes.data_as(C.POINTER(C.c_int32)),
+                                        len(self.struct_of_problem), device, C.byref(self._h)))
+        self.device = device
+        self.n_problems = len(self.struct_of_problem)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib().twr_jac_ops_destroy(self._h)
+            self._h = None
+
+    def layout(self):
+        """(x_off, g_off, jac_off), each n_problems + 1 prefix sums: twr_batch_layout of the same arguments."""
+        xo = np.zeros(self.n_problems + 1, dtype=np.int64)
+        go, jo = xo.copy(), xo.copy()
+        p64 = C.POINTER(C.c_int64)
+        _check(lib().twr_jac_ops_layout(self._h, xo.ctypes.data_as(p64), go.ctypes.data_as(p64), jo.ctypes.data_as(p64)))
+        return xo, go, jo
+
+    def bytes(self):
+        """twr_jac_ops_bytes: device bytes the handle holds, and the distinct patterns its tables hold once each."""
+        r, d = C.c_int64(0), C.c_int32(0)
+        _check(lib().twr_jac_ops_bytes(self._h, C.byref(r), C.byref(d)))
+        return dict(resident=r.value, distinct_patterns=d.value)
+
+    def mul_device(self, d_jac, d_v, d_y, stream=0):
+        """twr_jac_mul on raw device pointers (ints); asynchronous on `stream`."""
+        _check(lib().twr_jac_mul(self._h, C.c_void_p(d_jac), C.c_void_p(d_v), C.c_void_p(d_y), C.c_void_p(stream)))
+
+    def tmul_device(self, d_jac, d_w, d_z, stream=0):
+        """twr_jac_tmul on raw device pointers (ints); asynchronous on `stream`."""
+        _check(lib().twr_jac_tmul(self._h, C.c_void_p(d_jac), C.c_void_p(d_w), C.c_void_p(d_z), C.c_void_p(stream)))

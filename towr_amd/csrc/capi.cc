@@ -15,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "jac_products.hip"
 #include "launch.h"
 
 struct twr_structure {
@@ -123,6 +124,18 @@ struct twr_batch {
   // optional per-kernel timing (twr_batch_profile_begin/end): 4 events per recorded eval
   Events prof_events;
   int prof_capacity = 0, prof_count = 0;
+};
+
+struct twr_jac_ops {   // twr::PlanJacOps's tables and work lists on the device, and the slab of J^T w's partials
+  int device = 0, n_problems = 0;
+  std::vector<int64_t> x_off, g_off, j_off;
+  DevPtr<void> tables;
+  DevList<twr::JacMulWork> mul;
+  DevList<twr::JacTWork> tmul;
+  DevList<twr::JacFoldWork> fold;
+  DevPtr<double> slab;
+  int lds_x = 0, distinct_patterns = 0;
+  int64_t resident = 0;
 };
 
 namespace {
@@ -1043,6 +1056,112 @@ int twr_batch_host_buffers(twr_batch* b, double** h_x, double** h_g, double** h_
   } catch (const std::exception& e) {
     return fail(TWR_ERR_HIP, e.what());
   }
+}
+
+int twr_structure_transpose(const twr_structure* s, int32_t* col_ptr, int32_t* row_idx, int32_t* csr_pos) {
+  if (!s) return fail(TWR_ERR_INVALID, "null structure");
+  try {
+    const twr::CscPattern t = twr::TransposePattern(s->s);
+    if (col_ptr) std::memcpy(col_ptr, t.col_ptr.data(), t.col_ptr.size() * sizeof(int32_t));
+    if (row_idx && !t.row_idx.empty()) std::memcpy(row_idx, t.row_idx.data(), t.row_idx.size() * sizeof(int32_t));
+    if (csr_pos && !t.csr_pos.empty()) std::memcpy(csr_pos, t.csr_pos.data(), t.csr_pos.size() * sizeof(int32_t));
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+}
+
+int twr_jac_ops_create(const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem, int n_problems, int device,
+                       twr_jac_ops** out) {
+  if (!structs || !struct_of_problem || !out || n_structs < 1 || n_problems < 1) return fail(TWR_ERR_INVALID, "bad arguments");
+  twr::JacOpsPlan plan;
+  try {   // argument errors
+    std::vector<const twr::Structure*> sp(n_structs);
+    for (int i = 0; i < n_structs; ++i) {
+      if (!structs[i]) throw std::runtime_error("null structure");
+      sp[i] = &structs[i]->s;
+    }
+    plan = twr::PlanJacOps(sp, std::vector<int32_t>(struct_of_problem, struct_of_problem + n_problems));
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+  std::unique_ptr<twr_jac_ops> h(new twr_jac_ops());
+  try {   // device errors
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
+      return fail(TWR_ERR_NO_DEVICE, "no HIP device visible: towr_amd has no CPU fallback");
+    if (device < 0 || device >= n_dev) return fail(TWR_ERR_INVALID, "device ordinal out of range");
+    DeviceScope on(device);
+    TWR_HIP(on.status);
+    h->device = device;
+    h->n_problems = n_problems;
+    h->x_off = plan.x_off;
+    h->g_off = plan.g_off;
+    h->j_off = plan.j_off;
+    const size_t tb = std::max<size_t>(16, plan.tables.size());
+    h->tables = dev_alloc<void>(tb);
+    if (!plan.tables.empty()) TWR_HIP(hipMemcpy(h->tables.get(), plan.tables.data(), plan.tables.size(), hipMemcpyHostToDevice));
+    plan.Place(reinterpret_cast<uint64_t>(h->tables.get()));
+    if (!plan.mul.empty()) h->mul = upload(plan.mul);
+    if (!plan.tmul.empty()) h->tmul = upload(plan.tmul);
+    if (!plan.fold.empty()) h->fold = upload(plan.fold);
+    h->slab = dev_alloc<double>(sizeof(double) * std::max<size_t>(1, (size_t)plan.slab));
+    h->lds_x = plan.mul_lds_x;
+    h->distinct_patterns = plan.distinct_patterns;
+    h->resident = (int64_t)tb + (int64_t)(plan.mul.size() * sizeof(twr::JacMulWork) + plan.tmul.size() * sizeof(twr::JacTWork) +
+                                          plan.fold.size() * sizeof(twr::JacFoldWork)) +
+                  8 * std::max<int64_t>(1, plan.slab);
+    *out = h.release();
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    twr_jac_ops_destroy(h.release());
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+void twr_jac_ops_destroy(twr_jac_ops* ops) {
+  if (!ops) return;
+  DeviceScope on(ops->device);
+  delete ops;
+}
+
+int twr_jac_ops_layout(const twr_jac_ops* ops, int64_t* x_off, int64_t* g_off, int64_t* jac_off) {
+  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
+  const size_t bytes = (ops->n_problems + 1) * sizeof(int64_t);
+  if (x_off) std::memcpy(x_off, ops->x_off.data(), bytes);
+  if (g_off) std::memcpy(g_off, ops->g_off.data(), bytes);
+  if (jac_off) std::memcpy(jac_off, ops->j_off.data(), bytes);
+  return TWR_OK;
+}
+
+int twr_jac_ops_bytes(const twr_jac_ops* ops, int64_t* resident, int32_t* distinct_patterns) {
+  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
+  if (resident) *resident = ops->resident;
+  if (distinct_patterns) *distinct_patterns = ops->distinct_patterns;
+  return TWR_OK;
+}
+
+int twr_jac_mul(twr_jac_ops* ops, const double* d_jac, const double* d_v, double* d_y, void* hip_stream) {
+  if (!ops || !d_jac || !d_v || !d_y) return fail(TWR_ERR_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(d_jac) | reinterpret_cast<uintptr_t>(d_v) | reinterpret_cast<uintptr_t>(d_y)) & 7)
+    return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(ops->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipError_t e = twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, d_v, d_y, static_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return TWR_OK;
+}
+
+int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_z, void* hip_stream) {
+  if (!ops || !d_jac || !d_w || !d_z) return fail(TWR_ERR_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(d_jac) | reinterpret_cast<uintptr_t>(d_w) | reinterpret_cast<uintptr_t>(d_z)) & 7)
+    return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(ops->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipError_t e = twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, d_w, ops->slab.get(), d_z,
+                                      static_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return TWR_OK;
 }
 
 }  // extern "C"

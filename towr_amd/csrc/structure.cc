@@ -2305,4 +2305,187 @@ EvalPlan PlanEval(const EvalShape& s) {
   return plan;
 }
 
+// ---------------------------------------------------------------- products with the Jacobian values (jac_products.hip)
+namespace {
+void CheckPattern(const Structure& S) {
+  const int n = S.n_vars, m = S.n_rows;
+  if ((int)S.row_ptr.size() != m + 1 || (int)S.col_idx.size() != S.nnz || S.row_ptr[0] != 0 || S.row_ptr[m] != S.nnz)
+    throw std::runtime_error("CSR pattern does not match its sizes");
+  if (n > 65536) throw std::runtime_error("more than 65536 variables: column indices do not fit 16 bits");
+  for (int r = 0; r < m; ++r) {
+    if (S.row_ptr[r + 1] < S.row_ptr[r]) throw std::runtime_error("row_ptr descends");
+    for (int k = S.row_ptr[r]; k < S.row_ptr[r + 1]; ++k) {
+      const int c = S.col_idx[k];
+      if (c < 0 || c >= n) throw std::runtime_error("column index outside [0, n_vars)");
+      if (k > S.row_ptr[r] && c <= S.col_idx[k - 1])
+        throw std::runtime_error("row " + std::to_string(r) + ": column indices not strictly ascending (unsorted or duplicate entries)");
+    }
+  }
+}
+
+template <class T>
+uint64_t AppendTable(std::vector<char>& out, const T* data, size_t count) {
+  const size_t at = (out.size() + 15) / 16 * 16;
+  out.resize(at + count * sizeof(T));
+  if (count) std::memcpy(out.data() + at, data, count * sizeof(T));
+  return at;
+}
+
+uint64_t HashWords(uint64_t h, const void* data, size_t bytes) {   // FNV-1a over 8-byte words (a bucket key only)
+  const char* p = static_cast<const char*>(data);
+  size_t i = 0;
+  for (; i + 8 <= bytes; i += 8) {
+    uint64_t w;
+    std::memcpy(&w, p + i, 8);
+    h = (h ^ w) * 1099511628211ull;
+    h ^= h >> 29;
+  }
+  for (; i < bytes; ++i) h = (h ^ (unsigned char)p[i]) * 1099511628211ull;
+  return h;
+}
+
+struct JacTables {   // one distinct pattern: byte offsets into JacOpsPlan::tables, its blocks, partials per problem
+  uint64_t col = 0, row_ptr = 0, fold_ptr = 0, fold_slot = 0;
+  std::vector<std::pair<int, int>> rows;   // J v blocks [r0, r1)
+  struct TBlock {
+    int k0, k1, r_first, span, ncols;
+    uint64_t map;
+    int64_t slot;                          // first partial, relative to the problem's
+  };
+  std::vector<TBlock> tblocks;
+  int64_t slots = 0;
+};
+
+JacTables BuildJacTables(const Structure& S, JacOpsPlan& J) {
+  const int n = S.n_vars, m = S.n_rows, nnz = S.nnz;
+  JacTables P;
+  const std::vector<uint16_t> col(S.col_idx.begin(), S.col_idx.end());   // < 65536: CheckPattern
+  P.col = AppendTable(J.tables, col.data(), col.size());
+  P.row_ptr = AppendTable(J.tables, S.row_ptr.data(), S.row_ptr.size());
+  J.table_bytes_mul += 2 * (int64_t)nnz + 4 * (int64_t)(m + 1);
+  for (int r0 = 0; r0 < m;) {
+    int r1 = r0 + 1;
+    while (r1 < m && r1 - r0 < kJacMulRows && S.row_ptr[r1 + 1] - S.row_ptr[r0] <= kJacMulNnz) ++r1;
+    P.rows.push_back({r0, r1});
+    r0 = r1;
+  }
+  std::vector<int> row_of(nnz);
+  for (int r = 0; r < m; ++r) std::fill(row_of.begin() + S.row_ptr[r], row_of.begin() + S.row_ptr[r + 1], r);
+  std::vector<int> stamp(n, -1);
+  std::vector<std::vector<int32_t>> slots_of(n);   // the partials of every column, in block order
+  int64_t tbytes = 4 * (int64_t)(m + 1);
+  for (int k0 = 0; k0 < nnz;) {
+    const int b = (int)P.tblocks.size();
+    int k1 = k0, ncols = 0;
+    while (k1 < nnz && k1 - k0 < kJacTNnz && row_of[k1] - row_of[k0] < kJacTSpan) {
+      const int c = S.col_idx[k1];
+      if (stamp[c] != b) {
+        if (ncols == kJacTCols) break;
+        stamp[c] = b;
+        ++ncols;
+      }
+      ++k1;
+    }
+    std::vector<std::pair<int, int>> e;   // (column, entry - k0), sorted: the block's columns ascending, each in row order
+    for (int k = k0; k < k1; ++k) e.push_back({S.col_idx[k], k - k0});
+    std::sort(e.begin(), e.end());
+    std::vector<uint16_t> map(ncols + 1 + e.size());
+    int j = -1;
+    for (size_t i = 0; i < e.size(); ++i) {
+      if (i == 0 || e[i].first != e[i - 1].first) {
+        map[++j] = (uint16_t)i;
+        slots_of[e[i].first].push_back((int32_t)(P.slots + j));
+      }
+      map[ncols + 1 + i] = (uint16_t)e[i].second;
+    }
+    map[ncols] = (uint16_t)e.size();
+    const uint64_t at = AppendTable(J.tables, map.data(), map.size());
+    tbytes += 2 * (int64_t)map.size();
+    P.tblocks.push_back({k0, k1, row_of[k0], row_of[k1 - 1] - row_of[k0] + 1, ncols, at, P.slots});
+    P.slots += ncols;
+    k0 = k1;
+  }
+  std::vector<int32_t> fptr(n + 1, 0), fslot;
+  for (int c = 0; c < n; ++c) {
+    fslot.insert(fslot.end(), slots_of[c].begin(), slots_of[c].end());
+    fptr[c + 1] = (int32_t)fslot.size();
+  }
+  P.fold_ptr = AppendTable(J.tables, fptr.data(), fptr.size());
+  P.fold_slot = AppendTable(J.tables, fslot.data(), fslot.size());
+  J.table_bytes_tmul += tbytes + 4 * (int64_t)(fptr.size() + fslot.size());
+  return P;
+}
+}  // namespace
+
+CscPattern TransposePattern(const Structure& S) {
+  CheckPattern(S);
+  CscPattern t;
+  t.col_ptr.assign(S.n_vars + 1, 0);
+  for (int k = 0; k < S.nnz; ++k) ++t.col_ptr[S.col_idx[k] + 1];
+  for (int c = 0; c < S.n_vars; ++c) t.col_ptr[c + 1] += t.col_ptr[c];
+  t.row_idx.resize(S.nnz);
+  t.csr_pos.resize(S.nnz);
+  std::vector<int32_t> next(t.col_ptr.begin(), t.col_ptr.end() - 1);
+  for (int r = 0; r < S.n_rows; ++r)
+    for (int k = S.row_ptr[r]; k < S.row_ptr[r + 1]; ++k) {
+      const int q = next[S.col_idx[k]]++;
+      t.row_idx[q] = r;
+      t.csr_pos[q] = k;
+    }
+  return t;
+}
+
+void JacOpsPlan::Place(uint64_t base) {
+  for (auto& w : mul) w.col += base, w.row_ptr += base;
+  for (auto& w : tmul) w.map += base, w.row_ptr += base;
+  for (auto& w : fold) w.ptr += base, w.slot += base;
+}
+
+JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem) {
+  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
+  JacOpsPlan J;
+  std::vector<JacTables> pats;
+  std::vector<const Structure*> first;   // the first structure of every distinct pattern
+  std::unordered_map<uint64_t, std::vector<int>> by_hash;
+  J.pattern_of_struct.resize(n_structs);
+  for (int i = 0; i < n_structs; ++i) {
+    const Structure& S = *structs[i];
+    CheckPattern(S);
+    uint64_t h = HashWords(1469598103934665603ull ^ (uint64_t)S.n_vars, S.row_ptr.data(), S.row_ptr.size() * sizeof(int32_t));
+    h = HashWords(h, S.col_idx.data(), S.col_idx.size() * sizeof(int32_t));
+    std::vector<int>& bucket = by_hash[h];
+    int pid = -1;
+    for (int q : bucket)
+      if (first[q]->n_vars == S.n_vars && first[q]->row_ptr == S.row_ptr && first[q]->col_idx == S.col_idx) pid = q;
+    if (pid < 0) {
+      pid = (int)pats.size();
+      bucket.push_back(pid);
+      first.push_back(&S);
+      pats.push_back(BuildJacTables(S, J));
+    }
+    J.pattern_of_struct[i] = pid;
+  }
+  J.distinct_patterns = (int)pats.size();
+  J.x_off.assign(n_problems + 1, 0);
+  J.g_off.assign(n_problems + 1, 0);
+  J.j_off.assign(n_problems + 1, 0);
+  for (int p = 0; p < n_problems; ++p) {
+    const int si = struct_of_problem[p];
+    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
+    const Structure& S = *structs[si];
+    const JacTables& P = pats[J.pattern_of_struct[si]];
+    J.x_off[p + 1] = J.x_off[p] + S.n_vars;
+    J.g_off[p + 1] = J.g_off[p] + S.n_rows;
+    J.j_off[p + 1] = J.j_off[p] + S.nnz;
+    for (const auto& rb : P.rows) J.mul.push_back({J.x_off[p], J.g_off[p], J.j_off[p], P.col, P.row_ptr, rb.first, rb.second, S.n_vars, 0});
+    for (const auto& tb : P.tblocks)
+      J.tmul.push_back({J.g_off[p], J.j_off[p], J.slab + tb.slot, tb.map, P.row_ptr, tb.k0, tb.k1, tb.r_first, tb.span, tb.ncols, 0});
+    for (int c0 = 0; c0 < S.n_vars; c0 += kJacFoldCols)
+      J.fold.push_back({J.x_off[p], J.slab, P.fold_ptr, P.fold_slot, c0, std::min(S.n_vars, c0 + kJacFoldCols)});
+    J.slab += P.slots;
+    if (S.n_vars <= kJacLdsX) J.mul_lds_x = std::max(J.mul_lds_x, S.n_vars);
+  }
+  return J;
+}
+
 }  // namespace twr

@@ -263,6 +263,63 @@ struct EvalPlan {
   LaunchStep step[kMaxSteps];
 };
 EvalPlan PlanEval(const EvalShape& shape);
+// Products with a batch's Jacobian values (twr_jac_mul: y = J v, twr_jac_tmul: z = J^T w; jac_products.hip), planned on the host
+// (no HIP).  The CSC view of a structure's CSR pattern: col_ptr[n + 1]; per entry its row and its position in the CSR value
+// array, rows ascending within a column.  Throws when a row's columns do not ascend strictly (unsorted or duplicate entries)
+// or leave [0, n_vars): the products rely on both.
+struct CscPattern {
+  std::vector<int32_t> col_ptr, row_idx, csr_pos;
+};
+CscPattern TransposePattern(const Structure& S);
+// Work split of the two products (both: workgroups of kJacThreads lanes; every index from these tables, never from J, v or w).
+//   J v:    blocks of consecutive rows, at most kJacMulRows rows and kJacMulNnz entries (a longer row is a block of its own).  The
+//           block's entries are streamed with 16-byte loads, each multiplied by v[col] (v staged in LDS when n <= kJacLdsX, else
+//           gathered from memory) into an LDS tile of kJacMulNnz products; the lane of a row then sums its products in column
+//           order, across tiles for a longer row.
+//   J^T w:  blocks of consecutive ENTRIES (rows need not be whole), at most kJacTNnz of them, kJacTCols distinct columns and rows
+//           within a span of kJacTSpan.  The block's values are staged in LDS, every one multiplied by its row's w; the lane of a
+//           column sums its products in row order (the block's map) into one partial of the slab; the fold then sums every
+//           column's partials in block order (exact 0 for a column without entries).
+// The order of every sum is a function of the pattern alone: not of the batch, the call or the device.
+constexpr int kJacThreads = 256;
+constexpr int kJacMulRows = 256, kJacMulNnz = 2048;
+constexpr int kJacTNnz = 2048, kJacTCols = 256, kJacTSpan = 512;
+constexpr int kJacLdsX = 6144;       // doubles of v jac_mul_kernel stages in LDS at most (48 KB; 64 KB with the products)
+constexpr int kJacFoldCols = 256;    // columns of one fold item
+// The work records (device layout; the table fields are byte offsets into JacOpsPlan::tables until Place() makes them addresses)
+struct JacMulWork {     // rows [r0, r1) of one problem
+  int64_t x_off, g_off, j_off;
+  uint64_t col, row_ptr;           // the pattern's uint16 col[nnz], int32 row_ptr[m + 1]
+  int32_t r0, r1, n, pad;          // n: variables (v is staged in LDS when n <= kJacLdsX)
+};
+struct JacTWork {       // entries [k0, k1) of one problem, rows [r_first, r_first + span)
+  int64_t g_off, j_off, slab;      // slab: the block's first partial (its columns' partials follow in map order)
+  uint64_t map, row_ptr;           // the block's uint16 lcol_ptr[ncols + 1], then uint16 pos[k1 - k0] (entry - k0, per column in
+                                   // row order); the pattern's int32 row_ptr[m + 1]
+  int32_t k0, k1, r_first, span, ncols, pad;
+};
+struct JacFoldWork {    // columns [c0, c1) of one problem
+  int64_t x_off, slab;             // slab: the problem's first partial
+  uint64_t ptr, slot;              // the pattern's int32 fold_ptr[n + 1], int32 fold_slot[]: column c sums
+                                   // slab[fold_slot[fold_ptr[c] .. fold_ptr[c + 1])] in that order
+  int32_t c0, c1;
+};
+struct JacOpsPlan {
+  std::vector<int64_t> x_off, g_off, j_off;   // n_problems + 1: the layout of PlanBatch for the same arguments
+  std::vector<char> tables;                   // every distinct pattern's tables, once (16-byte aligned)
+  std::vector<int32_t> pattern_of_struct;     // the distinct pattern every structure reads
+  int distinct_patterns = 0;
+  std::vector<JacMulWork> mul;                // problem by problem, blocks in row order
+  std::vector<JacTWork> tmul;                 // problem by problem, blocks in entry order
+  std::vector<JacFoldWork> fold;
+  int64_t slab = 0;                           // partials of one J^T w (doubles)
+  int mul_lds_x = 0;                          // largest n <= kJacLdsX of the batch (the v jac_mul_kernel stages)
+  int64_t table_bytes_mul = 0, table_bytes_tmul = 0;   // bytes of the distinct tables each product reads
+  void Place(uint64_t base);                  // table offsets -> device addresses (base: where `tables` lives)
+};
+// (structs, struct_of_problem) as for twr_batch_create.  Byte-identical patterns (n, m, row_ptr, col_idx) share one set of tables.
+JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
+
 // fpowr GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53): samples while t <= t_total + 1e-5, t accumulated
 int SampleCount(double t_total, double dt);
 void GaitCombo(int n_ee, int combo, double t_total, double swing_scale, twr_schedule* out);
