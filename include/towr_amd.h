@@ -442,6 +442,46 @@ int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, doubl
  * products rely on it). */
 int twr_structure_transpose(const twr_structure* s, int32_t* col_ptr, int32_t* row_idx, int32_t* csr_pos);
 
+/* The damped weighted least-squares step with the Jacobian values of a batch, on the device (new; the linear solve in the middle
+ * of a Levenberg-Marquardt / damped Gauss-Newton method), per problem p and for the whole batch at once:
+ *   d_p = argmin_d  sum_r w_r (J_p d - b_p)_r^2 + mu_p |d|^2     <=>   (J_p^T W_p J_p + mu_p I) d_p = J_p^T W_p b_p
+ * by CGLS on top of twr_jac_mul / twr_jac_tmul: matrix-free, no factorisation, J^T J never formed (towr's J is rank deficient;
+ * mu > 0 makes the step unique).  A handle of its own, created from a twr_jac_ops it BORROWS (ops must outlive it) and the
+ * arguments ops was created with: a mismatch in the problem count or in any problem's n / m is TWR_ERR_INVALID, and so is a
+ * NULL ops (checked before any device is touched).  The handle owns the solver's workspace and the device copy of the per-row
+ * bounds (twr_structure_bounds; byte-identical tables stored once); a twr_jac_ops that never asks for a solve allocates nothing.
+ * All three calls are asynchronous and stream-ordered on hip_stream and capturable in a hipGraph (kernel launches only); device
+ * scope, error codes, the sticky HIP error, NULL and 8-byte alignment checks as twr_jac_mul.  At most ONE call per handle in
+ * flight, and none together with a product on the borrowed ops (the solve uses the handle's workspace and the ops' slab).
+ * Outputs must not overlap inputs.  No atomics: every per-problem sum is taken in an order fixed by the problem's sizes alone,
+ * so a problem's outputs have the same bits wherever it sits in whatever batch, on every call and stream, and a NaN / Inf in
+ * one problem's inputs reaches that problem's outputs only.
+ *   twr_jac_dot:       d_out[p] = sum_i a_i b_i over the x layout (space 0) or the g layout (space 1)
+ *   twr_jac_violation: d_r = g - min(max(g, lower), upper): |r_i| is the per-row quantity twr_batch_score reduces, a NaN g_i gives
+ *                      a NaN r_i.  Optional (NULL to leave out): d_w weights (NULL = 1), d_w_active = w [r != 0] (the active-set
+ *                      weights), d_merit[p] = 1/2 sum_i w_i r_i^2.
+ *   twr_jac_lsq_solve: d_d (x layout) = the step above from d = 0: r = b, s = J^T(w o r), p = s, gamma = gamma0 = s^T s; repeat
+ *                      q = J p, delta = q^T(w o q) + mu p^T p, alpha = gamma / delta, d += alpha p, r -= alpha q,
+ *                      s = J^T(w o r) - mu d, gamma' = s^T s, beta = gamma' / gamma, p = s + beta p.  At most `iters` iterations; a
+ *                      problem stops when gamma <= tol^2 gamma0, and from then on its d does not change whatever the rest of the
+ *                      batch still does (a larger `iters` gives the same bits).  d_w NULL = unit weights.  d_mu: one mu >= 0 per
+ *                      problem, read on the device; the launch sequence depends on iters alone, no scalar comes to the host.
+ *                      d_info[4p ..]: iterations taken, |s| / |s0|, |s0|, status: 0 converged (also |s0| = 0: b = 0 or a structure
+ *                      without rows, d = 0), 1 iteration cap, 2 bad input (mu < 0 or not finite, a non-finite |s0| or gamma, a
+ *                      delta that is not a positive finite number); d is then what it was when the problem stopped, zeros if
+ *                      that was at the start.  iters == 0 writes d = 0 and |s0|. */
+typedef struct twr_jac_lsq twr_jac_lsq;
+int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem,
+                       int n_problems, twr_jac_lsq** out);
+void twr_jac_lsq_destroy(twr_jac_lsq* lsq);
+/* resident: device bytes the handle holds (bound tables, work records, workspace) */
+int twr_jac_lsq_bytes(const twr_jac_lsq* lsq, int64_t* resident);
+int twr_jac_dot(twr_jac_lsq* lsq, int space, const double* d_a, const double* d_b, double* d_out, void* hip_stream);
+int twr_jac_violation(twr_jac_lsq* lsq, const double* d_g, const double* d_w, double* d_r, double* d_w_active, double* d_merit,
+                      void* hip_stream);
+int twr_jac_lsq_solve(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu, int iters,
+                      double tol, double* d_d, double* d_info, void* hip_stream);
+
 /* Tuning knobs.  The DEFAULT build reads nothing from the environment: the values below are compiled in.  A build with
  * -DTWR_TUNING_KNOBS (make -C towr_amd/csrc TUNING=1) reads them, for A/B measurements (scripts/ab.py):
  * TWR_STREAM_NT when a batch is created, TWR_HOST_ZERO_COPY[_X] once per process, the launch knobs (the BPC, FUSED knobs) on

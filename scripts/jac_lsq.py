@@ -1,0 +1,185 @@
+"""Time twr_jac_lsq_solve on the device and run a small Levenberg-Marquardt loop on top of it; prints one JSON line.
+
+Workloads: C3 (ANYmal trot, K = 200, 8192 problems of one structure) and the 1024-candidate C5 Stairs sweep, built as
+scripts/jac_products.py builds them; buffers as torch hands them out, HIP events, median of --rounds.
+  * cgls: milliseconds per CGLS iteration (a --cg-iters solve with tol = 0, so that no problem stops, divided by --cg-iters)
+    against one twr_jac_mul + one twr_jac_tmul timed in the same process on the same buffers, and the ratio of the two.  By
+    bytes an iteration is 2 * 8 (n + m + nnz) in the two products plus about 8 (8 n + 6 m) in the vector kernels.
+  * lm: --lm-steps steps of eval -> violation -> solve -> x + d -> eval(values) -> violation, the accept / reject per problem in
+    torch on the device (mu / 3 on accept, * 10 on reject; no synchronise inside a step): the batch's merit 1/2 sum viol^2 and
+    its summed inf-norm scores before and after, and the device time per step split into evaluation and solve.
+mu starts at 1e-2 lambda_max(J^T W J) per problem, lambda_max from --power-iters power iterations with the two products and
+twr_jac_dot, all on the device.
+Usage (each GPU step under its own time limit):
+  timeout -k 10 600 python scripts/jac_lsq.py --workload c3 && timeout -k 10 600 python scripts/jac_lsq.py --workload c5
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import towr_amd as ta  # noqa: E402
+from jac_products import c3, c5  # noqa: E402
+
+
+class Problem:
+    def __init__(self, torch, structs, order, x_h):
+        self.torch, self.dev = torch, torch.device("cuda", 0)
+        self.st = torch.cuda.current_stream().cuda_stream
+        self.batch = ta.Batch(structs, order, device=0)
+        self.ops = ta.JacOps(structs, order, device=0)
+        self.lsq = ta.JacLsq(self.ops)
+        self.xo, self.go, self.jo = self.ops.layout()
+        self.P = len(order)
+        self.X, self.G, self.J = int(self.xo[-1]), int(self.go[-1]), int(self.jo[-1])
+        self.x = torch.from_numpy(x_h).to(self.dev)
+        self.of_x = torch.repeat_interleave(torch.arange(self.P, device=self.dev), torch.from_numpy(np.diff(self.xo)).to(self.dev))
+        self.jac = self.vec(self.J)
+
+    def vec(self, n):
+        return self.torch.zeros(n, dtype=self.torch.float64, device=self.dev)
+
+    def lambda_max(self, wa, iters):
+        """Per-problem power iteration on J^T W J: v <- J^T (w o (J v)) / |v|, lambda = v^T J^T W J v / v^T v."""
+        torch = self.torch
+        v = torch.from_numpy(np.random.default_rng(3).normal(size=self.X)).to(self.dev)
+        y, z, vv, vz = self.vec(self.G), self.vec(self.X), self.vec(self.P), self.vec(self.P)
+        for _ in range(iters):
+            self.ops.mul_device(self.jac.data_ptr(), v.data_ptr(), y.data_ptr(), self.st)
+            y.mul_(wa)
+            self.ops.tmul_device(self.jac.data_ptr(), y.data_ptr(), z.data_ptr(), self.st)
+            self.lsq.dot_device(self.lsq.X, v.data_ptr(), v.data_ptr(), vv.data_ptr(), self.st)
+            self.lsq.dot_device(self.lsq.X, v.data_ptr(), z.data_ptr(), vz.data_ptr(), self.st)
+            v = z / torch.sqrt(self.lsq_dot(z, z))[self.of_x].clamp_min(1e-300)
+        return vz / vv.clamp_min(1e-300)
+
+    def lsq_dot(self, a, b):
+        out = self.vec(self.P)
+        self.lsq.dot_device(self.lsq.X, a.data_ptr(), b.data_ptr(), out.data_ptr(), self.st)
+        return out
+
+
+def timed(torch, f, steps, rounds):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ms = []
+    for _ in range(rounds):
+        e0.record()
+        for _ in range(steps):
+            f()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1) / steps)
+    return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+
+
+def measure(torch, name, structs, order, x_h, a):
+    Q = Problem(torch, structs, order, x_h)
+    st, lsq, ops, batch = Q.st, Q.lsq, Q.ops, Q.batch
+    g, r, wa, merit, d, info = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(Q.X), Q.vec(4 * Q.P)
+    g2, r2, merit2, scores = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(16 * Q.P)
+    batch.eval_device(Q.x.data_ptr(), g.data_ptr(), Q.jac.data_ptr(), ta.EVAL_BOTH, st)
+    lsq.violation_device(g.data_ptr(), r.data_ptr(), d_w_active=wa.data_ptr(), d_merit=merit.data_ptr(), stream=st)
+    b = -r
+    lam = Q.lambda_max(wa, a.power_iters)
+    mu = 1e-2 * lam
+    torch.cuda.synchronize()
+    out = {"workload": name, "problems": Q.P, "jac_lsq_bytes": lsq.bytes()["resident"], "jac_ops_bytes": ops.bytes()["resident"],
+           "lambda_max": [float(lam.min()), float(lam.max())]}
+
+    # ---- one CGLS iteration against the two products
+    y, z = Q.vec(Q.G), Q.vec(Q.X)
+
+    def solve(iters, tol):
+        lsq.solve_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), iters, tol, d_w=wa.data_ptr(), stream=st)
+
+    calls = {"mul": lambda: ops.mul_device(Q.jac.data_ptr(), d.data_ptr(), y.data_ptr(), st),
+             "tmul": lambda: ops.tmul_device(Q.jac.data_ptr(), r.data_ptr(), z.data_ptr(), st),
+             "solve": lambda: solve(a.cg_iters, 0.0), "solve0": lambda: solve(0, 0.0)}
+    for f in calls.values():
+        f()
+        f()
+    torch.cuda.synchronize()
+    t = {k: timed(torch, f, a.steps if k in ("mul", "tmul") else 2, a.rounds) for k, f in calls.items()}
+    per_iter = (t["solve"][0] - t["solve0"][0]) / a.cg_iters
+    products = t["mul"][0] + t["tmul"][0]
+    nb = 8 * (Q.X + Q.G + Q.J)
+    out["cgls"] = {"cg_iters": a.cg_iters, "ms_solve": t["solve"], "ms_start": t["solve0"], "ms_per_iteration": t["solve"][0] / a.cg_iters,
+                   "ms_per_iteration_without_start": per_iter, "ms_mul": t["mul"], "ms_tmul": t["tmul"],
+                   "ms_products": products, "ratio_to_products": t["solve"][0] / a.cg_iters / products,
+                   "ratio_without_start": per_iter / products,
+                   "bytes_products": 2 * nb, "bytes_vectors": 8 * (8 * Q.X + 6 * Q.G),
+                   "ratio_by_bytes": 1.0 + 8 * (8 * Q.X + 6 * Q.G) / (2 * nb)}
+    solve(a.cg_iters, 1e-10)
+    torch.cuda.synchronize()
+    it = info.view(-1, 4)
+    out["cgls"]["at_tol_1e-10"] = {"iterations_min_max": [float(it[:, 0].min()), float(it[:, 0].max())],
+                                   "status_counts": [int((it[:, 3] == s).sum()) for s in (0, 1, 2)]}
+
+    # ---- Levenberg-Marquardt
+    def score_sum():
+        batch.eval_scores_device(Q.x.data_ptr(), scores.data_ptr(), d_g=g2.data_ptr(), stream=st)
+        return float(scores.view(Q.P, 8, 2)[:, :, 0].sum())
+
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(a.lm_steps)]
+    out["lm"] = {"steps": a.lm_steps, "cg_iters": a.lm_cg_iters, "merit_before": float(merit.sum()), "scores_before": score_sum()}
+    accepted = Q.vec(a.lm_steps)
+    for k in range(a.lm_steps):   # nothing in here waits for the device
+        ev[k][0].record()
+        batch.eval_device(Q.x.data_ptr(), g.data_ptr(), Q.jac.data_ptr(), ta.EVAL_BOTH, st)
+        lsq.violation_device(g.data_ptr(), r.data_ptr(), d_w_active=wa.data_ptr(), d_merit=merit.data_ptr(), stream=st)
+        torch.neg(r, out=b)
+        ev[k][1].record()
+        lsq.solve_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), a.lm_cg_iters, 1e-8, d_w=wa.data_ptr(),
+                         stream=st)
+        ev[k][2].record()
+        xt = Q.x + d
+        batch.eval_device(xt.data_ptr(), g2.data_ptr(), 0, ta.EVAL_VALUES, st)
+        lsq.violation_device(g2.data_ptr(), r2.data_ptr(), d_merit=merit2.data_ptr(), stream=st)
+        ok = merit2 < merit
+        Q.x = torch.where(ok[Q.of_x], xt, Q.x)
+        mu = torch.where(ok, mu / 3.0, mu * 10.0)
+        accepted[k] = ok.sum()
+        ev[k][3].record()
+    torch.cuda.synchronize()
+    batch.eval_device(Q.x.data_ptr(), g.data_ptr(), 0, ta.EVAL_VALUES, st)
+    lsq.violation_device(g.data_ptr(), r.data_ptr(), d_merit=merit.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    ms_eval = [e[0].elapsed_time(e[1]) + e[2].elapsed_time(e[3]) for e in ev]
+    ms_solve = [e[1].elapsed_time(e[2]) for e in ev]
+    out["lm"].update(merit_after=float(merit.sum()), scores_after=score_sum(), accepted_per_step=[int(v) for v in accepted.cpu()],
+                     ms_eval_per_step=float(np.median(ms_eval)), ms_solve_per_step=float(np.median(ms_solve)),
+                     viol_inf_after_min_median_max=[float(v) for v in np.quantile(
+                         scores.view(Q.P, 8, 2)[:, :, 0].max(dim=1).values.cpu().numpy(), [0, 0.5, 1])])
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--cg-iters", type=int, default=50)
+    ap.add_argument("--power-iters", type=int, default=30)
+    ap.add_argument("--lm-steps", type=int, default=8)
+    ap.add_argument("--lm-cg-iters", type=int, default=60)
+    ap.add_argument("--workload", choices=("c3", "c5", "both"), default="both")
+    ap.add_argument("--c3-problems", type=int, default=8192)
+    a = ap.parse_args()
+    import torch
+
+    res = []
+    if a.workload in ("c3", "both"):
+        res.append(measure(torch, "C3", *c3(a.c3_problems), a))
+        torch.cuda.empty_cache()
+    if a.workload in ("c5", "both"):
+        res.append(measure(torch, "C5 stairs sweep", *c5(), a))
+    print(json.dumps({"jac_lsq": res}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

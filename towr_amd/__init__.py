@@ -169,6 +169,15 @@ def lib():
         L.twr_jac_ops_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
         L.twr_jac_mul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.twr_jac_tmul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_lsq_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32), C.c_int,
+                                         C.POINTER(C.c_void_p)]
+        L.twr_jac_lsq_destroy.argtypes = [C.c_void_p]
+        L.twr_jac_lsq_destroy.restype = None
+        L.twr_jac_lsq_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.twr_jac_dot.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_violation.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]
+        L.twr_jac_lsq_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -611,3 +620,48 @@ class JacOps:
     def tmul_device(self, d_jac, d_w, d_z, stream=0):
         """twr_jac_tmul on raw device pointers (ints); asynchronous on `stream`."""
         _check(lib().twr_jac_tmul(self._h, C.c_void_p(d_jac), C.c_void_p(d_w), C.c_void_p(d_z), C.c_void_p(stream)))
+
+
+class JacLsq:
+    """The damped weighted least-squares step with the Jacobian values of a batch on the device (twr_jac_lsq_*), on top of the
+    products of `jac_ops` (borrowed: it is kept alive here) and in its x / g / jac layout: per problem
+    (J^T W J + mu I) d = J^T W b by CGLS, the bound-violation residual that feeds it, and per-problem dot products."""
+
+    X, G = 0, 1   # the `space` of dot_device
+
+    def __init__(self, jac_ops):
+        self.ops = jac_ops
+        hs = (C.c_void_p * len(jac_ops.structures))(*[s._h for s in jac_ops.structures])
+        self._h = C.c_void_p()
+        _check(lib().twr_jac_lsq_create(jac_ops._h, hs, len(jac_ops.structures),
+                                        jac_ops.struct_of_problem.ctypes.data_as(C.POINTER(C.c_int32)), jac_ops.n_problems,
+                                        C.byref(self._h)))
+        self.device = jac_ops.device
+        self.n_problems = jac_ops.n_problems
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib().twr_jac_lsq_destroy(self._h)
+            self._h = None
+
+    def bytes(self):
+        """twr_jac_lsq_bytes: device bytes the handle holds (bound tables, work records, workspace)."""
+        r = C.c_int64(0)
+        _check(lib().twr_jac_lsq_bytes(self._h, C.byref(r)))
+        return dict(resident=r.value)
+
+    def dot_device(self, space, d_a, d_b, d_out, stream=0):
+        """twr_jac_dot on raw device pointers (ints): d_out[p] = a_p . b_p over the x layout (space 0) or the g layout (1)."""
+        _check(lib().twr_jac_dot(self._h, space, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out), C.c_void_p(stream)))
+
+    def violation_device(self, d_g, d_r, d_w=0, d_w_active=0, d_merit=0, stream=0):
+        """twr_jac_violation on raw device pointers (ints, 0 = leave out): r = g - clip(g, lower, upper), w_active = w [r != 0],
+        merit[p] = 1/2 sum w r^2."""
+        _check(lib().twr_jac_violation(self._h, C.c_void_p(d_g), C.c_void_p(d_w), C.c_void_p(d_r), C.c_void_p(d_w_active),
+                                       C.c_void_p(d_merit), C.c_void_p(stream)))
+
+    def solve_device(self, d_jac, d_b, d_mu, d_d, d_info, iters, tol, d_w=0, stream=0):
+        """twr_jac_lsq_solve on raw device pointers (ints; d_w 0 = unit weights); asynchronous on `stream`.  d_info: 4 doubles
+        per problem (iterations, |s| / |s0|, |s0|, status)."""
+        _check(lib().twr_jac_lsq_solve(self._h, C.c_void_p(d_jac), C.c_void_p(d_b), C.c_void_p(d_w), C.c_void_p(d_mu), int(iters),
+                                       float(tol), C.c_void_p(d_d), C.c_void_p(d_info), C.c_void_p(stream)))

@@ -15,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "jac_lsq.hip"
 #include "jac_products.hip"
 #include "launch.h"
 
@@ -135,6 +136,17 @@ struct twr_jac_ops {   // twr::PlanJacOps's tables and work lists on the device,
   DevList<twr::JacFoldWork> fold;
   DevPtr<double> slab;
   int lds_x = 0, distinct_patterns = 0;
+  int64_t resident = 0;
+};
+
+struct twr_jac_lsq {   // twr::PlanJacLsq's work records and bound tables on the device, and the solver's workspace
+  twr_jac_ops* ops = nullptr;   // borrowed
+  int device = 0, n_problems = 0;
+  DevPtr<void> bounds;
+  DevList<twr::JacLsqWork> work;
+  DevPtr<double> ws;
+  twr::LsqBuffers buf{};
+  int lds_x = 0;
   int64_t resident = 0;
 };
 
@@ -1162,6 +1174,107 @@ int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, doubl
                                       static_cast<hipStream_t>(hip_stream));
   if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
   return TWR_OK;
+}
+
+int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem,
+                       int n_problems, twr_jac_lsq** out) {
+  if (!ops || !structs || !struct_of_problem || !out || n_structs < 1 || n_problems < 1) return fail(TWR_ERR_INVALID, "bad arguments");
+  twr::JacLsqPlan plan;
+  try {   // argument errors
+    std::vector<const twr::Structure*> sp(n_structs);
+    for (int i = 0; i < n_structs; ++i) {
+      if (!structs[i]) throw std::runtime_error("null structure");
+      sp[i] = &structs[i]->s;
+    }
+    plan = twr::PlanJacLsq(sp, std::vector<int32_t>(struct_of_problem, struct_of_problem + n_problems));
+    if (n_problems != ops->n_problems || plan.x_off != ops->x_off || plan.g_off != ops->g_off)
+      throw std::runtime_error("the structures are not the ones the products handle was created with");
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+  std::unique_ptr<twr_jac_lsq> h(new twr_jac_lsq());
+  try {   // device errors
+    DeviceScope on(ops->device);
+    TWR_HIP(on.status);
+    h->ops = ops;
+    h->device = ops->device;
+    h->n_problems = n_problems;
+    const size_t bb = std::max<size_t>(16, plan.bounds.size());
+    h->bounds = dev_alloc<void>(bb);
+    if (!plan.bounds.empty()) TWR_HIP(hipMemcpy(h->bounds.get(), plan.bounds.data(), plan.bounds.size(), hipMemcpyHostToDevice));
+    plan.Place(reinterpret_cast<uint64_t>(h->bounds.get()));
+    h->work = upload(plan.work);
+    h->ws = dev_alloc<double>(sizeof(double) * (size_t)plan.ws_doubles);
+    double* w = h->ws.get();
+    h->buf = {w + plan.ws_p, w + plan.ws_z, w + plan.ws_q, w + plan.ws_r, w + plan.ws_t, w + plan.ws_rec};
+    h->lds_x = plan.lds_x;
+    h->resident = (int64_t)bb + (int64_t)(plan.work.size() * sizeof(twr::JacLsqWork)) + 8 * plan.ws_doubles;
+    *out = h.release();
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    twr_jac_lsq_destroy(h.release());
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+void twr_jac_lsq_destroy(twr_jac_lsq* lsq) {
+  if (!lsq) return;
+  DeviceScope on(lsq->device);
+  delete lsq;
+}
+
+int twr_jac_lsq_bytes(const twr_jac_lsq* lsq, int64_t* resident) {
+  if (!lsq) return fail(TWR_ERR_INVALID, "null handle");
+  if (resident) *resident = lsq->resident;
+  return TWR_OK;
+}
+
+namespace {
+bool misaligned(std::initializer_list<const void*> ptrs) {   // NULL (an optional buffer left out) counts as aligned
+  uintptr_t bits = 0;
+  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
+  return (bits & 7) != 0;
+}
+int lsq_launched(hipError_t e) {
+  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return TWR_OK;
+}
+}  // namespace
+
+int twr_jac_dot(twr_jac_lsq* lsq, int space, const double* d_a, const double* d_b, double* d_out, void* hip_stream) {
+  if (!lsq || !d_a || !d_b || !d_out) return fail(TWR_ERR_INVALID, "null argument");
+  if (space != 0 && space != 1) return fail(TWR_ERR_INVALID, "space is 0 (the x layout) or 1 (the g layout)");
+  if (misaligned({d_a, d_b, d_out})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return lsq_launched(twr::launch_lsq_dot(lsq->work.d.get(), lsq->work.n, space, d_a, d_b, d_out, static_cast<hipStream_t>(hip_stream)));
+}
+
+int twr_jac_violation(twr_jac_lsq* lsq, const double* d_g, const double* d_w, double* d_r, double* d_w_active, double* d_merit,
+                      void* hip_stream) {
+  if (!lsq || !d_g || !d_r) return fail(TWR_ERR_INVALID, "null argument");
+  if (misaligned({d_g, d_w, d_r, d_w_active, d_merit})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return lsq_launched(twr::launch_lsq_violation(lsq->work.d.get(), lsq->work.n, d_g, d_w, d_r, d_w_active, d_merit,
+                                                static_cast<hipStream_t>(hip_stream)));
+}
+
+int twr_jac_lsq_solve(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu, int iters,
+                      double tol, double* d_d, double* d_info, void* hip_stream) {
+  if (!lsq || !d_jac || !d_b || !d_mu || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
+  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
+  if (misaligned({d_jac, d_b, d_w, d_mu, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  const twr_jac_ops* ops = lsq->ops;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  return lsq_launched(twr::launch_lsq_solve(
+      lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, d_b, d_w, d_mu, iters, tol, d_d, d_info, stream,
+      [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
+      [&](const double* w, double* z) {
+        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
+      }));
 }
 
 }  // extern "C"

@@ -1,0 +1,307 @@
+// The damped weighted least-squares step with a batch's Jacobian values, per problem p (twr_jac_lsq_solve, include/towr_amd.h):
+//   d_p = argmin_d  sum_r w_r (J_p d - b_p)_r^2 + mu_p |d|^2      <=>   (J_p^T W_p J_p + mu_p I) d_p = J_p^T W_p b_p
+// by CGLS on top of the two products of jac_products.hip (used as they are), and what feeds it: the bound-violation residual
+// (twr_jac_violation) and per-problem dot products (twr_jac_dot).  One workgroup of kLsqThreads lanes per problem in every kernel
+// here; the work records, the workspace and the bound tables are planned on the host (twr::PlanJacLsq, structure.h).
+//   lsq_start_kernel:  d = 0, r = b, t = w o r                                   (then z = J^T t by the product kernels)
+//   lsq_dir_kernel:    s = z - mu d, gamma' = s^T s; first: gamma0 = gamma', p = s; later: beta = gamma' / gamma, convergence
+//                      test, p = s + beta p; writes the problem's info                (then q = J p)
+//   lsq_step_kernel:   delta = q^T (w o q) + mu p^T p, alpha = gamma / delta, d += alpha p, r -= alpha q, t = w o r
+// Every scalar (alpha, beta, gamma, mu, the state) stays on the device: the launch sequence depends on `iters` alone.  A problem
+// that has stopped (converged, or bad input) is skipped by its workgroup in every later kernel: its d, r, p no longer change.
+// No atomics: every sum is taken by lsq_sum in an order fixed by the vector's length (structure.h), so a problem's outputs have
+// the same bits wherever it sits in whatever batch.  Every index comes from the work record, never from the data.
+// Included by capi.cc (compiled as HIP for gfx950).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "jac_products.hip"
+#include "structure.h"
+
+namespace twr {
+
+// The pair (a[i], a[i + 1]) of a vector of `len` doubles, i even: one 16-byte load where the vector starts on a 16-byte boundary
+// (al; offsets in the batch layout are only 8-byte aligned in general), else two 8-byte loads.  The element behind the end reads
+// as 0 and is never used in a sum or stored.
+__device__ inline bool lsq_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+__device__ inline double2 lsq_ld(const double* __restrict__ a, int i, int len, bool al) {
+  if (i + 1 < len) {
+    if (al) return *reinterpret_cast<const double2*>(a + i);
+    return make_double2(a[i], a[i + 1]);
+  }
+  return make_double2(a[i], 0.0);
+}
+__device__ inline void lsq_st(double* __restrict__ a, int i, int len, bool al, double2 v) {
+  if (i + 1 < len) {
+    if (al) *reinterpret_cast<double2*>(a + i) = v;
+    else a[i] = v.x, a[i + 1] = v.y;
+  } else {
+    a[i] = v.x;
+  }
+}
+
+// Sums of K values over the workgroup, the same bits in every lane: a butterfly over the wave (both partners of a step add the
+// same two numbers), lane 0 of every wave to LDS, then the waves' partials in wave order.  red: K * (kLsqThreads / 64) doubles.
+template <int K>
+__device__ inline void lsq_sum(double (&v)[K], double* red) {
+  constexpr int kWaves = kLsqThreads / 64;
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int s = 32; s >= 1; s >>= 1) v[k] += __shfl_xor(v[k], s, 64);
+  const int wave = threadIdx.x / 64;
+  if ((threadIdx.x & 63) == 0)
+#pragma unroll
+    for (int k = 0; k < K; ++k) red[wave * K + k] = v[k];
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    double acc = red[k];
+#pragma unroll
+    for (int w = 1; w < kWaves; ++w) acc += red[w * K + k];
+    v[k] = acc;
+  }
+  __syncthreads();   // red may be written again
+}
+
+// out[p] = sum_i a_i b_i over the x layout (space 0) or the g layout
+__global__ __launch_bounds__(kLsqThreads) void lsq_dot_kernel(const JacLsqWork* __restrict__ work, int space,
+                                                              const double* __restrict__ a, const double* __restrict__ b,
+                                                              double* __restrict__ out) {
+  __shared__ double red[kLsqThreads / 64];
+  const JacLsqWork W = work[blockIdx.x];
+  const int len = space == 0 ? W.n : W.m;
+  const int64_t off = space == 0 ? W.x_off : W.g_off;
+  const double* ap = a + off;
+  const double* bp = b + off;
+  const bool aa = lsq_aligned(ap), ab = lsq_aligned(bp);
+  double acc[1] = {0.0};
+  for (int i = 2 * (int)threadIdx.x; i < len; i += 2 * kLsqThreads) {
+    const double2 x = lsq_ld(ap, i, len, aa), y = lsq_ld(bp, i, len, ab);
+    acc[0] += x.x * y.x;
+    if (i + 1 < len) acc[0] += x.y * y.y;
+  }
+  lsq_sum(acc, red);
+  if (threadIdx.x == 0) out[blockIdx.x] = acc[0];
+}
+
+// r = g - min(max(g, lower), upper), a NaN g staying NaN; w_active = w [r != 0]; merit = 1/2 sum_i w_i r_i^2 (w NULL: 1)
+__device__ inline double lsq_viol(double g, double lo, double hi) {
+  double c = g < lo ? lo : g;
+  c = c > hi ? hi : c;
+  return g - c;
+}
+__global__ __launch_bounds__(kLsqThreads) void lsq_violation_kernel(const JacLsqWork* __restrict__ work, const double* __restrict__ g,
+                                                                    const double* __restrict__ w, double* __restrict__ r,
+                                                                    double* __restrict__ w_active, double* __restrict__ merit) {
+  __shared__ double red[kLsqThreads / 64];
+  const JacLsqWork W = work[blockIdx.x];
+  const int m = W.m;
+  const double* gp = g + W.g_off;
+  const double* wp = w ? w + W.g_off : nullptr;
+  double* rp = r + W.g_off;
+  double* ap = w_active ? w_active + W.g_off : nullptr;
+  const double* lo = jac_table<double>(W.lower);
+  const double* hi = jac_table<double>(W.upper);
+  const bool ag = lsq_aligned(gp), aw = lsq_aligned(wp), ar = lsq_aligned(rp), aa = lsq_aligned(ap), al = lsq_aligned(lo),
+             ah = lsq_aligned(hi);
+  double acc[1] = {0.0};
+  for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
+    const double2 gv = lsq_ld(gp, i, m, ag), l = lsq_ld(lo, i, m, al), h = lsq_ld(hi, i, m, ah);
+    const double2 wv = wp ? lsq_ld(wp, i, m, aw) : make_double2(1.0, 1.0);
+    const double2 rv = make_double2(lsq_viol(gv.x, l.x, h.x), lsq_viol(gv.y, l.y, h.y));
+    lsq_st(rp, i, m, ar, rv);
+    if (ap) lsq_st(ap, i, m, aa, make_double2(wv.x * (rv.x != 0.0 ? 1.0 : 0.0), wv.y * (rv.y != 0.0 ? 1.0 : 0.0)));
+    acc[0] += wv.x * (rv.x * rv.x);
+    if (i + 1 < m) acc[0] += wv.y * (rv.y * rv.y);
+  }
+  if (!merit) return;
+  lsq_sum(acc, red);
+  if (threadIdx.x == 0) merit[blockIdx.x] = 0.5 * acc[0];
+}
+
+// d = 0, r = b, t = w o r (w NULL: t = r), and the problem's state: running
+__global__ __launch_bounds__(kLsqThreads) void lsq_start_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                                const double* __restrict__ b, const double* __restrict__ w,
+                                                                double* __restrict__ d, double* __restrict__ r, double* __restrict__ t) {
+  const JacLsqWork W = work[blockIdx.x];
+  double* dp = d + W.x_off;
+  const bool ad = lsq_aligned(dp);
+  for (int i = 2 * (int)threadIdx.x; i < W.n; i += 2 * kLsqThreads) lsq_st(dp, i, W.n, ad, make_double2(0.0, 0.0));
+  const double* bp = b + W.g_off;
+  const double* wp = w ? w + W.g_off : nullptr;
+  double* rp = r + W.g_off;
+  double* tp = t + W.g_off;
+  const bool ab = lsq_aligned(bp), aw = lsq_aligned(wp), ar = lsq_aligned(rp), at = lsq_aligned(tp);
+  for (int i = 2 * (int)threadIdx.x; i < W.m; i += 2 * kLsqThreads) {
+    const double2 bv = lsq_ld(bp, i, W.m, ab);
+    const double2 wv = wp ? lsq_ld(wp, i, W.m, aw) : make_double2(1.0, 1.0);
+    lsq_st(rp, i, W.m, ar, bv);
+    lsq_st(tp, i, W.m, at, wp ? make_double2(wv.x * bv.x, wv.y * bv.y) : bv);
+  }
+  if (threadIdx.x == 0) rec[(int64_t)kLsqRec * blockIdx.x + kLsqState] = kLsqRunning;
+}
+
+__device__ inline bool lsq_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and Inf
+
+// After q = J p.  A problem that is running: delta, alpha, the three updates and the next J^T's input.
+__global__ __launch_bounds__(kLsqThreads) void lsq_step_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                               const double* __restrict__ mu, const double* __restrict__ q,
+                                                               const double* __restrict__ w, const double* __restrict__ p,
+                                                               double* __restrict__ d, double* __restrict__ r, double* __restrict__ t) {
+  __shared__ double red[2 * (kLsqThreads / 64)];
+  double* rc = rec + (int64_t)kLsqRec * blockIdx.x;
+  if (rc[kLsqState] != kLsqRunning) return;   // the whole workgroup: every lane reads the same word, written by an earlier launch
+  const double gamma = rc[kLsqGamma], m_u = mu[blockIdx.x];
+  const JacLsqWork W = work[blockIdx.x];
+  const int n = W.n, m = W.m;
+  const double* qp = q + W.g_off;
+  const double* wp = w ? w + W.g_off : nullptr;
+  const double* pp = p + W.x_off;
+  double* dp = d + W.x_off;
+  double* rp = r + W.g_off;
+  double* tp = t + W.g_off;
+  const bool aq = lsq_aligned(qp), aw = lsq_aligned(wp), ap = lsq_aligned(pp), ad = lsq_aligned(dp), ar = lsq_aligned(rp),
+             at = lsq_aligned(tp);
+  double acc[2] = {0.0, 0.0};   // q^T (w o q), p^T p
+  for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
+    const double2 qv = lsq_ld(qp, i, m, aq);
+    const double2 wv = wp ? lsq_ld(wp, i, m, aw) : make_double2(1.0, 1.0);
+    acc[0] += qv.x * (wv.x * qv.x);
+    if (i + 1 < m) acc[0] += qv.y * (wv.y * qv.y);
+  }
+  for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+    const double2 pv = lsq_ld(pp, i, n, ap);
+    acc[1] += pv.x * pv.x;
+    if (i + 1 < n) acc[1] += pv.y * pv.y;
+  }
+  lsq_sum(acc, red);
+  const double delta = acc[0] + m_u * acc[1];
+  if (!(delta > 0.0) || !lsq_finite(delta)) {   // NaN, Inf, or no curvature along p: alpha would not be a number
+    if (threadIdx.x == 0) rc[kLsqState] = 2.0;
+    return;
+  }
+  const double alpha = gamma / delta;
+  for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+    const double2 pv = lsq_ld(pp, i, n, ap), dv = lsq_ld(dp, i, n, ad);
+    lsq_st(dp, i, n, ad, make_double2(fma(alpha, pv.x, dv.x), fma(alpha, pv.y, dv.y)));
+  }
+  for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
+    const double2 qv = lsq_ld(qp, i, m, aq), rv = lsq_ld(rp, i, m, ar);
+    const double2 rn = make_double2(fma(-alpha, qv.x, rv.x), fma(-alpha, qv.y, rv.y));
+    lsq_st(rp, i, m, ar, rn);
+    if (wp) {
+      const double2 wv = lsq_ld(wp, i, m, aw);
+      lsq_st(tp, i, m, at, make_double2(wv.x * rn.x, wv.y * rn.y));
+    } else {
+      lsq_st(tp, i, m, at, rn);
+    }
+  }
+  if (threadIdx.x == 0) rc[kLsqIters] += 1.0;
+}
+
+// After z = J^T t.  s = z - mu d (kept in LDS when n <= lds_x, else formed again from memory by the same expression), gamma',
+// and the new direction.  first: the start of a solve (d = 0, so s = z), which also checks mu and sets gamma0.
+__global__ __launch_bounds__(kLsqThreads) void lsq_dir_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                              const double* __restrict__ mu, const double* __restrict__ z,
+                                                              const double* __restrict__ d, double* __restrict__ p,
+                                                              double* __restrict__ info, double tol2, int first, int lds_x) {
+  extern __shared__ double lsq_s[];   // lds_x doubles
+  __shared__ double red[kLsqThreads / 64];
+  double* rc = rec + (int64_t)kLsqRec * blockIdx.x;
+  if (!first && rc[kLsqState] != kLsqRunning) {   // stopped: only the status is written again (the step kernel may have set it)
+    if (threadIdx.x == 0) info[4 * (int64_t)blockIdx.x + 3] = rc[kLsqState];
+    return;
+  }
+  const double m_u = mu[blockIdx.x], gamma = rc[kLsqGamma], gamma0 = rc[kLsqGamma0], iters = rc[kLsqIters];
+  const JacLsqWork W = work[blockIdx.x];
+  const int n = W.n;
+  const double* zp = z + W.x_off;
+  const double* dp = d + W.x_off;
+  double* pp = p + W.x_off;
+  const bool az = lsq_aligned(zp), ad = lsq_aligned(dp), ap = lsq_aligned(pp), staged = n <= lds_x;
+  const auto s_at = [&](int i) {
+    const double2 zv = lsq_ld(zp, i, n, az);
+    if (first) return zv;
+    const double2 dv = lsq_ld(dp, i, n, ad);
+    return make_double2(fma(-m_u, dv.x, zv.x), fma(-m_u, dv.y, zv.y));
+  };
+  double acc[1] = {0.0};
+  for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+    const double2 sv = s_at(i);
+    if (staged) {   // the lane reads back what it wrote: no barrier
+      lsq_s[i] = sv.x;
+      if (i + 1 < n) lsq_s[i + 1] = sv.y;
+    }
+    acc[0] += sv.x * sv.x;
+    if (i + 1 < n) acc[0] += sv.y * sv.y;
+  }
+  lsq_sum(acc, red);
+  const double gn = acc[0];
+  double state = kLsqRunning, beta = 0.0, g0 = gamma0;
+  if (first) {
+    g0 = gn;
+    if (!(m_u >= 0.0) || !lsq_finite(m_u) || !lsq_finite(gn)) state = 2.0;
+    else if (gn <= tol2 * gn) state = 0.0;   // |s0| = 0 (b = 0, no rows), or tol >= 1
+  } else {
+    if (!lsq_finite(gn)) state = 2.0;
+    else if (gn <= tol2 * g0) state = 0.0;
+    else beta = gn / gamma;
+  }
+  if (state == kLsqRunning)
+    for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+      const double2 sv = staged ? make_double2(lsq_s[i], i + 1 < n ? lsq_s[i + 1] : 0.0) : s_at(i);
+      if (first) {
+        lsq_st(pp, i, n, ap, sv);
+      } else {
+        const double2 pv = lsq_ld(pp, i, n, ap);
+        lsq_st(pp, i, n, ap, make_double2(fma(beta, pv.x, sv.x), fma(beta, pv.y, sv.y)));
+      }
+    }
+  if (threadIdx.x == 0) {
+    rc[kLsqGamma] = gn;
+    rc[kLsqState] = state;
+    if (first) rc[kLsqGamma0] = g0, rc[kLsqIters] = 0.0;
+    double* o = info + 4 * (int64_t)blockIdx.x;
+    o[0] = first ? 0.0 : iters;
+    o[1] = g0 == 0.0 ? 0.0 : sqrt(gn / g0);
+    o[2] = sqrt(g0);
+    o[3] = state == kLsqRunning ? 1.0 : state;   // still running when the last launch has gone by: the iteration cap
+  }
+}
+
+struct LsqBuffers {   // the handle's workspace (JacLsqPlan's segments)
+  double *p, *z, *q, *r, *t, *rec;
+};
+
+inline hipError_t launch_lsq_dot(const JacLsqWork* work, int n, int space, const double* a, const double* b, double* out,
+                                 hipStream_t stream) {
+  return jac_launch(lsq_dot_kernel, n, kLsqThreads, 0, stream, work, space, a, b, out);
+}
+
+inline hipError_t launch_lsq_violation(const JacLsqWork* work, int n, const double* g, const double* w, double* r, double* w_active,
+                                       double* merit, hipStream_t stream) {
+  return jac_launch(lsq_violation_kernel, n, kLsqThreads, 0, stream, work, g, w, r, w_active, merit);
+}
+
+// The whole solve: 3 launches to start, 5 per iteration (J p, step, J^T t and its fold, direction), none of them conditional.
+template <class Mul, class TMul>
+inline hipError_t launch_lsq_solve(const JacLsqWork* work, int n, int lds_x, const LsqBuffers& ws, const double* b, const double* w,
+                                   const double* mu, int iters, double tol, double* d, double* info, hipStream_t stream, Mul mul,
+                                   TMul tmul) {
+  const size_t lds = sizeof(double) * (size_t)lds_x;
+  const double tol2 = tol * tol;
+  hipError_t e = jac_launch(lsq_start_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, ws.r, ws.t);
+  if (e == hipSuccess) e = tmul(ws.t, ws.z);
+  if (e == hipSuccess) e = jac_launch(lsq_dir_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, d, ws.p, info, tol2, 1, lds_x);
+  for (int k = 0; k < iters && e == hipSuccess; ++k) {
+    e = mul(ws.p, ws.q);
+    if (e == hipSuccess) e = jac_launch(lsq_step_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.q, w, ws.p, d, ws.r, ws.t);
+    if (e == hipSuccess) e = tmul(ws.t, ws.z);
+    if (e == hipSuccess)
+      e = jac_launch(lsq_dir_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, d, ws.p, info, tol2, 0, lds_x);
+  }
+  return e;
+}
+
+}  // namespace twr

@@ -2488,4 +2488,65 @@ JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::v
   return J;
 }
 
+void JacLsqPlan::Place(uint64_t base) {
+  for (auto& w : work) w.lower += base, w.upper += base;
+}
+
+JacLsqPlan PlanJacLsq(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem) {
+  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
+  JacLsqPlan L;
+  struct Table {
+    const Structure* first;
+    uint64_t lower, upper;
+  };
+  std::vector<Table> tabs;
+  std::unordered_map<uint64_t, std::vector<int>> by_hash;
+  L.bounds_of_struct.resize(n_structs);
+  for (int i = 0; i < n_structs; ++i) {
+    const Structure& S = *structs[i];
+    if ((int)S.lower.size() != S.n_rows || (int)S.upper.size() != S.n_rows) throw std::runtime_error("bounds do not match the rows");
+    uint64_t h = HashWords(1469598103934665603ull ^ (uint64_t)S.n_rows, S.lower.data(), S.lower.size() * sizeof(double));
+    h = HashWords(h, S.upper.data(), S.upper.size() * sizeof(double));
+    std::vector<int>& bucket = by_hash[h];
+    const size_t bytes = (size_t)S.n_rows * sizeof(double);
+    int tid = -1;
+    for (int q : bucket) {   // byte-identical, not ==: -0.0 and 0.0 are different tables, NaN bounds equal themselves
+      const Structure& F = *tabs[q].first;
+      if (F.n_rows == S.n_rows && (bytes == 0 || (std::memcmp(F.lower.data(), S.lower.data(), bytes) == 0 &&
+                                                  std::memcmp(F.upper.data(), S.upper.data(), bytes) == 0)))
+        tid = q;
+    }
+    if (tid < 0) {
+      tid = (int)tabs.size();
+      bucket.push_back(tid);
+      const uint64_t lo = AppendTable(L.bounds, S.lower.data(), S.lower.size());
+      tabs.push_back({&S, lo, AppendTable(L.bounds, S.upper.data(), S.upper.size())});
+    }
+    L.bounds_of_struct[i] = tid;
+  }
+  L.distinct_bounds = (int)tabs.size();
+  L.x_off.assign(n_problems + 1, 0);
+  L.g_off.assign(n_problems + 1, 0);
+  for (int p = 0; p < n_problems; ++p) {
+    const int si = struct_of_problem[p];
+    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
+    const Structure& S = *structs[si];
+    const Table& T = tabs[L.bounds_of_struct[si]];
+    L.work.push_back({L.x_off[p], L.g_off[p], T.lower, T.upper, S.n_vars, S.n_rows});
+    L.x_off[p + 1] = L.x_off[p] + S.n_vars;
+    L.g_off[p + 1] = L.g_off[p] + S.n_rows;
+    if (S.n_vars <= kJacLdsX) L.lds_x = std::max(L.lds_x, S.n_vars);
+  }
+  const auto even = [](int64_t v) { return (v + 1) / 2 * 2; };
+  const int64_t X = even(L.x_off[n_problems]), G = even(L.g_off[n_problems]);
+  L.ws_p = 0;
+  L.ws_z = L.ws_p + X;
+  L.ws_q = L.ws_z + X;
+  L.ws_r = L.ws_q + G;
+  L.ws_t = L.ws_r + G;
+  L.ws_rec = L.ws_t + G;
+  L.ws_doubles = L.ws_rec + (int64_t)kLsqRec * n_problems;
+  return L;
+}
+
 }  // namespace twr

@@ -320,6 +320,38 @@ struct JacOpsPlan {
 // (structs, struct_of_problem) as for twr_batch_create.  Byte-identical patterns (n, m, row_ptr, col_idx) share one set of tables.
 JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
 
+// The damped weighted least-squares step with a batch's Jacobian (twr_jac_lsq_solve, twr_jac_violation, twr_jac_dot; jac_lsq.hip),
+// planned on the host (no HIP): one work record per problem, the solver's workspace and the per-row bound tables.
+//   workspace (doubles, every segment starts on a 16-byte boundary): p and z in the x layout, q, r and t in the g layout, then
+//   kLsqRec doubles of scalars per problem.  A vector of problem p lives at segment + x_off[p] / g_off[p], as in the batch.
+//   bounds: per distinct (lower, upper) table lower[m] then upper[m], 16-byte aligned; structures whose tables are
+//   byte-identical share one copy.  These are the structures' own per-row bounds (Structure::lower / upper), any number of
+//   distinct pairs: nothing here reads PackBlob's compact score record.
+// Every sum of the kernels is taken by kLsqThreads lanes over aligned index pairs: lane t adds the elements of the pairs
+// {2j, 2j + 1}, j = t, t + kLsqThreads, ... in index order, then a fixed tree over the wave, then the waves' partials in wave
+// order: a function of the vector's length alone.
+constexpr int kLsqThreads = 256;
+constexpr int kLsqRec = 4;    // per-problem scalars: the slots below
+enum { kLsqGamma = 0, kLsqGamma0 = 1, kLsqIters = 2, kLsqState = 3 };   // state: kLsqRunning, or the status the problem stopped with
+constexpr double kLsqRunning = -1.0;
+struct JacLsqWork {     // one problem (device layout; lower / upper are byte offsets into JacLsqPlan::bounds until Place())
+  int64_t x_off, g_off;
+  uint64_t lower, upper;           // double[m] each
+  int32_t n, m;
+};
+struct JacLsqPlan {
+  std::vector<int64_t> x_off, g_off;          // n_problems + 1: the layout of PlanBatch / PlanJacOps for the same arguments
+  std::vector<JacLsqWork> work;               // problem by problem
+  std::vector<char> bounds;                   // every distinct bound table, once
+  std::vector<int32_t> bounds_of_struct;      // the distinct table every structure reads
+  int distinct_bounds = 0;
+  int64_t ws_p = 0, ws_z = 0, ws_q = 0, ws_r = 0, ws_t = 0, ws_rec = 0;   // segment starts (doubles)
+  int64_t ws_doubles = 0;                     // the whole workspace
+  int lds_x = 0;                              // largest n <= kJacLdsX of the batch (the s the direction kernel keeps in LDS)
+  void Place(uint64_t base);                  // bound offsets -> device addresses (base: where `bounds` lives)
+};
+JacLsqPlan PlanJacLsq(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
+
 // fpowr GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53): samples while t <= t_total + 1e-5, t accumulated
 int SampleCount(double t_total, double dt);
 void GaitCombo(int n_ee, int combo, double t_total, double swing_scale, twr_schedule* out);
