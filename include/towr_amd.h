@@ -436,6 +436,14 @@ int twr_jac_ops_layout(const twr_jac_ops* ops, int64_t* x_off, int64_t* g_off, i
 int twr_jac_ops_bytes(const twr_jac_ops* ops, int64_t* resident, int32_t* distinct_patterns);
 int twr_jac_mul(twr_jac_ops* ops, const double* d_jac, const double* d_v, double* d_y, void* hip_stream);
 int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_z, void* hip_stream);
+/* Weighted squared column norms: d_out[x_off[p] + k] = sum_r w[g_off[p] + r] J_p[r][k]^2 (d_w NULL: unit weights) -- what
+ * Marquardt's scaled damping (twr_jac_col_scale below), a Jacobi preconditioner and Ipopt-style variable scaling need.  It runs
+ * over J^T w's work list, block maps, slab and fold, the values squared as they are staged, so everything said of twr_jac_tmul
+ * holds word for word: the order of every sum is a function of the pattern alone (same bits wherever the problem sits, on every
+ * call, stream and device), a column without entries gets an exact 0, a NaN / Inf stays in its problem, capturable, ONE call
+ * per handle in flight (the slab), the same NULL / alignment / device-scope / sticky-error rules.  With w >= 0 every term is
+ * non-negative: the result is 0 exactly when the column has no entry with w_r J_rk^2 != 0. */
+int twr_jac_col_sqnorms(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_out, void* hip_stream);
 /* Host introspection: the CSC view of the CSR pattern -- col_ptr[n_vars + 1], and per entry row_idx[nnz] (ascending within a
  * column) and csr_pos[nnz], its position in the CSR value array (CSC values = csr_values[csr_pos]).  Any pointer may be NULL.
  * TWR_ERR_INVALID if a row's column indices do not ascend strictly (they always do for the patterns the factory builds; the
@@ -474,13 +482,36 @@ typedef struct twr_jac_lsq twr_jac_lsq;
 int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem,
                        int n_problems, twr_jac_lsq** out);
 void twr_jac_lsq_destroy(twr_jac_lsq* lsq);
-/* resident: device bytes the handle holds (bound tables, work records, workspace) */
+/* resident: device bytes the handle holds (bound tables, work records, workspace; the scaled solve's once reserved) */
 int twr_jac_lsq_bytes(const twr_jac_lsq* lsq, int64_t* resident);
 int twr_jac_dot(twr_jac_lsq* lsq, int space, const double* d_a, const double* d_b, double* d_out, void* hip_stream);
 int twr_jac_violation(twr_jac_lsq* lsq, const double* d_g, const double* d_w, double* d_r, double* d_w_active, double* d_merit,
                       void* hip_stream);
 int twr_jac_lsq_solve(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu, int iters,
                       double tol, double* d_d, double* d_info, void* hip_stream);
+/* Marquardt-scaled damping: towr's variables are metres, radians, m/s and newtons in one vector and the weighted column norms
+ * of its Jacobian span nine orders of magnitude, so mu I damps some variables not at all and freezes others.  With
+ * C = diag(c), c_k = 1 / (column norm k), the step
+ *   d_p = argmin_d  sum_r w_r (J_p d - b_p)_r^2 + mu_p sum_k (d_k / c_k)^2    <=>   (J^T W J + mu C^-2) d = J^T W b
+ * does not depend on the units of x.  Same rules as the calls above (stream order, capture, one call per handle in flight,
+ * bits independent of the batch, containment, NULL / alignment checks).
+ *   twr_jac_col_scale:        d_scale (x layout) from d_colsq (twr_jac_col_sqnorms): a_k = colsq_k, or, with d_colsq_max given
+ *                             (in / out, x layout: the running maximum over the steps of an LM loop, start it at 0),
+ *                             a_k = colsq_max_k = max(colsq_max_k, colsq_k); top = max_k a_k;
+ *                             c_k = 1 / sqrt(max(a_k, rel_floor top)); c_k = 1 for every k of a problem with top == 0.  A NaN a_k
+ *                             gives a NaN c_k for that k alone.  rel_floor outside (0, 1] is TWR_ERR_INVALID.
+ *   twr_jac_lsq_solve_scaled: the iteration of twr_jac_lsq_solve on J C in e = d / c: s = c o J^T(w o r) - mu e, p = s + beta p,
+ *                             q = J (c o p), delta = q^T(w o q) + mu p^T p, e += alpha p, d = c o e, r -= alpha q.  Stopping rule,
+ *                             d_info, status codes, freezing of finished problems and the launch sequence as twr_jac_lsq_solve,
+ *                             |s| and |s0| being the scaled quantities; with c = 1 it returns the bits of twr_jac_lsq_solve.  A c_k
+ *                             that is not a positive finite number is bad input: status 2, d = 0.
+ *   twr_jac_lsq_reserve_scaled: allocates the scaled solve's two extra vectors (x layout), once; twr_jac_lsq_bytes counts them
+ *                             from then on.  twr_jac_lsq_solve_scaled calls it itself when it has not been called: that one call
+ *                             allocates and can NOT be captured in a hipGraph -- reserve before capturing. */
+int twr_jac_lsq_reserve_scaled(twr_jac_lsq* lsq);
+int twr_jac_col_scale(twr_jac_lsq* lsq, const double* d_colsq, double* d_colsq_max, double rel_floor, double* d_scale, void* hip_stream);
+int twr_jac_lsq_solve_scaled(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
+                             const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream);
 
 /* Tuning knobs.  The DEFAULT build reads nothing from the environment: the values below are compiled in.  A build with
  * -DTWR_TUNING_KNOBS (make -C towr_amd/csrc TUNING=1) reads them, for A/B measurements (scripts/ab.py):

@@ -10,6 +10,12 @@ scripts/jac_products.py builds them; buffers as torch hands them out, HIP events
     its summed inf-norm scores before and after, and the device time per step split into evaluation and solve.
 mu starts at 1e-2 lambda_max(J^T W J) per problem, lambda_max from --power-iters power iterations with the two products and
 twr_jac_dot, all on the device.
+--damping identity (default: the output above, unchanged) | marquardt | both.  marquardt damps with mu C^-2, C = diag(1 / weighted
+column norm): per LM step twr_jac_col_sqnorms (active-set weights) -> twr_jac_col_scale (running maximum, rel_floor 1e-12) ->
+twr_jac_lsq_solve_scaled, mu starting at 1e-2 lambda_max(C J^T W J C) (the same power iteration, c applied in torch).  It adds
+  * scaled: ms of twr_jac_col_sqnorms against twr_jac_tmul on the same buffers, of twr_jac_col_scale, and per iteration of the
+    scaled solve against the unscaled one;
+  * lm_marquardt: the lm block for the scaled damping, from the same x0.
 Usage (each GPU step under its own time limit):
   timeout -k 10 600 python scripts/jac_lsq.py --workload c3 && timeout -k 10 600 python scripts/jac_lsq.py --workload c5
 """
@@ -45,15 +51,19 @@ class Problem:
     def vec(self, n):
         return self.torch.zeros(n, dtype=self.torch.float64, device=self.dev)
 
-    def lambda_max(self, wa, iters):
-        """Per-problem power iteration on J^T W J: v <- J^T (w o (J v)) / |v|, lambda = v^T J^T W J v / v^T v."""
+    def lambda_max(self, wa, iters, c=None):
+        """Per-problem power iteration on J^T W J (c given: on C J^T W J C): v <- J^T (w o (J v)) / |v|,
+        lambda = v^T J^T W J v / v^T v."""
         torch = self.torch
         v = torch.from_numpy(np.random.default_rng(3).normal(size=self.X)).to(self.dev)
         y, z, vv, vz = self.vec(self.G), self.vec(self.X), self.vec(self.P), self.vec(self.P)
         for _ in range(iters):
-            self.ops.mul_device(self.jac.data_ptr(), v.data_ptr(), y.data_ptr(), self.st)
+            cv = v if c is None else c * v
+            self.ops.mul_device(self.jac.data_ptr(), cv.data_ptr(), y.data_ptr(), self.st)
             y.mul_(wa)
             self.ops.tmul_device(self.jac.data_ptr(), y.data_ptr(), z.data_ptr(), self.st)
+            if c is not None:
+                z.mul_(c)
             self.lsq.dot_device(self.lsq.X, v.data_ptr(), v.data_ptr(), vv.data_ptr(), self.st)
             self.lsq.dot_device(self.lsq.X, v.data_ptr(), z.data_ptr(), vz.data_ptr(), self.st)
             v = z / torch.sqrt(self.lsq_dot(z, z))[self.of_x].clamp_min(1e-300)
@@ -78,13 +88,115 @@ def timed(torch, f, steps, rounds):
     return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
 
 
+REL_FLOOR = 1e-12
+
+
+def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30):
+    """The LM loop from Q.x (left at the last accepted point).  damping "identity": mu I with the given mu; "marquardt": mu C^-2,
+    mu = 1e-2 lambda_max(C J^T W J C) at the start when None."""
+    st, lsq, ops, batch = Q.st, Q.lsq, Q.ops, Q.batch
+    g, r, b, wa, merit, d, info = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(Q.X), Q.vec(4 * Q.P)
+    g2, r2, merit2, scores = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(16 * Q.P)
+    scaled = damping == "marquardt"
+    if scaled:
+        colsq, colmax, c = Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X)
+        lsq.reserve_scaled()
+
+    def linearise():
+        batch.eval_device(Q.x.data_ptr(), g.data_ptr(), Q.jac.data_ptr(), ta.EVAL_BOTH, st)
+        lsq.violation_device(g.data_ptr(), r.data_ptr(), d_w_active=wa.data_ptr(), d_merit=merit.data_ptr(), stream=st)
+        torch.neg(r, out=b)
+        if scaled:
+            ops.col_sqnorms_device(Q.jac.data_ptr(), colsq.data_ptr(), d_w=wa.data_ptr(), stream=st)
+            lsq.col_scale_device(colsq.data_ptr(), c.data_ptr(), REL_FLOOR, d_colsq_max=colmax.data_ptr(), stream=st)
+
+    def score_sum():
+        batch.eval_scores_device(Q.x.data_ptr(), scores.data_ptr(), d_g=g2.data_ptr(), stream=st)
+        return float(scores.view(Q.P, 8, 2)[:, :, 0].sum())
+
+    linearise()
+    if mu is None:
+        mu = 1e-2 * Q.lambda_max(wa, power_iters, c if scaled else None)
+    else:
+        mu = mu.clone()
+    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(lm_steps)]
+    res = {"steps": lm_steps, "cg_iters": lm_cg_iters, "merit_before": float(merit.sum()), "scores_before": score_sum()}
+    merit_before = merit.clone()
+    accepted = Q.vec(lm_steps)
+    for k in range(lm_steps):   # nothing in here waits for the device
+        ev[k][0].record()
+        linearise()
+        ev[k][1].record()
+        if scaled:
+            lsq.solve_scaled_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), c.data_ptr(), d.data_ptr(), info.data_ptr(),
+                                    lm_cg_iters, 1e-8, d_w=wa.data_ptr(), stream=st)
+        else:
+            lsq.solve_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), lm_cg_iters, 1e-8,
+                             d_w=wa.data_ptr(), stream=st)
+        ev[k][2].record()
+        xt = Q.x + d
+        batch.eval_device(xt.data_ptr(), g2.data_ptr(), 0, ta.EVAL_VALUES, st)
+        lsq.violation_device(g2.data_ptr(), r2.data_ptr(), d_merit=merit2.data_ptr(), stream=st)
+        ok = merit2 < merit
+        Q.x = torch.where(ok[Q.of_x], xt, Q.x)
+        mu = torch.where(ok, mu / 3.0, mu * 10.0)
+        accepted[k] = ok.sum()
+        ev[k][3].record()
+    torch.cuda.synchronize()
+    batch.eval_device(Q.x.data_ptr(), g.data_ptr(), 0, ta.EVAL_VALUES, st)
+    lsq.violation_device(g.data_ptr(), r.data_ptr(), d_merit=merit.data_ptr(), stream=st)
+    torch.cuda.synchronize()
+    ms_eval = [e[0].elapsed_time(e[1]) + e[2].elapsed_time(e[3]) for e in ev]
+    ms_solve = [e[1].elapsed_time(e[2]) for e in ev]
+    res.update(merit_after=float(merit.sum()), scores_after=score_sum(), accepted_per_step=[int(v) for v in accepted.cpu()],
+               ms_eval_per_step=float(np.median(ms_eval)), ms_solve_per_step=float(np.median(ms_solve)),
+               viol_inf_after_min_median_max=[float(v) for v in np.quantile(
+                   scores.view(Q.P, 8, 2)[:, :, 0].max(dim=1).values.cpu().numpy(), [0, 0.5, 1])])
+    Q.merit_before, Q.merit_after = merit_before, merit.clone()   # per problem, for callers that compare dampings
+    return res
+
+
+def measure_scaled(torch, Q, b, wa, mu, a):
+    """twr_jac_col_sqnorms against twr_jac_tmul, and the scaled CGLS iteration against the unscaled one, on the same buffers
+    (J, b, wa of the starting point)."""
+    st, lsq, ops = Q.st, Q.lsq, Q.ops
+    colsq, c, z, d, info = Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(4 * Q.P)
+    lsq.reserve_scaled()
+    ops.col_sqnorms_device(Q.jac.data_ptr(), colsq.data_ptr(), d_w=wa.data_ptr(), stream=st)
+    lsq.col_scale_device(colsq.data_ptr(), c.data_ptr(), REL_FLOOR, stream=st)
+    calls = {"tmul": lambda: ops.tmul_device(Q.jac.data_ptr(), wa.data_ptr(), z.data_ptr(), st),
+             "col_sqnorms": lambda: ops.col_sqnorms_device(Q.jac.data_ptr(), colsq.data_ptr(), d_w=wa.data_ptr(), stream=st),
+             "col_scale": lambda: lsq.col_scale_device(colsq.data_ptr(), c.data_ptr(), REL_FLOOR, stream=st)}
+    for iters in (a.cg_iters, 0):
+        calls["solve%d" % iters] = lambda iters=iters: lsq.solve_device(
+            Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), iters, 0.0, d_w=wa.data_ptr(), stream=st)
+        calls["scaled%d" % iters] = lambda iters=iters: lsq.solve_scaled_device(
+            Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), c.data_ptr(), d.data_ptr(), info.data_ptr(), iters, 0.0, d_w=wa.data_ptr(),
+            stream=st)
+    for f in calls.values():
+        f()
+        f()
+    torch.cuda.synchronize()
+    t = {k: timed(torch, f, a.steps if k in ("tmul", "col_sqnorms", "col_scale") else 2, a.rounds) for k, f in calls.items()}
+    n = a.cg_iters
+    per = {k: (t["%s%d" % (k, n)][0] - t["%s0" % k][0]) / n for k in ("solve", "scaled")}
+    nb = 2 * 8 * (Q.X + Q.G + Q.J) + 8 * (8 * Q.X + 6 * Q.G)
+    cs = colsq.view(-1)
+    return {"ms_tmul": t["tmul"], "ms_col_sqnorms": t["col_sqnorms"], "col_sqnorms_to_tmul": t["col_sqnorms"][0] / t["tmul"][0],
+            "ms_col_scale": t["col_scale"], "cg_iters": n, "ms_solve": t["solve%d" % n], "ms_solve_scaled": t["scaled%d" % n],
+            "ms_per_iteration_without_start": per["solve"], "ms_per_scaled_iteration_without_start": per["scaled"],
+            "scaled_to_unscaled": per["scaled"] / per["solve"], "ratio_by_bytes": 1.0 + 8 * 4 * Q.X / nb,
+            "jac_lsq_bytes_with_scaled": lsq.bytes()["resident"],
+            "zero_columns": int((cs == 0).sum()), "col_norm_min_positive_max": [
+                float(cs[cs > 0].min().sqrt()) if bool((cs > 0).any()) else 0.0, float(cs.max().sqrt())]}
+
+
 def measure(torch, name, structs, order, x_h, a):
     Q = Problem(torch, structs, order, x_h)
     st, lsq, ops, batch = Q.st, Q.lsq, Q.ops, Q.batch
-    g, r, wa, merit, d, info = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(Q.X), Q.vec(4 * Q.P)
-    g2, r2, merit2, scores = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(16 * Q.P)
+    g, r, wa, d, info = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.X), Q.vec(4 * Q.P)
     batch.eval_device(Q.x.data_ptr(), g.data_ptr(), Q.jac.data_ptr(), ta.EVAL_BOTH, st)
-    lsq.violation_device(g.data_ptr(), r.data_ptr(), d_w_active=wa.data_ptr(), d_merit=merit.data_ptr(), stream=st)
+    lsq.violation_device(g.data_ptr(), r.data_ptr(), d_w_active=wa.data_ptr(), stream=st)
     b = -r
     lam = Q.lambda_max(wa, a.power_iters)
     mu = 1e-2 * lam
@@ -122,40 +234,15 @@ def measure(torch, name, structs, order, x_h, a):
                                    "status_counts": [int((it[:, 3] == s).sum()) for s in (0, 1, 2)]}
 
     # ---- Levenberg-Marquardt
-    def score_sum():
-        batch.eval_scores_device(Q.x.data_ptr(), scores.data_ptr(), d_g=g2.data_ptr(), stream=st)
-        return float(scores.view(Q.P, 8, 2)[:, :, 0].sum())
-
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(a.lm_steps)]
-    out["lm"] = {"steps": a.lm_steps, "cg_iters": a.lm_cg_iters, "merit_before": float(merit.sum()), "scores_before": score_sum()}
-    accepted = Q.vec(a.lm_steps)
-    for k in range(a.lm_steps):   # nothing in here waits for the device
-        ev[k][0].record()
-        batch.eval_device(Q.x.data_ptr(), g.data_ptr(), Q.jac.data_ptr(), ta.EVAL_BOTH, st)
-        lsq.violation_device(g.data_ptr(), r.data_ptr(), d_w_active=wa.data_ptr(), d_merit=merit.data_ptr(), stream=st)
-        torch.neg(r, out=b)
-        ev[k][1].record()
-        lsq.solve_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), a.lm_cg_iters, 1e-8, d_w=wa.data_ptr(),
-                         stream=st)
-        ev[k][2].record()
-        xt = Q.x + d
-        batch.eval_device(xt.data_ptr(), g2.data_ptr(), 0, ta.EVAL_VALUES, st)
-        lsq.violation_device(g2.data_ptr(), r2.data_ptr(), d_merit=merit2.data_ptr(), stream=st)
-        ok = merit2 < merit
-        Q.x = torch.where(ok[Q.of_x], xt, Q.x)
-        mu = torch.where(ok, mu / 3.0, mu * 10.0)
-        accepted[k] = ok.sum()
-        ev[k][3].record()
-    torch.cuda.synchronize()
-    batch.eval_device(Q.x.data_ptr(), g.data_ptr(), 0, ta.EVAL_VALUES, st)
-    lsq.violation_device(g.data_ptr(), r.data_ptr(), d_merit=merit.data_ptr(), stream=st)
-    torch.cuda.synchronize()
-    ms_eval = [e[0].elapsed_time(e[1]) + e[2].elapsed_time(e[3]) for e in ev]
-    ms_solve = [e[1].elapsed_time(e[2]) for e in ev]
-    out["lm"].update(merit_after=float(merit.sum()), scores_after=score_sum(), accepted_per_step=[int(v) for v in accepted.cpu()],
-                     ms_eval_per_step=float(np.median(ms_eval)), ms_solve_per_step=float(np.median(ms_solve)),
-                     viol_inf_after_min_median_max=[float(v) for v in np.quantile(
-                         scores.view(Q.P, 8, 2)[:, :, 0].max(dim=1).values.cpu().numpy(), [0, 0.5, 1])])
+    x0 = Q.x.clone()
+    if a.damping != "identity":
+        out["scaled"] = measure_scaled(torch, Q, b, wa, mu, a)   # J, b, wa still those of x0
+    out["lm"] = lm_loop(torch, Q, "identity", mu, a.lm_steps, a.lm_cg_iters)
+    if a.damping != "identity":
+        Q.x = x0
+        out["lm_marquardt"] = lm_loop(torch, Q, "marquardt", None, a.lm_steps, a.lm_cg_iters, a.power_iters)
+    if a.damping == "marquardt":
+        del out["lm"]
     return out
 
 
@@ -169,6 +256,7 @@ def main():
     ap.add_argument("--lm-cg-iters", type=int, default=60)
     ap.add_argument("--workload", choices=("c3", "c5", "both"), default="both")
     ap.add_argument("--c3-problems", type=int, default=8192)
+    ap.add_argument("--damping", choices=("identity", "marquardt", "both"), default="identity")
     a = ap.parse_args()
     import torch
 

@@ -1,0 +1,94 @@
+// Checks of the scaled solve's part of the least-squares plan (twr_jac_lsq_solve_scaled) on the host: the second workspace
+// twr::PlanJacLsq plans (ws2_*: e and c o p in the x layout), and that the first workspace keeps the formula it had before the
+// scaled solve existed.  Built and run by tests/test_jac_scaled_plan.py (g++ against towr_amd/csrc/structure.cc under ASan + UBSan,
+// no HIP).
+#include <algorithm>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+#include <utility>
+#include <vector>
+
+#include "../towr_amd/csrc/structure.h"
+
+static int fails = 0;
+#define CHECK(cond, ...)                  \
+  do {                                    \
+    if (!(cond)) {                        \
+      std::fprintf(stderr, __VA_ARGS__);  \
+      std::fprintf(stderr, "\n");         \
+      ++fails;                            \
+    }                                     \
+  } while (0)
+
+static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 200,
+                            double base_poly = 0.1) {
+  twr::Structure S;
+  twr::ModelPreset(robot, terrain, &S.model);
+  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
+  twr_params& p = S.params;
+  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
+  p.duration_base_poly = base_poly;
+  p.polys_per_swing = 2;
+  p.polys_per_stance_force = 3;
+  p.constraint_sets = sets;
+  p.reserved_ = 0;
+  p.dt_base_motion = 0.025;
+  p.base_z_init = -S.model.nominal_stance[0][2];
+  S.Build();
+  return S;
+}
+
+static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop) {
+  const twr::JacLsqPlan L = twr::PlanJacLsq(sp, sop), K = twr::PlanJacLsq(sp, sop);
+  CHECK(L.ws2_e == K.ws2_e && L.ws2_cp == K.ws2_cp && L.ws2_doubles == K.ws2_doubles && L.ws_doubles == K.ws_doubles,
+        "%s: planning twice differs", name);
+  const int n = (int)sop.size();
+  int64_t X = 0, G = 0;   // the layout, summed here from the structures
+  for (int p = 0; p < n; ++p) X += sp[sop[p]]->n_vars, G += sp[sop[p]]->n_rows;
+  CHECK(L.x_off[n] == X && L.g_off[n] == G, "%s: layout", name);
+  // the second allocation: two x-layout segments on 16-byte boundaries, disjoint, inside it, and no larger than two padded vectors
+  std::vector<std::pair<int64_t, int64_t>> seg = {{L.ws2_e, X}, {L.ws2_cp, X}};
+  for (const auto& s : seg)
+    CHECK(s.first >= 0 && s.first % 2 == 0 && s.first + s.second <= L.ws2_doubles, "%s: segment [%lld, +%lld) outside %lld or odd", name,
+          (long long)s.first, (long long)s.second, (long long)L.ws2_doubles);
+  std::sort(seg.begin(), seg.end());
+  CHECK(seg[0].first + seg[0].second <= seg[1].first, "%s: e and c o p overlap", name);
+  CHECK(L.ws2_doubles <= 2 * ((X + 1) / 2 * 2), "%s: second workspace of %lld doubles for two vectors of %lld", name,
+        (long long)L.ws2_doubles, (long long)X);
+  // the first allocation: the formula it had without the scaled solve (p, z; q, r, t; the records), every segment padded to even
+  const int64_t Xe = (X + 1) / 2 * 2, Ge = (G + 1) / 2 * 2;
+  CHECK(L.ws_p == 0 && L.ws_z == Xe && L.ws_q == 2 * Xe && L.ws_r == 2 * Xe + Ge && L.ws_t == 2 * Xe + 2 * Ge &&
+            L.ws_rec == 2 * Xe + 3 * Ge && L.ws_doubles == 2 * Xe + 3 * Ge + (int64_t)twr::kLsqRec * n,
+        "%s: the first workspace changed: %lld doubles", name, (long long)L.ws_doubles);
+  CHECK((int)L.work.size() == n && sizeof(twr::JacLsqWork) == 40, "%s: work records", name);
+  std::printf("scaled plan %-8s %4d problems: workspace %lld doubles, second workspace %lld doubles (e at %lld, c o p at %lld)\n", name, n,
+              (long long)L.ws_doubles, (long long)L.ws2_doubles, (long long)L.ws2_e, (long long)L.ws2_cp);
+}
+
+int main() {
+  const twr::Structure c3 = build(3, 0, 1, 2.0, 63), c3_hot = build(3, 0, 1, 2.0, 27);
+  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1);
+  plan_case("C3x16", {&c3_hot}, std::vector<int32_t>(16, 0));
+  plan_case("every", {&every, &c3}, {0, 1, 0});
+  std::vector<twr::Structure> ss;
+  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9));
+  std::vector<const twr::Structure*> sp;
+  for (const auto& s : ss) sp.push_back(&s);
+  plan_case("ragged", sp, {0, 1, 2, 3, 4, 5, 3, 1, 1, 0});
+  plan_case("one", sp, {3});
+  const twr::Structure wide = build(3, 0, 1, 2.0, 27, 1.0, 200, 0.003);
+  CHECK(wide.n_vars > twr::kJacLdsX, "the wide structure has %d variables", wide.n_vars);
+  plan_case("wide", {&wide, &c3_hot}, {0, 1, 0});
+  // an odd number of variables in all: the segments still start on 16-byte boundaries
+  bool odd = false;
+  for (size_t i = 0; i < ss.size() && !odd; ++i)
+    if (ss[i].n_vars % 2) {
+      plan_case("odd", {&ss[i]}, {0});
+      plan_case("odd x3", {&ss[i]}, {0, 0, 0});
+      odd = true;
+    }
+  if (!odd) std::printf("scaled plan: no structure with an odd variable count among the ragged ones\n");
+  std::printf("jac_scaled_plan_driver: %d failures\n", fails);
+  return fails ? 1 : 0;
+}

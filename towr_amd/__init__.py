@@ -178,6 +178,11 @@ def lib():
         L.twr_jac_violation.argtypes = [C.c_void_p] + [C.c_void_p] * 5 + [C.c_void_p]
         L.twr_jac_lsq_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p,
                                         C.c_void_p, C.c_void_p]
+        L.twr_jac_col_sqnorms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_lsq_reserve_scaled.argtypes = [C.c_void_p]
+        L.twr_jac_col_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        L.twr_jac_lsq_solve_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                               C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -621,11 +626,17 @@ class JacOps:
         """twr_jac_tmul on raw device pointers (ints); asynchronous on `stream`."""
         _check(lib().twr_jac_tmul(self._h, C.c_void_p(d_jac), C.c_void_p(d_w), C.c_void_p(d_z), C.c_void_p(stream)))
 
+    def col_sqnorms_device(self, d_jac, d_out, d_w=0, stream=0):
+        """twr_jac_col_sqnorms on raw device pointers (ints; d_w 0 = unit weights): d_out[k] = sum_r w_r J[r][k]^2 in the x
+        layout; asynchronous on `stream`."""
+        _check(lib().twr_jac_col_sqnorms(self._h, C.c_void_p(d_jac), C.c_void_p(d_w), C.c_void_p(d_out), C.c_void_p(stream)))
+
 
 class JacLsq:
     """The damped weighted least-squares step with the Jacobian values of a batch on the device (twr_jac_lsq_*), on top of the
     products of `jac_ops` (borrowed: it is kept alive here) and in its x / g / jac layout: per problem
-    (J^T W J + mu I) d = J^T W b by CGLS, the bound-violation residual that feeds it, and per-problem dot products."""
+    (J^T W J + mu I) d = J^T W b by CGLS, the bound-violation residual that feeds it, and per-problem dot products; with
+    Marquardt's scaling (col_scale_device from JacOps.col_sqnorms_device, then solve_scaled_device) mu C^-2 in place of mu I."""
 
     X, G = 0, 1   # the `space` of dot_device
 
@@ -665,3 +676,20 @@ class JacLsq:
         per problem (iterations, |s| / |s0|, |s0|, status)."""
         _check(lib().twr_jac_lsq_solve(self._h, C.c_void_p(d_jac), C.c_void_p(d_b), C.c_void_p(d_w), C.c_void_p(d_mu), int(iters),
                                        float(tol), C.c_void_p(d_d), C.c_void_p(d_info), C.c_void_p(stream)))
+
+    def reserve_scaled(self):
+        """twr_jac_lsq_reserve_scaled: allocate the scaled solve's two extra vectors now (before a hipGraph capture)."""
+        _check(lib().twr_jac_lsq_reserve_scaled(self._h))
+
+    def col_scale_device(self, d_colsq, d_scale, rel_floor, d_colsq_max=0, stream=0):
+        """twr_jac_col_scale on raw device pointers (ints): c = 1 / sqrt(max(a, rel_floor max(a))) per problem, a = colsq or the
+        running maximum d_colsq_max (in / out, 0 = leave out)."""
+        _check(lib().twr_jac_col_scale(self._h, C.c_void_p(d_colsq), C.c_void_p(d_colsq_max), float(rel_floor), C.c_void_p(d_scale),
+                                       C.c_void_p(stream)))
+
+    def solve_scaled_device(self, d_jac, d_b, d_mu, d_scale, d_d, d_info, iters, tol, d_w=0, stream=0):
+        """twr_jac_lsq_solve_scaled on raw device pointers (ints; d_w 0 = unit weights): (J^T W J + mu C^-2) d = J^T W b with
+        C = diag(d_scale); d_info as solve_device, in the scaled variables."""
+        _check(lib().twr_jac_lsq_solve_scaled(self._h, C.c_void_p(d_jac), C.c_void_p(d_b), C.c_void_p(d_w), C.c_void_p(d_mu),
+                                              C.c_void_p(d_scale), int(iters), float(tol), C.c_void_p(d_d), C.c_void_p(d_info),
+                                              C.c_void_p(stream)))

@@ -148,6 +148,9 @@ struct twr_jac_lsq {   // twr::PlanJacLsq's work records and bound tables on the
   twr::LsqBuffers buf{};
   int lds_x = 0;
   int64_t resident = 0;
+  DevPtr<double> ws2;           // the scaled solve's vectors (twr_jac_lsq_reserve_scaled); resident counts them once they exist
+  twr::LsqScaledBuffers buf2{};
+  int64_t ws2_e = 0, ws2_cp = 0, ws2_doubles = 0;
 };
 
 namespace {
@@ -1176,6 +1179,18 @@ int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, doubl
   return TWR_OK;
 }
 
+int twr_jac_col_sqnorms(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_out, void* hip_stream) {
+  if (!ops || !d_jac || !d_out) return fail(TWR_ERR_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(d_jac) | reinterpret_cast<uintptr_t>(d_w) | reinterpret_cast<uintptr_t>(d_out)) & 7)
+    return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(ops->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipError_t e = twr::launch_jac_colsq(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, d_w, ops->slab.get(), d_out,
+                                       static_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return TWR_OK;
+}
+
 int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem,
                        int n_problems, twr_jac_lsq** out) {
   if (!ops || !structs || !struct_of_problem || !out || n_structs < 1 || n_problems < 1) return fail(TWR_ERR_INVALID, "bad arguments");
@@ -1209,6 +1224,7 @@ int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, in
     h->buf = {w + plan.ws_p, w + plan.ws_z, w + plan.ws_q, w + plan.ws_r, w + plan.ws_t, w + plan.ws_rec};
     h->lds_x = plan.lds_x;
     h->resident = (int64_t)bb + (int64_t)(plan.work.size() * sizeof(twr::JacLsqWork)) + 8 * plan.ws_doubles;
+    h->ws2_e = plan.ws2_e, h->ws2_cp = plan.ws2_cp, h->ws2_doubles = plan.ws2_doubles;
     *out = h.release();
     return TWR_OK;
   } catch (const std::exception& e) {
@@ -1271,6 +1287,52 @@ int twr_jac_lsq_solve(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, 
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   return lsq_launched(twr::launch_lsq_solve(
       lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, d_b, d_w, d_mu, iters, tol, d_d, d_info, stream,
+      [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
+      [&](const double* w, double* z) {
+        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
+      }));
+}
+
+int twr_jac_lsq_reserve_scaled(twr_jac_lsq* lsq) {
+  if (!lsq) return fail(TWR_ERR_INVALID, "null handle");
+  if (lsq->ws2) return TWR_OK;
+  try {
+    DeviceScope on(lsq->device);
+    TWR_HIP(on.status);
+    lsq->ws2 = dev_alloc<double>(std::max<size_t>(16, sizeof(double) * (size_t)lsq->ws2_doubles));
+    lsq->buf2 = {lsq->ws2.get() + lsq->ws2_e, lsq->ws2.get() + lsq->ws2_cp};
+    lsq->resident += 8 * lsq->ws2_doubles;
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+int twr_jac_col_scale(twr_jac_lsq* lsq, const double* d_colsq, double* d_colsq_max, double rel_floor, double* d_scale, void* hip_stream) {
+  if (!lsq || !d_colsq || !d_scale) return fail(TWR_ERR_INVALID, "null argument");
+  if (!(rel_floor > 0.0 && rel_floor <= 1.0)) return fail(TWR_ERR_INVALID, "rel_floor must be in (0, 1]");
+  if (misaligned({d_colsq, d_colsq_max, d_scale})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return lsq_launched(twr::launch_lsq_col_scale(lsq->work.d.get(), lsq->work.n, d_colsq, d_colsq_max, rel_floor, d_scale,
+                                                static_cast<hipStream_t>(hip_stream)));
+}
+
+int twr_jac_lsq_solve_scaled(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
+                             const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream) {
+  if (!lsq || !d_jac || !d_b || !d_mu || !d_scale || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
+  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
+  if (misaligned({d_jac, d_b, d_w, d_mu, d_scale, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  if (!lsq->ws2) {
+    const int rc = twr_jac_lsq_reserve_scaled(lsq);
+    if (rc != TWR_OK) return rc;
+  }
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  const twr_jac_ops* ops = lsq->ops;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  return lsq_launched(twr::launch_lsq_solve_scaled(
+      lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, lsq->buf2, d_b, d_w, d_mu, d_scale, iters, tol, d_d, d_info, stream,
       [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
       [&](const double* w, double* z) {
         return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);

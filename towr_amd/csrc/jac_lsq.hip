@@ -7,6 +7,10 @@
 //   lsq_dir_kernel:    s = z - mu d, gamma' = s^T s; first: gamma0 = gamma', p = s; later: beta = gamma' / gamma, convergence
 //                      test, p = s + beta p; writes the problem's info                (then q = J p)
 //   lsq_step_kernel:   delta = q^T (w o q) + mu p^T p, alpha = gamma / delta, d += alpha p, r -= alpha q, t = w o r
+// The Marquardt-scaled step (twr_jac_col_scale, twr_jac_lsq_solve_scaled): (J^T W J + mu C^-2) d = J^T W b, C = diag(c), is the
+// same iteration on J C in e = d / c.  The three kernels above are thin wrappers of bodies templated on SCALED; their _scaled
+// siblings read c, keep e and c o p (for J to read) in a second workspace and write d = c o e; the products are used as they are.
+//   lsq_col_scale_kernel:  c_k = 1 / sqrt(max(a_k, rel_floor max_k a_k)) from the squared column norms (or their running maximum)
 // Every scalar (alpha, beta, gamma, mu, the state) stays on the device: the launch sequence depends on `iters` alone.  A problem
 // that has stopped (converged, or bad input) is skipped by its workgroup in every later kernel: its d, r, p no longer change.
 // No atomics: every sum is taken by lsq_sum in an order fixed by the vector's length (structure.h), so a problem's outputs have
@@ -120,14 +124,20 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_violation_kernel(const JacLsq
   if (threadIdx.x == 0) merit[blockIdx.x] = 0.5 * acc[0];
 }
 
-// d = 0, r = b, t = w o r (w NULL: t = r), and the problem's state: running
-__global__ __launch_bounds__(kLsqThreads) void lsq_start_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
-                                                                const double* __restrict__ b, const double* __restrict__ w,
-                                                                double* __restrict__ d, double* __restrict__ r, double* __restrict__ t) {
+// d = 0, r = b, t = w o r (w NULL: t = r), and the problem's state: running.  SCALED: e = 0 as well.
+template <bool SCALED>
+__device__ inline void lsq_start_body(const JacLsqWork* __restrict__ work, double* __restrict__ rec, const double* __restrict__ b,
+                                      const double* __restrict__ w, double* __restrict__ d, double* __restrict__ e,
+                                      double* __restrict__ r, double* __restrict__ t) {
   const JacLsqWork W = work[blockIdx.x];
   double* dp = d + W.x_off;
   const bool ad = lsq_aligned(dp);
   for (int i = 2 * (int)threadIdx.x; i < W.n; i += 2 * kLsqThreads) lsq_st(dp, i, W.n, ad, make_double2(0.0, 0.0));
+  if constexpr (SCALED) {
+    double* ep = e + W.x_off;
+    const bool ae = lsq_aligned(ep);
+    for (int i = 2 * (int)threadIdx.x; i < W.n; i += 2 * kLsqThreads) lsq_st(ep, i, W.n, ae, make_double2(0.0, 0.0));
+  }
   const double* bp = b + W.g_off;
   const double* wp = w ? w + W.g_off : nullptr;
   double* rp = r + W.g_off;
@@ -141,15 +151,27 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_start_kernel(const JacLsqWork
   }
   if (threadIdx.x == 0) rec[(int64_t)kLsqRec * blockIdx.x + kLsqState] = kLsqRunning;
 }
+__global__ __launch_bounds__(kLsqThreads) void lsq_start_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                                const double* __restrict__ b, const double* __restrict__ w,
+                                                                double* __restrict__ d, double* __restrict__ r, double* __restrict__ t) {
+  lsq_start_body<false>(work, rec, b, w, d, nullptr, r, t);
+}
+__global__ __launch_bounds__(kLsqThreads) void lsq_start_scaled_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                                       const double* __restrict__ b, const double* __restrict__ w,
+                                                                       double* __restrict__ d, double* __restrict__ e,
+                                                                       double* __restrict__ r, double* __restrict__ t) {
+  lsq_start_body<true>(work, rec, b, w, d, e, r, t);
+}
 
 __device__ inline bool lsq_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and Inf
 
-// After q = J p.  A problem that is running: delta, alpha, the three updates and the next J^T's input.
-__global__ __launch_bounds__(kLsqThreads) void lsq_step_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
-                                                               const double* __restrict__ mu, const double* __restrict__ q,
-                                                               const double* __restrict__ w, const double* __restrict__ p,
-                                                               double* __restrict__ d, double* __restrict__ r, double* __restrict__ t) {
-  __shared__ double red[2 * (kLsqThreads / 64)];
+// After q = J p.  A problem that is running: delta, alpha, the three updates and the next J^T's input.  SCALED (q = J (c o p)):
+// the update is e += alpha p, and d = c o e is written beside it.
+template <bool SCALED>
+__device__ inline void lsq_step_body(const JacLsqWork* __restrict__ work, double* __restrict__ rec, const double* __restrict__ mu,
+                                     const double* __restrict__ q, const double* __restrict__ w, const double* __restrict__ p,
+                                     const double* __restrict__ c, double* __restrict__ e, double* __restrict__ d,
+                                     double* __restrict__ r, double* __restrict__ t, double* red) {
   double* rc = rec + (int64_t)kLsqRec * blockIdx.x;
   if (rc[kLsqState] != kLsqRunning) return;   // the whole workgroup: every lane reads the same word, written by an earlier launch
   const double gamma = rc[kLsqGamma], m_u = mu[blockIdx.x];
@@ -182,9 +204,21 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_step_kernel(const JacLsqWork*
     return;
   }
   const double alpha = gamma / delta;
-  for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
-    const double2 pv = lsq_ld(pp, i, n, ap), dv = lsq_ld(dp, i, n, ad);
-    lsq_st(dp, i, n, ad, make_double2(fma(alpha, pv.x, dv.x), fma(alpha, pv.y, dv.y)));
+  if constexpr (SCALED) {
+    const double* cp = c + W.x_off;
+    double* ep = e + W.x_off;
+    const bool ac = lsq_aligned(cp), ae = lsq_aligned(ep);
+    for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+      const double2 pv = lsq_ld(pp, i, n, ap), ev = lsq_ld(ep, i, n, ae), cv = lsq_ld(cp, i, n, ac);
+      const double2 en = make_double2(fma(alpha, pv.x, ev.x), fma(alpha, pv.y, ev.y));
+      lsq_st(ep, i, n, ae, en);
+      lsq_st(dp, i, n, ad, make_double2(cv.x * en.x, cv.y * en.y));
+    }
+  } else {
+    for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+      const double2 pv = lsq_ld(pp, i, n, ap), dv = lsq_ld(dp, i, n, ad);
+      lsq_st(dp, i, n, ad, make_double2(fma(alpha, pv.x, dv.x), fma(alpha, pv.y, dv.y)));
+    }
   }
   for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
     const double2 qv = lsq_ld(qp, i, m, aq), rv = lsq_ld(rp, i, m, ar);
@@ -199,15 +233,32 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_step_kernel(const JacLsqWork*
   }
   if (threadIdx.x == 0) rc[kLsqIters] += 1.0;
 }
+__global__ __launch_bounds__(kLsqThreads) void lsq_step_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                               const double* __restrict__ mu, const double* __restrict__ q,
+                                                               const double* __restrict__ w, const double* __restrict__ p,
+                                                               double* __restrict__ d, double* __restrict__ r, double* __restrict__ t) {
+  __shared__ double red[2 * (kLsqThreads / 64)];
+  lsq_step_body<false>(work, rec, mu, q, w, p, nullptr, nullptr, d, r, t, red);
+}
+__global__ __launch_bounds__(kLsqThreads) void lsq_step_scaled_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                                      const double* __restrict__ mu, const double* __restrict__ q,
+                                                                      const double* __restrict__ w, const double* __restrict__ p,
+                                                                      const double* __restrict__ c, double* __restrict__ e,
+                                                                      double* __restrict__ d, double* __restrict__ r,
+                                                                      double* __restrict__ t) {
+  __shared__ double red[2 * (kLsqThreads / 64)];
+  lsq_step_body<true>(work, rec, mu, q, w, p, c, e, d, r, t, red);
+}
 
 // After z = J^T t.  s = z - mu d (kept in LDS when n <= lds_x, else formed again from memory by the same expression), gamma',
 // and the new direction.  first: the start of a solve (d = 0, so s = z), which also checks mu and sets gamma0.
-__global__ __launch_bounds__(kLsqThreads) void lsq_dir_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
-                                                              const double* __restrict__ mu, const double* __restrict__ z,
-                                                              const double* __restrict__ d, double* __restrict__ p,
-                                                              double* __restrict__ info, double tol2, int first, int lds_x) {
-  extern __shared__ double lsq_s[];   // lds_x doubles
-  __shared__ double red[kLsqThreads / 64];
+// SCALED: `d` is e, s = c o z - mu e, and c o p is written to `cp` for J to read; first also counts the c_k that are not
+// positive finite numbers (bad input: status 2).
+template <bool SCALED>
+__device__ inline void lsq_dir_body(const JacLsqWork* __restrict__ work, double* __restrict__ rec, const double* __restrict__ mu,
+                                    const double* __restrict__ z, const double* __restrict__ d, const double* __restrict__ c,
+                                    double* __restrict__ p, double* __restrict__ cp, double* __restrict__ info, double tol2, int first,
+                                    int lds_x, double* lsq_s, double* red) {
   double* rc = rec + (int64_t)kLsqRec * blockIdx.x;
   if (!first && rc[kLsqState] != kLsqRunning) {   // stopped: only the status is written again (the step kernel may have set it)
     if (threadIdx.x == 0) info[4 * (int64_t)blockIdx.x + 3] = rc[kLsqState];
@@ -220,15 +271,28 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_dir_kernel(const JacLsqWork* 
   const double* dp = d + W.x_off;
   double* pp = p + W.x_off;
   const bool az = lsq_aligned(zp), ad = lsq_aligned(dp), ap = lsq_aligned(pp), staged = n <= lds_x;
+  const double* cs = SCALED ? c + W.x_off : nullptr;
+  double* cpp = SCALED ? cp + W.x_off : nullptr;
+  const bool ac = lsq_aligned(cs), acp = lsq_aligned(cpp);
   const auto s_at = [&](int i) {
-    const double2 zv = lsq_ld(zp, i, n, az);
+    double2 zv = lsq_ld(zp, i, n, az);
+    if constexpr (SCALED) {
+      const double2 cv = lsq_ld(cs, i, n, ac);
+      zv = make_double2(cv.x * zv.x, cv.y * zv.y);
+    }
     if (first) return zv;
     const double2 dv = lsq_ld(dp, i, n, ad);
     return make_double2(fma(-m_u, dv.x, zv.x), fma(-m_u, dv.y, zv.y));
   };
-  double acc[1] = {0.0};
+  double acc[SCALED ? 2 : 1] = {};   // s^T s; SCALED: and the bad c_k
   for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
     const double2 sv = s_at(i);
+    if constexpr (SCALED)
+      if (first) {
+        const double2 cv = lsq_ld(cs, i, n, ac);
+        if (!(cv.x > 0.0) || !lsq_finite(cv.x)) acc[1] += 1.0;
+        if (i + 1 < n && (!(cv.y > 0.0) || !lsq_finite(cv.y))) acc[1] += 1.0;
+      }
     if (staged) {   // the lane reads back what it wrote: no barrier
       lsq_s[i] = sv.x;
       if (i + 1 < n) lsq_s[i + 1] = sv.y;
@@ -241,7 +305,9 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_dir_kernel(const JacLsqWork* 
   double state = kLsqRunning, beta = 0.0, g0 = gamma0;
   if (first) {
     g0 = gn;
-    if (!(m_u >= 0.0) || !lsq_finite(m_u) || !lsq_finite(gn)) state = 2.0;
+    bool bad = !(m_u >= 0.0) || !lsq_finite(m_u) || !lsq_finite(gn);
+    if constexpr (SCALED) bad = bad || acc[1] != 0.0;
+    if (bad) state = 2.0;
     else if (gn <= tol2 * gn) state = 0.0;   // |s0| = 0 (b = 0, no rows), or tol >= 1
   } else {
     if (!lsq_finite(gn)) state = 2.0;
@@ -251,11 +317,15 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_dir_kernel(const JacLsqWork* 
   if (state == kLsqRunning)
     for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
       const double2 sv = staged ? make_double2(lsq_s[i], i + 1 < n ? lsq_s[i + 1] : 0.0) : s_at(i);
-      if (first) {
-        lsq_st(pp, i, n, ap, sv);
-      } else {
+      double2 pn = sv;
+      if (!first) {
         const double2 pv = lsq_ld(pp, i, n, ap);
-        lsq_st(pp, i, n, ap, make_double2(fma(beta, pv.x, sv.x), fma(beta, pv.y, sv.y)));
+        pn = make_double2(fma(beta, pv.x, sv.x), fma(beta, pv.y, sv.y));
+      }
+      lsq_st(pp, i, n, ap, pn);
+      if constexpr (SCALED) {
+        const double2 cv = lsq_ld(cs, i, n, ac);
+        lsq_st(cpp, i, n, acp, make_double2(cv.x * pn.x, cv.y * pn.y));
       }
     }
   if (threadIdx.x == 0) {
@@ -269,9 +339,68 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_dir_kernel(const JacLsqWork* 
     o[3] = state == kLsqRunning ? 1.0 : state;   // still running when the last launch has gone by: the iteration cap
   }
 }
+__global__ __launch_bounds__(kLsqThreads) void lsq_dir_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                              const double* __restrict__ mu, const double* __restrict__ z,
+                                                              const double* __restrict__ d, double* __restrict__ p,
+                                                              double* __restrict__ info, double tol2, int first, int lds_x) {
+  extern __shared__ double lsq_s[];   // lds_x doubles
+  __shared__ double red[kLsqThreads / 64];
+  lsq_dir_body<false>(work, rec, mu, z, d, nullptr, p, nullptr, info, tol2, first, lds_x, lsq_s, red);
+}
+__global__ __launch_bounds__(kLsqThreads) void lsq_dir_scaled_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                                     const double* __restrict__ mu, const double* __restrict__ z,
+                                                                     const double* __restrict__ e, const double* __restrict__ c,
+                                                                     double* __restrict__ p, double* __restrict__ cp,
+                                                                     double* __restrict__ info, double tol2, int first, int lds_x) {
+  extern __shared__ double lsq_s[];   // lds_x doubles
+  __shared__ double red[2 * (kLsqThreads / 64)];
+  lsq_dir_body<true>(work, rec, mu, z, e, c, p, cp, info, tol2, first, lds_x, lsq_s, red);
+}
+
+// c_k = 1 / sqrt(max(a_k, rel_floor top)), top = max_k a_k, a = colsq or the running maximum colsq_max = max(colsq_max, colsq)
+// (in / out, may be NULL); c = 1 for a problem with top == 0.  A NaN a_k gives a NaN c_k and takes no part in top.
+__device__ inline double lsq_scale_a(double m, double a) { return a != a ? a : (m < a ? a : m); }   // max that keeps either NaN
+__global__ __launch_bounds__(kLsqThreads) void lsq_col_scale_kernel(const JacLsqWork* __restrict__ work,
+                                                                    const double* __restrict__ colsq, double* __restrict__ colsq_max,
+                                                                    double rel_floor, double* __restrict__ scale) {
+  __shared__ double red[kLsqThreads / 64];
+  const JacLsqWork W = work[blockIdx.x];
+  const int n = W.n;
+  const double* ap = colsq + W.x_off;
+  double* mp = colsq_max ? colsq_max + W.x_off : nullptr;
+  double* sp = scale + W.x_off;
+  const bool aa = lsq_aligned(ap), am = lsq_aligned(mp), as = lsq_aligned(sp);
+  const auto a_at = [&](int i) {
+    const double2 a = lsq_ld(ap, i, n, aa);
+    if (!mp) return a;
+    const double2 m = lsq_ld(mp, i, n, am);
+    return make_double2(lsq_scale_a(m.x, a.x), lsq_scale_a(m.y, a.y));
+  };
+  double top = 0.0;
+  for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+    const double2 a = a_at(i);
+    top = fmax(top, a.x);   // fmax drops a NaN
+    if (i + 1 < n) top = fmax(top, a.y);
+  }
+  for (int s = 32; s >= 1; s >>= 1) top = fmax(top, __shfl_xor(top, s, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x / 64] = top;
+  __syncthreads();
+  top = red[0];
+  for (int w = 1; w < kLsqThreads / 64; ++w) top = fmax(top, red[w]);
+  const double f = rel_floor * top;
+  const auto c_of = [&](double a) { return a != a ? a : (top == 0.0 ? 1.0 : 1.0 / sqrt(a < f ? f : a)); };
+  for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {   // the pairs this lane read above
+    const double2 a = a_at(i);
+    if (mp) lsq_st(mp, i, n, am, a);
+    lsq_st(sp, i, n, as, make_double2(c_of(a.x), c_of(a.y)));
+  }
+}
 
 struct LsqBuffers {   // the handle's workspace (JacLsqPlan's segments)
   double *p, *z, *q, *r, *t, *rec;
+};
+struct LsqScaledBuffers {   // the second allocation (twr_jac_lsq_reserve_scaled): e = d / c, and c o p for J to read
+  double *e, *cp;
 };
 
 inline hipError_t launch_lsq_dot(const JacLsqWork* work, int n, int space, const double* a, const double* b, double* out,
@@ -300,6 +429,34 @@ inline hipError_t launch_lsq_solve(const JacLsqWork* work, int n, int lds_x, con
     if (e == hipSuccess) e = tmul(ws.t, ws.z);
     if (e == hipSuccess)
       e = jac_launch(lsq_dir_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, d, ws.p, info, tol2, 0, lds_x);
+  }
+  return e;
+}
+
+inline hipError_t launch_lsq_col_scale(const JacLsqWork* work, int n, const double* colsq, double* colsq_max, double rel_floor,
+                                       double* scale, hipStream_t stream) {
+  return jac_launch(lsq_col_scale_kernel, n, kLsqThreads, 0, stream, work, colsq, colsq_max, rel_floor, scale);
+}
+
+// The same sequence on J C in e = d / c: the product kernels as they are, the vector kernels' SCALED instantiations.
+template <class Mul, class TMul>
+inline hipError_t launch_lsq_solve_scaled(const JacLsqWork* work, int n, int lds_x, const LsqBuffers& ws, const LsqScaledBuffers& sc,
+                                          const double* b, const double* w, const double* mu, const double* c, int iters, double tol,
+                                          double* d, double* info, hipStream_t stream, Mul mul, TMul tmul) {
+  const size_t lds = sizeof(double) * (size_t)lds_x;
+  const double tol2 = tol * tol;
+  hipError_t e = jac_launch(lsq_start_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, sc.e, ws.r, ws.t);
+  if (e == hipSuccess) e = tmul(ws.t, ws.z);
+  if (e == hipSuccess)
+    e = jac_launch(lsq_dir_scaled_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 1, lds_x);
+  for (int k = 0; k < iters && e == hipSuccess; ++k) {
+    e = mul(sc.cp, ws.q);
+    if (e == hipSuccess)
+      e = jac_launch(lsq_step_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.q, w, ws.p, c, sc.e, d, ws.r, ws.t);
+    if (e == hipSuccess) e = tmul(ws.t, ws.z);
+    if (e == hipSuccess)
+      e = jac_launch(lsq_dir_scaled_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 0,
+                     lds_x);
   }
   return e;
 }

@@ -1,6 +1,7 @@
 // Products with a batch's Jacobian values, per problem p (twr_jac_mul / twr_jac_tmul, include/towr_amd.h):
 //   jac_mul_kernel:                    y[g_off[p] + r] = sum_k J_p[r][k] v[x_off[p] + k]
 //   jac_tmul_kernel + jac_fold_kernel: z[x_off[p] + k] = sum_r J_p[r][k] w[g_off[p] + r]
+//   jac_colsq_kernel + jac_fold_kernel: c[x_off[p] + k] = sum_r w[g_off[p] + r] J_p[r][k]^2   (twr_jac_col_sqnorms)
 // The work split, the tables and the order of every sum are planned on the host (twr::PlanJacOps, structure.h).  No atomics:
 // every output is written by exactly one lane, which sums its terms in an order fixed by the pattern alone, so a problem's
 // outputs have the same bits wherever it sits in whatever batch.  Every index comes from the plan's tables; J, v and w are
@@ -87,15 +88,18 @@ __global__ __launch_bounds__(kJacThreads) void jac_mul_kernel(const JacMulWork* 
 }
 
 // One partial of z = J^T w per column of the entries [k0, k1) of one problem: the values times their row's w in LDS, then lane
-// j adds the products of the block's j-th column in row order.
-__global__ __launch_bounds__(kJacThreads) void jac_tmul_kernel(const JacTWork* __restrict__ work, const double* __restrict__ jac,
-                                                               const double* __restrict__ wv, double* __restrict__ slab) {
-  __shared__ double vals[kJacTNnz];
-  __shared__ double ws[kJacTSpan];
-  const JacTWork t = work[blockIdx.x];
-  const double* wp = wv + t.g_off + t.r_first;
-  for (int i = threadIdx.x; i < t.span; i += kJacThreads) ws[i] = wp[i];
-  jac_stream(jac + t.j_off, t.k0, t.k1, [&](int i, double a) { vals[i] = a; });
+// j adds the products of the block's j-th column in row order.  kSquare: the values are squared as they are staged and wv may be
+// NULL (unit weights): one partial of the weighted squared column norms (twr_jac_col_sqnorms).
+template <bool kSquare>
+__device__ inline void jac_tmul_block(const JacTWork& t, const double* __restrict__ jac, const double* __restrict__ wv,
+                                      double* __restrict__ slab, double* vals, double* ws) {
+  if (kSquare && !wv) {
+    for (int i = threadIdx.x; i < t.span; i += kJacThreads) ws[i] = 1.0;
+  } else {
+    const double* wp = wv + t.g_off + t.r_first;
+    for (int i = threadIdx.x; i < t.span; i += kJacThreads) ws[i] = wp[i];
+  }
+  jac_stream(jac + t.j_off, t.k0, t.k1, [&](int i, double a) { vals[i] = kSquare ? a * a : a; });
   __syncthreads();
   const int32_t* rp = jac_table<int32_t>(t.row_ptr);
   for (int i = threadIdx.x; i < t.span; i += kJacThreads) {
@@ -111,6 +115,20 @@ __global__ __launch_bounds__(kJacThreads) void jac_tmul_kernel(const JacTWork* _
     for (int i = a; i < b; ++i) acc += vals[pos[i]];
     slab[t.slab + threadIdx.x] = acc;
   }
+}
+
+__global__ __launch_bounds__(kJacThreads) void jac_tmul_kernel(const JacTWork* __restrict__ work, const double* __restrict__ jac,
+                                                               const double* __restrict__ wv, double* __restrict__ slab) {
+  __shared__ double vals[kJacTNnz];
+  __shared__ double ws[kJacTSpan];
+  jac_tmul_block<false>(work[blockIdx.x], jac, wv, slab, vals, ws);
+}
+
+__global__ __launch_bounds__(kJacThreads) void jac_colsq_kernel(const JacTWork* __restrict__ work, const double* __restrict__ jac,
+                                                                const double* __restrict__ wv, double* __restrict__ slab) {
+  __shared__ double vals[kJacTNnz];
+  __shared__ double ws[kJacTSpan];
+  jac_tmul_block<true>(work[blockIdx.x], jac, wv, slab, vals, ws);
 }
 
 // z[c] = the partials of column c in block order; 0 for a column without entries.
@@ -154,6 +172,15 @@ inline hipError_t launch_jac_tmul(const JacTWork* work, int n_work, const JacFol
   hipError_t e = hipSuccess;
   if (n_work > 0) e = jac_launch(jac_tmul_kernel, n_work, kJacThreads, 0, stream, work, jac, w, slab);
   if (e == hipSuccess && n_fold > 0) e = jac_launch(jac_fold_kernel, n_fold, kJacFoldCols, 0, stream, fold, slab, z);
+  return e;
+}
+
+// out[k] = sum_r w_r J[r][k]^2 (w NULL: unit weights): J^T w's work list, slab and fold
+inline hipError_t launch_jac_colsq(const JacTWork* work, int n_work, const JacFoldWork* fold, int n_fold, const double* jac,
+                                   const double* w, double* slab, double* out, hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  if (n_work > 0) e = jac_launch(jac_colsq_kernel, n_work, kJacThreads, 0, stream, work, jac, w, slab);
+  if (e == hipSuccess && n_fold > 0) e = jac_launch(jac_fold_kernel, n_fold, kJacFoldCols, 0, stream, fold, slab, out);
   return e;
 }
 

@@ -2546,6 +2546,9 @@ JacLsqPlan PlanJacLsq(const std::vector<const Structure*>& structs, const std::v
   L.ws_t = L.ws_r + G;
   L.ws_rec = L.ws_t + G;
   L.ws_doubles = L.ws_rec + (int64_t)kLsqRec * n_problems;
+  L.ws2_e = 0;
+  L.ws2_cp = L.ws2_e + X;
+  L.ws2_doubles = L.ws2_cp + X;
   return L;
 }
 

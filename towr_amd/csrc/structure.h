@@ -324,6 +324,8 @@ JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::v
 // planned on the host (no HIP): one work record per problem, the solver's workspace and the per-row bound tables.
 //   workspace (doubles, every segment starts on a 16-byte boundary): p and z in the x layout, q, r and t in the g layout, then
 //   kLsqRec doubles of scalars per problem.  A vector of problem p lives at segment + x_off[p] / g_off[p], as in the batch.
+//   The Marquardt-scaled solve (twr_jac_lsq_solve_scaled) adds two vectors in the x layout, planned as a workspace of their
+//   own (ws2_*) that the handle allocates only when that solve is used.
 //   bounds: per distinct (lower, upper) table lower[m] then upper[m], 16-byte aligned; structures whose tables are
 //   byte-identical share one copy.  These are the structures' own per-row bounds (Structure::lower / upper), any number of
 //   distinct pairs: nothing here reads PackBlob's compact score record.
@@ -347,6 +349,8 @@ struct JacLsqPlan {
   int distinct_bounds = 0;
   int64_t ws_p = 0, ws_z = 0, ws_q = 0, ws_r = 0, ws_t = 0, ws_rec = 0;   // segment starts (doubles)
   int64_t ws_doubles = 0;                     // the whole workspace
+  int64_t ws2_e = 0, ws2_cp = 0;              // the scaled solve's own workspace, a second allocation made on first use
+  int64_t ws2_doubles = 0;                    // (twr_jac_lsq_reserve_scaled): e = d / c and c o p in the x layout, segment starts
   int lds_x = 0;                              // largest n <= kJacLdsX of the batch (the s the direction kernel keeps in LDS)
   void Place(uint64_t base);                  // bound offsets -> device addresses (base: where `bounds` lives)
 };
