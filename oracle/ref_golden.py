@@ -1,0 +1,203 @@
+"""TEST INFRASTRUCTURE ONLY -- records what the reference's own code computes as fixtures tests/golden/ref_*.npz:
+
+    python -m oracle.ref_golden [names...]          (no name: every case of CASES)
+
+Runs only where oracle/_ref/ref_dump exists (oracle/ref_dump/build.sh, i.e. where the reference sources are).  A
+fixture holds the case description (robot, terrain, schedule, every parameter, CSV heights if any), the Jacobian pattern
+once (jac_row, jac_col), constraint and variable bounds (rows lower / upper), the set tables, and for each of several x: x, g, jac_val --
+recorded outputs of the reference's programs, nothing else.  tests/test_ref_golden.py replays them against the oracle,
+the structure builder (CPU) and the device (GPU) on boxes that do not have the reference.
+
+The cases are chosen for what the mpmath fixtures and the hand known-answers cannot reach: entries the reference DEFINES
+rather than derives (force rows x footholds on curved terrain, terrain rows of gridded terrain, explicit zeros), bounds,
+every robot and constraint name, optimised timings, odd schedules, and the BASELINE sizes where the quirk lives."""
+import os
+import sys
+import tempfile
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+N_EE = {"monoped": 1, "biped": 2, "hyq": 4, "anymal": 4, "go1": 4}
+
+
+def _combo(robot, combo, T, scale=1.0):
+    import towr_amd as ta
+
+    return ta.gait_combo(N_EE[robot], combo, T, scale)
+
+
+def _sched(durs, contact):
+    import towr_amd as ta
+
+    return ta.schedule(durs, contact)
+
+
+def _mp_schedule(name):
+    d = np.load(os.path.join(GOLDEN, name + ".npz"))
+    durs, o = [], 0
+    for k in d["n_phases"]:
+        durs.append(d["phase_durations"][o:o + k])
+        o += k
+    return _sched(durs, list(d["contact_at_start"]))
+
+
+def _k(T, K):
+    dt = T / (K - 1.5)
+    return dict(dt_dynamic=dt, dt_rom=dt)
+
+
+def _phases(n_ee, n_ph, T, start_contact, seed):
+    rng = np.random.default_rng(seed)
+    durs = []
+    for _ in range(n_ee):
+        d = rng.uniform(0.2, 0.6, size=n_ph)
+        durs.append(d * (T / d.sum()))
+    return _sched(durs, [int(start_contact)] * n_ee)
+
+
+# name -> (robot, terrain, schedule builder, params, x families); an x family is ("guess" | "perturbed" | "wild" | "snapped", seed)
+W2 = (("wild", 1), ("wild", 2))
+P1 = (("perturbed", 1),)
+W1 = (("wild", 1),)
+COARSE = dict(dt_dynamic=0.3, dt_rom=0.25, duration_base_poly=0.2, dt_base_motion=0.11)
+CASES = {
+    # the quirk entries: force + terrain sets at wild footholds spread over the terrain features
+    # (quirk_gap runs on the schedule and, first, at the x of tests/golden/mp_full_anymal_trot_gap.npz, so that the mpmath
+    # chain-rule values of the same entries can serve as a negative control in tests/test_ref_golden.py)
+    "quirk_gap": ("anymal", "gap", lambda: _mp_schedule("mp_full_anymal_trot_gap"), dict(constraint_sets=17),
+                  (("mp_full_anymal_trot_gap", 0), ("wild", 1), ("wild", 2))),
+    "quirk_stairs": ("anymal", "stairs", lambda: _combo("anymal", 0, 2.4), dict(constraint_sets=17), W2),
+    "quirk_block": ("hyq", "block", lambda: _combo("hyq", 2, 1.8), dict(constraint_sets=17), W2),
+    "quirk_slope": ("biped", "slope", lambda: _combo("biped", 1, 1.6), dict(constraint_sets=17), W2),
+    "quirk_chimney": ("go1", "chimney", lambda: _combo("go1", 3, 2.0), dict(constraint_sets=17), W2),
+    "quirk_chimney_lr": ("monoped", "chimney_lr", lambda: _combo("monoped", 2, 2.0), dict(constraint_sets=17), W2),
+    "quirk_gap_default_sets": ("biped", "gap", lambda: _combo("biped", 0, 1.6, 0.9), dict(constraint_sets=63, dt_dynamic=0.2, dt_rom=0.2), W1),
+    # every robot, every constraint name incl. baseMotion, optimised timings
+    "every_monoped": ("monoped", "flat", lambda: _combo("monoped", 2, 1.2), dict(constraint_sets=255, base_z_init=0.58, **COARSE), P1),
+    "every_biped": ("biped", "slope", lambda: _combo("biped", 1, 1.2), dict(constraint_sets=255, base_z_init=0.65, **COARSE), W1),
+    "every_hyq": ("hyq", "chimney", lambda: _combo("hyq", 3, 1.0), dict(constraint_sets=255, base_z_init=0.58, **COARSE), P1),
+    "every_anymal": ("anymal", "stairs", lambda: _combo("anymal", 1, 1.0), dict(constraint_sets=255, base_z_init=0.42, **COARSE), W1),
+    "every_go1": ("go1", "block", lambda: _combo("go1", 0, 1.2), dict(constraint_sets=255, base_z_init=0.3, **COARSE), P1),
+    "timings_63_monoped": ("monoped", "stairs", lambda: _combo("monoped", 1, 1.2), dict(constraint_sets=63, dt_dynamic=0.2, dt_rom=0.2), W1),
+    "timings_127_biped": ("biped", "gap", lambda: _combo("biped", 0, 1.2), dict(constraint_sets=127, **COARSE), P1),
+    "timings_rom_only": ("biped", "flat", lambda: _combo("biped", 2, 1.2), dict(constraint_sets=64 | 8, dt_rom=0.21), W1),
+    "timings_dynamic_only": ("biped", "block", lambda: _combo("biped", 2, 1.2), dict(constraint_sets=64 | 2, dt_dynamic=0.23), P1),
+    "timings_terrain_force": ("hyq", "slope", lambda: _combo("hyq", 1, 1.2), dict(constraint_sets=64 | 16 | 1), W1),
+    "polys_3_1": ("biped", "stairs", lambda: _combo("biped", 3, 1.2), dict(constraint_sets=63, polys_per_swing=3, polys_per_stance_force=1, **COARSE), P1),
+    "polys_1_4_timings": ("monoped", "gap", lambda: _combo("monoped", 0, 1.2), dict(constraint_sets=127, polys_per_swing=1, polys_per_stance_force=4,
+                                                                                  **COARSE), W1),
+    "fine_base_spline": ("monoped", "slope", lambda: _combo("monoped", 2, 0.9), dict(constraint_sets=31 | 128, duration_base_poly=0.023, base_z_init=0.6,
+                                                                                    dt_dynamic=0.27, dt_rom=0.3, dt_base_motion=0.1), P1),
+    # schedules
+    "flight_start_end": ("biped", "gap", lambda: _phases(2, 4, 1.3, False, 11), dict(constraint_sets=31, **COARSE), W1),   # swing, stance, swing, stance
+    "flight_start_ends_in_flight": ("monoped", "block", lambda: _phases(1, 3, 1.1, False, 12), dict(constraint_sets=31 | 64, **COARSE), P1),
+    "standing_one_phase": ("anymal", "flat", lambda: _phases(4, 1, 0.9, True, 13), dict(constraint_sets=31 | 128, base_z_init=0.45, **COARSE), P1),
+    "phases_31": ("monoped", "stairs", lambda: _phases(1, 31, 9.0, True, 14), dict(constraint_sets=63 | 64, dt_dynamic=1.1, dt_rom=0.9, duration_base_poly=0.9), W1),
+    "two_nodes": ("hyq", "slope", lambda: _combo("hyq", 0, 1.2), dict(constraint_sets=63, dt_dynamic=1.7, dt_rom=1.3, duration_base_poly=0.3), W1),
+    # gridded terrain, footholds snapped onto cell edges
+    "csv_snapped": ("anymal", "csv", lambda: _combo("anymal", 1, 1.2), dict(constraint_sets=17), (("snapped", 1), ("snapped", 2))),
+    # BASELINE sizes: C1-C3 at default x families, C4 / C5 (where the quirk lives) at one wild and one perturbed x each
+    "c1_hopper": ("monoped", "flat", lambda: _sched([[0.4, 0.2, 0.4, 0.2, 0.4, 0.2, 0.2]], [1]), dict(), (("guess", 0), ("perturbed", 1))),
+    "c2_biped_k100": ("biped", "flat", lambda: _combo("biped", 0, 2.0), _k(2.0, 100), (("guess", 0),)),
+    "c3_anymal_trot_k200": ("anymal", "flat", lambda: _combo("anymal", 1, 2.0), _k(2.0, 200), (("guess", 0),)),
+    "c4_gap_k200_wild": ("anymal", "gap", lambda: _combo("anymal", 2, 1.8, 0.9), _k(1.8, 200), W1),
+    "c4_gap_k200_perturbed": ("anymal", "gap", lambda: _combo("anymal", 2, 1.8, 0.9), _k(1.8, 200), P1),
+    "c5_stairs_k200_wild": ("anymal", "stairs", lambda: _combo("anymal", 0, 2.4, 1.1), _k(2.4, 200), W1),
+    "c5_stairs_k200_perturbed": ("anymal", "stairs", lambda: _combo("anymal", 0, 2.4, 1.1), _k(2.4, 200), P1),
+}
+
+
+def csv_heights(name):
+    rng = np.random.default_rng(21 + len(name))
+    return np.round(rng.uniform(0.0, 0.3, size=(16, 22)), 2)
+
+
+def make_x(case, family, seed):
+    if family.startswith("mp_"):
+        return np.load(os.path.join(GOLDEN, family + ".npz"))["x"].copy()
+    if family == "guess":
+        return case.x_guess()
+    if family == "perturbed":
+        return case.x_perturbed(seed)
+    x = case.x_wild(seed)
+    if family == "snapped":   # a third of the foothold coordinates next to the edges of the 0.17 m cells (inside and outside
+        # the slope window), a tenth of them exactly ON an edge (k * 0.17 as the double product: the tie of the cell index)
+        rng = np.random.default_rng(500 + seed)
+        for vs in case.S.var_sets:
+            if vs["name"].startswith("ee-motion"):
+                seg = x[vs["offset"]:vs["offset"] + vs["size"]]
+                pick = rng.random(seg.size) < 0.35
+                seg[pick] = np.round(seg[pick] / 0.17) * 0.17 + rng.uniform(-0.004, 0.004, size=pick.sum())
+                exact = rng.random(seg.size) < 0.1
+                seg[exact] = np.round(seg[exact] / 0.17) * 0.17
+    return x
+
+
+def save_npz_lzma(path, arrays):
+    """An .npz (numpy.load reads it like any other) whose members are LZMA-compressed: the Jacobian values repeat over
+    long distances (the same polynomial weights at every sample), which deflate's 32 KB window cannot see -- 424 KB
+    instead of 655 KB for the values of a K = 200 problem."""
+    import zipfile
+
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_LZMA) as z:
+        for k, v in arrays.items():
+            info = zipfile.ZipInfo(k + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_LZMA
+            with z.open(info, "w", force_zip64=True) as f:
+                np.lib.format.write_array(f, np.asanyarray(v), allow_pickle=False)
+
+
+def record(name, workdir):
+    from oracle import ref_run
+    from tests.common import Case
+
+    robot, terrain, sched, params, families = CASES[name]
+    grid = csv_heights(name) if terrain == "csv" else None
+    case = Case(robot, terrain, sched(), grid=grid, **params)
+    args, kw = ref_run.case_args(case)
+    xs, gs, js, first = [], [], [], None
+    for family, seed in families:
+        x = make_x(case, family, seed)
+        d = ref_run.run(os.path.join(workdir, "%s_%s%d" % (name, family, seed)), *args, x=x, **kw)
+        assert np.array_equal(d["x"], x)
+        if first is None:
+            first = d
+        assert np.array_equal(d["jac_row"], first["jac_row"]) and np.array_equal(d["jac_col"], first["jac_col"]), "the pattern must not depend on x"
+        xs.append(x), gs.append(d["g"]), js.append(d["jac_val"])
+    p = case.params
+    out = dict(robot=robot, terrain=terrain, n_phases=np.array([len(v) for v in first["durations"]], dtype=np.int32),
+               phase_durations=np.concatenate(case.sched.durations()), contact_at_start=np.array(case.sched.contact(), dtype=np.int32),
+               constraint_sets=np.int32(p.constraint_sets), x_family=np.array(["%s%d" % f for f in families]),
+               jac_row=first["jac_row"], jac_col=first["jac_col"], g_bounds=np.array([first["g_lower"], first["g_upper"]]),
+               x_bounds=np.array([first["x_lower"], first["x_upper"]]),
+               con_names=np.array([n for n, _ in first["con_sets"]]), con_rows=np.array([r for _, r in first["con_sets"]], dtype=np.int32),
+               var_names=np.array([n for n, _ in first["var_sets"]]), var_rows=np.array([r for _, r in first["var_sets"]], dtype=np.int32),
+               x=np.array(xs), g=np.array(gs), jac_val=np.array(js), reference_deps=ref_run.deps())
+    out["params"] = np.array([getattr(p, k) for k in ref_run.PARAM_KEYS], dtype=np.float64)   # in the order of ref_run.PARAM_KEYS
+    if grid is not None:
+        out["csv_heights"] = grid
+    path = os.path.join(GOLDEN, "ref_%s.npz" % name)
+    save_npz_lzma(path, out)
+    return path, os.path.getsize(path), len(first["g"]), len(first["jac_row"])
+
+
+def main(names):
+    from oracle import ref_run
+
+    if not ref_run.available():
+        raise SystemExit("oracle/_ref/ref_dump is not built: run oracle/ref_dump/build.sh where the reference sources are")
+    total = 0
+    with tempfile.TemporaryDirectory() as work:
+        for name in names or list(CASES):
+            path, size, m, nnz = record(name, work)
+            total += size
+            print("%-34s m=%6d nnz=%7d %8d bytes" % (os.path.basename(path), m, nnz, size))
+    print("total %d bytes" % total)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

@@ -1,0 +1,107 @@
+"""TEST INFRASTRUCTURE ONLY -- runs oracle/_ref/ref_dump (the reference's own code, built by oracle/ref_dump/build.sh)
+on one problem description and reads its dump back.  Used by tests/test_ref_dump.py and by oracle/ref_golden.py; needs
+nothing but numpy, so it also works where the product library is not built."""
+import os
+import subprocess
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+REF = os.path.join(ROOT, "oracle", "_ref")
+ROBOTS = {"monoped": 0, "biped": 1, "hyq": 2, "anymal": 3, "go1": 4}                                   # RobotModel::Robot
+TERRAINS = {"flat": 0, "block": 1, "stairs": 2, "gap": 3, "slope": 4, "chimney": 5, "chimney_lr": 6}   # HeightMap::TerrainID
+PARAM_KEYS = ("dt_dynamic", "dt_rom", "duration_base_poly", "polys_per_swing", "polys_per_stance_force", "dt_base_motion",
+              "base_z_init")
+
+
+def available():
+    """True where oracle/_ref/ref_dump was built (here, or on the box this tree was copied from)."""
+    status = os.path.join(REF, "STATUS")
+    return os.path.exists(os.path.join(REF, "ref_dump")) and os.path.exists(status) and open(status).read().strip() == "available"
+
+
+def deps():
+    p = os.path.join(REF, "DEPS")
+    return open(p).read().strip() if os.path.exists(p) else "unknown"
+
+
+def command(prefix, robot, terrain, mask, x="guess", durations=None, contact=None, combo=0, T=0.0, goal_x=1.0, params=None,
+            csv_heights=None, extra=()):
+    """The ref_dump command line for one problem; writes the input files it names next to `prefix`.  `params` holds any
+    of PARAM_KEYS; `x` is "guess" or the variable vector; the schedule is either (durations, contact) or (combo, T)."""
+    params = dict(params or {})
+    if isinstance(x, str):
+        xarg = x
+    else:
+        xarg = prefix + "_xin.txt"
+        np.savetxt(xarg, np.asarray(x), fmt="%.17g")
+    cmd = [os.path.join(REF, "ref_dump"), str(ROBOTS[robot]), str(TERRAINS.get(terrain, 0)), str(int(combo)), "%.17g" % T, str(int(mask)),
+           xarg, "%.17g" % goal_x, prefix]
+    if durations is not None:
+        with open(prefix + "_phases_in.txt", "w") as f:
+            for d, c in zip(durations, contact):
+                f.write("%d %s\n" % (int(c), " ".join("%.17g" % v for v in d)))
+        cmd += ["--phases", prefix + "_phases_in.txt"]
+    if "dt_dynamic" in params or "dt_rom" in params:
+        cmd += ["--dt", "%.17g" % params.get("dt_dynamic", 0.0), "%.17g" % params.get("dt_rom", 0.0)]
+    if any(k in params for k in PARAM_KEYS[2:]):
+        z = params.get("base_z_init", float("nan"))
+        cmd += ["--params", "%.17g" % params.get("duration_base_poly", 0.0), str(int(params.get("polys_per_swing", 0))),
+                str(int(params.get("polys_per_stance_force", 0))), "%.17g" % params.get("dt_base_motion", 0.0),
+                "nan" if z != z else "%.17g" % z]
+    if terrain == "csv":
+        np.savetxt(prefix + "_heights.csv", np.asarray(csv_heights), fmt="%.17g", delimiter=",")
+        cmd += ["--csv", prefix + "_heights.csv"]
+    return cmd + list(extra)
+
+
+def read(prefix):
+    """The dump of one ref_dump run as a dict of numpy arrays (+ the set tables and the schedule)."""
+    trip = np.loadtxt(prefix + "_jac.txt", ndmin=2)
+    out = dict(x=np.loadtxt(prefix + "_x.txt", ndmin=1), g=np.loadtxt(prefix + "_g.txt", ndmin=1),
+               jac_row=trip[:, 0].astype(np.int32), jac_col=trip[:, 1].astype(np.int32), jac_val=trip[:, 2].copy())
+    b = np.loadtxt(prefix + "_bounds.txt", ndmin=2)
+    xb = np.loadtxt(prefix + "_xbounds.txt", ndmin=2)
+    out.update(g_lower=b[:, 0].copy(), g_upper=b[:, 1].copy(), x_lower=xb[:, 0].copy(), x_upper=xb[:, 1].copy())
+    con, var = [], []
+    for line in open(prefix + "_sets.txt"):
+        kind, name, rows = line.split()
+        (con if kind == "con" else var).append((name, int(rows)))
+    out["con_sets"], out["var_sets"] = con, var
+    durations, contact = [], []
+    for line in open(prefix + "_phases.txt"):
+        t = line.split()
+        contact.append(int(t[0]))
+        durations.append([float(v) for v in t[1:]])
+    out["durations"], out["contact"] = durations, contact
+    return out
+
+
+def run(prefix, *args, timeout=600, **kw):
+    cmd = command(prefix, *args, **kw)
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    if r.returncode != 0:
+        raise RuntimeError("ref_dump exit %d: %s\n%s" % (r.returncode, " ".join(cmd), (r.stdout + r.stderr)[-2000:]))
+    return read(prefix)
+
+
+def case_args(case):
+    """(args, kwargs) of command() / run() for a tests.common.Case (every field a Case can set reaches the reference)."""
+    p = case.params
+    params = {k: getattr(p, k) for k in PARAM_KEYS}
+    kw = dict(durations=case.sched.durations(), contact=case.sched.contact(), params=params)
+    if case.terrain == "csv":
+        kw["csv_heights"] = case.grid.heights
+    return (case.robot, case.terrain, p.constraint_sets), kw
+
+
+def formulation_states(case, goal_x=1.0):
+    """(initial base position, final base position, initial feet) that oracle/ref_dump/ref_dump.cc sets up around the
+    formulation for a tests.common.Case: nominal stance on the ground, the base at base_z_init (default: nominal
+    height), the goal at goal_x with the base at nominal height above the terrain (nlp_formulation.cc:105-108)."""
+    lin0, ee0 = case.nominal_start()
+    z_nominal = lin0[2]
+    z = case.params.base_z_init
+    if z == z:
+        lin0 = [0.0, 0.0, z]
+    return lin0, [goal_x, 0.0, case.P.terrain_probe(goal_x, 0.0)[0] + z_nominal], ee0
