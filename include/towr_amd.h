@@ -444,6 +444,29 @@ int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, doubl
  * per handle in flight (the slab), the same NULL / alignment / device-scope / sticky-error rules.  With w >= 0 every term is
  * non-negative: the result is 0 exactly when the column has no entry with w_r J_rk^2 != 0. */
 int twr_jac_col_sqnorms(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_out, void* hip_stream);
+/* The normal product in one pass over J: d_u[x_off[p] + k] = (J_p^T (w o (J_p v)))_k in the x layout and, unless d_y is NULL,
+ * d_y = J v in the g layout (d_w NULL: unit weights) -- what an iteration of CG on the normal equations needs, with the
+ * Jacobian values read from memory once instead of once per product.  Blocks of whole rows: a block's values are kept in LDS
+ * while its rows' sums y_r are taken, multiplied by t_r = w_r y_r there, and summed per column into partials that the fold of
+ * twr_jac_tmul adds in block order (structure.h, twr::PlanJacNormal).  Everything said of the two products holds: no atomics,
+ * the order of every sum a function of the pattern alone (same bits wherever the problem sits, on every call, stream and
+ * device; d_y NULL does not change d_u), a column without entries gets an exact 0, a structure without rows writes no y and
+ * zeros to u, J, v and w are only multiplied and added (a NaN / Inf stays in its problem), stream-ordered and capturable, ONE
+ * call per handle in flight (the one-pass slab), the same NULL (d_w and d_y may be) / alignment / device-scope / sticky-error
+ * rules.  u is not bit-identical to twr_jac_tmul of w o twr_jac_mul(v): the blocks differ.
+ *   twr_jac_ops_reserve_normal: plans, uploads and allocates the one-pass tables, work list and slab, once; twr_jac_ops_bytes
+ *                               counts them from then on, and a handle that never asks holds what it held before.  The calls
+ *                               that need them (twr_jac_normal_mul, twr_jac_lsq_solve_onepass) call it themselves when it has
+ *                               not been called: that one call allocates and can NOT be captured in a hipGraph -- reserve
+ *                               before capturing.
+ *   twr_jac_ops_reserve_normal_tile: the same with an LDS tile of tile_entries (1 .. 2048) entries instead of 2048, for tuning
+ *                               and for tests (a small tile turns ordinary rows into rows longer than a tile).  Results
+ *                               keep every property above; their bits depend on the tile.  TWR_ERR_INVALID once the tables
+ *                               exist for another tile. */
+int twr_jac_ops_reserve_normal(twr_jac_ops* ops);
+int twr_jac_ops_reserve_normal_tile(twr_jac_ops* ops, int tile_entries);
+int twr_jac_normal_mul(twr_jac_ops* ops, const double* d_jac, const double* d_w, const double* d_v, double* d_y, double* d_u,
+                       void* hip_stream);
 /* Host introspection: the CSC view of the CSR pattern -- col_ptr[n_vars + 1], and per entry row_idx[nnz] (ascending within a
  * column) and csr_pos[nnz], its position in the CSR value array (CSC values = csr_values[csr_pos]).  Any pointer may be NULL.
  * TWR_ERR_INVALID if a row's column indices do not ascend strictly (they always do for the patterns the factory builds; the
@@ -512,6 +535,23 @@ int twr_jac_lsq_reserve_scaled(twr_jac_lsq* lsq);
 int twr_jac_col_scale(twr_jac_lsq* lsq, const double* d_colsq, double* d_colsq_max, double rel_floor, double* d_scale, void* hip_stream);
 int twr_jac_lsq_solve_scaled(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
                              const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream);
+/* The same step with J read once per iteration: the gradient is recurred instead of formed from r.  From d = 0: r = b,
+ * s = J^T(w o b) (twr_jac_tmul), p = s, gamma = gamma0 = s^T s; repeat (q, u) = twr_jac_normal_mul(p),
+ * delta = q^T(w o q) + mu p^T p, alpha = gamma / delta, d += alpha p, r -= alpha q, s -= alpha (u + mu p), gamma' = s^T s,
+ * beta = gamma' / gamma, p = s + beta p: three launches per iteration (the one-pass product, its fold, one vector kernel)
+ * instead of five.  In exact arithmetic these are the iterates of twr_jac_lsq_solve; in floating point the recurred s drifts
+ * from the true gradient by rounding only, and d is close to, not bit-identical with, twr_jac_lsq_solve's.
+ * d_scale NULL: the unscaled step.  Otherwise the Marquardt-scaled step of twr_jac_lsq_solve_scaled, the same iteration on J C
+ * in e = d / c: s0 = c o J^T(w o b), the product reads c o p, u is multiplied by c, d = c o e; with c = 1 it returns the bits
+ * of the unscaled one-pass solve.  Stopping rule, d_info, status codes, freezing of finished problems, iters == 0 and the bad
+ * mu / bad c rules as twr_jac_lsq_solve[_scaled]; the launch sequence depends on iters alone; d has the same bits in any batch,
+ * call and stream and under any larger iters.  The first call allocates (twr_jac_ops_reserve_normal on the borrowed ops, two
+ * more vectors in the x layout here, twr_jac_lsq_reserve_scaled with d_scale) and can NOT be captured: before capturing, call
+ * twr_jac_lsq_reserve_onepass (scaled != 0: for a d_scale as well), which makes all of them, once.  twr_jac_lsq_bytes and
+ * twr_jac_ops_bytes count the additions from then on. */
+int twr_jac_lsq_reserve_onepass(twr_jac_lsq* lsq, int scaled);
+int twr_jac_lsq_solve_onepass(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
+                              const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream);
 
 /* Tuning knobs.  The DEFAULT build reads nothing from the environment: the values below are compiled in.  A build with
  * -DTWR_TUNING_KNOBS (make -C towr_amd/csrc TUNING=1) reads them, for A/B measurements (scripts/ab.py):

@@ -16,6 +16,15 @@ twr_jac_lsq_solve_scaled, mu starting at 1e-2 lambda_max(C J^T W J C) (the same 
   * scaled: ms of twr_jac_col_sqnorms against twr_jac_tmul on the same buffers, of twr_jac_col_scale, and per iteration of the
     scaled solve against the unscaled one;
   * lm_marquardt: the lm block for the scaled damping, from the same x0.
+--solver cgls (default: the output above, unchanged) | onepass | both.  onepass is twr_jac_lsq_solve_onepass: J read once per
+iteration by twr_jac_normal_mul, the gradient recurred.  It adds
+  * onepass: ms of twr_jac_normal_mul against twr_jac_mul + twr_jac_tmul on the same buffers, and per iteration of the one-pass
+    solve by the protocol of cgls (same process, same buffers, (a --cg-iters solve - a 0-iteration solve) / --cg-iters at
+    tol = 0); with both, its ratio to the CGLS iteration of this process, next to the ratio by bytes: an iteration moves
+    8 (n + m + nnz) + 8 (n + m) in the product (plus its tables and partials) and about 8 (7 n + 5 m) in the vector kernel,
+    against 2 * 8 (n + m + nnz) + 8 (8 n + 6 m);
+  * lm_onepass (lm_marquardt_onepass): the lm blocks with the one-pass solve, from the same x0.  With onepass alone the CGLS
+    blocks are left out.
 Usage (each GPU step under its own time limit):
   timeout -k 10 600 python scripts/jac_lsq.py --workload c3 && timeout -k 10 600 python scripts/jac_lsq.py --workload c5
 """
@@ -91,9 +100,9 @@ def timed(torch, f, steps, rounds):
 REL_FLOOR = 1e-12
 
 
-def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30):
+def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver="cgls"):
     """The LM loop from Q.x (left at the last accepted point).  damping "identity": mu I with the given mu; "marquardt": mu C^-2,
-    mu = 1e-2 lambda_max(C J^T W J C) at the start when None."""
+    mu = 1e-2 lambda_max(C J^T W J C) at the start when None.  solver "onepass": twr_jac_lsq_solve_onepass for the step."""
     st, lsq, ops, batch = Q.st, Q.lsq, Q.ops, Q.batch
     g, r, b, wa, merit, d, info = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(Q.X), Q.vec(4 * Q.P)
     g2, r2, merit2, scores = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(16 * Q.P)
@@ -101,6 +110,8 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30):
     if scaled:
         colsq, colmax, c = Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X)
         lsq.reserve_scaled()
+    if solver == "onepass":
+        lsq.reserve_onepass(scaled)
 
     def linearise():
         batch.eval_device(Q.x.data_ptr(), g.data_ptr(), Q.jac.data_ptr(), ta.EVAL_BOTH, st)
@@ -127,7 +138,10 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30):
         ev[k][0].record()
         linearise()
         ev[k][1].record()
-        if scaled:
+        if solver == "onepass":
+            lsq.solve_onepass_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), lm_cg_iters, 1e-8,
+                                     d_w=wa.data_ptr(), d_scale=c.data_ptr() if scaled else 0, stream=st)
+        elif scaled:
             lsq.solve_scaled_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), c.data_ptr(), d.data_ptr(), info.data_ptr(),
                                     lm_cg_iters, 1e-8, d_w=wa.data_ptr(), stream=st)
         else:
@@ -191,6 +205,51 @@ def measure_scaled(torch, Q, b, wa, mu, a):
                 float(cs[cs > 0].min().sqrt()) if bool((cs > 0).any()) else 0.0, float(cs.max().sqrt())]}
 
 
+def measure_onepass(torch, Q, b, wa, mu, a, cgls_per_iter):
+    """twr_jac_normal_mul against the two products, and the one-pass iteration by the protocol of the cgls block, on the same
+    buffers (J, b, wa of the starting point).  cgls_per_iter: the CGLS iteration of this process (None: not measured)."""
+    st, lsq, ops = Q.st, Q.lsq, Q.ops
+    y, z, u, d, info = Q.vec(Q.G), Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(4 * Q.P)
+    v = torch.from_numpy(np.random.default_rng(9).normal(size=Q.X)).to(Q.dev)
+    ops_bytes_before = ops.bytes()["resident"]
+    if a.normal_tile:
+        ops.reserve_normal(a.normal_tile)
+    lsq.reserve_onepass()
+
+    def solve(iters, tol):
+        lsq.solve_onepass_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), iters, tol,
+                                 d_w=wa.data_ptr(), stream=st)
+
+    calls = {"mul": lambda: ops.mul_device(Q.jac.data_ptr(), v.data_ptr(), y.data_ptr(), st),
+             "tmul": lambda: ops.tmul_device(Q.jac.data_ptr(), y.data_ptr(), z.data_ptr(), st),
+             "normal": lambda: ops.normal_mul_device(Q.jac.data_ptr(), v.data_ptr(), u.data_ptr(), d_w=wa.data_ptr(), d_y=y.data_ptr(),
+                                                     stream=st),
+             "solve": lambda: solve(a.cg_iters, 0.0), "solve0": lambda: solve(0, 0.0)}
+    for f in calls.values():
+        f()
+        f()
+    torch.cuda.synchronize()
+    t = {k: timed(torch, f, a.steps if k in ("mul", "tmul", "normal") else 2, a.rounds) for k, f in calls.items()}
+    per_iter = (t["solve"][0] - t["solve0"][0]) / a.cg_iters
+    nb = 8 * (Q.X + Q.G + Q.J)
+    by_onepass, by_cgls = nb + 8 * (Q.X + Q.G) + 8 * (7 * Q.X + 5 * Q.G), 2 * nb + 8 * (8 * Q.X + 6 * Q.G)
+    res = {"cg_iters": a.cg_iters, "tile": a.normal_tile or 2048, "ms_solve": t["solve"], "ms_start": t["solve0"],
+           "ms_per_iteration_without_start": per_iter, "ms_normal": t["normal"], "ms_mul": t["mul"], "ms_tmul": t["tmul"],
+           "normal_to_products": t["normal"][0] / (t["mul"][0] + t["tmul"][0]),
+           "bytes_onepass_iteration": by_onepass, "bytes_cgls_iteration": by_cgls, "ratio_by_bytes": by_onepass / by_cgls,
+           "jac_ops_bytes_before": ops_bytes_before, "jac_ops_bytes_with_normal": ops.bytes()["resident"],
+           "jac_lsq_bytes_with_onepass": lsq.bytes()["resident"]}
+    if cgls_per_iter is not None:
+        res["ms_per_cgls_iteration_without_start"] = cgls_per_iter
+        res["onepass_to_cgls"] = per_iter / cgls_per_iter
+    solve(a.cg_iters, 1e-10)
+    torch.cuda.synchronize()
+    it = info.view(-1, 4)
+    res["at_tol_1e-10"] = {"iterations_min_max": [float(it[:, 0].min()), float(it[:, 0].max())],
+                           "status_counts": [int((it[:, 3] == s).sum()) for s in (0, 1, 2)]}
+    return res
+
+
 def measure(torch, name, structs, order, x_h, a):
     Q = Problem(torch, structs, order, x_h)
     st, lsq, ops, batch = Q.st, Q.lsq, Q.ops, Q.batch
@@ -200,49 +259,56 @@ def measure(torch, name, structs, order, x_h, a):
     b = -r
     lam = Q.lambda_max(wa, a.power_iters)
     mu = 1e-2 * lam
+    cgls, onepass = a.solver != "onepass", a.solver != "cgls"   # which solvers are measured: nothing is run for the other
     torch.cuda.synchronize()
     out = {"workload": name, "problems": Q.P, "jac_lsq_bytes": lsq.bytes()["resident"], "jac_ops_bytes": ops.bytes()["resident"],
            "lambda_max": [float(lam.min()), float(lam.max())]}
 
     # ---- one CGLS iteration against the two products
-    y, z = Q.vec(Q.G), Q.vec(Q.X)
+    per_iter = None
+    if cgls:
+        y, z = Q.vec(Q.G), Q.vec(Q.X)
 
-    def solve(iters, tol):
-        lsq.solve_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), iters, tol, d_w=wa.data_ptr(), stream=st)
+        def solve(iters, tol):
+            lsq.solve_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), iters, tol, d_w=wa.data_ptr(), stream=st)
 
-    calls = {"mul": lambda: ops.mul_device(Q.jac.data_ptr(), d.data_ptr(), y.data_ptr(), st),
-             "tmul": lambda: ops.tmul_device(Q.jac.data_ptr(), r.data_ptr(), z.data_ptr(), st),
-             "solve": lambda: solve(a.cg_iters, 0.0), "solve0": lambda: solve(0, 0.0)}
-    for f in calls.values():
-        f()
-        f()
-    torch.cuda.synchronize()
-    t = {k: timed(torch, f, a.steps if k in ("mul", "tmul") else 2, a.rounds) for k, f in calls.items()}
-    per_iter = (t["solve"][0] - t["solve0"][0]) / a.cg_iters
-    products = t["mul"][0] + t["tmul"][0]
-    nb = 8 * (Q.X + Q.G + Q.J)
-    out["cgls"] = {"cg_iters": a.cg_iters, "ms_solve": t["solve"], "ms_start": t["solve0"], "ms_per_iteration": t["solve"][0] / a.cg_iters,
-                   "ms_per_iteration_without_start": per_iter, "ms_mul": t["mul"], "ms_tmul": t["tmul"],
-                   "ms_products": products, "ratio_to_products": t["solve"][0] / a.cg_iters / products,
-                   "ratio_without_start": per_iter / products,
-                   "bytes_products": 2 * nb, "bytes_vectors": 8 * (8 * Q.X + 6 * Q.G),
-                   "ratio_by_bytes": 1.0 + 8 * (8 * Q.X + 6 * Q.G) / (2 * nb)}
-    solve(a.cg_iters, 1e-10)
-    torch.cuda.synchronize()
-    it = info.view(-1, 4)
-    out["cgls"]["at_tol_1e-10"] = {"iterations_min_max": [float(it[:, 0].min()), float(it[:, 0].max())],
-                                   "status_counts": [int((it[:, 3] == s).sum()) for s in (0, 1, 2)]}
+        calls = {"mul": lambda: ops.mul_device(Q.jac.data_ptr(), d.data_ptr(), y.data_ptr(), st),
+                 "tmul": lambda: ops.tmul_device(Q.jac.data_ptr(), r.data_ptr(), z.data_ptr(), st),
+                 "solve": lambda: solve(a.cg_iters, 0.0), "solve0": lambda: solve(0, 0.0)}
+        for f in calls.values():
+            f()
+            f()
+        torch.cuda.synchronize()
+        t = {k: timed(torch, f, a.steps if k in ("mul", "tmul") else 2, a.rounds) for k, f in calls.items()}
+        per_iter = (t["solve"][0] - t["solve0"][0]) / a.cg_iters
+        products = t["mul"][0] + t["tmul"][0]
+        nb = 8 * (Q.X + Q.G + Q.J)
+        out["cgls"] = {"cg_iters": a.cg_iters, "ms_solve": t["solve"], "ms_start": t["solve0"], "ms_per_iteration": t["solve"][0] / a.cg_iters,
+                       "ms_per_iteration_without_start": per_iter, "ms_mul": t["mul"], "ms_tmul": t["tmul"],
+                       "ms_products": products, "ratio_to_products": t["solve"][0] / a.cg_iters / products,
+                       "ratio_without_start": per_iter / products,
+                       "bytes_products": 2 * nb, "bytes_vectors": 8 * (8 * Q.X + 6 * Q.G),
+                       "ratio_by_bytes": 1.0 + 8 * (8 * Q.X + 6 * Q.G) / (2 * nb)}
+        solve(a.cg_iters, 1e-10)
+        torch.cuda.synchronize()
+        it = info.view(-1, 4)
+        out["cgls"]["at_tol_1e-10"] = {"iterations_min_max": [float(it[:, 0].min()), float(it[:, 0].max())],
+                                       "status_counts": [int((it[:, 3] == s).sum()) for s in (0, 1, 2)]}
 
     # ---- Levenberg-Marquardt
     x0 = Q.x.clone()
-    if a.damping != "identity":
+    if cgls and a.damping != "identity":
         out["scaled"] = measure_scaled(torch, Q, b, wa, mu, a)   # J, b, wa still those of x0
-    out["lm"] = lm_loop(torch, Q, "identity", mu, a.lm_steps, a.lm_cg_iters)
-    if a.damping != "identity":
-        Q.x = x0
-        out["lm_marquardt"] = lm_loop(torch, Q, "marquardt", None, a.lm_steps, a.lm_cg_iters, a.power_iters)
-    if a.damping == "marquardt":
-        del out["lm"]
+    if onepass:
+        out["onepass"] = measure_onepass(torch, Q, b, wa, mu, a, per_iter)
+    for damping, key in (("identity", "lm"), ("marquardt", "lm_marquardt")):
+        if a.damping not in (damping, "both"):
+            continue
+        for solver, suffix in (("cgls", ""), ("onepass", "_onepass")):
+            if (cgls, onepass)[solver == "onepass"]:
+                Q.x = x0.clone()   # every loop from the same point (a loop leaves Q.x at its last accepted one)
+                out[key + suffix] = lm_loop(torch, Q, damping, mu if damping == "identity" else None, a.lm_steps, a.lm_cg_iters,
+                                            a.power_iters, solver=solver)
     return out
 
 
@@ -257,6 +323,8 @@ def main():
     ap.add_argument("--workload", choices=("c3", "c5", "both"), default="both")
     ap.add_argument("--c3-problems", type=int, default=8192)
     ap.add_argument("--damping", choices=("identity", "marquardt", "both"), default="identity")
+    ap.add_argument("--solver", choices=("cgls", "onepass", "both"), default="cgls")
+    ap.add_argument("--normal-tile", type=int, default=0, help="LDS tile of the one-pass product in entries (0: the default, 2048)")
     a = ap.parse_args()
     import torch
 

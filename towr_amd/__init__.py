@@ -183,6 +183,12 @@ def lib():
         L.twr_jac_col_scale.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         L.twr_jac_lsq_solve_scaled.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_ops_reserve_normal.argtypes = [C.c_void_p]
+        L.twr_jac_ops_reserve_normal_tile.argtypes = [C.c_void_p, C.c_int]
+        L.twr_jac_normal_mul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_lsq_reserve_onepass.argtypes = [C.c_void_p, C.c_int]
+        L.twr_jac_lsq_solve_onepass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -631,6 +637,21 @@ class JacOps:
         layout; asynchronous on `stream`."""
         _check(lib().twr_jac_col_sqnorms(self._h, C.c_void_p(d_jac), C.c_void_p(d_w), C.c_void_p(d_out), C.c_void_p(stream)))
 
+    def reserve_normal(self, tile_entries=None):
+        """twr_jac_ops_reserve_normal: plan, upload and allocate the one-pass product's tables and slab now (before a hipGraph
+        capture); bytes() counts them from then on.  tile_entries (1 .. 2048): twr_jac_ops_reserve_normal_tile, a smaller LDS
+        tile for tuning and tests."""
+        if tile_entries is None:
+            _check(lib().twr_jac_ops_reserve_normal(self._h))
+        else:
+            _check(lib().twr_jac_ops_reserve_normal_tile(self._h, int(tile_entries)))
+
+    def normal_mul_device(self, d_jac, d_v, d_u, d_w=0, d_y=0, stream=0):
+        """twr_jac_normal_mul on raw device pointers (ints; d_w 0 = unit weights, d_y 0 = leave out): u = J^T (w o (J v)) in the
+        x layout and y = J v in the g layout from one pass over J; asynchronous on `stream`."""
+        _check(lib().twr_jac_normal_mul(self._h, C.c_void_p(d_jac), C.c_void_p(d_w), C.c_void_p(d_v), C.c_void_p(d_y), C.c_void_p(d_u),
+                                        C.c_void_p(stream)))
+
 
 class JacLsq:
     """The damped weighted least-squares step with the Jacobian values of a batch on the device (twr_jac_lsq_*), on top of the
@@ -693,3 +714,15 @@ class JacLsq:
         _check(lib().twr_jac_lsq_solve_scaled(self._h, C.c_void_p(d_jac), C.c_void_p(d_b), C.c_void_p(d_w), C.c_void_p(d_mu),
                                               C.c_void_p(d_scale), int(iters), float(tol), C.c_void_p(d_d), C.c_void_p(d_info),
                                               C.c_void_p(stream)))
+
+    def reserve_onepass(self, scaled=False):
+        """twr_jac_lsq_reserve_onepass: everything solve_onepass_device allocates on first use (the one-pass product of the
+        borrowed JacOps, two vectors here, with `scaled` the scaled solve's), now (before a hipGraph capture)."""
+        _check(lib().twr_jac_lsq_reserve_onepass(self._h, int(bool(scaled))))
+
+    def solve_onepass_device(self, d_jac, d_b, d_mu, d_d, d_info, iters, tol, d_w=0, d_scale=0, stream=0):
+        """twr_jac_lsq_solve_onepass on raw device pointers (ints; d_w 0 = unit weights, d_scale 0 = the unscaled step): the step
+        of solve_device / solve_scaled_device with J read once per iteration; d_info as solve_device."""
+        _check(lib().twr_jac_lsq_solve_onepass(self._h, C.c_void_p(d_jac), C.c_void_p(d_b), C.c_void_p(d_w), C.c_void_p(d_mu),
+                                               C.c_void_p(d_scale), int(iters), float(tol), C.c_void_p(d_d), C.c_void_p(d_info),
+                                               C.c_void_p(stream)))

@@ -137,6 +137,22 @@ struct twr_jac_ops {   // twr::PlanJacOps's tables and work lists on the device,
   DevPtr<double> slab;
   int lds_x = 0, distinct_patterns = 0;
   int64_t resident = 0;
+  // The one-pass product (twr_jac_ops_reserve_normal): planned, uploaded and allocated on first use, from the patterns the
+  // device tables hold (read back then).  Until then the host keeps, per distinct pattern, its sizes and where its col /
+  // row_ptr tables lie (twr::JacPatternPlaces of the plan the handle was made from), and every problem's pattern.
+  struct PatternSizes {
+    int32_t n, m, nnz;
+  };
+  std::vector<PatternSizes> pattern_sizes;
+  std::vector<twr::JacPatternPlace> pattern_places;
+  std::vector<int32_t> pattern_of_problem;
+  size_t table_bytes = 0;
+  bool normal_ready = false;
+  DevPtr<void> ntables;
+  DevList<twr::JacNormalWork> nwork;
+  DevList<twr::JacFoldWork> nfold;
+  DevPtr<double> nslab;
+  int n_lds_x = 0, n_tile = 0;
 };
 
 struct twr_jac_lsq {   // twr::PlanJacLsq's work records and bound tables on the device, and the solver's workspace
@@ -151,6 +167,9 @@ struct twr_jac_lsq {   // twr::PlanJacLsq's work records and bound tables on the
   DevPtr<double> ws2;           // the scaled solve's vectors (twr_jac_lsq_reserve_scaled); resident counts them once they exist
   twr::LsqScaledBuffers buf2{};
   int64_t ws2_e = 0, ws2_cp = 0, ws2_doubles = 0;
+  DevPtr<double> ws3;           // the one-pass solve's vectors (twr_jac_lsq_solve_onepass); resident counts them once they exist
+  twr::LsqOnepassBuffers buf3{};
+  int64_t ws3_s = 0, ws3_u = 0, ws3_doubles = 0;
 };
 
 namespace {
@@ -1116,6 +1135,12 @@ int twr_jac_ops_create(const twr_structure* const* structs, int n_structs, const
     const size_t tb = std::max<size_t>(16, plan.tables.size());
     h->tables = dev_alloc<void>(tb);
     if (!plan.tables.empty()) TWR_HIP(hipMemcpy(h->tables.get(), plan.tables.data(), plan.tables.size(), hipMemcpyHostToDevice));
+    h->table_bytes = plan.tables.size();
+    h->pattern_places = twr::JacPatternPlaces(plan, std::vector<int32_t>(struct_of_problem, struct_of_problem + n_problems));
+    for (const twr::JacPatternPlace& a : h->pattern_places) {   // (a structure no problem uses leaves its pattern without a place)
+      if (a.first_struct < 0) h->pattern_sizes.push_back({0, 0, 0});
+      else h->pattern_sizes.push_back({structs[a.first_struct]->s.n_vars, structs[a.first_struct]->s.n_rows, structs[a.first_struct]->s.nnz});
+    }
     plan.Place(reinterpret_cast<uint64_t>(h->tables.get()));
     if (!plan.mul.empty()) h->mul = upload(plan.mul);
     if (!plan.tmul.empty()) h->tmul = upload(plan.tmul);
@@ -1123,6 +1148,8 @@ int twr_jac_ops_create(const twr_structure* const* structs, int n_structs, const
     h->slab = dev_alloc<double>(sizeof(double) * std::max<size_t>(1, (size_t)plan.slab));
     h->lds_x = plan.mul_lds_x;
     h->distinct_patterns = plan.distinct_patterns;
+    h->pattern_of_problem.resize(n_problems);
+    for (int p = 0; p < n_problems; ++p) h->pattern_of_problem[p] = plan.pattern_of_struct[struct_of_problem[p]];
     h->resident = (int64_t)tb + (int64_t)(plan.mul.size() * sizeof(twr::JacMulWork) + plan.tmul.size() * sizeof(twr::JacTWork) +
                                           plan.fold.size() * sizeof(twr::JacFoldWork)) +
                   8 * std::max<int64_t>(1, plan.slab);
@@ -1191,6 +1218,97 @@ int twr_jac_col_sqnorms(twr_jac_ops* ops, const double* d_jac, const double* d_w
   return TWR_OK;
 }
 
+int twr_jac_ops_reserve_normal(twr_jac_ops* ops) { return twr_jac_ops_reserve_normal_tile(ops, twr::kJacNormNnz); }
+
+int twr_jac_ops_reserve_normal_tile(twr_jac_ops* ops, int tile_entries) {
+  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
+  if (tile_entries < 1 || tile_entries > twr::kJacNormNnz) return fail(TWR_ERR_INVALID, "the tile is 1 .. 2048 entries");
+  if (ops->normal_ready)
+    return ops->n_tile == tile_entries ? TWR_OK : fail(TWR_ERR_INVALID, "the one-pass tables exist, made for another tile");
+  twr::JacNormalPlan plan;
+  std::vector<char> tables(ops->table_bytes);
+  try {
+    DeviceScope on(ops->device);
+    TWR_HIP(on.status);
+    if (!tables.empty()) TWR_HIP(hipMemcpy(tables.data(), ops->tables.get(), tables.size(), hipMemcpyDeviceToHost));
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+  try {
+    std::vector<twr::Structure> pats(ops->pattern_sizes.size());
+    std::vector<const twr::Structure*> sp;
+    for (size_t q = 0; q < pats.size(); ++q) {
+      const twr_jac_ops::PatternSizes& Z = ops->pattern_sizes[q];
+      const twr::JacPatternPlace& A = ops->pattern_places[q];
+      twr::Structure& S = pats[q];
+      S.n_vars = Z.n, S.n_rows = Z.m, S.nnz = Z.nnz;
+      S.row_ptr.assign(Z.m + 1, 0);
+      S.col_idx.resize(Z.nnz);
+      if (Z.m > 0) {
+        if (A.row_ptr + sizeof(int32_t) * (Z.m + 1) > tables.size() || A.col + sizeof(uint16_t) * Z.nnz > tables.size())
+          throw std::runtime_error("a pattern's tables lie outside the handle's");
+        std::memcpy(S.row_ptr.data(), tables.data() + A.row_ptr, sizeof(int32_t) * (Z.m + 1));
+        const uint16_t* col = reinterpret_cast<const uint16_t*>(tables.data() + A.col);
+        std::copy(col, col + Z.nnz, S.col_idx.begin());
+      }
+      sp.push_back(&S);
+    }
+    plan = twr::PlanJacNormal(sp, ops->pattern_places, ops->pattern_of_problem, tile_entries);
+    if (plan.x_off != ops->x_off || plan.g_off != ops->g_off || plan.j_off != ops->j_off)
+      throw std::runtime_error("the one-pass plan's layout is not the handle's");
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+  try {
+    DeviceScope on(ops->device);
+    TWR_HIP(on.status);
+    TWR_HIP(twr::prepare_jac_normal());
+    const size_t tb = std::max<size_t>(16, plan.tables.size());
+    DevPtr<void> tables = dev_alloc<void>(tb);
+    if (!plan.tables.empty()) TWR_HIP(hipMemcpy(tables.get(), plan.tables.data(), plan.tables.size(), hipMemcpyHostToDevice));
+    plan.Place(reinterpret_cast<uint64_t>(ops->tables.get()), reinterpret_cast<uint64_t>(tables.get()));
+    DevList<twr::JacNormalWork> work;
+    DevList<twr::JacFoldWork> fold;
+    if (!plan.work.empty()) work = upload(plan.work);
+    if (!plan.fold.empty()) fold = upload(plan.fold);
+    DevPtr<double> slab = dev_alloc<double>(sizeof(double) * std::max<size_t>(1, (size_t)plan.slab));
+    ops->ntables = std::move(tables);
+    ops->nwork = std::move(work);
+    ops->nfold = std::move(fold);
+    ops->nslab = std::move(slab);
+    ops->n_lds_x = plan.lds_x;
+    ops->n_tile = plan.tile;
+    ops->resident += (int64_t)tb + (int64_t)(plan.work.size() * sizeof(twr::JacNormalWork) + plan.fold.size() * sizeof(twr::JacFoldWork)) +
+                     8 * std::max<int64_t>(1, plan.slab);
+    ops->normal_ready = true;
+    ops->pattern_sizes.clear();
+    ops->pattern_places.clear();
+    ops->pattern_of_problem.clear();
+    ops->pattern_of_problem.shrink_to_fit();
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+int twr_jac_normal_mul(twr_jac_ops* ops, const double* d_jac, const double* d_w, const double* d_v, double* d_y, double* d_u,
+                       void* hip_stream) {
+  if (!ops || !d_jac || !d_v || !d_u) return fail(TWR_ERR_INVALID, "null argument");
+  if ((reinterpret_cast<uintptr_t>(d_jac) | reinterpret_cast<uintptr_t>(d_w) | reinterpret_cast<uintptr_t>(d_v) |
+       reinterpret_cast<uintptr_t>(d_y) | reinterpret_cast<uintptr_t>(d_u)) & 7)
+    return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  if (!ops->normal_ready) {
+    const int rc = twr_jac_ops_reserve_normal(ops);
+    if (rc != TWR_OK) return rc;
+  }
+  DeviceScope on(ops->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipError_t e = twr::launch_jac_normal(ops->nwork.d.get(), ops->nwork.n, ops->n_lds_x, ops->n_tile, ops->nfold.d.get(), ops->nfold.n, d_jac, d_w, d_v,
+                                        d_y, ops->nslab.get(), d_u, static_cast<hipStream_t>(hip_stream));
+  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  return TWR_OK;
+}
+
 int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem,
                        int n_problems, twr_jac_lsq** out) {
   if (!ops || !structs || !struct_of_problem || !out || n_structs < 1 || n_problems < 1) return fail(TWR_ERR_INVALID, "bad arguments");
@@ -1225,6 +1343,7 @@ int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, in
     h->lds_x = plan.lds_x;
     h->resident = (int64_t)bb + (int64_t)(plan.work.size() * sizeof(twr::JacLsqWork)) + 8 * plan.ws_doubles;
     h->ws2_e = plan.ws2_e, h->ws2_cp = plan.ws2_cp, h->ws2_doubles = plan.ws2_doubles;
+    h->ws3_s = plan.ws3_s, h->ws3_u = plan.ws3_u, h->ws3_doubles = plan.ws3_doubles;
     *out = h.release();
     return TWR_OK;
   } catch (const std::exception& e) {
@@ -1336,6 +1455,47 @@ int twr_jac_lsq_solve_scaled(twr_jac_lsq* lsq, const double* d_jac, const double
       [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
       [&](const double* w, double* z) {
         return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
+      }));
+}
+
+int twr_jac_lsq_reserve_onepass(twr_jac_lsq* lsq, int scaled) {
+  if (!lsq) return fail(TWR_ERR_INVALID, "null handle");
+  int rc = lsq->ops->normal_ready ? TWR_OK : twr_jac_ops_reserve_normal(lsq->ops);   // (tables of any tile serve)
+  if (rc == TWR_OK && scaled) rc = twr_jac_lsq_reserve_scaled(lsq);
+  if (rc != TWR_OK || lsq->ws3) return rc;
+  try {
+    DeviceScope on(lsq->device);
+    TWR_HIP(on.status);
+    lsq->ws3 = dev_alloc<double>(std::max<size_t>(16, sizeof(double) * (size_t)lsq->ws3_doubles));
+    lsq->buf3 = {lsq->ws3.get() + lsq->ws3_s, lsq->ws3.get() + lsq->ws3_u};
+    lsq->resident += 8 * lsq->ws3_doubles;
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+int twr_jac_lsq_solve_onepass(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
+                              const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream) {
+  if (!lsq || !d_jac || !d_b || !d_mu || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
+  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
+  if (misaligned({d_jac, d_b, d_w, d_mu, d_scale, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  twr_jac_ops* ops = lsq->ops;
+  if (!ops->normal_ready || !lsq->ws3 || (d_scale && !lsq->ws2)) {
+    const int rc = twr_jac_lsq_reserve_onepass(lsq, d_scale != nullptr);
+    if (rc != TWR_OK) return rc;
+  }
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  return lsq_launched(twr::launch_lsq_solve_onepass(
+      lsq->work.d.get(), lsq->work.n, lsq->buf, lsq->buf2, lsq->buf3, d_b, d_w, d_mu, d_scale, iters, tol, d_d, d_info, stream,
+      [&](const double* w, double* z) {
+        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
+      },
+      [&](const double* v, double* y, double* u) {
+        return twr::launch_jac_normal(ops->nwork.d.get(), ops->nwork.n, ops->n_lds_x, ops->n_tile, ops->nfold.d.get(), ops->nfold.n, d_jac, d_w, v, y,
+                                      ops->nslab.get(), u, stream);
       }));
 }
 

@@ -11,6 +11,7 @@
 // same iteration on J C in e = d / c.  The three kernels above are thin wrappers of bodies templated on SCALED; their _scaled
 // siblings read c, keep e and c o p (for J to read) in a second workspace and write d = c o e; the products are used as they are.
 //   lsq_col_scale_kernel:  c_k = 1 / sqrt(max(a_k, rel_floor max_k a_k)) from the squared column norms (or their running maximum)
+// The one-pass solve (twr_jac_lsq_solve_onepass) recurs s instead and needs one vector kernel per iteration (lsq_onepass_kernel).
 // Every scalar (alpha, beta, gamma, mu, the state) stays on the device: the launch sequence depends on `iters` alone.  A problem
 // that has stopped (converged, or bad input) is skipped by its workgroup in every later kernel: its d, r, p no longer change.
 // No atomics: every sum is taken by lsq_sum in an order fixed by the vector's length (structure.h), so a problem's outputs have
@@ -357,6 +358,168 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_dir_scaled_kernel(const JacLs
   lsq_dir_body<true>(work, rec, mu, z, e, c, p, cp, info, tol2, first, lds_x, lsq_s, red);
 }
 
+// The one-pass solve (twr_jac_lsq_solve_onepass): the gradient s is recurred, s -= alpha (u + mu p) with u = J^T (w o (J p)) from
+// the one-pass product, so the vector work of an iteration needs no product in its middle and is this one kernel.
+//   first (after z = J^T (w o b)): s = z, gamma0 = gamma = s^T s, the checks of mu (and c), p = s.
+//   later (after (q, u) = normal(p)): delta, alpha, d += alpha p, r -= alpha q, s -= alpha (u + mu p), gamma' = s^T s, the
+//   convergence test, beta, p = s + beta p; writes the problem's info.
+// SCALED: the iteration on J C in e = d / c: s0 = c o z, the product read c o p (written to `cp`), u is multiplied by c,
+// e += alpha p and d = c o e.  With c = 1 every one of these is exact: the bits of the unscaled kernel.
+// A lane reads back from memory only what it wrote itself (the same index pairs): no barrier for s.
+template <bool SCALED>
+__device__ inline void lsq_onepass_body(const JacLsqWork* __restrict__ work, double* __restrict__ rec, const double* __restrict__ mu,
+                                        const double* __restrict__ z, const double* __restrict__ q, const double* __restrict__ u,
+                                        const double* __restrict__ w, const double* __restrict__ c, double* __restrict__ p,
+                                        double* __restrict__ cp, double* __restrict__ s, double* __restrict__ e, double* __restrict__ d,
+                                        double* __restrict__ r, double* __restrict__ info, double tol2, int first, double* red) {
+  double* rc = rec + (int64_t)kLsqRec * blockIdx.x;
+  double* o = info + 4 * (int64_t)blockIdx.x;
+  if (!first && rc[kLsqState] != kLsqRunning) {   // stopped: only the status is written again
+    if (threadIdx.x == 0) o[3] = rc[kLsqState];
+    return;
+  }
+  const double m_u = mu[blockIdx.x];
+  const JacLsqWork W = work[blockIdx.x];
+  const int n = W.n, m = W.m;
+  double* pp = p + W.x_off;
+  double* sp = s + W.x_off;
+  const double* cs = SCALED ? c + W.x_off : nullptr;
+  double* cpp = SCALED ? cp + W.x_off : nullptr;
+  const bool ap = lsq_aligned(pp), as = lsq_aligned(sp), ac = lsq_aligned(cs), acp = lsq_aligned(cpp);
+  const auto put_p = [&](int i, double2 pn) {
+    lsq_st(pp, i, n, ap, pn);
+    if constexpr (SCALED) {
+      const double2 cv = lsq_ld(cs, i, n, ac);
+      lsq_st(cpp, i, n, acp, make_double2(cv.x * pn.x, cv.y * pn.y));
+    }
+  };
+  if (first) {
+    const double* zp = z + W.x_off;
+    const bool az = lsq_aligned(zp);
+    double acc[SCALED ? 2 : 1] = {};   // s^T s; SCALED: and the bad c_k
+    for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+      double2 sv = lsq_ld(zp, i, n, az);
+      if constexpr (SCALED) {
+        const double2 cv = lsq_ld(cs, i, n, ac);
+        sv = make_double2(cv.x * sv.x, cv.y * sv.y);
+        if (!(cv.x > 0.0) || !lsq_finite(cv.x)) acc[1] += 1.0;
+        if (i + 1 < n && (!(cv.y > 0.0) || !lsq_finite(cv.y))) acc[1] += 1.0;
+      }
+      lsq_st(sp, i, n, as, sv);
+      acc[0] += sv.x * sv.x;
+      if (i + 1 < n) acc[0] += sv.y * sv.y;
+    }
+    lsq_sum(acc, red);
+    const double gn = acc[0];
+    double state = kLsqRunning;
+    bool bad = !(m_u >= 0.0) || !lsq_finite(m_u) || !lsq_finite(gn);
+    if constexpr (SCALED) bad = bad || acc[1] != 0.0;
+    if (bad) state = 2.0;
+    else if (gn <= tol2 * gn) state = 0.0;   // |s0| = 0 (b = 0, no rows), or tol >= 1
+    if (state == kLsqRunning)
+      for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) put_p(i, lsq_ld(sp, i, n, as));
+    if (threadIdx.x == 0) {
+      rc[kLsqGamma] = gn, rc[kLsqGamma0] = gn, rc[kLsqIters] = 0.0, rc[kLsqState] = state;
+      o[0] = 0.0;
+      o[1] = gn == 0.0 ? 0.0 : sqrt(gn / gn);
+      o[2] = sqrt(gn);
+      o[3] = state == kLsqRunning ? 1.0 : state;
+    }
+    return;
+  }
+  const double gamma = rc[kLsqGamma], g0 = rc[kLsqGamma0], iters = rc[kLsqIters];
+  const double* qp = q + W.g_off;
+  const double* wp = w ? w + W.g_off : nullptr;
+  const double* up = u + W.x_off;
+  double* dp = d + W.x_off;
+  double* rp = r + W.g_off;
+  const bool aq = lsq_aligned(qp), aw = lsq_aligned(wp), au = lsq_aligned(up), ad = lsq_aligned(dp), ar = lsq_aligned(rp);
+  double acc[2] = {0.0, 0.0};   // q^T (w o q), p^T p
+  for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
+    const double2 qv = lsq_ld(qp, i, m, aq);
+    const double2 wv = wp ? lsq_ld(wp, i, m, aw) : make_double2(1.0, 1.0);
+    acc[0] += qv.x * (wv.x * qv.x);
+    if (i + 1 < m) acc[0] += qv.y * (wv.y * qv.y);
+  }
+  for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+    const double2 pv = lsq_ld(pp, i, n, ap);
+    acc[1] += pv.x * pv.x;
+    if (i + 1 < n) acc[1] += pv.y * pv.y;
+  }
+  lsq_sum(acc, red);
+  const double delta = acc[0] + m_u * acc[1];
+  if (!(delta > 0.0) || !lsq_finite(delta)) {   // NaN, Inf, or no curvature along p: alpha would not be a number
+    if (threadIdx.x == 0) rc[kLsqState] = 2.0, o[3] = 2.0;
+    return;
+  }
+  const double alpha = gamma / delta;
+  double* ep = SCALED ? e + W.x_off : nullptr;
+  const bool ae = lsq_aligned(ep);
+  double gs[1] = {0.0};   // s^T s of the new s
+  for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+    const double2 pv = lsq_ld(pp, i, n, ap), sv = lsq_ld(sp, i, n, as);
+    double2 uv = lsq_ld(up, i, n, au);
+    if constexpr (SCALED) {
+      const double2 cv = lsq_ld(cs, i, n, ac), ev = lsq_ld(ep, i, n, ae);
+      uv = make_double2(cv.x * uv.x, cv.y * uv.y);
+      const double2 en = make_double2(fma(alpha, pv.x, ev.x), fma(alpha, pv.y, ev.y));
+      lsq_st(ep, i, n, ae, en);
+      lsq_st(dp, i, n, ad, make_double2(cv.x * en.x, cv.y * en.y));
+    } else {
+      const double2 dv = lsq_ld(dp, i, n, ad);
+      lsq_st(dp, i, n, ad, make_double2(fma(alpha, pv.x, dv.x), fma(alpha, pv.y, dv.y)));
+    }
+    const double2 sn = make_double2(fma(-alpha, fma(m_u, pv.x, uv.x), sv.x), fma(-alpha, fma(m_u, pv.y, uv.y), sv.y));
+    lsq_st(sp, i, n, as, sn);
+    gs[0] += sn.x * sn.x;
+    if (i + 1 < n) gs[0] += sn.y * sn.y;
+  }
+  for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
+    const double2 qv = lsq_ld(qp, i, m, aq), rv = lsq_ld(rp, i, m, ar);
+    lsq_st(rp, i, m, ar, make_double2(fma(-alpha, qv.x, rv.x), fma(-alpha, qv.y, rv.y)));
+  }
+  lsq_sum(gs, red);
+  const double gn = gs[0];
+  double state = kLsqRunning, beta = 0.0;
+  if (!lsq_finite(gn)) state = 2.0;
+  else if (gn <= tol2 * g0) state = 0.0;
+  else beta = gn / gamma;
+  if (state == kLsqRunning)
+    for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
+      const double2 sv = lsq_ld(sp, i, n, as), pv = lsq_ld(pp, i, n, ap);
+      put_p(i, make_double2(fma(beta, pv.x, sv.x), fma(beta, pv.y, sv.y)));
+    }
+  if (threadIdx.x == 0) {
+    rc[kLsqGamma] = gn;
+    rc[kLsqState] = state;
+    rc[kLsqIters] = iters + 1.0;
+    o[0] = iters + 1.0;
+    o[1] = g0 == 0.0 ? 0.0 : sqrt(gn / g0);
+    o[2] = sqrt(g0);
+    o[3] = state == kLsqRunning ? 1.0 : state;   // still running when the last launch has gone by: the iteration cap
+  }
+}
+__global__ __launch_bounds__(kLsqThreads) void lsq_onepass_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                                  const double* __restrict__ mu, const double* __restrict__ z,
+                                                                  const double* __restrict__ q, const double* __restrict__ u,
+                                                                  const double* __restrict__ w, double* __restrict__ p,
+                                                                  double* __restrict__ s, double* __restrict__ d, double* __restrict__ r,
+                                                                  double* __restrict__ info, double tol2, int first) {
+  __shared__ double red[2 * (kLsqThreads / 64)];
+  lsq_onepass_body<false>(work, rec, mu, z, q, u, w, nullptr, p, nullptr, s, nullptr, d, r, info, tol2, first, red);
+}
+__global__ __launch_bounds__(kLsqThreads) void lsq_onepass_scaled_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                                         const double* __restrict__ mu, const double* __restrict__ z,
+                                                                         const double* __restrict__ q, const double* __restrict__ u,
+                                                                         const double* __restrict__ w, const double* __restrict__ c,
+                                                                         double* __restrict__ p, double* __restrict__ cp,
+                                                                         double* __restrict__ s, double* __restrict__ e,
+                                                                         double* __restrict__ d, double* __restrict__ r,
+                                                                         double* __restrict__ info, double tol2, int first) {
+  __shared__ double red[2 * (kLsqThreads / 64)];
+  lsq_onepass_body<true>(work, rec, mu, z, q, u, w, c, p, cp, s, e, d, r, info, tol2, first, red);
+}
+
 // c_k = 1 / sqrt(max(a_k, rel_floor top)), top = max_k a_k, a = colsq or the running maximum colsq_max = max(colsq_max, colsq)
 // (in / out, may be NULL); c = 1 for a problem with top == 0.  A NaN a_k gives a NaN c_k and takes no part in top.
 __device__ inline double lsq_scale_a(double m, double a) { return a != a ? a : (m < a ? a : m); }   // max that keeps either NaN
@@ -429,6 +592,36 @@ inline hipError_t launch_lsq_solve(const JacLsqWork* work, int n, int lds_x, con
     if (e == hipSuccess) e = tmul(ws.t, ws.z);
     if (e == hipSuccess)
       e = jac_launch(lsq_dir_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, d, ws.p, info, tol2, 0, lds_x);
+  }
+  return e;
+}
+
+struct LsqOnepassBuffers {   // the third allocation (twr_jac_lsq_solve_onepass): the recurred s, and u = J^T (w o (J p))
+  double *s, *u;
+};
+
+// The one-pass solve: 4 launches to start (start, J^T t and its fold, first), 3 per iteration (the one-pass product, its fold,
+// the vector kernel), none of them conditional.  c NULL: the unscaled step; else sc holds e and c o p.
+template <class TMul, class Normal>
+inline hipError_t launch_lsq_solve_onepass(const JacLsqWork* work, int n, const LsqBuffers& ws, const LsqScaledBuffers& sc,
+                                           const LsqOnepassBuffers& op, const double* b, const double* w, const double* mu,
+                                           const double* c, int iters, double tol, double* d, double* info, hipStream_t stream,
+                                           TMul tmul, Normal normal) {
+  const double tol2 = tol * tol;
+  const auto vec = [&](int first) {
+    if (c)
+      return jac_launch(lsq_onepass_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.z, ws.q, op.u, w, c, ws.p, sc.cp, op.s,
+                        sc.e, d, ws.r, info, tol2, first);
+    return jac_launch(lsq_onepass_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.z, ws.q, op.u, w, ws.p, op.s, d, ws.r, info,
+                      tol2, first);
+  };
+  hipError_t e = c ? jac_launch(lsq_start_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, sc.e, ws.r, ws.t)
+                   : jac_launch(lsq_start_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, ws.r, ws.t);
+  if (e == hipSuccess) e = tmul(ws.t, ws.z);
+  if (e == hipSuccess) e = vec(1);
+  for (int k = 0; k < iters && e == hipSuccess; ++k) {
+    e = normal(c ? sc.cp : ws.p, ws.q, op.u);
+    if (e == hipSuccess) e = vec(0);
   }
   return e;
 }

@@ -2,6 +2,8 @@
 //   jac_mul_kernel:                    y[g_off[p] + r] = sum_k J_p[r][k] v[x_off[p] + k]
 //   jac_tmul_kernel + jac_fold_kernel: z[x_off[p] + k] = sum_r J_p[r][k] w[g_off[p] + r]
 //   jac_colsq_kernel + jac_fold_kernel: c[x_off[p] + k] = sum_r w[g_off[p] + r] J_p[r][k]^2   (twr_jac_col_sqnorms)
+//   jac_normal_kernel + jac_fold_kernel: u = J_p^T (w o (J_p v)) and y = J_p v from one pass over J_p   (twr_jac_normal_mul;
+//                                        twr::PlanJacNormal)
 // The work split, the tables and the order of every sum are planned on the host (twr::PlanJacOps, structure.h).  No atomics:
 // every output is written by exactly one lane, which sums its terms in an order fixed by the pattern alone, so a problem's
 // outputs have the same bits wherever it sits in whatever batch.  Every index comes from the plan's tables; J, v and w are
@@ -144,6 +146,78 @@ __global__ __launch_bounds__(kJacFoldCols) void jac_fold_kernel(const JacFoldWor
   z[f.x_off + c] = acc;
 }
 
+// One pass over the rows [r0, r1) of one problem for u = J^T (w o (J v)) (twr_jac_normal_mul; twr::PlanJacNormal): the block's
+// values are read once, kept raw in `vals` and multiplied by v[col] in `prod`.  Lane t owns row r0 + t: it adds the row's products
+// in column order (y_r), forms t_r = w_r y_r and multiplies the row's raw values by it (its own entries: no barrier in between).
+// The column lanes then loop over the block's columns, each adding its column's products in row order into one partial.
+template <bool kStaged>
+__device__ inline void jac_normal_block(const JacNormalWork& w, const double* __restrict__ jac, const double* __restrict__ wv,
+                                        const double* __restrict__ v, double* __restrict__ y, double* __restrict__ slab, int tile,
+                                        double* prod, double* vals, double* vs) {
+  const uint16_t* col = jac_table<uint16_t>(w.col);
+  const int32_t* rp = jac_table<int32_t>(w.row_ptr);
+  const double* vp = v + w.x_off;
+  if (kStaged) {
+    for (int i = threadIdx.x; i < w.n; i += kJacThreads) vs[i] = vp[i];
+    __syncthreads();
+  }
+  const double* J = jac + w.j_off;
+  const int b0 = rp[w.r0], b1 = rp[w.r1];
+  if (w.is_long) {   // one row of more than a tile: lane 0 adds the tiles' products in column order, then a partial per entry
+    double acc = 0.0;
+    for (int t0 = b0; t0 < b1; t0 += tile) {
+      const int t1 = min(b1, t0 + tile);
+      jac_stream(J, t0, t1, [&](int i, double a) { prod[i] = a * (kStaged ? vs[col[t0 + i]] : vp[col[t0 + i]]); });
+      __syncthreads();
+      if (threadIdx.x == 0)
+        for (int k = 0; k < t1 - t0; ++k) acc += prod[k];
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      if (y) y[w.g_off + w.r0] = acc;
+      vals[0] = wv ? wv[w.g_off + w.r0] * acc : acc;
+    }
+    __syncthreads();
+    const double t = vals[0];
+    double* out = slab + w.slab;
+    jac_stream(J, b0, b1, [&](int i, double a) { out[i] = a * t; });
+    return;
+  }
+  jac_stream(J, b0, b1, [&](int i, double a) {
+    vals[i] = a;
+    prod[i] = a * (kStaged ? vs[col[b0 + i]] : vp[col[b0 + i]]);
+  });
+  __syncthreads();
+  const int r = w.r0 + (int)threadIdx.x;
+  if (r < w.r1) {
+    const int a = rp[r] - b0, b = rp[r + 1] - b0;
+    double acc = 0.0;
+    for (int k = a; k < b; ++k) acc += prod[k];
+    if (y) y[w.g_off + r] = acc;
+    const double t = wv ? wv[w.g_off + r] * acc : acc;
+    for (int k = a; k < b; ++k) vals[k] *= t;
+  }
+  __syncthreads();
+  const uint16_t* map = jac_table<uint16_t>(w.map);
+  const uint16_t* pos = map + w.ncols + 1;
+  for (int j = threadIdx.x; j < w.ncols; j += kJacThreads) {
+    const int a = map[j], b = map[j + 1];
+    double acc = 0.0;
+    for (int i = a; i < b; ++i) acc += vals[pos[i]];
+    slab[w.slab + j] = acc;
+  }
+}
+
+__global__ __launch_bounds__(kJacThreads) void jac_normal_kernel(const JacNormalWork* __restrict__ work, const double* __restrict__ jac,
+                                                                 const double* __restrict__ wv, const double* __restrict__ v,
+                                                                 double* __restrict__ y, double* __restrict__ slab, int lds_x,
+                                                                 int tile) {
+  extern __shared__ double jac_lds[];   // `tile` products, `tile` raw values (the plan's tile), then the problem's v (lds_x doubles)
+  const JacNormalWork w = work[blockIdx.x];
+  if (w.n <= lds_x) jac_normal_block<true>(w, jac, wv, v, y, slab, tile, jac_lds, jac_lds + tile, jac_lds + 2 * tile);
+  else jac_normal_block<false>(w, jac, wv, v, y, slab, tile, jac_lds, jac_lds + tile, nullptr);
+}
+
 // hipLaunchKernel returns the launch's status instead of leaving it in the thread's sticky error slot
 template <typename... P, typename... A>
 inline hipError_t jac_launch(void (*kern)(P...), int grid, int block, size_t lds, hipStream_t stream, A... args) {
@@ -172,6 +246,21 @@ inline hipError_t launch_jac_tmul(const JacTWork* work, int n_work, const JacFol
   hipError_t e = hipSuccess;
   if (n_work > 0) e = jac_launch(jac_tmul_kernel, n_work, kJacThreads, 0, stream, work, jac, w, slab);
   if (e == hipSuccess && n_fold > 0) e = jac_launch(jac_fold_kernel, n_fold, kJacFoldCols, 0, stream, fold, slab, z);
+  return e;
+}
+
+// u = J^T (w o (J v)), y = J v (y NULL: not written; w NULL: unit weights): the one pass, then the fold over its own slab.  With
+// v staged the kernel's LDS passes 64 KB: prepare_jac_normal raises the limit once, on the handle's device, outside any capture.
+inline size_t jac_normal_lds_bytes(int lds_x, int tile) { return sizeof(double) * (2 * (size_t)tile + lds_x); }
+inline hipError_t prepare_jac_normal() {
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(jac_normal_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+}
+inline hipError_t launch_jac_normal(const JacNormalWork* work, int n_work, int lds_x, int tile, const JacFoldWork* fold, int n_fold,
+                                    const double* jac, const double* w, const double* v, double* y, double* slab, double* u,
+                                    hipStream_t stream) {
+  hipError_t e = hipSuccess;
+  if (n_work > 0) e = jac_launch(jac_normal_kernel, n_work, kJacThreads, jac_normal_lds_bytes(lds_x, tile), stream, work, jac, w, v, y, slab, lds_x, tile);
+  if (e == hipSuccess && n_fold > 0) e = jac_launch(jac_fold_kernel, n_fold, kJacFoldCols, 0, stream, fold, slab, u);
   return e;
 }
 

@@ -2488,6 +2488,128 @@ JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::v
   return J;
 }
 
+// ---------------------------------------------------------------- the one-pass normal product (jac_products.hip jac_normal_kernel)
+namespace {
+struct JacNormalTables {   // one distinct pattern: byte offsets into JacNormalPlan::tables, its blocks, partials per problem
+  uint64_t fold_ptr = 0, fold_slot = 0;
+  struct Block {
+    int r0, r1, ncols, is_long;
+    uint64_t map;
+    int64_t slot;   // first partial, relative to the problem's
+  };
+  std::vector<Block> blocks;
+  int64_t slots = 0;
+};
+
+JacNormalTables BuildJacNormalTables(const Structure& S, JacNormalPlan& N, int tile) {
+  const int n = S.n_vars, m = S.n_rows;
+  JacNormalTables P;
+  std::vector<std::vector<int32_t>> slots_of(n);   // the partials of every column, in block order
+  for (int r0 = 0; r0 < m;) {
+    int r1 = r0 + 1;
+    while (r1 < m && r1 - r0 < kJacThreads && S.row_ptr[r1 + 1] - S.row_ptr[r0] <= tile) ++r1;
+    const int k0 = S.row_ptr[r0], k1 = S.row_ptr[r1];
+    if (k1 - k0 > tile) {   // one long row: a partial per entry, in column order
+      for (int k = k0; k < k1; ++k) slots_of[S.col_idx[k]].push_back((int32_t)(P.slots + (k - k0)));
+      P.blocks.push_back({r0, r1, k1 - k0, 1, 0, P.slots});
+      P.slots += k1 - k0;
+    } else if (k1 > k0) {
+      std::vector<std::pair<int, int>> e;   // (column, entry - k0), sorted: the block's columns ascending, each in row order
+      for (int k = k0; k < k1; ++k) e.push_back({S.col_idx[k], k - k0});
+      std::sort(e.begin(), e.end());
+      int ncols = 0;
+      for (size_t i = 0; i < e.size(); ++i) ncols += i == 0 || e[i].first != e[i - 1].first;
+      std::vector<uint16_t> map(ncols + 1 + e.size());
+      int j = -1;
+      for (size_t i = 0; i < e.size(); ++i) {
+        if (i == 0 || e[i].first != e[i - 1].first) {
+          map[++j] = (uint16_t)i;
+          slots_of[e[i].first].push_back((int32_t)(P.slots + j));
+        }
+        map[ncols + 1 + i] = (uint16_t)e[i].second;
+      }
+      map[ncols] = (uint16_t)e.size();
+      P.blocks.push_back({r0, r1, ncols, 0, AppendTable(N.tables, map.data(), map.size()), P.slots});
+      P.slots += ncols;
+    } else {
+      P.blocks.push_back({r0, r1, 0, 0, 0, P.slots});   // rows without entries: y = 0 is still theirs to write
+    }
+    r0 = r1;
+  }
+  std::vector<int32_t> fptr(n + 1, 0), fslot;
+  for (int c = 0; c < n; ++c) {
+    fslot.insert(fslot.end(), slots_of[c].begin(), slots_of[c].end());
+    fptr[c + 1] = (int32_t)fslot.size();
+  }
+  P.fold_ptr = AppendTable(N.tables, fptr.data(), fptr.size());
+  P.fold_slot = AppendTable(N.tables, fslot.data(), fslot.size());
+  return P;
+}
+}  // namespace
+
+void JacNormalPlan::Place(uint64_t ops_base, uint64_t base) {
+  for (auto& w : work) w.col += ops_base, w.row_ptr += ops_base, w.map += base;
+  for (auto& w : fold) w.ptr += base, w.slot += base;
+}
+
+std::vector<JacPatternPlace> JacPatternPlaces(const JacOpsPlan& J, const std::vector<int32_t>& struct_of_problem) {
+  std::vector<JacPatternPlace> at(J.distinct_patterns, JacPatternPlace{-1, 0, 0});
+  size_t k = 0;
+  for (size_t p = 0; p < struct_of_problem.size(); ++p) {   // J.mul is problem by problem; a problem without rows has no record
+    while (k < J.mul.size() && J.mul[k].x_off < J.x_off[p]) ++k;
+    JacPatternPlace& a = at[J.pattern_of_struct[struct_of_problem[p]]];
+    if (a.first_struct >= 0) continue;
+    a.first_struct = struct_of_problem[p];
+    if (k < J.mul.size() && J.mul[k].x_off == J.x_off[p]) a.col = J.mul[k].col, a.row_ptr = J.mul[k].row_ptr;
+  }
+  return at;
+}
+
+JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& patterns, const std::vector<JacPatternPlace>& places,
+                            const std::vector<int32_t>& pattern_of_problem, int tile) {
+  const int n_patterns = (int)patterns.size(), n_problems = (int)pattern_of_problem.size();
+  if (tile < 1 || tile > kJacNormNnz) throw std::runtime_error("the one-pass tile is 1 .. kJacNormNnz entries");
+  if (places.size() != patterns.size()) throw std::runtime_error("one place per pattern");
+  JacNormalPlan N;
+  N.tile = tile;
+  std::vector<JacNormalTables> npats;
+  for (const Structure* S : patterns) {
+    CheckPattern(*S);
+    npats.push_back(BuildJacNormalTables(*S, N, tile));
+  }
+  N.x_off.assign(n_problems + 1, 0);
+  N.g_off.assign(n_problems + 1, 0);
+  N.j_off.assign(n_problems + 1, 0);
+  for (int p = 0; p < n_problems; ++p) {
+    const int q = pattern_of_problem[p];
+    if (q < 0 || q >= n_patterns) throw std::runtime_error("pattern_of_problem out of range");
+    const Structure& S = *patterns[q];
+    const JacNormalTables& Q = npats[q];
+    N.x_off[p + 1] = N.x_off[p] + S.n_vars;
+    N.g_off[p + 1] = N.g_off[p] + S.n_rows;
+    N.j_off[p + 1] = N.j_off[p] + S.nnz;
+    for (const auto& b : Q.blocks)
+      N.work.push_back({N.x_off[p], N.g_off[p], N.j_off[p], N.slab + b.slot, places[q].col, places[q].row_ptr, b.map, b.r0, b.r1,
+                        S.n_vars, b.ncols, b.is_long, 0});
+    for (int c0 = 0; c0 < S.n_vars; c0 += kJacFoldCols)
+      N.fold.push_back({N.x_off[p], N.slab, Q.fold_ptr, Q.fold_slot, c0, std::min(S.n_vars, c0 + kJacFoldCols)});
+    N.slab += Q.slots;
+    if (S.n_vars <= kJacLdsX) N.lds_x = std::max(N.lds_x, S.n_vars);
+  }
+  return N;
+}
+
+JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem, int tile) {
+  const JacOpsPlan J = PlanJacOps(structs, struct_of_problem);   // (checks the patterns and struct_of_problem)
+  const std::vector<JacPatternPlace> places = JacPatternPlaces(J, struct_of_problem);
+  std::vector<const Structure*> patterns(places.size(), nullptr);   // (a pattern no problem has is still a structure's)
+  for (size_t i = 0; i < structs.size(); ++i)
+    if (!patterns[J.pattern_of_struct[i]]) patterns[J.pattern_of_struct[i]] = structs[i];
+  std::vector<int32_t> pattern_of_problem;
+  for (int32_t si : struct_of_problem) pattern_of_problem.push_back(J.pattern_of_struct[si]);
+  return PlanJacNormal(patterns, places, pattern_of_problem, tile);
+}
+
 void JacLsqPlan::Place(uint64_t base) {
   for (auto& w : work) w.lower += base, w.upper += base;
 }
@@ -2549,6 +2671,9 @@ JacLsqPlan PlanJacLsq(const std::vector<const Structure*>& structs, const std::v
   L.ws2_e = 0;
   L.ws2_cp = L.ws2_e + X;
   L.ws2_doubles = L.ws2_cp + X;
+  L.ws3_s = 0;
+  L.ws3_u = L.ws3_s + X;
+  L.ws3_doubles = L.ws3_u + X;
   return L;
 }
 

@@ -320,12 +320,61 @@ struct JacOpsPlan {
 // (structs, struct_of_problem) as for twr_batch_create.  Byte-identical patterns (n, m, row_ptr, col_idx) share one set of tables.
 JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
 
+// The one-pass normal product u = J^T (w o (J v)), y = J v (twr_jac_normal_mul; jac_products.hip jac_normal_kernel), planned on the
+// host (no HIP): a plan of its own next to PlanJacOps, for the same arguments and in the same x / g / jac layout.
+//   Blocks of consecutive WHOLE rows of one problem, at most kJacThreads rows and one tile of entries (kJacNormNnz).  The block's values are
+//   streamed once into LDS, raw and multiplied by v[col]; the lane of a row sums its products in column order (y_r), forms
+//   t_r = w_r y_r and multiplies the row's raw values by it; the column lanes then loop over the block's distinct columns (any
+//   number of them), each summing its column's products in row order (the block's map, of the JacTWork kind) into one partial of
+//   the slab; jac_fold_kernel sums every column's partials in block order (JacFoldWork, exact 0 for a column without entries).
+//   A row of more than kJacNormNnz entries is a block of its own (long = 1): lane 0 sums its products tile by tile in column
+//   order, then the tiles are streamed again and every entry times t_r is a partial of its own (a row's columns are distinct;
+//   no map).
+// The col / row_ptr tables are PlanJacOps's (offsets into JacOpsPlan::tables for the same arguments); the block maps and the
+// fold tables live in `tables` here.  The order of every sum is a function of the pattern alone.
+constexpr int kJacNormNnz = 2048;
+struct JacNormalWork {  // rows [r0, r1) of one problem
+  int64_t x_off, g_off, j_off, slab;   // slab: the block's first partial (its columns' partials follow in map order)
+  uint64_t col, row_ptr;               // the pattern's tables in JacOpsPlan::tables
+  uint64_t map;                        // the block's uint16 lcol_ptr[ncols + 1], then uint16 pos[entries] (entry - row_ptr[r0], per
+                                       // column in row order); unused by a long row
+  int32_t r0, r1, n, ncols, is_long, pad;   // ncols: partials the block writes
+};
+struct JacNormalPlan {
+  std::vector<int64_t> x_off, g_off, j_off;   // n_problems + 1: the layout of PlanJacOps for the same arguments
+  std::vector<char> tables;                   // every distinct pattern's block maps and fold tables, once (16-byte aligned)
+  std::vector<JacNormalWork> work;            // problem by problem, blocks in row order
+  std::vector<JacFoldWork> fold;
+  int64_t slab = 0;                           // partials of one product (doubles)
+  int lds_x = 0;                              // largest n <= kJacLdsX of the batch (the v the kernel stages)
+  int tile = kJacNormNnz;                     // entries of one LDS tile: what the blocks were cut for
+  // col / row_ptr -> addresses in the products' tables (ops_base), maps and fold tables -> addresses in `tables` (base)
+  void Place(uint64_t ops_base, uint64_t base);
+};
+// Where the products' plan J (not yet placed) keeps the col / row_ptr tables of every distinct pattern (byte offsets into
+// J.tables; 0 for a pattern without rows, which has no J v record to read them from), and the first structure that has it.
+struct JacPatternPlace {
+  int32_t first_struct;
+  uint64_t col, row_ptr;
+};
+std::vector<JacPatternPlace> JacPatternPlaces(const JacOpsPlan& J, const std::vector<int32_t>& struct_of_problem);
+// The plan from the distinct patterns (only n_vars, n_rows, nnz, row_ptr and col_idx of a Structure are read), the places of
+// their tables and every problem's pattern: what a twr_jac_ops handle keeps.  tile: entries of one LDS tile, 1 .. kJacNormNnz
+// (kJacNormNnz unless a test wants long rows out of short ones).
+JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& patterns, const std::vector<JacPatternPlace>& places,
+                            const std::vector<int32_t>& pattern_of_problem, int tile = kJacNormNnz);
+// The same from the arguments of PlanJacOps, which it calls for the places: the unplaced JacOpsPlan of these arguments is the
+// one whose tables the work records point into.
+JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem,
+                            int tile = kJacNormNnz);
+
 // The damped weighted least-squares step with a batch's Jacobian (twr_jac_lsq_solve, twr_jac_violation, twr_jac_dot; jac_lsq.hip),
 // planned on the host (no HIP): one work record per problem, the solver's workspace and the per-row bound tables.
 //   workspace (doubles, every segment starts on a 16-byte boundary): p and z in the x layout, q, r and t in the g layout, then
 //   kLsqRec doubles of scalars per problem.  A vector of problem p lives at segment + x_off[p] / g_off[p], as in the batch.
 //   The Marquardt-scaled solve (twr_jac_lsq_solve_scaled) adds two vectors in the x layout, planned as a workspace of their
-//   own (ws2_*) that the handle allocates only when that solve is used.
+//   own (ws2_*) that the handle allocates only when that solve is used; the one-pass solve (twr_jac_lsq_solve_onepass) adds
+//   two more (ws3_*: the recurred s, and u), allocated only when that solve is used.
 //   bounds: per distinct (lower, upper) table lower[m] then upper[m], 16-byte aligned; structures whose tables are
 //   byte-identical share one copy.  These are the structures' own per-row bounds (Structure::lower / upper), any number of
 //   distinct pairs: nothing here reads PackBlob's compact score record.
@@ -351,6 +400,8 @@ struct JacLsqPlan {
   int64_t ws_doubles = 0;                     // the whole workspace
   int64_t ws2_e = 0, ws2_cp = 0;              // the scaled solve's own workspace, a second allocation made on first use
   int64_t ws2_doubles = 0;                    // (twr_jac_lsq_reserve_scaled): e = d / c and c o p in the x layout, segment starts
+  int64_t ws3_s = 0, ws3_u = 0;               // the one-pass solve's own workspace, a third allocation made on first use
+  int64_t ws3_doubles = 0;                    // (twr_jac_lsq_solve_onepass): the recurred s and u = J^T(w o (J p)) in the x layout
   int lds_x = 0;                              // largest n <= kJacLdsX of the batch (the s the direction kernel keeps in LDS)
   void Place(uint64_t base);                  // bound offsets -> device addresses (base: where `bounds` lives)
 };
