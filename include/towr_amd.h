@@ -553,6 +553,74 @@ int twr_jac_lsq_reserve_onepass(twr_jac_lsq* lsq, int scaled);
 int twr_jac_lsq_solve_onepass(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
                               const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream);
 
+/* Variable bounds (new): a bound-constrained Levenberg-Marquardt step and its driver, by projected active-set LM (the way Ceres
+ * and scipy's trf treat boxes).  towr fixes the start state, the final base state and the initial footholds with lo == up and,
+ * with optimised timings, boxes every phase duration (twr_structure_variable_bounds); x + d of the free step leaves all of them.
+ * Here the fixed and the blocked variables are taken out of the solve by an exact zero in the column scale, the trial point is
+ * projected onto the box, and accept / reject and mu are decided per problem on the device.  Same rules as the calls above:
+ * asynchronous and stream-ordered, capturable (kernel launches only), no atomics, every per-problem sum in an order fixed by the
+ * problem's sizes alone (the same bits wherever the problem sits in whatever batch, on every call and stream), a NaN / Inf in
+ * one problem's inputs stays in that problem, NULL / 8-byte alignment checks, one call per handle in flight.
+ *   twr_jac_lsq_solve_masked: the iteration of twr_jac_lsq_solve_scaled (CGLS), where a c_k that is exactly 0 is legal and means
+ *                             "variable k does not move": e_k stays 0, d_k is an exact +0, and |s|, |s0| are taken over the
+ *                             free scaled space.  A c_k that is negative, NaN or Inf stays bad input (status 2).  With no zero
+ *                             in c it returns the bits of twr_jac_lsq_solve_scaled.  Launch sequence, freezing, d_info, status
+ *                             codes and the workspace (twr_jac_lsq_reserve_scaled) as twr_jac_lsq_solve_scaled.
+ *   twr_jac_free_set:         d_scale_out[k] = blocked_k ? +0 : d_scale_in[k] (d_scale_in NULL: 1), with
+ *                             blocked_k = (x_k <= lo_k && z_k <= 0) || (x_k >= up_k && z_k >= 0), z = J^T(w o b) the direction
+ *                             of descent: a variable on a bound that the step would push outwards, and every variable with
+ *                             lo == up that sits on its value.  d_nfree[p] = the number of free variables of problem p (as a
+ *                             double).  x, lo, up, z and the scales are in the x layout; bounds of +-1e20 (ifopt's NoBound)
+ *                             are ordinary numbers.  d_scale_out may be d_scale_in.
+ * The driver, a handle of its own that BORROWS the batch, the twr_jac_lsq and, through it, its twr_jac_ops: all of them must
+ * outlive it and share one layout and device (a mismatch is TWR_ERR_INVALID; NULL arguments are checked before any device is
+ * touched).  It
+ * owns its workspace (twr::PlanJacLm, structure.h); twr_jac_lm_create also reserves the scaled solve's vectors of lsq.
+ *   twr_jac_lm_start: binds the caller's buffers -- d_x (in / out), d_xlo, d_xup (x layout), d_g, d_jac (the caller's, g / jac
+ *                     layout; the linearisation of the last step is left in them) --, projects x onto the box, linearises and
+ *                     sets mu0 = clamp(tau lambda_max(C_f J^T W J C_f)), lambda_max from power_iters power iterations on the
+ *                     device from a fixed start vector (power_iters == 0: mu0 = tau).  A problem whose x holds a NaN, an Inf
+ *                     or a value beyond +-1e20 (ifopt's "no bound": not a number to the NLP), or whose bounds hold a NaN or
+ *                     lo > up, is BAD from here on and its x is not touched, not even projected.
+ *   twr_jac_lm_step:  one step as one chain of launches, no host synchronisation, no scalar to the host, the sequence a function
+ *                     of the parameters alone (capturable after start, k steps as well): eval(BOTH) at x; violation (r, active
+ *                     weights w, merit); b = -r; column norms and the scale c with the running maximum; z = J^T(w o b); free
+ *                     set; masked solve; x_t = min(max(x + d, lo), up); eval(VALUES) at x_t; violation; accept per problem:
+ *                     ok = merit_t < merit (a NaN rejects), x = x_t where ok, mu = clamp(mu mu_down) or clamp(mu mu_up).
+ *                     A problem whose merit at the linearisation is <= merit_done is DONE: x and mu never change again.  A
+ *                     non-finite merit at the linearisation or a solve status 2 makes it BAD: x stays as it is.  The merit
+ *                     a trial is compared with is the recorded one (the first linearisation's, then the accepted trials'),
+ *                     so a problem's recorded merit never rises.  The re-linearisation after a reject is not skipped.
+ *   twr_jac_lm_state: copies the records to d_out (device, TWR_JAC_LM_REC doubles per problem), stream-ordered: merit at start,
+ *                     current merit, mu, steps taken, steps accepted, free variables and CG iterations of the last step taken,
+ *                     state (0 running, 1 done, 2 bad).
+ *   twr_jac_lm_bytes: device bytes the handle owns. */
+#define TWR_JAC_LM_REC 8
+typedef struct twr_jac_lm_params {
+  int32_t cg_iters;      /* 60: the iteration cap of the masked solve */
+  int32_t power_iters;   /* 30 */
+  double cg_tol;         /* 1e-8 */
+  double mu_down;        /* 1/3: mu *= mu_down after an accepted step */
+  double mu_up;          /* 10:  mu *= mu_up after a rejected one */
+  double mu_min, mu_max; /* 1e-16, 1e16: mu is clamped to these, so a problem that keeps rejecting cannot run mu to Inf */
+  double rel_floor;      /* 1e-12: twr_jac_col_scale */
+  double tau;            /* 1e-2 */
+  double merit_done;     /* 0 */
+} twr_jac_lm_params;
+typedef struct twr_jac_lm twr_jac_lm;
+int twr_jac_lm_params_default(twr_jac_lm_params* out);
+int twr_jac_lsq_solve_masked(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
+                             const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream);
+int twr_jac_free_set(twr_jac_lsq* lsq, const double* d_x, const double* d_xlo, const double* d_xup, const double* d_z,
+                     const double* d_scale_in, double* d_scale_out, double* d_nfree, void* hip_stream);
+int twr_jac_lm_create(twr_batch* batch, twr_jac_lsq* lsq, const twr_jac_lm_params* params, twr_jac_lm** out);
+void twr_jac_lm_destroy(twr_jac_lm* lm);
+int twr_jac_lm_bytes(const twr_jac_lm* lm, int64_t* resident);
+int twr_jac_lm_start(twr_jac_lm* lm, double* d_x, const double* d_xlo, const double* d_xup, double* d_g, double* d_jac,
+                     void* hip_stream);
+int twr_jac_lm_step(twr_jac_lm* lm, void* hip_stream);
+int twr_jac_lm_state(twr_jac_lm* lm, double* d_out /* TWR_JAC_LM_REC * n_problems */, void* hip_stream);
+
 /* Tuning knobs.  The DEFAULT build reads nothing from the environment: the values below are compiled in.  A build with
  * -DTWR_TUNING_KNOBS (make -C towr_amd/csrc TUNING=1) reads them, for A/B measurements (scripts/ab.py):
  * TWR_STREAM_NT when a batch is created, TWR_HOST_ZERO_COPY[_X] once per process, the launch knobs (the BPC, FUSED knobs) on

@@ -25,6 +25,15 @@ iteration by twr_jac_normal_mul, the gradient recurred.  It adds
     against 2 * 8 (n + m + nnz) + 8 (8 n + 6 m);
   * lm_onepass (lm_marquardt_onepass): the lm blocks with the one-pass solve, from the same x0.  With onepass alone the CGLS
     blocks are left out.
+--bounds (default off: the output above, unchanged): towr's variable bounds (twr_structure_variable_bounds for the start and goal
+of the guess: 23 base values and 3 per foot fixed, every phase duration boxed with optimised timings).  It adds
+  * to every lm block: fixed_off_max, the largest distance of a fixed variable from its value at the end, and outside_box;
+  * masked: ms per iteration of twr_jac_lsq_solve_masked against twr_jac_lsq_solve_scaled by the protocol of cgls, on the same
+    buffers (the scale of the starting point with its free set's zeros);
+  * lm_box: the Marquardt loop as projected active-set LM, in torch on top of twr_jac_free_set and twr_jac_lsq_solve_masked
+    (free counts per step as well);
+  * with --driver device, lm_box_device: the same loop by twr_jac_lm_start / twr_jac_lm_step, nothing in torch: merits, accepted
+    per step, free counts, states, and ms per step eager and as a replayed hipGraph of one step, next to the torch loop's.
 Usage (each GPU step under its own time limit):
   timeout -k 10 600 python scripts/jac_lsq.py --workload c3 && timeout -k 10 600 python scripts/jac_lsq.py --workload c5
 """
@@ -100,9 +109,30 @@ def timed(torch, f, steps, rounds):
 REL_FLOOR = 1e-12
 
 
-def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver="cgls"):
+def variable_bounds(torch, Q, structs, order):
+    """(lo, up) on the device: twr_structure_variable_bounds of every problem for the start and goal of bench.perturbed_inputs."""
+    per = {}
+    for s in set(order):
+        S, m = structs[s], structs[s].model
+        z = -m.nominal_stance[0][2]
+        ee = [[m.nominal_stance[e][0], m.nominal_stance[e][1], 0.0] for e in range(m.n_ee)]
+        per[s] = S.variable_bounds([0, 0, z] + [0] * 9, [1.0, 0, z] + [0] * 9, ee)
+    lo, up = (np.concatenate([per[s][k] for s in order]) for k in (0, 1))
+    return torch.from_numpy(lo).to(Q.dev), torch.from_numpy(up).to(Q.dev)
+
+
+def box_report(Q, bounds):
+    lo, up = bounds
+    fixed = lo == up
+    return {"fixed_variables": int(fixed.sum()), "fixed_off_max": float((Q.x - lo)[fixed].abs().max()),
+            "outside_box": int(((Q.x < lo) | (Q.x > up))[~fixed].sum())}
+
+
+def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver="cgls", bounds=None, box=False):
     """The LM loop from Q.x (left at the last accepted point).  damping "identity": mu I with the given mu; "marquardt": mu C^-2,
-    mu = 1e-2 lambda_max(C J^T W J C) at the start when None.  solver "onepass": twr_jac_lsq_solve_onepass for the step."""
+    mu = 1e-2 lambda_max(C J^T W J C) at the start when None.  solver "onepass": twr_jac_lsq_solve_onepass for the step.
+    bounds (lo, up): reported on; with box (marquardt, cgls) honoured: projected active-set LM, the restatement of twr_jac_lm_step
+    in torch."""
     st, lsq, ops, batch = Q.st, Q.lsq, Q.ops, Q.batch
     g, r, b, wa, merit, d, info = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(Q.X), Q.vec(4 * Q.P)
     g2, r2, merit2, scores = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.P), Q.vec(16 * Q.P)
@@ -112,6 +142,12 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver
         lsq.reserve_scaled()
     if solver == "onepass":
         lsq.reserve_onepass(scaled)
+    if box:
+        assert scaled and solver == "cgls" and bounds is not None
+        lo, up = bounds
+        Q.x = torch.minimum(torch.maximum(Q.x, lo), up)
+        z, cf, nfree = Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.P)
+        free_counts = torch.zeros(lm_steps, 3, dtype=torch.float64, device=Q.dev)
 
     def linearise():
         batch.eval_device(Q.x.data_ptr(), g.data_ptr(), Q.jac.data_ptr(), ta.EVAL_BOTH, st)
@@ -120,6 +156,11 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver
         if scaled:
             ops.col_sqnorms_device(Q.jac.data_ptr(), colsq.data_ptr(), d_w=wa.data_ptr(), stream=st)
             lsq.col_scale_device(colsq.data_ptr(), c.data_ptr(), REL_FLOOR, d_colsq_max=colmax.data_ptr(), stream=st)
+        if box:
+            t = wa * b
+            ops.tmul_device(Q.jac.data_ptr(), t.data_ptr(), z.data_ptr(), st)
+            lsq.free_set_device(Q.x.data_ptr(), lo.data_ptr(), up.data_ptr(), z.data_ptr(), cf.data_ptr(), nfree.data_ptr(),
+                                d_scale_in=c.data_ptr(), stream=st)
 
     def score_sum():
         batch.eval_scores_device(Q.x.data_ptr(), scores.data_ptr(), d_g=g2.data_ptr(), stream=st)
@@ -127,7 +168,7 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver
 
     linearise()
     if mu is None:
-        mu = 1e-2 * Q.lambda_max(wa, power_iters, c if scaled else None)
+        mu = 1e-2 * Q.lambda_max(wa, power_iters, (cf if box else c) if scaled else None)
     else:
         mu = mu.clone()
     ev = [[torch.cuda.Event(enable_timing=True) for _ in range(4)] for _ in range(lm_steps)]
@@ -141,6 +182,10 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver
         if solver == "onepass":
             lsq.solve_onepass_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), lm_cg_iters, 1e-8,
                                      d_w=wa.data_ptr(), d_scale=c.data_ptr() if scaled else 0, stream=st)
+        elif box:
+            lsq.solve_masked_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), cf.data_ptr(), d.data_ptr(), info.data_ptr(),
+                                    lm_cg_iters, 1e-8, d_w=wa.data_ptr(), stream=st)
+            free_counts[k] = torch.stack([nfree.min(), nfree.median(), nfree.max()])
         elif scaled:
             lsq.solve_scaled_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), c.data_ptr(), d.data_ptr(), info.data_ptr(),
                                     lm_cg_iters, 1e-8, d_w=wa.data_ptr(), stream=st)
@@ -149,6 +194,8 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver
                              d_w=wa.data_ptr(), stream=st)
         ev[k][2].record()
         xt = Q.x + d
+        if box:
+            xt = torch.minimum(torch.maximum(xt, lo), up)
         batch.eval_device(xt.data_ptr(), g2.data_ptr(), 0, ta.EVAL_VALUES, st)
         lsq.violation_device(g2.data_ptr(), r2.data_ptr(), d_merit=merit2.data_ptr(), stream=st)
         ok = merit2 < merit
@@ -167,7 +214,97 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver
                viol_inf_after_min_median_max=[float(v) for v in np.quantile(
                    scores.view(Q.P, 8, 2)[:, :, 0].max(dim=1).values.cpu().numpy(), [0, 0.5, 1])])
     Q.merit_before, Q.merit_after = merit_before, merit.clone()   # per problem, for callers that compare dampings
+    if bounds is not None:
+        res.update(box_report(Q, bounds), ms_step=float(np.median([e[0].elapsed_time(e[3]) for e in ev])))
+    if box:
+        res["free_min_median_max_per_step"] = free_counts.cpu().numpy().tolist()
     return res
+
+
+def lm_device(torch, Q, bounds, a):
+    """The bounded loop by the driver (twr_jac_lm_*): eager steps, then from the same start a captured graph of one step replayed."""
+    lo, up = bounds
+    st = Q.st
+    lm = ta.JacLm(Q.batch, Q.lsq, cg_iters=a.lm_cg_iters, power_iters=a.power_iters)
+    g, rec = Q.vec(Q.G), Q.vec(ta.JacLm.REC * Q.P)
+    x0 = Q.x.clone()
+    F = {k: i for i, k in enumerate(ta.JacLm.FIELDS)}
+
+    def state():
+        lm.state_device(rec.data_ptr(), st)
+        torch.cuda.synchronize()
+        return rec.view(Q.P, -1).clone()
+
+    def start():
+        Q.x.copy_(x0)
+        lm.start_device(Q.x.data_ptr(), lo.data_ptr(), up.data_ptr(), g.data_ptr(), Q.jac.data_ptr(), st)
+
+    def timed_steps(step):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.lm_steps + 1)]
+        acc = []
+        ev[0].record()
+        for k in range(a.lm_steps):
+            step()
+            ev[k + 1].record()
+            lm.state_device(rec.data_ptr(), st)   # stream-ordered copy of the records: no synchronise
+            acc.append(rec.view(Q.P, -1)[:, F["accepted"]].sum().clone())
+        torch.cuda.synchronize()
+        acc = [float(v) for v in acc]
+        return [ev[k].elapsed_time(ev[k + 1]) for k in range(a.lm_steps)], [int(b - c) for b, c in zip(acc, [0.0] + acc[:-1])]
+
+    start()
+    s0 = state()
+    ms_eager, accepted = timed_steps(lambda: lm.step_device(st))
+    s1 = state()
+    x_eager = Q.x.clone()
+    res = {"steps": a.lm_steps, "cg_iters": a.lm_cg_iters, "jac_lm_bytes": lm.bytes()["resident"],
+           "merit_before": float(s0[:, F["merit"]].sum()), "merit_after": float(s1[:, F["merit"]].sum()),
+           "accepted_per_step": accepted, "states_running_done_bad": [int((s1[:, F["state"]] == v).sum()) for v in (0, 1, 2)],
+           "free_min_median_max": [float(v) for v in (s1[:, F["free"]].min(), s1[:, F["free"]].median(), s1[:, F["free"]].max())],
+           "mu0_min_max": [float(s0[:, F["mu"]].min()), float(s0[:, F["mu"]].max())],
+           "ms_step_eager": float(np.median(ms_eager)), **box_report(Q, bounds)}
+    start()
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        lm.step_device(torch.cuda.current_stream().cuda_stream)
+    ms_graph, _ = timed_steps(graph.replay)
+    res.update(ms_step_graph=float(np.median(ms_graph)), graph_bits_equal_eager=bool(torch.equal(Q.x, x_eager)))
+    Q.merit_before, Q.merit_after = s0[:, F["merit"]].clone(), s1[:, F["merit"]].clone()
+    return res
+
+
+def measure_masked(torch, Q, b, wa, mu, a, bounds):
+    """The masked CGLS iteration against the scaled one: same process, same buffers, the protocol of the cgls block."""
+    st, lsq, ops = Q.st, Q.lsq, Q.ops
+    lo, up = bounds
+    colsq, c, cf, z, d, info, nfree = Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(4 * Q.P), Q.vec(Q.P)
+    lsq.reserve_scaled()
+    xp = torch.minimum(torch.maximum(Q.x, lo), up)
+    t = wa * b
+    ops.col_sqnorms_device(Q.jac.data_ptr(), colsq.data_ptr(), d_w=wa.data_ptr(), stream=st)
+    lsq.col_scale_device(colsq.data_ptr(), c.data_ptr(), REL_FLOOR, stream=st)
+    ops.tmul_device(Q.jac.data_ptr(), t.data_ptr(), z.data_ptr(), st)
+    calls = {"free_set": lambda: lsq.free_set_device(xp.data_ptr(), lo.data_ptr(), up.data_ptr(), z.data_ptr(), cf.data_ptr(),
+                                                     nfree.data_ptr(), d_scale_in=c.data_ptr(), stream=st)}
+    for iters in (a.cg_iters, 0):
+        calls["scaled%d" % iters] = lambda iters=iters: lsq.solve_scaled_device(
+            Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), c.data_ptr(), d.data_ptr(), info.data_ptr(), iters, 0.0, d_w=wa.data_ptr(),
+            stream=st)
+        calls["masked%d" % iters] = lambda iters=iters: lsq.solve_masked_device(
+            Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), cf.data_ptr(), d.data_ptr(), info.data_ptr(), iters, 0.0, d_w=wa.data_ptr(),
+            stream=st)
+    for f in calls.values():
+        f()
+        f()
+    torch.cuda.synchronize()
+    t = {k: timed(torch, f, a.steps if k == "free_set" else 2, a.rounds) for k, f in calls.items()}
+    n = a.cg_iters
+    per = {k: (t["%s%d" % (k, n)][0] - t["%s0" % k][0]) / n for k in ("scaled", "masked")}
+    return {"cg_iters": n, "ms_free_set": t["free_set"], "ms_solve_scaled": t["scaled%d" % n], "ms_solve_masked": t["masked%d" % n],
+            "ms_per_scaled_iteration_without_start": per["scaled"], "ms_per_masked_iteration_without_start": per["masked"],
+            "masked_to_scaled": per["masked"] / per["scaled"], "ratio_by_bytes": 1.0,
+            "free_min_max": [float(nfree.min()), float(nfree.max())]}
 
 
 def measure_scaled(torch, Q, b, wa, mu, a):
@@ -297,6 +434,9 @@ def measure(torch, name, structs, order, x_h, a):
 
     # ---- Levenberg-Marquardt
     x0 = Q.x.clone()
+    bounds = variable_bounds(torch, Q, structs, order) if a.bounds else None
+    if a.bounds:
+        out["masked"] = measure_masked(torch, Q, b, wa, mu, a, bounds)
     if cgls and a.damping != "identity":
         out["scaled"] = measure_scaled(torch, Q, b, wa, mu, a)   # J, b, wa still those of x0
     if onepass:
@@ -308,7 +448,13 @@ def measure(torch, name, structs, order, x_h, a):
             if (cgls, onepass)[solver == "onepass"]:
                 Q.x = x0.clone()   # every loop from the same point (a loop leaves Q.x at its last accepted one)
                 out[key + suffix] = lm_loop(torch, Q, damping, mu if damping == "identity" else None, a.lm_steps, a.lm_cg_iters,
-                                            a.power_iters, solver=solver)
+                                            a.power_iters, solver=solver, bounds=bounds)
+    if a.bounds:
+        Q.x = x0.clone()
+        out["lm_box"] = lm_loop(torch, Q, "marquardt", None, a.lm_steps, a.lm_cg_iters, a.power_iters, bounds=bounds, box=True)
+        if a.driver == "device":
+            Q.x = x0.clone()
+            out["lm_box_device"] = lm_device(torch, Q, bounds, a)
     return out
 
 
@@ -324,6 +470,8 @@ def main():
     ap.add_argument("--c3-problems", type=int, default=8192)
     ap.add_argument("--damping", choices=("identity", "marquardt", "both"), default="identity")
     ap.add_argument("--solver", choices=("cgls", "onepass", "both"), default="cgls")
+    ap.add_argument("--bounds", action="store_true", help="honour towr's variable bounds: the masked solve and the bounded LM loop")
+    ap.add_argument("--driver", choices=("torch", "device"), default="torch", help="with --bounds: also run the loop by twr_jac_lm_*")
     ap.add_argument("--normal-tile", type=int, default=0, help="LDS tile of the one-pass product in entries (0: the default, 2048)")
     a = ap.parse_args()
     import torch

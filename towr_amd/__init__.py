@@ -59,6 +59,13 @@ class SetInfo(C.Structure):
                 ("nnz_offset", C.c_int32), ("nnz", C.c_int32)]
 
 
+class JacLmParams(C.Structure):
+    """twr_jac_lm_params"""
+    _fields_ = [("cg_iters", C.c_int32), ("power_iters", C.c_int32), ("cg_tol", C.c_double), ("mu_down", C.c_double),
+                ("mu_up", C.c_double), ("mu_min", C.c_double), ("mu_max", C.c_double), ("rel_floor", C.c_double),
+                ("tau", C.c_double), ("merit_done", C.c_double)]
+
+
 _lib = None
 _dp = C.POINTER(C.c_double)
 
@@ -189,6 +196,16 @@ def lib():
         L.twr_jac_lsq_reserve_onepass.argtypes = [C.c_void_p, C.c_int]
         L.twr_jac_lsq_solve_onepass.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                                 C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_lsq_solve_masked.argtypes = L.twr_jac_lsq_solve_scaled.argtypes
+        L.twr_jac_free_set.argtypes = [C.c_void_p] * 9
+        L.twr_jac_lm_params_default.argtypes = [C.POINTER(JacLmParams)]
+        L.twr_jac_lm_create.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(JacLmParams), C.POINTER(C.c_void_p)]
+        L.twr_jac_lm_destroy.argtypes = [C.c_void_p]
+        L.twr_jac_lm_destroy.restype = None
+        L.twr_jac_lm_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.twr_jac_lm_start.argtypes = [C.c_void_p] * 7
+        L.twr_jac_lm_step.argtypes = [C.c_void_p, C.c_void_p]
+        L.twr_jac_lm_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -726,3 +743,62 @@ class JacLsq:
         _check(lib().twr_jac_lsq_solve_onepass(self._h, C.c_void_p(d_jac), C.c_void_p(d_b), C.c_void_p(d_w), C.c_void_p(d_mu),
                                                C.c_void_p(d_scale), int(iters), float(tol), C.c_void_p(d_d), C.c_void_p(d_info),
                                                C.c_void_p(stream)))
+
+    def solve_masked_device(self, d_jac, d_b, d_mu, d_scale, d_d, d_info, iters, tol, d_w=0, stream=0):
+        """twr_jac_lsq_solve_masked on raw device pointers (ints; d_w 0 = unit weights): solve_scaled_device where a scale of
+        exactly 0 takes its variable out of the solve (d_k = +0); with no zero in d_scale, the bits of solve_scaled_device."""
+        _check(lib().twr_jac_lsq_solve_masked(self._h, C.c_void_p(d_jac), C.c_void_p(d_b), C.c_void_p(d_w), C.c_void_p(d_mu),
+                                              C.c_void_p(d_scale), int(iters), float(tol), C.c_void_p(d_d), C.c_void_p(d_info),
+                                              C.c_void_p(stream)))
+
+    def free_set_device(self, d_x, d_xlo, d_xup, d_z, d_scale_out, d_nfree, d_scale_in=0, stream=0):
+        """twr_jac_free_set on raw device pointers (ints): scale_out = 0 for every variable on a bound that z = J^T(w o b) pushes
+        outwards (every fixed variable on its value), else scale_in (0 = ones); d_nfree[p] = the free count (doubles)."""
+        _check(lib().twr_jac_free_set(self._h, C.c_void_p(d_x), C.c_void_p(d_xlo), C.c_void_p(d_xup), C.c_void_p(d_z),
+                                      C.c_void_p(d_scale_in), C.c_void_p(d_scale_out), C.c_void_p(d_nfree), C.c_void_p(stream)))
+
+
+class JacLm:
+    """The bound-constrained Levenberg-Marquardt driver on the device (twr_jac_lm_*): projected active-set LM on a Batch and a
+    JacLsq of the same layout (both borrowed: they are kept alive here).  Parameters as keywords (twr_jac_lm_params: cg_iters,
+    cg_tol, power_iters, mu_down, mu_up, mu_min, mu_max, rel_floor, tau, merit_done)."""
+
+    REC = 8   # TWR_JAC_LM_REC: doubles per problem of state_device
+    FIELDS = ("merit_start", "merit", "mu", "steps", "accepted", "free", "cg_iters", "state")
+    RUNNING, DONE, BAD = 0, 1, 2
+
+    def __init__(self, batch, jac_lsq, **params):
+        self.batch, self.lsq = batch, jac_lsq
+        self.params = JacLmParams()
+        _check(lib().twr_jac_lm_params_default(C.byref(self.params)))
+        for k, v in params.items():
+            if k not in dict(JacLmParams._fields_):
+                raise TypeError("unknown LM parameter %r" % k)
+            setattr(self.params, k, v)
+        self._h = C.c_void_p()
+        _check(lib().twr_jac_lm_create(batch._h, jac_lsq._h, C.byref(self.params), C.byref(self._h)))
+        self.n_problems = jac_lsq.n_problems
+
+    def __del__(self):
+        if getattr(self, "_h", None) and lib is not None:
+            lib().twr_jac_lm_destroy(self._h)
+            self._h = None
+
+    def bytes(self):
+        r = C.c_int64(0)
+        _check(lib().twr_jac_lm_bytes(self._h, C.byref(r)))
+        return dict(resident=r.value)
+
+    def start_device(self, d_x, d_xlo, d_xup, d_g, d_jac, stream=0):
+        """twr_jac_lm_start on raw device pointers (ints): binds them (they must stay alive while steps are taken), projects x
+        onto the box, linearises and sets mu0."""
+        _check(lib().twr_jac_lm_start(self._h, C.c_void_p(d_x), C.c_void_p(d_xlo), C.c_void_p(d_xup), C.c_void_p(d_g),
+                                      C.c_void_p(d_jac), C.c_void_p(stream)))
+
+    def step_device(self, stream=0):
+        """twr_jac_lm_step: one step, one chain of launches on `stream`, capturable."""
+        _check(lib().twr_jac_lm_step(self._h, C.c_void_p(stream)))
+
+    def state_device(self, d_out, stream=0):
+        """twr_jac_lm_state: REC doubles per problem to d_out (FIELDS)."""
+        _check(lib().twr_jac_lm_state(self._h, C.c_void_p(d_out), C.c_void_p(stream)))

@@ -15,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "jac_lm.hip"
 #include "jac_lsq.hip"
 #include "jac_products.hip"
 #include "launch.h"
@@ -170,6 +171,18 @@ struct twr_jac_lsq {   // twr::PlanJacLsq's work records and bound tables on the
   DevPtr<double> ws3;           // the one-pass solve's vectors (twr_jac_lsq_solve_onepass); resident counts them once they exist
   twr::LsqOnepassBuffers buf3{};
   int64_t ws3_s = 0, ws3_u = 0, ws3_doubles = 0;
+};
+
+struct twr_jac_lm {   // the bounded LM driver: twr::PlanJacLm's workspace, and what twr_jac_lm_start bound
+  twr_batch* batch = nullptr;   // borrowed
+  twr_jac_lsq* lsq = nullptr;   // borrowed (and through it its twr_jac_ops)
+  int device = 0, n_problems = 0;
+  twr_jac_lm_params params{};
+  DevPtr<double> ws;
+  twr::LmBuffers buf{};
+  int64_t resident = 0;
+  double *x = nullptr, *g = nullptr, *jac = nullptr;   // the caller's (twr_jac_lm_start)
+  const double *xlo = nullptr, *xup = nullptr;
 };
 
 namespace {
@@ -1497,6 +1510,219 @@ int twr_jac_lsq_solve_onepass(twr_jac_lsq* lsq, const double* d_jac, const doubl
         return twr::launch_jac_normal(ops->nwork.d.get(), ops->nwork.n, ops->n_lds_x, ops->n_tile, ops->nfold.d.get(), ops->nfold.n, d_jac, d_w, v, y,
                                       ops->nslab.get(), u, stream);
       }));
+}
+
+int twr_jac_lsq_solve_masked(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
+                             const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream) {
+  if (!lsq || !d_jac || !d_b || !d_mu || !d_scale || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
+  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
+  if (misaligned({d_jac, d_b, d_w, d_mu, d_scale, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  if (!lsq->ws2) {
+    const int rc = twr_jac_lsq_reserve_scaled(lsq);
+    if (rc != TWR_OK) return rc;
+  }
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  const twr_jac_ops* ops = lsq->ops;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  return lsq_launched(twr::launch_lsq_solve_scaled(
+      lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, lsq->buf2, d_b, d_w, d_mu, d_scale, iters, tol, d_d, d_info, stream,
+      [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
+      [&](const double* w, double* z) {
+        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
+      },
+      true));
+}
+
+int twr_jac_free_set(twr_jac_lsq* lsq, const double* d_x, const double* d_xlo, const double* d_xup, const double* d_z,
+                     const double* d_scale_in, double* d_scale_out, double* d_nfree, void* hip_stream) {
+  if (!lsq || !d_x || !d_xlo || !d_xup || !d_z || !d_scale_out || !d_nfree) return fail(TWR_ERR_INVALID, "null argument");
+  if (misaligned({d_x, d_xlo, d_xup, d_z, d_scale_in, d_scale_out, d_nfree})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return lsq_launched(twr::launch_lm_free_set(lsq->work.d.get(), lsq->work.n, d_x, d_xlo, d_xup, d_z, d_scale_in, d_scale_out, d_nfree,
+                                              static_cast<hipStream_t>(hip_stream)));
+}
+
+int twr_jac_lm_params_default(twr_jac_lm_params* out) {
+  if (!out) return fail(TWR_ERR_INVALID, "null output");
+  out->cg_iters = 60;
+  out->power_iters = 30;
+  out->cg_tol = 1e-8;
+  out->mu_down = 1.0 / 3.0;
+  out->mu_up = 10.0;
+  out->mu_min = 1e-16;
+  out->mu_max = 1e16;
+  out->rel_floor = 1e-12;
+  out->tau = 1e-2;
+  out->merit_done = 0.0;
+  return TWR_OK;
+}
+
+int twr_jac_lm_create(twr_batch* batch, twr_jac_lsq* lsq, const twr_jac_lm_params* params, twr_jac_lm** out) {
+  if (!batch || !lsq || !params || !out) return fail(TWR_ERR_INVALID, "null argument");
+  const twr_jac_lm_params& q = *params;
+  if (q.cg_iters < 0 || q.power_iters < 0 || !(q.cg_tol >= 0.0) || !(q.mu_down > 0.0 && q.mu_down <= 1.0) || !(q.mu_up >= 1.0) ||
+      !(q.mu_min >= 0.0 && q.mu_min <= q.mu_max) || !std::isfinite(q.mu_up) || !std::isfinite(q.mu_max) ||
+      !(q.rel_floor > 0.0 && q.rel_floor <= 1.0) || !(q.tau > 0.0) || !std::isfinite(q.tau) || q.merit_done != q.merit_done)
+    return fail(TWR_ERR_INVALID, "bad LM parameters");
+  const twr_jac_ops* ops = lsq->ops;
+  if (batch->n_problems != ops->n_problems || batch->plan.x_off != ops->x_off || batch->plan.g_off != ops->g_off ||
+      batch->plan.j_off != ops->j_off)
+    return fail(TWR_ERR_INVALID, "the batch's layout is not the products handle's");
+  if (batch->device != lsq->device) return fail(TWR_ERR_INVALID, "the batch and the solver live on different devices");
+  const int n = batch->n_problems;
+  twr::JacLmPlan plan;   // (from the layout: the plan reads the sizes alone)
+  {
+    std::vector<twr::Structure> sizes(n);
+    std::vector<const twr::Structure*> sp(n);
+    std::vector<int32_t> sop(n);
+    for (int p = 0; p < n; ++p) {
+      sizes[p].n_vars = (int)(ops->x_off[p + 1] - ops->x_off[p]);
+      sizes[p].n_rows = (int)(ops->g_off[p + 1] - ops->g_off[p]);
+      sp[p] = &sizes[p], sop[p] = p;
+    }
+    try {
+      plan = twr::PlanJacLm(sp, sop);
+    } catch (const std::exception& e) {
+      return fail(TWR_ERR_INVALID, e.what());
+    }
+  }
+  if (plan.x_off != ops->x_off || plan.g_off != ops->g_off) return fail(TWR_ERR_INVALID, "the driver's plan does not match the layout");
+  const int rc = twr_jac_lsq_reserve_scaled(lsq);
+  if (rc != TWR_OK) return rc;
+  std::unique_ptr<twr_jac_lm> h(new twr_jac_lm());
+  try {
+    DeviceScope on(lsq->device);
+    TWR_HIP(on.status);
+    h->batch = batch, h->lsq = lsq, h->device = lsq->device, h->n_problems = n, h->params = q;
+    h->ws = dev_zeros<double>(std::max<size_t>(2, (size_t)plan.ws_doubles));
+    double* w = h->ws.get();
+    h->buf = {w + plan.ws_xt, w + plan.ws_d,  w + plan.ws_z,  w + plan.ws_colsq, w + plan.ws_colmax,  w + plan.ws_c,
+              w + plan.ws_cf, w + plan.ws_r,  w + plan.ws_b,  w + plan.ws_wa,    w + plan.ws_gt,      w + plan.ws_rt,
+              w + plan.ws_rec, w + plan.ws_mu, w + plan.ws_merit_t, w + plan.ws_merit_lin, w + plan.ws_nfree, w + plan.ws_info};
+    h->resident = 8 * std::max<int64_t>(2, plan.ws_doubles);
+    *out = h.release();
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    twr_jac_lm_destroy(h.release());
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+void twr_jac_lm_destroy(twr_jac_lm* lm) {
+  if (!lm) return;
+  DeviceScope on(lm->device);
+  delete lm;
+}
+
+int twr_jac_lm_bytes(const twr_jac_lm* lm, int64_t* resident) {
+  if (!lm) return fail(TWR_ERR_INVALID, "null handle");
+  if (resident) *resident = lm->resident;
+  return TWR_OK;
+}
+
+static_assert(TWR_JAC_LM_REC == twr::kLmRec, "the record of twr_jac_lm_state");
+
+namespace {
+twr::LmParams lm_device_params(const twr_jac_lm_params& q) { return {q.mu_down, q.mu_up, q.mu_min, q.mu_max, q.tau, q.merit_done}; }
+
+// eval(BOTH) at x, violation, b = -r, the column norms and the scale with the running maximum, z = J^T(w o b), the free set
+int lm_linearise(twr_jac_lm* lm, int first, hipStream_t stream) {
+  twr_jac_lsq* lsq = lm->lsq;
+  twr_jac_ops* ops = lsq->ops;
+  const twr::LmBuffers& B = lm->buf;
+  const twr::JacLsqWork* work = lsq->work.d.get();
+  const int n = lm->n_problems;
+  int rc = twr_batch_eval(lm->batch, lm->x, lm->g, lm->jac, TWR_EVAL_BOTH, stream);
+  if (rc != TWR_OK) return rc;
+  hipError_t e = twr::launch_lsq_violation(work, n, lm->g, nullptr, B.r, B.wa, B.merit_lin, stream);
+  if (e == hipSuccess)   // (w o b goes to rt, which is free until the trial point's violation)
+    e = twr::jac_launch(twr::lm_rhs_kernel, n, twr::kLsqThreads, 0, stream, work, B.r, B.wa, B.merit_lin, B.b, B.rt, B.rec,
+                        lm->params.merit_done, first);
+  if (e == hipSuccess)
+    e = twr::launch_jac_colsq(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, lm->jac, B.wa, ops->slab.get(), B.colsq, stream);
+  if (e == hipSuccess) e = twr::launch_lsq_col_scale(work, n, B.colsq, B.colmax, lm->params.rel_floor, B.c, stream);
+  if (e == hipSuccess)
+    e = twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, lm->jac, B.rt, ops->slab.get(), B.z, stream);
+  if (e == hipSuccess) e = twr::launch_lm_free_set(work, n, lm->x, lm->xlo, lm->xup, B.z, B.c, B.cf, B.nfree, stream);
+  return lsq_launched(e);
+}
+}  // namespace
+
+int twr_jac_lm_start(twr_jac_lm* lm, double* d_x, const double* d_xlo, const double* d_xup, double* d_g, double* d_jac,
+                     void* hip_stream) {
+  if (!lm || !d_x || !d_xlo || !d_xup || !d_g || !d_jac) return fail(TWR_ERR_INVALID, "null argument");
+  if (misaligned({d_x, d_xlo, d_xup, d_g, d_jac})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(lm->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  lm->x = d_x, lm->xlo = d_xlo, lm->xup = d_xup, lm->g = d_g, lm->jac = d_jac;
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  twr_jac_lsq* lsq = lm->lsq;
+  twr_jac_ops* ops = lsq->ops;
+  const twr::LmBuffers& B = lm->buf;
+  const twr::JacLsqWork* work = lsq->work.d.get();
+  const int n = lm->n_problems, iters = lm->params.power_iters;
+  const twr::LmParams P = lm_device_params(lm->params);
+  // the power iteration borrows d (v), xt (cf o v), z (u) and gt (y)
+  hipError_t e = twr::jac_launch(twr::lm_project_kernel, n, twr::kLsqThreads, 0, stream, work, d_x, d_xlo, d_xup, B.colmax, B.d, B.rec, B.mu,
+                                 lm->params.tau);
+  if (e != hipSuccess) return lsq_launched(e);
+  const int rc = lm_linearise(lm, 1, stream);
+  if (rc != TWR_OK) return rc;
+  e = twr::jac_launch(twr::lm_normalise_kernel, n, twr::kLsqThreads, 0, stream, work, B.cf, B.d, B.z, B.xt, B.rec, B.mu, P, 0, iters == 0);
+  for (int k = 0; k < iters && e == hipSuccess; ++k) {
+    e = twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, B.xt, B.gt, stream);
+    if (e == hipSuccess) e = twr::jac_launch(twr::lm_weight_kernel, n, twr::kLsqThreads, 0, stream, work, B.wa, B.gt);
+    if (e == hipSuccess)
+      e = twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, B.gt, ops->slab.get(), B.z, stream);
+    if (e == hipSuccess)
+      e = twr::jac_launch(twr::lm_normalise_kernel, n, twr::kLsqThreads, 0, stream, work, B.cf, B.d, B.z, B.xt, B.rec, B.mu, P, 1,
+                          k == iters - 1);
+  }
+  return lsq_launched(e);
+}
+
+int twr_jac_lm_step(twr_jac_lm* lm, void* hip_stream) {
+  if (!lm) return fail(TWR_ERR_INVALID, "null handle");
+  if (!lm->x) return fail(TWR_ERR_INVALID, "twr_jac_lm_start has not been called");
+  DeviceScope on(lm->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+  twr_jac_lsq* lsq = lm->lsq;
+  const twr_jac_ops* ops = lsq->ops;
+  const twr::LmBuffers& B = lm->buf;
+  const twr::JacLsqWork* work = lsq->work.d.get();
+  const int n = lm->n_problems;
+  int rc = lm_linearise(lm, 0, stream);
+  if (rc != TWR_OK) return rc;
+  const double* d_jac = lm->jac;
+  hipError_t e = twr::launch_lsq_solve_scaled(
+      work, n, lsq->lds_x, lsq->buf, lsq->buf2, B.b, B.wa, B.mu, B.cf, lm->params.cg_iters, lm->params.cg_tol, B.d, B.info, stream,
+      [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
+      [&](const double* w, double* z) {
+        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
+      },
+      true);
+  if (e == hipSuccess)
+    e = twr::jac_launch(twr::lm_trial_kernel, n, twr::kLsqThreads, 0, stream, work, B.rec, lm->x, B.d, lm->xlo, lm->xup, B.xt);
+  if (e != hipSuccess) return lsq_launched(e);
+  rc = twr_batch_eval(lm->batch, B.xt, B.gt, nullptr, TWR_EVAL_VALUES, stream);
+  if (rc != TWR_OK) return rc;
+  e = twr::launch_lsq_violation(work, n, B.gt, nullptr, B.rt, nullptr, B.merit_t, stream);
+  if (e == hipSuccess)
+    e = twr::jac_launch(twr::lm_accept_kernel, n, twr::kLsqThreads, 0, stream, work, B.rec, B.mu, B.merit_t, B.info, B.nfree, lm->x, B.xt,
+                        lm_device_params(lm->params));
+  return lsq_launched(e);
+}
+
+int twr_jac_lm_state(twr_jac_lm* lm, double* d_out, void* hip_stream) {
+  if (!lm || !d_out) return fail(TWR_ERR_INVALID, "null argument");
+  if (misaligned({d_out})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  DeviceScope on(lm->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return lsq_launched(hipMemcpyAsync(d_out, lm->buf.rec, sizeof(double) * twr::kLmRec * (size_t)lm->n_problems, hipMemcpyDeviceToDevice,
+                                     static_cast<hipStream_t>(hip_stream)));
 }
 
 }  // extern "C"

@@ -254,8 +254,10 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_step_scaled_kernel(const JacL
 // After z = J^T t.  s = z - mu d (kept in LDS when n <= lds_x, else formed again from memory by the same expression), gamma',
 // and the new direction.  first: the start of a solve (d = 0, so s = z), which also checks mu and sets gamma0.
 // SCALED: `d` is e, s = c o z - mu e, and c o p is written to `cp` for J to read; first also counts the c_k that are not
-// positive finite numbers (bad input: status 2).
-template <bool SCALED>
+// positive finite numbers (bad input: status 2).  MASKED (twr_jac_lsq_solve_masked; with SCALED): a c_k that is exactly 0 is legal
+// and takes variable k out of the solve: its s is an exact +0 whatever z holds, so p, e and d = c o e stay +0 and |s| is taken over
+// the free variables; only a negative, NaN or Inf c_k is bad.  The other instantiations are the code they were.
+template <bool SCALED, bool MASKED = false>
 __device__ inline void lsq_dir_body(const JacLsqWork* __restrict__ work, double* __restrict__ rec, const double* __restrict__ mu,
                                     const double* __restrict__ z, const double* __restrict__ d, const double* __restrict__ c,
                                     double* __restrict__ p, double* __restrict__ cp, double* __restrict__ info, double tol2, int first,
@@ -280,6 +282,7 @@ __device__ inline void lsq_dir_body(const JacLsqWork* __restrict__ work, double*
     if constexpr (SCALED) {
       const double2 cv = lsq_ld(cs, i, n, ac);
       zv = make_double2(cv.x * zv.x, cv.y * zv.y);
+      if constexpr (MASKED) zv = make_double2(cv.x == 0.0 ? 0.0 : zv.x, cv.y == 0.0 ? 0.0 : zv.y);
     }
     if (first) return zv;
     const double2 dv = lsq_ld(dp, i, n, ad);
@@ -291,8 +294,13 @@ __device__ inline void lsq_dir_body(const JacLsqWork* __restrict__ work, double*
     if constexpr (SCALED)
       if (first) {
         const double2 cv = lsq_ld(cs, i, n, ac);
-        if (!(cv.x > 0.0) || !lsq_finite(cv.x)) acc[1] += 1.0;
-        if (i + 1 < n && (!(cv.y > 0.0) || !lsq_finite(cv.y))) acc[1] += 1.0;
+        if constexpr (MASKED) {
+          if (!(cv.x >= 0.0) || !lsq_finite(cv.x)) acc[1] += 1.0;
+          if (i + 1 < n && (!(cv.y >= 0.0) || !lsq_finite(cv.y))) acc[1] += 1.0;
+        } else {
+          if (!(cv.x > 0.0) || !lsq_finite(cv.x)) acc[1] += 1.0;
+          if (i + 1 < n && (!(cv.y > 0.0) || !lsq_finite(cv.y))) acc[1] += 1.0;
+        }
       }
     if (staged) {   // the lane reads back what it wrote: no barrier
       lsq_s[i] = sv.x;
@@ -356,6 +364,15 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_dir_scaled_kernel(const JacLs
   extern __shared__ double lsq_s[];   // lds_x doubles
   __shared__ double red[2 * (kLsqThreads / 64)];
   lsq_dir_body<true>(work, rec, mu, z, e, c, p, cp, info, tol2, first, lds_x, lsq_s, red);
+}
+__global__ __launch_bounds__(kLsqThreads) void lsq_dir_masked_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
+                                                                     const double* __restrict__ mu, const double* __restrict__ z,
+                                                                     const double* __restrict__ e, const double* __restrict__ c,
+                                                                     double* __restrict__ p, double* __restrict__ cp,
+                                                                     double* __restrict__ info, double tol2, int first, int lds_x) {
+  extern __shared__ double lsq_s[];   // lds_x doubles
+  __shared__ double red[2 * (kLsqThreads / 64)];
+  lsq_dir_body<true, true>(work, rec, mu, z, e, c, p, cp, info, tol2, first, lds_x, lsq_s, red);
 }
 
 // The one-pass solve (twr_jac_lsq_solve_onepass): the gradient s is recurred, s -= alpha (u + mu p) with u = J^T (w o (J p)) from
@@ -631,25 +648,27 @@ inline hipError_t launch_lsq_col_scale(const JacLsqWork* work, int n, const doub
   return jac_launch(lsq_col_scale_kernel, n, kLsqThreads, 0, stream, work, colsq, colsq_max, rel_floor, scale);
 }
 
-// The same sequence on J C in e = d / c: the product kernels as they are, the vector kernels' SCALED instantiations.
+// The same sequence on J C in e = d / c: the product kernels as they are, the vector kernels' SCALED instantiations.  masked:
+// the direction kernel's MASKED instantiation (twr_jac_lsq_solve_masked); the start and step kernels serve as they are, since
+// p_k = +0 keeps e_k and d_k = c_k e_k at +0.
 template <class Mul, class TMul>
 inline hipError_t launch_lsq_solve_scaled(const JacLsqWork* work, int n, int lds_x, const LsqBuffers& ws, const LsqScaledBuffers& sc,
                                           const double* b, const double* w, const double* mu, const double* c, int iters, double tol,
-                                          double* d, double* info, hipStream_t stream, Mul mul, TMul tmul) {
+                                          double* d, double* info, hipStream_t stream, Mul mul, TMul tmul, bool masked = false) {
   const size_t lds = sizeof(double) * (size_t)lds_x;
   const double tol2 = tol * tol;
+  const auto dir = masked ? lsq_dir_masked_kernel : lsq_dir_scaled_kernel;
   hipError_t e = jac_launch(lsq_start_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, sc.e, ws.r, ws.t);
   if (e == hipSuccess) e = tmul(ws.t, ws.z);
   if (e == hipSuccess)
-    e = jac_launch(lsq_dir_scaled_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 1, lds_x);
+    e = jac_launch(dir, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 1, lds_x);
   for (int k = 0; k < iters && e == hipSuccess; ++k) {
     e = mul(sc.cp, ws.q);
     if (e == hipSuccess)
       e = jac_launch(lsq_step_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.q, w, ws.p, c, sc.e, d, ws.r, ws.t);
     if (e == hipSuccess) e = tmul(ws.t, ws.z);
     if (e == hipSuccess)
-      e = jac_launch(lsq_dir_scaled_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 0,
-                     lds_x);
+      e = jac_launch(dir, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 0, lds_x);
   }
   return e;
 }

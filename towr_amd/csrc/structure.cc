@@ -2677,4 +2677,28 @@ JacLsqPlan PlanJacLsq(const std::vector<const Structure*>& structs, const std::v
   return L;
 }
 
+JacLmPlan PlanJacLm(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem) {
+  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
+  JacLmPlan L;
+  L.x_off.assign(n_problems + 1, 0);
+  L.g_off.assign(n_problems + 1, 0);
+  for (int p = 0; p < n_problems; ++p) {
+    const int si = struct_of_problem[p];
+    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
+    L.x_off[p + 1] = L.x_off[p] + structs[si]->n_vars;
+    L.g_off[p + 1] = L.g_off[p] + structs[si]->n_rows;
+  }
+  const auto even = [](int64_t v) { return (v + 1) / 2 * 2; };
+  const int64_t X = even(L.x_off[n_problems]), G = even(L.g_off[n_problems]), P = even(n_problems);
+  int64_t at = 0;
+  const auto take = [&](int64_t& seg, int64_t len) { seg = at, at += len; };
+  for (int64_t* s : {&L.ws_xt, &L.ws_d, &L.ws_z, &L.ws_colsq, &L.ws_colmax, &L.ws_c, &L.ws_cf}) take(*s, X);
+  for (int64_t* s : {&L.ws_r, &L.ws_b, &L.ws_wa, &L.ws_gt, &L.ws_rt}) take(*s, G);
+  take(L.ws_rec, even((int64_t)kLmRec * n_problems));
+  for (int64_t* s : {&L.ws_mu, &L.ws_merit_t, &L.ws_merit_lin, &L.ws_nfree}) take(*s, P);
+  take(L.ws_info, even((int64_t)4 * n_problems));
+  L.ws_doubles = at;
+  return L;
+}
+
 }  // namespace twr

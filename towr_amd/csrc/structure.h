@@ -407,6 +407,27 @@ struct JacLsqPlan {
 };
 JacLsqPlan PlanJacLsq(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
 
+// The bound-constrained Levenberg-Marquardt driver (twr_jac_lm_*; jac_lm.hip), planned on the host (no HIP): the workspace of a
+// twr_jac_lm handle in the x / g layout of PlanJacLsq for the same arguments (only n_vars and n_rows of a Structure are read).
+//   workspace (doubles, every segment starts on a 16-byte boundary):
+//     x layout: xt (the trial point), d (the step), z = J^T(w o b), colsq, colmax (the running maximum), c (the Marquardt scale),
+//               cf (c with an exact 0 for every fixed / blocked variable);
+//     g layout: r (the violation), b = -r, wa (the active-set weights), gt and rt (values and violation at the trial point);
+//     per problem: kLmRec doubles of state (the record twr_jac_lm_state copies out), mu, the trial merit, the merit of the
+//               linearisation, the free count, the 4 doubles of the solve's info.
+//   The power iteration of twr_jac_lm_start borrows d (v), xt (cf o v), z (u) and gt (y): nothing of its own.
+constexpr int kLmRec = 8;   // the record of a problem: the slots below
+enum { kLmMerit0 = 0, kLmMerit = 1, kLmMu = 2, kLmSteps = 3, kLmAccepted = 4, kLmFree = 5, kLmCgIters = 6, kLmState = 7 };
+constexpr double kLmRunning = 0.0, kLmDone = 1.0, kLmBad = 2.0;   // kLmState
+struct JacLmPlan {
+  std::vector<int64_t> x_off, g_off;   // n_problems + 1: the layout of PlanBatch / PlanJacOps / PlanJacLsq for the same arguments
+  int64_t ws_xt = 0, ws_d = 0, ws_z = 0, ws_colsq = 0, ws_colmax = 0, ws_c = 0, ws_cf = 0;   // segment starts (doubles)
+  int64_t ws_r = 0, ws_b = 0, ws_wa = 0, ws_gt = 0, ws_rt = 0;
+  int64_t ws_rec = 0, ws_mu = 0, ws_merit_t = 0, ws_merit_lin = 0, ws_nfree = 0, ws_info = 0;
+  int64_t ws_doubles = 0;              // the whole workspace
+};
+JacLmPlan PlanJacLm(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
+
 // fpowr GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53): samples while t <= t_total + 1e-5, t accumulated
 int SampleCount(double t_total, double dt);
 void GaitCombo(int n_ee, int combo, double t_total, double swing_scale, twr_schedule* out);
