@@ -36,7 +36,7 @@ extern "C" {
 #define TWR_MAX_PHASES 32
 #define TWR_NAME_LEN 40
 
-enum { TWR_OK = 0, TWR_ERR_INVALID = -1, TWR_ERR_HIP = -2, TWR_ERR_NO_DEVICE = -3, TWR_ERR_INTERNAL = -4 };
+enum { TWR_OK = 0, TWR_ERR_INVALID = -1, TWR_ERR_HIP = -2, TWR_ERR_NO_DEVICE = -3, TWR_ERR_INTERNAL = -4, TWR_ERR_UNSUPPORTED = -5 };
 
 /* RobotModel::Robot (robot_model.h:70-75) */
 enum { TWR_ROBOT_MONOPED = 0, TWR_ROBOT_BIPED, TWR_ROBOT_HYQ, TWR_ROBOT_ANYMAL, TWR_ROBOT_GO1 };
@@ -620,6 +620,67 @@ int twr_jac_lm_start(twr_jac_lm* lm, double* d_x, const double* d_xlo, const dou
                      void* hip_stream);
 int twr_jac_lm_step(twr_jac_lm* lm, void* hip_stream);
 int twr_jac_lm_state(twr_jac_lm* lm, double* d_out /* TWR_JAC_LM_REC * n_problems */, void* hip_stream);
+
+/* The Gram matrix (new): N_p = J_p^T W_p J_p formed ONCE per linearisation and kept, and the damped step solved on it.  The CGLS
+ * calls above read the Jacobian values twice per iteration (once with the one-pass product); N is small (C3: 70 552 stored values
+ * against 102 896 of J) and an iteration of CG on it reads nothing else, so the whole solve is ONE launch with every vector in
+ * LDS.  Where the duration columns are dense (optimised timings with every constraint set) N is larger than 2 nnz J and CGLS
+ * stays the better solve: an alternative the caller picks, no existing call changes.  Planned on the host (structure.h,
+ * twr::PlanJacGram): per distinct pattern the pattern of N = J^T J as FULL symmetric CSR (structural: an explicit zero of J
+ * counts, a column of J without entries is an empty row and column; column indices ascending, 16 bits on the device) and, per
+ * stored entry (i, j) of the lower triangle, the list of its terms (row r, position of J_ri, position of J_rj) in ascending r,
+ * packed in 64 bits; byte-identical patterns are stored once.
+ * LIMITS, checked by twr_jac_ops_reserve_gram (TWR_ERR_UNSUPPORTED, twr_last_error says which): at most 65 536 rows and
+ * 16 777 216 Jacobian entries per problem (16 + 24 + 24 bits of a term), fewer than 2^31 terms per pattern, and at most 3412
+ * variables per problem (the solve keeps six vectors of n doubles in the 160 KiB of LDS one workgroup may have).
+ * The rules of the calls above hold: asynchronous and stream-ordered on hip_stream, capturable in a hipGraph (kernel launches
+ * only) once reserved, at most ONE call per handle in flight, outputs must not overlap inputs, NULL and 8-byte alignment are
+ * checked before any device is touched, no atomics and the order of every sum a function of the pattern alone (a problem's
+ * outputs have the same bits wherever it sits in whatever batch, on every call and stream), a NaN / Inf in one problem's inputs
+ * stays in that problem, and a structure without rows has N = 0 (no stored value) and d = 0 with status 0.
+ *   twr_structure_gram_pattern: host introspection, the pattern of N of one structure: row_ptr[n + 1], col_idx[nnz N].  Any
+ *                             pointer may be NULL; *nnz alone gives the size.
+ *   twr_jac_ops_reserve_gram: plans and uploads the tables and work lists, once; twr_jac_ops_bytes counts them from then on and a
+ *                             handle that never asks holds what it held before.  The calls that need them call it themselves
+ *                             when it has not been called: that one call allocates and can NOT be captured -- reserve first.
+ *   twr_jac_ops_gram_layout:  gram_off[n_problems + 1] (doubles, every start on a 16-byte boundary): the values of N_p are
+ *                             d_gram[gram_off[p] + k], k over the CSR pattern above.  The CALLER owns the value buffer of
+ *                             gram_off[n_problems] doubles, as it owns d_jac: 4.6 GB for 8192 C3 problems.  Needs the reserve.
+ *   twr_jac_gram:             d_gram = J^T W J for every problem (d_w NULL: unit weights, the same bits as weights of 1).  One
+ *                             lane per entry of the lower triangle adds (w_r J_ri) J_rj in ascending r with fused multiply-adds
+ *                             and stores the sum to (i, j) and (j, i): N_ij and N_ji carry the same bits.
+ *   twr_jac_gram_mul:         d_u[x_off[p] + i] = sum_j N_p[i][j] v[x_off[p] + j] (x layout): power iterations, tests.
+ *   twr_jac_lsq_solve_gram:   (C N C + mu I) e = c o z, d = c o e by CG from e = 0, z = J^T (w o b) from the caller
+ *                             (twr_jac_tmul): s = c o z, p = s, gamma = gamma0 = s^T s; repeat u = c o (N (c o p)),
+ *                             delta = p^T u + mu p^T p, alpha = gamma / delta, e += alpha p, s -= alpha (u + mu p),
+ *                             gamma' = s^T s, beta = gamma' / gamma, p = s + beta p.  The gradient s is RECURRED, never formed
+ *                             again from a residual (there is none): it drifts from the true gradient by rounding only, as in
+ *                             twr_jac_lsq_solve_onepass, and d is close to, not bit-identical with, the CGLS calls'.  d_scale
+ *                             NULL: c = 1 (the same bits as a scale of ones).  A c_k that is exactly 0 means "variable k does
+ *                             not move", as in twr_jac_lsq_solve_masked: d_k is an exact +0 and |s|, |s0| are taken over the free
+ *                             space; a negative, NaN or Inf c_k is bad input.  Stopping rule (gamma <= tol^2 gamma0), d_info,
+ *                             status codes 0 / 1 / 2, the bad mu rule, iters == 0 (d = 0 and |s0|) and "a larger iters gives
+ *                             the same bits" as twr_jac_lsq_solve_scaled; on bad input d_info[4p + 1] is sqrt(gamma / gamma0)
+ *                             as it stood: 1 for a bad mu or c with a finite |s0|, or where N holds a NaN (the first delta),
+ *                             NaN where |s0| itself is not finite.  One launch whose shape depends on the batch alone;
+ *                             one workgroup per problem, which ends when its problem stops.  The solve multiplies, then adds
+ *                             (no fused multiply-add), every sum in a stated order (jac_gram.hip): scripts/gram_cpu.py
+ *                             gram_cg_device restates it in numpy bit for bit, the iteration counts included. */
+int twr_structure_gram_pattern(const twr_structure* s, int32_t* row_ptr /* n + 1 */, int32_t* col_idx, int64_t* nnz);
+int twr_jac_ops_reserve_gram(twr_jac_ops* ops);
+int twr_jac_ops_gram_layout(const twr_jac_ops* ops, int64_t* gram_off /* n_problems + 1 */);
+int twr_jac_gram(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_gram, void* hip_stream);
+int twr_jac_gram_mul(twr_jac_ops* ops, const double* d_gram, const double* d_v, double* d_u, void* hip_stream);
+int twr_jac_lsq_solve_gram(twr_jac_lsq* lsq, const double* d_gram, const double* d_z, const double* d_mu, const double* d_scale,
+                           int iters, double tol, double* d_d, double* d_info, void* hip_stream);
+/* The linear solve of the driver: TWR_JAC_LM_CGLS (the default: twr_jac_lsq_solve_masked) or TWR_JAC_LM_GRAM (twr_jac_gram on the
+ * active-set weights, then twr_jac_lsq_solve_gram with the z and the free set of the linearisation; everything else about a
+ * step -- records, DONE / BAD, capture of k steps, no scalar to the host -- is unchanged).  Legal between twr_jac_lm_create and
+ * twr_jac_lm_start (TWR_ERR_INVALID later).  TWR_JAC_LM_GRAM reserves the Gram tables of the borrowed twr_jac_ops
+ * (TWR_ERR_UNSUPPORTED where they have none) and allocates the driver's own N, which twr_jac_lm_bytes counts from then on.
+ * The power iteration of twr_jac_lm_start runs on J with either solver.  twr_jac_lm_params keeps its layout. */
+enum { TWR_JAC_LM_CGLS = 0, TWR_JAC_LM_GRAM = 1 };
+int twr_jac_lm_set_solver(twr_jac_lm* lm, int solver);
 
 /* Tuning knobs.  The DEFAULT build reads nothing from the environment: the values below are compiled in.  A build with
  * -DTWR_TUNING_KNOBS (make -C towr_amd/csrc TUNING=1) reads them, for A/B measurements (scripts/ab.py):

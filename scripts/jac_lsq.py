@@ -34,6 +34,15 @@ of the guess: 23 base values and 3 per foot fixed, every phase duration boxed wi
     (free counts per step as well);
   * with --driver device, lm_box_device: the same loop by twr_jac_lm_start / twr_jac_lm_step, nothing in torch: merits, accepted
     per step, free counts, states, and ms per step eager and as a replayed hipGraph of one step, next to the torch loop's.
+--solver gram (next to cgls, which is timed in the same process on the same buffers): the Gram matrix N = J^T W J formed once
+(twr_jac_gram) and the solve on it in one launch (twr_jac_lsq_solve_gram).  It adds
+  * gram: ms of twr_jac_gram against twr_jac_tmul, of twr_jac_gram_mul, per iteration of the Gram solve against the masked CGLS
+    iteration by the protocol of cgls ((a --lm-cg-iters solve - a 0-iteration solve) / --lm-cg-iters at tol = 0), the whole
+    --lm-cg-iters solve with formation against twr_jac_lsq_solve_masked, the ratio by bytes (8 nnz N + 2 nnz N of column indices
+    against 2 * 8 (n + m + nnz) + 8 (8 n + 6 m)) and what the handles hold; the scale is the starting point's, with its free
+    set's zeros under --bounds.
+--lm-solver gram | both (with --bounds --driver device): lm_box_device_gram, the driver's loop with TWR_JAC_LM_GRAM, next to
+lm_box_device.
 Usage (each GPU step under its own time limit):
   timeout -k 10 600 python scripts/jac_lsq.py --workload c3 && timeout -k 10 600 python scripts/jac_lsq.py --workload c5
 """
@@ -221,11 +230,11 @@ def lm_loop(torch, Q, damping, mu, lm_steps, lm_cg_iters, power_iters=30, solver
     return res
 
 
-def lm_device(torch, Q, bounds, a):
+def lm_device(torch, Q, bounds, a, solver="cgls"):
     """The bounded loop by the driver (twr_jac_lm_*): eager steps, then from the same start a captured graph of one step replayed."""
     lo, up = bounds
     st = Q.st
-    lm = ta.JacLm(Q.batch, Q.lsq, cg_iters=a.lm_cg_iters, power_iters=a.power_iters)
+    lm = ta.JacLm(Q.batch, Q.lsq, solver=solver, cg_iters=a.lm_cg_iters, power_iters=a.power_iters)
     g, rec = Q.vec(Q.G), Q.vec(ta.JacLm.REC * Q.P)
     x0 = Q.x.clone()
     F = {k: i for i, k in enumerate(ta.JacLm.FIELDS)}
@@ -257,7 +266,7 @@ def lm_device(torch, Q, bounds, a):
     ms_eager, accepted = timed_steps(lambda: lm.step_device(st))
     s1 = state()
     x_eager = Q.x.clone()
-    res = {"steps": a.lm_steps, "cg_iters": a.lm_cg_iters, "jac_lm_bytes": lm.bytes()["resident"],
+    res = {"steps": a.lm_steps, "cg_iters": a.lm_cg_iters, "solver": solver, "jac_lm_bytes": lm.bytes()["resident"],
            "merit_before": float(s0[:, F["merit"]].sum()), "merit_after": float(s1[:, F["merit"]].sum()),
            "accepted_per_step": accepted, "states_running_done_bad": [int((s1[:, F["state"]] == v).sum()) for v in (0, 1, 2)],
            "free_min_median_max": [float(v) for v in (s1[:, F["free"]].min(), s1[:, F["free"]].median(), s1[:, F["free"]].max())],
@@ -305,6 +314,76 @@ def measure_masked(torch, Q, b, wa, mu, a, bounds):
             "ms_per_scaled_iteration_without_start": per["scaled"], "ms_per_masked_iteration_without_start": per["masked"],
             "masked_to_scaled": per["masked"] / per["scaled"], "ratio_by_bytes": 1.0,
             "free_min_max": [float(nfree.min()), float(nfree.max())]}
+
+
+def measure_gram(torch, Q, b, wa, mu, a, bounds):
+    """twr_jac_gram, twr_jac_gram_mul and the Gram solve against twr_jac_tmul and the masked CGLS solve: same process, same
+    buffers (J, b, wa of the starting point), the protocol of the cgls block."""
+    st, lsq, ops = Q.st, Q.lsq, Q.ops
+    colsq, c, cf, z, u, d, info, nfree = Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(Q.X), Q.vec(4 * Q.P), Q.vec(Q.P)
+    lsq.reserve_scaled()
+    ops_before = ops.bytes()
+    ops.reserve_gram()
+    gram_off = ops.gram_layout()
+    N = Q.vec(max(2, int(gram_off[-1])))
+    t = wa * b
+    ops.col_sqnorms_device(Q.jac.data_ptr(), colsq.data_ptr(), d_w=wa.data_ptr(), stream=st)
+    lsq.col_scale_device(colsq.data_ptr(), c.data_ptr(), REL_FLOOR, stream=st)
+    ops.tmul_device(Q.jac.data_ptr(), t.data_ptr(), z.data_ptr(), st)
+    if bounds is not None:
+        lo, up = bounds
+        xp = torch.minimum(torch.maximum(Q.x, lo), up)
+        lsq.free_set_device(xp.data_ptr(), lo.data_ptr(), up.data_ptr(), z.data_ptr(), cf.data_ptr(), nfree.data_ptr(),
+                            d_scale_in=c.data_ptr(), stream=st)
+    else:
+        cf.copy_(c)
+    # mu for the system the two solves see, C_f J^T W J C_f (the caller's mu is 1e-2 lambda_max of the unscaled matrix, under which
+    # the scaled system is mu I to rounding and a recurred gradient reaches exactly 0 within a few iterations)
+    mu = 1e-2 * Q.lambda_max(wa, a.power_iters, cf)
+    n = a.lm_cg_iters
+    calls = {"tmul": lambda: ops.tmul_device(Q.jac.data_ptr(), t.data_ptr(), z.data_ptr(), st),
+             "gram": lambda: ops.gram_device(Q.jac.data_ptr(), N.data_ptr(), d_w=wa.data_ptr(), stream=st),
+             "gram_mul": lambda: ops.gram_mul_device(N.data_ptr(), z.data_ptr(), u.data_ptr(), stream=st)}
+    for iters in (n, 0):
+        calls["masked%d" % iters] = lambda iters=iters: lsq.solve_masked_device(
+            Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), cf.data_ptr(), d.data_ptr(), info.data_ptr(), iters, 0.0, d_w=wa.data_ptr(),
+            stream=st)
+        calls["solve_gram%d" % iters] = lambda iters=iters: lsq.solve_gram_device(
+            N.data_ptr(), z.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), iters, 0.0, d_scale=cf.data_ptr(), stream=st)
+    for f in calls.values():
+        f()
+        f()
+    torch.cuda.synchronize()
+    tm = {k: timed(torch, f, a.steps if k in ("tmul", "gram", "gram_mul") else 2, a.rounds) for k, f in calls.items()}
+    per = {k: (tm["%s%d" % (k, n)][0] - tm["%s0" % k][0]) / n for k in ("masked", "solve_gram")}
+    nnz_n = int(np.diff(gram_off).sum())
+    by_gram, by_cgls = 10 * nnz_n, 2 * 8 * (Q.X + Q.G + Q.J) + 8 * (8 * Q.X + 6 * Q.G)
+    res = {"cg_iters": n, "ms_tmul": tm["tmul"], "ms_gram": tm["gram"], "gram_to_tmul": tm["gram"][0] / tm["tmul"][0],
+           "ms_gram_mul": tm["gram_mul"], "ms_solve_masked": tm["masked%d" % n], "ms_solve_gram": tm["solve_gram%d" % n],
+           "ms_solve_gram_start": tm["solve_gram0"], "ms_per_masked_iteration_without_start": per["masked"],
+           "ms_per_gram_iteration_without_start": per["solve_gram"], "gram_to_cgls_iteration": per["solve_gram"] / per["masked"],
+           "bytes_gram_iteration": by_gram, "bytes_cgls_iteration": by_cgls, "ratio_by_bytes": by_gram / by_cgls,
+           "ms_gram_plus_solve": tm["gram"][0] + tm["solve_gram%d" % n][0],
+           "gram_plus_solve_to_masked": (tm["gram"][0] + tm["solve_gram%d" % n][0]) / tm["masked%d" % n][0],
+           "nnz_jac": Q.J, "nnz_gram_padded": nnz_n, "gram_value_bytes": 8 * int(gram_off[-1]),
+           "jac_ops_bytes_before": ops_before["resident"], "jac_ops_bytes_with_gram": ops.bytes()["resident"],
+           "distinct_patterns": ops_before["distinct_patterns"],
+           "mu_scaled_min_max": [float(mu.min()), float(mu.max())]}
+    calls["solve_gram%d" % n]()   # the timed solve again: every problem must have run to the cap, or the times above are not iterations
+    torch.cuda.synchronize()
+    res["gram_iterations_at_tol_0_min_max"] = [float(info.view(-1, 4)[:, 0].min()), float(info.view(-1, 4)[:, 0].max())]
+    for name in ("gram", "masked"):   # what --lm-cg-iters iterations reach at the driver's tol
+        if name == "gram":
+            lsq.solve_gram_device(N.data_ptr(), z.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), n, 1e-8, d_scale=cf.data_ptr(), stream=st)
+        else:
+            lsq.solve_masked_device(Q.jac.data_ptr(), b.data_ptr(), mu.data_ptr(), cf.data_ptr(), d.data_ptr(), info.data_ptr(), n, 1e-8,
+                                    d_w=wa.data_ptr(), stream=st)
+        torch.cuda.synchronize()
+        it = info.view(-1, 4)
+        res["%s_at_tol_1e-8" % name] = {"iterations_min_max": [float(it[:, 0].min()), float(it[:, 0].max())],
+                                        "rel_min_max": [float(it[:, 1].min()), float(it[:, 1].max())],
+                                        "status_counts": [int((it[:, 3] == s).sum()) for s in (0, 1, 2)]}
+    return res
 
 
 def measure_scaled(torch, Q, b, wa, mu, a):
@@ -396,7 +475,7 @@ def measure(torch, name, structs, order, x_h, a):
     b = -r
     lam = Q.lambda_max(wa, a.power_iters)
     mu = 1e-2 * lam
-    cgls, onepass = a.solver != "onepass", a.solver != "cgls"   # which solvers are measured: nothing is run for the other
+    cgls, onepass = a.solver != "onepass", a.solver in ("onepass", "both")   # which solvers are measured: nothing is run for the other
     torch.cuda.synchronize()
     out = {"workload": name, "problems": Q.P, "jac_lsq_bytes": lsq.bytes()["resident"], "jac_ops_bytes": ops.bytes()["resident"],
            "lambda_max": [float(lam.min()), float(lam.max())]}
@@ -441,6 +520,8 @@ def measure(torch, name, structs, order, x_h, a):
         out["scaled"] = measure_scaled(torch, Q, b, wa, mu, a)   # J, b, wa still those of x0
     if onepass:
         out["onepass"] = measure_onepass(torch, Q, b, wa, mu, a, per_iter)
+    if a.solver == "gram":
+        out["gram"] = measure_gram(torch, Q, b, wa, mu, a, bounds)
     for damping, key in (("identity", "lm"), ("marquardt", "lm_marquardt")):
         if a.damping not in (damping, "both"):
             continue
@@ -453,8 +534,12 @@ def measure(torch, name, structs, order, x_h, a):
         Q.x = x0.clone()
         out["lm_box"] = lm_loop(torch, Q, "marquardt", None, a.lm_steps, a.lm_cg_iters, a.power_iters, bounds=bounds, box=True)
         if a.driver == "device":
-            Q.x = x0.clone()
-            out["lm_box_device"] = lm_device(torch, Q, bounds, a)
+            if a.lm_solver in ("cgls", "both"):
+                Q.x = x0.clone()
+                out["lm_box_device"] = lm_device(torch, Q, bounds, a)
+            if a.lm_solver in ("gram", "both"):
+                Q.x = x0.clone()
+                out["lm_box_device_gram"] = lm_device(torch, Q, bounds, a, solver="gram")
     return out
 
 
@@ -469,7 +554,8 @@ def main():
     ap.add_argument("--workload", choices=("c3", "c5", "both"), default="both")
     ap.add_argument("--c3-problems", type=int, default=8192)
     ap.add_argument("--damping", choices=("identity", "marquardt", "both"), default="identity")
-    ap.add_argument("--solver", choices=("cgls", "onepass", "both"), default="cgls")
+    ap.add_argument("--solver", choices=("cgls", "onepass", "both", "gram"), default="cgls")
+    ap.add_argument("--lm-solver", choices=("cgls", "gram", "both"), default="cgls", help="with --driver device: the driver's linear solve")
     ap.add_argument("--bounds", action="store_true", help="honour towr's variable bounds: the masked solve and the bounded LM loop")
     ap.add_argument("--driver", choices=("torch", "device"), default="torch", help="with --bounds: also run the loop by twr_jac_lm_*")
     ap.add_argument("--normal-tile", type=int, default=0, help="LDS tile of the one-pass product in entries (0: the default, 2048)")

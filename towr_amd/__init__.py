@@ -206,6 +206,14 @@ def lib():
         L.twr_jac_lm_start.argtypes = [C.c_void_p] * 7
         L.twr_jac_lm_step.argtypes = [C.c_void_p, C.c_void_p]
         L.twr_jac_lm_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_structure_gram_pattern.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.twr_jac_ops_reserve_gram.argtypes = [C.c_void_p]
+        L.twr_jac_ops_gram_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64)]
+        L.twr_jac_gram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_gram_mul.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_lsq_solve_gram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_jac_lm_set_solver.argtypes = [C.c_void_p, C.c_int]
         _lib = L
     return _lib
 
@@ -428,6 +436,16 @@ class Structure:
         cs = np.zeros(self.nnz, dtype=np.int32)
         _check(lib().twr_structure_transpose(self._h, cp.ctypes.data, ri.ctypes.data, cs.ctypes.data))
         return cp, ri, cs
+
+    def gram_pattern(self):
+        """twr_structure_gram_pattern: the pattern of N = J^T J as full symmetric CSR (row_ptr[n + 1], col_idx[nnz N], columns
+        ascending); structural, so an explicit zero of J counts."""
+        nnz = C.c_int64(0)
+        _check(lib().twr_structure_gram_pattern(self._h, None, None, C.byref(nnz)))
+        rp = np.zeros(self.n + 1, dtype=np.int32)
+        ci = np.zeros(nnz.value, dtype=np.int32)
+        _check(lib().twr_structure_gram_pattern(self._h, rp.ctypes.data, ci.ctypes.data, None))
+        return rp, ci
 
     def sample_count(self, dt=0.01):
         """Records fpowr::GetTrajectory produces for this structure at step dt."""
@@ -669,6 +687,26 @@ class JacOps:
         _check(lib().twr_jac_normal_mul(self._h, C.c_void_p(d_jac), C.c_void_p(d_w), C.c_void_p(d_v), C.c_void_p(d_y), C.c_void_p(d_u),
                                         C.c_void_p(stream)))
 
+    def reserve_gram(self):
+        """twr_jac_ops_reserve_gram: plan and upload the Gram matrix's tables and work lists now (before a hipGraph capture);
+        bytes() counts them from then on.  TowrError -5 (unsupported) for a structure beyond the limits of the tables."""
+        _check(lib().twr_jac_ops_reserve_gram(self._h))
+
+    def gram_layout(self):
+        """twr_jac_ops_gram_layout: gram_off, n_problems + 1 prefix sums (doubles) into the caller's value buffer of N."""
+        go = np.zeros(self.n_problems + 1, dtype=np.int64)
+        _check(lib().twr_jac_ops_gram_layout(self._h, go.ctypes.data_as(C.POINTER(C.c_int64))))
+        return go
+
+    def gram_device(self, d_jac, d_gram, d_w=0, stream=0):
+        """twr_jac_gram on raw device pointers (ints; d_w 0 = unit weights): N = J^T W J of every problem, full symmetric CSR
+        values at gram_layout(); asynchronous on `stream`."""
+        _check(lib().twr_jac_gram(self._h, C.c_void_p(d_jac), C.c_void_p(d_w), C.c_void_p(d_gram), C.c_void_p(stream)))
+
+    def gram_mul_device(self, d_gram, d_v, d_u, stream=0):
+        """twr_jac_gram_mul on raw device pointers (ints): u = N v in the x layout; asynchronous on `stream`."""
+        _check(lib().twr_jac_gram_mul(self._h, C.c_void_p(d_gram), C.c_void_p(d_v), C.c_void_p(d_u), C.c_void_p(stream)))
+
 
 class JacLsq:
     """The damped weighted least-squares step with the Jacobian values of a batch on the device (twr_jac_lsq_*), on top of the
@@ -757,6 +795,13 @@ class JacLsq:
         _check(lib().twr_jac_free_set(self._h, C.c_void_p(d_x), C.c_void_p(d_xlo), C.c_void_p(d_xup), C.c_void_p(d_z),
                                       C.c_void_p(d_scale_in), C.c_void_p(d_scale_out), C.c_void_p(d_nfree), C.c_void_p(stream)))
 
+    def solve_gram_device(self, d_gram, d_z, d_mu, d_d, d_info, iters, tol, d_scale=0, stream=0):
+        """twr_jac_lsq_solve_gram on raw device pointers (ints; d_scale 0 = ones, an exact 0 in it takes its variable out):
+        (C N C + mu I) e = c o z, d = c o e by CG on the Gram matrix of JacOps.gram_device, z = J^T (w o b) from
+        JacOps.tmul_device; the whole solve is one launch.  d_info as solve_device."""
+        _check(lib().twr_jac_lsq_solve_gram(self._h, C.c_void_p(d_gram), C.c_void_p(d_z), C.c_void_p(d_mu), C.c_void_p(d_scale),
+                                            int(iters), float(tol), C.c_void_p(d_d), C.c_void_p(d_info), C.c_void_p(stream)))
+
 
 class JacLm:
     """The bound-constrained Levenberg-Marquardt driver on the device (twr_jac_lm_*): projected active-set LM on a Batch and a
@@ -766,9 +811,12 @@ class JacLm:
     REC = 8   # TWR_JAC_LM_REC: doubles per problem of state_device
     FIELDS = ("merit_start", "merit", "mu", "steps", "accepted", "free", "cg_iters", "state")
     RUNNING, DONE, BAD = 0, 1, 2
+    SOLVERS = {"cgls": 0, "gram": 1}   # TWR_JAC_LM_CGLS, TWR_JAC_LM_GRAM
 
-    def __init__(self, batch, jac_lsq, **params):
-        self.batch, self.lsq = batch, jac_lsq
+    def __init__(self, batch, jac_lsq, solver="cgls", **params):
+        if solver not in self.SOLVERS:
+            raise TypeError("unknown LM solver %r" % (solver,))
+        self.batch, self.lsq, self.solver = batch, jac_lsq, solver
         self.params = JacLmParams()
         _check(lib().twr_jac_lm_params_default(C.byref(self.params)))
         for k, v in params.items():
@@ -778,6 +826,8 @@ class JacLm:
         self._h = C.c_void_p()
         _check(lib().twr_jac_lm_create(batch._h, jac_lsq._h, C.byref(self.params), C.byref(self._h)))
         self.n_problems = jac_lsq.n_problems
+        if solver != "cgls":   # (the default is what twr_jac_lm_create leaves)
+            _check(lib().twr_jac_lm_set_solver(self._h, self.SOLVERS[solver]))
 
     def __del__(self):
         if getattr(self, "_h", None) and lib is not None:

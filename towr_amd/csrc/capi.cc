@@ -15,6 +15,7 @@
 #include <utility>
 #include <vector>
 
+#include "jac_gram.hip"
 #include "jac_lm.hip"
 #include "jac_lsq.hip"
 #include "jac_products.hip"
@@ -138,9 +139,10 @@ struct twr_jac_ops {   // twr::PlanJacOps's tables and work lists on the device,
   DevPtr<double> slab;
   int lds_x = 0, distinct_patterns = 0;
   int64_t resident = 0;
-  // The one-pass product (twr_jac_ops_reserve_normal): planned, uploaded and allocated on first use, from the patterns the
-  // device tables hold (read back then).  Until then the host keeps, per distinct pattern, its sizes and where its col /
-  // row_ptr tables lie (twr::JacPatternPlaces of the plan the handle was made from), and every problem's pattern.
+  // The one-pass product (twr_jac_ops_reserve_normal) and the Gram matrix (twr_jac_ops_reserve_gram): planned, uploaded and
+  // allocated on first use, from the patterns the device tables hold (read back then).  For that the host keeps, per distinct
+  // pattern, its sizes and where its col / row_ptr tables lie (twr::JacPatternPlaces of the plan the handle was made from), and
+  // every problem's pattern.
   struct PatternSizes {
     int32_t n, m, nnz;
   };
@@ -154,6 +156,14 @@ struct twr_jac_ops {   // twr::PlanJacOps's tables and work lists on the device,
   DevList<twr::JacFoldWork> nfold;
   DevPtr<double> nslab;
   int n_lds_x = 0, n_tile = 0;
+  // The Gram matrix (twr_jac_ops_reserve_gram): twr::PlanJacGram's tables and work lists, made from the same patterns
+  bool gram_ready = false;
+  std::vector<int64_t> gram_off;
+  DevPtr<void> gtables;
+  DevList<twr::JacGramWork> gform;
+  DevList<twr::JacGramMulWork> gmul;
+  DevList<twr::JacGramSolveWork> gsolve;
+  int gram_max_n = 0;
 };
 
 struct twr_jac_lsq {   // twr::PlanJacLsq's work records and bound tables on the device, and the solver's workspace
@@ -178,6 +188,8 @@ struct twr_jac_lm {   // the bounded LM driver: twr::PlanJacLm's workspace, and 
   twr_jac_lsq* lsq = nullptr;   // borrowed (and through it its twr_jac_ops)
   int device = 0, n_problems = 0;
   twr_jac_lm_params params{};
+  int solver = TWR_JAC_LM_CGLS;
+  DevPtr<double> gram;          // the driver's own N (twr_jac_lm_set_solver with TWR_JAC_LM_GRAM)
   DevPtr<double> ws;
   twr::LmBuffers buf{};
   int64_t resident = 0;
@@ -1231,14 +1243,10 @@ int twr_jac_col_sqnorms(twr_jac_ops* ops, const double* d_jac, const double* d_w
   return TWR_OK;
 }
 
-int twr_jac_ops_reserve_normal(twr_jac_ops* ops) { return twr_jac_ops_reserve_normal_tile(ops, twr::kJacNormNnz); }
-
-int twr_jac_ops_reserve_normal_tile(twr_jac_ops* ops, int tile_entries) {
-  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
-  if (tile_entries < 1 || tile_entries > twr::kJacNormNnz) return fail(TWR_ERR_INVALID, "the tile is 1 .. 2048 entries");
-  if (ops->normal_ready)
-    return ops->n_tile == tile_entries ? TWR_OK : fail(TWR_ERR_INVALID, "the one-pass tables exist, made for another tile");
-  twr::JacNormalPlan plan;
+namespace {
+// The distinct patterns of a products handle as structures (n_vars, n_rows, nnz, row_ptr, col_idx alone), read back from the
+// tables the device holds: what the plans made after twr_jac_ops_create start from.
+int ops_patterns(twr_jac_ops* ops, std::vector<twr::Structure>* out) {
   std::vector<char> tables(ops->table_bytes);
   try {
     DeviceScope on(ops->device);
@@ -1247,25 +1255,41 @@ int twr_jac_ops_reserve_normal_tile(twr_jac_ops* ops, int tile_entries) {
   } catch (const std::exception& e) {
     return fail(TWR_ERR_HIP, e.what());
   }
-  try {
-    std::vector<twr::Structure> pats(ops->pattern_sizes.size());
-    std::vector<const twr::Structure*> sp;
-    for (size_t q = 0; q < pats.size(); ++q) {
-      const twr_jac_ops::PatternSizes& Z = ops->pattern_sizes[q];
-      const twr::JacPatternPlace& A = ops->pattern_places[q];
-      twr::Structure& S = pats[q];
-      S.n_vars = Z.n, S.n_rows = Z.m, S.nnz = Z.nnz;
-      S.row_ptr.assign(Z.m + 1, 0);
-      S.col_idx.resize(Z.nnz);
-      if (Z.m > 0) {
-        if (A.row_ptr + sizeof(int32_t) * (Z.m + 1) > tables.size() || A.col + sizeof(uint16_t) * Z.nnz > tables.size())
-          throw std::runtime_error("a pattern's tables lie outside the handle's");
-        std::memcpy(S.row_ptr.data(), tables.data() + A.row_ptr, sizeof(int32_t) * (Z.m + 1));
-        const uint16_t* col = reinterpret_cast<const uint16_t*>(tables.data() + A.col);
-        std::copy(col, col + Z.nnz, S.col_idx.begin());
-      }
-      sp.push_back(&S);
+  std::vector<twr::Structure>& pats = *out;
+  pats.assign(ops->pattern_sizes.size(), twr::Structure{});
+  for (size_t q = 0; q < pats.size(); ++q) {
+    const twr_jac_ops::PatternSizes& Z = ops->pattern_sizes[q];
+    const twr::JacPatternPlace& A = ops->pattern_places[q];
+    twr::Structure& S = pats[q];
+    S.n_vars = Z.n, S.n_rows = Z.m, S.nnz = Z.nnz;
+    S.row_ptr.assign(Z.m + 1, 0);
+    S.col_idx.resize(Z.nnz);
+    if (Z.m > 0) {
+      if (A.row_ptr + sizeof(int32_t) * (Z.m + 1) > tables.size() || A.col + sizeof(uint16_t) * Z.nnz > tables.size())
+        return fail(TWR_ERR_INVALID, "a pattern's tables lie outside the handle's");
+      std::memcpy(S.row_ptr.data(), tables.data() + A.row_ptr, sizeof(int32_t) * (Z.m + 1));
+      const uint16_t* col = reinterpret_cast<const uint16_t*>(tables.data() + A.col);
+      std::copy(col, col + Z.nnz, S.col_idx.begin());
     }
+  }
+  return TWR_OK;
+}
+}  // namespace
+
+int twr_jac_ops_reserve_normal(twr_jac_ops* ops) { return twr_jac_ops_reserve_normal_tile(ops, twr::kJacNormNnz); }
+
+int twr_jac_ops_reserve_normal_tile(twr_jac_ops* ops, int tile_entries) {
+  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
+  if (tile_entries < 1 || tile_entries > twr::kJacNormNnz) return fail(TWR_ERR_INVALID, "the tile is 1 .. 2048 entries");
+  if (ops->normal_ready)
+    return ops->n_tile == tile_entries ? TWR_OK : fail(TWR_ERR_INVALID, "the one-pass tables exist, made for another tile");
+  twr::JacNormalPlan plan;
+  std::vector<twr::Structure> pats;
+  int rc = ops_patterns(ops, &pats);
+  if (rc != TWR_OK) return rc;
+  try {
+    std::vector<const twr::Structure*> sp;
+    for (const twr::Structure& S : pats) sp.push_back(&S);
     plan = twr::PlanJacNormal(sp, ops->pattern_places, ops->pattern_of_problem, tile_entries);
     if (plan.x_off != ops->x_off || plan.g_off != ops->g_off || plan.j_off != ops->j_off)
       throw std::runtime_error("the one-pass plan's layout is not the handle's");
@@ -1294,10 +1318,6 @@ int twr_jac_ops_reserve_normal_tile(twr_jac_ops* ops, int tile_entries) {
     ops->resident += (int64_t)tb + (int64_t)(plan.work.size() * sizeof(twr::JacNormalWork) + plan.fold.size() * sizeof(twr::JacFoldWork)) +
                      8 * std::max<int64_t>(1, plan.slab);
     ops->normal_ready = true;
-    ops->pattern_sizes.clear();
-    ops->pattern_places.clear();
-    ops->pattern_of_problem.clear();
-    ops->pattern_of_problem.shrink_to_fit();
     return TWR_OK;
   } catch (const std::exception& e) {
     return fail(TWR_ERR_HIP, e.what());
@@ -1544,6 +1564,114 @@ int twr_jac_free_set(twr_jac_lsq* lsq, const double* d_x, const double* d_xlo, c
                                               static_cast<hipStream_t>(hip_stream)));
 }
 
+int twr_structure_gram_pattern(const twr_structure* s, int32_t* row_ptr, int32_t* col_idx, int64_t* nnz) {
+  if (!s) return fail(TWR_ERR_INVALID, "null structure");
+  try {
+    std::vector<int32_t> rp, ci;
+    twr::GramPattern(s->s, &rp, &ci);
+    if (row_ptr) std::memcpy(row_ptr, rp.data(), rp.size() * sizeof(int32_t));
+    if (col_idx && !ci.empty()) std::memcpy(col_idx, ci.data(), ci.size() * sizeof(int32_t));
+    if (nnz) *nnz = (int64_t)ci.size();
+    return TWR_OK;
+  } catch (const twr::JacGramUnsupported& e) {
+    return fail(TWR_ERR_UNSUPPORTED, e.what());
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+}
+
+int twr_jac_ops_reserve_gram(twr_jac_ops* ops) {
+  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
+  if (ops->gram_ready) return TWR_OK;
+  twr::JacGramPlan plan;
+  std::vector<twr::Structure> pats;
+  const int rc = ops_patterns(ops, &pats);
+  if (rc != TWR_OK) return rc;
+  try {
+    std::vector<const twr::Structure*> sp;
+    for (const twr::Structure& S : pats) sp.push_back(&S);
+    plan = twr::PlanJacGram(sp, ops->pattern_of_problem);
+    if (plan.x_off != ops->x_off || plan.g_off != ops->g_off || plan.j_off != ops->j_off)
+      throw std::runtime_error("the Gram plan's layout is not the handle's");
+  } catch (const twr::JacGramUnsupported& e) {
+    return fail(TWR_ERR_UNSUPPORTED, e.what());
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+  try {
+    DeviceScope on(ops->device);
+    TWR_HIP(on.status);
+    TWR_HIP(twr::prepare_gram_cg());
+    const size_t tb = std::max<size_t>(16, plan.tables.size());
+    DevPtr<void> tables = dev_alloc<void>(tb);
+    if (!plan.tables.empty()) TWR_HIP(hipMemcpy(tables.get(), plan.tables.data(), plan.tables.size(), hipMemcpyHostToDevice));
+    plan.Place(reinterpret_cast<uint64_t>(tables.get()));
+    DevList<twr::JacGramWork> form;
+    DevList<twr::JacGramMulWork> mul;
+    if (!plan.form.empty()) form = upload(plan.form);
+    if (!plan.mul.empty()) mul = upload(plan.mul);
+    ops->gsolve = upload(plan.solve);
+    ops->gtables = std::move(tables);
+    ops->gform = std::move(form);
+    ops->gmul = std::move(mul);
+    ops->gram_off = plan.gram_off;
+    ops->gram_max_n = plan.max_n;
+    ops->resident += (int64_t)tb + (int64_t)(plan.form.size() * sizeof(twr::JacGramWork) + plan.mul.size() * sizeof(twr::JacGramMulWork) +
+                                             plan.solve.size() * sizeof(twr::JacGramSolveWork));
+    ops->gram_ready = true;
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+int twr_jac_ops_gram_layout(const twr_jac_ops* ops, int64_t* gram_off) {
+  if (!ops || !gram_off) return fail(TWR_ERR_INVALID, "null argument");
+  if (!ops->gram_ready) return fail(TWR_ERR_INVALID, "twr_jac_ops_reserve_gram has not been called");
+  std::memcpy(gram_off, ops->gram_off.data(), (ops->n_problems + 1) * sizeof(int64_t));
+  return TWR_OK;
+}
+
+int twr_jac_gram(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_gram, void* hip_stream) {
+  if (!ops || !d_jac || !d_gram) return fail(TWR_ERR_INVALID, "null argument");
+  if (misaligned({d_jac, d_w, d_gram})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  if (!ops->gram_ready) {
+    const int rc = twr_jac_ops_reserve_gram(ops);
+    if (rc != TWR_OK) return rc;
+  }
+  DeviceScope on(ops->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return lsq_launched(twr::launch_jac_gram(ops->gform.d.get(), ops->gform.n, d_jac, d_w, d_gram, static_cast<hipStream_t>(hip_stream)));
+}
+
+int twr_jac_gram_mul(twr_jac_ops* ops, const double* d_gram, const double* d_v, double* d_u, void* hip_stream) {
+  if (!ops || !d_gram || !d_v || !d_u) return fail(TWR_ERR_INVALID, "null argument");
+  if (misaligned({d_gram, d_v, d_u})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  if (!ops->gram_ready) {
+    const int rc = twr_jac_ops_reserve_gram(ops);
+    if (rc != TWR_OK) return rc;
+  }
+  DeviceScope on(ops->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return lsq_launched(twr::launch_jac_gram_mul(ops->gmul.d.get(), ops->gmul.n, d_gram, d_v, d_u, static_cast<hipStream_t>(hip_stream)));
+}
+
+int twr_jac_lsq_solve_gram(twr_jac_lsq* lsq, const double* d_gram, const double* d_z, const double* d_mu, const double* d_scale, int iters,
+                           double tol, double* d_d, double* d_info, void* hip_stream) {
+  if (!lsq || !d_gram || !d_z || !d_mu || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
+  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
+  if (misaligned({d_gram, d_z, d_mu, d_scale, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
+  twr_jac_ops* ops = lsq->ops;
+  if (!ops->gram_ready) {
+    const int rc = twr_jac_ops_reserve_gram(ops);
+    if (rc != TWR_OK) return rc;
+  }
+  DeviceScope on(lsq->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return lsq_launched(twr::launch_gram_cg(ops->gsolve.d.get(), ops->gsolve.n, ops->gram_max_n, d_gram, d_z, d_mu, d_scale, iters, tol, d_d, d_info,
+                                          static_cast<hipStream_t>(hip_stream)));
+}
+
 int twr_jac_lm_params_default(twr_jac_lm_params* out) {
   if (!out) return fail(TWR_ERR_INVALID, "null output");
   out->cg_iters = 60;
@@ -1624,6 +1752,28 @@ int twr_jac_lm_bytes(const twr_jac_lm* lm, int64_t* resident) {
 
 static_assert(TWR_JAC_LM_REC == twr::kLmRec, "the record of twr_jac_lm_state");
 
+int twr_jac_lm_set_solver(twr_jac_lm* lm, int solver) {
+  if (!lm) return fail(TWR_ERR_INVALID, "null handle");
+  if (solver != TWR_JAC_LM_CGLS && solver != TWR_JAC_LM_GRAM) return fail(TWR_ERR_INVALID, "solver is TWR_JAC_LM_CGLS or TWR_JAC_LM_GRAM");
+  if (lm->x) return fail(TWR_ERR_INVALID, "the solver is chosen between twr_jac_lm_create and twr_jac_lm_start");
+  if (solver == TWR_JAC_LM_GRAM && !lm->gram) {
+    twr_jac_ops* ops = lm->lsq->ops;
+    const int rc = twr_jac_ops_reserve_gram(ops);
+    if (rc != TWR_OK) return rc;
+    try {
+      DeviceScope on(lm->device);
+      TWR_HIP(on.status);
+      const int64_t doubles = std::max<int64_t>(2, ops->gram_off.back());
+      lm->gram = dev_zeros<double>((size_t)doubles);
+      lm->resident += 8 * doubles;
+    } catch (const std::exception& e) {
+      return fail(TWR_ERR_HIP, e.what());
+    }
+  }
+  lm->solver = solver;
+  return TWR_OK;
+}
+
 namespace {
 twr::LmParams lm_device_params(const twr_jac_lm_params& q) { return {q.mu_down, q.mu_up, q.mu_min, q.mu_max, q.tau, q.merit_done}; }
 
@@ -1697,13 +1847,21 @@ int twr_jac_lm_step(twr_jac_lm* lm, void* hip_stream) {
   int rc = lm_linearise(lm, 0, stream);
   if (rc != TWR_OK) return rc;
   const double* d_jac = lm->jac;
-  hipError_t e = twr::launch_lsq_solve_scaled(
-      work, n, lsq->lds_x, lsq->buf, lsq->buf2, B.b, B.wa, B.mu, B.cf, lm->params.cg_iters, lm->params.cg_tol, B.d, B.info, stream,
-      [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
-      [&](const double* w, double* z) {
-        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
-      },
-      true);
+  hipError_t e = hipSuccess;
+  if (lm->solver == TWR_JAC_LM_GRAM) {   // N = J^T W_a J once, then the whole masked solve on it in one launch (z is the linearisation's)
+    e = twr::launch_jac_gram(ops->gform.d.get(), ops->gform.n, d_jac, B.wa, lm->gram.get(), stream);
+    if (e == hipSuccess)
+      e = twr::launch_gram_cg(ops->gsolve.d.get(), ops->gsolve.n, ops->gram_max_n, lm->gram.get(), B.z, B.mu, B.cf, lm->params.cg_iters,
+                              lm->params.cg_tol, B.d, B.info, stream);
+  } else {
+    e = twr::launch_lsq_solve_scaled(
+        work, n, lsq->lds_x, lsq->buf, lsq->buf2, B.b, B.wa, B.mu, B.cf, lm->params.cg_iters, lm->params.cg_tol, B.d, B.info, stream,
+        [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
+        [&](const double* w, double* z) {
+          return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
+        },
+        true);
+  }
   if (e == hipSuccess)
     e = twr::jac_launch(twr::lm_trial_kernel, n, twr::kLsqThreads, 0, stream, work, B.rec, lm->x, B.d, lm->xlo, lm->xup, B.xt);
   if (e != hipSuccess) return lsq_launched(e);

@@ -3,13 +3,17 @@
 #include "structure.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstddef>
+#include <cstdint>
 #include <cstring>
+#include <exception>
 #include <limits>
 #include <map>
 #include <numeric>
 #include <stdexcept>
+#include <thread>
 #include <tuple>
 #include <unordered_map>
 
@@ -2608,6 +2612,178 @@ JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& structs, const 
   std::vector<int32_t> pattern_of_problem;
   for (int32_t si : struct_of_problem) pattern_of_problem.push_back(J.pattern_of_struct[si]);
   return PlanJacNormal(patterns, places, pattern_of_problem, tile);
+}
+
+// ---------------------------------------------------------------- the Gram matrix N = J^T W J (jac_gram.hip)
+void GramPattern(const Structure& S, std::vector<int32_t>* row_ptr, std::vector<int32_t>* col_idx) {
+  const CscPattern T = TransposePattern(S);   // (checks the pattern)
+  const int n = S.n_vars;
+  row_ptr->assign(n + 1, 0);
+  col_idx->clear();
+  std::vector<int> stamp(n, -1);
+  std::vector<int32_t> cols;
+  for (int i = 0; i < n; ++i) {   // row i of N: the columns of every row of J that has an entry in column i
+    cols.clear();
+    for (int q = T.col_ptr[i]; q < T.col_ptr[i + 1]; ++q) {
+      const int r = T.row_idx[q];
+      for (int k = S.row_ptr[r]; k < S.row_ptr[r + 1]; ++k) {
+        const int c = S.col_idx[k];
+        if (stamp[c] != i) stamp[c] = i, cols.push_back(c);
+      }
+    }
+    std::sort(cols.begin(), cols.end());
+    if (col_idx->size() + cols.size() > (size_t)INT32_MAX) throw JacGramUnsupported("the Gram matrix has more than 2^31 - 1 entries");
+    col_idx->insert(col_idx->end(), cols.begin(), cols.end());
+    (*row_ptr)[i + 1] = (int32_t)col_idx->size();
+  }
+}
+
+namespace {
+// One pattern's tables, appended to `tables` (offsets into it)
+JacGramPattern BuildGramTables(const Structure& S, std::vector<char>& tables) {
+  const int n = S.n_vars;
+  if (S.n_rows > kGramMaxRows)
+    throw JacGramUnsupported("the Gram tables hold a row of J in 16 bits: " + std::to_string(S.n_rows) + " rows, at most " + std::to_string(kGramMaxRows));
+  if (S.nnz > kGramMaxNnz)
+    throw JacGramUnsupported("the Gram tables hold a position in J in 24 bits: " + std::to_string(S.nnz) + " entries, at most " + std::to_string(kGramMaxNnz));
+  if (n > kGramMaxVars)
+    throw JacGramUnsupported("the Gram solve keeps " + std::to_string(kGramSolveVectors) + " vectors of n doubles in one workgroup's LDS (" +
+                             std::to_string(kGramLdsBytes) + " bytes): " + std::to_string(n) + " variables, at most " + std::to_string(kGramMaxVars));
+  JacGramPattern P;
+  std::vector<int32_t> rp, ci;
+  GramPattern(S, &rp, &ci);
+  const CscPattern T = TransposePattern(S);
+  P.n = n;
+  P.nnz = (int32_t)ci.size();
+  // the lower entries in CSR order, and every one's terms in ascending row
+  std::vector<int32_t> lpos, lmirror;
+  std::vector<std::vector<uint64_t>> terms;
+  std::vector<int32_t> where(n, -1);   // column -> lower entry of the row in hand
+  for (int i = 0; i < n; ++i) {
+    for (int e = rp[i]; e < rp[i + 1] && ci[e] <= i; ++e) {
+      const int j = ci[e];
+      where[j] = (int32_t)lpos.size();
+      lpos.push_back(e);
+      lmirror.push_back((int32_t)(std::lower_bound(ci.begin() + rp[j], ci.begin() + rp[j + 1], i) - ci.begin()));
+      terms.emplace_back();
+    }
+    for (int q = T.col_ptr[i]; q < T.col_ptr[i + 1]; ++q) {
+      const int r = T.row_idx[q];
+      for (int k = S.row_ptr[r]; k < S.row_ptr[r + 1] && S.col_idx[k] <= i; ++k)
+        terms[where[S.col_idx[k]]].push_back((uint64_t)r << 48 | (uint64_t)T.csr_pos[q] << 24 | (uint64_t)k);
+    }
+  }
+  P.lower = (int32_t)lpos.size();
+  std::vector<int32_t> order(P.lower);
+  for (int e = 0; e < P.lower; ++e) order[e] = e;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return terms[a].size() > terms[b].size(); });
+  P.slices = (P.lower + kGramSlice - 1) / kGramSlice;
+  std::vector<int32_t> pos(P.lower), mirror(P.lower), cnt(P.lower), slice_ptr(P.slices + 1, 0);
+  std::vector<uint64_t> words;
+  for (int s = 0; s < P.slices; ++s) {
+    const int e0 = s * kGramSlice, e1 = std::min(P.lower, e0 + kGramSlice);
+    const size_t width = terms[order[e0]].size(), at = words.size();
+    if (at + width * kGramSlice > (size_t)INT32_MAX) throw JacGramUnsupported("the Gram contribution table has more than 2^31 - 1 words");
+    words.resize(at + width * kGramSlice, kGramPad);
+    for (int e = e0; e < e1; ++e) {
+      const std::vector<uint64_t>& t = terms[order[e]];
+      pos[e] = lpos[order[e]], mirror[e] = lmirror[order[e]], cnt[e] = (int32_t)t.size();
+      for (size_t k = 0; k < t.size(); ++k) words[at + k * kGramSlice + (e - e0)] = t[k];
+      P.products += (int64_t)t.size();
+    }
+    slice_ptr[s + 1] = (int32_t)words.size();
+  }
+  P.n_words = (int64_t)words.size();
+  std::vector<uint16_t> col(ci.begin(), ci.end());
+  P.row_ptr = AppendTable(tables, rp.data(), rp.size());
+  P.col = AppendTable(tables, col.data(), col.size());
+  P.pos = AppendTable(tables, pos.data(), pos.size());
+  P.mirror = AppendTable(tables, mirror.data(), mirror.size());
+  P.cnt = AppendTable(tables, cnt.data(), cnt.size());
+  P.slice_ptr = AppendTable(tables, slice_ptr.data(), slice_ptr.size());
+  P.words = AppendTable(tables, words.data(), words.size());
+  return P;
+}
+}  // namespace
+
+void JacGramPlan::Place(uint64_t base) {
+  for (auto& w : form) w.pos += base, w.mirror += base, w.cnt += base, w.slice_ptr += base, w.words += base;
+  for (auto& w : mul) w.row_ptr += base, w.col += base;
+  for (auto& w : solve) w.row_ptr += base, w.col += base;
+}
+
+JacGramPlan PlanJacGram(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem) {
+  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
+  JacGramPlan G;
+  std::vector<const Structure*> first;   // the first structure of every distinct pattern
+  std::unordered_map<uint64_t, std::vector<int>> by_hash;
+  G.pattern_of_struct.resize(n_structs);
+  for (int i = 0; i < n_structs; ++i) {
+    const Structure& S = *structs[i];
+    CheckPattern(S);
+    uint64_t h = HashWords(1469598103934665603ull ^ (uint64_t)S.n_vars, S.row_ptr.data(), S.row_ptr.size() * sizeof(int32_t));
+    h = HashWords(h, S.col_idx.data(), S.col_idx.size() * sizeof(int32_t));
+    std::vector<int>& bucket = by_hash[h];
+    int pid = -1;
+    for (int q : bucket)
+      if (first[q]->n_vars == S.n_vars && first[q]->row_ptr == S.row_ptr && first[q]->col_idx == S.col_idx) pid = q;
+    if (pid < 0) {
+      pid = (int)G.patterns.size();
+      bucket.push_back(pid);
+      first.push_back(&S);
+      G.patterns.emplace_back();
+    }
+    G.pattern_of_struct[i] = pid;
+  }
+  // The distinct patterns are planned side by side (a sweep has a thousand of them at a third of a second each), every one into
+  // tables of its own, which are then laid end to end in pattern order: the plan does not depend on the number of threads.
+  const int n_pat = (int)first.size();
+  std::vector<std::vector<char>> local(n_pat);
+  std::vector<std::exception_ptr> failed(n_pat);
+  std::atomic<int> next{0};
+  const auto worker = [&] {
+    for (int q = next++; q < n_pat; q = next++) {
+      try {
+        G.patterns[q] = BuildGramTables(*first[q], local[q]);
+      } catch (...) {
+        failed[q] = std::current_exception();
+      }
+    }
+  };
+  const int n_threads = std::max(1, std::min({n_pat, kGramPlanThreads, (int)std::thread::hardware_concurrency()}));
+  std::vector<std::thread> pool;
+  for (int t = 1; t < n_threads; ++t) pool.emplace_back(worker);
+  worker();
+  for (std::thread& t : pool) t.join();
+  for (int q = 0; q < n_pat; ++q)
+    if (failed[q]) std::rethrow_exception(failed[q]);   // the first pattern that failed, whatever thread had it
+  for (int q = 0; q < n_pat; ++q) {
+    const uint64_t base = AppendTable(G.tables, local[q].data(), local[q].size());
+    JacGramPattern& P = G.patterns[q];
+    P.row_ptr += base, P.col += base, P.pos += base, P.mirror += base, P.cnt += base, P.slice_ptr += base, P.words += base;
+    std::vector<char>().swap(local[q]);
+  }
+  G.x_off.assign(n_problems + 1, 0);
+  G.g_off.assign(n_problems + 1, 0);
+  G.j_off.assign(n_problems + 1, 0);
+  G.gram_off.assign(n_problems + 1, 0);
+  for (int p = 0; p < n_problems; ++p) {
+    const int si = struct_of_problem[p];
+    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
+    const Structure& S = *structs[si];
+    const JacGramPattern& P = G.patterns[G.pattern_of_struct[si]];
+    G.x_off[p + 1] = G.x_off[p] + S.n_vars;
+    G.g_off[p + 1] = G.g_off[p] + S.n_rows;
+    G.j_off[p + 1] = G.j_off[p] + S.nnz;
+    G.gram_off[p + 1] = G.gram_off[p] + (P.nnz + 1) / 2 * 2;
+    for (int e0 = 0; e0 < P.lower; e0 += kGramThreads)
+      G.form.push_back({G.g_off[p], G.j_off[p], G.gram_off[p], P.pos, P.mirror, P.cnt, P.slice_ptr, P.words, e0, std::min(P.lower, e0 + kGramThreads)});
+    for (int r0 = 0; r0 < S.n_vars; r0 += kGramThreads)
+      G.mul.push_back({G.x_off[p], G.gram_off[p], P.row_ptr, P.col, r0, std::min(S.n_vars, r0 + kGramThreads)});
+    G.solve.push_back({G.x_off[p], G.gram_off[p], P.row_ptr, P.col, S.n_vars, 0});
+    G.max_n = std::max(G.max_n, S.n_vars);
+  }
+  return G;
 }
 
 void JacLsqPlan::Place(uint64_t base) {

@@ -4,6 +4,7 @@
 // SplineHolder and the constraint constructors (see citations in structure.cc).
 #pragma once
 #include <memory>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
@@ -367,6 +368,73 @@ JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& patterns, const
 // one whose tables the work records point into.
 JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem,
                             int tile = kJacNormNnz);
+
+// The Gram matrix N = J^T W J of every problem, formed once and kept (twr_jac_gram, twr_jac_gram_mul, twr_jac_lsq_solve_gram;
+// jac_gram.hip), planned on the host (no HIP) for the arguments of PlanJacOps and in its x / g / jac layout.  Per distinct pattern:
+//   the pattern of N = J^T J as full symmetric CSR -- int32 row_ptr[n + 1], uint16 col[nnz N], columns ascending.  Structural
+//   only: an explicit zero of J counts, a column of J without entries gives an empty row and column.
+//   the contribution table of the LOWER triangle (i >= j; the kernel writes the sum to (i, j) and to (j, i), so both carry the
+//   same bits): the lower entries are sorted by the length of their lists, longest first (ties in CSR order), and cut into
+//   slices of kGramSlice entries, one lane each.  Per sorted entry: int32 pos[] (its place in the problem's values), int32
+//   mirror[] (the place of (j, i); == pos on the diagonal), int32 cnt[] (its terms).  Per slice int32 slice_ptr[]: where its
+//   words start; term t of lane l is word[slice_ptr[s] + t * kGramSlice + l] (lanes of a slice read consecutive words; the
+//   slice is as wide as its first, longest list, shorter lists are padded with kGramPad), terms in ascending row r:
+//       word = r << 48 | position of J_ri in the CSR values << 24 | position of J_rj
+//   hence the limits of the packing: at most kGramMaxRows rows and kGramMaxNnz Jacobian entries per problem.  A lane adds its
+//   terms in table order: the order of every sum is a function of the pattern alone, and no list is split.
+// The values of problem p start at gram_off[p] of one value array (doubles; every start on a 16-byte boundary).
+// The solve keeps six vectors of n doubles and its reduction scratch in one workgroup's LDS (kGramLdsBytes, the most a single
+// workgroup may have on gfx950): at most kGramMaxVars variables per problem.
+// Whatever passes one of these limits makes PlanJacGram throw JacGramUnsupported (TWR_ERR_UNSUPPORTED at the C ABI).
+constexpr int kGramThreads = 256;
+constexpr int kGramSlice = 64;                  // lanes of one slice: a wave
+constexpr int kGramRowLanes = 16;               // lanes that share a row of N in the products
+constexpr int kGramMaxRows = 1 << 16;
+constexpr int kGramMaxNnz = 1 << 24;
+constexpr uint64_t kGramPad = ~0ull;
+constexpr int kGramLdsBytes = 160 * 1024;
+constexpr int kGramSolveVectors = 6;            // e, s, p, c, c o p and N (c o p)
+constexpr int kGramRed = 2 * (kGramThreads / 64);   // doubles of reduction scratch
+constexpr int kGramPlanThreads = 16;              // host threads PlanJacGram plans distinct patterns with, at most
+constexpr int kGramMaxVars = (kGramLdsBytes / 8 - kGramRed) / kGramSolveVectors;
+struct JacGramUnsupported : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
+struct JacGramWork {    // sorted lower entries [e0, e1) of one problem: kGramThreads / kGramSlice slices at most
+  int64_t g_off, j_off, gram_off;
+  uint64_t pos, mirror, cnt, slice_ptr, words;   // the pattern's tables (slice_ptr indexed by e / kGramSlice)
+  int32_t e0, e1;
+};
+struct JacGramMulWork { // rows [r0, r1) of N of one problem
+  int64_t x_off, gram_off;
+  uint64_t row_ptr, col;
+  int32_t r0, r1;
+};
+struct JacGramSolveWork {   // one problem
+  int64_t x_off, gram_off;
+  uint64_t row_ptr, col;
+  int32_t n, pad;
+};
+struct JacGramPattern { // one distinct pattern: byte offsets into JacGramPlan::tables, and its sizes
+  uint64_t row_ptr = 0, col = 0, pos = 0, mirror = 0, cnt = 0, slice_ptr = 0, words = 0;
+  int32_t n = 0, nnz = 0, lower = 0, slices = 0;
+  int64_t n_words = 0, products = 0;            // padded table words; terms of the lower triangle
+};
+struct JacGramPlan {
+  std::vector<int64_t> x_off, g_off, j_off;   // n_problems + 1: the layout of PlanJacOps for the same arguments
+  std::vector<int64_t> gram_off;              // n_problems + 1: into the value array (doubles), every one even
+  std::vector<char> tables;                   // every distinct pattern's tables, once (16-byte aligned)
+  std::vector<JacGramPattern> patterns;
+  std::vector<int32_t> pattern_of_struct;
+  std::vector<JacGramWork> form;              // problem by problem, slices in sorted order
+  std::vector<JacGramMulWork> mul;            // problem by problem, kGramThreads rows each
+  std::vector<JacGramSolveWork> solve;        // one per problem
+  int max_n = 0;                              // the largest n of the batch (sizes the solve's LDS)
+  void Place(uint64_t base);                  // table offsets -> device addresses (base: where `tables` lives)
+};
+JacGramPlan PlanJacGram(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
+// One structure's pattern of N alone (twr_structure_gram_pattern): row_ptr[n + 1], col_idx[nnz N]
+void GramPattern(const Structure& S, std::vector<int32_t>* row_ptr, std::vector<int32_t>* col_idx);
 
 // The damped weighted least-squares step with a batch's Jacobian (twr_jac_lsq_solve, twr_jac_violation, twr_jac_dot; jac_lsq.hip),
 // planned on the host (no HIP): one work record per problem, the solver's workspace and the per-row bound tables.
