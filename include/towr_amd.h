@@ -253,6 +253,11 @@ int twr_batch_table_bytes(const twr_batch* b, int64_t* resident, int64_t* dyn_la
  * 256 MB of output per evaluation: a sweep whose candidates all bring their own tables); the values written are the
  * same bits either way. */
 int twr_batch_streaming_stores(const twr_batch* b);
+/* Slices per problem of the "dynamic" set when every problem of the batch references the same structure with fixed
+ * timings (a uniform batch: many x for one NLP), else 0.  With per-kernel launches (large batches, or profiling events)
+ * such a batch is evaluated by a kernel whose waves each own one slice kind and load its tables once per launch, when the
+ * resident grid divides into the kinds (structure.h DynUniformCols); the values written are the same bits either way. */
+int twr_batch_dyn_uniform_kinds(const twr_batch* b);
 /* Ragged layout of the batch arrays, each n_problems+1 prefix sums in units of doubles:
  * problem p owns x[x_off[p]..x_off[p+1]), g[g_off[p]..), jac[jac_off[p]..). */
 int twr_batch_layout(const twr_batch* b, int64_t* x_off, int64_t* g_off, int64_t* jac_off);

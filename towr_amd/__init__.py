@@ -141,6 +141,7 @@ def lib():
         L.twr_batch_num_problems.argtypes = [C.c_void_p]
         L.twr_batch_table_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.twr_batch_streaming_stores.argtypes = [C.c_void_p]
+        L.twr_batch_dyn_uniform_kinds.argtypes = [C.c_void_p]
         L.twr_batch_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.twr_batch_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.twr_batch_status.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
@@ -505,6 +506,11 @@ class Batch:
     def streaming_stores(self):
         """True when the batch streams its Jacobian values out with non-temporal stores (twr_batch_streaming_stores)."""
         return bool(lib().twr_batch_streaming_stores(self._h))
+
+    def dyn_uniform_kinds(self):
+        """Slices per problem of the "dynamic" set when every problem references one structure with fixed timings (the
+        batch may then run dyn_uniform_kernel), else 0 (twr_batch_dyn_uniform_kinds)."""
+        return int(lib().twr_batch_dyn_uniform_kinds(self._h))
 
     def status(self, stream=0):
         """Per-problem non-finite flags of the last eval_device(..., flags | EVAL_CHECK): bit 0 g, bit 1 jac."""

@@ -658,6 +658,8 @@ int twr_batch_num_problems(const twr_batch* b) { return b ? b->n_problems : 0; }
 
 int twr_batch_streaming_stores(const twr_batch* b) { return b && b->plan.stream_nt ? 1 : 0; }
 
+int twr_batch_dyn_uniform_kinds(const twr_batch* b) { return b ? b->plan.dyn_uniform.s : 0; }
+
 int twr_batch_table_bytes(const twr_batch* b, int64_t* resident, int64_t* dyn_layout, int64_t* dyn_layout_distinct) {
   if (!b) return fail(TWR_ERR_INVALID, "null batch");
   if (resident) *resident = b->table_bytes;
@@ -716,6 +718,7 @@ int twr_batch_eval(twr_batch* b, const double* d_x, double* d_g, double* d_jac, 
   for (int f = 0; f < 4; ++f) s.fam[f] = b->fam[f].n;
   s.rom_max_vals = P.rom_max_vals; s.flat_max_x = P.flat_max_x; s.dyn_map_chunks = P.dyn_map_chunks; s.node_families = P.node_families;
   s.pdyn_img_cap = P.pdyn_img_cap; s.prom_img_cap = P.prom_img_cap; s.stream_nt = P.stream_nt;
+  s.dyn_uniform = P.dyn_uniform;
   s.flags = flags & TWR_EVAL_BOTH;
   s.events = ev != nullptr;
   s.tuning = tuning_knobs();

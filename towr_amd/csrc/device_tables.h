@@ -454,6 +454,34 @@ struct DynWork {          // cnt <= 16 time nodes of "dynamic"
 };
 static_assert(sizeof(DynWork) == 96, "DynWork layout");
 
+// Uniform dyn list (structure.h PlanBatch / PlanEval): every problem of the batch is the SAME structure, so slice `kind` of
+// every problem reads the same records and differs in three offsets that are affine in the problem index.  A wave of
+// dyn_uniform_kernel owns one kind for the whole launch: it loads that kind's records once, from the slice of problem 0 at
+// list position kind * first_stride, and then takes one problem per iteration.  Workgroups are dealt round-robin over the 8
+// XCDs, so workgroup b is wave w = b / 8 of XCD r = b % 8: kind w % s, column c = w / s; in iteration t it evaluates problem
+// r + 8 (t * cols + c) -- all s slices of a problem run on one XCD in the same iteration, as with the interleaved list.
+struct DynUniform {
+  int32_t s;              // slices (kinds) per problem
+  int32_t cols;           // columns: problems one XCD takes per iteration; the grid is 8 * s * cols workgroups
+  int32_t first_stride;   // list positions between two slices of problem 0 (min(8, problems), the interleaved order)
+  int32_t n_problems;
+  int32_t x_stride, g_stride, j_stride;   // doubles between two problems' x, g and Jacobian values
+  int32_t pad;
+};
+static_assert(sizeof(DynUniform) == 32, "DynUniform layout");
+// What workgroup `block` of a uniform launch does: its kind, its first problem and the step between its problems.  first >=
+// n_problems: no work.  (The one definition of the schedule: the kernel and the planner's CPU checks both call it.)
+struct DynUniformSlot {
+  int32_t kind, first, step;
+};
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline DynUniformSlot dyn_uniform_slot(const DynUniform& u, int block) {
+  const int r = block & 7, w = block >> 3;
+  return DynUniformSlot{w % u.s, r + 8 * (w / u.s), 8 * u.cols};
+}
+
 struct RomWork {          // cnt <= 64 time nodes of "rangeofmotion-<ee>"
   uint64_t nodes;         // RomNode[k0..]
   uint64_t segs;          // RomSeg[] of this slice

@@ -5,6 +5,8 @@
 // A dyn/rom workgroup is one wavefront (64 lanes); it walks a strided list of work items, each one a
 // *contiguous* slice of one problem's CSR value array:
 //   dyn_kernel   dynamic           : <= 16 consecutive time nodes k, FOUR lanes per node (6 rows each)
+//   dyn_uniform_kernel             : the same for a batch whose problems all share one structure: a wave owns one slice
+//                                    kind, loads its records once and walks problems (device_tables.h DynUniform)
 //   rom_kernel   rangeofmotion-ee  : lanes = consecutive time nodes k               (3 rows each)
 //   node_kernel  terrain-* / force-* / splineacc-base-* / swing-* (+ totalduration-*) of one problem:
 //                four waves, one per family, lanes = spline nodes / rows (node_kernel2: the first two families only)
@@ -1185,6 +1187,110 @@ __global__ __launch_bounds__(64, TWR_DYN_WAVES) void dyn_kernel(const DynWork* _
                                                     double* __restrict__ g, double* __restrict__ jac, double* __restrict__ dump) {
   __shared__ __attribute__((aligned(16))) double stage[kDynLds];
   dyn_body<WANT_G, WANT_J, XC, NT>(work, n_work, x, g, jac, dump, stage, threadIdx.x, blockIdx.x, gridDim.x);
+}
+
+// ---------------------------------------------------------------- dynamic, uniform list (dyn_uniform_kernel)
+// Every problem of the batch is the same structure (device_tables.h DynUniform): the wave owns ONE slice kind, loads that
+// kind's DynWork, selector, staging map, front records and tile codes once, before the loop, and then walks problems, not
+// list positions.  Per iteration it gathers x of the problem after next, as dyn_body does, and forms the three offsets
+// from the problem index; the 20 record loads of a dyn_body iteration (two of them dependent) are gone.  Same phases F O B
+// S, the same single call sites of dyn2_front / dyn2_back / copy_out_fixed, the same clamped unconditional x prefetch and
+// a constant count of vector-memory instructions per iteration.  Nothing of the image is kept from slice to slice: every
+// value is recomputed and rewritten.
+// Results are bit-identical to dyn_body's: the records pass through an empty asm at the top of every iteration, so the
+// compiler sees fresh values there, exactly as after dyn_body's loads, and hoists no arithmetic on them out of the loop
+// (a product of two record constants computed ahead of the loop could no longer contract into the FMA it forms in dyn_body).
+TWR_DEV void dyn_fresh(double& v) { asm volatile("" : "+v"(v)); }
+TWR_DEV void dyn_fresh(uint32_t& v) { asm volatile("" : "+v"(v)); }
+template <bool WANT_G, bool WANT_J, int XC, bool NT>
+TWR_DEV void dyn_uniform_body(const DynWork* __restrict__ work, const DynUniform u, const double* __restrict__ x,
+                              double* __restrict__ g, double* __restrict__ jac, double* __restrict__ dump, double* stage, int lane,
+                              int block) {
+  static_assert(XC == 2 || XC == 4, "staging map chunks");
+  constexpr int kG0 = WANT_J ? kDynG0 : 0, kX0 = kG0 + 96;
+  double* gst = stage + kG0;
+  char* xs = reinterpret_cast<char*>(stage + kX0);
+  const DynUniformSlot sl = dyn_uniform_slot(u, block);
+  if (sl.first >= u.n_problems) return;
+  constexpr int NIT = (kDynImage + 2 + 127) / 128;
+  if (lane < 2) stage[kX0 + lane] = 0.0;   // the zero pair
+  DynWork wt = work[sl.kind * u.first_stride];   // this kind's slice of problem 0
+  uint2 mapr;
+  if (XC == 4) mapr = gptr<uint2>(wt.map)[lane];
+  else mapr = make_uint2(gptr<uint32_t>(wt.map)[lane], 0u);
+  auto gather_x = [&](int p, double xr[XC]) {
+    const double* xp = x + wt.x_off + (int64_t)p * u.x_stride;
+    xr[0] = xp[mapr.x & 0xFFFFu];
+    xr[1] = xp[mapr.x >> 16];
+    if (XC == 4) {
+      xr[XC - 2] = xp[mapr.y & 0xFFFFu];
+      xr[XC - 1] = xp[mapr.y >> 16];
+    }
+  };
+  auto stage_x = [&](const double xr[XC]) {
+#pragma unroll
+    for (int c = 0; c < XC; ++c)
+      if (64 * c + lane < kDynXsCap) stage[kX0 + 2 + 64 * c + lane] = xr[c];
+  };
+  auto copy_out = [&](double* pdst, double* pg) {   // (as in dyn_body; the kind's value and node counts)
+    const int ppar = (int)((reinterpret_cast<uintptr_t>(pdst) >> 3) & 1);
+    if (WANT_J) copy_out_fixed<NIT, NT ? 2 : kDynCopyBatch, NT>(pdst, stage, wt.nvals, ppar, lane);
+    if (WANT_G) {
+      const int last = 6 * wt.cnt - 1;
+      pg[min(lane, last)] = gst[min(lane, last)];
+      pg[min(lane + 64, last)] = gst[min(lane + 64, last)];
+    }
+  };
+  const int plast = sl.first + (u.n_problems - 1 - sl.first) / sl.step * sl.step;   // this wave's last problem
+  const uint32_t sel = dyn2_load_sel(wt, lane);
+  DynFrontRec fr;
+  dyn2_load_front(wt, sel, lane, fr);
+  DynCodes cd;
+  dyn2_load_codes(wt, sel, cd);
+  double xr[XC];
+  gather_x(sl.first, xr);
+  stage_x(xr);                                           // x(first problem): the only exposed gather
+  gather_x(min(sl.first + sl.step, plast), xr);
+  double* pdst = dump;                                   // (first iteration: nothing pending, same instruction count)
+  double* pg = dump + kDynImage + 2;
+  for (int p = sl.first; p <= plast; p += sl.step) {
+    // (in place: the records stay in the registers they were loaded into, no copies)
+    asm volatile("" : "+s"(wt.hdr));
+    dyn_fresh(fr.nd.t); dyn_fresh(fr.nd.tb); dyn_fresh(fr.nd.iTb);
+    dyn_fresh(fr.t0m); dyn_fresh(fr.iTm); dyn_fresh(fr.t0f); dyn_fresh(fr.iTf);
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+      dyn_fresh(fr.relm[q]); dyn_fresh(fr.presm[q]); dyn_fresh(fr.relf[q]); dyn_fresh(fr.presf[q]);
+    }
+    dyn_fresh(fr.flagsm); dyn_fresh(fr.flagsf);
+#pragma unroll
+    for (int q = 0; q < 5; ++q) dyn_fresh(fr.tl[q]);
+#pragma unroll
+    for (int q = 0; q < 6; ++q) dyn_fresh(cd.m[q]);
+#pragma unroll
+    for (int q = 0; q < 9; ++q) dyn_fresh(cd.f[q]);
+    double* dst = jac + wt.j_off + (int64_t)p * u.j_stride;
+    const int par = (int)((reinterpret_cast<uintptr_t>(dst) >> 3) & 1);
+    Dyn2Front S;
+    dyn2_front(fr, xs, lane, S);                                                             // F
+    __builtin_amdgcn_s_setprio(3);
+    copy_out(pdst, pg);                                                                      // O
+    __builtin_amdgcn_s_setprio(0);
+    dyn2_back(wt, fr, cd, S, gst, reinterpret_cast<char*>(stage + par), lane, WANT_G, WANT_J);    // B
+    stage_x(xr);                                                                             // S
+    gather_x(min(p + 2 * sl.step, plast), xr);
+    pdst = dst;
+    pg = g + wt.g_off + (int64_t)p * u.g_stride;
+  }
+  copy_out(pdst, pg);                                    // last problem of this wave
+}
+
+template <bool WANT_G, bool WANT_J, int XC, bool NT>
+__global__ __launch_bounds__(64, TWR_DYN_WAVES) void dyn_uniform_kernel(const DynWork* __restrict__ work, const DynUniform u,
+                                                                        const double* __restrict__ x, double* __restrict__ g,
+                                                                        double* __restrict__ jac, double* __restrict__ dump) {
+  __shared__ __attribute__((aligned(16))) double stage[kDynLds];
+  dyn_uniform_body<WANT_G, WANT_J, XC, NT>(work, u, x, g, jac, dump, stage, threadIdx.x, blockIdx.x);
 }
 
 // Values only (TWR_EVAL_VALUES: Ipopt's eval_g, a planner's scoring step): problems with fixed timings take the one-lane-per-
@@ -3614,6 +3720,12 @@ static DynFn dyn_kernel_fn(const LaunchStep& p) {
     return pick<kStoresNT>(p.store, [&](auto st) -> DynFn { return dyn_kernel<StoreG(st), StoreJ(st), xc, StoreNT(st)>; });
   });
 }
+using DynUniformFn = void (*)(const DynWork*, DynUniform, const double*, double*, double*, double*);
+static DynUniformFn dyn_uniform_kernel_fn(const LaunchStep& p) {
+  return pick<kDynXc>(p.xc, [&](auto xc) {
+    return pick<kStoresNT>(p.store, [&](auto st) -> DynUniformFn { return dyn_uniform_kernel<StoreG(st), StoreJ(st), xc, StoreNT(st)>; });
+  });
+}
 static PDynFn dyn_phase_kernel_fn(const LaunchStep& p) {
   return pick<kDynPhaseNits>(p.nit, [&](auto nit) {
     return pick<kStores>(p.store, [&](auto st) -> PDynFn { return dyn_phase_kernel<nit, StoreG(st), StoreJ(st)>; });
@@ -3637,7 +3749,10 @@ hipError_t launch_eval(const EvalShape& s, const EvalBuffers& b, hipStream_t str
     const int* a = p.arg;
     switch (p.kernel) {
       case Launch::kEvent: (void)hipEventRecord(ev[a[0]], stream); break;
-      case Launch::kDyn: st = twr_first(st, twr_launch(dyn_kernel_fn(p), grid, block, p.lds, stream, b.dyn, s.dyn, b.x, b.g, b.jac, b.dump)); break;
+      case Launch::kDyn:
+        if (p.uni.s > 0) st = twr_first(st, twr_launch(dyn_uniform_kernel_fn(p), grid, block, p.lds, stream, b.dyn, p.uni, b.x, b.g, b.jac, b.dump));
+        else st = twr_first(st, twr_launch(dyn_kernel_fn(p), grid, block, p.lds, stream, b.dyn, s.dyn, b.x, b.g, b.jac, b.dump));
+        break;
       case Launch::kRom: st = twr_first(st, twr_launch(rom_kernel_fn(p), grid, block, p.lds, stream, b.rom, s.rom, b.x, b.g, b.jac)); break;
       case Launch::kFused:
         st = twr_first(st, twr_launch(fused_kernel_fn(p), grid, block, p.lds, stream, b.rom, s.rom, a[0], b.dyn, s.dyn, a[1], b.node, b.x, b.g,

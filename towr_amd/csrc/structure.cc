@@ -2048,6 +2048,20 @@ BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vec
   pdyn_first.push_back((int)L.pdyn.size());
   Interleave(L.dyn, dyn_first);
   Interleave(L.rom, rom_first);
+  // Uniform dyn list: one structure with fixed timings for every problem -- in the flagship batch and in its real use, many
+  // x for one NLP -- so problem p's slice of a kind is problem 0's with x, g and jac moved on by p strides.  (By structure
+  // INDEX: two equal structures are two tables in the arena, and a batch of them takes the general kernel.)  The interleaved
+  // order puts problem 0's slices min(8, n) positions apart.
+  {
+    bool one = n_problems > 0;
+    for (int si : struct_of_problem) one = one && si == struct_of_problem[0];
+    if (one) {
+      const Structure& S = *structs[struct_of_problem[0]];
+      const int s = (int)S.dyn_slices.size();
+      if (!S.timings && s > 0 && L.dyn.size() == (size_t)s * (size_t)n_problems)
+        b.dyn_uniform = DynUniform{s, 0, std::min(8, n_problems), n_problems, S.n_vars, S.n_rows, S.nnz, 0};
+    }
+  }
   Interleave(L.pdyn, pdyn_first);
   // Store policy of the copy-out (kernels.hip copy_out_fixed): non-temporal when the batch is SWEEP-LIKE -- fewer than four
   // problems per structure on average, so every evaluation re-reads tables (and x) that only that problem uses -- AND one
@@ -2279,7 +2293,17 @@ EvalPlan PlanEval(const EvalShape& s) {
     return plan;
   }
   event(0);
-  if (s.dyn > 0) add(Launch::kDyn, store_nt, 0, xc, s.dyn, t.dyn_bpc * s.n_cu, 64);
+  if (s.dyn > 0) {
+    LaunchStep& p = add(Launch::kDyn, store_nt, 0, xc, s.dyn, t.dyn_bpc * s.n_cu, 64);
+    // A uniform list (BatchPlan::dyn_uniform) goes to dyn_uniform_kernel, whose waves own one slice kind each and load its
+    // records once per launch, when the grid divides into kinds without idling the residency (DynUniformCols).
+    const int cols = DynUniformCols(s.dyn_uniform.s, s.dyn_uniform.n_problems, t.dyn_bpc * s.n_cu);
+    if (cols > 0 && s.dyn == s.dyn_uniform.s * s.dyn_uniform.n_problems) {
+      p.uni = s.dyn_uniform;
+      p.uni.cols = cols;
+      p.grid = 8 * p.uni.s * cols;
+    }
+  }
   // optimised-timings problems: the pre-pass (segment lookup -> records), then the persistent kernels; their LDS per
   // workgroup is the image of one pass, and their residency follows from it
   if (s.ploc > 0) add(Launch::kLocate, store, 0, 0, s.ploc, s.ploc, kLocateThreads);

@@ -3,6 +3,7 @@
 // information over NlpFormulation::GetVariableSets/GetConstraints, NodesVariables*,
 // SplineHolder and the constraint constructors (see citations in structure.cc).
 #pragma once
+#include <algorithm>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -196,6 +197,10 @@ struct BatchPlan {
   int rom_max_vals = 0;        // Jacobian values of the largest rom slice (picks the copy-out length)
   int flat_max_x = 0;          // variables of the largest problem of the values-only path (the LDS a wave stages x in)
   int dyn_map_chunks = 2;      // 2: every dyn slice of the batch stages <= 128 doubles of x (256-byte staging maps), else 4
+  // Uniform dyn list (device_tables.h DynUniform): every problem references ONE structure with fixed timings, so the dyn list
+  // holds the same s slices for every problem.  s = 0 otherwise; `cols` is left to PlanEval (it depends on the grid).  The
+  // list itself is the same bytes either way: a uniform launch reads the records of problem 0 only.
+  DynUniform dyn_uniform = {0, 0, 0, 0, 0, 0, 0, 0};
   int node_families = 4;       // 2 when no problem has more than terrain-* / force-* work for the node kernel
   int pdyn_img_cap = 0, prom_img_cap = 0;   // doubles of the LDS images of dyn_phase_kernel / rom_phase_kernel (largest pass)
   bool stream_nt = false;      // non-temporal copy-out stores (StreamNonTemporal)
@@ -224,6 +229,7 @@ struct EvalShape {
   // what PlanBatch decided for the batch (BatchPlan)
   int rom_max_vals = 0, flat_max_x = 0, dyn_map_chunks = 2, node_families = 4, pdyn_img_cap = 0, prom_img_cap = 0;
   bool stream_nt = false;
+  DynUniform dyn_uniform = {0, 0, 0, 0, 0, 0, 0, 0};   // BatchPlan::dyn_uniform (s = 0: the general dyn_kernel)
   int flags = 0;                  // TWR_EVAL_VALUES | TWR_EVAL_JACOBIAN, or kEvalScores (| kEvalBest)
   bool events = false;            // per-kernel profiling events are recorded
   bool score_fused = false;       // BatchPlan::score_fused
@@ -257,7 +263,20 @@ struct LaunchStep {
   // kEvent: the event; kFused: rom and dyn blocks; kChunk: blocks per family; kValues, kScores: groups, node families, x bytes;
   // kFold, kScoreG, kBest: problems
   int arg[4] = {0, 0, 0, 0};
+  // kDyn of a uniform list, when the grid rule of PlanEval holds: s > 0 selects dyn_uniform_kernel, cols is filled in
+  DynUniform uni = {0, 0, 0, 0, 0, 0, 0, 0};
 };
+// Grid of a uniform dyn launch.  The persistent grid holds W0 = grid / 8 waves per XCD; every wave owns one of the s slice
+// kinds, so the grid is trimmed to W = s * (W0 / s) waves per XCD, cols = W / s problems per XCD and iteration (no more
+// columns than the batch has problems for: ceil(n / 8)).  Returns 0 -- keep the general kernel -- when the trimming would
+// idle more than 1/32 of the residency (W0 - W > W0 / 32): s = 16 loses nothing of 256, s = 5 keeps 255, s = 6 keeps 252.
+inline int DynUniformCols(int s, int n_problems, int resident_grid) {
+  const int w0 = resident_grid / 8;
+  if (s <= 0 || n_problems <= 0 || w0 < s) return 0;
+  const int w = s * (w0 / s);
+  if (w0 - w > w0 / 32) return 0;
+  return std::min(w / s, (n_problems + 7) / 8);
+}
 struct EvalPlan {
   static constexpr int kMaxSteps = 10;
   int n = 0;
