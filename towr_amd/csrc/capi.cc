@@ -1,230 +1,23 @@
-// C ABI of libtowr_amd.so (see include/towr_amd.h).  Host runtime: handles, error
-// reporting, device table upload, work-list construction and the launch.
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
+// C ABI of libtowr_amd.so (see include/towr_amd.h), the batch runtime: structures, batches, their evaluation, sampling,
+// planes and scoring; error reporting.  The Jacobian linear algebra (twr_jac_*) is capi_jac.cc, which alone includes jac_*.hip.
 #include <atomic>
 #include <cmath>
 #include <cstddef>
 #include <cstring>
-#include <memory>
-#include <stdexcept>
-#include <string>
 #include <thread>
-#include <type_traits>
 #include <utility>
-#include <vector>
 
-#include "jac_gram.hip"
-#include "jac_lm.hip"
-#include "jac_lsq.hip"
-#include "jac_products.hip"
-#include "launch.h"
-
-struct twr_structure {
-  twr::Structure s;
-};
-struct twr_terrain_grid {
-  std::shared_ptr<twr::TerrainGrid> g;
-};
-
-// Makes `device` current for a scope and restores the calling thread's device afterwards: no entry point of the library
-// leaves its caller on another device (one process may drive several GPUs).  The caller's error state is not touched.
-struct DeviceScope {
-  int prev = -1;
-  bool switched = false;
-  hipError_t status = hipSuccess;
-  explicit DeviceScope(int device) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device) {
-      status = hipSetDevice(device);
-      switched = status == hipSuccess;
-    }
-  }
-  ~DeviceScope() {
-    if (switched && prev >= 0) (void)hipSetDevice(prev);
-  }
-  DeviceScope(const DeviceScope&) = delete;
-  DeviceScope& operator=(const DeviceScope&) = delete;
-};
-
-// Owners of what a handle holds on its device.  They release it where they are destroyed, so whoever destroys a handle
-// holds a DeviceScope of its device (twr_batch_destroy, twr_planes_destroy).
-struct HipFree {
-  void operator()(void* p) const { (void)hipFree(p); }
-};
-struct HipHostFree {
-  void operator()(void* p) const { (void)hipHostFree(p); }
-};
-struct HipStreamDestroy {
-  void operator()(hipStream_t s) const { (void)hipStreamDestroy(s); }
-};
-template <class T> using DevPtr = std::unique_ptr<T, HipFree>;
-template <class T> using PinnedPtr = std::unique_ptr<T, HipHostFree>;
-using StreamPtr = std::unique_ptr<std::remove_pointer_t<hipStream_t>, HipStreamDestroy>;
-template <class T> struct DevList {   // a work list in device memory
-  DevPtr<T> d;
-  int n = 0;
-};
-struct Events {   // hipEvent_t[] (launch_eval records into consecutive ones)
-  std::vector<hipEvent_t> ev;
-  Events() = default;
-  Events(const Events&) = delete;
-  Events& operator=(const Events&) = delete;
-  ~Events() { clear(); }
-  void clear() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-    ev.clear();
-  }
-};
-
-struct twr_planes {
-  int device = 0;
-  std::vector<int32_t> start;      // polygon r = points [start[r], start[r+1])
-  std::vector<double> world_xy;    // PlanarRegionsToPolygons output
-  DevPtr<double> d_xy;
-  DevPtr<int32_t> d_start;
-};
-
-struct twr_batch {
-  int device = 0;
-  int n_problems = 0, n_ee = 0, n_cu = 0;
-  twr::BatchPlan plan;                       // offsets, what twr_batch_sample needs, policy (its work lists are on the device, below)
-  DevPtr<void> arena;                        // ONE allocation for the tables of all structures (a sweep has a thousand
-                                             // of them: one mapping with large pages instead of a thousand small ones,
-                                             // one upload instead of a thousand)
-  int64_t table_bytes = 0;                   // arena bytes
-  std::vector<DevPtr<void>> grids;           // device copies of the distinct gridded terrains
-  DevList<twr::DynWork> dyn;
-  DevList<twr::RomWork> rom;
-  DevList<twr::NodeWork> node;               // (+ the end entry, not counted)
-  DevList<twr::FlatWork> flat;               // values-only evaluation of dynamic / rangeofmotion-* (empty: not for this batch)
-  DevList<twr::FamWork> fam[4];              // chunk lists of node_chunk_kernel (large batches only)
-  // optimised-timings problems have their own work lists
-  DevList<twr::PDynWork> pdyn;
-  DevList<twr::LocWork> ploc;
-  DevList<twr::RomPhaseWork> prom;
-  DevPtr<void> precs;                        // scratch: x-dependent DynLoc / RomRec records of the optimised-timings problems
-  DevList<int64_t> goff, joff;               // device copies of g_off / j_off (TWR_EVAL_CHECK)
-  DevPtr<int32_t> status;                    // per-problem non-finite flags of the last checked evaluation
-  DevPtr<double> dump;                       // where dyn_kernel's first (empty) copy-out of every workgroup goes
-  DevPtr<double> best;                       // twr_batch_best: per-block results (2 doubles each) + the block counter behind them
-  DevList<uint64_t> score_blob;              // twr_batch_eval_scores without g (plan.score_fused): BatchPlan::Lists score_*
-  DevList<int32_t> score_first, score_slot;
-  DevPtr<double> score_slab;                 // the scoring launch's partial records (kScorePartial doubles each)
-  DevList<twr::SampleWork> swork;            // work list of the last twr_batch_sample call (cached per dt / stride)
-  double swork_dt = 0.0;
-  int64_t swork_stride = -1;
-  DevList<twr::SampleWork> gwork;            // work list of the last twr_batch_initial_guess call (cached per count / stride)
-  int gwork_times = -1;
-  int64_t gwork_stride = -1;
-  // lazily sized scratch for twr_batch_eval_host
-  DevPtr<double> d_x, d_g, d_j;
-  PinnedPtr<double> p_x, p_g, p_j;           // page-locked host buffers (twr_batch_host_buffers)
-  // twr_batch_eval_host runs on a stream of the batch's own (non-blocking: it neither waits for nor holds up work the host
-  // application has on the NULL stream or on other blocking streams); created on first use
-  StreamPtr host_stream;
-  // optional per-kernel timing (twr_batch_profile_begin/end): 4 events per recorded eval
-  Events prof_events;
-  int prof_capacity = 0, prof_count = 0;
-};
-
-struct twr_jac_ops {   // twr::PlanJacOps's tables and work lists on the device, and the slab of J^T w's partials
-  int device = 0, n_problems = 0;
-  std::vector<int64_t> x_off, g_off, j_off;
-  DevPtr<void> tables;
-  DevList<twr::JacMulWork> mul;
-  DevList<twr::JacTWork> tmul;
-  DevList<twr::JacFoldWork> fold;
-  DevPtr<double> slab;
-  int lds_x = 0, distinct_patterns = 0;
-  int64_t resident = 0;
-  // The one-pass product (twr_jac_ops_reserve_normal) and the Gram matrix (twr_jac_ops_reserve_gram): planned, uploaded and
-  // allocated on first use, from the patterns the device tables hold (read back then).  For that the host keeps, per distinct
-  // pattern, its sizes and where its col / row_ptr tables lie (twr::JacPatternPlaces of the plan the handle was made from), and
-  // every problem's pattern.
-  struct PatternSizes {
-    int32_t n, m, nnz;
-  };
-  std::vector<PatternSizes> pattern_sizes;
-  std::vector<twr::JacPatternPlace> pattern_places;
-  std::vector<int32_t> pattern_of_problem;
-  size_t table_bytes = 0;
-  bool normal_ready = false;
-  DevPtr<void> ntables;
-  DevList<twr::JacNormalWork> nwork;
-  DevList<twr::JacFoldWork> nfold;
-  DevPtr<double> nslab;
-  int n_lds_x = 0, n_tile = 0;
-  // The Gram matrix (twr_jac_ops_reserve_gram): twr::PlanJacGram's tables and work lists, made from the same patterns
-  bool gram_ready = false;
-  std::vector<int64_t> gram_off;
-  DevPtr<void> gtables;
-  DevList<twr::JacGramWork> gform;
-  DevList<twr::JacGramMulWork> gmul;
-  DevList<twr::JacGramSolveWork> gsolve;
-  int gram_max_n = 0;
-};
-
-struct twr_jac_lsq {   // twr::PlanJacLsq's work records and bound tables on the device, and the solver's workspace
-  twr_jac_ops* ops = nullptr;   // borrowed
-  int device = 0, n_problems = 0;
-  DevPtr<void> bounds;
-  DevList<twr::JacLsqWork> work;
-  DevPtr<double> ws;
-  twr::LsqBuffers buf{};
-  int lds_x = 0;
-  int64_t resident = 0;
-  DevPtr<double> ws2;           // the scaled solve's vectors (twr_jac_lsq_reserve_scaled); resident counts them once they exist
-  twr::LsqScaledBuffers buf2{};
-  int64_t ws2_e = 0, ws2_cp = 0, ws2_doubles = 0;
-  DevPtr<double> ws3;           // the one-pass solve's vectors (twr_jac_lsq_solve_onepass); resident counts them once they exist
-  twr::LsqOnepassBuffers buf3{};
-  int64_t ws3_s = 0, ws3_u = 0, ws3_doubles = 0;
-};
-
-struct twr_jac_lm {   // the bounded LM driver: twr::PlanJacLm's workspace, and what twr_jac_lm_start bound
-  twr_batch* batch = nullptr;   // borrowed
-  twr_jac_lsq* lsq = nullptr;   // borrowed (and through it its twr_jac_ops)
-  int device = 0, n_problems = 0;
-  twr_jac_lm_params params{};
-  int solver = TWR_JAC_LM_CGLS;
-  DevPtr<double> gram;          // the driver's own N (twr_jac_lm_set_solver with TWR_JAC_LM_GRAM)
-  DevPtr<double> ws;
-  twr::LmBuffers buf{};
-  int64_t resident = 0;
-  double *x = nullptr, *g = nullptr, *jac = nullptr;   // the caller's (twr_jac_lm_start)
-  const double *xlo = nullptr, *xup = nullptr;
-};
+#include "capi_internal.h"
 
 namespace {
 thread_local std::string g_err;
+}
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-#define TWR_HIP(call)                                                                              \
-  do {                                                                                             \
-    hipError_t e_ = (call);                                                                        \
-    if (e_ != hipSuccess) throw std::runtime_error(std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
 
-template <class T> DevPtr<T> dev_alloc(size_t bytes) {
-  void* p = nullptr;
-  TWR_HIP(hipMalloc(&p, bytes));
-  return DevPtr<T>(static_cast<T*>(p));
-}
-template <class T> DevPtr<T> dev_zeros(size_t count) {
-  DevPtr<T> d = dev_alloc<T>(count * sizeof(T));
-  TWR_HIP(hipMemset(d.get(), 0, count * sizeof(T)));
-  return d;
-}
-template <class T> DevList<T> upload(const std::vector<T>& v) {
-  DevList<T> l{dev_alloc<T>(v.size() * sizeof(T)), (int)v.size()};
-  TWR_HIP(hipMemcpy(l.d.get(), v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-  return l;
-}
-
+namespace {
 // sample_kernel's work list (twr_batch_sample, twr_batch_initial_guess): count(p) samples of problem p, 64 per item, its
 // records from p * stride on.  The old list is freed once the new one is known.
 template <class Count>
@@ -571,12 +364,9 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
     if (device < 0 || device >= n_dev) return fail(TWR_ERR_INVALID, "device ordinal out of range");
     DeviceScope on(device);
     TWR_HIP(on.status);
-    std::vector<const twr::Structure*> sp(n_structs);
-    for (int i = 0; i < n_structs; ++i) {
-      if (!structs[i]) throw std::runtime_error("null structure");
-      if (structs[i]->s.n_ee != structs[0]->s.n_ee) throw std::runtime_error("all structures of a batch must share n_ee");
-      sp[i] = &structs[i]->s;
-    }
+    const std::vector<const twr::Structure*> sp = structure_ptrs(structs, n_structs);
+    for (const twr::Structure* s : sp)
+      if (s->n_ee != sp[0]->n_ee) throw std::runtime_error("all structures of a batch must share n_ee");
     b->device = device;
     b->n_problems = n_problems;
     b->n_ee = sp[0]->n_ee;
@@ -617,15 +407,14 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
     b->rom = upload(L.rom);
     b->node = upload(L.node);
     b->node.n = n_problems;
-    if (!L.flat.empty()) b->flat = upload(L.flat);
-    for (int f = 0; f < 4; ++f)
-      if (!L.fam[f].empty()) b->fam[f] = upload(L.fam[f]);
+    b->flat = upload_nonempty(L.flat);
+    for (int f = 0; f < 4; ++f) b->fam[f] = upload_nonempty(L.fam[f]);
     b->goff = upload(b->plan.g_off);
     b->joff = upload(b->plan.j_off);
     b->dump = dev_zeros<double>(twr::kDynDump);
     b->best = dev_zeros<double>(2 * (size_t)twr::best_max_blocks() + 1);
     if (b->plan.score_fused) {
-      if (!L.score_blob.empty()) b->score_blob = upload(L.score_blob);
+      b->score_blob = upload_nonempty(L.score_blob);
       b->score_first = upload(L.score_first);
       b->score_slot = upload(L.score_slot);
       b->score_slab = dev_alloc<double>(sizeof(double) * twr::kScorePartial * (size_t)b->plan.score_slab);
@@ -636,8 +425,8 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
       b->plan.PlaceRecords(reinterpret_cast<uint64_t>(b->precs.get()));
       b->ploc = upload(L.ploc);
     }
-    if (!L.prom.empty()) b->prom = upload(L.prom);
-    if (!L.pdyn.empty()) b->pdyn = upload(L.pdyn);
+    b->prom = upload_nonempty(L.prom);
+    b->pdyn = upload_nonempty(L.pdyn);
     b->plan.lists = twr::BatchPlan::Lists();   // (on the device now)
     TWR_HIP(twr::prepare_phase_kernels(b->plan.pdyn_img_cap, b->plan.prom_img_cap));
     *out = b.release();
@@ -726,7 +515,7 @@ int twr_batch_eval(twr_batch* b, const double* d_x, double* d_g, double* d_jac, 
                              {b->fam[0].d.get(), b->fam[1].d.get(), b->fam[2].d.get(), b->fam[3].d.get()},
                              b->pdyn.d.get(), b->ploc.d.get(), b->prom.d.get(), d_x, d_g, d_jac, b->dump.get()};
   hipError_t e = twr::launch_eval(s, buf, stream, ev);
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return launched(e);
   if (flags & TWR_EVAL_CHECK) {
     e = twr::launch_check(b->n_problems, b->goff.d.get(), b->joff.d.get(), d_g, d_jac, b->status.get(), flags & TWR_EVAL_BOTH, stream);
     if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("check kernel launch: ") + hipGetErrorString(e));
@@ -877,8 +666,7 @@ int twr_batch_sample(twr_batch* b, const double* d_x, double dt, double* d_out, 
       b->swork_stride = problem_stride;
     }
     hipError_t e = twr::launch_sample(b->swork.d.get(), b->swork.n, d_x, d_out, dt, nullptr, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return TWR_OK;
+    return launched(e);
   } catch (const std::exception& e) {
     return fail(TWR_ERR_HIP, e.what());
   }
@@ -897,8 +685,7 @@ int twr_batch_initial_guess(twr_batch* b, const double* d_x, const double* d_tim
       b->gwork_stride = problem_stride;
     }
     hipError_t e = twr::launch_sample(b->gwork.d.get(), b->gwork.n, d_x, d_out, 0.0, d_times, static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return TWR_OK;
+    return launched(e);
   } catch (const std::exception& e) {
     return fail(TWR_ERR_HIP, e.what());
   }
@@ -976,8 +763,7 @@ int twr_batch_contact_planes(twr_batch* b, const twr_planes* planes, const doubl
   if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
   hipError_t e = twr::launch_planes(d_plan, d_counts, planes->d_xy.get(), planes->d_start.get(), (int)planes->start.size() - 1, b->n_problems,
                                     max_steps, b->n_ee, d_plane_index, static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
+  return launched(e);
 }
 
 int twr_batch_score(twr_batch* b, const double* d_g, double* d_scores, void* hip_stream) {
@@ -985,8 +771,7 @@ int twr_batch_score(twr_batch* b, const double* d_g, double* d_scores, void* hip
   DeviceScope on(b->device);
   if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
   hipError_t e = twr::launch_score(b->node.d.get(), b->n_problems, d_g, d_scores, static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
+  return launched(e);
 }
 
 int twr_batch_score_best(twr_batch* b, const double* d_g, double* d_scores, uint32_t families, int64_t index_offset, double* d_best,
@@ -1002,8 +787,7 @@ int twr_batch_score_best(twr_batch* b, const double* d_g, double* d_scores, uint
   hipError_t e = twr::launch_score(b->node.d.get(), b->n_problems, d_g, d_scores, static_cast<hipStream_t>(hip_stream));
   if (e == hipSuccess)
     e = twr::launch_best(d_scores, b->n_problems, families, b->best.get(), counter, d_best, (double)index_offset, static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
+  return launched(e);
 }
 
 int twr_batch_scores_without_g(const twr_batch* b) { return b && b->plan.score_fused ? 1 : 0; }
@@ -1042,8 +826,7 @@ int eval_scores(twr_batch* b, const double* d_x, double* d_g, double* d_scores, 
   buf.best_counter = reinterpret_cast<unsigned*>(b->best.get() + 2 * (size_t)twr::best_max_blocks());
   buf.best = d_best;
   hipError_t e = twr::launch_eval(s, buf, static_cast<hipStream_t>(hip_stream), nullptr);
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
+  return launched(e);
 }
 }  // namespace
 
@@ -1064,8 +847,7 @@ int twr_batch_best(twr_batch* b, const double* d_scores, int32_t n_candidates, u
   if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
   unsigned* counter = reinterpret_cast<unsigned*>(b->best.get() + 2 * (size_t)twr::best_max_blocks());
   hipError_t e = twr::launch_best(d_scores, n_candidates, families, b->best.get(), counter, d_best, 0.0, static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
+  return launched(e);
 }
 
 int twr_structure_contact_steps_max(const twr_structure* s, int32_t* max_steps) {
@@ -1089,8 +871,7 @@ int twr_batch_contact_plan(twr_batch* b, const double* d_x, double dt, double ti
     }
     hipError_t e = twr::launch_contact_plan(b->node.d.get(), b->n_problems, d_x, d_out, d_counts, dt, time_horizon, n_max, max_steps,
                                             static_cast<hipStream_t>(hip_stream));
-    if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-    return TWR_OK;
+    return launched(e);
   } catch (const std::exception& e) {
     return fail(TWR_ERR_HIP, e.what());
   }
@@ -1118,772 +899,6 @@ int twr_batch_host_buffers(twr_batch* b, double** h_x, double** h_g, double** h_
   } catch (const std::exception& e) {
     return fail(TWR_ERR_HIP, e.what());
   }
-}
-
-int twr_structure_transpose(const twr_structure* s, int32_t* col_ptr, int32_t* row_idx, int32_t* csr_pos) {
-  if (!s) return fail(TWR_ERR_INVALID, "null structure");
-  try {
-    const twr::CscPattern t = twr::TransposePattern(s->s);
-    if (col_ptr) std::memcpy(col_ptr, t.col_ptr.data(), t.col_ptr.size() * sizeof(int32_t));
-    if (row_idx && !t.row_idx.empty()) std::memcpy(row_idx, t.row_idx.data(), t.row_idx.size() * sizeof(int32_t));
-    if (csr_pos && !t.csr_pos.empty()) std::memcpy(csr_pos, t.csr_pos.data(), t.csr_pos.size() * sizeof(int32_t));
-    return TWR_OK;
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_INVALID, e.what());
-  }
-}
-
-int twr_jac_ops_create(const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem, int n_problems, int device,
-                       twr_jac_ops** out) {
-  if (!structs || !struct_of_problem || !out || n_structs < 1 || n_problems < 1) return fail(TWR_ERR_INVALID, "bad arguments");
-  twr::JacOpsPlan plan;
-  try {   // argument errors
-    std::vector<const twr::Structure*> sp(n_structs);
-    for (int i = 0; i < n_structs; ++i) {
-      if (!structs[i]) throw std::runtime_error("null structure");
-      sp[i] = &structs[i]->s;
-    }
-    plan = twr::PlanJacOps(sp, std::vector<int32_t>(struct_of_problem, struct_of_problem + n_problems));
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_INVALID, e.what());
-  }
-  std::unique_ptr<twr_jac_ops> h(new twr_jac_ops());
-  try {   // device errors
-    int n_dev = 0;
-    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev == 0)
-      return fail(TWR_ERR_NO_DEVICE, "no HIP device visible: towr_amd has no CPU fallback");
-    if (device < 0 || device >= n_dev) return fail(TWR_ERR_INVALID, "device ordinal out of range");
-    DeviceScope on(device);
-    TWR_HIP(on.status);
-    h->device = device;
-    h->n_problems = n_problems;
-    h->x_off = plan.x_off;
-    h->g_off = plan.g_off;
-    h->j_off = plan.j_off;
-    const size_t tb = std::max<size_t>(16, plan.tables.size());
-    h->tables = dev_alloc<void>(tb);
-    if (!plan.tables.empty()) TWR_HIP(hipMemcpy(h->tables.get(), plan.tables.data(), plan.tables.size(), hipMemcpyHostToDevice));
-    h->table_bytes = plan.tables.size();
-    h->pattern_places = twr::JacPatternPlaces(plan, std::vector<int32_t>(struct_of_problem, struct_of_problem + n_problems));
-    for (const twr::JacPatternPlace& a : h->pattern_places) {   // (a structure no problem uses leaves its pattern without a place)
-      if (a.first_struct < 0) h->pattern_sizes.push_back({0, 0, 0});
-      else h->pattern_sizes.push_back({structs[a.first_struct]->s.n_vars, structs[a.first_struct]->s.n_rows, structs[a.first_struct]->s.nnz});
-    }
-    plan.Place(reinterpret_cast<uint64_t>(h->tables.get()));
-    if (!plan.mul.empty()) h->mul = upload(plan.mul);
-    if (!plan.tmul.empty()) h->tmul = upload(plan.tmul);
-    if (!plan.fold.empty()) h->fold = upload(plan.fold);
-    h->slab = dev_alloc<double>(sizeof(double) * std::max<size_t>(1, (size_t)plan.slab));
-    h->lds_x = plan.mul_lds_x;
-    h->distinct_patterns = plan.distinct_patterns;
-    h->pattern_of_problem.resize(n_problems);
-    for (int p = 0; p < n_problems; ++p) h->pattern_of_problem[p] = plan.pattern_of_struct[struct_of_problem[p]];
-    h->resident = (int64_t)tb + (int64_t)(plan.mul.size() * sizeof(twr::JacMulWork) + plan.tmul.size() * sizeof(twr::JacTWork) +
-                                          plan.fold.size() * sizeof(twr::JacFoldWork)) +
-                  8 * std::max<int64_t>(1, plan.slab);
-    *out = h.release();
-    return TWR_OK;
-  } catch (const std::exception& e) {
-    twr_jac_ops_destroy(h.release());
-    return fail(TWR_ERR_HIP, e.what());
-  }
-}
-
-void twr_jac_ops_destroy(twr_jac_ops* ops) {
-  if (!ops) return;
-  DeviceScope on(ops->device);
-  delete ops;
-}
-
-int twr_jac_ops_layout(const twr_jac_ops* ops, int64_t* x_off, int64_t* g_off, int64_t* jac_off) {
-  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
-  const size_t bytes = (ops->n_problems + 1) * sizeof(int64_t);
-  if (x_off) std::memcpy(x_off, ops->x_off.data(), bytes);
-  if (g_off) std::memcpy(g_off, ops->g_off.data(), bytes);
-  if (jac_off) std::memcpy(jac_off, ops->j_off.data(), bytes);
-  return TWR_OK;
-}
-
-int twr_jac_ops_bytes(const twr_jac_ops* ops, int64_t* resident, int32_t* distinct_patterns) {
-  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
-  if (resident) *resident = ops->resident;
-  if (distinct_patterns) *distinct_patterns = ops->distinct_patterns;
-  return TWR_OK;
-}
-
-int twr_jac_mul(twr_jac_ops* ops, const double* d_jac, const double* d_v, double* d_y, void* hip_stream) {
-  if (!ops || !d_jac || !d_v || !d_y) return fail(TWR_ERR_INVALID, "null argument");
-  if ((reinterpret_cast<uintptr_t>(d_jac) | reinterpret_cast<uintptr_t>(d_v) | reinterpret_cast<uintptr_t>(d_y)) & 7)
-    return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(ops->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  hipError_t e = twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, d_v, d_y, static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
-}
-
-int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_z, void* hip_stream) {
-  if (!ops || !d_jac || !d_w || !d_z) return fail(TWR_ERR_INVALID, "null argument");
-  if ((reinterpret_cast<uintptr_t>(d_jac) | reinterpret_cast<uintptr_t>(d_w) | reinterpret_cast<uintptr_t>(d_z)) & 7)
-    return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(ops->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  hipError_t e = twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, d_w, ops->slab.get(), d_z,
-                                      static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
-}
-
-int twr_jac_col_sqnorms(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_out, void* hip_stream) {
-  if (!ops || !d_jac || !d_out) return fail(TWR_ERR_INVALID, "null argument");
-  if ((reinterpret_cast<uintptr_t>(d_jac) | reinterpret_cast<uintptr_t>(d_w) | reinterpret_cast<uintptr_t>(d_out)) & 7)
-    return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(ops->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  hipError_t e = twr::launch_jac_colsq(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, d_w, ops->slab.get(), d_out,
-                                       static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
-}
-
-namespace {
-// The distinct patterns of a products handle as structures (n_vars, n_rows, nnz, row_ptr, col_idx alone), read back from the
-// tables the device holds: what the plans made after twr_jac_ops_create start from.
-int ops_patterns(twr_jac_ops* ops, std::vector<twr::Structure>* out) {
-  std::vector<char> tables(ops->table_bytes);
-  try {
-    DeviceScope on(ops->device);
-    TWR_HIP(on.status);
-    if (!tables.empty()) TWR_HIP(hipMemcpy(tables.data(), ops->tables.get(), tables.size(), hipMemcpyDeviceToHost));
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_HIP, e.what());
-  }
-  std::vector<twr::Structure>& pats = *out;
-  pats.assign(ops->pattern_sizes.size(), twr::Structure{});
-  for (size_t q = 0; q < pats.size(); ++q) {
-    const twr_jac_ops::PatternSizes& Z = ops->pattern_sizes[q];
-    const twr::JacPatternPlace& A = ops->pattern_places[q];
-    twr::Structure& S = pats[q];
-    S.n_vars = Z.n, S.n_rows = Z.m, S.nnz = Z.nnz;
-    S.row_ptr.assign(Z.m + 1, 0);
-    S.col_idx.resize(Z.nnz);
-    if (Z.m > 0) {
-      if (A.row_ptr + sizeof(int32_t) * (Z.m + 1) > tables.size() || A.col + sizeof(uint16_t) * Z.nnz > tables.size())
-        return fail(TWR_ERR_INVALID, "a pattern's tables lie outside the handle's");
-      std::memcpy(S.row_ptr.data(), tables.data() + A.row_ptr, sizeof(int32_t) * (Z.m + 1));
-      const uint16_t* col = reinterpret_cast<const uint16_t*>(tables.data() + A.col);
-      std::copy(col, col + Z.nnz, S.col_idx.begin());
-    }
-  }
-  return TWR_OK;
-}
-}  // namespace
-
-int twr_jac_ops_reserve_normal(twr_jac_ops* ops) { return twr_jac_ops_reserve_normal_tile(ops, twr::kJacNormNnz); }
-
-int twr_jac_ops_reserve_normal_tile(twr_jac_ops* ops, int tile_entries) {
-  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
-  if (tile_entries < 1 || tile_entries > twr::kJacNormNnz) return fail(TWR_ERR_INVALID, "the tile is 1 .. 2048 entries");
-  if (ops->normal_ready)
-    return ops->n_tile == tile_entries ? TWR_OK : fail(TWR_ERR_INVALID, "the one-pass tables exist, made for another tile");
-  twr::JacNormalPlan plan;
-  std::vector<twr::Structure> pats;
-  int rc = ops_patterns(ops, &pats);
-  if (rc != TWR_OK) return rc;
-  try {
-    std::vector<const twr::Structure*> sp;
-    for (const twr::Structure& S : pats) sp.push_back(&S);
-    plan = twr::PlanJacNormal(sp, ops->pattern_places, ops->pattern_of_problem, tile_entries);
-    if (plan.x_off != ops->x_off || plan.g_off != ops->g_off || plan.j_off != ops->j_off)
-      throw std::runtime_error("the one-pass plan's layout is not the handle's");
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_INVALID, e.what());
-  }
-  try {
-    DeviceScope on(ops->device);
-    TWR_HIP(on.status);
-    TWR_HIP(twr::prepare_jac_normal());
-    const size_t tb = std::max<size_t>(16, plan.tables.size());
-    DevPtr<void> tables = dev_alloc<void>(tb);
-    if (!plan.tables.empty()) TWR_HIP(hipMemcpy(tables.get(), plan.tables.data(), plan.tables.size(), hipMemcpyHostToDevice));
-    plan.Place(reinterpret_cast<uint64_t>(ops->tables.get()), reinterpret_cast<uint64_t>(tables.get()));
-    DevList<twr::JacNormalWork> work;
-    DevList<twr::JacFoldWork> fold;
-    if (!plan.work.empty()) work = upload(plan.work);
-    if (!plan.fold.empty()) fold = upload(plan.fold);
-    DevPtr<double> slab = dev_alloc<double>(sizeof(double) * std::max<size_t>(1, (size_t)plan.slab));
-    ops->ntables = std::move(tables);
-    ops->nwork = std::move(work);
-    ops->nfold = std::move(fold);
-    ops->nslab = std::move(slab);
-    ops->n_lds_x = plan.lds_x;
-    ops->n_tile = plan.tile;
-    ops->resident += (int64_t)tb + (int64_t)(plan.work.size() * sizeof(twr::JacNormalWork) + plan.fold.size() * sizeof(twr::JacFoldWork)) +
-                     8 * std::max<int64_t>(1, plan.slab);
-    ops->normal_ready = true;
-    return TWR_OK;
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_HIP, e.what());
-  }
-}
-
-int twr_jac_normal_mul(twr_jac_ops* ops, const double* d_jac, const double* d_w, const double* d_v, double* d_y, double* d_u,
-                       void* hip_stream) {
-  if (!ops || !d_jac || !d_v || !d_u) return fail(TWR_ERR_INVALID, "null argument");
-  if ((reinterpret_cast<uintptr_t>(d_jac) | reinterpret_cast<uintptr_t>(d_w) | reinterpret_cast<uintptr_t>(d_v) |
-       reinterpret_cast<uintptr_t>(d_y) | reinterpret_cast<uintptr_t>(d_u)) & 7)
-    return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  if (!ops->normal_ready) {
-    const int rc = twr_jac_ops_reserve_normal(ops);
-    if (rc != TWR_OK) return rc;
-  }
-  DeviceScope on(ops->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  hipError_t e = twr::launch_jac_normal(ops->nwork.d.get(), ops->nwork.n, ops->n_lds_x, ops->n_tile, ops->nfold.d.get(), ops->nfold.n, d_jac, d_w, d_v,
-                                        d_y, ops->nslab.get(), d_u, static_cast<hipStream_t>(hip_stream));
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
-}
-
-int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem,
-                       int n_problems, twr_jac_lsq** out) {
-  if (!ops || !structs || !struct_of_problem || !out || n_structs < 1 || n_problems < 1) return fail(TWR_ERR_INVALID, "bad arguments");
-  twr::JacLsqPlan plan;
-  try {   // argument errors
-    std::vector<const twr::Structure*> sp(n_structs);
-    for (int i = 0; i < n_structs; ++i) {
-      if (!structs[i]) throw std::runtime_error("null structure");
-      sp[i] = &structs[i]->s;
-    }
-    plan = twr::PlanJacLsq(sp, std::vector<int32_t>(struct_of_problem, struct_of_problem + n_problems));
-    if (n_problems != ops->n_problems || plan.x_off != ops->x_off || plan.g_off != ops->g_off)
-      throw std::runtime_error("the structures are not the ones the products handle was created with");
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_INVALID, e.what());
-  }
-  std::unique_ptr<twr_jac_lsq> h(new twr_jac_lsq());
-  try {   // device errors
-    DeviceScope on(ops->device);
-    TWR_HIP(on.status);
-    h->ops = ops;
-    h->device = ops->device;
-    h->n_problems = n_problems;
-    const size_t bb = std::max<size_t>(16, plan.bounds.size());
-    h->bounds = dev_alloc<void>(bb);
-    if (!plan.bounds.empty()) TWR_HIP(hipMemcpy(h->bounds.get(), plan.bounds.data(), plan.bounds.size(), hipMemcpyHostToDevice));
-    plan.Place(reinterpret_cast<uint64_t>(h->bounds.get()));
-    h->work = upload(plan.work);
-    h->ws = dev_alloc<double>(sizeof(double) * (size_t)plan.ws_doubles);
-    double* w = h->ws.get();
-    h->buf = {w + plan.ws_p, w + plan.ws_z, w + plan.ws_q, w + plan.ws_r, w + plan.ws_t, w + plan.ws_rec};
-    h->lds_x = plan.lds_x;
-    h->resident = (int64_t)bb + (int64_t)(plan.work.size() * sizeof(twr::JacLsqWork)) + 8 * plan.ws_doubles;
-    h->ws2_e = plan.ws2_e, h->ws2_cp = plan.ws2_cp, h->ws2_doubles = plan.ws2_doubles;
-    h->ws3_s = plan.ws3_s, h->ws3_u = plan.ws3_u, h->ws3_doubles = plan.ws3_doubles;
-    *out = h.release();
-    return TWR_OK;
-  } catch (const std::exception& e) {
-    twr_jac_lsq_destroy(h.release());
-    return fail(TWR_ERR_HIP, e.what());
-  }
-}
-
-void twr_jac_lsq_destroy(twr_jac_lsq* lsq) {
-  if (!lsq) return;
-  DeviceScope on(lsq->device);
-  delete lsq;
-}
-
-int twr_jac_lsq_bytes(const twr_jac_lsq* lsq, int64_t* resident) {
-  if (!lsq) return fail(TWR_ERR_INVALID, "null handle");
-  if (resident) *resident = lsq->resident;
-  return TWR_OK;
-}
-
-namespace {
-bool misaligned(std::initializer_list<const void*> ptrs) {   // NULL (an optional buffer left out) counts as aligned
-  uintptr_t bits = 0;
-  for (const void* p : ptrs) bits |= reinterpret_cast<uintptr_t>(p);
-  return (bits & 7) != 0;
-}
-int lsq_launched(hipError_t e) {
-  if (e != hipSuccess) return fail(TWR_ERR_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
-  return TWR_OK;
-}
-}  // namespace
-
-int twr_jac_dot(twr_jac_lsq* lsq, int space, const double* d_a, const double* d_b, double* d_out, void* hip_stream) {
-  if (!lsq || !d_a || !d_b || !d_out) return fail(TWR_ERR_INVALID, "null argument");
-  if (space != 0 && space != 1) return fail(TWR_ERR_INVALID, "space is 0 (the x layout) or 1 (the g layout)");
-  if (misaligned({d_a, d_b, d_out})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  return lsq_launched(twr::launch_lsq_dot(lsq->work.d.get(), lsq->work.n, space, d_a, d_b, d_out, static_cast<hipStream_t>(hip_stream)));
-}
-
-int twr_jac_violation(twr_jac_lsq* lsq, const double* d_g, const double* d_w, double* d_r, double* d_w_active, double* d_merit,
-                      void* hip_stream) {
-  if (!lsq || !d_g || !d_r) return fail(TWR_ERR_INVALID, "null argument");
-  if (misaligned({d_g, d_w, d_r, d_w_active, d_merit})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  return lsq_launched(twr::launch_lsq_violation(lsq->work.d.get(), lsq->work.n, d_g, d_w, d_r, d_w_active, d_merit,
-                                                static_cast<hipStream_t>(hip_stream)));
-}
-
-int twr_jac_lsq_solve(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu, int iters,
-                      double tol, double* d_d, double* d_info, void* hip_stream) {
-  if (!lsq || !d_jac || !d_b || !d_mu || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
-  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
-  if (misaligned({d_jac, d_b, d_w, d_mu, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  const twr_jac_ops* ops = lsq->ops;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  return lsq_launched(twr::launch_lsq_solve(
-      lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, d_b, d_w, d_mu, iters, tol, d_d, d_info, stream,
-      [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
-      [&](const double* w, double* z) {
-        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
-      }));
-}
-
-int twr_jac_lsq_reserve_scaled(twr_jac_lsq* lsq) {
-  if (!lsq) return fail(TWR_ERR_INVALID, "null handle");
-  if (lsq->ws2) return TWR_OK;
-  try {
-    DeviceScope on(lsq->device);
-    TWR_HIP(on.status);
-    lsq->ws2 = dev_alloc<double>(std::max<size_t>(16, sizeof(double) * (size_t)lsq->ws2_doubles));
-    lsq->buf2 = {lsq->ws2.get() + lsq->ws2_e, lsq->ws2.get() + lsq->ws2_cp};
-    lsq->resident += 8 * lsq->ws2_doubles;
-    return TWR_OK;
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_HIP, e.what());
-  }
-}
-
-int twr_jac_col_scale(twr_jac_lsq* lsq, const double* d_colsq, double* d_colsq_max, double rel_floor, double* d_scale, void* hip_stream) {
-  if (!lsq || !d_colsq || !d_scale) return fail(TWR_ERR_INVALID, "null argument");
-  if (!(rel_floor > 0.0 && rel_floor <= 1.0)) return fail(TWR_ERR_INVALID, "rel_floor must be in (0, 1]");
-  if (misaligned({d_colsq, d_colsq_max, d_scale})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  return lsq_launched(twr::launch_lsq_col_scale(lsq->work.d.get(), lsq->work.n, d_colsq, d_colsq_max, rel_floor, d_scale,
-                                                static_cast<hipStream_t>(hip_stream)));
-}
-
-int twr_jac_lsq_solve_scaled(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
-                             const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream) {
-  if (!lsq || !d_jac || !d_b || !d_mu || !d_scale || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
-  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
-  if (misaligned({d_jac, d_b, d_w, d_mu, d_scale, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  if (!lsq->ws2) {
-    const int rc = twr_jac_lsq_reserve_scaled(lsq);
-    if (rc != TWR_OK) return rc;
-  }
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  const twr_jac_ops* ops = lsq->ops;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  return lsq_launched(twr::launch_lsq_solve_scaled(
-      lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, lsq->buf2, d_b, d_w, d_mu, d_scale, iters, tol, d_d, d_info, stream,
-      [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
-      [&](const double* w, double* z) {
-        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
-      }));
-}
-
-int twr_jac_lsq_reserve_onepass(twr_jac_lsq* lsq, int scaled) {
-  if (!lsq) return fail(TWR_ERR_INVALID, "null handle");
-  int rc = lsq->ops->normal_ready ? TWR_OK : twr_jac_ops_reserve_normal(lsq->ops);   // (tables of any tile serve)
-  if (rc == TWR_OK && scaled) rc = twr_jac_lsq_reserve_scaled(lsq);
-  if (rc != TWR_OK || lsq->ws3) return rc;
-  try {
-    DeviceScope on(lsq->device);
-    TWR_HIP(on.status);
-    lsq->ws3 = dev_alloc<double>(std::max<size_t>(16, sizeof(double) * (size_t)lsq->ws3_doubles));
-    lsq->buf3 = {lsq->ws3.get() + lsq->ws3_s, lsq->ws3.get() + lsq->ws3_u};
-    lsq->resident += 8 * lsq->ws3_doubles;
-    return TWR_OK;
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_HIP, e.what());
-  }
-}
-
-int twr_jac_lsq_solve_onepass(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
-                              const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream) {
-  if (!lsq || !d_jac || !d_b || !d_mu || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
-  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
-  if (misaligned({d_jac, d_b, d_w, d_mu, d_scale, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  twr_jac_ops* ops = lsq->ops;
-  if (!ops->normal_ready || !lsq->ws3 || (d_scale && !lsq->ws2)) {
-    const int rc = twr_jac_lsq_reserve_onepass(lsq, d_scale != nullptr);
-    if (rc != TWR_OK) return rc;
-  }
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  return lsq_launched(twr::launch_lsq_solve_onepass(
-      lsq->work.d.get(), lsq->work.n, lsq->buf, lsq->buf2, lsq->buf3, d_b, d_w, d_mu, d_scale, iters, tol, d_d, d_info, stream,
-      [&](const double* w, double* z) {
-        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
-      },
-      [&](const double* v, double* y, double* u) {
-        return twr::launch_jac_normal(ops->nwork.d.get(), ops->nwork.n, ops->n_lds_x, ops->n_tile, ops->nfold.d.get(), ops->nfold.n, d_jac, d_w, v, y,
-                                      ops->nslab.get(), u, stream);
-      }));
-}
-
-int twr_jac_lsq_solve_masked(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const double* d_w, const double* d_mu,
-                             const double* d_scale, int iters, double tol, double* d_d, double* d_info, void* hip_stream) {
-  if (!lsq || !d_jac || !d_b || !d_mu || !d_scale || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
-  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
-  if (misaligned({d_jac, d_b, d_w, d_mu, d_scale, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  if (!lsq->ws2) {
-    const int rc = twr_jac_lsq_reserve_scaled(lsq);
-    if (rc != TWR_OK) return rc;
-  }
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  const twr_jac_ops* ops = lsq->ops;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  return lsq_launched(twr::launch_lsq_solve_scaled(
-      lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, lsq->buf2, d_b, d_w, d_mu, d_scale, iters, tol, d_d, d_info, stream,
-      [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
-      [&](const double* w, double* z) {
-        return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
-      },
-      true));
-}
-
-int twr_jac_free_set(twr_jac_lsq* lsq, const double* d_x, const double* d_xlo, const double* d_xup, const double* d_z,
-                     const double* d_scale_in, double* d_scale_out, double* d_nfree, void* hip_stream) {
-  if (!lsq || !d_x || !d_xlo || !d_xup || !d_z || !d_scale_out || !d_nfree) return fail(TWR_ERR_INVALID, "null argument");
-  if (misaligned({d_x, d_xlo, d_xup, d_z, d_scale_in, d_scale_out, d_nfree})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  return lsq_launched(twr::launch_lm_free_set(lsq->work.d.get(), lsq->work.n, d_x, d_xlo, d_xup, d_z, d_scale_in, d_scale_out, d_nfree,
-                                              static_cast<hipStream_t>(hip_stream)));
-}
-
-int twr_structure_gram_pattern(const twr_structure* s, int32_t* row_ptr, int32_t* col_idx, int64_t* nnz) {
-  if (!s) return fail(TWR_ERR_INVALID, "null structure");
-  try {
-    std::vector<int32_t> rp, ci;
-    twr::GramPattern(s->s, &rp, &ci);
-    if (row_ptr) std::memcpy(row_ptr, rp.data(), rp.size() * sizeof(int32_t));
-    if (col_idx && !ci.empty()) std::memcpy(col_idx, ci.data(), ci.size() * sizeof(int32_t));
-    if (nnz) *nnz = (int64_t)ci.size();
-    return TWR_OK;
-  } catch (const twr::JacGramUnsupported& e) {
-    return fail(TWR_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_INVALID, e.what());
-  }
-}
-
-int twr_jac_ops_reserve_gram(twr_jac_ops* ops) {
-  if (!ops) return fail(TWR_ERR_INVALID, "null handle");
-  if (ops->gram_ready) return TWR_OK;
-  twr::JacGramPlan plan;
-  std::vector<twr::Structure> pats;
-  const int rc = ops_patterns(ops, &pats);
-  if (rc != TWR_OK) return rc;
-  try {
-    std::vector<const twr::Structure*> sp;
-    for (const twr::Structure& S : pats) sp.push_back(&S);
-    plan = twr::PlanJacGram(sp, ops->pattern_of_problem);
-    if (plan.x_off != ops->x_off || plan.g_off != ops->g_off || plan.j_off != ops->j_off)
-      throw std::runtime_error("the Gram plan's layout is not the handle's");
-  } catch (const twr::JacGramUnsupported& e) {
-    return fail(TWR_ERR_UNSUPPORTED, e.what());
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_INVALID, e.what());
-  }
-  try {
-    DeviceScope on(ops->device);
-    TWR_HIP(on.status);
-    TWR_HIP(twr::prepare_gram_cg());
-    const size_t tb = std::max<size_t>(16, plan.tables.size());
-    DevPtr<void> tables = dev_alloc<void>(tb);
-    if (!plan.tables.empty()) TWR_HIP(hipMemcpy(tables.get(), plan.tables.data(), plan.tables.size(), hipMemcpyHostToDevice));
-    plan.Place(reinterpret_cast<uint64_t>(tables.get()));
-    DevList<twr::JacGramWork> form;
-    DevList<twr::JacGramMulWork> mul;
-    if (!plan.form.empty()) form = upload(plan.form);
-    if (!plan.mul.empty()) mul = upload(plan.mul);
-    ops->gsolve = upload(plan.solve);
-    ops->gtables = std::move(tables);
-    ops->gform = std::move(form);
-    ops->gmul = std::move(mul);
-    ops->gram_off = plan.gram_off;
-    ops->gram_max_n = plan.max_n;
-    ops->resident += (int64_t)tb + (int64_t)(plan.form.size() * sizeof(twr::JacGramWork) + plan.mul.size() * sizeof(twr::JacGramMulWork) +
-                                             plan.solve.size() * sizeof(twr::JacGramSolveWork));
-    ops->gram_ready = true;
-    return TWR_OK;
-  } catch (const std::exception& e) {
-    return fail(TWR_ERR_HIP, e.what());
-  }
-}
-
-int twr_jac_ops_gram_layout(const twr_jac_ops* ops, int64_t* gram_off) {
-  if (!ops || !gram_off) return fail(TWR_ERR_INVALID, "null argument");
-  if (!ops->gram_ready) return fail(TWR_ERR_INVALID, "twr_jac_ops_reserve_gram has not been called");
-  std::memcpy(gram_off, ops->gram_off.data(), (ops->n_problems + 1) * sizeof(int64_t));
-  return TWR_OK;
-}
-
-int twr_jac_gram(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_gram, void* hip_stream) {
-  if (!ops || !d_jac || !d_gram) return fail(TWR_ERR_INVALID, "null argument");
-  if (misaligned({d_jac, d_w, d_gram})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  if (!ops->gram_ready) {
-    const int rc = twr_jac_ops_reserve_gram(ops);
-    if (rc != TWR_OK) return rc;
-  }
-  DeviceScope on(ops->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  return lsq_launched(twr::launch_jac_gram(ops->gform.d.get(), ops->gform.n, d_jac, d_w, d_gram, static_cast<hipStream_t>(hip_stream)));
-}
-
-int twr_jac_gram_mul(twr_jac_ops* ops, const double* d_gram, const double* d_v, double* d_u, void* hip_stream) {
-  if (!ops || !d_gram || !d_v || !d_u) return fail(TWR_ERR_INVALID, "null argument");
-  if (misaligned({d_gram, d_v, d_u})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  if (!ops->gram_ready) {
-    const int rc = twr_jac_ops_reserve_gram(ops);
-    if (rc != TWR_OK) return rc;
-  }
-  DeviceScope on(ops->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  return lsq_launched(twr::launch_jac_gram_mul(ops->gmul.d.get(), ops->gmul.n, d_gram, d_v, d_u, static_cast<hipStream_t>(hip_stream)));
-}
-
-int twr_jac_lsq_solve_gram(twr_jac_lsq* lsq, const double* d_gram, const double* d_z, const double* d_mu, const double* d_scale, int iters,
-                           double tol, double* d_d, double* d_info, void* hip_stream) {
-  if (!lsq || !d_gram || !d_z || !d_mu || !d_d || !d_info) return fail(TWR_ERR_INVALID, "null argument");
-  if (iters < 0 || !(tol >= 0.0)) return fail(TWR_ERR_INVALID, "iters and tol must not be negative");
-  if (misaligned({d_gram, d_z, d_mu, d_scale, d_d, d_info})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  twr_jac_ops* ops = lsq->ops;
-  if (!ops->gram_ready) {
-    const int rc = twr_jac_ops_reserve_gram(ops);
-    if (rc != TWR_OK) return rc;
-  }
-  DeviceScope on(lsq->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  return lsq_launched(twr::launch_gram_cg(ops->gsolve.d.get(), ops->gsolve.n, ops->gram_max_n, d_gram, d_z, d_mu, d_scale, iters, tol, d_d, d_info,
-                                          static_cast<hipStream_t>(hip_stream)));
-}
-
-int twr_jac_lm_params_default(twr_jac_lm_params* out) {
-  if (!out) return fail(TWR_ERR_INVALID, "null output");
-  out->cg_iters = 60;
-  out->power_iters = 30;
-  out->cg_tol = 1e-8;
-  out->mu_down = 1.0 / 3.0;
-  out->mu_up = 10.0;
-  out->mu_min = 1e-16;
-  out->mu_max = 1e16;
-  out->rel_floor = 1e-12;
-  out->tau = 1e-2;
-  out->merit_done = 0.0;
-  return TWR_OK;
-}
-
-int twr_jac_lm_create(twr_batch* batch, twr_jac_lsq* lsq, const twr_jac_lm_params* params, twr_jac_lm** out) {
-  if (!batch || !lsq || !params || !out) return fail(TWR_ERR_INVALID, "null argument");
-  const twr_jac_lm_params& q = *params;
-  if (q.cg_iters < 0 || q.power_iters < 0 || !(q.cg_tol >= 0.0) || !(q.mu_down > 0.0 && q.mu_down <= 1.0) || !(q.mu_up >= 1.0) ||
-      !(q.mu_min >= 0.0 && q.mu_min <= q.mu_max) || !std::isfinite(q.mu_up) || !std::isfinite(q.mu_max) ||
-      !(q.rel_floor > 0.0 && q.rel_floor <= 1.0) || !(q.tau > 0.0) || !std::isfinite(q.tau) || q.merit_done != q.merit_done)
-    return fail(TWR_ERR_INVALID, "bad LM parameters");
-  const twr_jac_ops* ops = lsq->ops;
-  if (batch->n_problems != ops->n_problems || batch->plan.x_off != ops->x_off || batch->plan.g_off != ops->g_off ||
-      batch->plan.j_off != ops->j_off)
-    return fail(TWR_ERR_INVALID, "the batch's layout is not the products handle's");
-  if (batch->device != lsq->device) return fail(TWR_ERR_INVALID, "the batch and the solver live on different devices");
-  const int n = batch->n_problems;
-  twr::JacLmPlan plan;   // (from the layout: the plan reads the sizes alone)
-  {
-    std::vector<twr::Structure> sizes(n);
-    std::vector<const twr::Structure*> sp(n);
-    std::vector<int32_t> sop(n);
-    for (int p = 0; p < n; ++p) {
-      sizes[p].n_vars = (int)(ops->x_off[p + 1] - ops->x_off[p]);
-      sizes[p].n_rows = (int)(ops->g_off[p + 1] - ops->g_off[p]);
-      sp[p] = &sizes[p], sop[p] = p;
-    }
-    try {
-      plan = twr::PlanJacLm(sp, sop);
-    } catch (const std::exception& e) {
-      return fail(TWR_ERR_INVALID, e.what());
-    }
-  }
-  if (plan.x_off != ops->x_off || plan.g_off != ops->g_off) return fail(TWR_ERR_INVALID, "the driver's plan does not match the layout");
-  const int rc = twr_jac_lsq_reserve_scaled(lsq);
-  if (rc != TWR_OK) return rc;
-  std::unique_ptr<twr_jac_lm> h(new twr_jac_lm());
-  try {
-    DeviceScope on(lsq->device);
-    TWR_HIP(on.status);
-    h->batch = batch, h->lsq = lsq, h->device = lsq->device, h->n_problems = n, h->params = q;
-    h->ws = dev_zeros<double>(std::max<size_t>(2, (size_t)plan.ws_doubles));
-    double* w = h->ws.get();
-    h->buf = {w + plan.ws_xt, w + plan.ws_d,  w + plan.ws_z,  w + plan.ws_colsq, w + plan.ws_colmax,  w + plan.ws_c,
-              w + plan.ws_cf, w + plan.ws_r,  w + plan.ws_b,  w + plan.ws_wa,    w + plan.ws_gt,      w + plan.ws_rt,
-              w + plan.ws_rec, w + plan.ws_mu, w + plan.ws_merit_t, w + plan.ws_merit_lin, w + plan.ws_nfree, w + plan.ws_info};
-    h->resident = 8 * std::max<int64_t>(2, plan.ws_doubles);
-    *out = h.release();
-    return TWR_OK;
-  } catch (const std::exception& e) {
-    twr_jac_lm_destroy(h.release());
-    return fail(TWR_ERR_HIP, e.what());
-  }
-}
-
-void twr_jac_lm_destroy(twr_jac_lm* lm) {
-  if (!lm) return;
-  DeviceScope on(lm->device);
-  delete lm;
-}
-
-int twr_jac_lm_bytes(const twr_jac_lm* lm, int64_t* resident) {
-  if (!lm) return fail(TWR_ERR_INVALID, "null handle");
-  if (resident) *resident = lm->resident;
-  return TWR_OK;
-}
-
-static_assert(TWR_JAC_LM_REC == twr::kLmRec, "the record of twr_jac_lm_state");
-
-int twr_jac_lm_set_solver(twr_jac_lm* lm, int solver) {
-  if (!lm) return fail(TWR_ERR_INVALID, "null handle");
-  if (solver != TWR_JAC_LM_CGLS && solver != TWR_JAC_LM_GRAM) return fail(TWR_ERR_INVALID, "solver is TWR_JAC_LM_CGLS or TWR_JAC_LM_GRAM");
-  if (lm->x) return fail(TWR_ERR_INVALID, "the solver is chosen between twr_jac_lm_create and twr_jac_lm_start");
-  if (solver == TWR_JAC_LM_GRAM && !lm->gram) {
-    twr_jac_ops* ops = lm->lsq->ops;
-    const int rc = twr_jac_ops_reserve_gram(ops);
-    if (rc != TWR_OK) return rc;
-    try {
-      DeviceScope on(lm->device);
-      TWR_HIP(on.status);
-      const int64_t doubles = std::max<int64_t>(2, ops->gram_off.back());
-      lm->gram = dev_zeros<double>((size_t)doubles);
-      lm->resident += 8 * doubles;
-    } catch (const std::exception& e) {
-      return fail(TWR_ERR_HIP, e.what());
-    }
-  }
-  lm->solver = solver;
-  return TWR_OK;
-}
-
-namespace {
-twr::LmParams lm_device_params(const twr_jac_lm_params& q) { return {q.mu_down, q.mu_up, q.mu_min, q.mu_max, q.tau, q.merit_done}; }
-
-// eval(BOTH) at x, violation, b = -r, the column norms and the scale with the running maximum, z = J^T(w o b), the free set
-int lm_linearise(twr_jac_lm* lm, int first, hipStream_t stream) {
-  twr_jac_lsq* lsq = lm->lsq;
-  twr_jac_ops* ops = lsq->ops;
-  const twr::LmBuffers& B = lm->buf;
-  const twr::JacLsqWork* work = lsq->work.d.get();
-  const int n = lm->n_problems;
-  int rc = twr_batch_eval(lm->batch, lm->x, lm->g, lm->jac, TWR_EVAL_BOTH, stream);
-  if (rc != TWR_OK) return rc;
-  hipError_t e = twr::launch_lsq_violation(work, n, lm->g, nullptr, B.r, B.wa, B.merit_lin, stream);
-  if (e == hipSuccess)   // (w o b goes to rt, which is free until the trial point's violation)
-    e = twr::jac_launch(twr::lm_rhs_kernel, n, twr::kLsqThreads, 0, stream, work, B.r, B.wa, B.merit_lin, B.b, B.rt, B.rec,
-                        lm->params.merit_done, first);
-  if (e == hipSuccess)
-    e = twr::launch_jac_colsq(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, lm->jac, B.wa, ops->slab.get(), B.colsq, stream);
-  if (e == hipSuccess) e = twr::launch_lsq_col_scale(work, n, B.colsq, B.colmax, lm->params.rel_floor, B.c, stream);
-  if (e == hipSuccess)
-    e = twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, lm->jac, B.rt, ops->slab.get(), B.z, stream);
-  if (e == hipSuccess) e = twr::launch_lm_free_set(work, n, lm->x, lm->xlo, lm->xup, B.z, B.c, B.cf, B.nfree, stream);
-  return lsq_launched(e);
-}
-}  // namespace
-
-int twr_jac_lm_start(twr_jac_lm* lm, double* d_x, const double* d_xlo, const double* d_xup, double* d_g, double* d_jac,
-                     void* hip_stream) {
-  if (!lm || !d_x || !d_xlo || !d_xup || !d_g || !d_jac) return fail(TWR_ERR_INVALID, "null argument");
-  if (misaligned({d_x, d_xlo, d_xup, d_g, d_jac})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(lm->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  lm->x = d_x, lm->xlo = d_xlo, lm->xup = d_xup, lm->g = d_g, lm->jac = d_jac;
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  twr_jac_lsq* lsq = lm->lsq;
-  twr_jac_ops* ops = lsq->ops;
-  const twr::LmBuffers& B = lm->buf;
-  const twr::JacLsqWork* work = lsq->work.d.get();
-  const int n = lm->n_problems, iters = lm->params.power_iters;
-  const twr::LmParams P = lm_device_params(lm->params);
-  // the power iteration borrows d (v), xt (cf o v), z (u) and gt (y)
-  hipError_t e = twr::jac_launch(twr::lm_project_kernel, n, twr::kLsqThreads, 0, stream, work, d_x, d_xlo, d_xup, B.colmax, B.d, B.rec, B.mu,
-                                 lm->params.tau);
-  if (e != hipSuccess) return lsq_launched(e);
-  const int rc = lm_linearise(lm, 1, stream);
-  if (rc != TWR_OK) return rc;
-  e = twr::jac_launch(twr::lm_normalise_kernel, n, twr::kLsqThreads, 0, stream, work, B.cf, B.d, B.z, B.xt, B.rec, B.mu, P, 0, iters == 0);
-  for (int k = 0; k < iters && e == hipSuccess; ++k) {
-    e = twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, B.xt, B.gt, stream);
-    if (e == hipSuccess) e = twr::jac_launch(twr::lm_weight_kernel, n, twr::kLsqThreads, 0, stream, work, B.wa, B.gt);
-    if (e == hipSuccess)
-      e = twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, B.gt, ops->slab.get(), B.z, stream);
-    if (e == hipSuccess)
-      e = twr::jac_launch(twr::lm_normalise_kernel, n, twr::kLsqThreads, 0, stream, work, B.cf, B.d, B.z, B.xt, B.rec, B.mu, P, 1,
-                          k == iters - 1);
-  }
-  return lsq_launched(e);
-}
-
-int twr_jac_lm_step(twr_jac_lm* lm, void* hip_stream) {
-  if (!lm) return fail(TWR_ERR_INVALID, "null handle");
-  if (!lm->x) return fail(TWR_ERR_INVALID, "twr_jac_lm_start has not been called");
-  DeviceScope on(lm->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  twr_jac_lsq* lsq = lm->lsq;
-  const twr_jac_ops* ops = lsq->ops;
-  const twr::LmBuffers& B = lm->buf;
-  const twr::JacLsqWork* work = lsq->work.d.get();
-  const int n = lm->n_problems;
-  int rc = lm_linearise(lm, 0, stream);
-  if (rc != TWR_OK) return rc;
-  const double* d_jac = lm->jac;
-  hipError_t e = hipSuccess;
-  if (lm->solver == TWR_JAC_LM_GRAM) {   // N = J^T W_a J once, then the whole masked solve on it in one launch (z is the linearisation's)
-    e = twr::launch_jac_gram(ops->gform.d.get(), ops->gform.n, d_jac, B.wa, lm->gram.get(), stream);
-    if (e == hipSuccess)
-      e = twr::launch_gram_cg(ops->gsolve.d.get(), ops->gsolve.n, ops->gram_max_n, lm->gram.get(), B.z, B.mu, B.cf, lm->params.cg_iters,
-                              lm->params.cg_tol, B.d, B.info, stream);
-  } else {
-    e = twr::launch_lsq_solve_scaled(
-        work, n, lsq->lds_x, lsq->buf, lsq->buf2, B.b, B.wa, B.mu, B.cf, lm->params.cg_iters, lm->params.cg_tol, B.d, B.info, stream,
-        [&](const double* v, double* y) { return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, d_jac, v, y, stream); },
-        [&](const double* w, double* z) {
-          return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, d_jac, w, ops->slab.get(), z, stream);
-        },
-        true);
-  }
-  if (e == hipSuccess)
-    e = twr::jac_launch(twr::lm_trial_kernel, n, twr::kLsqThreads, 0, stream, work, B.rec, lm->x, B.d, lm->xlo, lm->xup, B.xt);
-  if (e != hipSuccess) return lsq_launched(e);
-  rc = twr_batch_eval(lm->batch, B.xt, B.gt, nullptr, TWR_EVAL_VALUES, stream);
-  if (rc != TWR_OK) return rc;
-  e = twr::launch_lsq_violation(work, n, B.gt, nullptr, B.rt, nullptr, B.merit_t, stream);
-  if (e == hipSuccess)
-    e = twr::jac_launch(twr::lm_accept_kernel, n, twr::kLsqThreads, 0, stream, work, B.rec, B.mu, B.merit_t, B.info, B.nfree, lm->x, B.xt,
-                        lm_device_params(lm->params));
-  return lsq_launched(e);
-}
-
-int twr_jac_lm_state(twr_jac_lm* lm, double* d_out, void* hip_stream) {
-  if (!lm || !d_out) return fail(TWR_ERR_INVALID, "null argument");
-  if (misaligned({d_out})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  DeviceScope on(lm->device);
-  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
-  return lsq_launched(hipMemcpyAsync(d_out, lm->buf.rec, sizeof(double) * twr::kLmRec * (size_t)lm->n_problems, hipMemcpyDeviceToDevice,
-                                     static_cast<hipStream_t>(hip_stream)));
 }
 
 }  // extern "C"

@@ -13,7 +13,7 @@
 // No atomics; the order of every sum is a function of the pattern alone.  The row product and the CG multiply, then add (no fused
 // multiply-add: `fp contract(off)` in their bodies), every sum in the order stated here, so that the numpy restatement
 // (scripts/gram_cpu.py gram_cg_device) takes the same roundings in the same order and stops at the same iteration.
-// Included by capi.cc (compiled as HIP for gfx950).
+// Included by capi_jac.cc (compiled as HIP for gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -13,7 +13,7 @@
 // One workgroup of kLsqThreads lanes per problem in every kernel, the sums by lsq_sum over the index pairs of jac_lsq.hip: an order
 // fixed by the vector's length, so x after any number of steps has the same bits wherever the problem sits.  No atomics.  Every
 // index comes from the work record, never from the data.  The workspace is planned on the host (twr::PlanJacLm, structure.h).
-// Included by capi.cc (compiled as HIP for gfx950).
+// Included by capi_jac.cc (compiled as HIP for gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 

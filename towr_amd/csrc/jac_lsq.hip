@@ -16,7 +16,7 @@
 // that has stopped (converged, or bad input) is skipped by its workgroup in every later kernel: its d, r, p no longer change.
 // No atomics: every sum is taken by lsq_sum in an order fixed by the vector's length (structure.h), so a problem's outputs have
 // the same bits wherever it sits in whatever batch.  Every index comes from the work record, never from the data.
-// Included by capi.cc (compiled as HIP for gfx950).
+// Included by capi_jac.cc (compiled as HIP for gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -594,19 +594,21 @@ inline hipError_t launch_lsq_violation(const JacLsqWork* work, int n, const doub
 }
 
 // The whole solve: 3 launches to start, 5 per iteration (J p, step, J^T t and its fold, direction), none of them conditional.
-template <class Mul, class TMul>
+// J: the products with the Jacobian on J.stream, where the vector kernels go too: J.mul(v, y) for y = J v, J.tmul(w, z) for
+// z = J^T w and (the one-pass solve) J.normal(w, v, y, u) for u = J^T (w o (J v)), y = J v.
+template <class Products>
 inline hipError_t launch_lsq_solve(const JacLsqWork* work, int n, int lds_x, const LsqBuffers& ws, const double* b, const double* w,
-                                   const double* mu, int iters, double tol, double* d, double* info, hipStream_t stream, Mul mul,
-                                   TMul tmul) {
+                                   const double* mu, int iters, double tol, double* d, double* info, const Products& J) {
+  const hipStream_t stream = J.stream;
   const size_t lds = sizeof(double) * (size_t)lds_x;
   const double tol2 = tol * tol;
   hipError_t e = jac_launch(lsq_start_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, ws.r, ws.t);
-  if (e == hipSuccess) e = tmul(ws.t, ws.z);
+  if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
   if (e == hipSuccess) e = jac_launch(lsq_dir_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, d, ws.p, info, tol2, 1, lds_x);
   for (int k = 0; k < iters && e == hipSuccess; ++k) {
-    e = mul(ws.p, ws.q);
+    e = J.mul(ws.p, ws.q);
     if (e == hipSuccess) e = jac_launch(lsq_step_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.q, w, ws.p, d, ws.r, ws.t);
-    if (e == hipSuccess) e = tmul(ws.t, ws.z);
+    if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
     if (e == hipSuccess)
       e = jac_launch(lsq_dir_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, d, ws.p, info, tol2, 0, lds_x);
   }
@@ -619,11 +621,11 @@ struct LsqOnepassBuffers {   // the third allocation (twr_jac_lsq_solve_onepass)
 
 // The one-pass solve: 4 launches to start (start, J^T t and its fold, first), 3 per iteration (the one-pass product, its fold,
 // the vector kernel), none of them conditional.  c NULL: the unscaled step; else sc holds e and c o p.
-template <class TMul, class Normal>
+template <class Products>
 inline hipError_t launch_lsq_solve_onepass(const JacLsqWork* work, int n, const LsqBuffers& ws, const LsqScaledBuffers& sc,
                                            const LsqOnepassBuffers& op, const double* b, const double* w, const double* mu,
-                                           const double* c, int iters, double tol, double* d, double* info, hipStream_t stream,
-                                           TMul tmul, Normal normal) {
+                                           const double* c, int iters, double tol, double* d, double* info, const Products& J) {
+  const hipStream_t stream = J.stream;
   const double tol2 = tol * tol;
   const auto vec = [&](int first) {
     if (c)
@@ -634,10 +636,10 @@ inline hipError_t launch_lsq_solve_onepass(const JacLsqWork* work, int n, const 
   };
   hipError_t e = c ? jac_launch(lsq_start_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, sc.e, ws.r, ws.t)
                    : jac_launch(lsq_start_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, ws.r, ws.t);
-  if (e == hipSuccess) e = tmul(ws.t, ws.z);
+  if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
   if (e == hipSuccess) e = vec(1);
   for (int k = 0; k < iters && e == hipSuccess; ++k) {
-    e = normal(c ? sc.cp : ws.p, ws.q, op.u);
+    e = J.normal(w, c ? sc.cp : ws.p, ws.q, op.u);
     if (e == hipSuccess) e = vec(0);
   }
   return e;
@@ -651,22 +653,23 @@ inline hipError_t launch_lsq_col_scale(const JacLsqWork* work, int n, const doub
 // The same sequence on J C in e = d / c: the product kernels as they are, the vector kernels' SCALED instantiations.  masked:
 // the direction kernel's MASKED instantiation (twr_jac_lsq_solve_masked); the start and step kernels serve as they are, since
 // p_k = +0 keeps e_k and d_k = c_k e_k at +0.
-template <class Mul, class TMul>
+template <class Products>
 inline hipError_t launch_lsq_solve_scaled(const JacLsqWork* work, int n, int lds_x, const LsqBuffers& ws, const LsqScaledBuffers& sc,
                                           const double* b, const double* w, const double* mu, const double* c, int iters, double tol,
-                                          double* d, double* info, hipStream_t stream, Mul mul, TMul tmul, bool masked = false) {
+                                          double* d, double* info, const Products& J, bool masked) {
+  const hipStream_t stream = J.stream;
   const size_t lds = sizeof(double) * (size_t)lds_x;
   const double tol2 = tol * tol;
   const auto dir = masked ? lsq_dir_masked_kernel : lsq_dir_scaled_kernel;
   hipError_t e = jac_launch(lsq_start_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, sc.e, ws.r, ws.t);
-  if (e == hipSuccess) e = tmul(ws.t, ws.z);
+  if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
   if (e == hipSuccess)
     e = jac_launch(dir, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 1, lds_x);
   for (int k = 0; k < iters && e == hipSuccess; ++k) {
-    e = mul(sc.cp, ws.q);
+    e = J.mul(sc.cp, ws.q);
     if (e == hipSuccess)
       e = jac_launch(lsq_step_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.q, w, ws.p, c, sc.e, d, ws.r, ws.t);
-    if (e == hipSuccess) e = tmul(ws.t, ws.z);
+    if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
     if (e == hipSuccess)
       e = jac_launch(dir, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 0, lds_x);
   }

@@ -8,7 +8,7 @@
 // every output is written by exactly one lane, which sums its terms in an order fixed by the pattern alone, so a problem's
 // outputs have the same bits wherever it sits in whatever batch.  Every index comes from the plan's tables; J, v and w are
 // only multiplied and added, so a NaN or Inf in one problem's inputs reaches that problem's outputs and no other's.
-// Included by capi.cc (compiled as HIP for gfx950).
+// Included by capi_jac.cc (compiled as HIP for gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 
