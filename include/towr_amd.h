@@ -258,6 +258,32 @@ int twr_batch_streaming_stores(const twr_batch* b);
  * such a batch is evaluated by a kernel whose waves each own one slice kind and load its tables once per launch, when the
  * resident grid divides into the kinds (structure.h DynUniformCols); the values written are the same bits either way. */
 int twr_batch_dyn_uniform_kinds(const twr_batch* b);
+/* The launches a call on this batch would issue, in order, without issuing them: which kernel, which template instantiation
+ * of it, grid, block and dynamic LDS.  Read-only: planned from the same shape and by the same planner as the call itself
+ * (structure.h MakeEvalShape / PlanEval), so it is what the device runs, for this device's CU count and memory-side cache.
+ *   request TWR_PLAN_EVAL:       twr_batch_eval(flags); events != 0: as between twr_batch_profile_begin and _end
+ *   request TWR_PLAN_SCORES:     twr_batch_eval_scores      (flags and events are ignored: these record no events)
+ *   request TWR_PLAN_SCORE_BEST: twr_batch_eval_score_best
+ * Up to max_steps steps are written; *n_steps is the number the call issues (event records are not steps).
+ *   kernel:        "dyn_kernel", "dyn_uniform_kernel", "rom_kernel", "eval_fused_kernel", "phase_locate_kernel",
+ *                  "dyn_phase_kernel", "rom_phase_kernel", "node_kernel", "node_kernel2", "node_chunk_kernel",
+ *                  "eval_values_kernel", "eval_scores_kernel", "score_fold_kernel", "score_kernel", "best_kernel"
+ *   instantiation: the kernel with its template key, e.g. "eval_fused_kernel<34,xc2,GJNT>", "rom_kernel<26,J>",
+ *                  "dyn_uniform_kernel<GJ,xc4>", "eval_values_kernel<5>"; the plain name of a kernel with one body
+ *   store:         "G", "J", "GJ", "JNT", "GJNT" (NT: non-temporal copy-out stores); "" for a kernel without the parameter
+ *   nit:           store instructions of the copy-out (0: run-time length); xc: 64-entry chunks of the dyn staging maps, or the
+ *                  doubles of x per thread (NX) of the values-only / scoring kernels
+ *   uniform_kinds: slice kinds of a dyn_uniform_kernel launch, else 0 */
+enum { TWR_PLAN_EVAL = 0, TWR_PLAN_SCORES = 1, TWR_PLAN_SCORE_BEST = 2 };
+typedef struct twr_launch_step {
+  char kernel[32];
+  char instantiation[48];
+  char store[8];
+  int32_t nit, xc;
+  int32_t grid, block, lds_bytes;
+  int32_t uniform_kinds;
+} twr_launch_step;
+int twr_batch_eval_plan(const twr_batch* b, int request, int flags, int events, twr_launch_step* steps, int max_steps, int* n_steps);
 /* Ragged layout of the batch arrays, each n_problems+1 prefix sums in units of doubles:
  * problem p owns x[x_off[p]..x_off[p+1]), g[g_off[p]..), jac[jac_off[p]..). */
 int twr_batch_layout(const twr_batch* b, int64_t* x_off, int64_t* g_off, int64_t* jac_off);

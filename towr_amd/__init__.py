@@ -59,6 +59,12 @@ class SetInfo(C.Structure):
                 ("nnz_offset", C.c_int32), ("nnz", C.c_int32)]
 
 
+class LaunchStep(C.Structure):
+    """twr_launch_step: one launch of a planned call (Batch.eval_plan)."""
+    _fields_ = [("kernel", C.c_char * 32), ("instantiation", C.c_char * 48), ("store", C.c_char * 8), ("nit", C.c_int32),
+                ("xc", C.c_int32), ("grid", C.c_int32), ("block", C.c_int32), ("lds_bytes", C.c_int32), ("uniform_kinds", C.c_int32)]
+
+
 class JacLmParams(C.Structure):
     """twr_jac_lm_params"""
     _fields_ = [("cg_iters", C.c_int32), ("power_iters", C.c_int32), ("cg_tol", C.c_double), ("mu_down", C.c_double),
@@ -142,6 +148,7 @@ def lib():
         L.twr_batch_table_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.twr_batch_streaming_stores.argtypes = [C.c_void_p]
         L.twr_batch_dyn_uniform_kinds.argtypes = [C.c_void_p]
+        L.twr_batch_eval_plan.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(LaunchStep), C.c_int, C.POINTER(C.c_int)]
         L.twr_batch_layout.argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         L.twr_batch_eval.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.twr_batch_status.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]
@@ -511,6 +518,19 @@ class Batch:
         """Slices per problem of the "dynamic" set when every problem references one structure with fixed timings (the
         batch may then run dyn_uniform_kernel), else 0 (twr_batch_dyn_uniform_kinds)."""
         return int(lib().twr_batch_dyn_uniform_kinds(self._h))
+
+    def eval_plan(self, flags=EVAL_BOTH, events=False, request="eval"):
+        """The launches a call on this batch would issue, in order, without issuing them (twr_batch_eval_plan): a list of dicts
+        {kernel, instantiation, store, nit, xc, grid, block, lds_bytes, uniform_kinds}, kernels and instantiations by name
+        ("eval_fused_kernel", "eval_fused_kernel<34,xc2,GJ>").  request: "eval" (eval_device with `flags`; events=True: as
+        between profile_begin and profile_end), "scores" (eval_scores_device) or "score_best" (eval_score_best_device)."""
+        req = {"eval": 0, "scores": 1, "score_best": 2}[request]
+        steps = (LaunchStep * 16)()
+        n = C.c_int(0)
+        _check(lib().twr_batch_eval_plan(self._h, req, int(flags), int(bool(events)), steps, len(steps), C.byref(n)))
+        assert n.value <= len(steps)
+        return [dict(kernel=s.kernel.decode(), instantiation=s.instantiation.decode(), store=s.store.decode(), nit=s.nit, xc=s.xc,
+                     grid=s.grid, block=s.block, lds_bytes=s.lds_bytes, uniform_kinds=s.uniform_kinds) for s in steps[:n.value]]
 
     def status(self, stream=0):
         """Per-problem non-finite flags of the last eval_device(..., flags | EVAL_CHECK): bit 0 g, bit 1 jac."""

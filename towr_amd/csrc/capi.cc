@@ -488,6 +488,46 @@ static twr::LaunchTuning tuning_knobs() {
   return t;
 }
 
+// The shape of a call on this batch (structure.h MakeEvalShape): what twr_batch_eval, the scoring entry points and
+// twr_batch_eval_plan all plan from.
+static twr::EvalShape eval_shape(const twr_batch* b, int flags, bool events) {
+  twr::EvalCounts c;
+  c.dyn = b->dyn.n, c.rom = b->rom.n, c.node = b->node.n, c.flat = b->flat.n, c.pdyn = b->pdyn.n, c.ploc = b->ploc.n, c.prom = b->prom.n;
+  for (int f = 0; f < 4; ++f) c.fam[f] = b->fam[f].n;
+  return twr::MakeEvalShape(b->plan, c, b->n_cu, flags, events, tuning_knobs());
+}
+
+int twr_batch_eval_plan(const twr_batch* b, int request, int flags, int events, twr_launch_step* steps, int max_steps, int* n_steps) {
+  if (!b || !n_steps || (max_steps > 0 && !steps)) return fail(TWR_ERR_INVALID, "null argument");
+  if (request != TWR_PLAN_EVAL && request != TWR_PLAN_SCORES && request != TWR_PLAN_SCORE_BEST) return fail(TWR_ERR_INVALID, "unknown request");
+  if (request == TWR_PLAN_EVAL && (flags & TWR_EVAL_BOTH) == 0) return fail(TWR_ERR_INVALID, "flags select nothing");
+  const int f = request == TWR_PLAN_EVAL ? flags & TWR_EVAL_BOTH : twr::kEvalScores | (request == TWR_PLAN_SCORE_BEST ? twr::kEvalBest : 0);
+  const twr::EvalPlan plan = twr::PlanEval(eval_shape(b, f, events != 0));
+  int n = 0;
+  for (int i = 0; i < plan.n; ++i) {
+    const twr::LaunchStep& p = plan.step[i];
+    if (p.kernel == twr::Launch::kEvent) continue;
+    if (n < max_steps) {
+      twr_launch_step& o = steps[n];
+      std::memset(&o, 0, sizeof(o));
+      std::strncpy(o.kernel, twr::KernelName(p), sizeof(o.kernel) - 1);
+      std::strncpy(o.instantiation, twr::InstantiationName(p).c_str(), sizeof(o.instantiation) - 1);
+      const bool has_store = p.kernel == twr::Launch::kDyn || p.kernel == twr::Launch::kRom || p.kernel == twr::Launch::kFused ||
+                             p.kernel == twr::Launch::kDynPhase || p.kernel == twr::Launch::kRomPhase || p.kernel == twr::Launch::kChunk;
+      if (has_store) std::strncpy(o.store, twr::StoreName(p.store), sizeof(o.store) - 1);
+      o.nit = p.nit;
+      o.xc = p.xc;
+      o.grid = p.grid;
+      o.block = p.block;
+      o.lds_bytes = p.lds;
+      o.uniform_kinds = p.uni.s;
+    }
+    ++n;
+  }
+  *n_steps = n;
+  return TWR_OK;
+}
+
 int twr_batch_eval(twr_batch* b, const double* d_x, double* d_g, double* d_jac, int flags, void* hip_stream) {
   if (!b || !d_x) return fail(TWR_ERR_INVALID, "null argument");
   if ((flags & TWR_EVAL_BOTH) == 0) return fail(TWR_ERR_INVALID, "flags select nothing");
@@ -500,17 +540,7 @@ int twr_batch_eval(twr_batch* b, const double* d_x, double* d_g, double* d_jac, 
   hipEvent_t* ev = nullptr;
   if (b->prof_count < b->prof_capacity) ev = b->prof_events.ev.data() + 4 * b->prof_count++;
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
-  const twr::BatchPlan& P = b->plan;
-  twr::EvalShape s;
-  s.n_cu = b->n_cu;
-  s.dyn = b->dyn.n; s.rom = b->rom.n; s.node = b->node.n; s.flat = b->flat.n; s.pdyn = b->pdyn.n; s.ploc = b->ploc.n; s.prom = b->prom.n;
-  for (int f = 0; f < 4; ++f) s.fam[f] = b->fam[f].n;
-  s.rom_max_vals = P.rom_max_vals; s.flat_max_x = P.flat_max_x; s.dyn_map_chunks = P.dyn_map_chunks; s.node_families = P.node_families;
-  s.pdyn_img_cap = P.pdyn_img_cap; s.prom_img_cap = P.prom_img_cap; s.stream_nt = P.stream_nt;
-  s.dyn_uniform = P.dyn_uniform;
-  s.flags = flags & TWR_EVAL_BOTH;
-  s.events = ev != nullptr;
-  s.tuning = tuning_knobs();
+  const twr::EvalShape s = eval_shape(b, flags & TWR_EVAL_BOTH, ev != nullptr);
   const twr::EvalBuffers buf{b->dyn.d.get(), b->rom.d.get(), b->node.d.get(), b->flat.d.get(),
                              {b->fam[0].d.get(), b->fam[1].d.get(), b->fam[2].d.get(), b->fam[3].d.get()},
                              b->pdyn.d.get(), b->ploc.d.get(), b->prom.d.get(), d_x, d_g, d_jac, b->dump.get()};
@@ -803,15 +833,7 @@ int eval_scores(twr_batch* b, const double* d_x, double* d_g, double* d_scores, 
   DeviceScope on(b->device);
   if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
   const twr::BatchPlan& P = b->plan;
-  twr::EvalShape s;
-  s.n_cu = b->n_cu;
-  s.dyn = b->dyn.n; s.rom = b->rom.n; s.node = b->node.n; s.flat = b->flat.n; s.pdyn = b->pdyn.n; s.ploc = b->ploc.n; s.prom = b->prom.n;
-  for (int f = 0; f < 4; ++f) s.fam[f] = b->fam[f].n;
-  s.rom_max_vals = P.rom_max_vals; s.flat_max_x = P.flat_max_x; s.dyn_map_chunks = P.dyn_map_chunks; s.node_families = P.node_families;
-  s.pdyn_img_cap = P.pdyn_img_cap; s.prom_img_cap = P.prom_img_cap; s.stream_nt = P.stream_nt;
-  s.flags = twr::kEvalScores | (best ? twr::kEvalBest : 0);
-  s.score_fused = P.score_fused;
-  s.tuning = tuning_knobs();
+  const twr::EvalShape s = eval_shape(b, twr::kEvalScores | (best ? twr::kEvalBest : 0), false);
   twr::EvalBuffers buf{b->dyn.d.get(), b->rom.d.get(), b->node.d.get(), b->flat.d.get(),
                        {b->fam[0].d.get(), b->fam[1].d.get(), b->fam[2].d.get(), b->fam[3].d.get()},
                        b->pdyn.d.get(), b->ploc.d.get(), b->prom.d.get(), d_x, P.score_fused ? nullptr : d_g, nullptr, b->dump.get()};

@@ -2333,6 +2333,78 @@ EvalPlan PlanEval(const EvalShape& s) {
   return plan;
 }
 
+EvalCounts CountsOf(const BatchPlan& P) {
+  const BatchPlan::Lists& L = P.lists;
+  EvalCounts c;
+  c.dyn = (int)L.dyn.size(), c.rom = (int)L.rom.size(), c.node = std::max(0, (int)L.node.size() - 1), c.flat = (int)L.flat.size();
+  for (int f = 0; f < 4; ++f) c.fam[f] = (int)L.fam[f].size();
+  c.pdyn = (int)L.pdyn.size(), c.ploc = (int)L.ploc.size(), c.prom = (int)L.prom.size();
+  return c;
+}
+
+EvalShape MakeEvalShape(const BatchPlan& P, const EvalCounts& c, int n_cu, int flags, bool events, const LaunchTuning& tuning) {
+  const bool scoring = flags & kEvalScores;
+  EvalShape s;
+  s.n_cu = n_cu;
+  s.dyn = c.dyn, s.rom = c.rom, s.node = c.node, s.flat = c.flat, s.pdyn = c.pdyn, s.ploc = c.ploc, s.prom = c.prom;
+  for (int f = 0; f < 4; ++f) s.fam[f] = c.fam[f];
+  s.rom_max_vals = P.rom_max_vals, s.flat_max_x = P.flat_max_x, s.dyn_map_chunks = P.dyn_map_chunks, s.node_families = P.node_families;
+  s.pdyn_img_cap = P.pdyn_img_cap, s.prom_img_cap = P.prom_img_cap, s.stream_nt = P.stream_nt;
+  if (!scoring) s.dyn_uniform = P.dyn_uniform;
+  s.flags = scoring ? flags & (kEvalScores | kEvalBest) : flags & 3;
+  s.events = events && !scoring;
+  s.score_fused = scoring && P.score_fused;
+  s.tuning = tuning;
+  return s;
+}
+
+const char* StoreName(int store) {
+  switch (store) {
+    case kStoreG: return "G";
+    case kStoreJ: return "J";
+    case kStoreGJ: return "GJ";
+    case kStoreJNT: return "JNT";
+    case kStoreGJNT: return "GJNT";
+  }
+  return "?";
+}
+
+const char* KernelName(const LaunchStep& p) {
+  switch (p.kernel) {
+    case Launch::kEvent: return "";
+    case Launch::kDyn: return p.uni.s > 0 ? "dyn_uniform_kernel" : "dyn_kernel";
+    case Launch::kRom: return "rom_kernel";
+    case Launch::kFused: return "eval_fused_kernel";
+    case Launch::kLocate: return "phase_locate_kernel";
+    case Launch::kDynPhase: return "dyn_phase_kernel";
+    case Launch::kRomPhase: return "rom_phase_kernel";
+    case Launch::kNode: return "node_kernel";
+    case Launch::kNode2: return "node_kernel2";
+    case Launch::kChunk: return "node_chunk_kernel";
+    case Launch::kValues: return "eval_values_kernel";
+    case Launch::kScores: return "eval_scores_kernel";
+    case Launch::kFold: return "score_fold_kernel";
+    case Launch::kScoreG: return "score_kernel";
+    case Launch::kBest: return "best_kernel";
+  }
+  return "?";
+}
+
+std::string InstantiationName(const LaunchStep& p) {
+  const std::string k = KernelName(p), st = StoreName(p.store);
+  switch (p.kernel) {
+    case Launch::kDyn: return k + "<" + st + ",xc" + std::to_string(p.xc) + ">";
+    case Launch::kRom:
+    case Launch::kDynPhase:
+    case Launch::kRomPhase: return k + "<" + std::to_string(p.nit) + "," + st + ">";
+    case Launch::kFused: return k + "<" + std::to_string(p.nit) + ",xc" + std::to_string(p.xc) + "," + st + ">";
+    case Launch::kChunk: return k + "<" + st + ">";
+    case Launch::kValues:
+    case Launch::kScores: return k + "<" + std::to_string(p.xc) + ">";
+    default: return k;
+  }
+}
+
 // ---------------------------------------------------------------- products with the Jacobian values (jac_products.hip)
 namespace {
 void CheckPattern(const Structure& S) {

@@ -283,6 +283,23 @@ struct EvalPlan {
   LaunchStep step[kMaxSteps];
 };
 EvalPlan PlanEval(const EvalShape& shape);
+// The shape of one call, assembled in ONE place for twr_batch_eval, the scoring entry points and twr_batch_eval_plan (and the
+// host checks of the plans): the list counts as the batch holds them on the device, the policy PlanBatch decided, the request.
+// `flags`: TWR_EVAL_* bits of an evaluation, or kEvalScores (| kEvalBest).  A scoring request records no per-kernel events and
+// plans its fall-back evaluation without the uniform dyn list (its launches are the general kernels').
+struct EvalCounts {
+  int dyn = 0, rom = 0, node = 0, flat = 0, fam[4] = {0, 0, 0, 0}, pdyn = 0, ploc = 0, prom = 0;
+};
+EvalCounts CountsOf(const BatchPlan& plan);   // of a plan that still holds its lists (node: without the end entry)
+EvalShape MakeEvalShape(const BatchPlan& plan, const EvalCounts& counts, int n_cu, int flags, bool events, const LaunchTuning& tuning);
+// A step as the kernel it launches and the instantiation of it, spelled as the kernels' template lists are keyed:
+//   dyn_kernel<GJ,xc2>  dyn_uniform_kernel<JNT,xc4>  rom_kernel<26,GJ>  eval_fused_kernel<34,xc2,GJNT>  dyn_phase_kernel<40,J>
+//   rom_phase_kernel<0,GJ>  node_chunk_kernel<G>  eval_values_kernel<3>  eval_scores_kernel<8>
+// and the plain names of the kernels that have one body (node_kernel, node_kernel2, phase_locate_kernel, score_fold_kernel,
+// score_kernel, best_kernel).  "" for an event.
+const char* StoreName(int store);
+const char* KernelName(const LaunchStep& step);
+std::string InstantiationName(const LaunchStep& step);
 // Products with a batch's Jacobian values (twr_jac_mul: y = J v, twr_jac_tmul: z = J^T w; jac_products.hip), planned on the host
 // (no HIP).  The CSC view of a structure's CSR pattern: col_ptr[n + 1]; per entry its row and its position in the CSR value
 // array, rows ascending within a column.  Throws when a row's columns do not ascend strictly (unsorted or duplicate entries)
