@@ -29,6 +29,20 @@
 //                        compare them with the reference's own sets on this x: names, rows, bounds, values, Jacobian
 //                        (needs -DTOWR_AMD_ROOT=<repository> at configure time, libtowr_amd.so and a GPU); exit code 3
 //                        when they differ by more than 1e-9 relative
+//   the extractors fpowr runs on a solution (fpowr/include/fpowr/{footstep_plan_extractor,initial_guess_extractor,
+//   nearest_plane_lookup}.h, included below where they lie), on the splines as EvaluateConstraints(x) left them.  They
+//   compile on the stand-ins for ROS / xpp / tf / boost::geometry under subset/fpowr_deps; exit code 4 where the build has
+//   them compiled out, exit code 5 for a sample time the reference's Spline::GetSegmentID is not defined for
+//   (t > T + 1e-10, which GetTrajectory's own loop reaches when an accumulated t falls into (T + 1e-10, T + 1e-5]):
+//     --sample DT        <out prefix>_traj.txt: fpowr::GetTrajectory(solution, DT), one line per state,
+//                        [t | base lin p v a (9) | q w x y z | w (3) | wd (3) | per foot: contact, p v a (9), force (3)],
+//                        the feet in xpp order (fpowr_xpp_ee_map.h is executed)
+//     --guess-times FILE <out prefix>_guess.txt: fpowr::ExtractInitialGuesses for the times in FILE (one per line, in
+//                        that order), 49 doubles per line: time, state (12), controls (36)
+//     --planes FILE HORIZON   <out prefix>_plan.txt: what fpowr::ExtractFootstepPlan puts into the message for the planar
+//                        regions in FILE (one line per region: position x y z, orientation x y z w, number of boundary
+//                        points, then their local x y) and the time horizon: per footstep state one line, the
+//                        duration, then the contact_set (plane index per foot, -1 = in the air)
 #include <ifopt/problem.h>
 #include <towr/initialization/gait_generator.h>
 #include <towr/nlp_formulation.h>
@@ -37,6 +51,13 @@
 #if __has_include(<grid_map_ros/grid_map_ros.hpp>) && __has_include(<convex_plane_decomposition_msgs/PlanarTerrain.h>)
 #include <towr/terrain/grid_height_map.h>
 #define TWR_REF_HAVE_GRID_MAP 1
+#endif
+
+#ifdef TWR_REF_EXTRACTORS
+// one translation unit only: the three headers define non-inline functions
+#include <fpowr/footstep_plan_extractor.h>
+#include <fpowr/initial_guess_extractor.h>
+#include <fpowr/nearest_plane_lookup.h>
 #endif
 
 #include <cmath>
@@ -48,6 +69,17 @@
 
 #ifdef TWR_WITH_BINDING
 #include "towr_binding.h"
+#endif
+
+#ifdef TWR_REF_EXTRACTORS
+// true when GetTrajectory(solution, dt) stays inside what Spline::GetSegmentID defines: the loop of
+// footstep_plan_extractor.h:22-50 repeated on the times alone
+static bool SampleTimesDefined(double T, double dt) {
+  if (!(dt > 0.0)) return false;
+  for (double t = 0.0; t <= T + 1e-5; t += dt)
+    if (t > T + 1e-10) return false;
+  return true;
+}
 #endif
 
 int main(int argc, char** argv) {
@@ -65,6 +97,8 @@ int main(int argc, char** argv) {
   double dur_base_poly = 0.0, dt_base_motion = 0.0, base_z = std::nan("");
   int polys_swing = 0, polys_force = 0;
   bool binding = false;
+  double sample_dt = 0.0, plan_horizon = 0.0;
+  std::string guess_file, planes_file;
   for (int i = 9; i < argc; ++i) {
     const std::string a = argv[i];
     if (a == "--phases" && i + 1 < argc) phases_file = argv[++i];
@@ -85,6 +119,12 @@ int main(int argc, char** argv) {
       dt_base_motion = std::atof(argv[++i]);
       base_z = std::atof(argv[++i]);
     } else if (a == "--binding") binding = true;
+    else if (a == "--sample" && i + 1 < argc) sample_dt = std::atof(argv[++i]);
+    else if (a == "--guess-times" && i + 1 < argc) guess_file = argv[++i];
+    else if (a == "--planes" && i + 2 < argc) {
+      planes_file = argv[++i];
+      plan_horizon = std::atof(argv[++i]);
+    }
     else {
       std::fprintf(stderr, "unknown option %s\n", a.c_str());
       return 2;
@@ -206,6 +246,102 @@ int main(int argc, char** argv) {
     }
   }
   std::printf("ref_dump: n=%d m=%d nnz=%d\n", (int)x.size(), (int)g.size(), (int)jac.nonZeros());
+
+  if (sample_dt != 0.0 || !guess_file.empty() || !planes_file.empty()) {
+#ifdef TWR_REF_EXTRACTORS
+    // (`solution` holds x: EvaluateConstraints above set the variables, and the splines observe them)
+    const double T_total = solution.base_linear_->GetTotalTime();
+    auto goal = std::make_shared<fpowr::FootstepPlanGoal>();
+    if (sample_dt != 0.0) {
+      if (!SampleTimesDefined(T_total, sample_dt)) {
+        std::fprintf(stderr, "--sample %.17g: a sample time beyond T + 1e-10 (T = %.17g)\n", sample_dt, T_total);
+        return 5;
+      }
+      std::ofstream ot(prefix + "_traj.txt");
+      ot.precision(17);
+      for (const auto& st : fpowr::GetTrajectory(solution, sample_dt)) {
+        ot << st.t_global_;
+        for (const Eigen::VectorXd* v : {&st.base_.lin.p_, &st.base_.lin.v_, &st.base_.lin.a_})
+          for (int d = 0; d < 3; ++d) ot << " " << (*v)(d);
+        ot << " " << st.base_.ang.q.w() << " " << st.base_.ang.q.x() << " " << st.base_.ang.q.y() << " " << st.base_.ang.q.z();
+        for (int d = 0; d < 3; ++d) ot << " " << st.base_.ang.w(d);
+        for (int d = 0; d < 3; ++d) ot << " " << st.base_.ang.wd(d);
+        for (auto ee : st.ee_contact_.GetEEsOrdered()) {
+          ot << " " << (st.ee_contact_.at(ee) ? 1 : 0);
+          for (const Eigen::VectorXd* v : {&st.ee_motion_.at(ee).p_, &st.ee_motion_.at(ee).v_, &st.ee_motion_.at(ee).a_})
+            for (int d = 0; d < 3; ++d) ot << " " << (*v)(d);
+          for (int d = 0; d < 3; ++d) ot << " " << st.ee_forces_.at(ee)(d);
+        }
+        ot << "\n";
+      }
+    }
+    if (!guess_file.empty()) {
+      std::ifstream in(guess_file);
+      for (double t; in >> t;) {
+        if (!(t >= 0.0 && t <= T_total + 1e-10)) {
+          std::fprintf(stderr, "--guess-times: %.17g lies outside [0, T + 1e-10] (T = %.17g)\n", t, T_total);
+          return 5;
+        }
+        goal->state_sample_times.push_back(t);
+      }
+      fpowr::InitialGuessArray msg;
+      fpowr::ExtractInitialGuesses(goal, solution, msg);
+      std::ofstream og2(prefix + "_guess.txt");
+      og2.precision(17);
+      for (const auto& ig : msg.initial_guesses) {
+        og2 << ig.time;
+        for (double v : ig.state) og2 << " " << v;
+        for (double v : ig.controls) og2 << " " << v;
+        og2 << "\n";
+      }
+    }
+    if (!planes_file.empty()) {
+      if (!SampleTimesDefined(T_total, 0.01)) {   // (ExtractFootstepPlan samples at its fixed 0.01 s)
+        std::fprintf(stderr, "--planes: a sample time of the 0.01 s trajectory lies beyond T + 1e-10 (T = %.17g)\n", T_total);
+        return 5;
+      }
+      std::ifstream in(planes_file);
+      std::string line;
+      while (std::getline(in, line)) {
+        std::istringstream ls(line);
+        convex_plane_decomposition_msgs::PlanarRegion region;
+        auto& pp = region.plane_parameters;
+        int k = 0;
+        if (!(ls >> pp.position.x >> pp.position.y >> pp.position.z >> pp.orientation.x >> pp.orientation.y >> pp.orientation.z >>
+              pp.orientation.w >> k))
+          continue;
+        for (int i = 0; i < k; ++i) {
+          double px = 0.0, py = 0.0;
+          if (!(ls >> px >> py)) {
+            std::fprintf(stderr, "%s: a region with fewer boundary points than it announces\n", planes_file.c_str());
+            return 2;
+          }
+          convex_plane_decomposition_msgs::Point2d pt;
+          pt.x = px;
+          pt.y = py;
+          if (static_cast<double>(pt.x) != px || static_cast<double>(pt.y) != py) {
+            std::fprintf(stderr, "%s: a boundary point the message's number format does not hold exactly\n", planes_file.c_str());
+            return 2;
+          }
+          region.boundary.outer_boundary.points.push_back(pt);
+        }
+        goal->terrain.planarRegions.push_back(region);
+      }
+      fpowr::FootstepPlan plan;
+      fpowr::ExtractFootstepPlan(goal, solution, plan_horizon, plan);
+      std::ofstream opl(prefix + "_plan.txt");
+      opl.precision(17);
+      for (const auto& cd : plan.contact_data) {
+        opl << cd.duration;
+        for (int idx : cd.contact_set) opl << " " << idx;
+        opl << "\n";
+      }
+    }
+#else
+    std::fprintf(stderr, "--sample / --guess-times / --planes: this build has the fpowr extractors compiled out\n");
+    return 4;
+#endif
+  }
 
   if (binding) {
 #ifdef TWR_WITH_BINDING

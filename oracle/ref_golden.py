@@ -8,6 +8,8 @@ once (jac_row, jac_col), constraint and variable bounds (rows lower / upper), th
 recorded outputs of the reference's programs, nothing else.  tests/test_ref_golden.py replays them against the oracle,
 the structure builder (CPU) and the device (GPU) on boxes that do not have the reference.
 
+    python -m oracle.ref_golden --traj [names...]   (the fixtures tests/golden/reftraj_*.npz, see TRAJ_CASES below)
+
 The cases are chosen for what the mpmath fixtures and the hand known-answers cannot reach: entries the reference DEFINES
 rather than derives (force rows x footholds on curved terrain, terrain rows of gridded terrain, explicit zeros), bounds,
 every robot and constraint name, optimised timings, odd schedules, and the BASELINE sizes where the quirk lives."""
@@ -185,12 +187,143 @@ def record(name, workdir):
     return path, os.path.getsize(path), len(first["g"]), len(first["jac_row"])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/golden/reftraj_<case>.npz: what fpowr's extractors (footstep_plan_extractor.h, initial_guess_extractor.h,
+# nearest_plane_lookup.h -- the reference's own headers, run by ref_dump --sample / --guess-times / --planes) produce on a
+# solution x.  (The prefix keeps them out of the ref_*.npz glob and its size budget.)  Per case: the problem description
+# with the keys of the ref_* fixtures, x[k], dt and traj[k] = GetTrajectory(x[k], dt), guess_times and guess[k] =
+# ExtractInitialGuesses, the planar regions (regions, region_start, region_xy) and, from ExtractFootstepPlan at the
+# reference's fixed 0.01 s and its 2 s horizon, plan_steps[k], plan_duration[k], plan_contact_set[k] (padded to the
+# longest plan with NaN / -2) plus plan_state[k]: the rows of GetTrajectory(x[k], 0.01) at which the contact flags
+# change, i.e. the footstep states themselves (the quadrupeds record traj at a coarser dt to stay within the size budget).
+# tests/test_ref_traj.py states what the set has to cover and asserts it on the recorded arrays.
+PLAN_DT, PLAN_HORIZON = 0.01, 2.0   # footstep_plan_extractor.h:87, footstep_plan_server.cc:31
+# name -> (robot, terrain, schedule builder, params, dt, x seeds, scale of base-ang)
+TRAJ_CASES = {
+    "hopper": ("monoped", "flat", lambda: _sched([[0.4, 0.2, 0.4, 0.2, 0.4, 0.2, 0.2]], [1]), dict(constraint_sets=63), 0.01, (1, 2), 4.0),
+    "monoped_timings": ("monoped", "stairs", lambda: _combo("monoped", 1, 1.2), dict(constraint_sets=127, polys_per_swing=3, duration_base_poly=0.13),
+                        0.01, (3,), 5.0),
+    "biped_swing_start": ("biped", "gap", lambda: _phases(2, 4, 1.3, False, 11), dict(constraint_sets=31), 0.01, (4,), 6.0),
+    "biped_timings": ("biped", "flat", lambda: _combo("biped", 0, 1.2), dict(constraint_sets=127, polys_per_stance_force=2), 0.01, (5,), 4.0),
+    "anymal_stairs": ("anymal", "stairs", lambda: _combo("anymal", 1, 2.0), dict(constraint_sets=63), 0.025, (6,), 5.0),
+    "anymal_gap_timings": ("anymal", "gap", lambda: _combo("anymal", 0, 2.0), dict(constraint_sets=127), 0.03, (7,), 5.0),
+}
+
+
+def traj_regions():
+    """The planar regions every reftraj fixture carries: (regions (n, 7) [position xyz | orientation xyzw], list of local
+    boundary points).  Boundary points are multiples of 1/64 (exact in the message's float32).  0 and 1 overlap; 1 is
+    counter-clockwise; 2 is not closed; 3 is tilted, with a quaternion that is not normalised; 4 has three points (below
+    the minimum of a ring: it holds nothing, only its two edges are near); 5 and 6 are one square listed twice, so every
+    contact nearest to it is exactly equidistant from both and the first-wins rule decides."""
+    sq = lambda x0, x1, y0, y1: np.array([[x0, y0], [x0, y1], [x1, y1], [x1, y0], [x0, y0]])   # clockwise, closed
+    c, s_ = np.cos(0.15), np.sin(0.15)
+    tilt = np.array([np.sin(0.25), 0.0, 0.0, np.cos(0.25)])              # 0.5 rad about x ...
+    yaw = np.array([0.0, 0.0, np.sin(0.35), np.cos(0.35)])               # ... then 0.7 rad about z
+    x1, y1, z1, w1 = yaw
+    x2, y2, z2, w2 = tilt
+    q = 2.0 * np.array([w1 * x2 + x1 * w2 + y1 * z2 - z1 * y2, w1 * y2 - x1 * z2 + y1 * w2 + z1 * x2,
+                        w1 * z2 + x1 * y2 - y1 * x2 + z1 * w2, w1 * w2 - x1 * x2 - y1 * y2 - z1 * z2])
+    regions = [[0.0, 0.0, 0.0, 0, 0, 0, 1], [0.5, 0.0, 0.05, 0, 0, s_, c], [0.875, 0.25, 0.0, 0, 0, 0, 1], [1.125, -0.25, 0.1, *q],
+               [0.25, -0.625, 0.0, 0, 0, 0, 1], [1.375, 0.0, 0.2, 0, 0, 0, 1], [1.375, 0.0, 0.2, 0, 0, 0, 1]]
+    pent = np.array([[0.25, 0.0], [0.078125, -0.234375], [-0.203125, -0.140625], [-0.203125, 0.140625], [0.078125, 0.234375]])   # open
+    bounds = [sq(-0.5, 0.5, -0.125, 0.5), sq(-0.375, 0.25, -0.375, 0.375)[::-1].copy(), pent, sq(-0.25, 0.25, -0.1875, 0.1875),
+              np.array([[-0.125, 0.0], [0.125, 0.0], [0.0, -0.125]]), sq(-0.0625, 0.0625, -0.0625, 0.0625), sq(-0.0625, 0.0625, -0.0625, 0.0625)]
+    for b in bounds:
+        assert np.array_equal(b.astype(np.float32).astype(np.float64), b)
+    return np.array(regions, dtype=np.float64), bounds
+
+
+def sample_times_defined(T, dt, times=()):
+    """The trap of GetTrajectory: it samples while t <= T + 1e-5, and the reference's Spline::GetSegmentID is undefined
+    beyond T + 1e-10.  True when no accumulated sample time and none of `times` leaves what is defined."""
+    t = 0.0
+    while t <= T + 1e-5:
+        if t > T + 1e-10:
+            return False
+        t += dt
+    return all(0.0 <= v <= T + 1e-10 for v in times)
+
+
+def make_traj_x(case, seed, ang_scale):
+    """x_perturbed (timings included) with base-ang scaled and shaken, so that the rotation leaves the trace > 0 branch"""
+    x = case.x_perturbed(seed, sigma=0.25)
+    rng = np.random.default_rng(700 + seed)
+    for vs in case.S.var_sets:
+        a, b = vs["offset"], vs["offset"] + vs["size"]
+        if vs["name"] == "base-ang":
+            x[a:b] = x[a:b] * ang_scale + rng.normal(size=b - a) * 1.5
+        if vs["name"].startswith("ee-schedule"):   # back to +- 10 % of the given durations
+            e = int(vs["name"][len("ee-schedule"):])
+            x[a:b] = np.asarray(case.sched.durations()[e][:-1]) * (1.0 + 0.1 * rng.uniform(-1, 1, size=b - a))
+    return x
+
+
+def compute_traj(name, workdir):
+    """the arrays of reftraj_<name>.npz, from a run of the reference's code"""
+    from oracle import ref_run
+    from tests.common import Case
+
+    robot, terrain, sched, params, dt, seeds, ang_scale = TRAJ_CASES[name]
+    case = Case(robot, terrain, sched(), **params)
+    n_ee, p = N_EE[robot], case.params
+    T = float(np.sum(case.sched.durations()[0]))
+    rng = np.random.default_rng(len(name))
+    times = np.concatenate([[0.0, T, p.duration_base_poly, 2 * p.duration_base_poly, case.sched.durations()[0][0], 0.5 * T],
+                            rng.uniform(0.0, T, 66)])
+    assert len(times) > 64 and np.any(np.diff(times) < 0)
+    for step in (dt, PLAN_DT):
+        if not sample_times_defined(T, step, times):
+            raise SystemExit("%s: dt = %g or a guess time leaves [0, T + 1e-10] (T = %.17g)" % (name, step, T))
+    regions, bounds = traj_regions()
+    args, kw = ref_run.case_args(case)
+    xs, trajs, guesses, durs, sets, states = [], [], [], [], [], []
+    for seed in seeds:
+        x = make_traj_x(case, seed, ang_scale)
+        d = ref_run.run(os.path.join(workdir, "%s_%d" % (name, seed)), *args, x=x, sample_dt=dt, guess_times=times,
+                        planes=(regions, bounds, PLAN_HORIZON), **kw)
+        fine = ref_run.run(os.path.join(workdir, "%s_%d_fine" % (name, seed)), *args, x=x, sample_dt=PLAN_DT, **kw)["traj"]
+        assert np.array_equal(d["x"], x)
+        flags = fine[:, 20::13][:, :n_ee]
+        change = np.concatenate([[True], np.any(flags[1:] != flags[:-1], axis=1)])
+        assert change.sum() == len(d["plan_duration"]), "the footstep states are where the flags of the 0.01 s trajectory change"
+        xs.append(x), trajs.append(d["traj"]), guesses.append(d["guess"])
+        durs.append(d["plan_duration"]), sets.append(d["plan_contact_set"]), states.append(fine[change])
+    steps = np.array([len(v) for v in durs], dtype=np.int32)
+    pad = lambda rows, fill, dtype: np.array([np.concatenate([v, np.full((steps.max() - len(v),) + v.shape[1:], fill, dtype=dtype)]) for v in rows])
+    out = dict(robot=robot, terrain=terrain, n_phases=np.array([len(v) for v in case.sched.durations()], dtype=np.int32),
+               phase_durations=np.concatenate(case.sched.durations()), contact_at_start=np.array(case.sched.contact(), dtype=np.int32),
+               constraint_sets=np.int32(p.constraint_sets), params=np.array([getattr(p, k) for k in ref_run.PARAM_KEYS], dtype=np.float64),
+               var_names=np.array([n for n, _ in d["var_sets"]]), var_rows=np.array([r for _, r in d["var_sets"]], dtype=np.int32),
+               x=np.array(xs), dt=np.float64(dt), traj=np.array(trajs), guess_times=times, guess=np.array(guesses),
+               regions=regions, region_start=np.concatenate([[0], np.cumsum([len(b) for b in bounds])]).astype(np.int32),
+               region_xy=np.concatenate(bounds), plan_dt=np.float64(PLAN_DT), plan_horizon=np.float64(PLAN_HORIZON), plan_steps=steps,
+               plan_duration=pad(durs, np.nan, np.float64), plan_contact_set=pad(sets, -2, np.int32), plan_state=pad(states, np.nan, np.float64),
+               reference_deps=ref_run.deps())
+    return out
+
+
+def record_traj(name, workdir):
+    out = compute_traj(name, workdir)
+    path = os.path.join(GOLDEN, "reftraj_%s.npz" % name)
+    save_npz_lzma(path, out)
+    return path, os.path.getsize(path), out["traj"].shape[1], int(out["plan_steps"].max())
+
+
 def main(names):
     from oracle import ref_run
 
     if not ref_run.available():
         raise SystemExit("oracle/_ref/ref_dump is not built: run oracle/ref_dump/build.sh where the reference sources are")
     total = 0
+    if names and names[0] == "--traj":
+        with tempfile.TemporaryDirectory() as work:
+            for name in names[1:] or list(TRAJ_CASES):
+                path, size, n, steps = record_traj(name, work)
+                total += size
+                print("%-40s samples=%4d steps=%3d %8d bytes" % (os.path.basename(path), n, steps, size))
+        print("total %d bytes" % total)
+        return
     with tempfile.TemporaryDirectory() as work:
         for name in names or list(CASES):
             path, size, m, nnz = record(name, work)

@@ -26,9 +26,12 @@ def deps():
 
 
 def command(prefix, robot, terrain, mask, x="guess", durations=None, contact=None, combo=0, T=0.0, goal_x=1.0, params=None,
-            csv_heights=None, extra=()):
+            csv_heights=None, extra=(), sample_dt=None, guess_times=None, planes=None):
     """The ref_dump command line for one problem; writes the input files it names next to `prefix`.  `params` holds any
-    of PARAM_KEYS; `x` is "guess" or the variable vector; the schedule is either (durations, contact) or (combo, T)."""
+    of PARAM_KEYS; `x` is "guess" or the variable vector; the schedule is either (durations, contact) or (combo, T).
+    The fpowr extractors on that x: sample_dt (GetTrajectory), guess_times (ExtractInitialGuesses) and planes =
+    (regions (n, 7) [position xyz | orientation xyzw], one (k, 2) array of local boundary points per region, time horizon)
+    for ExtractFootstepPlan; read_extracted() reads what they wrote."""
     params = dict(params or {})
     if isinstance(x, str):
         xarg = x
@@ -52,7 +55,37 @@ def command(prefix, robot, terrain, mask, x="guess", durations=None, contact=Non
     if terrain == "csv":
         np.savetxt(prefix + "_heights.csv", np.asarray(csv_heights), fmt="%.17g", delimiter=",")
         cmd += ["--csv", prefix + "_heights.csv"]
+    if sample_dt is not None:
+        cmd += ["--sample", "%.17g" % sample_dt]
+    if guess_times is not None:
+        np.savetxt(prefix + "_guess_times.txt", np.asarray(guess_times, dtype=np.float64), fmt="%.17g")
+        cmd += ["--guess-times", prefix + "_guess_times.txt"]
+    if planes is not None:
+        regions, boundaries, horizon = planes
+        with open(prefix + "_planes.txt", "w") as f:
+            for r, b in zip(np.asarray(regions, dtype=np.float64).reshape(-1, 7), boundaries):
+                b = np.asarray(b, dtype=np.float64).reshape(-1, 2)
+                f.write(" ".join("%.17g" % v for v in list(r) + [len(b)] + list(b.reshape(-1))) + "\n")
+        cmd += ["--planes", prefix + "_planes.txt", "%.17g" % horizon]
     return cmd + list(extra)
+
+
+def read_extracted(prefix, n_ee):
+    """What --sample / --guess-times / --planes wrote, for those that were given: traj (n, 20 + 13 n_ee), guess (n, 49),
+    plan_duration (steps) and plan_contact_set (steps, n_ee)."""
+    out = {}
+    if os.path.exists(prefix + "_traj.txt"):
+        out["traj"] = np.loadtxt(prefix + "_traj.txt", ndmin=2)
+        assert out["traj"].shape[1] == 20 + 13 * n_ee
+    if os.path.exists(prefix + "_guess.txt"):
+        out["guess"] = np.loadtxt(prefix + "_guess.txt", ndmin=2)
+        assert out["guess"].shape[1] == 49
+    if os.path.exists(prefix + "_plan.txt"):
+        plan = np.loadtxt(prefix + "_plan.txt", ndmin=2)
+        assert plan.shape[1] == 1 + n_ee
+        out["plan_duration"] = plan[:, 0].copy()
+        out["plan_contact_set"] = plan[:, 1:].astype(np.int32)
+    return out
 
 
 def read(prefix):
@@ -82,7 +115,9 @@ def run(prefix, *args, timeout=600, **kw):
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
     if r.returncode != 0:
         raise RuntimeError("ref_dump exit %d: %s\n%s" % (r.returncode, " ".join(cmd), (r.stdout + r.stderr)[-2000:]))
-    return read(prefix)
+    out = read(prefix)
+    out.update(read_extracted(prefix, len(out["contact"])))
+    return out
 
 
 def case_args(case):

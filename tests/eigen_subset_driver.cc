@@ -96,6 +96,9 @@ static void dense_ops(const std::string& t, int n) {
   VectorXd o; o.resize(n); D(t + "resize", o); o.setOnes(); D(t + "setOnes", o); o.setZero(); D(t + "setZero", o);
   Matrix3d C; C << 1, 2, 3, 4, 5, 6, 7, 8, 9; D(t + "comma_m", C);
   VectorXd cv(3); cv << s, 2.0, -1.0; D(t + "comma_v", cv);
+  VectorXd fin = (VectorXd(2) << s, -3.5).finished(); D(t + "comma_finished", fin);
+  VectorXd ws = VectorXd::Zero(n); ws.segment<3>(1) = a3; D(t + "segment_fixed_w", ws);
+  const VectorXd& cws = ws; Vector3d rs = cws.segment<3>(1); D(t + "segment_fixed", rs);
   D(t + "unit", Vector3d::Unit(1)); D(t + "zero3", Vector3d::Zero()); D(t + "zero_rc", MatrixXd::Zero(2, n)); D(t + "zero_n", VectorXd::Zero(n));
   Vector3d xyz(an(0), an(1), an(2)); xyz.z() = xyz.x() + 1.0; D(t + "xyz", xyz);
   Vector2d xy(1.5, -2.5); D(t + "xy", xy);

@@ -164,6 +164,10 @@ def test_dense_members_against_numpy(dump, n):
     eq("topRows_w", W)
     eq("setIdentity", np.eye(3)), eq("resize", np.zeros((n, 1))), eq("setOnes", np.ones((n, 1))), eq("setZero", np.zeros((n, 1)))
     eq("comma_m", np.arange(1.0, 10.0).reshape(3, 3)), eq("comma_v", np.array([[s], [2.0], [-1.0]]))
+    eq("comma_finished", np.array([[s], [-3.5]]))
+    ws = np.zeros((n, 1))
+    ws[1:4] = a3
+    eq("segment_fixed_w", ws), eq("segment_fixed", a3)
     eq("unit", np.array([[0.0], [1.0], [0.0]])), eq("zero3", np.zeros((3, 1))), eq("zero_rc", np.zeros((2, n))), eq("zero_n", np.zeros((n, 1)))
     eq("xyz", np.array([[an[0, 0]], [an[1, 0]], [an[0, 0] + 1.0]])), eq("xy", np.array([[1.5], [-2.5]])), eq("map", an)
     eq("rows_cols", np.array([[6.0], [float(n)], [float(n)]]))

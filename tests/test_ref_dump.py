@@ -163,11 +163,15 @@ def test_gait_tables_against_the_reference(tmp_path):
 def test_random_walk_against_the_reference(tmp_path):
     """random_case(seed) for a few hundred seeds, each at the reference's own initial guess, at x_perturbed and at x_wild:
     the reference vs the oracle through assert_parity, the reference's pattern vs Structure.row_ptr / col_idx, bounds,
-    variable bounds, initial guess and set tables.  (`grid_map` terrain needs ROS packages and is left out.)"""
+    variable bounds, initial guess and set tables.  (`grid_map` terrain needs ROS packages and is left out.)
+    Every sixth problem also runs fpowr's GetTrajectory in the reference (ref_dump --sample) at its perturbed x, against the
+    oracle's sample_trajectory at the bar of tests/test_ref_traj.py."""
     reference_built()
+    from oracle.ref_golden import sample_times_defined
     from tests.common import random_case
+    from tests.test_ref_traj import check_records, traj_exact_columns
 
-    worst, done = {}, 0
+    worst, done, sampled = {}, 0, 0
     with concurrent.futures.ThreadPoolExecutor(max_workers=WORKERS) as pool:
         for first in range(0, WALK_SEEDS, 64):   # (in chunks: the structures of a chunk are alive while its dumps run)
             jobs = []
@@ -178,7 +182,12 @@ def test_random_walk_against_the_reference(tmp_path):
                 args, kw = ref_run.case_args(case)
                 for tag, x in (("guess", "guess"), ("perturbed", case.x_perturbed(seed)), ("wild", case.x_wild(seed))):
                     prefix = str(tmp_path / ("s%d_%s" % (seed, tag)))
-                    jobs.append((case, seed, tag, x, pool.submit(ref_run.run, prefix, *args, x=x, **kw)))
+                    more = {}
+                    if tag == "perturbed" and seed % 6 == 0:   # between 40 and 90 samples, none where the reference is undefined
+                        T = float(np.sum(case.sched.durations()[0]))
+                        dts = [T / n for n in range(40 + seed % 50, 140) if sample_times_defined(T, T / n)]
+                        more = dict(sample_dt=dts[0])
+                    jobs.append((case, seed, tag, x, pool.submit(ref_run.run, prefix, *args, x=x, **more, **kw)))
             for case, seed, tag, x, fut in jobs:
                 d = fut.result()
                 what = "seed %d (%s/%s, sets %d) at %s" % (seed, case.robot, case.terrain, case.params.constraint_sets, tag)
@@ -187,11 +196,16 @@ def test_random_walk_against_the_reference(tmp_path):
                 else:
                     assert np.array_equal(d["x"], x), what
                     compare_case(case, d, x, what, worst)
+                    if "traj" in d:
+                        dt = d["traj"][1, 0]
+                        check_records(case.P.sample_trajectory(x, dt), d["traj"], traj_exact_columns(case.model.n_ee), what + " trajectory", worst, "traj")
+                        sampled += 1
                 done += 1
                 for f in glob.glob(str(tmp_path / ("s%d_%s_*" % (seed, tag)))):
                     os.remove(f)
-    assert done >= 2 * WALK_SEEDS
-    print("random walk: %d dumps, oracle vs reference worst error / scale: g %.3e, Jacobian %.3e" % (done, worst["g"], worst["jac"]))
+    assert done >= 2 * WALK_SEEDS and sampled >= WALK_SEEDS // 8
+    print("random walk: %d dumps, oracle vs reference worst error / scale: g %.3e, Jacobian %.3e; %d trajectories, worst %.3e" % (
+        done, worst["g"], worst["jac"], sampled, worst["traj"]))
 
 
 BINDING_CASES = (("monoped", "flat", 2, 2.0, 63), ("biped", "slope", 1, 1.6, 255), ("hyq", "chimney", 3, 2.0, 63), ("anymal", "gap", 1, 2.0, 27),
