@@ -256,11 +256,11 @@ int twr_batch_streaming_stores(const twr_batch* b);
 /* Slices per problem of the "dynamic" set when every problem of the batch references the same structure with fixed
  * timings (a uniform batch: many x for one NLP), else 0.  With per-kernel launches (large batches, or profiling events)
  * such a batch is evaluated by a kernel whose waves each own one slice kind and load its tables once per launch, when the
- * resident grid divides into the kinds (structure.h DynUniformCols); the values written are the same bits either way. */
+ * resident grid divides into the kinds (eval_plan.h DynUniformCols); the values written are the same bits either way. */
 int twr_batch_dyn_uniform_kinds(const twr_batch* b);
 /* The launches a call on this batch would issue, in order, without issuing them: which kernel, which template instantiation
  * of it, grid, block and dynamic LDS.  Read-only: planned from the same shape and by the same planner as the call itself
- * (structure.h MakeEvalShape / PlanEval), so it is what the device runs, for this device's CU count and memory-side cache.
+ * (batch_plan.h MakeEvalShape / eval_plan.h PlanEval), so it is what the device runs, for this device's CU count and memory-side cache.
  *   request TWR_PLAN_EVAL:       twr_batch_eval(flags); events != 0: as between twr_batch_profile_begin and _end
  *   request TWR_PLAN_SCORES:     twr_batch_eval_scores      (flags and events are ignored: these record no events)
  *   request TWR_PLAN_SCORE_BEST: twr_batch_eval_score_best
@@ -454,7 +454,7 @@ int twr_batch_host_buffers(twr_batch* b, double** h_x, double** h_g, double** h_
  * error codes and the sticky HIP error as twr_batch_eval; NULL buffers are TWR_ERR_INVALID, and so are buffers that are not
  * 8-byte aligned.  At most ONE product per handle in flight (J^T w keeps its partials in the handle's slab); handles on
  * different streams are independent.  Outputs must not overlap inputs.
- * Summation order is a function of the problem's structure alone (structure.h, twr::PlanJacOps): a problem's y and z have the
+ * Summation order is a function of the problem's structure alone (jac_plan.h, twr::PlanJacOps): a problem's y and z have the
  * same bits wherever it sits in whatever batch, on every call, stream and device, and a NaN / Inf in one problem's J, v or w
  * reaches that problem's outputs only.  A structure without rows: J v writes nothing, J^T w writes zeros; a column without
  * entries gets an exact 0. */
@@ -479,7 +479,7 @@ int twr_jac_col_sqnorms(twr_jac_ops* ops, const double* d_jac, const double* d_w
  * d_y = J v in the g layout (d_w NULL: unit weights) -- what an iteration of CG on the normal equations needs, with the
  * Jacobian values read from memory once instead of once per product.  Blocks of whole rows: a block's values are kept in LDS
  * while its rows' sums y_r are taken, multiplied by t_r = w_r y_r there, and summed per column into partials that the fold of
- * twr_jac_tmul adds in block order (structure.h, twr::PlanJacNormal).  Everything said of the two products holds: no atomics,
+ * twr_jac_tmul adds in block order (jac_plan.h, twr::PlanJacNormal).  Everything said of the two products holds: no atomics,
  * the order of every sum a function of the pattern alone (same bits wherever the problem sits, on every call, stream and
  * device; d_y NULL does not change d_u), a column without entries gets an exact 0, a structure without rows writes no y and
  * zeros to u, J, v and w are only multiplied and added (a NaN / Inf stays in its problem), stream-ordered and capturable, ONE
@@ -606,7 +606,7 @@ int twr_jac_lsq_solve_onepass(twr_jac_lsq* lsq, const double* d_jac, const doubl
  * The driver, a handle of its own that BORROWS the batch, the twr_jac_lsq and, through it, its twr_jac_ops: all of them must
  * outlive it and share one layout and device (a mismatch is TWR_ERR_INVALID; NULL arguments are checked before any device is
  * touched).  It
- * owns its workspace (twr::PlanJacLm, structure.h); twr_jac_lm_create also reserves the scaled solve's vectors of lsq.
+ * owns its workspace (twr::PlanJacLm, jac_plan.h); twr_jac_lm_create also reserves the scaled solve's vectors of lsq.
  *   twr_jac_lm_start: binds the caller's buffers -- d_x (in / out), d_xlo, d_xup (x layout), d_g, d_jac (the caller's, g / jac
  *                     layout; the linearisation of the last step is left in them) --, projects x onto the box, linearises and
  *                     sets mu0 = clamp(tau lambda_max(C_f J^T W J C_f)), lambda_max from power_iters power iterations on the
@@ -656,7 +656,7 @@ int twr_jac_lm_state(twr_jac_lm* lm, double* d_out /* TWR_JAC_LM_REC * n_problem
  * calls above read the Jacobian values twice per iteration (once with the one-pass product); N is small (C3: 70 552 stored values
  * against 102 896 of J) and an iteration of CG on it reads nothing else, so the whole solve is ONE launch with every vector in
  * LDS.  Where the duration columns are dense (optimised timings with every constraint set) N is larger than 2 nnz J and CGLS
- * stays the better solve: an alternative the caller picks, no existing call changes.  Planned on the host (structure.h,
+ * stays the better solve: an alternative the caller picks, no existing call changes.  Planned on the host (jac_plan.h,
  * twr::PlanJacGram): per distinct pattern the pattern of N = J^T J as FULL symmetric CSR (structural: an explicit zero of J
  * counts, a column of J without entries is an empty row and column; column indices ascending, 16 bits on the device) and, per
  * stored entry (i, j) of the lower triangle, the list of its terms (row r, position of J_ri, position of J_rj) in ascending r,

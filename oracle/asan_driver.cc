@@ -2,9 +2,9 @@
 // CPU oracle"; extended to the product's host-side structure builder, which contains no HIP).
 // Built by `make -C oracle asan` with -fsanitize=address,undefined and run by tests/test_sanitizers.py: walks
 // robots x gait combos x constraint-set masks (incl. optimised timings and baseMotion) through
-//   twr::Structure::Build / InitialGuess / VariableBounds   (towr_amd/csrc/structure.cc)
-//   twr::ShareLayoutTables / PlanBatch (what twr_batch_create uploads; structure.cc)
-//   twr::PlanEval (the launches of one twr_batch_eval; structure.cc)
+//   twr::Structure::Build / InitialGuess / VariableBounds   (towr_amd/csrc/structure.cc, presets.cc)
+//   twr::ShareLayoutTables / PlanBatch (what twr_batch_create uploads; batch_plan.cc)
+//   twr::PlanEval (the launches of one twr_batch_eval; eval_plan.cc)
 //   orc_create / orc_eval / orc_bounds / orc_sample_trajectory (oracle/towr_oracle.cc)
 // and cross-checks sizes and the CSR pattern of the two, so that every table write and every row of the
 // pattern builders executes under the sanitizers.
@@ -19,7 +19,7 @@
 #include <string>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
+#include "../towr_amd/csrc/batch_plan.h"
 #include "towr_oracle.h"
 
 static int fails = 0;
@@ -165,7 +165,7 @@ static void sharing_case() {
   for (size_t t = 0; t < sh.of[11].size(); ++t) CHECK(sh.of[11][t].owner <= 3, "sharing: a repeated structure owns a table");
 }
 
-// the store policy of a batch (structure.h): the measured cases of DESIGN 6.R4
+// the store policy of a batch (batch_plan.h): the measured cases of DESIGN 6.R4
 static void policy_case() {
   const int64_t per = 859216;   // bytes per callback of a K = 200 quadruped candidate
   CHECK(twr::StreamNonTemporal(1024, 1024, 1024 * per), "policy: the 1024-candidate sweep streams");

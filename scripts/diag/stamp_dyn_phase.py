@@ -42,7 +42,8 @@ hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 try:
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-o", os.path.join(SRC, "_kernels_stamps.o"), tmp], cwd=SRC)
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "--hip-link", "-fPIC", "-shared", "-o", os.path.join(ROOT, "towr_amd", "libtowr_amd_stamps.so"),
-                           "_kernels_stamps.o", "rom_tu.o", "structure.o", "capi.o", "capi_jac.o"], cwd=SRC)
+                           "_kernels_stamps.o", "rom_tu.o", "structure.o", "presets.o", "batch_plan.o", "eval_plan.o", "jac_plan.o", "capi.o",
+                           "capi_jac.o"], cwd=SRC)
 finally:
     for f in (tmp, os.path.join(SRC, "_kernels_stamps.o")):
         if os.path.exists(f):

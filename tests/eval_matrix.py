@@ -1,7 +1,7 @@
 """The instantiation matrix of the evaluation kernels, stated once.
 
-twr_batch_eval picks one template instantiation of each kernel from whole-batch quantities (structure.cc PlanBatch /
-PlanEval).  MATRIX below names small batches -- real shapes, nothing else -- that between them reach every instantiation
+twr_batch_eval picks one template instantiation of each kernel from whole-batch quantities (batch_plan.cc PlanBatch /
+eval_plan.cc PlanEval).  MATRIX below names small batches -- real shapes, nothing else -- that between them reach every instantiation
 that can be planned, and says which ones each batch reaches.  Two readers build the same structures from this text:
 
   tests/eval_matrix_driver.cc (run by tests/test_eval_matrix_plan.py, no GPU) plans every row with the product's planner and

@@ -3,7 +3,7 @@
 // without per-kernel events, and for the two scoring requests; each row must reach the instantiations it claims, and the
 // claims of all rows plus the exclusion list must be exactly the set of instantiations that exist -- enumerated here from the
 // key lists of structure.h, so a new instantiation without a row fails.
-// Built and run by tests/test_eval_matrix_plan.py (g++ against towr_amd/csrc/structure.cc, no HIP); the matrix text comes in
+// Built and run by tests/test_eval_matrix_plan.py (g++ against the host planner, no HIP); the matrix text comes in
 // as a file (argv[1]), the same text tests/test_eval_matrix.py builds its device batches from.  The device enters as 256 CUs
 // and a 256 MB memory-side cache (an MI355X); the GPU test holds the rows to the plan of the device it runs on.
 // With --print the plan of every call is listed (how the rows were found).
@@ -16,17 +16,8 @@
 #include <string>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                  \
-  do {                                    \
-    if (!(cond)) {                        \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fprintf(stderr, "\n");         \
-      ++fails;                            \
-    }                                     \
-  } while (0)
+#include "../towr_amd/csrc/batch_plan.h"
+#include "plan_driver_common.h"
 
 static const int kCu = 256;
 static const int64_t kCache = (int64_t)256 << 20;

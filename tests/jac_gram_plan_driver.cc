@@ -1,6 +1,6 @@
 // Checks of the Gram matrix's plan (twr_jac_gram, twr_jac_gram_mul, twr_jac_lsq_solve_gram) on the host: the tables and work lists
-// twr::PlanJacGram builds.  Built and run by tests/test_jac_gram_plan.py (g++ against towr_amd/csrc/structure.cc under ASan +
-// UBSan, no HIP).
+// twr::PlanJacGram builds.  Built and run by tests/test_jac_gram_plan.py (tests/host_build.py: g++ against the host planner
+// under ASan + UBSan, no HIP).
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
@@ -8,34 +8,8 @@
 #include <string>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                  \
-  do {                                    \
-    if (!(cond)) {                        \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fprintf(stderr, "\n");         \
-      ++fails;                            \
-    }                                     \
-  } while (0)
-
-static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 40) {
-  twr::Structure S;
-  twr::ModelPreset(robot, terrain, &S.model);
-  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
-  twr_params& p = S.params;
-  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
-  p.duration_base_poly = 0.1;
-  p.polys_per_swing = 2;
-  p.polys_per_stance_force = 3;
-  p.constraint_sets = sets;
-  p.reserved_ = 0;
-  p.dt_base_motion = 0.025;
-  p.base_z_init = -S.model.nominal_stance[0][2];
-  S.Build();
-  return S;
-}
+#include "../towr_amd/csrc/jac_plan.h"
+#include "plan_driver_common.h"
 
 // towr/test/hopper_example.cc:67-68: the monoped of BASELINE's C1 (tests/common.py hopper_schedule), towr's default time steps
 static twr::Structure hopper(int sets) {
@@ -56,32 +30,6 @@ static twr::Structure hopper(int sets) {
   p.base_z_init = -S.model.nominal_stance[0][2];
   S.Build();
   return S;
-}
-
-// A pattern made by hand (only what the plan reads): row r with len[r] entries from column first[r] on, every step-th column
-static twr::Structure pattern(int n, const std::vector<int>& first, const std::vector<int>& len, int step) {
-  twr::Structure S{};
-  S.n_vars = n;
-  S.n_rows = (int)len.size();
-  S.row_ptr.push_back(0);
-  for (size_t r = 0; r < len.size(); ++r) {
-    for (int j = 0; j < len[r]; ++j) S.col_idx.push_back(first[r] + j * step);
-    S.row_ptr.push_back((int32_t)S.col_idx.size());
-  }
-  S.nnz = (int)S.col_idx.size();
-  return S;
-}
-
-template <class T>
-static const T* table(const char* name, const std::vector<char>& tables, uint64_t off, size_t count) {
-  const bool ok = off % alignof(T) == 0 && off <= tables.size() && count * sizeof(T) <= tables.size() - off;
-  CHECK(ok, "%s: table [%llu, +%zu x %zu) outside the %zu bytes", name, (unsigned long long)off, count, sizeof(T), tables.size());
-  return ok ? reinterpret_cast<const T*>(tables.data() + off) : nullptr;
-}
-
-template <class T>
-static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
 }
 
 // One distinct pattern's tables against the structure they were made from
@@ -188,8 +136,34 @@ static void check_pattern(const char* name, const twr::JacGramPlan& G, const twr
   CHECK(products == lower_products, "%s: %lld products, the rows of J give %lld", name, (long long)products, (long long)lower_products);
 }
 
-static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop, int want_distinct) {
+// Everything PlanJacGram returns, as one number
+static uint64_t gram_fingerprint(const twr::JacGramPlan& G) {
+  Fnv f;
+  f.vec64(G.x_off), f.vec64(G.g_off), f.vec64(G.j_off), f.vec64(G.gram_off), f.vec64(G.tables), f.vec64(G.patterns);
+  f.vec64(G.pattern_of_struct), f.vec64(G.form), f.vec64(G.mul), f.vec64(G.solve), f.i64(G.max_n);
+  return f.h;
+}
+static_assert(sizeof(twr::JacGramPattern) == 88 && sizeof(twr::JacGramWork) == 72 && sizeof(twr::JacGramMulWork) == 40 &&
+                  sizeof(twr::JacGramSolveWork) == 40,
+              "hashed as bytes: no padding");
+
+// Recorded from the commit before the planner was cut into units (this driver with -DTWR_RECORD_PARENT): the plan before
+// and after Place.
+static const ParentRecord<2> kParent[] = {
+    {"hopper_all", {0x78885fe5fd7f6a9dull, 0x8d2d9e53793387b7ull}},
+    {"twins", {0xfe647b65299b3bfcull, 0xb2f96087f081483aull}},
+    {"mixed", {0x5ec1f26ba9ccbac5ull, 0xe9310c4b7fbb3c27ull}},
+};
+
+static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop, int want_distinct,
+                      bool recorded = false) {
   const twr::JacGramPlan G = twr::PlanJacGram(sp, sop), H = twr::PlanJacGram(sp, sop);
+  if (recorded) {
+    twr::JacGramPlan placed = G;
+    placed.Place(0x7e0000000000ull);
+    const uint64_t hash[2] = {gram_fingerprint(G), gram_fingerprint(placed)};
+    parent_record(kParent, name, hash);
+  }
   const twr::JacOpsPlan J = twr::PlanJacOps(sp, sop);
   CHECK(same_bytes(G.tables, H.tables) && same_bytes(G.form, H.form) && same_bytes(G.mul, H.mul) && same_bytes(G.solve, H.solve) &&
             G.gram_off == H.gram_off,
@@ -261,13 +235,13 @@ static void expect_unsupported(const char* what, F f) {
 }
 
 int main() {
-  const twr::Structure c1 = hopper(27), hopper_all = hopper(127), biped_all = build(1, 0, 0, 2.0, 127);
+  const twr::Structure c1 = hopper(27), hopper_all = hopper(127), biped_all = build(1, 0, 0, 2.0, 127, 1.0, 40);
   const twr::Structure anymal = build(3, 0, 1, 2.0, 27, 1.0, 21), anymal_twin = build(3, 0, 1, 2.0, 27, 1.0, 21);
   plan_case("C1", {&c1}, {0}, 1);
-  plan_case("hopper_all", {&hopper_all}, {0, 0, 0}, 1);
+  plan_case("hopper_all", {&hopper_all}, {0, 0, 0}, 1, true);
   plan_case("biped_all", {&biped_all}, {0}, 1);
   plan_case("anymal", {&anymal}, {0, 0}, 1);
-  plan_case("twins", {&anymal, &anymal_twin, &c1}, {0, 1, 2, 1, 0}, 2);   // byte-identical patterns share tables
+  plan_case("twins", {&anymal, &anymal_twin, &c1}, {0, 1, 2, 1, 0}, 2, true);   // byte-identical patterns share tables
   std::vector<twr::Structure> ss;
   for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 3 == 2 ? 127 : (i % 2 ? 27 : 63), 0.9, 14 + 3 * i));
   std::vector<const twr::Structure*> sp;
@@ -276,7 +250,7 @@ int main() {
   // no rows: N has no entries; an empty column between full ones; explicit structure made by hand
   const twr::Structure empty = pattern(7, {}, {}, 1), holes = pattern(9, {0, 2, 5, 0}, {2, 3, 2, 0}, 2);
   plan_case("no rows", {&empty}, {0, 0, 0}, 1);
-  plan_case("mixed", {&empty, &holes, &c1}, {1, 0, 2, 0, 1}, 3);
+  plan_case("mixed", {&empty, &holes, &c1}, {1, 0, 2, 0, 1}, 3, true);
   {
     const twr::JacGramPlan G = twr::PlanJacGram({&empty}, {0, 0});
     CHECK(G.gram_off.back() == 0 && G.form.empty() && G.patterns[0].nnz == 0 && G.solve.size() == 2, "no rows: N is not empty");

@@ -1,39 +1,13 @@
 // Checks of the bounded LM driver's plan (twr_jac_lm_*) on the host: the workspace segments twr::PlanJacLm lays out.  Built and run
-// by tests/test_jac_lm_plan.py (g++ against towr_amd/csrc/structure.cc under ASan + UBSan, no HIP).
+// by tests/test_jac_lm_plan.py (tests/host_build.py: g++ against the host planner under ASan + UBSan, no HIP).
 #include <algorithm>
 #include <cstdio>
 #include <string>
 #include <utility>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                  \
-  do {                                    \
-    if (!(cond)) {                        \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fprintf(stderr, "\n");         \
-      ++fails;                            \
-    }                                     \
-  } while (0)
-
-static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 40) {
-  twr::Structure S;
-  twr::ModelPreset(robot, terrain, &S.model);
-  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
-  twr_params& p = S.params;
-  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
-  p.duration_base_poly = 0.1;
-  p.polys_per_swing = 2;
-  p.polys_per_stance_force = 3;
-  p.constraint_sets = sets;
-  p.reserved_ = 0;
-  p.dt_base_motion = 0.025;
-  p.base_z_init = -S.model.nominal_stance[0][2];
-  S.Build();
-  return S;
-}
+#include "../towr_amd/csrc/jac_plan.h"
+#include "plan_driver_common.h"
 
 static twr::Structure sizes_only(int n, int m) {   // the plan reads n_vars and n_rows alone
   twr::Structure S;
@@ -41,8 +15,29 @@ static twr::Structure sizes_only(int n, int m) {   // the plan reads n_vars and 
   return S;
 }
 
-static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop) {
+// Everything PlanJacLm returns, as one number (the plan has nothing to Place)
+static uint64_t lm_fingerprint(const twr::JacLmPlan& L) {
+  Fnv f;
+  f.vec64(L.x_off), f.vec64(L.g_off);
+  for (int64_t v : {L.ws_xt, L.ws_d, L.ws_z, L.ws_colsq, L.ws_colmax, L.ws_c, L.ws_cf, L.ws_r, L.ws_b, L.ws_wa, L.ws_gt, L.ws_rt, L.ws_rec, L.ws_mu,
+                    L.ws_merit_t, L.ws_merit_lin, L.ws_nfree, L.ws_info, L.ws_doubles})
+    f.i64(v);
+  return f.h;
+}
+
+// Recorded from the commit before the planner was cut into units (this driver with -DTWR_RECORD_PARENT).
+static const ParentRecord<1> kParent[] = {
+    {"hopper x3", {0xb14ce8bbecf3c627ull}},
+    {"ragged", {0x3bf30e0547ad490full}},
+    {"odd", {0xa57699bdf4af0eddull}},
+};
+
+static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop, bool recorded = false) {
   const twr::JacLmPlan L = twr::PlanJacLm(sp, sop), K = twr::PlanJacLm(sp, sop);
+  if (recorded) {
+    const uint64_t hash[1] = {lm_fingerprint(L)};
+    parent_record(kParent, name, hash);
+  }
   const int n = (int)sop.size();
   CHECK(L.x_off == K.x_off && L.g_off == K.g_off && L.ws_doubles == K.ws_doubles && L.ws_info == K.ws_info && L.ws_rec == K.ws_rec,
         "%s: planning twice differs", name);
@@ -77,13 +72,13 @@ static void plan_case(const char* name, const std::vector<const twr::Structure*>
 }
 
 int main() {
-  const twr::Structure hopper = build(0, 0, 0, 2.0, 27), hopper_all = build(0, 0, 0, 2.0, 127), biped_all = build(1, 0, 0, 2.0, 127);
-  const twr::Structure anymal = build(3, 0, 1, 2.0, 27);
+  const twr::Structure hopper = build(0, 0, 0, 2.0, 27, 1.0, 40), hopper_all = build(0, 0, 0, 2.0, 127, 1.0, 40), biped_all = build(1, 0, 0, 2.0, 127, 1.0, 40);
+  const twr::Structure anymal = build(3, 0, 1, 2.0, 27, 1.0, 40);
   const twr::Structure odd = sizes_only(339, 273), empty = sizes_only(7, 0), one = sizes_only(1, 1);
   plan_case("hopper", {&hopper}, {0});
-  plan_case("hopper x3", {&hopper}, {0, 0, 0});
-  plan_case("ragged", {&hopper, &hopper_all, &biped_all, &anymal}, {0, 1, 2, 3, 2, 1, 0, 0, 3});
-  plan_case("odd", {&odd, &one}, {0, 1, 0, 0, 1});            // odd n and m: odd totals, odd problem counts
+  plan_case("hopper x3", {&hopper}, {0, 0, 0}, true);
+  plan_case("ragged", {&hopper, &hopper_all, &biped_all, &anymal}, {0, 1, 2, 3, 2, 1, 0, 0, 3}, true);
+  plan_case("odd", {&odd, &one}, {0, 1, 0, 0, 1}, true);            // odd n and m: odd totals, odd problem counts
   plan_case("no rows", {&empty}, {0, 0, 0});                   // G = 0: empty g segments
   plan_case("mixed", {&empty, &odd, &anymal}, {1, 0, 2, 0, 1});
   CHECK(hopper.n_vars % 2 == 1 || hopper_all.n_vars % 2 == 1 || odd.n_vars % 2 == 1, "no odd n among the cases");

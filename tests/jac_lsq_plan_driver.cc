@@ -1,6 +1,6 @@
 // Checks of the least-squares plan (twr_jac_lsq_*) on the host: the work records, the workspace segments and the bound tables
-// twr::PlanJacLsq builds.  Built and run by tests/test_jac_lsq_plan.py (g++ against towr_amd/csrc/structure.cc under ASan + UBSan,
-// no HIP).
+// twr::PlanJacLsq builds.  Built and run by tests/test_jac_lsq_plan.py (tests/host_build.py: g++ against the host planner under
+// ASan + UBSan, no HIP).
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -10,36 +10,8 @@
 #include <utility>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                  \
-  do {                                    \
-    if (!(cond)) {                        \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fprintf(stderr, "\n");         \
-      ++fails;                            \
-    }                                     \
-  } while (0)
-
-static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 200,
-                            std::shared_ptr<const twr::TerrainGrid> grid = nullptr, double base_poly = 0.1) {
-  twr::Structure S;
-  twr::ModelPreset(robot, terrain, &S.model);
-  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
-  twr_params& p = S.params;
-  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
-  p.duration_base_poly = base_poly;
-  p.polys_per_swing = 2;
-  p.polys_per_stance_force = 3;
-  p.constraint_sets = sets;
-  p.reserved_ = 0;
-  p.dt_base_motion = 0.025;
-  p.base_z_init = -S.model.nominal_stance[0][2];
-  S.grid = grid;
-  S.Build();
-  return S;
-}
+#include "../towr_amd/csrc/jac_plan.h"
+#include "plan_driver_common.h"
 
 static bool same_bounds(const twr::Structure& a, const twr::Structure& b) {
   const size_t bytes = a.lower.size() * sizeof(double);
@@ -47,13 +19,34 @@ static bool same_bounds(const twr::Structure& a, const twr::Structure& b) {
          (bytes == 0 || (std::memcmp(a.lower.data(), b.lower.data(), bytes) == 0 && std::memcmp(a.upper.data(), b.upper.data(), bytes) == 0));
 }
 
-template <class T>
-static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+// Everything PlanJacLsq returns, as one number
+static uint64_t lsq_fingerprint(const twr::JacLsqPlan& L) {
+  Fnv f;
+  f.vec64(L.x_off), f.vec64(L.g_off), f.vec64(L.work), f.vec64(L.bounds), f.vec64(L.bounds_of_struct);
+  for (int64_t v : {(int64_t)L.distinct_bounds, L.ws_p, L.ws_z, L.ws_q, L.ws_r, L.ws_t, L.ws_rec, L.ws_doubles, L.ws2_e, L.ws2_cp, L.ws2_doubles,
+                    L.ws3_s, L.ws3_u, L.ws3_doubles, (int64_t)L.lds_x})
+    f.i64(v);
+  return f.h;
 }
+static_assert(sizeof(twr::JacLsqWork) == 40, "hashed as bytes: no padding");
 
-static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop, int want_distinct) {
+// Recorded from the commit before the planner was cut into units (this driver with -DTWR_RECORD_PARENT): the plan before
+// and after Place.
+static const ParentRecord<2> kParent[] = {
+    {"twins", {0x4502fb002bb309d5ull, 0x11aa9304196727b5ull}},
+    {"every", {0x840001f8bca32d82ull, 0x0229a978e9e73ff6ull}},
+    {"per-row", {0x88195663af5b544cull, 0x431510b258405ad4ull}},
+};
+
+static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop, int want_distinct,
+                      bool recorded = false) {
   const twr::JacLsqPlan L = twr::PlanJacLsq(sp, sop), K = twr::PlanJacLsq(sp, sop);
+  if (recorded) {
+    twr::JacLsqPlan placed = L;
+    placed.Place(0x7e0000000000ull);
+    const uint64_t hash[2] = {lsq_fingerprint(L), lsq_fingerprint(placed)};
+    parent_record(kParent, name, hash);
+  }
   CHECK(same_bytes(L.work, K.work) && same_bytes(L.bounds, K.bounds) && L.bounds_of_struct == K.bounds_of_struct &&
             L.ws_doubles == K.ws_doubles && L.ws_rec == K.ws_rec,
         "%s: planning twice differs", name);
@@ -128,13 +121,13 @@ static void plan_case(const char* name, const std::vector<const twr::Structure*>
 }
 
 int main() {
-  const twr::Structure c3 = build(3, 0, 1, 2.0, 63), c3_hot = build(3, 0, 1, 2.0, 27), c3_twin = build(3, 0, 1, 2.0, 27);
-  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1);   // every family, optimised timings, base_z_init set
+  const twr::Structure c3 = build(3, 0, 1, 2.0, 63, 1.0, 200), c3_hot = build(3, 0, 1, 2.0, 27, 1.0, 200), c3_twin = build(3, 0, 1, 2.0, 27, 1.0, 200);
+  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1, 200);   // every family, optimised timings, base_z_init set
   plan_case("C3x16", {&c3_hot}, std::vector<int32_t>(16, 0), 1);
-  plan_case("twins", {&c3_hot, &c3_twin}, {0, 1, 1, 0}, 1);   // two structures from identical inputs: one table
-  plan_case("every", {&every, &c3}, {0, 1, 0}, 2);
+  plan_case("twins", {&c3_hot, &c3_twin}, {0, 1, 1, 0}, 1, true);   // two structures from identical inputs: one table
+  plan_case("every", {&every, &c3}, {0, 1, 0}, 2, true);
   std::vector<twr::Structure> ss;
-  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9));
+  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9, 200));
   std::vector<const twr::Structure*> sp;
   for (const auto& s : ss) sp.push_back(&s);
   plan_case("ragged", sp, {0, 1, 2, 3, 4, 5, 3, 1, 1, 0}, 6);
@@ -158,7 +151,7 @@ int main() {
   CHECK(zero_at >= 0, "C3 has no row with a lower bound of 0");
   if (zero_at >= 0) negzero.lower[zero_at] = -0.0;
   for (int r = 0; r < 400; ++r) many.lower[r] = -1.0 - r, many.upper[r] = 2.0 + 0.5 * r;
-  plan_case("per-row", {&c3_hot, &moved, &negzero, &many, &c3_twin}, {0, 1, 2, 3, 4, 3, 2, 1, 0}, 4);
+  plan_case("per-row", {&c3_hot, &moved, &negzero, &many, &c3_twin}, {0, 1, 2, 3, 4, 3, 2, 1, 0}, 4, true);
   bool threw = false;
   try {
     twr::PlanJacLsq({&c3_hot}, {0, 1});

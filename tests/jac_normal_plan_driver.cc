@@ -1,6 +1,6 @@
 // Checks of the one-pass normal product's plan (twr_jac_normal_mul) on the host: the tables and work lists twr::PlanJacNormal
-// builds, and that twr::PlanJacOps still gives what it gave.  Built and run by tests/test_jac_normal_plan.py (g++ against
-// towr_amd/csrc/structure.cc, no HIP).  With a directory as argument, every case's emulation of the plan's summation order on a
+// builds, and that twr::PlanJacOps still gives what it gave.  Built and run by tests/test_jac_normal_plan.py
+// (tests/host_build.py: g++ against the host planner, no HIP).  With a directory as argument, every case's emulation of the plan's summation order on a
 // random matrix is written there for the test to hold against scipy.  -DOPS_ONLY leaves out everything PlanJacNormal: the
 // program then only prints the fingerprints of PlanJacOps (how the ones in the test were taken from the commit before).
 #include <cstdio>
@@ -11,87 +11,44 @@
 #include <string>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                  \
-  do {                                    \
-    if (!(cond)) {                        \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fprintf(stderr, "\n");         \
-      ++fails;                            \
-    }                                     \
-  } while (0)
-
-static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 200,
-                            std::shared_ptr<const twr::TerrainGrid> grid = nullptr, double base_poly = 0.1) {
-  twr::Structure S;
-  twr::ModelPreset(robot, terrain, &S.model);
-  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
-  twr_params& p = S.params;
-  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
-  p.duration_base_poly = base_poly;
-  p.polys_per_swing = 2;
-  p.polys_per_stance_force = 3;
-  p.constraint_sets = sets;
-  p.reserved_ = 0;
-  p.dt_base_motion = 0.025;
-  p.base_z_init = -S.model.nominal_stance[0][2];
-  S.grid = grid;
-  S.Build();
-  return S;
-}
-
-// A pattern made by hand (only what the plans read): `rows` rows over n variables, row r with len[r] entries from column
-// first[r] on, every `step`-th column.
-static twr::Structure pattern(int n, const std::vector<int>& first, const std::vector<int>& len, int step) {
-  twr::Structure S{};
-  S.n_vars = n;
-  S.n_rows = (int)len.size();
-  S.row_ptr.push_back(0);
-  for (size_t r = 0; r < len.size(); ++r) {
-    for (int j = 0; j < len[r]; ++j) S.col_idx.push_back(first[r] + j * step);
-    S.row_ptr.push_back((int32_t)S.col_idx.size());
-  }
-  S.nnz = (int)S.col_idx.size();
-  return S;
-}
-
-static uint64_t fnv(uint64_t h, const void* data, size_t bytes) {
-  const unsigned char* p = static_cast<const unsigned char*>(data);
-  for (size_t i = 0; i < bytes; ++i) h = (h ^ p[i]) * 1099511628211ull;
-  return h;
-}
-template <class T>
-static uint64_t fnv(uint64_t h, const std::vector<T>& v) {
-  const uint64_t n = v.size();
-  h = fnv(h, &n, sizeof n);
-  return v.empty() ? h : fnv(h, v.data(), v.size() * sizeof(T));
-}
+#include "../towr_amd/csrc/jac_plan.h"
+#include "plan_driver_common.h"
 
 // Everything PlanJacOps returns, as one number
 static uint64_t ops_fingerprint(const twr::JacOpsPlan& J) {
-  uint64_t h = 1469598103934665603ull;
-  h = fnv(h, J.x_off), h = fnv(h, J.g_off), h = fnv(h, J.j_off), h = fnv(h, J.tables), h = fnv(h, J.pattern_of_struct);
-  h = fnv(h, J.mul), h = fnv(h, J.tmul), h = fnv(h, J.fold);
-  const int64_t tail[5] = {J.distinct_patterns, J.slab, J.mul_lds_x, J.table_bytes_mul, J.table_bytes_tmul};
-  return fnv(h, tail, sizeof tail);
+  Fnv f;
+  f.vec64(J.x_off), f.vec64(J.g_off), f.vec64(J.j_off), f.vec64(J.tables), f.vec64(J.pattern_of_struct);
+  f.vec64(J.mul), f.vec64(J.tmul), f.vec64(J.fold);
+  for (int64_t v : {(int64_t)J.distinct_patterns, J.slab, (int64_t)J.mul_lds_x, J.table_bytes_mul, J.table_bytes_tmul}) f.i64(v);
+  return f.h;
 }
 
 #ifndef OPS_ONLY
-template <class T>
-static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
+// Everything PlanJacNormal returns
+static uint64_t normal_fingerprint(const twr::JacNormalPlan& N) {
+  Fnv f;
+  f.vec64(N.x_off), f.vec64(N.g_off), f.vec64(N.j_off), f.vec64(N.tables), f.vec64(N.work), f.vec64(N.fold);
+  f.i64(N.slab), f.i64(N.lds_x), f.i64(N.tile);
+  return f.h;
 }
 
-// a table of `count` T at byte offset off of `tables`, or nullptr (and a failure) when it does not lie inside
-template <class T>
-static const T* table(const char* name, const std::vector<char>& tables, uint64_t off, size_t count) {
-  const bool ok = off % alignof(T) == 0 && off <= tables.size() && count * sizeof(T) <= tables.size() - off;
-  CHECK(ok, "%s: table [%llu, +%zu x %zu) outside the %zu bytes", name, (unsigned long long)off, count, sizeof(T), tables.size());
-  return ok ? reinterpret_cast<const T*>(tables.data() + off) : nullptr;
-}
+// Recorded from the commit before the planner was cut into units (this driver with -DTWR_RECORD_PARENT): the products' plan
+// after Place (before it: OPS_FINGERPRINTS of tests/test_jac_normal_plan.py), the one-pass plan at tiles of 256 and 1024
+// entries before and after Place.
+// {PlanJacOps placed; PlanJacNormal at a tile of 256, placed, at 1024, placed}
+static const ParentRecord<5> kParent[] = {
+    {"C3x16", {0x8e2becdde03d5e1eull, 0x8071889574083d95ull, 0xa89ea3d7852fe679ull, 0x81b73abadd89f034ull, 0xbf975fc11cff7a90ull}},
+    {"twins", {0xc0650b918436d2b1ull, 0xa7ca115457f5a065ull, 0x289f102421911eedull, 0xf7927d2d6e533d1aull, 0xb3043811888e4abeull}},
+    {"every", {0x3fc121df9bd4e0ffull, 0x7300c98e216ed2edull, 0x96d5ad51ae228ef5ull, 0xced325113e59cc41ull, 0x9c57fa596e99ef3eull}},
+    {"ragged", {0x78e115d51d01f5adull, 0x5645be43d402c5efull, 0x55ce00823feb4c77ull, 0xd060b78b4750edebull, 0x4574397672168224ull}},
+    {"grid", {0xdb169c20c50b6089ull, 0x30145d001c681739ull, 0x8187c221485f1c5eull, 0xabefaefddf0f163eull, 0xd8f7f9a80d119cdeull}},
+    {"wide", {0x6d2c011f92496debull, 0xbb8971a5f900a5d7ull, 0x5aac340088141f1bull, 0xc96cb970e2759ab4ull, 0x748570666619dc0cull}},
+    {"longrow", {0x4a47bf587cede2c9ull, 0x09fd84d2760dd97cull, 0x87cf897ad5044217ull, 0x10441f2ccd0979a1ull, 0x7e601572474bf245ull}},
+};
+static const uint64_t kOpsBase = 0x7e0000000000ull, kNormalBase = 0x7d0000000000ull;
+#endif
 
+#ifndef OPS_ONLY
 struct Shape {   // one problem's work records relative to the problem, and the order of the terms of every partial and column
   std::vector<int64_t> shape;
   std::vector<std::vector<int>> partial;   // [slot] -> CSR positions in summation order
@@ -240,6 +197,16 @@ static void plan_case(const char* name, const std::vector<const twr::Structure*>
   const twr::JacOpsPlan J = twr::PlanJacOps(sp, sop);
   std::printf("opsplan %s %016llx\n", name, (unsigned long long)ops_fingerprint(J));
 #ifndef OPS_ONLY
+  twr::JacOpsPlan placed = J;
+  placed.Place(kOpsBase);
+  uint64_t hash[5] = {ops_fingerprint(placed)};
+  for (int t = 0; t < 2; ++t) {
+    twr::JacNormalPlan T = twr::PlanJacNormal(sp, sop, t ? 1024 : 256);
+    hash[1 + 2 * t] = normal_fingerprint(T);
+    T.Place(kOpsBase, kNormalBase);
+    hash[2 + 2 * t] = normal_fingerprint(T);
+  }
+  parent_record(kParent, name, hash);
   const twr::JacNormalPlan N = twr::PlanJacNormal(sp, sop), M = twr::PlanJacNormal(sp, sop);
   CHECK(same_bytes(N.tables, M.tables) && same_bytes(N.work, M.work) && same_bytes(N.fold, M.fold) && N.slab == M.slab,
         "%s: planning twice differs", name);
@@ -317,13 +284,13 @@ static void plan_case(const char* name, const std::vector<const twr::Structure*>
 int main(int argc, char** argv) {
   const char* dir = argc > 1 ? argv[1] : nullptr;
   // the six batches of tests/jac_plan_driver.cc
-  const twr::Structure c3 = build(3, 0, 1, 2.0, 63), c3_hot = build(3, 0, 1, 2.0, 27), c3_twin = build(3, 0, 1, 2.0, 27);
-  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1);   // every family, optimised timings, base_z_init set
+  const twr::Structure c3 = build(3, 0, 1, 2.0, 63, 1.0, 200), c3_hot = build(3, 0, 1, 2.0, 27, 1.0, 200), c3_twin = build(3, 0, 1, 2.0, 27, 1.0, 200);
+  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1, 200);   // every family, optimised timings, base_z_init set
   plan_case("C3x16", {&c3_hot}, std::vector<int32_t>(16, 0), dir);
   plan_case("twins", {&c3_hot, &c3_twin}, {0, 1, 1, 0}, dir);
   plan_case("every", {&every, &c3}, {0, 1, 0}, dir);
   std::vector<twr::Structure> ss;
-  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9));
+  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9, 200));
   std::vector<const twr::Structure*> sp;
   for (const auto& s : ss) sp.push_back(&s);
   plan_case("ragged", sp, {0, 1, 2, 3, 4, 5, 3, 1, 1, 0}, dir);

@@ -1,5 +1,5 @@
 // Checks of the product plans (twr_jac_mul / twr_jac_tmul) on the host: the tables and work lists twr::PlanJacOps builds, and the
-// CSC view twr::TransposePattern.  Built and run by tests/test_jac_plan.py (g++ against towr_amd/csrc/structure.cc, no HIP).
+// CSC view twr::TransposePattern.  Built and run by tests/test_jac_plan.py (g++ against the host planner, no HIP).
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -7,45 +7,13 @@
 #include <string>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                  \
-  do {                                    \
-    if (!(cond)) {                        \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fprintf(stderr, "\n");         \
-      ++fails;                            \
-    }                                     \
-  } while (0)
-
-static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 200,
-                            std::shared_ptr<const twr::TerrainGrid> grid = nullptr, double base_poly = 0.1) {
-  twr::Structure S;
-  twr::ModelPreset(robot, terrain, &S.model);
-  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
-  twr_params& p = S.params;
-  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
-  p.duration_base_poly = base_poly;
-  p.polys_per_swing = 2;
-  p.polys_per_stance_force = 3;
-  p.constraint_sets = sets;
-  p.reserved_ = 0;
-  p.dt_base_motion = 0.025;
-  p.base_z_init = -S.model.nominal_stance[0][2];
-  S.grid = grid;
-  S.Build();
-  return S;
-}
+#include "../towr_amd/csrc/batch_plan.h"
+#include "../towr_amd/csrc/jac_plan.h"
+#include "plan_driver_common.h"
 
 template <class T>
 static const T* table(const twr::JacOpsPlan& J, uint64_t off) {
   return reinterpret_cast<const T*>(J.tables.data() + off);
-}
-
-template <class T>
-static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
 }
 
 // The terms of every output of problem p, in the order the kernels add them (CSR positions), with the per-problem parts of the
@@ -160,9 +128,7 @@ static std::vector<Order> plan_case(const char* name, const std::vector<const tw
             J.slab == K.slab && J.pattern_of_struct == K.pattern_of_struct,
         "%s: planning twice differs", name);
   CHECK(J.distinct_patterns == want_distinct, "%s: %d distinct patterns, want %d", name, J.distinct_patterns, want_distinct);
-  std::vector<uint64_t> at;
-  for (size_t i = 0; i < sp.size(); ++i) at.push_back(0x7f0000000000ull + 0x100000ull * i);
-  const twr::BatchPlan B = twr::PlanBatch(sp, sop, at, 256, (int64_t)256 << 20, twr::kForceChunk);
+  const twr::BatchPlan B = twr::PlanBatch(sp, sop, blob_at(sp.size()), 256, (int64_t)256 << 20, twr::kForceChunk);
   CHECK(J.x_off == B.x_off && J.g_off == B.g_off && J.j_off == B.j_off, "%s: layout differs from PlanBatch", name);
   const int n = (int)sop.size();
   // the problem of a work record: by x_off (every structure has variables), by j_off for J^T w (only problems with entries
@@ -206,13 +172,13 @@ static std::vector<Order> plan_case(const char* name, const std::vector<const tw
 }
 
 int main() {
-  const twr::Structure c3 = build(3, 0, 1, 2.0, 63), c3_hot = build(3, 0, 1, 2.0, 27), c3_twin = build(3, 0, 1, 2.0, 27);
-  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1);   // every family, optimised timings, base_z_init set
+  const twr::Structure c3 = build(3, 0, 1, 2.0, 63, 1.0, 200), c3_hot = build(3, 0, 1, 2.0, 27, 1.0, 200), c3_twin = build(3, 0, 1, 2.0, 27, 1.0, 200);
+  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1, 200);   // every family, optimised timings, base_z_init set
   plan_case("C3x16", {&c3_hot}, std::vector<int32_t>(16, 0), 1);
   plan_case("twins", {&c3_hot, &c3_twin}, {0, 1, 1, 0}, 1);   // two structures from identical inputs: one pattern
   plan_case("every", {&every, &c3}, {0, 1, 0}, 2);
   std::vector<twr::Structure> ss;
-  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9));
+  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9, 200));
   std::vector<const twr::Structure*> sp;
   for (const auto& s : ss) sp.push_back(&s);
   plan_case("ragged", sp, {0, 1, 2, 3, 4, 5, 3, 1, 1, 0}, 6);

@@ -1,6 +1,6 @@
 // Checks of the scaled solve's part of the least-squares plan (twr_jac_lsq_solve_scaled) on the host: the second workspace
 // twr::PlanJacLsq plans (ws2_*: e and c o p in the x layout), and that the first workspace keeps the formula it had before the
-// scaled solve existed.  Built and run by tests/test_jac_scaled_plan.py (g++ against towr_amd/csrc/structure.cc under ASan + UBSan,
+// scaled solve existed.  Built and run by tests/test_jac_scaled_plan.py (g++ against the host planner under ASan + UBSan,
 // no HIP).
 #include <algorithm>
 #include <cstdio>
@@ -9,35 +9,8 @@
 #include <utility>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                  \
-  do {                                    \
-    if (!(cond)) {                        \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fprintf(stderr, "\n");         \
-      ++fails;                            \
-    }                                     \
-  } while (0)
-
-static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 200,
-                            double base_poly = 0.1) {
-  twr::Structure S;
-  twr::ModelPreset(robot, terrain, &S.model);
-  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
-  twr_params& p = S.params;
-  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
-  p.duration_base_poly = base_poly;
-  p.polys_per_swing = 2;
-  p.polys_per_stance_force = 3;
-  p.constraint_sets = sets;
-  p.reserved_ = 0;
-  p.dt_base_motion = 0.025;
-  p.base_z_init = -S.model.nominal_stance[0][2];
-  S.Build();
-  return S;
-}
+#include "../towr_amd/csrc/jac_plan.h"
+#include "plan_driver_common.h"
 
 static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop) {
   const twr::JacLsqPlan L = twr::PlanJacLsq(sp, sop), K = twr::PlanJacLsq(sp, sop);
@@ -67,17 +40,17 @@ static void plan_case(const char* name, const std::vector<const twr::Structure*>
 }
 
 int main() {
-  const twr::Structure c3 = build(3, 0, 1, 2.0, 63), c3_hot = build(3, 0, 1, 2.0, 27);
-  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1);
+  const twr::Structure c3 = build(3, 0, 1, 2.0, 63, 1.0, 200), c3_hot = build(3, 0, 1, 2.0, 27, 1.0, 200);
+  const twr::Structure every = build(3, 2, 0, 2.4, 255, 1.1, 200);
   plan_case("C3x16", {&c3_hot}, std::vector<int32_t>(16, 0));
   plan_case("every", {&every, &c3}, {0, 1, 0});
   std::vector<twr::Structure> ss;
-  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9));
+  for (int i = 0; i < 6; ++i) ss.push_back(build(i % 2 ? 2 : 1, 4, i % 3, 1.2 + 0.3 * i, i % 2 ? 27 : 63, 0.9, 200));
   std::vector<const twr::Structure*> sp;
   for (const auto& s : ss) sp.push_back(&s);
   plan_case("ragged", sp, {0, 1, 2, 3, 4, 5, 3, 1, 1, 0});
   plan_case("one", sp, {3});
-  const twr::Structure wide = build(3, 0, 1, 2.0, 27, 1.0, 200, 0.003);
+  const twr::Structure wide = build(3, 0, 1, 2.0, 27, 1.0, 200, nullptr, 0.003);
   CHECK(wide.n_vars > twr::kJacLdsX, "the wide structure has %d variables", wide.n_vars);
   plan_case("wide", {&wide, &c3_hot}, {0, 1, 0});
   // an odd number of variables in all: the segments still start on 16-byte boundaries

@@ -1,42 +1,14 @@
 // Checks of the scoring plan (twr_batch_eval_scores) on the host: the lists twr::PlanBatch builds for the fold
 // (score_blob / score_first / score_slot, score_slab) and the steps twr::PlanEval plans for a scoring request (kEvalScores).
-// Built and run by tests/test_score_plan.py (g++ against towr_amd/csrc/structure.cc, no HIP).
+// Built and run by tests/test_score_plan.py (g++ against the host planner, no HIP).
 #include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "../towr_amd/csrc/structure.h"
-
-static int fails = 0;
-#define CHECK(cond, ...)                  \
-  do {                                    \
-    if (!(cond)) {                        \
-      std::fprintf(stderr, __VA_ARGS__);  \
-      std::fprintf(stderr, "\n");         \
-      ++fails;                            \
-    }                                     \
-  } while (0)
-
-static twr::Structure build(int robot, int terrain, int combo, double T, int sets, double scale = 1.0, int K = 200,
-                            std::shared_ptr<const twr::TerrainGrid> grid = nullptr, double base_poly = 0.1) {
-  twr::Structure S;
-  twr::ModelPreset(robot, terrain, &S.model);
-  twr::GaitCombo(S.model.n_ee, combo, T, scale, &S.schedule);
-  twr_params& p = S.params;
-  p.dt_dynamic = p.dt_rom = T / (K - 1.5);
-  p.duration_base_poly = base_poly;
-  p.polys_per_swing = 2;
-  p.polys_per_stance_force = 3;
-  p.constraint_sets = sets;
-  p.reserved_ = 0;
-  p.dt_base_motion = 0.025;
-  p.base_z_init = -S.model.nominal_stance[0][2];
-  S.grid = grid;
-  S.Build();
-  return S;
-}
+#include "../towr_amd/csrc/batch_plan.h"
+#include "plan_driver_common.h"
 
 static twr::EvalShape shape_of(const twr::BatchPlan& B, int n_cu, int flags, bool events = false) {
   const auto& L = B.lists;
@@ -115,15 +87,9 @@ static void check_coverage(const char* name, const std::vector<const twr::Struct
     if (L.flat[i].cnt > 0) CHECK(owner[i] >= 0, "%s: flat item %zu is in no problem's fold", name, i);
 }
 
-template <class T>
-static bool same_bytes(const std::vector<T>& a, const std::vector<T>& b) {
-  return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(T)) == 0);
-}
-
 static void plan_case(const char* name, const std::vector<const twr::Structure*>& sp, const std::vector<int32_t>& sop, bool fused) {
   const int n_cu = 256;
-  std::vector<uint64_t> at;
-  for (size_t i = 0; i < sp.size(); ++i) at.push_back(0x7f0000000000ull + 0x100000ull * i);
+  const std::vector<uint64_t> at = blob_at(sp.size());
   const twr::BatchPlan B = twr::PlanBatch(sp, sop, at, n_cu, (int64_t)256 << 20, twr::kForceChunk);
   const twr::BatchPlan C = twr::PlanBatch(sp, sop, at, n_cu, (int64_t)256 << 20, twr::kForceChunk);
   CHECK(B.score_fused == fused, "%s: score_fused %d, want %d", name, (int)B.score_fused, (int)fused);
@@ -185,13 +151,13 @@ static void plan_case(const char* name, const std::vector<const twr::Structure*>
 }
 
 int main() {
-  const twr::Structure c3 = build(3, 0, 1, 2.0, 63), c3_timings = build(3, 0, 1, 2.0, 127), c3_hot = build(3, 0, 1, 2.0, 27);
+  const twr::Structure c3 = build(3, 0, 1, 2.0, 63, 1.0, 200), c3_timings = build(3, 0, 1, 2.0, 127, 1.0, 200), c3_hot = build(3, 0, 1, 2.0, 27, 1.0, 200);
   plan_case("C3x2048", {&c3}, std::vector<int32_t>(2048, 0), true);   // the values path would chunk the node sets here
   plan_case("C3x200", {&c3}, std::vector<int32_t>(200, 0), true);
   plan_case("single", {&c3_hot}, {0}, true);
   std::vector<twr::Structure> ss;
   for (int i = 0; i < 11; ++i)
-    ss.push_back(build(2, 4, i == 10 ? 3 : 1, i < 8 ? 1.2 + 0.2 * i : 2.0, 27, i < 8 ? 0.80 : 0.80 + 0.016 * (i - 7)));
+    ss.push_back(build(2, 4, i == 10 ? 3 : 1, i < 8 ? 1.2 + 0.2 * i : 2.0, 27, i < 8 ? 0.80 : 0.80 + 0.016 * (i - 7), 200));
   std::vector<const twr::Structure*> sp;
   for (const auto& s : ss) sp.push_back(&s);
   plan_case("ragged", sp, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 3, 5, 5, 0}, true);
@@ -201,7 +167,7 @@ int main() {
   for (int i = 0; i < grid->rows * grid->cols; ++i) grid->heights.push_back(0.05 * ((i * 7919) % 13) / 13.0);
   const twr::Structure g1 = build(3, 7, 1, 2.0, 63, 1.0, 200, grid), g2 = build(3, 7, 0, 2.4, 27, 1.0, 120, grid);
   plan_case("grid", {&g1, &g2}, {0, 1, 1, 0, 0, 1, 0}, true);
-  const twr::Structure all = build(3, 2, 0, 2.4, 191, 1.1);   // every family but totalduration, baseMotion included
+  const twr::Structure all = build(3, 2, 0, 2.4, 191, 1.1, 200);   // every family but totalduration, baseMotion included
   plan_case("all-sets", {&all, &c3}, {0, 1, 0}, true);
   // the fallbacks: optimised timings, fixed and optimised timings mixed, more than 2046 variables
   plan_case("timings", {&c3_timings}, {0, 0}, false);

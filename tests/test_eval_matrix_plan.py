@@ -1,6 +1,6 @@
 """The instantiation matrix of the evaluation kernels (tests/eval_matrix.py), checked on the host: tests/eval_matrix_driver.cc,
-built with g++ against the product's planner (towr_amd/csrc/structure.cc) under UndefinedBehaviorSanitizer.  The driver
-enumerates the complete set of instantiations from the key lists of structure.h, builds every row of the matrix, plans every
+built with g++ against the product's planner (tests/host_build.py) under AddressSanitizer + UndefinedBehaviorSanitizer.  The driver
+enumerates the complete set of instantiations from the key lists of eval_plan.h, builds every row of the matrix, plans every
 flag set with and without per-kernel events plus the two scoring requests, and asserts that every row reaches what it
 claims and that the claims plus the exclusion list (at most 8 rule-quoted entries) are exactly the complete set."""
 import os
@@ -8,17 +8,12 @@ import subprocess
 import tempfile
 
 from tests import eval_matrix
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import plan_driver
 
 
 def test_matrix_covers_every_instantiation():
     with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "eval_matrix_driver")
-        subprocess.check_call(["g++", "-O1", "-g", "-D_GLIBCXX_ASSERTIONS", "-fsanitize=undefined", "-fno-sanitize-recover=undefined",
-                               "-std=c++17", "-Wall", "-Wno-sign-compare", "-o", exe,
-                               os.path.join(ROOT, "tests", "eval_matrix_driver.cc"),
-                               os.path.join(ROOT, "towr_amd", "csrc", "structure.cc")])
+        exe = plan_driver("eval_matrix_driver")
 
         def run(name, text):
             with open(os.path.join(tmp, name), "w") as f:

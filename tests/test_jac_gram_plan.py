@@ -1,12 +1,10 @@
 """Host side of the Gram matrix (twr_jac_gram, twr_jac_gram_mul, twr_jac_lsq_solve_gram, twr_jac_lm_set_solver): the plan of
-twr::PlanJacGram checked by tests/jac_gram_plan_driver.cc (g++ against towr_amd/csrc/structure.cc under AddressSanitizer +
+twr::PlanJacGram checked by tests/jac_gram_plan_driver.cc (g++ against the host planner, tests/host_build.py, under AddressSanitizer +
 UndefinedBehaviorSanitizer) -- the pattern against the structural P^T P taken naively, symmetry and ascending columns, every
 term of every stored entry against the rows of J, gram_off, shared tables, the work lists' coverage and the limits -- the
 argument checks of the new entry points, which need no device, and Structure.gram_pattern() against scipy."""
 import ctypes as C
-import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -15,18 +13,12 @@ import scipy.sparse as sp
 import towr_amd as ta
 
 from .common import Case, baseline_cases, hopper_schedule, random_case
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from .host_build import plan_driver
 
 
 def test_gram_plans():
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "jac_gram_plan_driver")
-        subprocess.check_call(["g++", "-O1", "-g", "-D_GLIBCXX_ASSERTIONS", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                               "-static-libasan", "-std=c++17", "-Wall", "-Wno-sign-compare", "-o", exe,
-                               os.path.join(ROOT, "tests", "jac_gram_plan_driver.cc"),
-                               os.path.join(ROOT, "towr_amd", "csrc", "structure.cc")])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
+    exe = plan_driver("jac_gram_plan_driver")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 failures" in r.stdout and "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr
 

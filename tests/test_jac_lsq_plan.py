@@ -1,30 +1,22 @@
 """Host side of the least-squares step (twr_jac_lsq_*): the plan of twr::PlanJacLsq checked by tests/jac_lsq_plan_driver.cc (g++
-against towr_amd/csrc/structure.cc under AddressSanitizer + UndefinedBehaviorSanitizer) on the shapes test_jac_plan.py uses --
+against the host planner, tests/host_build.py, under AddressSanitizer + UndefinedBehaviorSanitizer) on the shapes test_jac_plan.py uses --
 workspace segments disjoint and inside the allocation, every problem's record pointing at its own offsets, bound tables equal
 to the structures' per-row bounds (what twr_structure_bounds hands out) and shared exactly when byte-identical -- and the
 argument checks of the entry points, which need no device."""
 import ctypes as C
-import os
 import subprocess
-import tempfile
 
 import numpy as np
 
 import towr_amd as ta
 
 from .common import baseline_cases
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from .host_build import plan_driver
 
 
 def test_lsq_plans():
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "jac_lsq_plan_driver")
-        subprocess.check_call(["g++", "-O1", "-g", "-D_GLIBCXX_ASSERTIONS", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                               "-static-libasan", "-std=c++17", "-Wall", "-Wno-sign-compare", "-o", exe,
-                               os.path.join(ROOT, "tests", "jac_lsq_plan_driver.cc"),
-                               os.path.join(ROOT, "towr_amd", "csrc", "structure.cc")])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
+    exe = plan_driver("jac_lsq_plan_driver")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 failures" in r.stdout and "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr
 

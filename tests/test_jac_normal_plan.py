@@ -1,5 +1,5 @@
 """Host side of the one-pass normal product (twr_jac_normal_mul): the plan of twr::PlanJacNormal checked by
-tests/jac_normal_plan_driver.cc (g++ against towr_amd/csrc/structure.cc under AddressSanitizer + UndefinedBehaviorSanitizer)
+tests/jac_normal_plan_driver.cc (g++ against the host planner, tests/host_build.py, under AddressSanitizer + UndefinedBehaviorSanitizer)
 over the six batches of the product plans' test and a batch with rows longer than one tile: every entry in exactly one block
 and one partial, blocks of whole rows within the limits (a longer row alone), every partial folded once, by its column, in
 block order, every table inside the tables, identical plans when planning twice and alone.  The driver's emulation of the
@@ -14,13 +14,17 @@ import scipy.sparse as sp
 
 import towr_amd as ta
 
+from tests.host_build import plan_driver
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # FNV-1a over everything twr::PlanJacOps returns (ops_fingerprint of the driver: offsets, table bytes, the three work lists as
 # bytes -- their records have no padding --, slab and counters), taken from the commit before twr::PlanJacNormal existed.
 # PlanJacOps is meant to stay as it is; after an INTENDED change to it, take them again by the same recipe, from a checkout of
 # the commit that has the change:
-#   g++ -O1 -std=c++17 -DOPS_ONLY -o ops_only tests/jac_normal_plan_driver.cc towr_amd/csrc/structure.cc && ./ops_only
+#   cd towr_amd/csrc && g++ -O1 -std=c++17 -DOPS_ONLY -o ops_only ../../tests/jac_normal_plan_driver.cc structure.cc presets.cc jac_plan.cc
+#   ./ops_only
+# or, in the tests' own build, tests.host_build.plan_driver("jac_normal_plan_driver", defines=("OPS_ONLY",))
 # (-DOPS_ONLY leaves out everything that needs PlanJacNormal, so the driver builds against sources that lack it) and copy the
 # "opsplan <case> <fingerprint>" lines here.
 OPS_FINGERPRINTS = {
@@ -54,11 +58,7 @@ def _records(path):
 
 def test_normal_product_plans():
     with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "jac_normal_plan_driver")
-        subprocess.check_call(["g++", "-O1", "-g", "-D_GLIBCXX_ASSERTIONS", "-fsanitize=address,undefined",
-                               "-fno-sanitize-recover=undefined", "-static-libasan", "-std=c++17", "-Wall", "-Wno-sign-compare",
-                               "-o", exe, os.path.join(ROOT, "tests", "jac_normal_plan_driver.cc"),
-                               os.path.join(ROOT, "towr_amd", "csrc", "structure.cc")])
+        exe = plan_driver("jac_normal_plan_driver")
         out = os.path.join(tmp, "out")
         os.mkdir(out)
         r = subprocess.run([exe, out], capture_output=True, text=True, timeout=900)

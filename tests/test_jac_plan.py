@@ -1,11 +1,9 @@
 """Host side of the Jacobian products (twr_jac_mul / twr_jac_tmul): the CSC view twr_structure_transpose against scipy, and
-the product plans of twr::PlanJacOps checked by tests/jac_plan_driver.cc (g++ against towr_amd/csrc/structure.cc under
+the product plans of twr::PlanJacOps checked by tests/jac_plan_driver.cc (g++ against the host planner, tests/host_build.py, under AddressSanitizer +
 UndefinedBehaviorSanitizer): every entry covered once per product, every row and column written once, the order of every
 sum a function of the structure alone, identical plans when planning twice, one table for byte-identical patterns, and the
 layout of PlanBatch."""
-import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -14,8 +12,7 @@ import scipy.sparse as sp
 import towr_amd as ta
 
 from .common import Case, baseline_cases, random_case
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from .host_build import plan_driver
 
 
 def _assert_transpose(S, what=""):
@@ -63,12 +60,7 @@ def test_transpose_of_c3_sizes():
 
 
 def test_product_plans():
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "jac_plan_driver")
-        subprocess.check_call(["g++", "-O1", "-g", "-D_GLIBCXX_ASSERTIONS", "-fsanitize=undefined", "-fno-sanitize-recover=undefined",
-                               "-std=c++17", "-Wall", "-Wno-sign-compare", "-o", exe,
-                               os.path.join(ROOT, "tests", "jac_plan_driver.cc"),
-                               os.path.join(ROOT, "towr_amd", "csrc", "structure.cc")])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
+    exe = plan_driver("jac_plan_driver")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 failures" in r.stdout and "runtime error" not in r.stderr

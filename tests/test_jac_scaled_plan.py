@@ -1,27 +1,20 @@
 """Host side of the Marquardt-scaled least-squares step (twr_jac_col_sqnorms / twr_jac_col_scale / twr_jac_lsq_solve_scaled): the
 second workspace twr::PlanJacLsq plans for it, checked by tests/jac_scaled_plan_driver.cc (g++ against
-towr_amd/csrc/structure.cc under AddressSanitizer + UndefinedBehaviorSanitizer) -- segments on 16-byte boundaries, disjoint,
+the host planner, tests/host_build.py, under AddressSanitizer + UndefinedBehaviorSanitizer) -- segments on 16-byte boundaries, disjoint,
 inside the second allocation, the same when planned twice, the first workspace unchanged -- and the argument checks of the new
 entry points, which need no device."""
-import os
 import subprocess
-import tempfile
 
 import numpy as np
 
 import towr_amd as ta
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import plan_driver
 
 
 def test_scaled_plans():
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "jac_scaled_plan_driver")
-        subprocess.check_call(["g++", "-O1", "-g", "-D_GLIBCXX_ASSERTIONS", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                               "-static-libasan", "-std=c++17", "-Wall", "-Wno-sign-compare", "-o", exe,
-                               os.path.join(ROOT, "tests", "jac_scaled_plan_driver.cc"),
-                               os.path.join(ROOT, "towr_amd", "csrc", "structure.cc")])
-        r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
+    exe = plan_driver("jac_scaled_plan_driver")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "0 failures" in r.stdout and "runtime error" not in r.stderr and "ERROR: AddressSanitizer" not in r.stderr
 

@@ -488,7 +488,7 @@ static twr::LaunchTuning tuning_knobs() {
   return t;
 }
 
-// The shape of a call on this batch (structure.h MakeEvalShape): what twr_batch_eval, the scoring entry points and
+// The shape of a call on this batch (batch_plan.h MakeEvalShape): what twr_batch_eval, the scoring entry points and
 // twr_batch_eval_plan all plan from.
 static twr::EvalShape eval_shape(const twr_batch* b, int flags, bool events) {
   twr::EvalCounts c;

@@ -12,6 +12,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "jac_plan.h"
 #include "launch.h"
 
 struct twr_structure {

@@ -9,6 +9,7 @@
 #include "jac_lsq.hip"
 #include "jac_products.hip"
 #include "capi_internal.h"
+#include "jac_plan.h"
 
 struct twr_jac_ops {   // twr::PlanJacOps's tables and work lists on the device, and the slab of J^T w's partials
   int device = 0, n_problems = 0;

@@ -454,7 +454,7 @@ struct DynWork {          // cnt <= 16 time nodes of "dynamic"
 };
 static_assert(sizeof(DynWork) == 96, "DynWork layout");
 
-// Uniform dyn list (structure.h PlanBatch / PlanEval): every problem of the batch is the SAME structure, so slice `kind` of
+// Uniform dyn list (batch_plan.h PlanBatch / eval_plan.h PlanEval): every problem of the batch is the SAME structure, so slice `kind` of
 // every problem reads the same records and differs in three offsets that are affine in the problem index.  A wave of
 // dyn_uniform_kernel owns one kind for the whole launch: it loads that kind's records once, from the slice of problem 0 at
 // list position kind * first_stride, and then takes one problem per iteration.  Workgroups are dealt round-robin over the 8
@@ -556,7 +556,7 @@ struct RomPhaseWork {     // one pass: cnt <= 16 time nodes of one (problem, ee)
 };
 static_assert(sizeof(RomPhaseWork) == 56, "RomPhaseWork layout");
 
-// Launch geometry the host planner (structure.h PlanEval) shares with the kernels.
+// Launch geometry the host planner (eval_plan.h PlanEval) shares with the kernels.
 constexpr int kRomNitMax = (kRomStage + 2 + 127) / 128;   // 38: rom_kernel's copy-out of a whole image (store instructions)
 constexpr int kDynDump = kDynImage + 2 + 96;              // doubles of dyn_kernel's dump (its first, empty copy-out per workgroup)
 constexpr int kForceChunk = 32;                           // force nodes per chunk of node_chunk_kernel (25 values each)

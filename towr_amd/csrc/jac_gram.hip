@@ -1,6 +1,6 @@
 // The Gram matrix N_p = J_p^T W_p J_p of every problem of a batch, formed once per linearisation and kept, and what runs on it
 // (twr_jac_gram, twr_jac_gram_mul, twr_jac_lsq_solve_gram, include/towr_amd.h).  Tables and work lists are planned on the host
-// (twr::PlanJacGram, structure.h); every index comes from them, never from J, w, v or N.
+// (twr::PlanJacGram, jac_plan.h); every index comes from them, never from J, w, v or N.
 //   jac_gram_kernel:      one lane per stored entry (i, j), i >= j, of the lower triangle, in the planner's order (entries sorted
 //                         by the length of their lists, so the lanes of a wave do comparable work; a wave's table words lie
 //                         interleaved, term t of lane l at t * 64 + l, and are read in full lines).  The lane gathers J_ri and
@@ -19,7 +19,7 @@
 
 #include "jac_lsq.hip"
 #include "jac_products.hip"
-#include "structure.h"
+#include "jac_plan.h"
 
 namespace twr {
 

@@ -12,13 +12,13 @@
 //   lm_accept_kernel:    ok = merit_t < merit, x = xt where ok, mu, the counters
 // One workgroup of kLsqThreads lanes per problem in every kernel, the sums by lsq_sum over the index pairs of jac_lsq.hip: an order
 // fixed by the vector's length, so x after any number of steps has the same bits wherever the problem sits.  No atomics.  Every
-// index comes from the work record, never from the data.  The workspace is planned on the host (twr::PlanJacLm, structure.h).
+// index comes from the work record, never from the data.  The workspace is planned on the host (twr::PlanJacLm, jac_plan.h).
 // Included by capi_jac.cc (compiled as HIP for gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "jac_lsq.hip"
-#include "structure.h"
+#include "jac_plan.h"
 
 namespace twr {
 

@@ -2,7 +2,7 @@
 //   d_p = argmin_d  sum_r w_r (J_p d - b_p)_r^2 + mu_p |d|^2      <=>   (J_p^T W_p J_p + mu_p I) d_p = J_p^T W_p b_p
 // by CGLS on top of the two products of jac_products.hip (used as they are), and what feeds it: the bound-violation residual
 // (twr_jac_violation) and per-problem dot products (twr_jac_dot).  One workgroup of kLsqThreads lanes per problem in every kernel
-// here; the work records, the workspace and the bound tables are planned on the host (twr::PlanJacLsq, structure.h).
+// here; the work records, the workspace and the bound tables are planned on the host (twr::PlanJacLsq, jac_plan.h).
 //   lsq_start_kernel:  d = 0, r = b, t = w o r                                   (then z = J^T t by the product kernels)
 //   lsq_dir_kernel:    s = z - mu d, gamma' = s^T s; first: gamma0 = gamma', p = s; later: beta = gamma' / gamma, convergence
 //                      test, p = s + beta p; writes the problem's info                (then q = J p)
@@ -14,14 +14,14 @@
 // The one-pass solve (twr_jac_lsq_solve_onepass) recurs s instead and needs one vector kernel per iteration (lsq_onepass_kernel).
 // Every scalar (alpha, beta, gamma, mu, the state) stays on the device: the launch sequence depends on `iters` alone.  A problem
 // that has stopped (converged, or bad input) is skipped by its workgroup in every later kernel: its d, r, p no longer change.
-// No atomics: every sum is taken by lsq_sum in an order fixed by the vector's length (structure.h), so a problem's outputs have
+// No atomics: every sum is taken by lsq_sum in an order fixed by the vector's length (jac_plan.h), so a problem's outputs have
 // the same bits wherever it sits in whatever batch.  Every index comes from the work record, never from the data.
 // Included by capi_jac.cc (compiled as HIP for gfx950).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "jac_products.hip"
-#include "structure.h"
+#include "jac_plan.h"
 
 namespace twr {
 

@@ -4,7 +4,7 @@
 //   jac_colsq_kernel + jac_fold_kernel: c[x_off[p] + k] = sum_r w[g_off[p] + r] J_p[r][k]^2   (twr_jac_col_sqnorms)
 //   jac_normal_kernel + jac_fold_kernel: u = J_p^T (w o (J_p v)) and y = J_p v from one pass over J_p   (twr_jac_normal_mul;
 //                                        twr::PlanJacNormal)
-// The work split, the tables and the order of every sum are planned on the host (twr::PlanJacOps, structure.h).  No atomics:
+// The work split, the tables and the order of every sum are planned on the host (twr::PlanJacOps, jac_plan.h).  No atomics:
 // every output is written by exactly one lane, which sums its terms in an order fixed by the pattern alone, so a problem's
 // outputs have the same bits wherever it sits in whatever batch.  Every index comes from the plan's tables; J, v and w are
 // only multiplied and added, so a NaN or Inf in one problem's inputs reaches that problem's outputs and no other's.
@@ -14,7 +14,7 @@
 
 #include <tuple>
 
-#include "structure.h"
+#include "jac_plan.h"
 
 namespace twr {
 

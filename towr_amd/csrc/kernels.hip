@@ -96,7 +96,7 @@ static inline hipError_t twr_launch(void (*kern)(P...), dim3 grid, dim3 block, s
   return twr_launch_impl(reinterpret_cast<const void*>(kern), grid, block, lds, stream, vals, std::index_sequence_for<P...>{});
 }
 static inline hipError_t twr_first(hipError_t a, hipError_t b) { return a != hipSuccess ? a : b; }
-// The instantiation a planned launch names (structure.h: the key lists kStoresNT ... kValuesNx): pick<L>(v, f) returns
+// The instantiation a planned launch names (eval_plan.h: the key lists kStoresNT ... kValuesNx): pick<L>(v, f) returns
 // f(std::integral_constant<int, v>) if v is an entry of the list L, else a null kernel.  Every templated kernel has one
 // lookup built from these, the one place its instantiations are listed.
 template <const auto& L, class F, size_t... I>
@@ -1302,7 +1302,7 @@ constexpr int kDynValuesLds = 96 + 2 + kDynXsCap;
 // rom_kernel is compiled in its own translation unit (rom_tu.hip) with a different instruction scheduling
 // strategy: it is store bound and gains 4-5 % from clause-oriented scheduling, the VALU-bound kernels lose.
 constexpr int kRomLds = kRomStage + 2 + 64 + 192;   // doubles: image, per-lane trash slots, g
-// NIT = store instructions of the copy-out (structure.cc PlanEval picks it).
+// NIT = store instructions of the copy-out (eval_plan.cc PlanEval picks it).
 // (The hand-scheduled form of dyn_phase_kernel -- asm loads into AGPRs, one counted wait behind the copy-out -- was built
 // for this loop too and is SLOWER here, 0.98 vs 0.90 ms on one box: the compiler's clause-oriented schedule of the 28
 // loads with scalar bases and immediate offsets beats 28 separate asm loads with per-lane 64-bit addresses.)
@@ -2193,7 +2193,7 @@ __global__ __launch_bounds__(64 * kFlatGroup, 4) void eval_values_kernel(const F
 // it (ScoreAcc: same device functions, same arithmetic, the values go to the wave's running violations instead of g), and
 // every wave with work writes ONE partial record, wave w of workgroup b at slab + kScorePartial (4 b + w).  The node-based
 // sets are always taken by the launch's own node waves (one workgroup per problem, node_families waves), at every batch size:
-// node_chunk_kernel writes g.  score_fold_kernel then folds each problem's records in the order structure.cc planned.
+// node_chunk_kernel writes g.  score_fold_kernel then folds each problem's records in the order batch_plan.cc planned.
 // group_blob[b]: the blob of group b's problem (FlatWork carries no blob; the score record sits at its kScoreOff).
 template <int NX>
 __global__ __launch_bounds__(64 * kFlatGroup, 4) void eval_scores_kernel(const FlatWork* __restrict__ flat, const uint64_t* __restrict__ group_blob,
@@ -2239,7 +2239,7 @@ __global__ __launch_bounds__(64 * kFlatGroup, 4) void eval_scores_kernel(const F
   flat_stage_x<NX>(xr, w.i32(kFwNx), reinterpret_cast<double*>(xs), tid);
   if (cnt > 0 && !gather) flat_stage_polys(in, mine, lane);
   __syncthreads();
-  if (cnt <= 0) return;   // (an empty item has no partial record: structure.cc leaves it out of the fold)
+  if (cnt <= 0) return;   // (an empty item has no partial record: batch_plan.cc leaves it out of the fold)
   double* gs = reinterpret_cast<double*>(mine + kFlatPolyLds);
   if (w.i32(kFwDynamic) != 0) {
     if (gather) flat_dyn_math<true, true>(w, flat_node(in), nullptr, mine, xs, gs, lane, &sc);
@@ -3737,7 +3737,7 @@ static PRomFn rom_phase_kernel_fn(const LaunchStep& p) {
   });
 }
 
-// Host side of one evaluation: the launches structure.cc PlanEval plans (policy, thresholds and the measurements behind
+// Host side of one evaluation: the launches eval_plan.cc PlanEval plans (policy, thresholds and the measurements behind
 // them are there), issued in order on one stream.  Every launch is issued; the first error is returned.
 hipError_t launch_eval(const EvalShape& s, const EvalBuffers& b, hipStream_t stream, hipEvent_t* ev) {
   const EvalPlan plan = PlanEval(s);

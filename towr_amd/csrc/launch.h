@@ -2,7 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "structure.h"
+#include "batch_plan.h"
+#include "eval_plan.h"
 
 namespace twr {
 

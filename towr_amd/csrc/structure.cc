@@ -3,19 +3,15 @@
 #include "structure.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
-#include <exception>
 #include <limits>
 #include <map>
 #include <numeric>
 #include <stdexcept>
-#include <thread>
 #include <tuple>
-#include <unordered_map>
 
 namespace twr {
 
@@ -1564,1413 +1560,6 @@ void Structure::VariableBounds(const double* init_base, const double* final_base
         lower[off_schedule[e] + i] = 0.2;
         upper[off_schedule[e] + i] = 1.0;
       }
-}
-
-// ------------------------------------------------------------------ presets
-// RobotModel(Robot) (src/robot_model.cc:41-68) with the constants of
-// include/towr/models/examples/{monoped,biped,hyq,anymal}_model.h and models/go1/go1_model.h.
-void ModelPreset(int robot, int terrain, twr_model* m) {
-  std::memset(m, 0, sizeof(*m));
-  auto quad = [&](double xn, double yn, double zn) {
-    double s[4][3] = {{xn, yn, zn}, {xn, -yn, zn}, {-xn, yn, zn}, {-xn, -yn, zn}};  // LF RF LH RH
-    std::memcpy(m->nominal_stance, s, sizeof(s));
-  };
-  auto set = [&](int n_ee, double mass, double ixx, double iyy, double izz, double ixy, double ixz, double iyz,
-                 double dx, double dy, double dz) {
-    m->n_ee = n_ee;
-    m->mass = mass;
-    double I[6] = {ixx, iyy, izz, ixy, ixz, iyz};
-    std::memcpy(m->inertia, I, sizeof(I));
-    m->max_dev[0] = dx; m->max_dev[1] = dy; m->max_dev[2] = dz;
-  };
-  switch (robot) {
-    case TWR_ROBOT_MONOPED:
-      set(1, 20, 1.2, 5.5, 6.0, 0.0, -0.2, -0.01, 0.25, 0.15, 0.2);
-      m->nominal_stance[0][2] = -0.58;
-      break;
-    case TWR_ROBOT_BIPED:
-      set(2, 20, 1.209, 5.583, 6.056, 0.005, -0.190, -0.012, 0.25, 0.15, 0.15);
-      m->nominal_stance[0][1] = 0.20;  m->nominal_stance[0][2] = -0.65;
-      m->nominal_stance[1][1] = -0.20; m->nominal_stance[1][2] = -0.65;
-      break;
-    case TWR_ROBOT_HYQ:
-      set(4, 83, 4.26, 8.97, 9.88, -0.0063, 0.193, 0.0126, 0.25, 0.20, 0.10);
-      quad(0.31, 0.29, -0.58);
-      break;
-    case TWR_ROBOT_ANYMAL:
-      set(4, 29.5, 0.946438, 1.94478, 2.01835, 0.000938112, -0.00595386, -0.00146328, 0.15, 0.1, 0.10);
-      quad(0.34, 0.19, -0.42);
-      break;
-    case TWR_ROBOT_GO1:
-      set(4, 12.84, 0.0168128557, 0.063009565, 0.0716547275, -0.0002296769, -0.0002945293, -0.0000418731, 0.16, 0.12, 0.06);
-      quad(0.1881, 0.04675 + 0.08, -0.3);
-      break;
-    default: throw std::runtime_error("unknown robot id");
-  }
-  if (terrain < TWR_TERRAIN_FLAT || terrain > TWR_TERRAIN_GRID_MAP) throw std::runtime_error("unknown terrain id");
-  m->terrain_id = terrain;
-  m->gravity = 9.80665;     // dynamic_model.cc:37
-  m->friction = 0.5;        // height_map.h:136
-  m->force_limit = 1000.0;  // parameters.cc:48
-  m->flat_height = 0.0;
-}
-
-// ------------------------------------------------------------------ gait generator
-namespace {
-struct Stride {
-  std::vector<double> times;
-  std::vector<unsigned> contacts;  // bit e set = ee e in contact
-};
-enum G { Stand = 0, Flight, Walk1, Walk2, Walk2E, Run2, Run2E, Run1, Run1E, Run3, Run3E, Hop1, Hop1E, Hop2, Hop3, Hop3E, Hop5, Hop5E };
-
-Stride DropTransition(Stride s) {  // GaitGenerator::RemoveTransition (gait_generator.cc:131-144)
-  double last = s.times.back();
-  s.times.pop_back();
-  s.times.back() += last;
-  s.contacts.pop_back();
-  return s;
-}
-// quadruped contact states, ee bits LF=1 RF=2 LH=4 RH=8 (quadruped_gait_generator.cc:39-74)
-constexpr unsigned II = 0, PI = 4, bI = 8, IP = 1, Ib = 2, Pb = 4 | 2, bP = 8 | 1, BI = 12, IB = 3, PP = 4 | 1, bb = 8 | 2,
-                   Bb = 12 | 2, BP = 12 | 1, bB = 8 | 3, PB = 4 | 3, BB = 15;
-Stride QuadStride(int g) {  // quadruped_gait_generator.cc:89-366
-  switch (g) {
-    case Stand: return {{0.3}, {BB}};
-    case Flight: return {{0.3}, {Bb}};
-    case Walk1: return {{0.3, 0.2, 0.3, 0.2, 0.3, 0.2, 0.3, 0.2}, {bB, BB, Bb, BB, PB, BB, BP, BB}};
-    case Walk2: return {{0.25, 0.13, 0.25, 0.13, 0.25, 0.13, 0.25, 0.13}, {bB, bb, Bb, Pb, PB, PP, BP, bP}};
-    case Walk2E: return DropTransition(QuadStride(Walk2));
-    case Run1: return {{0.3, 0.2, 0.3, 0.2}, {bP, BB, Pb, BB}};
-    case Run2: return {{0.4, 0.1, 0.4, 0.1}, {bP, II, Pb, II}};
-    case Run2E: return {{0.4}, {bP}};
-    case Run3: return {{0.3, 0.1, 0.3, 0.1}, {PP, II, bb, II}};
-    case Run3E: return {{0.3}, {PP}};
-    case Hop1: return {{0.3, 0.1, 0.3, 0.1}, {BI, II, IB, II}};
-    case Hop1E: return {{0.3}, {BI}};
-    case Hop2: return {{0.3, 0.4, 0.3}, {BB, II, BB}};
-    case Hop3: return {{0.2, 0.3, 0.2, 0.2, 0.2, 0.3, 0.2, 0.2}, {Bb, BI, BP, bP, bB, IB, PB, Pb}};
-    case Hop3E: return DropTransition(QuadStride(Hop3));
-    case Hop5: return {{0.1, 0.2, 0.1, 0.1, 0.2, 0.1}, {Bb, BB, IP, Bb, BB, IP}};
-  }
-  throw std::runtime_error("quadruped gait not implemented");
-}
-Stride BipedStride(int g) {  // biped_gait_generator.cc:64-226, bits L=1 R=2
-  const unsigned I = 0, P = 1, b = 2, B = 3;
-  switch (g) {
-    case Stand: return {{0.2}, {B}};
-    case Flight: return {{0.5}, {I}};
-    case Walk1: case Walk2: return {{0.3, 0.05, 0.3, 0.05}, {b, B, P, B}};
-    case Run1: case Run3: return {{0.15, 0.4, 0.15 + 0.15, 0.4, 0.15}, {b, I, P, I, b}};
-    case Hop1: return {{0.15, 0.5, 0.15}, {B, I, B}};
-    case Hop2: return {{0.15, 0.4, 0.15}, {b, I, b}};
-    case Hop3: return {{0.2, 0.2, 0.2}, {P, I, P}};
-    case Hop5: return {{0.2, 0.3, 0.2, 0.2}, {P, I, b, B}};
-  }
-  throw std::runtime_error("biped gait not implemented");
-}
-Stride MonoStride(int g) {  // monoped_gait_generator.cc:50-120
-  switch (g) {
-    case Stand: return {{0.5}, {1}};
-    case Flight: return {{0.5}, {0}};
-    case Hop1: return {{0.3, 0.3}, {1, 0}};
-    case Hop2: return {{0.2, 0.3}, {1, 0}};
-  }
-  throw std::runtime_error("monoped gait not implemented");
-}
-std::vector<int> ComboGaits(int n_ee, int combo) {
-  static const std::vector<int> quad[5] = {{Stand, Walk2, Walk2, Walk2, Walk2E, Stand},   // quadruped_gait_generator.cc:76-87
-                                           {Stand, Run2, Run2, Run2, Run2E, Stand},
-                                           {Stand, Run3, Run3, Run3, Run3E, Stand},
-                                           {Stand, Hop1, Hop1, Hop1, Hop1E, Stand},
-                                           {Stand, Hop3, Hop3, Hop3, Hop3E, Stand}};
-  static const std::vector<int> biped[5] = {{Stand, Walk1, Walk1, Walk1, Walk1, Stand},   // biped_gait_generator.cc:51-62
-                                            {Stand, Run1, Run1, Run1, Run1, Stand},
-                                            {Stand, Hop1, Hop1, Hop1, Stand},
-                                            {Stand, Hop1, Hop2, Hop2, Stand},
-                                            {Stand, Hop5, Hop5, Hop5, Stand}};
-  static const std::vector<int> mono[5] = {{Stand, Hop1, Hop1, Hop1, Hop1, Stand},        // monoped_gait_generator.cc:37-48
-                                           {Stand, Hop1, Hop1, Hop1, Stand},
-                                           {Stand, Hop1, Hop1, Hop1, Hop1, Stand},
-                                           {Stand, Hop2, Hop2, Hop2, Stand},
-                                           {Stand, Hop2, Hop2, Hop2, Hop2, Hop2, Stand}};
-  if (combo < 0 || combo > 4) throw std::runtime_error("combo must be 0..4");
-  if (n_ee == 1) return mono[combo];
-  if (n_ee == 2) return biped[combo];
-  if (n_ee == 4) return quad[combo];
-  throw std::runtime_error("no gait generator for this leg count");  // gait_generator.cc:43-52
-}
-}  // namespace
-
-void GaitCombo(int n_ee, int combo, double t_total, double swing_scale, twr_schedule* out) {
-  std::vector<double> times;
-  std::vector<unsigned> contacts;
-  for (int g : ComboGaits(n_ee, combo)) {  // SetGaits (gait_generator.cc:113-129)
-    Stride s = n_ee == 1 ? MonoStride(g) : n_ee == 2 ? BipedStride(g) : QuadStride(g);
-    times.insert(times.end(), s.times.begin(), s.times.end());
-    contacts.insert(contacts.end(), s.contacts.begin(), s.contacts.end());
-  }
-  const unsigned all = (1u << n_ee) - 1;
-  for (size_t i = 0; i < times.size(); ++i)
-    if (contacts[i] != all) times[i] *= swing_scale;  // candidate enumeration knob (1.0 = reference)
-  std::memset(out, 0, sizeof(*out));
-  out->n_ee = n_ee;
-  // GetPhaseDurations() (gait_generator.cc:76-105)
-  std::vector<std::vector<double>> foot(n_ee);
-  std::vector<double> acc(n_ee, 0.0);
-  for (size_t ph = 0; ph + 1 < contacts.size(); ++ph)
-    for (int e = 0; e < n_ee; ++e) {
-      acc[e] += times[ph];
-      bool cur = (contacts[ph] >> e) & 1, nxt = (contacts[ph + 1] >> e) & 1;
-      if (cur != nxt) {
-        foot[e].push_back(acc[e]);
-        acc[e] = 0.0;
-      }
-    }
-  for (int e = 0; e < n_ee; ++e) foot[e].push_back(acc[e] + times.back());
-  for (int e = 0; e < n_ee; ++e) {
-    if (foot[e].size() > TWR_MAX_PHASES) throw std::runtime_error("too many phases");
-    // GetNormalizedPhaseDurations + GetPhaseDurations(T, ee) (gait_generator.cc:54-74)
-    double total = std::accumulate(foot[e].begin(), foot[e].end(), 0.0);
-    out->n_phases[e] = (int)foot[e].size();
-    out->in_contact_at_start[e] = (contacts.front() >> e) & 1;  // IsInContactAtStart :107-111
-    for (size_t i = 0; i < foot[e].size(); ++i) out->phase_durations[e][i] = (foot[e][i] / total) * t_total;
-  }
-}
-
-LayoutShare ShareLayoutTables(const std::vector<const Structure*>& structs) {
-  struct Seen {
-    const char* bytes;
-    uint32_t n;
-    LayoutShare::Ref ref;
-  };
-  auto hash = [](const char* p, size_t n) {   // FNV-1a over 8-byte words (a bucket key only: equality is decided by memcmp)
-    uint64_t h = 1469598103934665603ull;
-    size_t i = 0;
-    for (; i + 8 <= n; i += 8) {
-      uint64_t w;
-      std::memcpy(&w, p + i, 8);
-      h = (h ^ w) * 1099511628211ull;
-      h ^= h >> 29;
-    }
-    for (; i < n; ++i) h = (h ^ (unsigned char)p[i]) * 1099511628211ull;
-    return h;
-  };
-  LayoutShare out;
-  out.of.resize(structs.size());
-  std::unordered_map<uint64_t, std::vector<Seen>> by_hash;
-  for (size_t i = 0; i < structs.size(); ++i) {
-    const Structure& S = *structs[i];
-    for (const Structure::TableRef& tr : S.dyn_layout_tables) {
-      if ((size_t)tr.off + tr.bytes > S.blob.size()) throw std::runtime_error("layout table outside its blob");
-      const char* src = S.blob.data() + tr.off;
-      std::vector<Seen>& bucket = by_hash[hash(src, tr.bytes) ^ tr.bytes];
-      LayoutShare::Ref ref{(int)i, tr.off};
-      bool found = false;
-      for (const Seen& sn : bucket)
-        if (sn.n == tr.bytes && std::memcmp(sn.bytes, src, tr.bytes) == 0) {
-          ref = sn.ref;
-          found = true;
-          break;
-        }
-      if (!found) {
-        bucket.push_back({src, tr.bytes, ref});
-        out.bytes_distinct += tr.bytes;
-      }
-      out.bytes_built += tr.bytes;
-      out.of[i].push_back(ref);
-    }
-  }
-  return out;
-}
-
-std::vector<size_t> BlobOffsets(const std::vector<const Structure*>& structs) {
-  std::vector<size_t> off(structs.size() + 1, 0);
-  for (size_t i = 0; i < structs.size(); ++i) off[i + 1] = off[i] + (structs[i]->blob.size() + 255) / 256 * 256;
-  return off;
-}
-
-namespace {
-// XCD-aware order.  Workgroups are dealt round-robin over the 8 XCDs and the persistent grids are multiples of 8, so list
-// position j runs on XCD j % 8 (eval_fused_kernel's slice mapping relies on it, kernels.hip).  Interleaving the problems in
-// groups of 8 puts all items of one problem on ONE XCD (same L2): its x is fetched from HBM once per kernel instead of once
-// per XCD.  (Speed only; ragged item counts merely loosen the alignment.)  first: first item of every problem (+ end).
-template <class W>
-void Interleave(std::vector<W>& items, const std::vector<int>& first) {
-  const std::vector<W> src = items;
-  const int n = (int)first.size() - 1;
-  size_t out = 0;
-  for (int p0 = 0; p0 < n; p0 += 8) {
-    const int np = std::min(8, n - p0);
-    for (int s = 0;; ++s) {
-      bool any = false;
-      for (int k = 0; k < np; ++k)
-        if (first[p0 + k] + s < first[p0 + k + 1]) {
-          items[out++] = src[first[p0 + k] + s];
-          any = true;
-        }
-      if (!any) break;
-    }
-  }
-}
-}  // namespace
-
-void BatchPlan::PlaceRecords(uint64_t base) {
-  for (auto& lw : lists.ploc) {
-    if (lw.recs) lw.recs += base - 1;
-    if (lw.dyn_loc) lw.dyn_loc += base - 1;
-  }
-  for (auto& rw : lists.prom) rw.recs += base;
-  for (auto& pw : lists.pdyn) pw.loc += base;
-}
-
-BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem,
-                    const std::vector<uint64_t>& blob_at, int n_cu, int64_t cache_bytes, int force_chunk) {
-  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
-  BatchPlan b;
-  BatchPlan::Lists& L = b.lists;
-  // Layout tables of dyn_kernel (device_tables.h) are stored once per distinct CONTENT: a structure whose table is
-  // byte-identical to one of an earlier structure of the batch reads that one (its own copy stays in the arena, unread).
-  // Candidates of a sweep that differ in the total time only share all of them, and an evaluation then reads 24 B per
-  // time node + 16 B per polynomial of such a candidate instead of ~35 KB.  The model constants (DevStruct header) are
-  // taken from the first structure of the batch that has the same ones.
-  std::vector<std::unordered_map<uint32_t, uint64_t>> layout_at(n_structs);   // [structure][blob offset of the table] -> device address
-  std::vector<uint64_t> model_hdr(n_structs);
-  const LayoutShare share = ShareLayoutTables(structs);
-  b.dyn_layout_bytes = share.bytes_built;
-  b.dyn_layout_distinct_bytes = share.bytes_distinct;
-  for (int i = 0; i < n_structs; ++i) {
-    const auto& tabs = structs[i]->dyn_layout_tables;
-    for (size_t t = 0; t < tabs.size(); ++t) layout_at[i][tabs[t].off] = blob_at[share.of[i][t].owner] + share.of[i][t].off;
-    const DevStruct* H = reinterpret_cast<const DevStruct*>(structs[i]->blob.data());
-    model_hdr[i] = blob_at[i];
-    for (int q = 0; q < i; ++q) {
-      const DevStruct* Q = reinterpret_cast<const DevStruct*>(structs[q]->blob.data());
-      if (model_hdr[q] == blob_at[q] && Q->mass == H->mass && Q->gravity == H->gravity && std::memcmp(Q->Ib, H->Ib, sizeof(H->Ib)) == 0) {
-        model_hdr[i] = model_hdr[q];
-        break;
-      }
-    }
-    if (structs[i]->dyn_staged_max > 128) b.dyn_map_chunks = 4;
-  }
-  b.x_off.assign(n_problems + 1, 0);
-  b.g_off.assign(n_problems + 1, 0);
-  b.j_off.assign(n_problems + 1, 0);
-  std::vector<int> flat_group_p;             // the problem of every group of four flat items
-  bool flat_ok = true;
-  std::vector<int> dyn_first, rom_first, pdyn_first;   // first work item of every problem (+ end; pdyn: optimised timings only)
-  // (families that are switched off -- twr_params.constraint_sets -- simply have no work items; problems with
-  // optimised timings get PDynWork / LocWork / RomPhaseWork items instead of DynWork / RomWork)
-  for (int p = 0; p < n_problems; ++p) {
-    const int si = struct_of_problem[p];
-    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
-    const Structure& S = *structs[si];
-    const DevStruct* H = reinterpret_cast<const DevStruct*>(S.blob.data());
-    const uint64_t blob = blob_at[si];
-    const SampleTables* st = reinterpret_cast<const SampleTables*>(S.blob.data() + H->o_sample);
-    b.blob_of_problem.push_back(blob);
-    b.t_total.push_back(st->t_total);
-    b.sample_ok.push_back(st->n_base >= 0);
-    b.x_off[p + 1] = b.x_off[p] + S.n_vars;
-    b.g_off[p + 1] = b.g_off[p] + S.n_rows;
-    b.j_off[p + 1] = b.j_off[p] + S.nnz;
-    dyn_first.push_back((int)L.dyn.size());
-    rom_first.push_back((int)L.rom.size());
-    const SetInfo* dsp = S.FindSet("dynamic");
-    const SetInfo ds = dsp ? *dsp : SetInfo();
-    for (const auto& sl : S.dyn_slices) {   // fixed timings only (empty otherwise)
-      DynWork w;
-      std::memset(&w, 0, sizeof(w));
-      const auto& lay = layout_at[si];
-      w.nodes_t = blob + S.off_dyn_nodes_t + sizeof(DynNodeT) * (size_t)sl.k0;
-      w.nodes_l = lay.at(S.off_dyn_nodes_l) + sizeof(DynNodeL) * (size_t)sl.k0;
-      w.sel = lay.at(S.off_dyn_sel) + sizeof(DynSel) * (size_t)sl.k0 * 4;
-      w.tile = lay.at(S.off_dyn_tile);   // (records are addressed through DynSel::tile)
-      w.poly_t = blob + S.off_dyn_poly_t + sizeof(DynPolyT) * (size_t)sl.poly0;
-      w.poly_l = lay.at(S.off_dyn_poly_l) + sizeof(DynPolyL) * (size_t)sl.poly0;
-      w.map = lay.at(b.dyn_map_chunks == 2 ? sl.map2 : sl.map);
-      w.hdr = model_hdr[si];
-      w.x_off = b.x_off[p];
-      w.g_off = b.g_off[p] + ds.offset + 6 * sl.k0;
-      w.j_off = b.j_off[p] + S.row_ptr[ds.offset + 6 * sl.k0];
-      w.cnt = sl.cnt;
-      w.nvals = sl.nvals;
-      L.dyn.push_back(w);
-    }
-    for (int e = 0; e < (int)S.rom_slices.size(); ++e) {   // fixed timings only (empty otherwise)
-      if (S.rom_slices[e].empty()) continue;
-      const SetInfo& rs = *S.FindSet("rangeofmotion-" + std::to_string(e));
-      for (const auto& sl : S.rom_slices[e]) {
-        RomWork w;
-        std::memset(&w, 0, sizeof(w));
-        w.nodes = blob + S.off_rom_nodes + sizeof(RomNode) * (size_t)sl.k0;
-        w.segs = blob + sl.segs;
-        w.x_off = b.x_off[p];
-        w.g_off = b.g_off[p] + rs.offset + 3 * sl.k0;
-        w.j_off = b.j_off[p] + S.row_ptr[rs.offset + 3 * sl.k0];
-        w.off_lin = S.off_base_lin;
-        w.off_ang = S.off_base_ang;
-        w.cnt = sl.cnt;
-        w.nvals = sl.nvals;
-        w.ee = e;
-        b.rom_max_vals = std::max(b.rom_max_vals, w.nvals);
-        L.rom.push_back(w);
-      }
-    }
-    if (S.timings) {
-      const int Kd = (int)S.grid_dyn.size();
-      const size_t loc_off = b.records_bytes;   // DynLoc[4 * Kd] of this problem, then its RomRec arrays
-      const PhaseTables& pt = S.phase_tables;
-      if (dsp) {
-        // dyn_phase_kernel: a pass = the time nodes whose expanded rows fit the LDS image (four at sixteen lanes each,
-        // fewer when a node has more than 5120 values: the image then takes the whole 160 KB of a CU)
-        b.records_bytes += sizeof(DynLoc) * 4 * (size_t)Kd;
-        const int nv = pt.node_vals;
-        const int run = std::max(1, std::min(4, (160 * 128) / nv));
-        b.pdyn_img_cap = std::max(b.pdyn_img_cap, run * nv);
-        pdyn_first.push_back((int)L.pdyn.size());
-        for (int k0 = 0; k0 < Kd; k0 += run) {
-          PDynWork pw;
-          std::memset(&pw, 0, sizeof(pw));
-          pw.hdr = blob;
-          pw.loc = loc_off + sizeof(DynLoc) * (size_t)k0;
-          pw.loc_stride = (int32_t)(sizeof(DynLoc) * (size_t)Kd);
-          pw.shared = blob + pt.o_dyn_shared + sizeof(DynShared) * (size_t)k0;
-          pw.mput = blob + pt.o_mput;
-          pw.fput = blob + pt.o_fput;
-          pw.ee = blob + H->o_phase + offsetof(PhaseTables, ee);
-          pw.x_off = b.x_off[p];
-          pw.g_off = b.g_off[p] + dsp->offset + 6 * k0;
-          pw.j_off = b.j_off[p] + dsp->nnz_offset + (int64_t)k0 * nv;
-          pw.cnt = std::min(run, Kd - k0);
-          pw.node_vals = nv;
-          pw.off_lin = S.off_base_lin;
-          pw.off_ang = S.off_base_ang;
-          pw.n_ee = S.n_ee;
-          pw.n_mput = pt.n_mput;
-          pw.n_fput = pt.n_fput;
-          for (int q = 0; q < 5; ++q) pw.row_off[q] = pt.dyn_row_off[q];
-          L.pdyn.push_back(pw);
-        }
-      }
-      for (int e = 0; e < S.n_ee; ++e) {
-        const SetInfo* rs = S.FindSet("rangeofmotion-" + std::to_string(e));
-        if (!rs && !dsp) continue;
-        LocWork lw;
-        std::memset(&lw, 0, sizeof(lw));
-        lw.blob = blob;
-        lw.recs = rs ? b.records_bytes + 1 : 0;   // (+1: see BatchPlan::records_bytes)
-        lw.dyn_loc = dsp ? loc_off + sizeof(DynLoc) * (size_t)Kd * (size_t)e + 1 : 0;
-        lw.x_off = b.x_off[p];
-        lw.ee = e;
-        L.ploc.push_back(lw);
-        if (!rs) continue;
-        const int K = (int)S.grid_rom.size(), nv = pt.rom_node_vals[e];
-        const int run_max = std::max(1, std::min(16, (160 * 128) / nv));   // time nodes per pass (four lanes each)
-        const int n_pass = (K + run_max - 1) / run_max;
-        const int run = (K + n_pass - 1) / n_pass;                  // balanced: no short tail pass (it pays the full copy-out)
-        b.prom_img_cap = std::max(b.prom_img_cap, run * nv);
-        for (int k0 = 0; k0 < K; k0 += run) {
-          RomPhaseWork rw;
-          rw.recs = b.records_bytes + sizeof(RomRec) * (size_t)k0;
-          rw.x_off = b.x_off[p];
-          rw.g_off = b.g_off[p] + rs->offset + 3 * k0;
-          rw.j_off = b.j_off[p] + rs->nnz_offset + (int64_t)k0 * nv;
-          rw.off_lin = S.off_base_lin;
-          rw.off_ang = S.off_base_ang;
-          rw.cnt = std::min(run, K - k0);
-          rw.msize = pt.msize[e];
-          rw.ns = S.schedule.n_phases[e] - 1;
-          rw.node_vals = nv;
-          L.prom.push_back(rw);
-        }
-        b.records_bytes += sizeof(RomRec) * (size_t)K;
-      }
-    }
-    // values-only work items (device_tables.h FlatWork): 64 time nodes of the dynamic / range-of-motion grid each
-    if (S.timings) flat_ok = false;
-    if (S.off_flat_polys) {
-      auto items = [&](uint32_t off_nodes, const std::vector<Structure::FlatItem>& list, bool dynamic) {
-        for (const auto& it : list) {
-          FlatWork fw;
-          std::memset(&fw, 0, sizeof(fw));
-          fw.nodes = blob + off_nodes + sizeof(FlatNode) * (size_t)it.k0;
-          fw.polys = blob + S.off_flat_polys;
-          fw.x_off = b.x_off[p];
-          fw.g_off = b.g_off[p];
-          fw.k0 = it.k0;
-          fw.cnt = it.cnt;
-          fw.start[0] = it.start[0];
-          fw.start[1] = it.start[1];
-          fw.count = it.count;
-          fw.n_x = S.n_vars;
-          fw.n_ee = S.n_ee;
-          fw.off_lin = S.off_base_lin;
-          fw.off_ang = S.off_base_ang;
-          for (int e = 0; e < kMaxEE; ++e) fw.row_rom[e] = S.flat_row_rom[e];
-          fw.dynamic = dynamic ? 1 : 0;
-          fw.gather = it.gather ? 1 : 0;
-          if (dynamic) {
-            fw.row_dyn = S.flat_row_dyn;
-            fw.with_rom = S.flat_with_rom ? 1 : 0;
-            fw.mass = H->mass;
-            fw.gravity = H->gravity;
-            for (int i = 0; i < 6; ++i) fw.Ib[i] = H->Ib[i];
-          }
-          L.flat.push_back(fw);
-        }
-      };
-      b.flat_max_x = std::max(b.flat_max_x, S.n_vars);
-      items(S.off_flat_dyn, S.flat_items_dyn, true);
-      items(S.off_flat_rom, S.flat_items_rom, false);
-      while (L.flat.size() % 4 != 0) {   // whole groups: empty items that still carry the problem's x (the group copies it
-        FlatWork fw;                     // to LDS with all its threads)
-        std::memset(&fw, 0, sizeof(fw));
-        fw.x_off = b.x_off[p];
-        fw.n_x = S.n_vars;
-        L.flat.push_back(fw);
-      }
-      flat_group_p.resize(L.flat.size() / 4, p);
-    } else if (S.FindSet("rangeofmotion-0") || dsp) {
-      flat_ok = false;
-    }
-    NodeWork nw;
-    nw.blob = blob;
-    nw.x_off = b.x_off[p];
-    nw.g_off = b.g_off[p];
-    nw.j_off = b.j_off[p];
-    L.node.push_back(nw);
-  }
-  // one entry past the end carries the totals: a kernel reads a problem's row count as work[p + 1].g_off - work[p].g_off
-  // from the work list alone (score_kernel requests g before the structure's header has arrived)
-  L.node.push_back(NodeWork{0, b.x_off[n_problems], b.g_off[n_problems], b.j_off[n_problems]});
-  dyn_first.push_back((int)L.dyn.size());
-  rom_first.push_back((int)L.rom.size());
-  pdyn_first.push_back((int)L.pdyn.size());
-  Interleave(L.dyn, dyn_first);
-  Interleave(L.rom, rom_first);
-  // Uniform dyn list: one structure with fixed timings for every problem -- in the flagship batch and in its real use, many
-  // x for one NLP -- so problem p's slice of a kind is problem 0's with x, g and jac moved on by p strides.  (By structure
-  // INDEX: two equal structures are two tables in the arena, and a batch of them takes the general kernel.)  The interleaved
-  // order puts problem 0's slices min(8, n) positions apart.
-  {
-    bool one = n_problems > 0;
-    for (int si : struct_of_problem) one = one && si == struct_of_problem[0];
-    if (one) {
-      const Structure& S = *structs[struct_of_problem[0]];
-      const int s = (int)S.dyn_slices.size();
-      if (!S.timings && s > 0 && L.dyn.size() == (size_t)s * (size_t)n_problems)
-        b.dyn_uniform = DynUniform{s, 0, std::min(8, n_problems), n_problems, S.n_vars, S.n_rows, S.nnz, 0};
-    }
-  }
-  Interleave(L.pdyn, pdyn_first);
-  // Store policy of the copy-out (kernels.hip copy_out_fixed): non-temporal when the batch is SWEEP-LIKE -- fewer than four
-  // problems per structure on average, so every evaluation re-reads tables (and x) that only that problem uses -- AND one
-  // evaluation writes more than the device's memory-side cache holds (256 MB on an MI355X; by architecture name, structure.h), so that plain stores would flush those
-  // tables out of it between two evaluations.  Measured (one box, no per-kernel events): the C5 sweep at 512 /
-  // 1024 candidates 116-118 / 223-224 -> 99 / 209-211 us per step; at 256 candidates (220 MB of output, absorbed by the
-  // Infinity Cache as it is) 52 -> 55 us, and 8192 problems of ONE structure lose 15 % in rom_kernel -- hence the two conditions.
-  std::vector<char> used(n_structs, 0);
-  int n_used = 0;
-  for (int si : struct_of_problem)
-    if (!used[si]) {
-      used[si] = 1;
-      ++n_used;
-    }
-  b.stream_nt = StreamNonTemporal(n_used, n_problems, 8 * (b.g_off[n_problems] + b.j_off[n_problems]), cache_bytes);
-  b.node_families = 2;
-  for (const Structure* S : structs)
-    if (S->params.constraint_sets & ~(TWR_SET_TERRAIN | TWR_SET_DYNAMIC | TWR_SET_ROM | TWR_SET_FORCE)) b.node_families = 4;
-  if (!flat_ok) {
-    L.flat.clear();
-  } else {
-    // One problem, one XCD: workgroup r of the launch runs on XCD r modulo 8 and takes group r.  The groups of problem p go to
-    // workgroups = p modulo 8: its x comes from HBM once and from that XCD's L2 for its other groups.
-    std::vector<size_t> queue[8];   // queue c: the groups that go to the list positions = c modulo 8
-    for (size_t i = 0; i < flat_group_p.size(); ++i) queue[flat_group_p[i] % 8].push_back(i);
-    std::vector<FlatWork> out;
-    out.reserve(L.flat.size());
-    std::vector<size_t> order;      // the groups in list order
-    order.reserve(flat_group_p.size());
-    auto emit = [&](size_t group) {
-      out.insert(out.end(), L.flat.begin() + 4 * group, L.flat.begin() + 4 * group + 4);
-      order.push_back(group);
-    };
-    size_t depth = 0, k = 0;
-    for (const auto& q : queue) depth = std::max(depth, q.size());
-    for (; k < depth; ++k) {   // whole rounds of eight; a round in which a queue has run dry ends the interleaving
-      bool whole = true;
-      for (const auto& q : queue) whole = whole && k < q.size();
-      if (!whole) break;
-      for (const auto& q : queue) emit(q[k]);
-    }
-    for (const auto& q : queue)
-      for (size_t i = k; i < q.size(); ++i) emit(q[i]);
-    // candidate scoring without g: where every group went, then per problem its partial records in a fixed order (its groups
-    // in the order the structure lists its items, so the fold's sums do not depend on where the problem sits in the batch)
-    std::vector<int32_t> pos(flat_group_p.size());
-    for (size_t i = 0; i < order.size(); ++i) pos[order[i]] = (int32_t)i;
-    const int32_t n_groups = (int32_t)flat_group_p.size();
-    L.score_blob.resize(order.size());
-    for (size_t i = 0; i < order.size(); ++i) L.score_blob[i] = b.blob_of_problem[flat_group_p[order[i]]];
-    L.score_first.assign(1, 0);
-    size_t i = 0;
-    for (int p = 0; p < n_problems; ++p) {
-      for (; i < flat_group_p.size() && flat_group_p[i] == p; ++i)
-        for (int w = 0; w < kFlatGroup; ++w)
-          if (L.flat[kFlatGroup * i + w].cnt > 0) L.score_slot.push_back(kFlatGroup * pos[i] + w);   // (L.flat: still in list order)
-      for (int w = 0; w < b.node_families; ++w) L.score_slot.push_back(kFlatGroup * (n_groups + p) + w);
-      L.score_first.push_back((int32_t)L.score_slot.size());
-    }
-    b.score_fused = true;
-    b.score_slab = (int64_t)kFlatGroup * (n_groups + n_problems);
-    L.flat.swap(out);
-  }
-  // Large batches whose node-based sets are terrain / force / splineacc / swing only: per-family chunk lists for the
-  // persistent node_chunk_kernel (baseMotion and totalduration rows, and small batches -- where the fused launch or the
-  // one-workgroup-per-problem kernel is as good -- stay with node_kernel).
-  // (hot-path batches -- terrain and force rows only -- are faster on node_kernel2: 0.041 vs 0.047 ms per 8192 C3 problems)
-  // (from eight problems per CU on -- 2048 on the 256 CUs of an MI355X, where the cut-over was measured: below that the
-  // one-workgroup-per-problem kernel has enough waves in flight and no persistent loop to fill)
-  bool eligible = n_problems >= 8 * n_cu && b.node_families == 4;
-  for (const Structure* S : structs)
-    if (S->params.constraint_sets & (TWR_SET_BASE_ROM | TWR_SET_TOTAL_TIME)) eligible = false;
-  for (int p = 0; p < n_problems && eligible; ++p) {
-    const DevStruct* H = reinterpret_cast<const DevStruct*>(structs[struct_of_problem[p]]->blob.data());
-    auto add = [&](int f, int count, uint32_t table_off, size_t rec_bytes, int row0, int rows_per, int nnz0, int vals_per) {
-      const int chunk = f == 1 ? force_chunk : 64;
-      for (int i0 = 0; i0 < count; i0 += chunk) {
-        FamWork w;
-        std::memset(&w, 0, sizeof(w));
-        w.blob = b.blob_of_problem[p];
-        w.table = w.blob + table_off + (f == 2 ? 0 : rec_bytes * (size_t)i0);
-        w.x_off = b.x_off[p];
-        w.g_off = b.g_off[p] + row0 + (int64_t)rows_per * i0;
-        w.j_off = b.j_off[p] + nnz0 + (int64_t)vals_per * i0;
-        w.cnt = std::min(chunk, count - i0);
-        w.i0 = f == 2 ? i0 : 0;
-        w.aux0 = 3 * H->n_junctions;
-        w.aux1 = H->off_base_ang;
-        w.inv_t_swing = H->inv_t_swing;
-        L.fam[f].push_back(w);
-      }
-    };
-    add(0, H->n_terrain_rows, H->o_terrain_rows, sizeof(TerrainRow), H->row_terrain, 1, H->nnz_terrain, 3);
-    add(1, H->n_force_nodes, H->o_force_nodes, sizeof(ForceNode), H->row_force, 5, H->nnz_force, 25);
-    add(2, 6 * H->n_junctions, H->o_acc, sizeof(AccJunction), H->row_acc, 1, H->nnz_acc, 6);
-    add(3, H->n_swing_nodes, H->o_swing_nodes, sizeof(SwingNode), H->row_swing, 4, H->nnz_swing, 12);
-  }
-  return b;
-}
-
-// The dyn / rom grids are persistent: as many workgroups as are resident at once.  Residency is LDS bound; the occupancy API
-// over-reports it for the dynamic kernel (measured: 7 x 22.5 KB resident, an 8th starts a second round), so the per-CU
-// counts are fixed (LaunchTuning) rather than queried.  (Running dyn and rom concurrently on two streams was measured and is
-// slower than back to back.)
-EvalPlan PlanEval(const EvalShape& s) {
-  EvalPlan plan;
-  const LaunchTuning& t = s.tuning;
-  auto add = [&](Launch k, int store, int nit, int xc, int items, int grid, int block, int lds = 0) -> LaunchStep& {
-    LaunchStep& p = plan.step[plan.n++];
-    p.kernel = k;
-    p.store = store;
-    p.nit = nit;
-    p.xc = xc;
-    p.grid = std::min(items, grid);
-    p.block = block;
-    p.lds = lds;
-    return p;
-  };
-  auto event = [&](int i) {
-    if (s.events) plan.step[plan.n++].arg[0] = i;
-  };
-  const bool wg = s.flags & 1, wj = s.flags & 2;
-  const int store = wg && wj ? kStoreGJ : wj ? kStoreJ : kStoreG;   // non-temporal stores only go with the Jacobian
-  const int store_nt = !(s.stream_nt && wj) ? store : wg ? kStoreGJNT : kStoreJNT;
-  const int xc = s.dyn_map_chunks == 2 ? 2 : 4;
-  const int n_chunks = s.fam[0] + s.fam[1] + s.fam[2] + s.fam[3];
-  auto nodes = [&]() {   // the node-based sets (terrain-*, force-*, splineacc-*, swing-*, ...): last launch of every path
-    if (n_chunks > 0) {
-      // persistent waves per CU for ALL families together, shared out by their chunk counts (by count, not by bytes: an iteration
-      // costs about the same whatever the family -- weighting the force chunks 1.5 x ... 3 x was 4-15 % slower)
-      const int res = t.node_bpc * s.n_cu;
-      int gf[4], sum = 0;
-      for (int f = 0; f < 4; ++f) {
-        gf[f] = s.fam[f] == 0 ? 0 : std::min(s.fam[f], std::max(1, (int)((long long)res * s.fam[f] / n_chunks)));
-        sum += gf[f];
-      }
-      LaunchStep& p = add(Launch::kChunk, store, 0, 0, sum, sum, 64);
-      std::copy(gf, gf + 4, p.arg);
-    } else if (s.node > 0) {
-      add(s.node_families == 2 ? Launch::kNode2 : Launch::kNode, store, 0, 0, s.node, s.node, s.node_families == 2 ? 128 : 256);
-    }
-  };
-  // Candidate scores (twr_batch_eval_scores): with score_fused the values-only launch in its scoring instantiation
-  // (eval_scores_kernel: every wave reduces its rows to a partial record, the node-based sets always by the launch's own
-  // node waves -- node_chunk_kernel writes g) and the fold of the partial records into the score rows; otherwise exactly
-  // twr_batch_eval(TWR_EVAL_VALUES) and twr_batch_score.  Then twr_batch_best's launch if asked for.  No per-kernel events.
-  if (s.flags & kEvalScores) {
-    if (s.score_fused) {
-      const int nx = (s.flat_max_x + 64 * kFlatGroup - 1) / (64 * kFlatGroup);
-      const int n_groups = s.flat / kFlatGroup, items = n_groups + s.node;
-      LaunchStep& p = add(Launch::kScores, kStoreG, 0, nx <= 3 ? 3 : nx <= 5 ? 5 : 8, items, items, 64 * kFlatGroup, flat_lds_bytes(s.flat_max_x));
-      p.arg[0] = n_groups;
-      p.arg[1] = s.node_families;
-      p.arg[2] = flat_x_bytes(s.flat_max_x);
-      const int fold = (kFoldThreads * s.node + 255) / 256;
-      add(Launch::kFold, kStoreG, 0, 0, fold, fold, 256).arg[0] = s.node;
-    } else {
-      EvalShape v = s;
-      v.flags = 1;   // TWR_EVAL_VALUES
-      v.events = false;
-      plan = PlanEval(v);
-      add(Launch::kScoreG, kStoreG, 0, 0, s.node, s.node, 256).arg[0] = s.node;
-    }
-    if (s.flags & kEvalBest) {   // (launch_best's grid: four candidates per thread, at most 256 workgroups)
-      const int blocks = std::max(1, std::min((s.node + 1023) / 1024, 256));
-      add(Launch::kBest, kStoreG, 0, 0, blocks, blocks, 256).arg[0] = s.node;
-    }
-    return plan;
-  }
-  // Values only (no Jacobian), every problem with fixed timings and at most kFlatXCap variables: "dynamic" and "rangeofmotion-*"
-  // with one lane per time node (flat items), the node-based sets -- one launch (eval_values_kernel); with per-kernel events three.
-  if (wg && !wj && s.flat > 0 && s.pdyn == 0 && s.prom == 0 && s.ploc == 0) {
-    const int nf = !s.events && n_chunks == 0 ? s.node_families : 0;   // (large batches: the chunk kernel takes the node sets;
-                                                                        // with per-kernel events they are a launch of their own)
-    const int nx = (s.flat_max_x + 64 * kFlatGroup - 1) / (64 * kFlatGroup);
-    static_assert(kFlatXCap <= 8 * 64 * kFlatGroup, "largest instantiation of the values-only kernel");
-    const int n_groups = s.flat / kFlatGroup, items = n_groups + (nf > 0 ? s.node : 0);
-    event(0);
-    LaunchStep& p = add(Launch::kValues, kStoreG, 0, nx <= 3 ? 3 : nx <= 5 ? 5 : 8, items, items, 64 * kFlatGroup, flat_lds_bytes(s.flat_max_x));
-    p.arg[0] = n_groups;
-    p.arg[1] = nf;
-    p.arg[2] = flat_x_bytes(s.flat_max_x);
-    event(1);   // (the two flat families are one launch: the second interval is empty)
-    event(2);
-    if (nf == 0) nodes();
-    event(3);
-    return plan;
-  }
-  const int cap = t.rom_bpc * s.n_cu;
-  // The fused launch (the dyn, rom and node roles as blocks of one launch) is used while the rom role needs at most TWENTY
-  // rounds of its residency (rom_bpc workgroups per CU x n_cu).  Round-3 re-tune on one box, ragged sweep, fused vs three
-  // launches: 320 / 400 / 512 candidates 75 / 98 / 126 vs 83 / 104 / 128 us per step, 768 / 1024: 187 / 250 vs 183 / 235;
-  // round 4: 512 candidates 115 vs 124, 768 / 1024 equal.  The 512 candidates of a two-GPU shard of the C5 sweep are ~8500
-  // rom slices (the enumeration is ragged: 16.6 slices per candidate), 8.3 rounds on the 256 CUs of an MI355X.  With
-  // non-temporal stores (sweep-like batches) the fused launch stays ahead for longer -- 768 / 896 / 1024 candidates of the
-  // C5 sweep (12.7 / 14.9 / 17 thousand rom slices): 160-165 / 179 / 210 us as three launches, 148 / 166 / 202 us fused --
-  // twenty rounds there (the enumeration ends at 1040 candidates; nothing larger was measured).  Round 5, with the roles
-  // always co-resident: batches that share one structure, plain stores, 640 / 1024 / 2048 problems 129.5 / 193.5 / 365 us as
-  // three launches, 120 / 188 / 376 us fused -- twenty rounds for both store policies.  The thresholds are in units of the
-  // device's residency, not constants of one chip.
-  const int fused_max = t.fused_max_rom > 0 ? t.fused_max_rom : 20 * cap;
-  if (!s.events && s.pdyn == 0 && s.prom == 0 && s.rom > 0 && s.dyn > 0 && s.rom <= fused_max) {
-    const int half_dyn = (s.dyn + 1) / 2;
-    int g_rom = std::min(s.rom, cap), g_dyn = std::min(half_dyn, cap);
-    // When the two persistent roles do not fit the CUs together, the blocks of the later role only start as the earlier
-    // ones retire, i.e. the roles run one after the other.  For up to 2560 rom slices (160 quadruped candidates of
-    // K = 200) it pays to give each role half of the residency instead, so that the latency-bound dyn waves and the
-    // store-bound rom waves overlap from the start (64 / 128 / 160 candidates: 18.7 / 30.1 / 35.2 -> 17.5 / 27.8 /
-    // 31.6 us per step; from 200 candidates on the extra rounds cost more than the overlap gains).
-    // (round 3: five eighths for rom up to 3200 slices -- 128 / 160 / 200 candidates 27.5 / 33.5 / 40.5 us against 27.7 / 33.9 /
-    // 44.0 us with the round-2 rule "half each up to 2560"; from 256 candidates on unsplit was as good or better THEN.)
-    // Round 5, re-measured with the round-4 kernels (split tables, nt stores; one box, ragged sweep, us per step unsplit ->
-    // split): 256 candidates 53.8 -> 47.2 (five eighths; 48.6 at four), 320: 69.3 -> 62.5 (four), 384: 81.7 -> 74.5, 512:
-    // 100.9 -> 92.6, 768: 155.8 -> 145.9, 1024: 206.0 -> 194.1; six eighths loses everywhere.  The two roles are ALWAYS
-    // co-resident now: the latency-bound dyn waves fill the holes of the store-bound rom stream.
-    const int split = t.fused_split > 0 ? t.fused_split : (8 * s.rom <= 34 * cap ? 5 : 4);   // (4352 slices on 256 CUs)
-    if (split < 8 && g_rom + g_dyn > cap) {   // split = eighths of the residency given to rom (8 = never split)
-      g_rom = std::min(g_rom, cap * split / 8);
-      g_dyn = std::min(g_dyn, cap - cap * split / 8);
-    }
-    if (t.fused_grom > 0) g_rom = std::min(t.fused_grom, s.rom);
-    if (t.fused_gdyn > 0) g_dyn = std::min(t.fused_gdyn, half_dyn);
-    if (g_dyn >= 8) g_dyn &= ~7;   // (the XCD-aware slice mapping of the dyn role, eval_fused_kernel)
-    const int need = (s.rom_max_vals + 1 + 2 + 127) / 128;   // copy-out length of the rom role (as for rom_kernel below)
-    const int grid = g_rom + g_dyn + 2 * s.node;
-    LaunchStep& p = add(Launch::kFused, store_nt, need <= 34 ? 34 : kRomNitMax, xc, grid, grid, 128);
-    p.arg[0] = g_rom;
-    p.arg[1] = g_dyn;
-    return plan;
-  }
-  event(0);
-  if (s.dyn > 0) {
-    LaunchStep& p = add(Launch::kDyn, store_nt, 0, xc, s.dyn, t.dyn_bpc * s.n_cu, 64);
-    // A uniform list (BatchPlan::dyn_uniform) goes to dyn_uniform_kernel, whose waves own one slice kind each and load its
-    // records once per launch, when the grid divides into kinds without idling the residency (DynUniformCols).
-    const int cols = DynUniformCols(s.dyn_uniform.s, s.dyn_uniform.n_problems, t.dyn_bpc * s.n_cu);
-    if (cols > 0 && s.dyn == s.dyn_uniform.s * s.dyn_uniform.n_problems) {
-      p.uni = s.dyn_uniform;
-      p.uni.cols = cols;
-      p.grid = 8 * p.uni.s * cols;
-    }
-  }
-  // optimised-timings problems: the pre-pass (segment lookup -> records), then the persistent kernels; their LDS per
-  // workgroup is the image of one pass, and their residency follows from it
-  if (s.ploc > 0) add(Launch::kLocate, store, 0, 0, s.ploc, s.ploc, kLocateThreads);
-  auto phase_bpc = [&](int lds, int most, int knob) { return knob > 0 ? knob : std::max(1, std::min(most, 160 * 1024 / lds)); };
-  if (s.pdyn > 0) {   // (at most one wave per SIMD: the kernel uses the AGPR half of the register file as well)
-    const int lds = 8 * ((s.pdyn_img_cap + 1) & ~1);
-    add(Launch::kDynPhase, store, s.pdyn_img_cap <= 40 * 128 ? 40 : 0, 0, s.pdyn, phase_bpc(lds, 4, t.pdyn_bpc) * s.n_cu, 64, lds);
-  }
-  event(1);
-  if (s.prom > 0) {
-    const int lds = 8 * ((s.prom_img_cap + 1) & ~1), img = s.prom_img_cap;
-    const int nit = img <= 24 * 128 ? 24 : img <= 32 * 128 ? 32 : img <= 40 * 128 ? 40 : 0;
-    add(Launch::kRomPhase, store, nit, 0, s.prom, phase_bpc(lds, 8, t.prom_bpc) * s.n_cu, 64, lds);
-  }
-  if (s.rom > 0) {
-    // NIT = store instructions of rom_kernel's copy-out: the smallest instantiation that covers the largest slice of the
-    // batch (+ parity shift, rounded up to whole store instructions).  The stores past the end of a slice are re-stores of its
-    // last pair -- no HBM traffic, but requests all the same: C3's balanced 50-node slices need 34, and 34 instead of 38 is
-    // worth 4 % of the kernel (A/B on one box: 0.925 -> 0.883 ms together with the balanced slices; five 40-node slices with
-    // 27 stores each: 0.965 ms -- large slices win).
-    const int need = (s.rom_max_vals + 1 + 2 + 127) / 128;
-    add(Launch::kRom, store_nt, need <= 26 ? 26 : need <= 30 ? 30 : need <= 34 ? 34 : kRomNitMax, 0, s.rom, cap, 64);
-  }
-  event(2);
-  nodes();
-  event(3);
-  return plan;
-}
-
-EvalCounts CountsOf(const BatchPlan& P) {
-  const BatchPlan::Lists& L = P.lists;
-  EvalCounts c;
-  c.dyn = (int)L.dyn.size(), c.rom = (int)L.rom.size(), c.node = std::max(0, (int)L.node.size() - 1), c.flat = (int)L.flat.size();
-  for (int f = 0; f < 4; ++f) c.fam[f] = (int)L.fam[f].size();
-  c.pdyn = (int)L.pdyn.size(), c.ploc = (int)L.ploc.size(), c.prom = (int)L.prom.size();
-  return c;
-}
-
-EvalShape MakeEvalShape(const BatchPlan& P, const EvalCounts& c, int n_cu, int flags, bool events, const LaunchTuning& tuning) {
-  const bool scoring = flags & kEvalScores;
-  EvalShape s;
-  s.n_cu = n_cu;
-  s.dyn = c.dyn, s.rom = c.rom, s.node = c.node, s.flat = c.flat, s.pdyn = c.pdyn, s.ploc = c.ploc, s.prom = c.prom;
-  for (int f = 0; f < 4; ++f) s.fam[f] = c.fam[f];
-  s.rom_max_vals = P.rom_max_vals, s.flat_max_x = P.flat_max_x, s.dyn_map_chunks = P.dyn_map_chunks, s.node_families = P.node_families;
-  s.pdyn_img_cap = P.pdyn_img_cap, s.prom_img_cap = P.prom_img_cap, s.stream_nt = P.stream_nt;
-  if (!scoring) s.dyn_uniform = P.dyn_uniform;
-  s.flags = scoring ? flags & (kEvalScores | kEvalBest) : flags & 3;
-  s.events = events && !scoring;
-  s.score_fused = scoring && P.score_fused;
-  s.tuning = tuning;
-  return s;
-}
-
-const char* StoreName(int store) {
-  switch (store) {
-    case kStoreG: return "G";
-    case kStoreJ: return "J";
-    case kStoreGJ: return "GJ";
-    case kStoreJNT: return "JNT";
-    case kStoreGJNT: return "GJNT";
-  }
-  return "?";
-}
-
-const char* KernelName(const LaunchStep& p) {
-  switch (p.kernel) {
-    case Launch::kEvent: return "";
-    case Launch::kDyn: return p.uni.s > 0 ? "dyn_uniform_kernel" : "dyn_kernel";
-    case Launch::kRom: return "rom_kernel";
-    case Launch::kFused: return "eval_fused_kernel";
-    case Launch::kLocate: return "phase_locate_kernel";
-    case Launch::kDynPhase: return "dyn_phase_kernel";
-    case Launch::kRomPhase: return "rom_phase_kernel";
-    case Launch::kNode: return "node_kernel";
-    case Launch::kNode2: return "node_kernel2";
-    case Launch::kChunk: return "node_chunk_kernel";
-    case Launch::kValues: return "eval_values_kernel";
-    case Launch::kScores: return "eval_scores_kernel";
-    case Launch::kFold: return "score_fold_kernel";
-    case Launch::kScoreG: return "score_kernel";
-    case Launch::kBest: return "best_kernel";
-  }
-  return "?";
-}
-
-std::string InstantiationName(const LaunchStep& p) {
-  const std::string k = KernelName(p), st = StoreName(p.store);
-  switch (p.kernel) {
-    case Launch::kDyn: return k + "<" + st + ",xc" + std::to_string(p.xc) + ">";
-    case Launch::kRom:
-    case Launch::kDynPhase:
-    case Launch::kRomPhase: return k + "<" + std::to_string(p.nit) + "," + st + ">";
-    case Launch::kFused: return k + "<" + std::to_string(p.nit) + ",xc" + std::to_string(p.xc) + "," + st + ">";
-    case Launch::kChunk: return k + "<" + st + ">";
-    case Launch::kValues:
-    case Launch::kScores: return k + "<" + std::to_string(p.xc) + ">";
-    default: return k;
-  }
-}
-
-// ---------------------------------------------------------------- products with the Jacobian values (jac_products.hip)
-namespace {
-void CheckPattern(const Structure& S) {
-  const int n = S.n_vars, m = S.n_rows;
-  if ((int)S.row_ptr.size() != m + 1 || (int)S.col_idx.size() != S.nnz || S.row_ptr[0] != 0 || S.row_ptr[m] != S.nnz)
-    throw std::runtime_error("CSR pattern does not match its sizes");
-  if (n > 65536) throw std::runtime_error("more than 65536 variables: column indices do not fit 16 bits");
-  for (int r = 0; r < m; ++r) {
-    if (S.row_ptr[r + 1] < S.row_ptr[r]) throw std::runtime_error("row_ptr descends");
-    for (int k = S.row_ptr[r]; k < S.row_ptr[r + 1]; ++k) {
-      const int c = S.col_idx[k];
-      if (c < 0 || c >= n) throw std::runtime_error("column index outside [0, n_vars)");
-      if (k > S.row_ptr[r] && c <= S.col_idx[k - 1])
-        throw std::runtime_error("row " + std::to_string(r) + ": column indices not strictly ascending (unsorted or duplicate entries)");
-    }
-  }
-}
-
-template <class T>
-uint64_t AppendTable(std::vector<char>& out, const T* data, size_t count) {
-  const size_t at = (out.size() + 15) / 16 * 16;
-  out.resize(at + count * sizeof(T));
-  if (count) std::memcpy(out.data() + at, data, count * sizeof(T));
-  return at;
-}
-
-uint64_t HashWords(uint64_t h, const void* data, size_t bytes) {   // FNV-1a over 8-byte words (a bucket key only)
-  const char* p = static_cast<const char*>(data);
-  size_t i = 0;
-  for (; i + 8 <= bytes; i += 8) {
-    uint64_t w;
-    std::memcpy(&w, p + i, 8);
-    h = (h ^ w) * 1099511628211ull;
-    h ^= h >> 29;
-  }
-  for (; i < bytes; ++i) h = (h ^ (unsigned char)p[i]) * 1099511628211ull;
-  return h;
-}
-
-struct JacTables {   // one distinct pattern: byte offsets into JacOpsPlan::tables, its blocks, partials per problem
-  uint64_t col = 0, row_ptr = 0, fold_ptr = 0, fold_slot = 0;
-  std::vector<std::pair<int, int>> rows;   // J v blocks [r0, r1)
-  struct TBlock {
-    int k0, k1, r_first, span, ncols;
-    uint64_t map;
-    int64_t slot;                          // first partial, relative to the problem's
-  };
-  std::vector<TBlock> tblocks;
-  int64_t slots = 0;
-};
-
-JacTables BuildJacTables(const Structure& S, JacOpsPlan& J) {
-  const int n = S.n_vars, m = S.n_rows, nnz = S.nnz;
-  JacTables P;
-  const std::vector<uint16_t> col(S.col_idx.begin(), S.col_idx.end());   // < 65536: CheckPattern
-  P.col = AppendTable(J.tables, col.data(), col.size());
-  P.row_ptr = AppendTable(J.tables, S.row_ptr.data(), S.row_ptr.size());
-  J.table_bytes_mul += 2 * (int64_t)nnz + 4 * (int64_t)(m + 1);
-  for (int r0 = 0; r0 < m;) {
-    int r1 = r0 + 1;
-    while (r1 < m && r1 - r0 < kJacMulRows && S.row_ptr[r1 + 1] - S.row_ptr[r0] <= kJacMulNnz) ++r1;
-    P.rows.push_back({r0, r1});
-    r0 = r1;
-  }
-  std::vector<int> row_of(nnz);
-  for (int r = 0; r < m; ++r) std::fill(row_of.begin() + S.row_ptr[r], row_of.begin() + S.row_ptr[r + 1], r);
-  std::vector<int> stamp(n, -1);
-  std::vector<std::vector<int32_t>> slots_of(n);   // the partials of every column, in block order
-  int64_t tbytes = 4 * (int64_t)(m + 1);
-  for (int k0 = 0; k0 < nnz;) {
-    const int b = (int)P.tblocks.size();
-    int k1 = k0, ncols = 0;
-    while (k1 < nnz && k1 - k0 < kJacTNnz && row_of[k1] - row_of[k0] < kJacTSpan) {
-      const int c = S.col_idx[k1];
-      if (stamp[c] != b) {
-        if (ncols == kJacTCols) break;
-        stamp[c] = b;
-        ++ncols;
-      }
-      ++k1;
-    }
-    std::vector<std::pair<int, int>> e;   // (column, entry - k0), sorted: the block's columns ascending, each in row order
-    for (int k = k0; k < k1; ++k) e.push_back({S.col_idx[k], k - k0});
-    std::sort(e.begin(), e.end());
-    std::vector<uint16_t> map(ncols + 1 + e.size());
-    int j = -1;
-    for (size_t i = 0; i < e.size(); ++i) {
-      if (i == 0 || e[i].first != e[i - 1].first) {
-        map[++j] = (uint16_t)i;
-        slots_of[e[i].first].push_back((int32_t)(P.slots + j));
-      }
-      map[ncols + 1 + i] = (uint16_t)e[i].second;
-    }
-    map[ncols] = (uint16_t)e.size();
-    const uint64_t at = AppendTable(J.tables, map.data(), map.size());
-    tbytes += 2 * (int64_t)map.size();
-    P.tblocks.push_back({k0, k1, row_of[k0], row_of[k1 - 1] - row_of[k0] + 1, ncols, at, P.slots});
-    P.slots += ncols;
-    k0 = k1;
-  }
-  std::vector<int32_t> fptr(n + 1, 0), fslot;
-  for (int c = 0; c < n; ++c) {
-    fslot.insert(fslot.end(), slots_of[c].begin(), slots_of[c].end());
-    fptr[c + 1] = (int32_t)fslot.size();
-  }
-  P.fold_ptr = AppendTable(J.tables, fptr.data(), fptr.size());
-  P.fold_slot = AppendTable(J.tables, fslot.data(), fslot.size());
-  J.table_bytes_tmul += tbytes + 4 * (int64_t)(fptr.size() + fslot.size());
-  return P;
-}
-}  // namespace
-
-CscPattern TransposePattern(const Structure& S) {
-  CheckPattern(S);
-  CscPattern t;
-  t.col_ptr.assign(S.n_vars + 1, 0);
-  for (int k = 0; k < S.nnz; ++k) ++t.col_ptr[S.col_idx[k] + 1];
-  for (int c = 0; c < S.n_vars; ++c) t.col_ptr[c + 1] += t.col_ptr[c];
-  t.row_idx.resize(S.nnz);
-  t.csr_pos.resize(S.nnz);
-  std::vector<int32_t> next(t.col_ptr.begin(), t.col_ptr.end() - 1);
-  for (int r = 0; r < S.n_rows; ++r)
-    for (int k = S.row_ptr[r]; k < S.row_ptr[r + 1]; ++k) {
-      const int q = next[S.col_idx[k]]++;
-      t.row_idx[q] = r;
-      t.csr_pos[q] = k;
-    }
-  return t;
-}
-
-void JacOpsPlan::Place(uint64_t base) {
-  for (auto& w : mul) w.col += base, w.row_ptr += base;
-  for (auto& w : tmul) w.map += base, w.row_ptr += base;
-  for (auto& w : fold) w.ptr += base, w.slot += base;
-}
-
-JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem) {
-  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
-  JacOpsPlan J;
-  std::vector<JacTables> pats;
-  std::vector<const Structure*> first;   // the first structure of every distinct pattern
-  std::unordered_map<uint64_t, std::vector<int>> by_hash;
-  J.pattern_of_struct.resize(n_structs);
-  for (int i = 0; i < n_structs; ++i) {
-    const Structure& S = *structs[i];
-    CheckPattern(S);
-    uint64_t h = HashWords(1469598103934665603ull ^ (uint64_t)S.n_vars, S.row_ptr.data(), S.row_ptr.size() * sizeof(int32_t));
-    h = HashWords(h, S.col_idx.data(), S.col_idx.size() * sizeof(int32_t));
-    std::vector<int>& bucket = by_hash[h];
-    int pid = -1;
-    for (int q : bucket)
-      if (first[q]->n_vars == S.n_vars && first[q]->row_ptr == S.row_ptr && first[q]->col_idx == S.col_idx) pid = q;
-    if (pid < 0) {
-      pid = (int)pats.size();
-      bucket.push_back(pid);
-      first.push_back(&S);
-      pats.push_back(BuildJacTables(S, J));
-    }
-    J.pattern_of_struct[i] = pid;
-  }
-  J.distinct_patterns = (int)pats.size();
-  J.x_off.assign(n_problems + 1, 0);
-  J.g_off.assign(n_problems + 1, 0);
-  J.j_off.assign(n_problems + 1, 0);
-  for (int p = 0; p < n_problems; ++p) {
-    const int si = struct_of_problem[p];
-    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
-    const Structure& S = *structs[si];
-    const JacTables& P = pats[J.pattern_of_struct[si]];
-    J.x_off[p + 1] = J.x_off[p] + S.n_vars;
-    J.g_off[p + 1] = J.g_off[p] + S.n_rows;
-    J.j_off[p + 1] = J.j_off[p] + S.nnz;
-    for (const auto& rb : P.rows) J.mul.push_back({J.x_off[p], J.g_off[p], J.j_off[p], P.col, P.row_ptr, rb.first, rb.second, S.n_vars, 0});
-    for (const auto& tb : P.tblocks)
-      J.tmul.push_back({J.g_off[p], J.j_off[p], J.slab + tb.slot, tb.map, P.row_ptr, tb.k0, tb.k1, tb.r_first, tb.span, tb.ncols, 0});
-    for (int c0 = 0; c0 < S.n_vars; c0 += kJacFoldCols)
-      J.fold.push_back({J.x_off[p], J.slab, P.fold_ptr, P.fold_slot, c0, std::min(S.n_vars, c0 + kJacFoldCols)});
-    J.slab += P.slots;
-    if (S.n_vars <= kJacLdsX) J.mul_lds_x = std::max(J.mul_lds_x, S.n_vars);
-  }
-  return J;
-}
-
-// ---------------------------------------------------------------- the one-pass normal product (jac_products.hip jac_normal_kernel)
-namespace {
-struct JacNormalTables {   // one distinct pattern: byte offsets into JacNormalPlan::tables, its blocks, partials per problem
-  uint64_t fold_ptr = 0, fold_slot = 0;
-  struct Block {
-    int r0, r1, ncols, is_long;
-    uint64_t map;
-    int64_t slot;   // first partial, relative to the problem's
-  };
-  std::vector<Block> blocks;
-  int64_t slots = 0;
-};
-
-JacNormalTables BuildJacNormalTables(const Structure& S, JacNormalPlan& N, int tile) {
-  const int n = S.n_vars, m = S.n_rows;
-  JacNormalTables P;
-  std::vector<std::vector<int32_t>> slots_of(n);   // the partials of every column, in block order
-  for (int r0 = 0; r0 < m;) {
-    int r1 = r0 + 1;
-    while (r1 < m && r1 - r0 < kJacThreads && S.row_ptr[r1 + 1] - S.row_ptr[r0] <= tile) ++r1;
-    const int k0 = S.row_ptr[r0], k1 = S.row_ptr[r1];
-    if (k1 - k0 > tile) {   // one long row: a partial per entry, in column order
-      for (int k = k0; k < k1; ++k) slots_of[S.col_idx[k]].push_back((int32_t)(P.slots + (k - k0)));
-      P.blocks.push_back({r0, r1, k1 - k0, 1, 0, P.slots});
-      P.slots += k1 - k0;
-    } else if (k1 > k0) {
-      std::vector<std::pair<int, int>> e;   // (column, entry - k0), sorted: the block's columns ascending, each in row order
-      for (int k = k0; k < k1; ++k) e.push_back({S.col_idx[k], k - k0});
-      std::sort(e.begin(), e.end());
-      int ncols = 0;
-      for (size_t i = 0; i < e.size(); ++i) ncols += i == 0 || e[i].first != e[i - 1].first;
-      std::vector<uint16_t> map(ncols + 1 + e.size());
-      int j = -1;
-      for (size_t i = 0; i < e.size(); ++i) {
-        if (i == 0 || e[i].first != e[i - 1].first) {
-          map[++j] = (uint16_t)i;
-          slots_of[e[i].first].push_back((int32_t)(P.slots + j));
-        }
-        map[ncols + 1 + i] = (uint16_t)e[i].second;
-      }
-      map[ncols] = (uint16_t)e.size();
-      P.blocks.push_back({r0, r1, ncols, 0, AppendTable(N.tables, map.data(), map.size()), P.slots});
-      P.slots += ncols;
-    } else {
-      P.blocks.push_back({r0, r1, 0, 0, 0, P.slots});   // rows without entries: y = 0 is still theirs to write
-    }
-    r0 = r1;
-  }
-  std::vector<int32_t> fptr(n + 1, 0), fslot;
-  for (int c = 0; c < n; ++c) {
-    fslot.insert(fslot.end(), slots_of[c].begin(), slots_of[c].end());
-    fptr[c + 1] = (int32_t)fslot.size();
-  }
-  P.fold_ptr = AppendTable(N.tables, fptr.data(), fptr.size());
-  P.fold_slot = AppendTable(N.tables, fslot.data(), fslot.size());
-  return P;
-}
-}  // namespace
-
-void JacNormalPlan::Place(uint64_t ops_base, uint64_t base) {
-  for (auto& w : work) w.col += ops_base, w.row_ptr += ops_base, w.map += base;
-  for (auto& w : fold) w.ptr += base, w.slot += base;
-}
-
-std::vector<JacPatternPlace> JacPatternPlaces(const JacOpsPlan& J, const std::vector<int32_t>& struct_of_problem) {
-  std::vector<JacPatternPlace> at(J.distinct_patterns, JacPatternPlace{-1, 0, 0});
-  size_t k = 0;
-  for (size_t p = 0; p < struct_of_problem.size(); ++p) {   // J.mul is problem by problem; a problem without rows has no record
-    while (k < J.mul.size() && J.mul[k].x_off < J.x_off[p]) ++k;
-    JacPatternPlace& a = at[J.pattern_of_struct[struct_of_problem[p]]];
-    if (a.first_struct >= 0) continue;
-    a.first_struct = struct_of_problem[p];
-    if (k < J.mul.size() && J.mul[k].x_off == J.x_off[p]) a.col = J.mul[k].col, a.row_ptr = J.mul[k].row_ptr;
-  }
-  return at;
-}
-
-JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& patterns, const std::vector<JacPatternPlace>& places,
-                            const std::vector<int32_t>& pattern_of_problem, int tile) {
-  const int n_patterns = (int)patterns.size(), n_problems = (int)pattern_of_problem.size();
-  if (tile < 1 || tile > kJacNormNnz) throw std::runtime_error("the one-pass tile is 1 .. kJacNormNnz entries");
-  if (places.size() != patterns.size()) throw std::runtime_error("one place per pattern");
-  JacNormalPlan N;
-  N.tile = tile;
-  std::vector<JacNormalTables> npats;
-  for (const Structure* S : patterns) {
-    CheckPattern(*S);
-    npats.push_back(BuildJacNormalTables(*S, N, tile));
-  }
-  N.x_off.assign(n_problems + 1, 0);
-  N.g_off.assign(n_problems + 1, 0);
-  N.j_off.assign(n_problems + 1, 0);
-  for (int p = 0; p < n_problems; ++p) {
-    const int q = pattern_of_problem[p];
-    if (q < 0 || q >= n_patterns) throw std::runtime_error("pattern_of_problem out of range");
-    const Structure& S = *patterns[q];
-    const JacNormalTables& Q = npats[q];
-    N.x_off[p + 1] = N.x_off[p] + S.n_vars;
-    N.g_off[p + 1] = N.g_off[p] + S.n_rows;
-    N.j_off[p + 1] = N.j_off[p] + S.nnz;
-    for (const auto& b : Q.blocks)
-      N.work.push_back({N.x_off[p], N.g_off[p], N.j_off[p], N.slab + b.slot, places[q].col, places[q].row_ptr, b.map, b.r0, b.r1,
-                        S.n_vars, b.ncols, b.is_long, 0});
-    for (int c0 = 0; c0 < S.n_vars; c0 += kJacFoldCols)
-      N.fold.push_back({N.x_off[p], N.slab, Q.fold_ptr, Q.fold_slot, c0, std::min(S.n_vars, c0 + kJacFoldCols)});
-    N.slab += Q.slots;
-    if (S.n_vars <= kJacLdsX) N.lds_x = std::max(N.lds_x, S.n_vars);
-  }
-  return N;
-}
-
-JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem, int tile) {
-  const JacOpsPlan J = PlanJacOps(structs, struct_of_problem);   // (checks the patterns and struct_of_problem)
-  const std::vector<JacPatternPlace> places = JacPatternPlaces(J, struct_of_problem);
-  std::vector<const Structure*> patterns(places.size(), nullptr);   // (a pattern no problem has is still a structure's)
-  for (size_t i = 0; i < structs.size(); ++i)
-    if (!patterns[J.pattern_of_struct[i]]) patterns[J.pattern_of_struct[i]] = structs[i];
-  std::vector<int32_t> pattern_of_problem;
-  for (int32_t si : struct_of_problem) pattern_of_problem.push_back(J.pattern_of_struct[si]);
-  return PlanJacNormal(patterns, places, pattern_of_problem, tile);
-}
-
-// ---------------------------------------------------------------- the Gram matrix N = J^T W J (jac_gram.hip)
-void GramPattern(const Structure& S, std::vector<int32_t>* row_ptr, std::vector<int32_t>* col_idx) {
-  const CscPattern T = TransposePattern(S);   // (checks the pattern)
-  const int n = S.n_vars;
-  row_ptr->assign(n + 1, 0);
-  col_idx->clear();
-  std::vector<int> stamp(n, -1);
-  std::vector<int32_t> cols;
-  for (int i = 0; i < n; ++i) {   // row i of N: the columns of every row of J that has an entry in column i
-    cols.clear();
-    for (int q = T.col_ptr[i]; q < T.col_ptr[i + 1]; ++q) {
-      const int r = T.row_idx[q];
-      for (int k = S.row_ptr[r]; k < S.row_ptr[r + 1]; ++k) {
-        const int c = S.col_idx[k];
-        if (stamp[c] != i) stamp[c] = i, cols.push_back(c);
-      }
-    }
-    std::sort(cols.begin(), cols.end());
-    if (col_idx->size() + cols.size() > (size_t)INT32_MAX) throw JacGramUnsupported("the Gram matrix has more than 2^31 - 1 entries");
-    col_idx->insert(col_idx->end(), cols.begin(), cols.end());
-    (*row_ptr)[i + 1] = (int32_t)col_idx->size();
-  }
-}
-
-namespace {
-// One pattern's tables, appended to `tables` (offsets into it)
-JacGramPattern BuildGramTables(const Structure& S, std::vector<char>& tables) {
-  const int n = S.n_vars;
-  if (S.n_rows > kGramMaxRows)
-    throw JacGramUnsupported("the Gram tables hold a row of J in 16 bits: " + std::to_string(S.n_rows) + " rows, at most " + std::to_string(kGramMaxRows));
-  if (S.nnz > kGramMaxNnz)
-    throw JacGramUnsupported("the Gram tables hold a position in J in 24 bits: " + std::to_string(S.nnz) + " entries, at most " + std::to_string(kGramMaxNnz));
-  if (n > kGramMaxVars)
-    throw JacGramUnsupported("the Gram solve keeps " + std::to_string(kGramSolveVectors) + " vectors of n doubles in one workgroup's LDS (" +
-                             std::to_string(kGramLdsBytes) + " bytes): " + std::to_string(n) + " variables, at most " + std::to_string(kGramMaxVars));
-  JacGramPattern P;
-  std::vector<int32_t> rp, ci;
-  GramPattern(S, &rp, &ci);
-  const CscPattern T = TransposePattern(S);
-  P.n = n;
-  P.nnz = (int32_t)ci.size();
-  // the lower entries in CSR order, and every one's terms in ascending row
-  std::vector<int32_t> lpos, lmirror;
-  std::vector<std::vector<uint64_t>> terms;
-  std::vector<int32_t> where(n, -1);   // column -> lower entry of the row in hand
-  for (int i = 0; i < n; ++i) {
-    for (int e = rp[i]; e < rp[i + 1] && ci[e] <= i; ++e) {
-      const int j = ci[e];
-      where[j] = (int32_t)lpos.size();
-      lpos.push_back(e);
-      lmirror.push_back((int32_t)(std::lower_bound(ci.begin() + rp[j], ci.begin() + rp[j + 1], i) - ci.begin()));
-      terms.emplace_back();
-    }
-    for (int q = T.col_ptr[i]; q < T.col_ptr[i + 1]; ++q) {
-      const int r = T.row_idx[q];
-      for (int k = S.row_ptr[r]; k < S.row_ptr[r + 1] && S.col_idx[k] <= i; ++k)
-        terms[where[S.col_idx[k]]].push_back((uint64_t)r << 48 | (uint64_t)T.csr_pos[q] << 24 | (uint64_t)k);
-    }
-  }
-  P.lower = (int32_t)lpos.size();
-  std::vector<int32_t> order(P.lower);
-  for (int e = 0; e < P.lower; ++e) order[e] = e;
-  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return terms[a].size() > terms[b].size(); });
-  P.slices = (P.lower + kGramSlice - 1) / kGramSlice;
-  std::vector<int32_t> pos(P.lower), mirror(P.lower), cnt(P.lower), slice_ptr(P.slices + 1, 0);
-  std::vector<uint64_t> words;
-  for (int s = 0; s < P.slices; ++s) {
-    const int e0 = s * kGramSlice, e1 = std::min(P.lower, e0 + kGramSlice);
-    const size_t width = terms[order[e0]].size(), at = words.size();
-    if (at + width * kGramSlice > (size_t)INT32_MAX) throw JacGramUnsupported("the Gram contribution table has more than 2^31 - 1 words");
-    words.resize(at + width * kGramSlice, kGramPad);
-    for (int e = e0; e < e1; ++e) {
-      const std::vector<uint64_t>& t = terms[order[e]];
-      pos[e] = lpos[order[e]], mirror[e] = lmirror[order[e]], cnt[e] = (int32_t)t.size();
-      for (size_t k = 0; k < t.size(); ++k) words[at + k * kGramSlice + (e - e0)] = t[k];
-      P.products += (int64_t)t.size();
-    }
-    slice_ptr[s + 1] = (int32_t)words.size();
-  }
-  P.n_words = (int64_t)words.size();
-  std::vector<uint16_t> col(ci.begin(), ci.end());
-  P.row_ptr = AppendTable(tables, rp.data(), rp.size());
-  P.col = AppendTable(tables, col.data(), col.size());
-  P.pos = AppendTable(tables, pos.data(), pos.size());
-  P.mirror = AppendTable(tables, mirror.data(), mirror.size());
-  P.cnt = AppendTable(tables, cnt.data(), cnt.size());
-  P.slice_ptr = AppendTable(tables, slice_ptr.data(), slice_ptr.size());
-  P.words = AppendTable(tables, words.data(), words.size());
-  return P;
-}
-}  // namespace
-
-void JacGramPlan::Place(uint64_t base) {
-  for (auto& w : form) w.pos += base, w.mirror += base, w.cnt += base, w.slice_ptr += base, w.words += base;
-  for (auto& w : mul) w.row_ptr += base, w.col += base;
-  for (auto& w : solve) w.row_ptr += base, w.col += base;
-}
-
-JacGramPlan PlanJacGram(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem) {
-  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
-  JacGramPlan G;
-  std::vector<const Structure*> first;   // the first structure of every distinct pattern
-  std::unordered_map<uint64_t, std::vector<int>> by_hash;
-  G.pattern_of_struct.resize(n_structs);
-  for (int i = 0; i < n_structs; ++i) {
-    const Structure& S = *structs[i];
-    CheckPattern(S);
-    uint64_t h = HashWords(1469598103934665603ull ^ (uint64_t)S.n_vars, S.row_ptr.data(), S.row_ptr.size() * sizeof(int32_t));
-    h = HashWords(h, S.col_idx.data(), S.col_idx.size() * sizeof(int32_t));
-    std::vector<int>& bucket = by_hash[h];
-    int pid = -1;
-    for (int q : bucket)
-      if (first[q]->n_vars == S.n_vars && first[q]->row_ptr == S.row_ptr && first[q]->col_idx == S.col_idx) pid = q;
-    if (pid < 0) {
-      pid = (int)G.patterns.size();
-      bucket.push_back(pid);
-      first.push_back(&S);
-      G.patterns.emplace_back();
-    }
-    G.pattern_of_struct[i] = pid;
-  }
-  // The distinct patterns are planned side by side (a sweep has a thousand of them at a third of a second each), every one into
-  // tables of its own, which are then laid end to end in pattern order: the plan does not depend on the number of threads.
-  const int n_pat = (int)first.size();
-  std::vector<std::vector<char>> local(n_pat);
-  std::vector<std::exception_ptr> failed(n_pat);
-  std::atomic<int> next{0};
-  const auto worker = [&] {
-    for (int q = next++; q < n_pat; q = next++) {
-      try {
-        G.patterns[q] = BuildGramTables(*first[q], local[q]);
-      } catch (...) {
-        failed[q] = std::current_exception();
-      }
-    }
-  };
-  const int n_threads = std::max(1, std::min({n_pat, kGramPlanThreads, (int)std::thread::hardware_concurrency()}));
-  std::vector<std::thread> pool;
-  for (int t = 1; t < n_threads; ++t) pool.emplace_back(worker);
-  worker();
-  for (std::thread& t : pool) t.join();
-  for (int q = 0; q < n_pat; ++q)
-    if (failed[q]) std::rethrow_exception(failed[q]);   // the first pattern that failed, whatever thread had it
-  for (int q = 0; q < n_pat; ++q) {
-    const uint64_t base = AppendTable(G.tables, local[q].data(), local[q].size());
-    JacGramPattern& P = G.patterns[q];
-    P.row_ptr += base, P.col += base, P.pos += base, P.mirror += base, P.cnt += base, P.slice_ptr += base, P.words += base;
-    std::vector<char>().swap(local[q]);
-  }
-  G.x_off.assign(n_problems + 1, 0);
-  G.g_off.assign(n_problems + 1, 0);
-  G.j_off.assign(n_problems + 1, 0);
-  G.gram_off.assign(n_problems + 1, 0);
-  for (int p = 0; p < n_problems; ++p) {
-    const int si = struct_of_problem[p];
-    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
-    const Structure& S = *structs[si];
-    const JacGramPattern& P = G.patterns[G.pattern_of_struct[si]];
-    G.x_off[p + 1] = G.x_off[p] + S.n_vars;
-    G.g_off[p + 1] = G.g_off[p] + S.n_rows;
-    G.j_off[p + 1] = G.j_off[p] + S.nnz;
-    G.gram_off[p + 1] = G.gram_off[p] + (P.nnz + 1) / 2 * 2;
-    for (int e0 = 0; e0 < P.lower; e0 += kGramThreads)
-      G.form.push_back({G.g_off[p], G.j_off[p], G.gram_off[p], P.pos, P.mirror, P.cnt, P.slice_ptr, P.words, e0, std::min(P.lower, e0 + kGramThreads)});
-    for (int r0 = 0; r0 < S.n_vars; r0 += kGramThreads)
-      G.mul.push_back({G.x_off[p], G.gram_off[p], P.row_ptr, P.col, r0, std::min(S.n_vars, r0 + kGramThreads)});
-    G.solve.push_back({G.x_off[p], G.gram_off[p], P.row_ptr, P.col, S.n_vars, 0});
-    G.max_n = std::max(G.max_n, S.n_vars);
-  }
-  return G;
-}
-
-void JacLsqPlan::Place(uint64_t base) {
-  for (auto& w : work) w.lower += base, w.upper += base;
-}
-
-JacLsqPlan PlanJacLsq(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem) {
-  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
-  JacLsqPlan L;
-  struct Table {
-    const Structure* first;
-    uint64_t lower, upper;
-  };
-  std::vector<Table> tabs;
-  std::unordered_map<uint64_t, std::vector<int>> by_hash;
-  L.bounds_of_struct.resize(n_structs);
-  for (int i = 0; i < n_structs; ++i) {
-    const Structure& S = *structs[i];
-    if ((int)S.lower.size() != S.n_rows || (int)S.upper.size() != S.n_rows) throw std::runtime_error("bounds do not match the rows");
-    uint64_t h = HashWords(1469598103934665603ull ^ (uint64_t)S.n_rows, S.lower.data(), S.lower.size() * sizeof(double));
-    h = HashWords(h, S.upper.data(), S.upper.size() * sizeof(double));
-    std::vector<int>& bucket = by_hash[h];
-    const size_t bytes = (size_t)S.n_rows * sizeof(double);
-    int tid = -1;
-    for (int q : bucket) {   // byte-identical, not ==: -0.0 and 0.0 are different tables, NaN bounds equal themselves
-      const Structure& F = *tabs[q].first;
-      if (F.n_rows == S.n_rows && (bytes == 0 || (std::memcmp(F.lower.data(), S.lower.data(), bytes) == 0 &&
-                                                  std::memcmp(F.upper.data(), S.upper.data(), bytes) == 0)))
-        tid = q;
-    }
-    if (tid < 0) {
-      tid = (int)tabs.size();
-      bucket.push_back(tid);
-      const uint64_t lo = AppendTable(L.bounds, S.lower.data(), S.lower.size());
-      tabs.push_back({&S, lo, AppendTable(L.bounds, S.upper.data(), S.upper.size())});
-    }
-    L.bounds_of_struct[i] = tid;
-  }
-  L.distinct_bounds = (int)tabs.size();
-  L.x_off.assign(n_problems + 1, 0);
-  L.g_off.assign(n_problems + 1, 0);
-  for (int p = 0; p < n_problems; ++p) {
-    const int si = struct_of_problem[p];
-    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
-    const Structure& S = *structs[si];
-    const Table& T = tabs[L.bounds_of_struct[si]];
-    L.work.push_back({L.x_off[p], L.g_off[p], T.lower, T.upper, S.n_vars, S.n_rows});
-    L.x_off[p + 1] = L.x_off[p] + S.n_vars;
-    L.g_off[p + 1] = L.g_off[p] + S.n_rows;
-    if (S.n_vars <= kJacLdsX) L.lds_x = std::max(L.lds_x, S.n_vars);
-  }
-  const auto even = [](int64_t v) { return (v + 1) / 2 * 2; };
-  const int64_t X = even(L.x_off[n_problems]), G = even(L.g_off[n_problems]);
-  L.ws_p = 0;
-  L.ws_z = L.ws_p + X;
-  L.ws_q = L.ws_z + X;
-  L.ws_r = L.ws_q + G;
-  L.ws_t = L.ws_r + G;
-  L.ws_rec = L.ws_t + G;
-  L.ws_doubles = L.ws_rec + (int64_t)kLsqRec * n_problems;
-  L.ws2_e = 0;
-  L.ws2_cp = L.ws2_e + X;
-  L.ws2_doubles = L.ws2_cp + X;
-  L.ws3_s = 0;
-  L.ws3_u = L.ws3_s + X;
-  L.ws3_doubles = L.ws3_u + X;
-  return L;
-}
-
-JacLmPlan PlanJacLm(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem) {
-  const int n_structs = (int)structs.size(), n_problems = (int)struct_of_problem.size();
-  JacLmPlan L;
-  L.x_off.assign(n_problems + 1, 0);
-  L.g_off.assign(n_problems + 1, 0);
-  for (int p = 0; p < n_problems; ++p) {
-    const int si = struct_of_problem[p];
-    if (si < 0 || si >= n_structs) throw std::runtime_error("struct_of_problem out of range");
-    L.x_off[p + 1] = L.x_off[p] + structs[si]->n_vars;
-    L.g_off[p + 1] = L.g_off[p] + structs[si]->n_rows;
-  }
-  const auto even = [](int64_t v) { return (v + 1) / 2 * 2; };
-  const int64_t X = even(L.x_off[n_problems]), G = even(L.g_off[n_problems]), P = even(n_problems);
-  int64_t at = 0;
-  const auto take = [&](int64_t& seg, int64_t len) { seg = at, at += len; };
-  for (int64_t* s : {&L.ws_xt, &L.ws_d, &L.ws_z, &L.ws_colsq, &L.ws_colmax, &L.ws_c, &L.ws_cf}) take(*s, X);
-  for (int64_t* s : {&L.ws_r, &L.ws_b, &L.ws_wa, &L.ws_gt, &L.ws_rt}) take(*s, G);
-  take(L.ws_rec, even((int64_t)kLmRec * n_problems));
-  for (int64_t* s : {&L.ws_mu, &L.ws_merit_t, &L.ws_merit_lin, &L.ws_nfree}) take(*s, P);
-  take(L.ws_info, even((int64_t)4 * n_problems));
-  L.ws_doubles = at;
-  return L;
 }
 
 }  // namespace twr
