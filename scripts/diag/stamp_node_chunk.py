@@ -1,19 +1,14 @@
 #!/usr/bin/env python3
-"""Diagnostic build with s_memtime stamps around the phases of node_chunk_kernel's loop (patched COPY of kernels.hip ->
+"""Diagnostic build with s_memtime stamps around the phases of node_chunk_kernel's loop (patched COPY of kernels/node_chunk.h, compiled into kernels.hip ->
 towr_amd/libtowr_amd_nodestamps.so; the product source has no diagnostic hooks).  Run scripts/diag/node_stamps.py with
 TWR_AMD_LIB pointing at it.  Every stamp waits for the wave's LDS / scalar queue (s_memtime returns through lgkmcnt)."""
-import os
-import subprocess
+from stamp_build import build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-SRC = os.path.join(ROOT, "towr_amd", "csrc")
-s = open(os.path.join(SRC, "kernels.hip")).read()
+P = []
 
 
 def rep(old, new):
-    global s
-    assert old in s, old[:70]
-    s = s.replace(old, new, 1)
+    P.append((old, new))
 
 
 rep("template <int FAM, bool WANT_G, bool WANT_J>\nTWR_DEV void fam_body(",
@@ -30,20 +25,8 @@ rep("    fam_store<FAM, WANT_G, WANT_J>(w0, g, jac, stage, gst, par, lane);\n", 
 rep("    w1 = w2; in1 = in2;\n    w2 = w3;\n  }",
     "    w1 = w2; in1 = in2;\n    w2 = w3;\n    NSTAMP(3)\n    acc[7] += 1;\n  }\n"
     "  if (lane == 0 && i_first < 256 && WANT_G && WANT_J)\n    for (int q = 0; q < 8; ++q) g_node_stamps[(FAM * 256 + i_first) * 8 + q] = acc[q];")
-rep("#endif  // !TWR_TU_ROM\n\n}  // namespace twr",
-    "extern \"C\" int twr_debug_node_stamps(unsigned long long* out, int n) {\n"
-    "  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_node_stamps), sizeof(unsigned long long) * (size_t)n);\n}\n"
-    "#endif  // !TWR_TU_ROM\n\n}  // namespace twr")
-tmp = os.path.join(SRC, "_kernels_nodestamps.hip")
-open(tmp, "w").write(s)
-hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-try:
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-c", "-o", os.path.join(SRC, "_kernels_nodestamps.o"), tmp], cwd=SRC)
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "--hip-link", "-fPIC", "-shared", "-o", os.path.join(ROOT, "towr_amd", "libtowr_amd_nodestamps.so"),
-                           "_kernels_nodestamps.o", "rom_tu.o", "structure.o", "presets.o", "batch_plan.o", "eval_plan.o", "jac_plan.o", "capi.o",
-                           "capi_jac.o"], cwd=SRC)
-finally:
-    for f in (tmp, os.path.join(SRC, "_kernels_nodestamps.o")):
-        if os.path.exists(f):
-            os.remove(f)
+build("kernels/node_chunk.h", P,
+      "extern \"C\" int twr_debug_node_stamps(unsigned long long* out, int n) {\n"
+      "  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_node_stamps), sizeof(unsigned long long) * (size_t)n);\n}\n",
+      "libtowr_amd_nodestamps.so")
 print("towr_amd/libtowr_amd_nodestamps.so built; run: TWR_AMD_LIB=$PWD/towr_amd/libtowr_amd_nodestamps.so python3 scripts/diag/node_stamps.py")

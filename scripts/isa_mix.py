@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
-"""Instruction mix of the largest loop of one kernel in towr_amd/csrc/kernels.s (`make -C towr_amd/csrc asm`).
-usage: isa_mix.py <mangled-name-substring> [top]"""
+"""Instruction mix of the largest loop of one kernel in towr_amd/csrc/kernels.s (`make -C towr_amd/csrc asm`, which also
+writes rom_tu.s, the unit of rom_kernel: name that file as an argument).
+usage: isa_mix.py <mangled-name-substring> [top] [--whole] [towr_amd/csrc/rom_tu.s]"""
 import collections
 import re
 import sys
 
-path = "towr_amd/csrc/kernels.s"
+path = ([a for a in sys.argv[2:] if a.endswith(".s")] or ["towr_amd/csrc/kernels.s"])[0]
 lines = open(path).read().split("\n")
 key = sys.argv[1]
 top = int(sys.argv[2]) if len(sys.argv) > 2 and sys.argv[2].isdigit() else 40

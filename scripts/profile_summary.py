@@ -13,6 +13,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from bench import kernel_source_hash  # noqa: E402
+from kernel_header_hash import kernel_header_hash  # noqa: E402
 
 out, tag = sys.argv[1], sys.argv[2]
 prof = os.path.join(ROOT, "profiles")
@@ -127,6 +128,7 @@ def traffic(c):
 
 
 json.dump({"workload": "C3", "problems_per_gpu": 8192, "kernel_source_sha256": kernel_source_hash(),
+           "kernel_header_sha256": kernel_header_hash(),
            "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes; bytes = (WRITE_SIZE + 2*FETCH_SIZE) KiB",
            "hbm_bytes_per_launch": traffic(allc),
            "timings_2048": {"hbm_bytes_per_launch": traffic(tim)},

@@ -66,7 +66,7 @@ std::vector<size_t> BlobOffsets(const std::vector<const Structure*>& structs) {
 
 namespace {
 // XCD-aware order.  Workgroups are dealt round-robin over the 8 XCDs and the persistent grids are multiples of 8, so list
-// position j runs on XCD j % 8 (eval_fused_kernel's slice mapping relies on it, kernels.hip).  Interleaving the problems in
+// position j runs on XCD j % 8 (eval_fused_kernel's slice mapping relies on it, kernels/fused.h).  Interleaving the problems in
 // groups of 8 puts all items of one problem on ONE XCD (same L2): its x is fetched from HBM once per kernel instead of once
 // per XCD.  (Speed only; ragged item counts merely loosen the alignment.)  first: first item of every problem (+ end).
 template <class W>
@@ -393,7 +393,7 @@ void DecidePolicy(const BatchInputs& in, BatchPlan& b, int64_t cache_bytes) {
     if (!S.timings && s > 0 && b.lists.dyn.size() == (size_t)s * (size_t)n_problems)
       b.dyn_uniform = DynUniform{s, 0, std::min(8, n_problems), n_problems, S.n_vars, S.n_rows, S.nnz, 0};
   }
-  // Store policy of the copy-out (kernels.hip copy_out_fixed): non-temporal when the batch is SWEEP-LIKE -- fewer than four
+  // Store policy of the copy-out (kernels/copy_out.h copy_out_fixed): non-temporal when the batch is SWEEP-LIKE -- fewer than four
   // problems per structure on average, so every evaluation re-reads tables (and x) that only that problem uses -- AND one
   // evaluation writes more than the device's memory-side cache holds (256 MB on an MI355X; by architecture name, batch_plan.h), so that plain stores would flush those
   // tables out of it between two evaluations.  Measured (one box, no per-kernel events): the C5 sweep at 512 /

@@ -22,7 +22,7 @@ struct LayoutShare {
   int64_t bytes_built = 0, bytes_distinct = 0;
 };
 LayoutShare ShareLayoutTables(const std::vector<const Structure*>& structs);
-// Store policy of a batch (kernels.hip copy_out_fixed): non-temporal stores for SWEEP-LIKE batches -- fewer than
+// Store policy of a batch (kernels/copy_out.h copy_out_fixed): non-temporal stores for SWEEP-LIKE batches -- fewer than
 // four problems per structure on average, so that every evaluation re-reads tables and x that only one problem uses -- whose
 // evaluation writes more than the Infinity Cache holds, so that plain stores would flush those tables out of it.
 // The memory-side cache is a property of the DEVICE the batch lives on (HIP reports no field for it -- hipDeviceProp_t has

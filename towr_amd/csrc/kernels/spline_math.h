@@ -1,0 +1,208 @@
+#pragma once
+#include <stdint.h>
+
+#include "common.h"
+
+namespace twr {
+// ---------------------------------------------------------------- cubic Hermite weights
+// d{pos,vel,acc}/d{p0,v0,p1,v1} of CubicHermitePolynomial (src/polynomial.cc:140-234); iT = 1/T comes
+// from the tables (one IEEE division on the host instead of one per lane and spline).
+TWR_DEV void hermite_pos(double t, double iT, double w[4]) {
+  const double iT2 = iT * iT, iT3 = iT2 * iT;
+  const double t2 = t * t, t3 = t2 * t;
+  w[0] = 2.0 * t3 * iT3 - 3.0 * t2 * iT2 + 1.0;
+  w[1] = t - 2.0 * t2 * iT + t3 * iT2;
+  w[2] = 3.0 * t2 * iT2 - 2.0 * t3 * iT3;
+  w[3] = t3 * iT2 - t2 * iT;
+}
+TWR_DEV void hermite_all(double t, double iT, double wp[4], double wv[4], double wa[4]) {
+  hermite_pos(t, iT, wp);
+  const double iT2 = iT * iT, iT3 = iT2 * iT;
+  const double t2 = t * t;
+  wv[0] = 6.0 * t2 * iT3 - 6.0 * t * iT2;
+  wv[1] = 3.0 * t2 * iT2 - 4.0 * t * iT + 1.0;
+  wv[2] = 6.0 * t * iT2 - 6.0 * t2 * iT3;
+  wv[3] = 3.0 * t2 * iT2 - 2.0 * t * iT;
+  wa[0] = 12.0 * t * iT3 - 6.0 * iT2;
+  wa[1] = 6.0 * t * iT2 - 4.0 * iT;
+  wa[2] = 6.0 * iT2 - 12.0 * t * iT3;
+  wa[3] = 6.0 * t * iT2 - 2.0 * iT;
+}
+
+// ---------------------------------------------------------------- candidate descriptors
+TWR_DEV int meta_nslots(uint32_t meta) { return meta & 0xF; }
+TWR_DEV bool meta_shared(uint32_t meta) { return (meta >> 16) & 1; }
+// all 12 candidate loads are issued unconditionally (absent candidates read slot 0 and later get
+// weight 0): one memory round trip, no branches (Spline::GetPoint needs at most these 12 values)
+template <class Slot>   // slot(c): the 4-bit slot of candidate c, 0xF = absent
+TWR_DEV void gather12_by(const double* __restrict__ xp, int xbase, Slot slot, double v[12]) {
+#pragma unroll
+  for (int c = 0; c < 12; ++c) {
+    const int sl = slot(c);
+    v[c] = xp[xbase + (sl != 0xF ? sl : 0)];
+  }
+}
+TWR_DEV void gather12(const double* __restrict__ xp, int xbase, uint64_t slots, double v[12]) {
+  gather12_by(xp, xbase, [&](int c) { return (int)((slots >> (4 * c)) & 0xF); }, v);
+}
+// Position of an ee spline from its gathered node values (Spline::GetPoint, src/spline.cc:80-93, in
+// Hermite basis form).  A stance ee-motion polynomial keeps one shared position variable for both
+// nodes: w_p1 is folded into w_p0.
+TWR_DEV void ee_point(uint64_t slots, bool shared, double tl, double iT, const double v[12], double w[4], double out[3]) {
+  hermite_pos(tl, iT, w);
+  if (shared) w[0] += w[2];
+  out[0] = out[1] = out[2] = 0.0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const bool valid = ((slots >> (4 * (j * 3 + d))) & 0xF) != 0xF;
+      out[d] = fma(valid ? w[j] : 0.0, v[j * 3 + d], out[d]);
+    }
+}
+TWR_DEV void gather12c(const double* __restrict__ xp, int xbase, const uint16_t cand[12], double v[12]) {
+  gather12_by(xp, xbase, [&](int c) { return cand[c] & 0xF; }, v);
+}
+TWR_DEV uint64_t slots_of(const uint16_t cand[12]) {
+  uint64_t s = 0;
+#pragma unroll
+  for (int c = 0; c < 12; ++c) s |= (uint64_t)(cand[c] & 0xF) << (4 * c);
+  return s;
+}
+
+// entry (r,d), r != d, of the cross-product matrix [v]x (single_rigid_body_dynamics.cc:46-57)
+template <int R, int D>
+TWR_DEV double crs(const double v[3]) {
+  static_assert(R != D, "diagonal of a cross matrix is structurally absent");
+  constexpr int o = 3 - R - D;
+  constexpr bool pos = (R == 0 && D == 2) || (R == 1 && D == 0) || (R == 2 && D == 1);
+  return pos ? v[o] : -v[o];
+}
+TWR_DEV void cross3(const double a[3], const double b[3], double o[3]) {
+  o[0] = a[1] * b[2] - a[2] * b[1];
+  o[1] = a[2] * b[0] - a[0] * b[2];
+  o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// sin and cos of one Euler angle.  Cody-Waite reduction by pi/2 in three FMA steps and the fdlibm
+// minimax kernels (k_sin.c / k_cos.c coefficients), ~35 FP64 instructions for both results and
+// accurate to about 1 ulp for |x| < 1e5; anything larger (or non-finite) takes the ocml path.
+// The reference calls libm sin/cos (euler_converter.cc:133-221); the difference is rounding level.
+TWR_DEV void sincos_fast(double x, double* __restrict__ s, double* __restrict__ c) {
+  if (!(fabs(x) < 1.0e5)) {
+    sincos(x, s, c);
+    return;
+  }
+  // (the constants pass through an empty asm: they are then materialised where they are used -- two s_mov each -- instead
+  // of being hoisted out of the persistent loops, where the register allocator ends up spilling them to scratch)
+  auto K = [](double c) {
+    asm volatile("" : "+s"(c));
+    return c;
+  };
+  const double n = rint(x * K(6.36619772367581382433e-01));
+  double r = fma(-n, K(1.5707963267948966e+00), x);
+  r = fma(-n, K(6.1232339957367574e-17), r);
+  r = fma(-n, K(8.4784276603688985e-32), r);
+  const double z = r * r;
+  double ps = fma(z, K(1.58969099521155010221e-10), K(-2.50507602534068634195e-08));
+  ps = fma(z, ps, K(2.75573137070700676789e-06));
+  ps = fma(z, ps, K(-1.98412698298579493134e-04));
+  ps = fma(z, ps, K(8.33333333332248946124e-03));
+  ps = fma(z, ps, K(-1.66666666666666324348e-01));
+  const double sr = fma(z * r, ps, r);
+  double pc = fma(z, K(-1.13596475577881948265e-11), K(2.08757232129817482790e-09));
+  pc = fma(z, pc, K(-2.75573143513906633035e-07));
+  pc = fma(z, pc, K(2.48015872894767294178e-05));
+  pc = fma(z, pc, K(-1.38888888888741095749e-03));
+  pc = fma(z, pc, K(4.16666666666666019037e-02));
+  const double cr = fma(z * z, pc, fma(z, -0.5, 1.0));
+  const int q = (int)n & 3;
+  const double ss = (q & 1) ? cr : sr, cc = (q & 1) ? sr : cr;
+  *s = (q & 2) ? -ss : ss;
+  *c = ((q + 1) & 2) ? -cc : cc;
+}
+
+// ZYX Euler rotation base->world (euler_converter.cc:207-221).
+struct Rot {
+  double R[3][3];
+  double sx, cx, sy, cy, sz, cz;
+};
+TWR_DEV void rotation(const double e[3], Rot& o) {
+  double sx, cx, sy, cy, sz, cz;
+  sincos_fast(e[0], &sx, &cx);
+  sincos_fast(e[1], &sy, &cy);
+  sincos_fast(e[2], &sz, &cz);
+  o.sx = sx; o.cx = cx; o.sy = sy; o.cy = cy; o.sz = sz; o.cz = cz;
+  o.R[0][0] = cy * cz; o.R[0][1] = cz * sx * sy - cx * sz; o.R[0][2] = sx * sz + cx * cz * sy;
+  o.R[1][0] = cy * sz; o.R[1][1] = cx * cz + sx * sy * sz; o.R[1][2] = cx * sy * sz - cz * sx;
+  o.R[2][0] = -sy;     o.R[2][1] = cy * sx;                o.R[2][2] = cx * cy;
+}
+TWR_DEV void matvec(const double A[3][3], const double v[3], double o[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = A[i][0] * v[0] + A[i][1] * v[1] + A[i][2] * v[2];
+}
+TWR_DEV void matTvec(const double A[3][3], const double v[3], double o[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = A[0][i] * v[0] + A[1][i] * v[1] + A[2][i] * v[2];
+}
+TWR_DEV void symmul(const double I[6], const double v[3], double o[3]) {  // I = (00,01,02,11,12,22)
+  o[0] = I[0] * v[0] + I[1] * v[1] + I[2] * v[2];
+  o[1] = I[1] * v[0] + I[3] * v[1] + I[4] * v[2];
+  o[2] = I[2] * v[0] + I[4] * v[1] + I[5] * v[2];
+}
+
+// ---------------------------------------------------------------- quad helpers
+// The dynamic kernel maps FOUR lanes to one time node (a "quad" = lanes 4i..4i+3); they exchange
+// scalars with DPP quad permutes (no LDS, no memory).
+template <int CTRL>
+TWR_DEV double quad_perm(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+TWR_DEV double quad_sum(double v) {
+  v += quad_perm<0xB1>(v);  // lane ^ 1
+  v += quad_perm<0x4E>(v);  // lane ^ 2
+  return v;
+}
+TWR_DEV double sel3(int i, double a, double b, double c) { return i == 0 ? a : (i == 1 ? b : c); }
+
+// ---------------------------------------------------------------- optimised timings helpers
+// Spline::GetSegmentID + GetLocalTime (src/spline.cc:48-78) on durations that depend on x: the same
+// double-precision accumulation, eps and sequential subtraction as the reference (and the host Locate).
+TWR_DEV int locate_segment(const double* __restrict__ d, int n, double t, double& t_local) {
+  // Branch-free on purpose: with the reference's early `break` every iteration's load waits for the previous compare
+  // (a chain of dependent LDS round trips); predicated, the loads of an unrolled block go out together and only the
+  // additions are sequential.  Same additions and subtractions in the same order, so the same bits.
+  const double eps = 1e-10;
+  double acc = 0.0, tl = t;
+  int id = n - 1;  // (the reference asserts that a segment is found)
+  bool found = false;
+#pragma unroll 8
+  for (int i = 0; i < n; ++i) {
+    const double di = d[i];
+    acc += di;
+    const bool hit = !found && acc >= t - eps;
+    id = hit ? i : id;
+    found = found || hit;
+    if (!found && i < n - 1) tl -= di;   // t_local = t - sum of the durations BEFORE the segment, sequentially
+  }
+  t_local = tl;
+  return id;
+}
+// node values (p0,v0,p1,v1)[dim] of the active polynomial from its gathered candidates: values that are
+// not optimised are the constant 0, a stance ee-motion polynomial has p1 = p0
+TWR_DEV void node_values(uint64_t slots, bool shared, const double v[12], double nv[4][3]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const bool valid = ((slots >> (4 * (j * 3 + d))) & 0xF) != 0xF;
+      nv[j][d] = valid ? v[j * 3 + d] : 0.0;
+    }
+  if (shared) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) nv[2][d] = nv[0][d];
+  }
+}
+}  // namespace twr

@@ -1391,7 +1391,7 @@ void Structure::BuildSizes() {
 // truncates toward zero; a quotient <= -1 wraps to a huge size_t in the reference (formally undefined) and
 // fails the range check -- here a signed cell index that is invalid when negative.
 // Grid::GetHeight (include/towr/terrain/grid_height_map.h:29-46) over grid_map's published
-// atPosition(INTER_LINEAR) (restated in the device code, kernels.hip gridmap_sample; this host copy serves the
+// atPosition(INTER_LINEAR) (restated in the device code, kernels/terrain.h gridmap_sample; this host copy serves the
 // initial guess only): bilinear in double, rounded to float; nearest cell in the border band; FLT_MAX outside.
 static float GridMapSample(const TerrainGrid& g, double x, double y) {
   const int sx = g.rows, sy = g.cols;

@@ -77,7 +77,7 @@ inline std::shared_ptr<twr_terrain_grid> OwnGrid(twr_terrain_grid* g) {
   return std::shared_ptr<twr_terrain_grid>(g, [](twr_terrain_grid* p) { twr_terrain_grid_destroy(p); });
 }
 
-// The seven analytic maps carry compile-time constants only and are restated on the device (kernels.hip terrain_eval).
+// The seven analytic maps carry compile-time constants only and are restated on the device (kernels/terrain.h terrain_eval).
 // Throws for every other subclass, including the gridded ones (use GridTerrain / CsvTerrain for those).
 inline DeviceTerrain ToTwrTerrain(const towr::HeightMap& t) {
   DeviceTerrain d;
@@ -99,7 +99,7 @@ inline DeviceTerrain ToTwrTerrain(const towr::HeightMap& t) {
     throw std::runtime_error(
         "towr_amd: this HeightMap subclass has no device counterpart.  Gridded maps: pass GridTerrain(map) / "
         "CsvTerrain(path) to MakeDeviceConstraints; anything else: keep the CPU constraint sets for it, or add its "
-        "height function to terrain_eval in kernels.hip");
+        "height function to terrain_eval in kernels/terrain.h");
   return d;
 }
 
