@@ -7,12 +7,12 @@ import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.path.join(ROOT, "towr_amd", "csrc")
-OTHER_OBJ = ["rom_tu.o", "structure.o", "presets.o", "batch_plan.o", "eval_plan.o", "jac_plan.o", "capi.o", "capi_jac.o"]
+OTHER_OBJ = ["rom_tu.o", "util_tu.o", "structure.o", "presets.o", "batch_plan.o", "eval_plan.o", "jac_plan.o", "capi.o", "capi_jac.o"]
 UNIT_END = "\n}  // namespace twr\n"
 
 
 def build(source, patches, accessor, lib):
-    """source: the file that holds the patched text, relative to towr_amd/csrc (kernels/dyn.h, kernels.hip); patches: (old, new) pairs, every `old`
+    """source: the file that holds the patched text, relative to towr_amd/csrc (kernels/dyn.h, kernels/dyn_phase.h); patches: (old, new) pairs, every `old`
     must occur; accessor: code appended to the unit inside namespace twr; lib: name of the library under towr_amd/."""
     tmp = os.path.join(ROOT, "towr_amd", "_stamp_csrc")   # a sibling of csrc: relative includes resolve as in the product
     obj = os.path.join(SRC, "_kernels_stamps.o")

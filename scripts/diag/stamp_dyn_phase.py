@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Diagnostic build of the library with s_memtime stamps around the phases of dyn_phase_kernel (the product source has no
-diagnostic hooks): patches a COPY of kernels.hip, compiles it and links towr_amd/libtowr_amd_stamps.so.  Run
+diagnostic hooks): patches a COPY of kernels/dyn_phase.h, compiles kernels.hip with it and links towr_amd/libtowr_amd_stamps.so.  Run
 scripts/diag/pdyn_stamps.py with TWR_AMD_LIB pointing at that library to get the per-phase split.
 Every stamp waits for the wave's LDS / scalar queue (s_memtime returns through lgkmcnt): the split is what matters."""
 from stamp_build import build
@@ -28,7 +28,7 @@ rep("    PDynRec r1;\n    pdyn_wait_rec<(WANT_G ? 1 : 0)>(ar, r1);\n    pdyn_iss
 rep("    pdyn_wait_in<(WANT_J ? (NIT < 63 ? NIT : 63) : 0)>(ai, in);   // (NIT = 0: drains the copy-out)\n    w0 = w1;\n    r0 = r1;\n  }\n}",
     "    STAMP(6)\n    pdyn_wait_in<(WANT_J ? (NIT < 63 ? NIT : 63) : 0)>(ai, in);\n    w0 = w1;\n    r0 = r1;\n    acc[7] += 1;\n  }\n"
     "  if (lane == 0 && blockIdx.x < 1024 && WANT_G && WANT_J)\n    for (int q = 0; q < 8; ++q) g_pdyn_stamps[blockIdx.x * 8 + q] = acc[q];\n}")
-build("kernels.hip", P,
+build("kernels/dyn_phase.h", P,
       "extern \"C\" int twr_debug_pdyn_stamps(unsigned long long* out, int n) {\n"
       "  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_pdyn_stamps), sizeof(unsigned long long) * (size_t)n);\n}\n",
       "libtowr_amd_stamps.so")

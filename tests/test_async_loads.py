@@ -1,5 +1,5 @@
 """Static check of the hand-scheduled pipelines (dyn_phase_kernel, rom_phase_kernel): their prefetch loads are issued
-as asm into AGPRs behind the compiler's back and waited for with explicit counted s_waitcnt (kernels.hip, `aload`).  The
+as asm into AGPRs behind the compiler's back and waited for with explicit counted s_waitcnt (kernels/async_pipe.h, `aload`).  The
 protocol is only sound if NO instruction touches such an AGPR between its load and the wait that covers it -- the
 compiler does not know the register is in flight, so a live-range split or an early copy would read stale data.  This
 test disassembles the device code and replays every instantiation's instruction stream against an in-order model of the

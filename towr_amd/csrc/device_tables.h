@@ -1,5 +1,5 @@
 // Device-side tables shared by the host packer (structure.cc / capi.cc) and the HIP kernels
-// (kernels.hip).  Everything here is x-independent: it is what the reference recomputes on every
+// (kernels/*.h, util_tu.hip).  Everything here is x-independent: it is what the reference recomputes on every
 // call (active polynomial, local time, node->variable maps, CSR positions) hoisted to setup time and
 // flattened into one fixed-size record per lane, so that a lane needs exactly two dependent memory
 // round trips (its record, then its slice of x) before it can compute.

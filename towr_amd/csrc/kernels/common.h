@@ -24,6 +24,8 @@ TWR_DEV void lds_put(char* __restrict__ lds, uint32_t byte_off, double v) { *rei
 TWR_DEV double lds_f64(const char* __restrict__ lds, uint32_t byte_off) {
   return *reinterpret_cast<const double*>(lds + byte_off);
 }
+// NaN-propagating max of two violations (score_kernel, eval_scores_kernel): a NaN operand wins
+TWR_DEV double nan_max(double a, double b) { return (a != a || b != b) ? (a != a ? a : b) : fmax(a, b); }
 constexpr int TWR_MAX_PHASES_DEV = 32;  // = TWR_MAX_PHASES of include/towr_amd.h
 
 template <typename T>

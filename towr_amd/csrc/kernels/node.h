@@ -12,8 +12,6 @@ namespace twr {
 // all terrain-ee-motion_e (terrain_constraint.cc:57-108), force-ee-force_e, splineacc-base-* and
 // swing-ee-motion_e sets of one problem.  One workgroup of four waves per problem, one wave per family
 // (each with its own LDS image, no barriers), 64 spline nodes / rows at a time.
-// NaN-propagating max of two violations (score_kernel, eval_scores_kernel): a NaN operand wins
-TWR_DEV double nan_max(double a, double b) { return (a != a || b != b) ? (a != a ? a : b) : fmax(a, b); }
 // Candidate scoring without g (eval_scores_kernel): where the values-only kernel stores a constraint value, the scoring
 // instantiation turns it into the row's bound violation max(lower - g, g - upper, 0) -- bounds from the structure's score
 // record at kScoreOff (the row's 16-bit meta word, its (lower, upper) pair in the 2-KB head), exactly as score_kernel --

@@ -69,6 +69,8 @@ TWR_DEV uint64_t slots_of(const uint16_t cand[12]) {
   for (int c = 0; c < 12; ++c) s |= (uint64_t)(cand[c] & 0xF) << (4 * c);
   return s;
 }
+// the three slots (one per dimension, 12 bits) of node value j from the two dwords of such a word
+TWR_DEV uint32_t slots12(uint32_t lo, uint32_t hi, int j) { return (uint32_t)((((uint64_t)hi << 32) | lo) >> (12 * j)) & 0xFFFu; }
 
 // entry (r,d), r != d, of the cross-product matrix [v]x (single_rigid_body_dynamics.cc:46-57)
 template <int R, int D>
@@ -122,35 +124,6 @@ TWR_DEV void sincos_fast(double x, double* __restrict__ s, double* __restrict__ 
   *c = ((q + 1) & 2) ? -cc : cc;
 }
 
-// ZYX Euler rotation base->world (euler_converter.cc:207-221).
-struct Rot {
-  double R[3][3];
-  double sx, cx, sy, cy, sz, cz;
-};
-TWR_DEV void rotation(const double e[3], Rot& o) {
-  double sx, cx, sy, cy, sz, cz;
-  sincos_fast(e[0], &sx, &cx);
-  sincos_fast(e[1], &sy, &cy);
-  sincos_fast(e[2], &sz, &cz);
-  o.sx = sx; o.cx = cx; o.sy = sy; o.cy = cy; o.sz = sz; o.cz = cz;
-  o.R[0][0] = cy * cz; o.R[0][1] = cz * sx * sy - cx * sz; o.R[0][2] = sx * sz + cx * cz * sy;
-  o.R[1][0] = cy * sz; o.R[1][1] = cx * cz + sx * sy * sz; o.R[1][2] = cx * sy * sz - cz * sx;
-  o.R[2][0] = -sy;     o.R[2][1] = cy * sx;                o.R[2][2] = cx * cy;
-}
-TWR_DEV void matvec(const double A[3][3], const double v[3], double o[3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) o[i] = A[i][0] * v[0] + A[i][1] * v[1] + A[i][2] * v[2];
-}
-TWR_DEV void matTvec(const double A[3][3], const double v[3], double o[3]) {
-#pragma unroll
-  for (int i = 0; i < 3; ++i) o[i] = A[0][i] * v[0] + A[1][i] * v[1] + A[2][i] * v[2];
-}
-TWR_DEV void symmul(const double I[6], const double v[3], double o[3]) {  // I = (00,01,02,11,12,22)
-  o[0] = I[0] * v[0] + I[1] * v[1] + I[2] * v[2];
-  o[1] = I[1] * v[0] + I[3] * v[1] + I[4] * v[2];
-  o[2] = I[2] * v[0] + I[4] * v[1] + I[5] * v[2];
-}
-
 // ---------------------------------------------------------------- quad helpers
 // The dynamic kernel maps FOUR lanes to one time node (a "quad" = lanes 4i..4i+3); they exchange
 // scalars with DPP quad permutes (no LDS, no memory).
@@ -166,6 +139,44 @@ TWR_DEV double quad_sum(double v) {
   return v;
 }
 TWR_DEV double sel3(int i, double a, double b, double c) { return i == 0 ? a : (i == 1 ? b : c); }
+
+// ZYX Euler rotation base->world (euler_converter.cc:207-221).
+struct Rot {
+  double R[3][3];
+  double sx, cx, sy, cy, sz, cz;
+};
+TWR_DEV void rot_fill(double sx, double cx, double sy, double cy, double sz, double cz, Rot& o) {
+  o.sx = sx; o.cx = cx; o.sy = sy; o.cy = cy; o.sz = sz; o.cz = cz;
+  o.R[0][0] = cy * cz; o.R[0][1] = cz * sx * sy - cx * sz; o.R[0][2] = sx * sz + cx * cz * sy;
+  o.R[1][0] = cy * sz; o.R[1][1] = cx * cz + sx * sy * sz; o.R[1][2] = cx * sy * sz - cz * sx;
+  o.R[2][0] = -sy;     o.R[2][1] = cy * sx;                o.R[2][2] = cx * cy;
+}
+TWR_DEV void rotation(const double e[3], Rot& o) {
+  double sx, cx, sy, cy, sz, cz;
+  sincos_fast(e[0], &sx, &cx);
+  sincos_fast(e[1], &sy, &cy);
+  sincos_fast(e[2], &sz, &cz);
+  rot_fill(sx, cx, sy, cy, sz, cz, o);
+}
+// rotation() by the four lanes of a quad that hold the same e: lanes j = 0..2 evaluate one sincos each and broadcast it
+TWR_DEV void rotation_quad(int j, const double e[3], Rot& o) {
+  double my_s, my_c;
+  sincos_fast(sel3(j, e[0], e[1], e[2]), &my_s, &my_c);
+  rot_fill(quad_perm<0x00>(my_s), quad_perm<0x00>(my_c), quad_perm<0x55>(my_s), quad_perm<0x55>(my_c), quad_perm<0xAA>(my_s), quad_perm<0xAA>(my_c), o);
+}
+TWR_DEV void matvec(const double A[3][3], const double v[3], double o[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = A[i][0] * v[0] + A[i][1] * v[1] + A[i][2] * v[2];
+}
+TWR_DEV void matTvec(const double A[3][3], const double v[3], double o[3]) {
+#pragma unroll
+  for (int i = 0; i < 3; ++i) o[i] = A[0][i] * v[0] + A[1][i] * v[1] + A[2][i] * v[2];
+}
+TWR_DEV void symmul(const double I[6], const double v[3], double o[3]) {  // I = (00,01,02,11,12,22)
+  o[0] = I[0] * v[0] + I[1] * v[1] + I[2] * v[2];
+  o[1] = I[1] * v[0] + I[3] * v[1] + I[4] * v[2];
+  o[2] = I[2] * v[0] + I[4] * v[1] + I[5] * v[2];
+}
 
 // ---------------------------------------------------------------- optimised timings helpers
 // Spline::GetSegmentID + GetLocalTime (src/spline.cc:48-78) on durations that depend on x: the same

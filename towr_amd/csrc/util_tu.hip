@@ -1,0 +1,554 @@
+// Third translation unit of the kernels, plain flags: the utility kernels -- trajectory sampling, scoring from g, the planner's arg-min,
+// contact plan, nearest plane, TWR_EVAL_CHECK -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "launch.h"
+
+#include "kernels/common.h"
+#include "kernels/host_launch.h"
+#include "kernels/spline_math.h"
+#include "kernels/phase_durations.h"
+
+namespace twr {
+
+// ---------------------------------------------------------------- trajectory sampling
+// fpowr::GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53) for a batch of solutions: lane =
+// sample.  Durations (constants of the structure, or recomputed from x with optimised timings) go to LDS once
+// per workgroup; every lane accumulates its sample time like the reference (t += dt), locates the active
+// polynomial of every spline and evaluates position / velocity / acceleration in Hermite basis form.
+TWR_DEV void sample_spline(const double* __restrict__ xp, const PolyDesc& pd, double tl, double T, double p[3], double v[3],
+                           double a[3]) {
+  double X[12], nv[4][3], wp[4], wv[4], wa[4];
+  gather12c(xp, pd.xbase, pd.cand, X);
+  node_values(slots_of(pd.cand), meta_shared(pd.meta), X, nv);
+  hermite_all(tl, 1.0 / T, wp, wv, wa);
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    p[d] = wp[0] * nv[0][d] + wp[1] * nv[1][d] + wp[2] * nv[2][d] + wp[3] * nv[3][d];
+    v[d] = wv[0] * nv[0][d] + wv[1] * nv[1][d] + wv[2] * nv[2][d] + wv[3] * nv[3][d];
+    a[d] = wa[0] * nv[0][d] + wa[1] * nv[1][d] + wa[2] * nv[2][d] + wa[3] * nv[3][d];
+  }
+}
+// With `times` set the kernel is fpowr::ExtractInitialGuess (fpowr/include/fpowr/initial_guess_extractor.h:17-34)
+// instead: sample s of every problem is taken at times[s] and the record is [ t | state: base-lin p, base-ang p (Euler
+// angles), base-lin v, base-ang v (Euler rates) | controls (36): ee-motion acceleration of ee i at 3 i, twelve zeros
+// ("joint torques"), ee-force of ee i at 24 + 3 i ] = 49 doubles.
+__global__ __launch_bounds__(64) void sample_kernel(const SampleWork* __restrict__ work, const double* __restrict__ x,
+                                                    double* __restrict__ out, double dt, const double* __restrict__ times) {
+  __shared__ double s_bd[2 * kMaxPhasePolys], s_ph[kMaxEE][TWR_MAX_PHASES_DEV], s_md[kMaxEE][kMaxPhasePolys],
+      s_fd[kMaxEE][kMaxPhasePolys];
+  const SampleWork sw = work[blockIdx.x];
+  const char* blob = reinterpret_cast<const char*>(sw.blob);
+  const DevStruct* H = reinterpret_cast<const DevStruct*>(blob);
+  const SampleTables* ST = tbl<SampleTables>(blob, H->o_sample);
+  const double* xp = x + sw.x_off;
+  const int lane = threadIdx.x, n_ee = H->n_ee;
+  for (int q = lane; q < ST->n_base; q += 64) s_bd[q] = tbl<double>(blob, ST->o_bdur)[q];
+  for (int e = 0; e < n_ee; ++e) {
+    if (H->timings) {  // PhaseDurations::SetVariables + ConvertPhaseToPolyDurations (phase_durations.cc:77-103)
+      const PhaseTables* PT = tbl<PhaseTables>(blob, H->o_phase);
+      phase_poly_durations_wave(PT, blob, xp, e, s_ph[e], s_md[e], lane);
+      const PhasePoly* fp = tbl<PhasePoly>(blob, PT->o_fpoly[e]);
+      for (int q = lane; q < PT->n_fpoly[e]; q += 64) s_fd[e][q] = s_ph[e][fp[q].phase] / fp[q].n_in_phase;
+    } else {
+      for (int q = lane; q < ST->n_phases[e]; q += 64) s_ph[e][q] = tbl<double>(blob, ST->o_phdur[e])[q];
+      for (int q = lane; q < ST->n_mpoly[e]; q += 64) s_md[e][q] = tbl<double>(blob, ST->o_mdur[e])[q];
+      for (int q = lane; q < ST->n_fpoly[e]; q += 64) s_fd[e][q] = tbl<double>(blob, ST->o_fdur[e])[q];
+    }
+  }
+  __syncthreads();
+  if (lane >= sw.cnt) return;
+  const int s_idx = sw.s0 + lane;
+  double t = 0.0;
+  if (times) t = times[s_idx];
+  else for (int i = 0; i < s_idx; ++i) t += dt;   // the reference's accumulated sample time
+  const int rec = times ? 49 : 20 + 13 * n_ee;
+  double* o = out + sw.out_off + (int64_t)s_idx * rec;
+  o[0] = t;
+  // base-lin / base-ang (NodesVariablesAll: [p0 v0 p1 v1] x 3 of polynomial q at 6 q)
+  double tl;
+  const int qb = locate_segment(s_bd, ST->n_base, t, tl);
+  double wp[4], wv[4], wa[4];
+  hermite_all(tl, 1.0 / s_bd[qb], wp, wv, wa);
+  const double* xl = xp + ST->off_lin + 6 * qb;
+  const double* xa = xp + ST->off_ang + 6 * qb;
+  double e3[3], ed[3], edd[3];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    o[1 + d] = wp[0] * xl[d] + wp[1] * xl[3 + d] + wp[2] * xl[6 + d] + wp[3] * xl[9 + d];
+    o[4 + d] = wv[0] * xl[d] + wv[1] * xl[3 + d] + wv[2] * xl[6 + d] + wv[3] * xl[9 + d];
+    o[7 + d] = wa[0] * xl[d] + wa[1] * xl[3 + d] + wa[2] * xl[6 + d] + wa[3] * xl[9 + d];
+    e3[d] = wp[0] * xa[d] + wp[1] * xa[3 + d] + wp[2] * xa[6 + d] + wp[3] * xa[9 + d];
+    ed[d] = wv[0] * xa[d] + wv[1] * xa[3 + d] + wv[2] * xa[6 + d] + wv[3] * xa[9 + d];
+    edd[d] = wa[0] * xa[d] + wa[1] * xa[3 + d] + wa[2] * xa[6 + d] + wa[3] * xa[9 + d];
+  }
+  if (times) {   // ExtractInitialGuess record
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+      const double lv = o[4 + d];
+      o[4 + d] = e3[d];
+      o[7 + d] = lv;
+      o[10 + d] = ed[d];
+    }
+    for (int q = 13; q < 49; ++q) o[q] = 0.0;
+    for (int e = 0; e < n_ee; ++e) {
+      double tlm, tlf, p[3], v[3], a[3];
+      const int qm = locate_segment(s_md[e], ST->n_mpoly[e], t, tlm);
+      const int qf = locate_segment(s_fd[e], ST->n_fpoly[e], t, tlf);
+      sample_spline(xp, tbl<PolyDesc>(blob, ST->o_mdesc[e])[qm], tlm, s_md[e][qm], p, v, a);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) o[13 + 3 * e + d] = a[d];
+      sample_spline(xp, tbl<PolyDesc>(blob, ST->o_fdesc[e])[qf], tlf, s_fd[e][qf], p, v, a);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) o[37 + 3 * e + d] = p[d];
+    }
+    return;
+  }
+  Rot ro;
+  rotation(e3, ro);
+  {  // Eigen::Quaterniond(R) (euler_converter.cc:51-56; Eigen 3.3 Quaternion.h, quaternionbase_assign_impl)
+    const double (&m)[3][3] = ro.R;
+    double q[4];  // x y z w
+    double tr = m[0][0] + m[1][1] + m[2][2];
+    if (tr > 0) {
+      tr = sqrt(tr + 1.0);
+      q[3] = 0.5 * tr;
+      tr = 0.5 / tr;
+      q[0] = (m[2][1] - m[1][2]) * tr;
+      q[1] = (m[0][2] - m[2][0]) * tr;
+      q[2] = (m[1][0] - m[0][1]) * tr;
+    } else {
+      int i = 0;
+      if (m[1][1] > m[0][0]) i = 1;
+      if (m[2][2] > (i == 0 ? m[0][0] : m[1][1])) i = 2;
+      const int j = (i + 1) % 3, k = (j + 1) % 3;
+      auto M = [&](int r, int c) { return sel3(r, sel3(c, m[0][0], m[0][1], m[0][2]), sel3(c, m[1][0], m[1][1], m[1][2]),
+                                               sel3(c, m[2][0], m[2][1], m[2][2])); };
+      tr = sqrt(M(i, i) - M(j, j) - M(k, k) + 1.0);
+      const double qi = 0.5 * tr;
+      tr = 0.5 / tr;
+      const double qw = (M(k, j) - M(j, k)) * tr, qj = (M(j, i) + M(i, j)) * tr, qk = (M(k, i) + M(i, k)) * tr;
+      q[3] = qw;
+      q[0] = i == 0 ? qi : (j == 0 ? qj : qk);
+      q[1] = i == 1 ? qi : (j == 1 ? qj : qk);
+      q[2] = i == 2 ? qi : (j == 2 ? qj : qk);
+    }
+    o[10] = q[3]; o[11] = q[0]; o[12] = q[1]; o[13] = q[2];
+  }
+  {  // omega = M edot, omega_dot = Mdot edot + M eddot (euler_converter.cc:58-83,133-166)
+    const double sy = ro.sy, cy = ro.cy, sz = ro.sz, cz = ro.cz;
+    const double xd = ed[0], yd = ed[1], zd = ed[2];
+    const double Mx[3] = {cy * cz, cy * sz, -sy}, My[3] = {-sz, cz, 0.0};
+    const double Mdx[3] = {-cz * sy * yd - cy * sz * zd, cy * cz * zd - sy * sz * yd, -cy * yd};
+    const double Mdy[3] = {-cz * zd, -sz * zd, 0.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      o[14 + i] = Mx[i] * xd + My[i] * yd + (i == 2 ? zd : 0.0);
+      o[17 + i] = Mdx[i] * xd + Mdy[i] * yd + Mx[i] * edd[0] + My[i] * edd[1] + (i == 2 ? edd[2] : 0.0);
+    }
+  }
+  for (int e = 0; e < n_ee; ++e) {
+    double* oe = o + 20 + 13 * e;
+    double tlp, tlm, tlf;
+    const int phase = locate_segment(s_ph[e], ST->n_phases[e], t, tlp);   // PhaseDurations::IsContactPhase
+    oe[0] = ((phase & 1) == 0) == (ST->contact0[e] != 0) ? 1.0 : 0.0;
+    const int qm = locate_segment(s_md[e], ST->n_mpoly[e], t, tlm);
+    const int qf = locate_segment(s_fd[e], ST->n_fpoly[e], t, tlf);
+    const PolyDesc pm = tbl<PolyDesc>(blob, ST->o_mdesc[e])[qm];
+    const PolyDesc pf = tbl<PolyDesc>(blob, ST->o_fdesc[e])[qf];
+    double p[3], v[3], a[3];
+    sample_spline(xp, pm, tlm, s_md[e][qm], p, v, a);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) { oe[1 + d] = p[d]; oe[4 + d] = v[d]; oe[7 + d] = a[d]; }
+    sample_spline(xp, pf, tlf, s_fd[e][qf], p, v, a);
+#pragma unroll
+    for (int d = 0; d < 3; ++d) oe[10 + d] = p[d];
+  }
+}
+hipError_t launch_sample(const SampleWork* work, int n_work, const double* x, double* out, double dt, const double* times,
+                         hipStream_t stream) {
+  if (n_work <= 0) return hipSuccess;
+  return twr_launch(sample_kernel, dim3(n_work), dim3(64), 0, stream, work, x, out, dt, times);
+}
+
+// ---------------------------------------------------------------- candidate scoring
+// twr_batch_score: per problem and constraint family the inf- and 1-norm of the bound violation
+// max(lower - g, g - upper, 0) over the family's rows (bounds of ConstraintSet::GetBounds, twr_structure_bounds).
+// A sweep then returns 16 doubles per candidate instead of its Jacobian.
+// (round 5: 256 threads per problem, row r = 256 k + thread, sixteen rows per thread; family slot and bounds of a row come
+// from its 16-bit meta word and the structure's short table of distinct (lower, upper) pairs, device_tables.h ScoreTables.)
+// Two dependent round trips: (1) the work item and its successor (row count = difference of their g offsets; the list
+// carries an end entry), (2) the rows of g, the meta words of the rows AND the head of the score record (2 KB requested on spec:
+// the pair table) -> LDS -- the record sits at a fixed offset of the blob (kScoreOff), no field of the header is needed.  The slot of a thread's rows never falls, so it keeps one
+// running (max, sum) pair and hands it to its LDS cell when the slot moves on.  Round 4's kernel fetched a cold candidate's
+// fields one s_load at a time and 16 bytes of bounds per row: 25 us for 128 candidates, 43 us for 1024.
+__device__ __forceinline__ void best_of(double& v, int& i, double ov, int oi) {
+  if (ov < v || (ov == v && oi < i)) {
+    v = ov;
+    i = oi;
+  }
+}
+__global__ __launch_bounds__(256) void score_kernel(const NodeWork* __restrict__ work, const double* __restrict__ g,
+                                                    double* __restrict__ scores) {
+  constexpr int kHeadDwords = kScoreHeadBytes / 4, kTabDwords = (int)(sizeof(ScoreTables) / 4);
+  static_assert(kHeadDwords == 512 && kTabDwords + 4 * kScoreMaxPairs <= kHeadDwords, "the whole record within its head: two loads per thread");
+  __shared__ __attribute__((aligned(16))) int32_t s_tab[kHeadDwords];   // the record as in the blob
+  __shared__ double red[256 * 16 + 16 * 16];   // cell (2 slot + {max, sum}, thread), then the partial results of the fold
+  const int tid = threadIdx.x;
+  const NodeWork w = work[blockIdx.x];
+  const int n_rows = (int)(work[blockIdx.x + 1].g_off - w.g_off);
+  if (n_rows <= 0) {   // (uniform) a structure whose constraint sets have no rows: nothing is violated, nothing is read
+    if (tid < 16) scores[16 * (size_t)blockIdx.x + tid] = 0.0;
+    return;
+  }
+  const double* gp = g + w.g_off;
+  const char* blob = reinterpret_cast<const char*>(w.blob);
+#pragma unroll
+  for (int c = 0; c < 16; ++c) red[c * 256 + tid] = 0.0;   // (a cell is written at most once more; own cells only: no barrier)
+  int cur = 0;
+  double cm = 0.0, cs = 0.0;
+  for (int base = 0; base < n_rows; base += 16 * 256) {   // (one trip for structures of up to 4096 rows)
+    double v[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) v[k] = gp[min(base + 256 * k + tid, n_rows - 1)];
+    const int32_t* Tw = reinterpret_cast<const int32_t*>(tbl<ScoreTables>(blob, kScoreOff));   // (fixed offset: no header field)
+    const uint16_t* meta = reinterpret_cast<const uint16_t*>(blob + kScoreOff + kScoreHeadBytes);
+    uint32_t m[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) m[k] = meta[min(base + 256 * k + tid, n_rows - 1)];
+    if (base == 0) {
+      const int32_t a = Tw[tid], c = Tw[tid + 256];
+      s_tab[tid] = a;
+      s_tab[tid + 256] = c;
+      __syncthreads();
+    }
+    const double* s_pairs = reinterpret_cast<const double*>(s_tab + kTabDwords);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+      if (base + 256 * k < n_rows) {   // uniform
+        const bool live = base + 256 * k + tid < n_rows;
+        const int slot = (int)(m[k] >> 12), q = (int)(m[k] & 0xFFFu);
+        const double lo = s_pairs[2 * q], up = s_pairs[2 * q + 1], val = v[k];
+        // NaN-propagating: a non-finite constraint value makes the family's scores NaN instead of hiding in a max()
+        double viol = fmax(fmax(lo - val, val - up), 0.0);
+        if (val != val) viol = val;
+        if (live && slot != cur) {   // the slot moved on: hand over the running pair (rare: a few times per thread)
+          red[(2 * cur) * 256 + tid] = cm;
+          red[(2 * cur + 1) * 256 + tid] = cs;
+          cm = cs = 0.0;
+          cur = slot;
+        }
+        if (live) {
+          cm = nan_max(cm, viol);
+          cs += viol;
+        }
+      }
+    }
+  }
+  red[(2 * cur) * 256 + tid] = cm;
+  red[(2 * cur + 1) * 256 + tid] = cs;
+  // 256 threads x 16 cells -> 16 values, transposed: thread 16 c + j folds column j of threads c, c + 16, ..., then sixteen
+  // threads fold the sixteen partial results of their column and store it at its FAMILY's place
+  __syncthreads();
+  {
+    const int j = tid & 15, c = tid >> 4;   // column j (even: an inf-norm, odd: a 1-norm)
+    double acc = red[j * 256 + c];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) {
+      const double o = red[j * 256 + c + 16 * i];
+      acc = (j & 1) ? acc + o : nan_max(acc, o);
+    }
+    red[256 * 16 + c * 16 + j] = acc;
+  }
+  __syncthreads();
+  if (tid < 16) {
+    const int slot = reinterpret_cast<const int8_t*>(s_tab + 2)[tid >> 1];   // ScoreTables::slot_of_family[family tid / 2]
+    double acc = 0.0;
+    if (slot >= 0) {
+      const int j = 2 * slot + (tid & 1);
+      acc = red[256 * 16 + j];
+      for (int c = 1; c < 16; ++c) {
+        const double o = red[256 * 16 + c * 16 + j];
+        acc = (tid & 1) ? acc + o : nan_max(acc, o);
+      }
+    }
+    scores[16 * (size_t)blockIdx.x + tid] = acc;
+  }
+}
+hipError_t launch_score(const NodeWork* work, int n_problems, const double* g, double* scores, hipStream_t stream) {
+  return twr_launch(score_kernel, dim3(n_problems), dim3(256), 0, stream, work, g, scores);
+}
+
+// twr_batch_best: the planner's decision on the device -- arg-min over a score table of the summed inf-norm violations of
+// the chosen constraint families (the table may be longer than this batch: after an all-gather it holds the candidates of
+// every rank).  Same rule as towr_amd.dist.best_candidate: families summed in ascending order, NaN loses, first index wins
+// a tie.  One launch: every block reduces its stride of candidates, the last block to finish reduces the blocks' results
+// (threadfence + counter, reset for the next call) and writes best[0] = index, best[1] = its total.
+__global__ __launch_bounds__(256) void best_kernel(const double* __restrict__ scores, int n, unsigned families, double* __restrict__ partial,
+                                                   unsigned* __restrict__ counter, double* __restrict__ best, double index_offset) {
+  __shared__ double s_v[4];
+  __shared__ int s_i[4];
+  __shared__ bool s_last;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  double bv = __builtin_inf();
+  int bi = 0x7fffffff;
+  for (int c = blockIdx.x * 256 + tid; c < n; c += gridDim.x * 256) {
+    const double* row = scores + 16 * (size_t)c;
+    double t = 0.0;
+    bool first = true;
+#pragma unroll
+    for (int f = 0; f < 8; ++f)
+      if (families >> f & 1u) {
+        t = first ? row[2 * f] : t + row[2 * f];
+        first = false;
+      }
+    if (t != t) t = __builtin_inf();
+    best_of(bv, bi, t, c);
+  }
+  auto block_reduce = [&]() {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) best_of(bv, bi, __shfl_xor(bv, o), __shfl_xor(bi, o));
+    if (lane == 0) {
+      s_v[wave] = bv;
+      s_i[wave] = bi;
+    }
+    __syncthreads();
+    if (tid == 0)
+      for (int w = 1; w < 4; ++w) best_of(bv, bi, s_v[w], s_i[w]);
+  };
+  block_reduce();
+  if (tid == 0) {
+    partial[2 * blockIdx.x] = bv;
+    partial[2 * blockIdx.x + 1] = (double)bi;
+    __threadfence();
+    s_last = atomicAdd(counter, 1u) == gridDim.x - 1;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  bv = __builtin_inf();
+  bi = 0x7fffffff;
+  for (int k = tid; k < (int)gridDim.x; k += 256)
+    best_of(bv, bi, __builtin_nontemporal_load(partial + 2 * k), (int)__builtin_nontemporal_load(partial + 2 * k + 1));
+  __syncthreads();
+  block_reduce();
+  if (tid == 0) {
+    best[0] = index_offset + (double)(bi == 0x7fffffff ? 0 : bi);
+    best[1] = bv;
+    *counter = 0u;
+  }
+}
+int best_max_blocks() { return 256; }
+hipError_t launch_best(const double* scores, int n, unsigned families, double* partial, unsigned* counter, double* best, double index_offset,
+                       hipStream_t stream) {
+  int blocks = (n + 1023) / 1024;   // >= four candidates per thread before another block pays
+  blocks = blocks < 1 ? 1 : (blocks > best_max_blocks() ? best_max_blocks() : blocks);
+  return twr_launch(best_kernel, dim3(blocks), dim3(256), 0, stream, scores, n, families, partial, counter, best, index_offset);
+}
+
+// ---------------------------------------------------------------- contact plan
+// fpowr::ExtractFootstepPlan (fpowr/include/fpowr/footstep_plan_extractor.h:69-133) minus the nearest-plane lookup
+// (boost::geometry over ROS messages, left to the caller): the solution is sampled every dt like GetTrajectory
+// (t accumulated), a footstep state is the first sample and every sample whose contact flags differ from the
+// previous sample's (HasEndEffectorContactChanged, :55-67); its duration is the time to the next footstep state, the
+// last one lasts until time_horizon (:121-128).  One wave per problem, lane = sample, 64 samples per round, footstep
+// states compacted with a ballot.  Record: [ t | duration | contact per ee | ee-motion position (3) per ee ].
+__global__ __launch_bounds__(64) void contact_plan_kernel(const NodeWork* __restrict__ work, const double* __restrict__ x,
+                                                          double* __restrict__ out, int32_t* __restrict__ counts, double dt,
+                                                          double time_horizon, int n_samples_max, int max_steps) {
+  __shared__ double s_ph[kMaxEE][TWR_MAX_PHASES_DEV], s_md[kMaxEE][kMaxPhasePolys];
+  const NodeWork w = work[blockIdx.x];
+  const char* blob = reinterpret_cast<const char*>(w.blob);
+  const DevStruct* H = reinterpret_cast<const DevStruct*>(blob);
+  const SampleTables* ST = tbl<SampleTables>(blob, H->o_sample);
+  const double* xp = x + w.x_off;
+  const int lane = threadIdx.x, n_ee = H->n_ee;
+  for (int e = 0; e < n_ee; ++e) {
+    if (H->timings) {  // PhaseDurations::SetVariables + ConvertPhaseToPolyDurations (phase_durations.cc:77-103)
+      phase_poly_durations_wave(tbl<PhaseTables>(blob, H->o_phase), blob, xp, e, s_ph[e], s_md[e], lane);
+    } else {
+      for (int q = lane; q < ST->n_phases[e]; q += 64) s_ph[e][q] = tbl<double>(blob, ST->o_phdur[e])[q];
+      for (int q = lane; q < ST->n_mpoly[e]; q += 64) s_md[e][q] = tbl<double>(blob, ST->o_mdur[e])[q];
+    }
+  }
+  __syncthreads();
+  // GetTrajectory: while (t <= T + 1e-5) { ...; t += dt; }
+  const double T = ST->t_total;
+  const int rec = 2 + 4 * n_ee;
+  double* o = out + (size_t)blockIdx.x * (size_t)max_steps * rec;
+  int n_steps = 0;          // wave-uniform
+  double t_carry = 0.0;     // t of the last footstep state of the previous round (wave-uniform)
+  for (int s0 = 0; s0 < n_samples_max; s0 += 64) {
+    const int s_idx = s0 + lane;
+    double t = 0.0, tq = 0.0;   // this sample's and the previous sample's accumulated time (t += dt, like the reference)
+    for (int i = 0; i < s_idx; ++i) {
+      tq = t;
+      t += dt;
+    }
+    const bool live = t <= T + 1e-5;
+    unsigned mask = 0, mask_prev = 0;
+    for (int e = 0; e < n_ee; ++e) {  // PhaseDurations::IsContactPhase (phase_durations.cc:118-124)
+      double tl;
+      const int ph = locate_segment(s_ph[e], ST->n_phases[e], t, tl);
+      mask |= ((((ph & 1) == 0) == (ST->contact0[e] != 0)) ? 1u : 0u) << e;
+      const int pq = locate_segment(s_ph[e], ST->n_phases[e], tq, tl);
+      mask_prev |= ((((pq & 1) == 0) == (ST->contact0[e] != 0)) ? 1u : 0u) << e;
+    }
+    const bool step = live && (s_idx == 0 || mask != mask_prev);
+    const uint64_t ball = __ballot(step);
+    if (ball == 0) {
+      if (!__any(live)) break;
+      continue;
+    }
+    const uint64_t below = ball & ((1ull << lane) - 1ull);
+    const uint64_t above = lane == 63 ? 0ull : (ball >> (lane + 1));
+    const int my = n_steps + __popcll(below);
+    // time of the footstep state before this one: the closest step lane below, or the previous round's last
+    const double t_below = __shfl(t, below ? 63 - __clzll(below) : lane);
+    const double t_prev = below ? t_below : t_carry;
+    if (step && my < max_steps) {
+      double* r = o + (size_t)my * rec;
+      r[0] = t;
+      if (!above) r[1] = time_horizon - t;   // last footstep state so far (:125-127); a later round may close it
+      for (int e = 0; e < n_ee; ++e) {
+        r[2 + e] = (mask >> e) & 1u ? 1.0 : 0.0;
+        double tlm;
+        const int qm = locate_segment(s_md[e], ST->n_mpoly[e], t, tlm);
+        const PolyDesc pm = tbl<PolyDesc>(blob, ST->o_mdesc[e])[qm];
+        double p[3], v[3], a[3];
+        sample_spline(xp, pm, tlm, s_md[e][qm], p, v, a);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) r[2 + n_ee + 3 * e + d] = p[d];
+      }
+    }
+    // duration of the state before (:121-123) -- also when THIS state no longer fits the output (my == max_steps): the
+    // last record that was kept still gets its duration
+    if (step && my > 0 && my - 1 < max_steps) o[(size_t)(my - 1) * rec + 1] = t - t_prev;
+    t_carry = __shfl(t, 63 - __clzll(ball));
+    n_steps += __popcll(ball);
+  }
+  if (lane == 0) counts[blockIdx.x] = n_steps;
+}
+hipError_t launch_contact_plan(const NodeWork* work, int n_problems, const double* x, double* out, int32_t* counts, double dt,
+                               double time_horizon, int n_samples_max, int max_steps, hipStream_t stream) {
+  return twr_launch(contact_plan_kernel, dim3(n_problems), dim3(64), 0, stream, work, x, out, counts, dt, time_horizon,
+                    n_samples_max, max_steps);
+}
+
+// ---------------------------------------------------------------- nearest plane of a footstep
+// fpowr::NearestPlaneLookup::GetNearestPlaneIndex (nearest_plane_lookup.h:62-84) for every (problem, footstep state,
+// end-effector) of a contact plan: boost::geometry::distance(point, polygon) restated from Boost 1.71 (winding
+// strategy for covered_by, projected-point distance to the ring's consecutive points, no closing edge added; exact
+// coordinate comparisons where boost allows a few ulp).  One thread per foot, polygons read from global memory.
+TWR_DEV int ring_side(const double* __restrict__ xy, int n, double px, double py) {   // 1 inside, 0 boundary, -1 outside
+  if (n < 4) return -1;
+  int count = 0;
+  for (int i = 0; i + 1 < n; ++i) {
+    const double s1x = xy[2 * i], s1y = xy[2 * i + 1], s2x = xy[2 * i + 2], s2y = xy[2 * i + 3];
+    const bool eq1 = s1x == px, eq2 = s2x == px;
+    int c = 0;
+    if (eq1 && eq2) {
+      if ((s1y <= py && s2y >= py) || (s2y <= py && s1y >= py)) return 0;
+    } else {
+      c = eq1 ? (s2x > px ? 1 : -1) : eq2 ? (s1x > px ? -1 : 1) : (s1x < px && s2x > px) ? 2 : (s2x < px && s1x > px) ? -2 : 0;
+    }
+    if (c != 0) {
+      int side;
+      if (c == 1 || c == -1) {
+        const double sey = eq1 ? s1y : s2y;
+        side = py == sey ? 0 : (py < sey ? -c : c);
+      } else {
+        // (no FMA contraction: the sign of a tiny determinant must not depend on it)
+        const double det = __dsub_rn(__dmul_rn(s2x - s1x, py - s1y), __dmul_rn(s2y - s1y, px - s1x));
+        side = det > 0 ? 1 : (det < 0 ? -1 : 0);
+      }
+      if (side == 0) return 0;
+      if (side * c > 0) count += c;
+    }
+  }
+  return count == 0 ? -1 : 1;
+}
+TWR_DEV double ring_distance(const double* __restrict__ xy, int n, double px, double py) {
+  if (n == 0) return 0.0;
+  auto comparable = [&](double ax, double ay, double bx, double by) {
+    const double vx = bx - ax, vy = by - ay, wx = px - ax, wy = py - ay;
+    const double c1 = __dadd_rn(__dmul_rn(wx, vx), __dmul_rn(wy, vy));
+    if (c1 <= 0) return __dadd_rn(__dmul_rn(wx, wx), __dmul_rn(wy, wy));
+    const double c2 = __dadd_rn(__dmul_rn(vx, vx), __dmul_rn(vy, vy));
+    if (c2 <= c1) return __dadd_rn(__dmul_rn(px - bx, px - bx), __dmul_rn(py - by, py - by));
+    const double b = c1 / c2, qx = __dadd_rn(ax, __dmul_rn(b, vx)), qy = __dadd_rn(ay, __dmul_rn(b, vy));
+    return __dadd_rn(__dmul_rn(px - qx, px - qx), __dmul_rn(py - qy, py - qy));
+  };
+  if (n == 1) return sqrt(comparable(xy[0], xy[1], xy[0], xy[1]));
+  double best = comparable(xy[0], xy[1], xy[2], xy[3]);
+  for (int i = 0; i + 1 < n; ++i) {
+    const double c = comparable(xy[2 * i], xy[2 * i + 1], xy[2 * i + 2], xy[2 * i + 3]);
+    if (c == 0.0) return 0.0;
+    if (c < best) best = c;
+  }
+  return sqrt(best);
+}
+__global__ __launch_bounds__(256) void plane_kernel(const double* __restrict__ plan, const int32_t* __restrict__ counts,
+                                                    const double* __restrict__ poly_xy, const int32_t* __restrict__ poly_start,
+                                                    int n_polys, int n_problems, int max_steps, int n_ee,
+                                                    int32_t* __restrict__ plane_index) {
+  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (int64_t)n_problems * max_steps * n_ee) return;
+  const int e = (int)(id % n_ee), s = (int)((id / n_ee) % max_steps), p = (int)(id / ((int64_t)n_ee * max_steps));
+  const double* rec = plan + ((int64_t)p * max_steps + s) * (2 + 4 * n_ee);
+  int nearest = -1;
+  if (s < counts[p] && rec[2 + e] != 0.0) {
+    const double px = rec[2 + n_ee + 3 * e], py = rec[2 + n_ee + 3 * e + 1];
+    double min_distance = 1.7976931348623157e308;
+    for (int i = 0; i < n_polys; ++i) {
+      const double* xy = poly_xy + 2 * poly_start[i];
+      const int n = poly_start[i + 1] - poly_start[i];
+      const double distance = ring_side(xy, n, px, py) >= 0 ? 0.0 : ring_distance(xy, n, px, py);
+      if (distance < min_distance) {
+        min_distance = distance;
+        nearest = i;
+      }
+    }
+  }
+  plane_index[id] = nearest;
+}
+hipError_t launch_planes(const double* plan, const int32_t* counts, const double* poly_xy, const int32_t* poly_start, int n_polys,
+                         int n_problems, int max_steps, int n_ee, int32_t* plane_index, hipStream_t stream) {
+  const int64_t n = (int64_t)n_problems * max_steps * n_ee;
+  if (n <= 0) return hipSuccess;
+  return twr_launch(plane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, plan, counts, poly_xy, poly_start, n_polys,
+                    n_problems, max_steps, n_ee, plane_index);
+}
+
+// ---------------------------------------------------------------- TWR_EVAL_CHECK
+// Per-problem non-finite flags (failure detection): a separate pass over the outputs of one
+// evaluation, off the hot path (it re-reads g and jac once).  status[p] |= 1 if a constraint value of problem p is
+// NaN/Inf, |= 2 if a Jacobian value is.  Sixteen workgroups per problem, each scanning a contiguous share.
+constexpr int kCheckParts = 16;
+TWR_DEV bool non_finite(double v) { return (__double2hiint(v) & 0x7ff00000) == 0x7ff00000; }
+__global__ __launch_bounds__(256) void check_kernel(const int64_t* __restrict__ g_off, const int64_t* __restrict__ j_off,
+                                                    const double* __restrict__ g, const double* __restrict__ jac,
+                                                    int32_t* __restrict__ status, int flags) {
+  const int p = blockIdx.x / kCheckParts, part = blockIdx.x % kCheckParts;
+  int bad = 0;
+  if (flags & 1) {
+    const int64_t a = g_off[p], n = g_off[p + 1] - a;
+    const int64_t lo = a + n * part / kCheckParts, hi = a + n * (part + 1) / kCheckParts;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) bad |= non_finite(g[i]) ? 1 : 0;
+  }
+  if (flags & 2) {
+    const int64_t a = j_off[p], n = j_off[p + 1] - a;
+    const int64_t lo = a + n * part / kCheckParts, hi = a + n * (part + 1) / kCheckParts;
+    for (int64_t i = lo + threadIdx.x; i < hi; i += 256) bad |= non_finite(jac[i]) ? 2 : 0;
+  }
+  if (bad) atomicOr(&status[p], bad);
+}
+hipError_t launch_check(int n_problems, const int64_t* g_off, const int64_t* j_off, const double* g, const double* jac,
+                        int32_t* status, int flags, hipStream_t stream) {
+  hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)n_problems, stream);
+  if (e != hipSuccess) return e;
+  return twr_launch(check_kernel, dim3(n_problems * kCheckParts), dim3(256), 0, stream, g_off, j_off, g, jac, status, flags);
+}
+
+}  // namespace twr
