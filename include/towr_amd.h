@@ -695,7 +695,7 @@ int twr_jac_lm_state(twr_jac_lm* lm, double* d_out /* TWR_JAC_LM_REC * n_problem
  *                             as it stood: 1 for a bad mu or c with a finite |s0|, or where N holds a NaN (the first delta),
  *                             NaN where |s0| itself is not finite.  One launch whose shape depends on the batch alone;
  *                             one workgroup per problem, which ends when its problem stops.  The solve multiplies, then adds
- *                             (no fused multiply-add), every sum in a stated order (jac_gram.hip): scripts/gram_cpu.py
+ *                             (no fused multiply-add), every sum in a stated order (jac/gram.h): scripts/gram_cpu.py
  *                             gram_cg_device restates it in numpy bit for bit, the iteration counts included. */
 int twr_structure_gram_pattern(const twr_structure* s, int32_t* row_ptr /* n + 1 */, int32_t* col_idx, int64_t* nnz);
 int twr_jac_ops_reserve_gram(twr_jac_ops* ops);

@@ -7,7 +7,7 @@ import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 SRC = os.path.join(ROOT, "towr_amd", "csrc")
-OTHER_OBJ = ["rom_tu.o", "util_tu.o", "structure.o", "presets.o", "batch_plan.o", "eval_plan.o", "jac_plan.o", "capi.o", "capi_jac.o"]
+OTHER_OBJ = ["rom_tu.o", "util_tu.o", "jac_tu.o", "structure.o", "presets.o", "batch_plan.o", "eval_plan.o", "jac_plan.o", "capi.o", "capi_jac.o"]
 UNIT_END = "\n}  // namespace twr\n"
 
 

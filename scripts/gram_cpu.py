@@ -69,7 +69,7 @@ def gram_cg(N, z, mu, c, iters, tol):
     return k, np.where(free, c * e, 0.0), np.sqrt(gam / g0) if g0 > 0 else 0.0, status
 
 
-ROW_LANES, THREADS, WAVE = 16, 256, 64   # kGramRowLanes, kGramThreads and the wave of jac_gram.hip
+ROW_LANES, THREADS, WAVE = 16, 256, 64   # kGramRowLanes, kGramThreads and the wave of jac/gram.h
 
 
 def _butterfly(a, width):
@@ -83,7 +83,7 @@ def _butterfly(a, width):
 
 
 def _block_sum(terms):
-    """lsq_sum of jac_lsq.hip over the per-element terms of a vector: lane t adds the terms t, t + 256, ... in index order, a
+    """lsq_sum of jac/lsq.h over the per-element terms of a vector: lane t adds the terms t, t + 256, ... in index order, a
     butterfly over each wave of 64 lanes, then the four waves' sums in wave order."""
     n = terms.size
     rounds = max(1, -(-n // THREADS))
@@ -100,7 +100,7 @@ def _block_sum(terms):
 
 
 class _RowProduct:
-    """gram_row_dot of jac_gram.hip for every row of N at once: lane l of a row's 16 adds the products l, l + 16, ... in column
+    """gram_row_dot of jac/gram.h for every row of N at once: lane l of a row's 16 adds the products l, l + 16, ... in column
     order (multiply, then add), then a butterfly over the 16 lanes."""
 
     def __init__(self, N):

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Instruction mix of the largest loop of one kernel in towr_amd/csrc/kernels.s (`make -C towr_amd/csrc asm`, which also
-writes rom_tu.s, the unit of rom_kernel, and util_tu.s, the unit of the utility kernels: name that file as an argument).
-usage: isa_mix.py <mangled-name-substring> [top] [--whole] [towr_amd/csrc/rom_tu.s | towr_amd/csrc/util_tu.s]"""
+writes rom_tu.s, the unit of rom_kernel, util_tu.s, the unit of the utility kernels, and jac_tu.s, the unit of the Jacobian solver
+kernels: name that file as an argument).
+usage: isa_mix.py <mangled-name-substring> [top] [--whole] [towr_amd/csrc/rom_tu.s | towr_amd/csrc/util_tu.s | towr_amd/csrc/jac_tu.s]"""
 import collections
 import re
 import sys

@@ -1,9 +1,10 @@
 """Register / scratch usage of every kernel of a HIP source (device-only compile with -Rpass-analysis=kernel-resource-usage).
 Usage: python scripts/kernel_resources.py [filter-substring] [source] [extra hipcc flags ...]
 The default source is kernels.hip, the unit of every evaluation kernel but rom_kernel; for the rom unit, with its own
-scheduler flag, and for the utility kernels (sampling, scoring from g, best, contact plan, planes, check):
+scheduler flag, for the utility kernels (sampling, scoring from g, best, contact plan, planes, check) and for the Jacobian solver kernels:
   python scripts/kernel_resources.py rom towr_amd/csrc/rom_tu.hip -mllvm -amdgpu-sched-strategy=max-memory-clause
-  python scripts/kernel_resources.py "" towr_amd/csrc/util_tu.hip"""
+  python scripts/kernel_resources.py "" towr_amd/csrc/util_tu.hip
+  python scripts/kernel_resources.py "" towr_amd/csrc/jac_tu.hip"""
 import re, subprocess, sys
 flt = sys.argv[1] if len(sys.argv) > 1 else ""
 src = sys.argv[2] if len(sys.argv) > 2 else "towr_amd/csrc/kernels.hip"

@@ -55,7 +55,7 @@ def case_bounds(case, goal_x=1.0):
 
 
 def v0(n):
-    """The start vector of the driver's power iteration (lm_v0, jac_lm.hip): a fixed pattern in [0.5, 1.5)."""
+    """The start vector of the driver's power iteration (lm_v0, jac/lm.h): a fixed pattern in [0.5, 1.5)."""
     h = (np.arange(n, dtype=np.uint64) * np.uint64(2654435761) + np.uint64(0x9e3779b9)) & np.uint64(0xffffffff)
     h ^= h >> np.uint64(15)
     h = (h * np.uint64(0x85ebca6b)) & np.uint64(0xffffffff)

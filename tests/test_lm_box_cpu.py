@@ -39,7 +39,7 @@ def _run(name, seed, bounded):
 
 
 def test_start_vector_is_the_drivers():
-    """lm_v0 of jac_lm.hip in plain integers."""
+    """lm_v0 of jac/lm.h in plain integers."""
     def ref(k):
         h = (k * 2654435761 + 0x9e3779b9) & 0xffffffff
         h ^= h >> 15

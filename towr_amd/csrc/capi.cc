@@ -1,5 +1,5 @@
 // C ABI of libtowr_amd.so (see include/towr_amd.h), the batch runtime: structures, batches, their evaluation, sampling,
-// planes and scoring; error reporting.  The Jacobian linear algebra (twr_jac_*) is capi_jac.cc, which alone includes jac_*.hip.
+// planes and scoring; error reporting.  The Jacobian linear algebra (twr_jac_*) is capi_jac.cc, on the launchers of jac_tu.hip (jac_launch.h).
 #include <atomic>
 #include <cmath>
 #include <cstddef>

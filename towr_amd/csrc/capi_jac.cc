@@ -1,15 +1,11 @@
 // C ABI of libtowr_amd.so (see include/towr_amd.h), the Jacobian linear algebra: the products with J (twr_jac_ops), the damped
-// least-squares solves (twr_jac_lsq) and the bounded LM driver (twr_jac_lm).  The only unit that includes jac_*.hip: they define
-// kernels, so a second includer would define them twice.  Of a batch it uses twr_batch_eval and the layout alone.
+// least-squares solves (twr_jac_lsq) and the bounded LM driver (twr_jac_lm).  Host code: the handles, the argument checks and the
+// order of calls; every launch is a function of jac_tu.hip (jac_launch.h).  Of a batch it uses twr_batch_eval and the layout alone.
 #include <cmath>
 #include <cstring>
 
-#include "jac_gram.hip"
-#include "jac_lm.hip"
-#include "jac_lsq.hip"
-#include "jac_products.hip"
 #include "capi_internal.h"
-#include "jac_plan.h"
+#include "jac_launch.h"
 
 struct twr_jac_ops {   // twr::PlanJacOps's tables and work lists on the device, and the slab of J^T w's partials
   int device = 0, n_problems = 0;
@@ -81,25 +77,12 @@ struct twr_jac_lm {   // the bounded LM driver: twr::PlanJacLm's workspace, and 
 
 namespace {
 
-// A handle's products with one J on one stream: what the entry points launch, and the J the solves of jac_lsq.hip are given
-struct JacProducts {
-  const twr_jac_ops* ops;
-  const double* jac;
-  hipStream_t stream;
-  hipError_t mul(const double* v, double* y) const {   // y = J v
-    return twr::launch_jac_mul(ops->mul.d.get(), ops->mul.n, ops->lds_x, jac, v, y, stream);
-  }
-  hipError_t tmul(const double* w, double* z) const {   // z = J^T w
-    return twr::launch_jac_tmul(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, jac, w, ops->slab.get(), z, stream);
-  }
-  hipError_t colsq(const double* w, double* out) const {   // out[k] = sum_r w_r J[r][k]^2
-    return twr::launch_jac_colsq(ops->tmul.d.get(), ops->tmul.n, ops->fold.d.get(), ops->fold.n, jac, w, ops->slab.get(), out, stream);
-  }
-  hipError_t normal(const double* w, const double* v, double* y, double* u) const {   // u = J^T (w o (J v)), y = J v (once reserved)
-    return twr::launch_jac_normal(ops->nwork.d.get(), ops->nwork.n, ops->n_lds_x, ops->n_tile, ops->nfold.d.get(), ops->nfold.n, jac, w, v, y,
-                                  ops->nslab.get(), u, stream);
-  }
-};
+// A handle's products with one J on one stream: what the entry points launch, and the J the solves are given
+twr::JacProducts products(const twr_jac_ops* ops, const double* jac, void* hip_stream) {
+  return {ops->mul.d.get(),   ops->mul.n,   ops->tmul.d.get(),  ops->tmul.n,  ops->fold.d.get(), ops->fold.n,
+          ops->nwork.d.get(), ops->nwork.n, ops->nfold.d.get(), ops->nfold.n, ops->slab.get(),   ops->nslab.get(),
+          ops->lds_x,         ops->n_lds_x, ops->n_tile,        jac,          static_cast<hipStream_t>(hip_stream)};
+}
 
 // The launches of an entry point, on the handle's device (DeviceScope), as the entry point's return code
 template <class Launch> int on_device(int device, Launch launch) {
@@ -129,7 +112,7 @@ int solve_scaled(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, const
       [&] { return twr_jac_lsq_reserve_scaled(lsq); },
       [&] {
         return twr::launch_lsq_solve_scaled(lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, lsq->buf2, d_b, d_w, d_mu, d_scale, iters, tol,
-                                            d_d, d_info, JacProducts{lsq->ops, d_jac, static_cast<hipStream_t>(hip_stream)}, masked);
+                                            d_d, d_info, products(lsq->ops, d_jac, hip_stream), masked);
       });
 }
 
@@ -246,19 +229,19 @@ int twr_jac_ops_bytes(const twr_jac_ops* ops, int64_t* resident, int32_t* distin
 int twr_jac_mul(twr_jac_ops* ops, const double* d_jac, const double* d_v, double* d_y, void* hip_stream) {
   if (!ops || !d_jac || !d_v || !d_y) return fail(TWR_ERR_INVALID, "null argument");
   if (misaligned({d_jac, d_v, d_y})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  return on_device(ops->device, [&] { return JacProducts{ops, d_jac, static_cast<hipStream_t>(hip_stream)}.mul(d_v, d_y); });
+  return on_device(ops->device, [&] { return twr::launch_jac_mul(products(ops, d_jac, hip_stream), d_v, d_y); });
 }
 
 int twr_jac_tmul(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_z, void* hip_stream) {
   if (!ops || !d_jac || !d_w || !d_z) return fail(TWR_ERR_INVALID, "null argument");
   if (misaligned({d_jac, d_w, d_z})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  return on_device(ops->device, [&] { return JacProducts{ops, d_jac, static_cast<hipStream_t>(hip_stream)}.tmul(d_w, d_z); });
+  return on_device(ops->device, [&] { return twr::launch_jac_tmul(products(ops, d_jac, hip_stream), d_w, d_z); });
 }
 
 int twr_jac_col_sqnorms(twr_jac_ops* ops, const double* d_jac, const double* d_w, double* d_out, void* hip_stream) {
   if (!ops || !d_jac || !d_out) return fail(TWR_ERR_INVALID, "null argument");
   if (misaligned({d_jac, d_w, d_out})) return fail(TWR_ERR_INVALID, "buffers must be 8-byte aligned");
-  return on_device(ops->device, [&] { return JacProducts{ops, d_jac, static_cast<hipStream_t>(hip_stream)}.colsq(d_w, d_out); });
+  return on_device(ops->device, [&] { return twr::launch_jac_colsq(products(ops, d_jac, hip_stream), d_w, d_out); });
 }
 
 namespace {
@@ -347,7 +330,7 @@ int twr_jac_normal_mul(twr_jac_ops* ops, const double* d_jac, const double* d_w,
     const int rc = twr_jac_ops_reserve_normal(ops);
     if (rc != TWR_OK) return rc;
   }
-  return on_device(ops->device, [&] { return JacProducts{ops, d_jac, static_cast<hipStream_t>(hip_stream)}.normal(d_w, d_v, d_y, d_u); });
+  return on_device(ops->device, [&] { return twr::launch_jac_normal(products(ops, d_jac, hip_stream), d_w, d_v, d_y, d_u); });
 }
 
 int twr_jac_lsq_create(twr_jac_ops* ops, const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem,
@@ -423,7 +406,7 @@ int twr_jac_lsq_solve(twr_jac_lsq* lsq, const double* d_jac, const double* d_b, 
       lsq, !lsq || !d_jac || !d_b || !d_mu || !d_d || !d_info, iters, tol, {d_jac, d_b, d_w, d_mu, d_d, d_info}, [] { return TWR_OK; },
       [&] {
         return twr::launch_lsq_solve(lsq->work.d.get(), lsq->work.n, lsq->lds_x, lsq->buf, d_b, d_w, d_mu, iters, tol, d_d, d_info,
-                                     JacProducts{lsq->ops, d_jac, static_cast<hipStream_t>(hip_stream)});
+                                     products(lsq->ops, d_jac, hip_stream));
       });
 }
 
@@ -466,7 +449,7 @@ int twr_jac_lsq_solve_onepass(twr_jac_lsq* lsq, const double* d_jac, const doubl
       [&] { return twr_jac_lsq_reserve_onepass(lsq, d_scale != nullptr); },   // (what exists is left as it is)
       [&] {
         return twr::launch_lsq_solve_onepass(lsq->work.d.get(), lsq->work.n, lsq->buf, lsq->buf2, lsq->buf3, d_b, d_w, d_mu, d_scale, iters, tol,
-                                             d_d, d_info, JacProducts{lsq->ops, d_jac, static_cast<hipStream_t>(hip_stream)});
+                                             d_d, d_info, products(lsq->ops, d_jac, hip_stream));
       });
 }
 
@@ -687,24 +670,13 @@ int twr_jac_lm_set_solver(twr_jac_lm* lm, int solver) {
 namespace {
 twr::LmParams lm_device_params(const twr_jac_lm_params& q) { return {q.mu_down, q.mu_up, q.mu_min, q.mu_max, q.tau, q.merit_done}; }
 
-// eval(BOTH) at x, violation, b = -r, the column norms and the scale with the running maximum, z = J^T(w o b), the free set
+// eval(BOTH) at x, then what the linearisation is made of (twr::launch_lm_linearise)
 int lm_linearise(twr_jac_lm* lm, int first, hipStream_t stream) {
   twr_jac_lsq* lsq = lm->lsq;
-  const JacProducts J{lsq->ops, lm->jac, stream};
-  const twr::LmBuffers& B = lm->buf;
-  const twr::JacLsqWork* work = lsq->work.d.get();
-  const int n = lm->n_problems;
-  int rc = twr_batch_eval(lm->batch, lm->x, lm->g, lm->jac, TWR_EVAL_BOTH, stream);
+  const int rc = twr_batch_eval(lm->batch, lm->x, lm->g, lm->jac, TWR_EVAL_BOTH, stream);
   if (rc != TWR_OK) return rc;
-  hipError_t e = twr::launch_lsq_violation(work, n, lm->g, nullptr, B.r, B.wa, B.merit_lin, stream);
-  if (e == hipSuccess)   // (w o b goes to rt, which is free until the trial point's violation)
-    e = twr::jac_launch(twr::lm_rhs_kernel, n, twr::kLsqThreads, 0, stream, work, B.r, B.wa, B.merit_lin, B.b, B.rt, B.rec,
-                        lm->params.merit_done, first);
-  if (e == hipSuccess) e = J.colsq(B.wa, B.colsq);
-  if (e == hipSuccess) e = twr::launch_lsq_col_scale(work, n, B.colsq, B.colmax, lm->params.rel_floor, B.c, stream);
-  if (e == hipSuccess) e = J.tmul(B.rt, B.z);
-  if (e == hipSuccess) e = twr::launch_lm_free_set(work, n, lm->x, lm->xlo, lm->xup, B.z, B.c, B.cf, B.nfree, stream);
-  return launched(e);
+  return launched(twr::launch_lm_linearise(lsq->work.d.get(), lm->n_problems, lm->x, lm->g, lm->xlo, lm->xup, lm->buf, lm->params.merit_done,
+                                           lm->params.rel_floor, first, products(lsq->ops, lm->jac, stream)));
 }
 }  // namespace
 
@@ -719,27 +691,14 @@ int twr_jac_lm_start(twr_jac_lm* lm, double* d_x, const double* d_xlo, const dou
   lm->x = d_x, lm->xlo = d_xlo, lm->xup = d_xup, lm->g = d_g, lm->jac = d_jac;
   hipStream_t stream = static_cast<hipStream_t>(hip_stream);
   twr_jac_lsq* lsq = lm->lsq;
-  const JacProducts J{lsq->ops, d_jac, stream};
-  const twr::LmBuffers& B = lm->buf;
   const twr::JacLsqWork* work = lsq->work.d.get();
-  const int n = lm->n_problems, iters = lm->params.power_iters;
-  const twr::LmParams P = lm_device_params(lm->params);
-  // the power iteration borrows d (v), xt (cf o v), z (u) and gt (y)
-  hipError_t e = twr::jac_launch(twr::lm_project_kernel, n, twr::kLsqThreads, 0, stream, work, d_x, d_xlo, d_xup, B.colmax, B.d, B.rec, B.mu,
-                                 lm->params.tau);
+  const int n = lm->n_problems;
+  const hipError_t e = twr::launch_lm_project(work, n, d_x, d_xlo, d_xup, lm->buf, lm->params.tau, stream);
   if (e != hipSuccess) return launched(e);
   const int rc = lm_linearise(lm, 1, stream);
   if (rc != TWR_OK) return rc;
-  e = twr::jac_launch(twr::lm_normalise_kernel, n, twr::kLsqThreads, 0, stream, work, B.cf, B.d, B.z, B.xt, B.rec, B.mu, P, 0, iters == 0);
-  for (int k = 0; k < iters && e == hipSuccess; ++k) {
-    e = J.mul(B.xt, B.gt);
-    if (e == hipSuccess) e = twr::jac_launch(twr::lm_weight_kernel, n, twr::kLsqThreads, 0, stream, work, B.wa, B.gt);
-    if (e == hipSuccess) e = J.tmul(B.gt, B.z);
-    if (e == hipSuccess)
-      e = twr::jac_launch(twr::lm_normalise_kernel, n, twr::kLsqThreads, 0, stream, work, B.cf, B.d, B.z, B.xt, B.rec, B.mu, P, 1,
-                          k == iters - 1);
-  }
-  return launched(e);
+  return launched(twr::launch_lm_power(work, n, lm->buf, lm_device_params(lm->params), lm->params.power_iters,
+                                       products(lsq->ops, d_jac, stream)));
 }
 
 int twr_jac_lm_step(twr_jac_lm* lm, void* hip_stream) {
@@ -765,15 +724,11 @@ int twr_jac_lm_step(twr_jac_lm* lm, void* hip_stream) {
     rc = solve_scaled(lsq, lm->jac, B.b, B.wa, B.mu, B.cf, lm->params.cg_iters, lm->params.cg_tol, B.d, B.info, stream, true);
   }
   if (rc != TWR_OK) return rc;
-  hipError_t e = twr::jac_launch(twr::lm_trial_kernel, n, twr::kLsqThreads, 0, stream, work, B.rec, lm->x, B.d, lm->xlo, lm->xup, B.xt);
+  const hipError_t e = twr::launch_lm_trial(work, n, lm->x, lm->xlo, lm->xup, B, stream);
   if (e != hipSuccess) return launched(e);
   rc = twr_batch_eval(lm->batch, B.xt, B.gt, nullptr, TWR_EVAL_VALUES, stream);
   if (rc != TWR_OK) return rc;
-  e = twr::launch_lsq_violation(work, n, B.gt, nullptr, B.rt, nullptr, B.merit_t, stream);
-  if (e == hipSuccess)
-    e = twr::jac_launch(twr::lm_accept_kernel, n, twr::kLsqThreads, 0, stream, work, B.rec, B.mu, B.merit_t, B.info, B.nfree, lm->x, B.xt,
-                        lm_device_params(lm->params));
-  return launched(e);
+  return launched(twr::launch_lm_accept(work, n, lm->x, B, lm_device_params(lm->params), stream));
 }
 
 int twr_jac_lm_state(twr_jac_lm* lm, double* d_out, void* hip_stream) {

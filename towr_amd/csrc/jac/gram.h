@@ -9,17 +9,17 @@
 //                         a butterfly over the 16 lanes (both partners of a step add the same two numbers).
 //   gram_cg_kernel:       the whole solve (C N C + mu I) e = c o z, d = c o e of one problem in one workgroup: e, s, p, c, c o p and
 //                         N (c o p) in LDS, the rows of N streamed once per iteration by the row product above, the two dots of an
-//                         iteration by lsq_sum (jac_lsq.hip).  A problem that has stopped leaves the loop and its workgroup ends.
+//                         iteration by lsq_sum (lsq.h).  A problem that has stopped leaves the loop and its workgroup ends.
 // No atomics; the order of every sum is a function of the pattern alone.  The row product and the CG multiply, then add (no fused
 // multiply-add: `fp contract(off)` in their bodies), every sum in the order stated here, so that the numpy restatement
 // (scripts/gram_cpu.py gram_cg_device) takes the same roundings in the same order and stops at the same iteration.
-// Included by capi_jac.cc (compiled as HIP for gfx950).
+// Included by jac_tu.hip alone, which holds the launchers (jac_launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "jac_lsq.hip"
-#include "jac_products.hip"
-#include "jac_plan.h"
+#include "lsq.h"
+#include "products.h"
+#include "../jac_plan.h"
 
 namespace twr {
 
@@ -162,35 +162,8 @@ __global__ __launch_bounds__(kGramThreads) void gram_cg_kernel(const JacGramSolv
   if (k > 0)
     for (int i = tid; i < n; i += kGramThreads) dp[i] = c[i] == 0.0 ? 0.0 : c[i] * e[i];
   if (tid == 0) {
-    o[0] = (double)k;
-    o[1] = g0 == 0.0 ? 0.0 : sqrt(gamma / g0);
-    o[2] = sqrt(g0);
-    o[3] = state == kLsqRunning ? 1.0 : state;   // still running at the end of the loop: the iteration cap
+    lsq_info(o, (double)k, gamma, g0, state);
   }
-}
-
-inline size_t gram_cg_lds_bytes(int max_n) { return sizeof(double) * ((size_t)kGramSolveVectors * max_n + kGramRed); }
-// the solve's LDS may pass 64 KB: raises the kernel's limit once, on the handle's device, outside any capture
-inline hipError_t prepare_gram_cg() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(gram_cg_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kGramLdsBytes);
-}
-
-inline hipError_t launch_jac_gram(const JacGramWork* work, int n_work, const double* jac, const double* w, double* gram, hipStream_t stream) {
-  if (n_work == 0) return hipSuccess;
-  return jac_launch(jac_gram_kernel, n_work, kGramThreads, 0, stream, work, jac, w, gram);
-}
-
-inline hipError_t launch_jac_gram_mul(const JacGramMulWork* work, int n_work, const double* gram, const double* v, double* u,
-                                      hipStream_t stream) {
-  if (n_work == 0) return hipSuccess;
-  return jac_launch(jac_gram_mul_kernel, n_work, kGramThreads, 0, stream, work, gram, v, u);
-}
-
-inline hipError_t launch_gram_cg(const JacGramSolveWork* work, int n_problems, int max_n, const double* gram, const double* z,
-                                 const double* mu, const double* scale, int iters, double tol, double* d, double* info,
-                                 hipStream_t stream) {
-  return jac_launch(gram_cg_kernel, n_problems, kGramThreads, gram_cg_lds_bytes(max_n), stream, work, gram, z, mu, scale, iters, tol * tol, d,
-                    info, max_n);
 }
 
 }  // namespace twr

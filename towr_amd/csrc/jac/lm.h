@@ -1,5 +1,5 @@
 // The bound-constrained Levenberg-Marquardt driver (twr_jac_lm_*, twr_jac_free_set; include/towr_amd.h): the vector kernels between
-// the evaluation, the products and the masked solve of jac_lsq.hip.  Projected active-set LM: a variable that sits on a bound the
+// the evaluation, the products and the masked solve of lsq.h.  Projected active-set LM: a variable that sits on a bound the
 // step would push it through (every variable with lo == up among them) gets an exact 0 in the column scale and so stays out of the
 // solve, the trial point is projected onto the box, and accept / reject and mu are decided per problem here.
 //   lm_project_kernel:   x = min(max(x, lo), up), the checks of x and the bounds, the start of the problem's record, colmax = 0 and
@@ -10,23 +10,19 @@
 //   lm_normalise_kernel: u = cf o u, lambda = v^T u / v^T v, v = u / |u|, cv = cf o v; the last one sets mu0
 //   lm_trial_kernel:     xt = min(max(x + d, lo), up) (a problem that is not running: xt = x)
 //   lm_accept_kernel:    ok = merit_t < merit, x = xt where ok, mu, the counters
-// One workgroup of kLsqThreads lanes per problem in every kernel, the sums by lsq_sum over the index pairs of jac_lsq.hip: an order
+// One workgroup of kLsqThreads lanes per problem in every kernel, the sums by lsq_sum over the index pairs of lsq.h: an order
 // fixed by the vector's length, so x after any number of steps has the same bits wherever the problem sits.  No atomics.  Every
 // index comes from the work record, never from the data.  The workspace is planned on the host (twr::PlanJacLm, jac_plan.h).
-// Included by capi_jac.cc (compiled as HIP for gfx950).
+// Included by jac_tu.hip alone, which holds the launchers (jac_launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "jac_lsq.hip"
-#include "jac_plan.h"
+#include "lsq.h"
+#include "../jac_launch.h"   // LmParams, a kernel argument
 
 namespace twr {
 
 constexpr double kLmHuge = 1e20;   // ifopt's NoBound: an |x_k| beyond it is not a number to the NLP
-
-struct LmParams {   // twr_jac_lm_params, what the kernels read
-  double mu_down, mu_up, mu_min, mu_max, tau, merit_done;
-};
 
 __device__ inline double lm_clamp(double v, double lo, double hi) {   // a NaN v stays NaN
   double c = v < lo ? lo : v;
@@ -252,14 +248,5 @@ __global__ __launch_bounds__(kLsqThreads) void lm_accept_kernel(const JacLsqWork
     rc[kLmCgIters] = cg;
   }
 }
-
-inline hipError_t launch_lm_free_set(const JacLsqWork* work, int n, const double* x, const double* lo, const double* up,
-                                     const double* z, const double* c_in, double* c_out, double* nfree, hipStream_t stream) {
-  return jac_launch(lm_free_set_kernel, n, kLsqThreads, 0, stream, work, x, lo, up, z, c_in, c_out, nfree);
-}
-
-struct LmBuffers {   // the handle's workspace (JacLmPlan's segments)
-  double *xt, *d, *z, *colsq, *colmax, *c, *cf, *r, *b, *wa, *gt, *rt, *rec, *mu, *merit_t, *merit_lin, *nfree, *info;
-};
 
 }  // namespace twr

@@ -1,6 +1,6 @@
 // The damped weighted least-squares step with a batch's Jacobian values, per problem p (twr_jac_lsq_solve, include/towr_amd.h):
 //   d_p = argmin_d  sum_r w_r (J_p d - b_p)_r^2 + mu_p |d|^2      <=>   (J_p^T W_p J_p + mu_p I) d_p = J_p^T W_p b_p
-// by CGLS on top of the two products of jac_products.hip (used as they are), and what feeds it: the bound-violation residual
+// by CGLS on top of the two products of products.h (used as they are), and what feeds it: the bound-violation residual
 // (twr_jac_violation) and per-problem dot products (twr_jac_dot).  One workgroup of kLsqThreads lanes per problem in every kernel
 // here; the work records, the workspace and the bound tables are planned on the host (twr::PlanJacLsq, jac_plan.h).
 //   lsq_start_kernel:  d = 0, r = b, t = w o r                                   (then z = J^T t by the product kernels)
@@ -16,12 +16,12 @@
 // that has stopped (converged, or bad input) is skipped by its workgroup in every later kernel: its d, r, p no longer change.
 // No atomics: every sum is taken by lsq_sum in an order fixed by the vector's length (jac_plan.h), so a problem's outputs have
 // the same bits wherever it sits in whatever batch.  Every index comes from the work record, never from the data.
-// Included by capi_jac.cc (compiled as HIP for gfx950).
+// Included by jac_tu.hip alone, which holds the launchers (jac_launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "jac_products.hip"
-#include "jac_plan.h"
+#include "products.h"
+#include "../jac_plan.h"
 
 namespace twr {
 
@@ -43,6 +43,16 @@ __device__ inline void lsq_st(double* __restrict__ a, int i, int len, bool al, d
   } else {
     a[i] = v.x;
   }
+}
+
+// A lane's sum over its pairs: acc += a.x b.x, then a.y b.y where the pair is whole, in this order; weighted: a (w b)
+__device__ inline void lsq_add(double& acc, double2 a, double2 b, int i, int len) {
+  acc += a.x * b.x;
+  if (i + 1 < len) acc += a.y * b.y;
+}
+__device__ inline void lsq_add(double& acc, double2 a, double2 w, double2 b, int i, int len) {
+  acc += a.x * (w.x * b.x);
+  if (i + 1 < len) acc += a.y * (w.y * b.y);
 }
 
 // Sums of K values over the workgroup, the same bits in every lane: a butterfly over the wave (both partners of a step add the
@@ -83,8 +93,7 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_dot_kernel(const JacLsqWork* 
   double acc[1] = {0.0};
   for (int i = 2 * (int)threadIdx.x; i < len; i += 2 * kLsqThreads) {
     const double2 x = lsq_ld(ap, i, len, aa), y = lsq_ld(bp, i, len, ab);
-    acc[0] += x.x * y.x;
-    if (i + 1 < len) acc[0] += x.y * y.y;
+    lsq_add(acc[0], x, y, i, len);
   }
   lsq_sum(acc, red);
   if (threadIdx.x == 0) out[blockIdx.x] = acc[0];
@@ -117,7 +126,7 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_violation_kernel(const JacLsq
     const double2 rv = make_double2(lsq_viol(gv.x, l.x, h.x), lsq_viol(gv.y, l.y, h.y));
     lsq_st(rp, i, m, ar, rv);
     if (ap) lsq_st(ap, i, m, aa, make_double2(wv.x * (rv.x != 0.0 ? 1.0 : 0.0), wv.y * (rv.y != 0.0 ? 1.0 : 0.0)));
-    acc[0] += wv.x * (rv.x * rv.x);
+    acc[0] += wv.x * (rv.x * rv.x);   // (written out: through lsq_add the kernel's code differs)
     if (i + 1 < m) acc[0] += wv.y * (rv.y * rv.y);
   }
   if (!merit) return;
@@ -166,6 +175,14 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_start_scaled_kernel(const Jac
 
 __device__ inline bool lsq_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN and Inf
 
+// A problem's info record: iterations, |s| / |s0|, |s0|, status (still running when the last launch has gone by: the iteration cap)
+__device__ inline void lsq_info(double* o, double iters, double gn, double g0, double state) {
+  o[0] = iters;
+  o[1] = g0 == 0.0 ? 0.0 : sqrt(gn / g0);
+  o[2] = sqrt(g0);
+  o[3] = state == kLsqRunning ? 1.0 : state;
+}
+
 // After q = J p.  A problem that is running: delta, alpha, the three updates and the next J^T's input.  SCALED (q = J (c o p)):
 // the update is e += alpha p, and d = c o e is written beside it.
 template <bool SCALED>
@@ -190,13 +207,11 @@ __device__ inline void lsq_step_body(const JacLsqWork* __restrict__ work, double
   for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
     const double2 qv = lsq_ld(qp, i, m, aq);
     const double2 wv = wp ? lsq_ld(wp, i, m, aw) : make_double2(1.0, 1.0);
-    acc[0] += qv.x * (wv.x * qv.x);
-    if (i + 1 < m) acc[0] += qv.y * (wv.y * qv.y);
+    lsq_add(acc[0], qv, wv, qv, i, m);
   }
   for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
     const double2 pv = lsq_ld(pp, i, n, ap);
-    acc[1] += pv.x * pv.x;
-    if (i + 1 < n) acc[1] += pv.y * pv.y;
+    lsq_add(acc[1], pv, pv, i, n);
   }
   lsq_sum(acc, red);
   const double delta = acc[0] + m_u * acc[1];
@@ -306,8 +321,7 @@ __device__ inline void lsq_dir_body(const JacLsqWork* __restrict__ work, double*
       lsq_s[i] = sv.x;
       if (i + 1 < n) lsq_s[i + 1] = sv.y;
     }
-    acc[0] += sv.x * sv.x;
-    if (i + 1 < n) acc[0] += sv.y * sv.y;
+    lsq_add(acc[0], sv, sv, i, n);
   }
   lsq_sum(acc, red);
   const double gn = acc[0];
@@ -341,11 +355,7 @@ __device__ inline void lsq_dir_body(const JacLsqWork* __restrict__ work, double*
     rc[kLsqGamma] = gn;
     rc[kLsqState] = state;
     if (first) rc[kLsqGamma0] = g0, rc[kLsqIters] = 0.0;
-    double* o = info + 4 * (int64_t)blockIdx.x;
-    o[0] = first ? 0.0 : iters;
-    o[1] = g0 == 0.0 ? 0.0 : sqrt(gn / g0);
-    o[2] = sqrt(g0);
-    o[3] = state == kLsqRunning ? 1.0 : state;   // still running when the last launch has gone by: the iteration cap
+    lsq_info(info + 4 * (int64_t)blockIdx.x, first ? 0.0 : iters, gn, g0, state);
   }
 }
 __global__ __launch_bounds__(kLsqThreads) void lsq_dir_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
@@ -423,8 +433,7 @@ __device__ inline void lsq_onepass_body(const JacLsqWork* __restrict__ work, dou
         if (i + 1 < n && (!(cv.y > 0.0) || !lsq_finite(cv.y))) acc[1] += 1.0;
       }
       lsq_st(sp, i, n, as, sv);
-      acc[0] += sv.x * sv.x;
-      if (i + 1 < n) acc[0] += sv.y * sv.y;
+      lsq_add(acc[0], sv, sv, i, n);
     }
     lsq_sum(acc, red);
     const double gn = acc[0];
@@ -437,10 +446,7 @@ __device__ inline void lsq_onepass_body(const JacLsqWork* __restrict__ work, dou
       for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) put_p(i, lsq_ld(sp, i, n, as));
     if (threadIdx.x == 0) {
       rc[kLsqGamma] = gn, rc[kLsqGamma0] = gn, rc[kLsqIters] = 0.0, rc[kLsqState] = state;
-      o[0] = 0.0;
-      o[1] = gn == 0.0 ? 0.0 : sqrt(gn / gn);
-      o[2] = sqrt(gn);
-      o[3] = state == kLsqRunning ? 1.0 : state;
+      lsq_info(o, 0.0, gn, gn, state);
     }
     return;
   }
@@ -455,13 +461,11 @@ __device__ inline void lsq_onepass_body(const JacLsqWork* __restrict__ work, dou
   for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
     const double2 qv = lsq_ld(qp, i, m, aq);
     const double2 wv = wp ? lsq_ld(wp, i, m, aw) : make_double2(1.0, 1.0);
-    acc[0] += qv.x * (wv.x * qv.x);
-    if (i + 1 < m) acc[0] += qv.y * (wv.y * qv.y);
+    lsq_add(acc[0], qv, wv, qv, i, m);
   }
   for (int i = 2 * (int)threadIdx.x; i < n; i += 2 * kLsqThreads) {
     const double2 pv = lsq_ld(pp, i, n, ap);
-    acc[1] += pv.x * pv.x;
-    if (i + 1 < n) acc[1] += pv.y * pv.y;
+    lsq_add(acc[1], pv, pv, i, n);
   }
   lsq_sum(acc, red);
   const double delta = acc[0] + m_u * acc[1];
@@ -488,8 +492,7 @@ __device__ inline void lsq_onepass_body(const JacLsqWork* __restrict__ work, dou
     }
     const double2 sn = make_double2(fma(-alpha, fma(m_u, pv.x, uv.x), sv.x), fma(-alpha, fma(m_u, pv.y, uv.y), sv.y));
     lsq_st(sp, i, n, as, sn);
-    gs[0] += sn.x * sn.x;
-    if (i + 1 < n) gs[0] += sn.y * sn.y;
+    lsq_add(gs[0], sn, sn, i, n);
   }
   for (int i = 2 * (int)threadIdx.x; i < m; i += 2 * kLsqThreads) {
     const double2 qv = lsq_ld(qp, i, m, aq), rv = lsq_ld(rp, i, m, ar);
@@ -510,10 +513,7 @@ __device__ inline void lsq_onepass_body(const JacLsqWork* __restrict__ work, dou
     rc[kLsqGamma] = gn;
     rc[kLsqState] = state;
     rc[kLsqIters] = iters + 1.0;
-    o[0] = iters + 1.0;
-    o[1] = g0 == 0.0 ? 0.0 : sqrt(gn / g0);
-    o[2] = sqrt(g0);
-    o[3] = state == kLsqRunning ? 1.0 : state;   // still running when the last launch has gone by: the iteration cap
+    lsq_info(o, iters + 1.0, gn, g0, state);
   }
 }
 __global__ __launch_bounds__(kLsqThreads) void lsq_onepass_kernel(const JacLsqWork* __restrict__ work, double* __restrict__ rec,
@@ -574,106 +574,6 @@ __global__ __launch_bounds__(kLsqThreads) void lsq_col_scale_kernel(const JacLsq
     if (mp) lsq_st(mp, i, n, am, a);
     lsq_st(sp, i, n, as, make_double2(c_of(a.x), c_of(a.y)));
   }
-}
-
-struct LsqBuffers {   // the handle's workspace (JacLsqPlan's segments)
-  double *p, *z, *q, *r, *t, *rec;
-};
-struct LsqScaledBuffers {   // the second allocation (twr_jac_lsq_reserve_scaled): e = d / c, and c o p for J to read
-  double *e, *cp;
-};
-
-inline hipError_t launch_lsq_dot(const JacLsqWork* work, int n, int space, const double* a, const double* b, double* out,
-                                 hipStream_t stream) {
-  return jac_launch(lsq_dot_kernel, n, kLsqThreads, 0, stream, work, space, a, b, out);
-}
-
-inline hipError_t launch_lsq_violation(const JacLsqWork* work, int n, const double* g, const double* w, double* r, double* w_active,
-                                       double* merit, hipStream_t stream) {
-  return jac_launch(lsq_violation_kernel, n, kLsqThreads, 0, stream, work, g, w, r, w_active, merit);
-}
-
-// The whole solve: 3 launches to start, 5 per iteration (J p, step, J^T t and its fold, direction), none of them conditional.
-// J: the products with the Jacobian on J.stream, where the vector kernels go too: J.mul(v, y) for y = J v, J.tmul(w, z) for
-// z = J^T w and (the one-pass solve) J.normal(w, v, y, u) for u = J^T (w o (J v)), y = J v.
-template <class Products>
-inline hipError_t launch_lsq_solve(const JacLsqWork* work, int n, int lds_x, const LsqBuffers& ws, const double* b, const double* w,
-                                   const double* mu, int iters, double tol, double* d, double* info, const Products& J) {
-  const hipStream_t stream = J.stream;
-  const size_t lds = sizeof(double) * (size_t)lds_x;
-  const double tol2 = tol * tol;
-  hipError_t e = jac_launch(lsq_start_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, ws.r, ws.t);
-  if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
-  if (e == hipSuccess) e = jac_launch(lsq_dir_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, d, ws.p, info, tol2, 1, lds_x);
-  for (int k = 0; k < iters && e == hipSuccess; ++k) {
-    e = J.mul(ws.p, ws.q);
-    if (e == hipSuccess) e = jac_launch(lsq_step_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.q, w, ws.p, d, ws.r, ws.t);
-    if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
-    if (e == hipSuccess)
-      e = jac_launch(lsq_dir_kernel, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, d, ws.p, info, tol2, 0, lds_x);
-  }
-  return e;
-}
-
-struct LsqOnepassBuffers {   // the third allocation (twr_jac_lsq_solve_onepass): the recurred s, and u = J^T (w o (J p))
-  double *s, *u;
-};
-
-// The one-pass solve: 4 launches to start (start, J^T t and its fold, first), 3 per iteration (the one-pass product, its fold,
-// the vector kernel), none of them conditional.  c NULL: the unscaled step; else sc holds e and c o p.
-template <class Products>
-inline hipError_t launch_lsq_solve_onepass(const JacLsqWork* work, int n, const LsqBuffers& ws, const LsqScaledBuffers& sc,
-                                           const LsqOnepassBuffers& op, const double* b, const double* w, const double* mu,
-                                           const double* c, int iters, double tol, double* d, double* info, const Products& J) {
-  const hipStream_t stream = J.stream;
-  const double tol2 = tol * tol;
-  const auto vec = [&](int first) {
-    if (c)
-      return jac_launch(lsq_onepass_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.z, ws.q, op.u, w, c, ws.p, sc.cp, op.s,
-                        sc.e, d, ws.r, info, tol2, first);
-    return jac_launch(lsq_onepass_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.z, ws.q, op.u, w, ws.p, op.s, d, ws.r, info,
-                      tol2, first);
-  };
-  hipError_t e = c ? jac_launch(lsq_start_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, sc.e, ws.r, ws.t)
-                   : jac_launch(lsq_start_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, ws.r, ws.t);
-  if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
-  if (e == hipSuccess) e = vec(1);
-  for (int k = 0; k < iters && e == hipSuccess; ++k) {
-    e = J.normal(w, c ? sc.cp : ws.p, ws.q, op.u);
-    if (e == hipSuccess) e = vec(0);
-  }
-  return e;
-}
-
-inline hipError_t launch_lsq_col_scale(const JacLsqWork* work, int n, const double* colsq, double* colsq_max, double rel_floor,
-                                       double* scale, hipStream_t stream) {
-  return jac_launch(lsq_col_scale_kernel, n, kLsqThreads, 0, stream, work, colsq, colsq_max, rel_floor, scale);
-}
-
-// The same sequence on J C in e = d / c: the product kernels as they are, the vector kernels' SCALED instantiations.  masked:
-// the direction kernel's MASKED instantiation (twr_jac_lsq_solve_masked); the start and step kernels serve as they are, since
-// p_k = +0 keeps e_k and d_k = c_k e_k at +0.
-template <class Products>
-inline hipError_t launch_lsq_solve_scaled(const JacLsqWork* work, int n, int lds_x, const LsqBuffers& ws, const LsqScaledBuffers& sc,
-                                          const double* b, const double* w, const double* mu, const double* c, int iters, double tol,
-                                          double* d, double* info, const Products& J, bool masked) {
-  const hipStream_t stream = J.stream;
-  const size_t lds = sizeof(double) * (size_t)lds_x;
-  const double tol2 = tol * tol;
-  const auto dir = masked ? lsq_dir_masked_kernel : lsq_dir_scaled_kernel;
-  hipError_t e = jac_launch(lsq_start_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, b, w, d, sc.e, ws.r, ws.t);
-  if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
-  if (e == hipSuccess)
-    e = jac_launch(dir, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 1, lds_x);
-  for (int k = 0; k < iters && e == hipSuccess; ++k) {
-    e = J.mul(sc.cp, ws.q);
-    if (e == hipSuccess)
-      e = jac_launch(lsq_step_scaled_kernel, n, kLsqThreads, 0, stream, work, ws.rec, mu, ws.q, w, ws.p, c, sc.e, d, ws.r, ws.t);
-    if (e == hipSuccess) e = J.tmul(ws.t, ws.z);
-    if (e == hipSuccess)
-      e = jac_launch(dir, n, kLsqThreads, lds, stream, work, ws.rec, mu, ws.z, sc.e, c, ws.p, sc.cp, info, tol2, 0, lds_x);
-  }
-  return e;
 }
 
 }  // namespace twr

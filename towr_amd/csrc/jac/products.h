@@ -8,13 +8,13 @@
 // every output is written by exactly one lane, which sums its terms in an order fixed by the pattern alone, so a problem's
 // outputs have the same bits wherever it sits in whatever batch.  Every index comes from the plan's tables; J, v and w are
 // only multiplied and added, so a NaN or Inf in one problem's inputs reaches that problem's outputs and no other's.
-// Included by capi_jac.cc (compiled as HIP for gfx950).
+// Included by jac_tu.hip alone, which holds the launchers (jac_launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <tuple>
 
-#include "jac_plan.h"
+#include "../jac_plan.h"
 
 namespace twr {
 
@@ -229,48 +229,6 @@ inline hipError_t jac_launch(void (*kern)(P...), int grid, int block, size_t lds
         return hipLaunchKernel(reinterpret_cast<const void*>(kern), dim3(grid), dim3(block), ptrs, lds, stream);
       },
       vals);
-}
-
-inline size_t jac_mul_lds_bytes(int lds_x) { return sizeof(double) * ((size_t)kJacMulNnz + lds_x); }
-
-// y = J v: one workgroup per work item (nothing to launch for a batch without rows)
-inline hipError_t launch_jac_mul(const JacMulWork* work, int n_work, int lds_x, const double* jac, const double* v, double* y,
-                                 hipStream_t stream) {
-  if (n_work == 0) return hipSuccess;
-  return jac_launch(jac_mul_kernel, n_work, kJacThreads, jac_mul_lds_bytes(lds_x), stream, work, jac, v, y, lds_x);
-}
-
-// z = J^T w: the partials, then the fold (which also writes the zeros of columns without entries)
-inline hipError_t launch_jac_tmul(const JacTWork* work, int n_work, const JacFoldWork* fold, int n_fold, const double* jac,
-                                  const double* w, double* slab, double* z, hipStream_t stream) {
-  hipError_t e = hipSuccess;
-  if (n_work > 0) e = jac_launch(jac_tmul_kernel, n_work, kJacThreads, 0, stream, work, jac, w, slab);
-  if (e == hipSuccess && n_fold > 0) e = jac_launch(jac_fold_kernel, n_fold, kJacFoldCols, 0, stream, fold, slab, z);
-  return e;
-}
-
-// u = J^T (w o (J v)), y = J v (y NULL: not written; w NULL: unit weights): the one pass, then the fold over its own slab.  With
-// v staged the kernel's LDS passes 64 KB: prepare_jac_normal raises the limit once, on the handle's device, outside any capture.
-inline size_t jac_normal_lds_bytes(int lds_x, int tile) { return sizeof(double) * (2 * (size_t)tile + lds_x); }
-inline hipError_t prepare_jac_normal() {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(jac_normal_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-inline hipError_t launch_jac_normal(const JacNormalWork* work, int n_work, int lds_x, int tile, const JacFoldWork* fold, int n_fold,
-                                    const double* jac, const double* w, const double* v, double* y, double* slab, double* u,
-                                    hipStream_t stream) {
-  hipError_t e = hipSuccess;
-  if (n_work > 0) e = jac_launch(jac_normal_kernel, n_work, kJacThreads, jac_normal_lds_bytes(lds_x, tile), stream, work, jac, w, v, y, slab, lds_x, tile);
-  if (e == hipSuccess && n_fold > 0) e = jac_launch(jac_fold_kernel, n_fold, kJacFoldCols, 0, stream, fold, slab, u);
-  return e;
-}
-
-// out[k] = sum_r w_r J[r][k]^2 (w NULL: unit weights): J^T w's work list, slab and fold
-inline hipError_t launch_jac_colsq(const JacTWork* work, int n_work, const JacFoldWork* fold, int n_fold, const double* jac,
-                                   const double* w, double* slab, double* out, hipStream_t stream) {
-  hipError_t e = hipSuccess;
-  if (n_work > 0) e = jac_launch(jac_colsq_kernel, n_work, kJacThreads, 0, stream, work, jac, w, slab);
-  if (e == hipSuccess && n_fold > 0) e = jac_launch(jac_fold_kernel, n_fold, kJacFoldCols, 0, stream, fold, slab, out);
-  return e;
 }
 
 }  // namespace twr

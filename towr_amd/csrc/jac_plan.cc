@@ -15,7 +15,7 @@
 
 namespace twr {
 
-// ---------------------------------------------------------------- products with the Jacobian values (jac_products.hip)
+// ---------------------------------------------------------------- products with the Jacobian values (jac/products.h)
 namespace {
 void CheckPattern(const Structure& S) {
   const int n = S.n_vars, m = S.n_rows;
@@ -220,7 +220,7 @@ JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::v
   return J;
 }
 
-// ---------------------------------------------------------------- the one-pass normal product (jac_products.hip jac_normal_kernel)
+// ---------------------------------------------------------------- the one-pass normal product (jac/products.h jac_normal_kernel)
 namespace {
 struct JacNormalTables {   // one distinct pattern: byte offsets into JacNormalPlan::tables, its blocks, partials per problem
   uint64_t fold_ptr = 0, fold_slot = 0;
@@ -336,7 +336,7 @@ JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& structs, const 
   return PlanJacNormal(patterns, places, pattern_of_problem, tile);
 }
 
-// ---------------------------------------------------------------- the Gram matrix N = J^T W J (jac_gram.hip)
+// ---------------------------------------------------------------- the Gram matrix N = J^T W J (jac/gram.h)
 void GramPattern(const Structure& S, std::vector<int32_t>* row_ptr, std::vector<int32_t>* col_idx) {
   const CscPattern T = TransposePattern(S);   // (checks the pattern)
   const int n = S.n_vars;

@@ -9,7 +9,7 @@
 
 namespace twr {
 
-// Products with a batch's Jacobian values (twr_jac_mul: y = J v, twr_jac_tmul: z = J^T w; jac_products.hip), planned on the host
+// Products with a batch's Jacobian values (twr_jac_mul: y = J v, twr_jac_tmul: z = J^T w; jac/products.h), planned on the host
 // (no HIP).  The CSC view of a structure's CSR pattern: col_ptr[n + 1]; per entry its row and its position in the CSR value
 // array, rows ascending within a column.  Throws when a row's columns do not ascend strictly (unsorted or duplicate entries)
 // or leave [0, n_vars): the products rely on both.
@@ -66,7 +66,7 @@ struct JacOpsPlan {
 // (structs, struct_of_problem) as for twr_batch_create.  Byte-identical patterns (n, m, row_ptr, col_idx) share one set of tables.
 JacOpsPlan PlanJacOps(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
 
-// The one-pass normal product u = J^T (w o (J v)), y = J v (twr_jac_normal_mul; jac_products.hip jac_normal_kernel), planned on the
+// The one-pass normal product u = J^T (w o (J v)), y = J v (twr_jac_normal_mul; jac/products.h jac_normal_kernel), planned on the
 // host (no HIP): a plan of its own next to PlanJacOps, for the same arguments and in the same x / g / jac layout.
 //   Blocks of consecutive WHOLE rows of one problem, at most kJacThreads rows and one tile of entries (kJacNormNnz).  The block's values are
 //   streamed once into LDS, raw and multiplied by v[col]; the lane of a row sums its products in column order (y_r), forms
@@ -115,7 +115,7 @@ JacNormalPlan PlanJacNormal(const std::vector<const Structure*>& structs, const 
                             int tile = kJacNormNnz);
 
 // The Gram matrix N = J^T W J of every problem, formed once and kept (twr_jac_gram, twr_jac_gram_mul, twr_jac_lsq_solve_gram;
-// jac_gram.hip), planned on the host (no HIP) for the arguments of PlanJacOps and in its x / g / jac layout.  Per distinct pattern:
+// jac/gram.h), planned on the host (no HIP) for the arguments of PlanJacOps and in its x / g / jac layout.  Per distinct pattern:
 //   the pattern of N = J^T J as full symmetric CSR -- int32 row_ptr[n + 1], uint16 col[nnz N], columns ascending.  Structural
 //   only: an explicit zero of J counts, a column of J without entries gives an empty row and column.
 //   the contribution table of the LOWER triangle (i >= j; the kernel writes the sum to (i, j) and to (j, i), so both carry the
@@ -181,7 +181,7 @@ JacGramPlan PlanJacGram(const std::vector<const Structure*>& structs, const std:
 // One structure's pattern of N alone (twr_structure_gram_pattern): row_ptr[n + 1], col_idx[nnz N]
 void GramPattern(const Structure& S, std::vector<int32_t>* row_ptr, std::vector<int32_t>* col_idx);
 
-// The damped weighted least-squares step with a batch's Jacobian (twr_jac_lsq_solve, twr_jac_violation, twr_jac_dot; jac_lsq.hip),
+// The damped weighted least-squares step with a batch's Jacobian (twr_jac_lsq_solve, twr_jac_violation, twr_jac_dot; jac/lsq.h),
 // planned on the host (no HIP): one work record per problem, the solver's workspace and the per-row bound tables.
 //   workspace (doubles, every segment starts on a 16-byte boundary): p and z in the x layout, q, r and t in the g layout, then
 //   kLsqRec doubles of scalars per problem.  A vector of problem p lives at segment + x_off[p] / g_off[p], as in the batch.
@@ -220,7 +220,7 @@ struct JacLsqPlan {
 };
 JacLsqPlan PlanJacLsq(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem);
 
-// The bound-constrained Levenberg-Marquardt driver (twr_jac_lm_*; jac_lm.hip), planned on the host (no HIP): the workspace of a
+// The bound-constrained Levenberg-Marquardt driver (twr_jac_lm_*; jac/lm.h), planned on the host (no HIP): the workspace of a
 // twr_jac_lm handle in the x / g layout of PlanJacLsq for the same arguments (only n_vars and n_rows of a Structure are read).
 //   workspace (doubles, every segment starts on a 16-byte boundary):
 //     x layout: xt (the trial point), d (the step), z = J^T(w o b), colsq, colmax (the running maximum), c (the Marquardt scale),

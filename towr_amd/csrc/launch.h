@@ -1,4 +1,4 @@
-// Host launchers of the kernels (launch_eval, prepare_phase_kernels: kernels.hip; the utility kernels': util_tu.hip), called by the C ABI (capi.cc; capi_jac.cc reaches them through twr_batch_eval).
+// Host launchers of the kernels (launch_eval, prepare_phase_kernels: kernels.hip; the utility kernels': util_tu.hip), called by the C ABI (capi.cc; capi_jac.cc reaches them through twr_batch_eval; the solver kernels' launchers are jac_launch.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
