@@ -10,6 +10,8 @@ The linear sets (splineacc-*, swing-*: g = J x exactly) vanish identically on e.
 interpolated initial guess, so for their rows the scale of g is the magnitude of the terms that
 cancel, sum_k |J_rk x_k| (needs x), when that is larger than the set maximum.
 """
+from fractions import Fraction
+
 import numpy as np
 
 import towr_amd as ta
@@ -130,6 +132,58 @@ class Case:
                 e = int(vs["name"][len("ee-schedule"):])
                 x[a:b] = np.asarray(self.sched.durations()[e][:-1]) * (1.0 + 0.1 * rng.uniform(-1, 1, size=b - a))
         return x
+
+    def euler_positions(self):
+        """indices into x of the Euler angles of base-ang, [node, axis] (the first three of each node's six values)"""
+        vs = [v for v in self.S.var_sets if v["name"] == "base-ang"][0]
+        assert vs["size"] % 6 == 0
+        return vs["offset"] + 6 * np.arange(vs["size"] // 6)[:, None] + np.arange(3)[None, :]
+
+    def x_turned(self, seed):
+        """x_perturbed(seed) with every Euler angle turned into another quadrant: theta = k*pi/2 + delta, k cycling through
+        -6 .. 6 with node, axis and seed.  A quarter of the angles are the double nearest k*pi/2 (delta = 0), a quarter that
+        double's neighbour one ulp up or down, the rest have delta uniform in (-0.7, 0.7)."""
+        x = self.x_perturbed(seed)
+        idx = self.euler_positions()
+        rng = np.random.default_rng(4321 + seed)
+        node, axis = np.indices(idx.shape)
+        k = (node + 4 * axis + 5 * seed) % 13 - 6
+        theta = np.array([[nearest_quarter_turn(int(kk)) for kk in row] for row in k])
+        kind = rng.integers(4, size=idx.shape)       # 0: the multiple itself, 1: a neighbour, 2 and 3: anywhere in the quadrant
+        towards = np.where(rng.integers(2, size=idx.shape) == 1, np.inf, -np.inf)
+        delta = rng.uniform(-0.7, 0.7, size=idx.shape)
+        theta = np.where(kind == 1, np.nextafter(theta, towards), np.where(kind >= 2, theta + delta, theta))
+        x[idx] = theta
+        return x
+
+    def x_far(self, seed):
+        """x_perturbed(seed) with Euler angles on both sides of the 1e5 switch of sincos_fast: |theta| uniform in
+        [5e4, 1e5) where node + axis is even and in [1e5, 3e5] where it is odd, with random sign."""
+        x = self.x_perturbed(seed)
+        idx = self.euler_positions()
+        rng = np.random.default_rng(8765 + seed)
+        node, axis = np.indices(idx.shape)
+        below = np.minimum(rng.uniform(5e4, 1e5, size=idx.shape), np.nextafter(1e5, 0.0))
+        above = rng.uniform(1e5, 3e5, size=idx.shape)
+        x[idx] = rng.choice([-1.0, 1.0], size=idx.shape) * np.where((node + axis) % 2 == 0, below, above)
+        return x
+
+    def nudged(self, x, direction):
+        """x with every base-ang variable moved one ulp up (direction > 0) or down: how far the reference's own output moves
+        under it is the yardstick for points where the parity bar alone is below the conditioning of the problem"""
+        vs = [v for v in self.S.var_sets if v["name"] == "base-ang"][0]
+        y = np.array(x, dtype=np.float64)
+        seg = slice(vs["offset"], vs["offset"] + vs["size"])
+        y[seg] = np.nextafter(y[seg], np.inf if direction > 0 else -np.inf)
+        return y
+
+
+_HALF_PI = Fraction(1.5707963267948966) + Fraction(6.123233995736766e-17)   # pi/2 to 1e-33
+
+
+def nearest_quarter_turn(k):
+    """the double nearest k * pi/2 (the exact rational product, rounded once)"""
+    return float(k * _HALF_PI)
 
 
 def hopper_schedule():

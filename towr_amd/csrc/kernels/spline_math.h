@@ -86,42 +86,126 @@ TWR_DEV void cross3(const double a[3], const double b[3], double o[3]) {
   o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// sin and cos of one Euler angle.  Cody-Waite reduction by pi/2 in three FMA steps and the fdlibm
-// minimax kernels (k_sin.c / k_cos.c coefficients), ~35 FP64 instructions for both results and
-// accurate to about 1 ulp for |x| < 1e5; anything larger (or non-finite) takes the ocml path.
-// The reference calls libm sin/cos (euler_converter.cc:133-221); the difference is rounding level.
-TWR_DEV void sincos_fast(double x, double* __restrict__ s, double* __restrict__ c) {
-  if (!(fabs(x) < 1.0e5)) {
-    sincos(x, s, c);
-    return;
-  }
-  // (the constants pass through an empty asm: they are then materialised where they are used -- two s_mov each -- instead
-  // of being hoisted out of the persistent loops, where the register allocator ends up spilling them to scratch)
-  auto K = [](double c) {
+// A constant of the trigonometry passes through an empty asm: it is then materialised where it is used -- two s_mov -- instead
+// of being hoisted out of the persistent loops, where the register allocator ends up spilling it to scratch and reloading
+// it in the loop.  That holds for the cold side as well: its constants are hoisted just the same.
+struct InPlace {
+  TWR_DEV double operator()(double c) const {
     asm volatile("" : "+s"(c));
     return c;
-  };
-  const double n = rint(x * K(6.36619772367581382433e-01));
-  double r = fma(-n, K(1.5707963267948966e+00), x);
-  r = fma(-n, K(6.1232339957367574e-17), r);
-  r = fma(-n, K(8.4784276603688985e-32), r);
+  }
+};
+// The fdlibm minimax kernels (k_sin.c / k_cos.c coefficients) on a reduced argument |r| <= pi/4.
+TWR_DEV void sincos_reduced(double r, double& sr, double& cr) {
+  const InPlace K;
   const double z = r * r;
   double ps = fma(z, K(1.58969099521155010221e-10), K(-2.50507602534068634195e-08));
   ps = fma(z, ps, K(2.75573137070700676789e-06));
   ps = fma(z, ps, K(-1.98412698298579493134e-04));
   ps = fma(z, ps, K(8.33333333332248946124e-03));
   ps = fma(z, ps, K(-1.66666666666666324348e-01));
-  const double sr = fma(z * r, ps, r);
+  sr = fma(z * r, ps, r);
   double pc = fma(z, K(-1.13596475577881948265e-11), K(2.08757232129817482790e-09));
   pc = fma(z, pc, K(-2.75573143513906633035e-07));
   pc = fma(z, pc, K(2.48015872894767294178e-05));
   pc = fma(z, pc, K(-1.38888888888741095749e-03));
   pc = fma(z, pc, K(4.16666666666666019037e-02));
-  const double cr = fma(z * z, pc, fma(z, -0.5, 1.0));
-  const int q = (int)n & 3;
+  cr = fma(z * z, pc, fma(z, -0.5, 1.0));
+}
+// sin and cos of the reduced argument of quadrant q = n mod 4, where x = n * pi/2 + r
+TWR_DEV void sincos_quadrant(int q, double sr, double cr, double* __restrict__ s, double* __restrict__ c) {
   const double ss = (q & 1) ? cr : sr, cc = (q & 1) ? sr : cr;
   *s = (q & 2) ? -ss : ss;
   *c = ((q + 1) & 2) ? -cc : cc;
+}
+
+// sin and cos of a finite |x| >= 1e5 (the cold side of sincos_fast): Payne-Hanek reduction in integers.  |x| = m * 2^e with a
+// 53-bit m; the digits of 2/pi that weigh 4 or more in x * 2/pi only add multiples of 2 pi, so a window of 192 digits from
+// weight 2 downwards times m, modulo 2^192, is (x * 2/pi mod 4) * 2^190 to within 2^53 units.  No double lies closer to a
+// multiple of pi/2 than 2^-61 of its size (6381956970095103 * 2^797 does), which leaves 2^-76 of the reduced argument: it is
+// carried as a double-double through the multiplication by pi/2 into the kernels' first-order corrections.  The library
+// sincos keeps an absolute 2^-104 here and misses that case's cosine by 405 ulp; this stays within 1.5 ulp (tests/test_trig_probe.py).
+// The digits come from v_trig_preop_f64, four segments of 53, which starts at the digit of weight 2 itself once the biased
+// exponent exceeds 1077 and at the first digit below that.  No memory is read: a load here, cold as it is, sits inside the
+// persistent loops of every evaluation kernel and cost the flagship 4 % (a table of 2/pi was tried first).
+TWR_DEV void sincos_far(double x, double* __restrict__ s, double* __restrict__ c) {
+  const double ax = fabs(x);
+  const uint64_t bits = (uint64_t)__double_as_longlong(ax);
+  const int eb = (int)(bits >> 52);         // biased exponent: 1039 .. 2046
+  const uint64_t m = (bits & 0xFFFFFFFFFFFFFull) | (1ull << 52);
+  const int lead = eb > 1077 ? eb - 1077 : 0;                  // digits the instruction skips
+  const int back = 53 + lead - (eb >= 1968 ? 128 : 0);         // segment j is an integer below 2^53 times 2^-(back + 53 j)
+  const uint64_t c0 = (uint64_t)ldexp(__builtin_amdgcn_trig_preop(ax, 0), back);
+  const uint64_t c1 = (uint64_t)ldexp(__builtin_amdgcn_trig_preop(ax, 1), back + 53);
+  const uint64_t c2 = (uint64_t)ldexp(__builtin_amdgcn_trig_preop(ax, 2), back + 106);
+  const uint64_t c3 = (uint64_t)ldexp(__builtin_amdgcn_trig_preop(ax, 3), back + 159);
+  // the 212 digits as (w3:w2:w1:w0), then the 192 from the digit of weight 2 on: below exponent 1077 that digit lies
+  // 1077 - eb places in front of the first one (zeros)
+  const uint64_t w0 = c3 | (c2 << 53), w1 = (c2 >> 11) | (c1 << 42), w2 = (c1 >> 22) | (c0 << 31), w3 = c0 >> 33;
+  const int sh = 20 + (eb < 1077 ? 1077 - eb : 0);             // 20 .. 58
+  const uint64_t p0 = (w0 >> sh) | (w1 << (64 - sh)), p1 = (w1 >> sh) | (w2 << (64 - sh)), p2 = (w2 >> sh) | (w3 << (64 - sh));
+  // y = (m * (p2:p1:p0)) mod 2^192 = (y2:y1:y0), x * 2/pi mod 4 = y / 2^190
+  uint64_t y0 = m * p0;
+  const uint64_t mid = m * p1;
+  uint64_t y1 = mid + __umul64hi(m, p0);
+  uint64_t y2 = m * p2 + __umul64hi(m, p1) + (y1 < mid ? 1u : 0u);
+  const uint64_t n = (y2 + (1ull << 61)) >> 62;   // nearest integer (4 stands for 0)
+  y2 -= n << 62;                                  // the signed remainder, |y| <= 2^189
+  const bool neg = (int64_t)y2 < 0;
+  if (neg) {                                      // magnitude and sign
+    y0 = ~y0 + 1;
+    y1 = ~y1 + (y0 == 0 ? 1u : 0u);
+    y2 = ~y2 + ((y0 == 0 && y1 == 0) ? 1u : 0u);
+  }
+  int shift = 0;                                  // normalise: the leading one to bit 63 of y2
+  if (y2 == 0) { y2 = y1; y1 = y0; y0 = 0; shift = 64; }
+  if (y2 == 0) { y2 = y1; y1 = 0; shift = 128; }
+  double fh = 0.0, fl = 0.0;                      // y / 2^190 = fh + fl
+  if (y2 != 0) {
+    const int lz = __clzll((long long)y2);
+    const uint64_t a = lz ? (y2 << lz) | (y1 >> (64 - lz)) : y2;
+    const uint64_t lo = lz ? (y1 << lz) | (y0 >> (64 - lz)) : y1;
+    shift += lz;
+    fh = ldexp((double)(a >> 11), -51 - shift);                           // 53 digits: exact
+    fl = ldexp((double)(((a & 0x7FFull) << 53) | (lo >> 11)), -115 - shift);
+  }
+  if (neg) { fh = -fh; fl = -fl; }
+  const InPlace K;
+  const double pio2_h = K(1.5707963267948966e+00), pio2_l = K(6.1232339957367660e-17);
+  const double rh = fh * pio2_h;
+  const double rl = fma(fh, pio2_l, fl * pio2_h) + fma(fh, pio2_h, -rh);
+  double sr, cr;
+  sincos_reduced(rh, sr, cr);
+  double sa, ca;                                  // of |x|: sin(rh + rl) = sin rh + rl cos rh, cos(rh + rl) = cos rh - rl sin rh
+  sincos_quadrant((int)(n & 3), fma(rl, cr, sr), fma(-rl, sr, cr), &sa, &ca);
+  *s = x < 0.0 ? -sa : sa;
+  *c = ca;
+}
+
+// sin and cos of one Euler angle.  Cody-Waite reduction by pi/2 in three FMA steps and the fdlibm
+// minimax kernels, ~35 FP64 instructions for both results; a larger finite |x| takes sincos_far.
+// Measured against a 60-digit reference (tests/test_trig_probe.py): within 1.51 ulp for |x| < 1e5
+// and within 1.47 ulp above.  +-Inf and NaN give NaN.
+// The reference calls libm sin/cos (euler_converter.cc:133-221); the difference is rounding level.
+TWR_DEV void sincos_fast(double x, double* __restrict__ s, double* __restrict__ c) {
+  if (!(fabs(x) < 1.0e5)) {
+    if (fabs(x) < __builtin_inf()) sincos_far(x, s, c);
+    else *s = *c = x - x;
+    return;
+  }
+  const InPlace K;
+  // On |x|, the sign of x going onto the sine at the end: every step is odd in x, so this is the same bits as reducing x
+  // itself -- except at -0, where the reduction (-0 - (-0) * pi/2) and the polynomial (r + r^3 * p) both lose the sign of
+  // zero that the sine has to keep.
+  const double ax = fabs(x);
+  const double n = rint(ax * K(6.36619772367581382433e-01));
+  double r = fma(-n, K(1.5707963267948966e+00), ax);
+  r = fma(-n, K(6.1232339957367574e-17), r);
+  r = fma(-n, K(8.4784276603688985e-32), r);
+  double sr, cr, sa;
+  sincos_reduced(r, sr, cr);
+  sincos_quadrant((int)n & 3, sr, cr, &sa, c);
+  *s = __builtin_signbit(x) ? -sa : sa;
 }
 
 // ---------------------------------------------------------------- quad helpers
