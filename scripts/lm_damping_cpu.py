@@ -34,7 +34,7 @@ def cases():
 
 
 def cgls(A, b, w, mu, iters, tol):
-    """twr_jac_lsq_solve's iteration (tests/test_jac_lsq.py::_cgls)."""
+    """twr_jac_lsq_solve's iteration (tests/jac_ref.py::cgls)."""
     d = np.zeros(A.shape[1])
     r = b.copy()
     s = A.T @ (w * r)

@@ -9,46 +9,30 @@ Step accuracy.  The system is the first step's of the Gram loop, (C_f N C_f + mu
 mu = 1e-2 lambda_max(C_f N C_f) from a dense eigensolve, so cond <= 101; tol = 1e-10, cap 3000.  CG stops when its recurred
 gradient is below tol |s0|; with |e - e*| <= |residual| / mu and |e*| >= |s0| / (lambda_max + mu) that is
 |e - e*| <= 101 tol |e*|, and the bound asserted is 2 * 101 * tol in e = d / c over the free variables (the 2 for the drift of the
-recurred gradient, the bound of tests/test_jac_lsq.py).  Measured: at most 1.85e-9 in e; in d (what the device test compares,
+recurred gradient, the bound of tests/jac_ref.py).  Measured: at most 1.85e-9 in e; in d (what the device test compares,
 STEP_FIGURE) at most 2.57e-9 over both input sets (C4 stairs; 1.85e-9 over the 15), in 37 to 95 iterations.
 
 LM loop.  Final merit after 8 steps within [0.5, 2] of the CGLS loop's.  Measured: 0.9718 .. 1.0044 on the 15 inputs, equal accept
 sequences on all of them.  Under a 2e-8 relative jitter of every step (16 draws, python scripts/gram_cpu.py --seeds 3
---jitter-draws 16) the Gram loop's own final merit moves by the factors of JITTER_MEASURED below; a seed above 1.4 is dropped
+--jitter-draws 16) the Gram loop's own final merit moves by the factors of JITTER_MEASURED (tests/jac_ref.py, with the
+other figures the device tests share); a seed above 1.4 is dropped
 from the loop comparison by the rule of DESIGN 6.L (DROPPED: ANYmal seed 1 and biped SETS_ALL seed 0, the two seeds the CGLS loop
 flips on as well), and no input is dropped for another reason."""
-import functools
 import os
 import sys
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from .jac_ref import COND, DEVICE_INPUTS, DROPPED, JITTER_MEASURED, ROOT, STEP_FIGURE, TOL, case_of
+
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 import gram_cpu as gc  # noqa: E402
 import lm_box_cpu as lb  # noqa: E402
 
-from .common import baseline_cases  # noqa: E402
-
-TOL, CAP, COND = 1e-10, 3000, 101.0
+CAP = 3000
 INPUTS = [(name, seed) for name in gc.CASES for seed in range(3)]
-DEVICE_INPUTS = [(name, 0) for name in list(baseline_cases()) + ["hopper_all", "biped_all"]]
-# |d - d_direct| / |d_direct| of the restatement: the largest over INPUTS and DEVICE_INPUTS as measured by test_step_*; the
-# device test's bound is ten times this (tests/test_jac_gram.py), the project's convention
-STEP_FIGURE = 2.6e-9
-# the Gram loop's jitter factors (see above), seed by seed, and the seeds the rule drops
-JITTER_MEASURED = {("anymal", 0): 1.033, ("anymal", 1): 104.7, ("anymal", 2): 1.0001, ("C2_biped_K100", 0): 1.0005,
-                   ("C2_biped_K100", 1): 1.0, ("C2_biped_K100", 2): 1.0, ("hopper_all", 0): 1.0, ("hopper_all", 1): 1.0,
-                   ("hopper_all", 2): 1.0, ("C1_hopper", 0): 1.0, ("C1_hopper", 1): 1.0002, ("C1_hopper", 2): 1.0044,
-                   ("biped_all", 0): 1.565, ("biped_all", 1): 1.0002, ("biped_all", 2): 1.0011}
-DROPPED = tuple(k for k, f in JITTER_MEASURED.items() if f > 1.4)
-
-
-@functools.lru_cache(maxsize=None)
-def case_of(name):
-    return baseline_cases()[name]() if name in baseline_cases() else lb.cases()[name]()
 
 
 def step_errors(name, seed):

@@ -4,16 +4,17 @@ restatement (scripts/gram_cpu.py), the masked and scaled rules, bit-reproducibil
 caps, containment of NaN and bad mu / c, the edge cases, hipGraph capture, what the handles report to hold, and the bounded LM
 driver with the Gram solve against the restatement's loop.
 
-The ragged batch is the one of tests/test_jac_lsq.py (_ragged) less the structure of more than 3412 variables, which the Gram
+The ragged batch is the one of tests/jac_device.py (ragged) less the structure of more than 3412 variables, which the Gram
 tables refuse (TWR_ERR_UNSUPPORTED: the solve's six vectors would not fit one workgroup's LDS; checked here), its first 100
 problems: all seven structures, more than one block of every kernel, rows of J of more than 256 entries.
 
 Bounds.  N and N v: every entry within 1e-12 of the sum of the magnitudes of its terms (the bound of the products' tests).  The
 solve on the oracle's Jacobian: |d - d_direct| <= 10 STEP_FIGURE |d_direct| = 2.6e-8, ten times what the restatement measures on
 the same inputs (tests/test_gram_cpu.py: 2.57e-9).  Where mu is chosen here it is 1e-2 max_i sum_j |C N C|_ij >= 1e-2 lambda_max,
-so cond <= 101 and |e - e_direct| <= 2 * 101 * tol |e_direct| in e = d / c (the bound of tests/test_jac_lsq.py).  The driver: the
+so cond <= 101 and |e - e_direct| <= 2 * 101 * tol |e_direct| in e = d / c (the bound of tests/jac_ref.py).  The driver: the
 merit after one step within 1e-6 relative of the restatement's loop, after 8 steps within [0.5, 2] (the bounds of
-tests/test_jac_lm.py, on its problems: none of them is a seed the jitter rule of tests/test_gram_cpu.py drops)."""
+tests/test_jac_lm.py, on its problems, GROUPS of tests/jac_ref.py: none of them is a seed the jitter rule of tests/test_gram_cpu.py
+drops)."""
 import functools
 import os
 import sys
@@ -25,96 +26,33 @@ import scipy.sparse as sp
 import towr_amd as ta
 
 from .common import baseline_cases, random_case
-from .test_jac_lm import GROUPS, STEPS, F, _case, _Lm
-from .test_jac_lsq import COND, TOL, _Batch, _dev, _ragged, _same_bits, _torch
+from .jac_device import F, GramBatch, JacBatch, LmBatch, assert_replay_equals_eager, capture, dev, nan, ragged, ragged_x, torch_ctx
+from .jac_ref import COND, DEVICE_INPUTS, DROPPED, GROUPS, ITERS, ROOT, STEP_FIGURE, STEPS, TOL, case_of, lm_case, same_bits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 import gram_cpu as gc  # noqa: E402
 
-from .test_gram_cpu import DEVICE_INPUTS, DROPPED, STEP_FIGURE, case_of  # noqa: E402
-
 pytestmark = pytest.mark.gpu
 
 MAX_VARS = 3412   # the limit of twr_jac_ops_reserve_gram (include/towr_amd.h)
-ITERS = 200
 groups = pytest.mark.parametrize("group", list(GROUPS))
-
-
-def _nan(n):
-    torch, dev, _ = _torch()
-    return torch.full((max(1, int(n)),), float("nan"), dtype=torch.float64, device=dev)
-
-
-class _Gram:
-    """JacOps + JacLsq with the Gram tables reserved, the layout of N and every problem's pattern."""
-
-    def __init__(self, structs, order):
-        self.B = _Batch(structs, order)
-        self.ops, self.lsq, self.P = self.B.ops, self.B.lsq, self.B.P
-        self.ops.reserve_gram()
-        self.xo, self.go, self.jo = self.B.xo, self.B.go, self.B.jo
-        self.no = self.ops.gram_layout()
-        pats = [S.gram_pattern() for S in structs]
-        self.pat = [pats[s] for s in self.B.order]
-        self.structs = structs
-
-    def form(self, jac, w=None, stream=None):
-        torch, dev, st = _torch()
-        N = _nan(self.no[-1])
-        self.ops.gram_device(jac.data_ptr(), N.data_ptr(), d_w=0 if w is None else w.data_ptr(), stream=st if stream is None else stream)
-        torch.cuda.synchronize()
-        return N
-
-    def mul(self, N, v, stream=None):
-        torch, dev, st = _torch()
-        u = _nan(self.xo[-1])
-        self.ops.gram_mul_device(N.data_ptr(), v.data_ptr(), u.data_ptr(), stream=st if stream is None else stream)
-        torch.cuda.synchronize()
-        return u.cpu().numpy()[:int(self.xo[-1])]
-
-    def tmul(self, jac, t):
-        torch, dev, st = _torch()
-        z = _nan(self.xo[-1])
-        self.ops.tmul_device(jac.data_ptr(), t.data_ptr(), z.data_ptr(), st)
-        torch.cuda.synchronize()
-        return z
-
-    def solve(self, N, z, mu, c=None, iters=ITERS, tol=TOL, stream=None):
-        torch, dev, st = _torch()
-        d, info = _nan(self.xo[-1]), _nan(4 * self.P)
-        self.lsq.solve_gram_device(N.data_ptr(), z.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), iters, tol,
-                                   d_scale=0 if c is None else c.data_ptr(), stream=st if stream is None else stream)
-        torch.cuda.synchronize()
-        return d.cpu().numpy()[:int(self.xo[-1])], info.cpu().numpy().reshape(-1, 4)
-
-    def csr(self, p, N_h):
-        rp, ci = self.pat[p]
-        n = len(rp) - 1
-        return sp.csr_matrix((N_h[self.no[p]:self.no[p] + len(ci)], ci, rp), shape=(n, n))
-
-    def xs(self, p):
-        return slice(self.xo[p], self.xo[p + 1])
-
-    def gs(self, p):
-        return slice(self.go[p], self.go[p + 1])
 
 
 @functools.lru_cache(maxsize=None)
 def _ragged_gram(n=100):
     """The ragged batch the Gram tables take, linearised on the device at x_perturbed: shared by the tests, never changed."""
-    cases, order = _ragged()
+    cases, order = ragged()
     keep = [i for i, c in enumerate(cases) if c.S.n <= MAX_VARS]
     assert len(keep) == len(cases) - 1 and cases[3].S.n > MAX_VARS
     with pytest.raises(ta.TowrError, match="error -5.*variables"):   # the limit fires at reserve time, for the whole handle
         ta.JacOps([cases[0].S, cases[3].S], [0, 1]).reserve_gram()
     pairs = [(i, s) for i, s in enumerate(order) if s in keep][:n]
-    G = _Gram([cases[i].S for i in keep], [keep.index(s) for _, s in pairs])
-    x = _dev(np.concatenate([cases[s].x_perturbed(i) for i, s in pairs]))
-    g, jac = G.B.eval(x)
-    r, wa, _ = G.B.violation(g)
-    assert len(set(G.B.order)) == len(keep) and max(int(np.diff(S.row_ptr).max()) for S in G.structs) > 256
+    G = GramBatch([cases[i].S for i in keep], [keep.index(s) for _, s in pairs])
+    x = dev(np.concatenate([cases[s].x_perturbed(i) for i, s in pairs]))
+    g, jac = G.eval(x)
+    r, wa, _ = G.violation(g)
+    assert len(set(G.order)) == len(keep) and max(int(np.diff(S.row_ptr).max()) for S in G.structs) > 256
     assert (G.no % 2 == 0).all()
     return G, jac, -r, wa
 
@@ -133,20 +71,20 @@ def test_gram_against_scipy_on_a_ragged_batch():
     rng = np.random.default_rng(41)
     w_h = rng.uniform(0.0, 3.0, size=int(G.go[-1]))
     w_h[rng.integers(0, w_h.size, size=w_h.size // 10)] = 0.0   # non-negative, some exactly 0 (an inactive row)
-    ones = _dev(np.ones(int(G.go[-1])))
+    ones = dev(np.ones(int(G.go[-1])))
     N_null = G.form(jac).cpu().numpy()
-    assert _same_bits(N_null, G.form(jac, ones).cpu().numpy()), "d_w = NULL is not unit weights bit for bit"
-    for name, N_h, wh in (("unit", N_null, np.ones(w_h.size)), ("random", G.form(jac, _dev(w_h)).cpu().numpy(), w_h)):
+    assert same_bits(N_null, G.form(jac, ones).cpu().numpy()), "d_w = NULL is not unit weights bit for bit"
+    for name, N_h, wh in (("unit", N_null, np.ones(w_h.size)), ("random", G.form(jac, dev(w_h)).cpu().numpy(), w_h)):
         worst = 0.0
         for p in range(G.P):
-            A = G.B.A(p, jac_h)
+            A = G.A(p, jac_h)
             W = sp.diags(wh[G.gs(p)])
             ref, mag = (A.T @ W @ A).toarray(), (abs(A).T @ W @ abs(A)).toarray()
             got = G.csr(p, N_h)
             assert not np.isnan(got.data).any(), (name, p, "a stored value was not written")
             dense = got.toarray()
             err = np.abs(dense - ref)
-            assert (err <= 1e-12 * mag).all(), (name, p, G.B.order[p], float((err / np.maximum(mag, 1e-300)).max()))
+            assert (err <= 1e-12 * mag).all(), (name, p, G.order[p], float((err / np.maximum(mag, 1e-300)).max()))
             assert np.array_equal(dense.view(np.int64), dense.T.copy().view(np.int64)), (name, p, "N_ij and N_ji differ in their bits")
             worst = max(worst, float((err / np.maximum(mag, 1e-300)).max()))
         print("%s weights: worst |N - ref| / sum|terms| %.2e over %d problems" % (name, worst, G.P))
@@ -157,13 +95,13 @@ def test_gram_mul_against_scipy_on_the_same_matrices():
     N = G.form(jac, wa)
     N_h = N.cpu().numpy()
     v_h = np.random.default_rng(42).normal(size=int(G.xo[-1]))
-    u = G.mul(N, _dev(v_h))
+    u = G.mul(N, dev(v_h))
     worst = 0.0
     for p in range(G.P):
         Nc = G.csr(p, N_h)
         ref, mag = Nc @ v_h[G.xs(p)], abs(Nc) @ np.abs(v_h[G.xs(p)])
         err = np.abs(u[G.xs(p)] - ref)
-        assert (err <= 1e-12 * mag).all(), (p, G.B.order[p], float((err / np.maximum(mag, 1e-300)).max()))
+        assert (err <= 1e-12 * mag).all(), (p, G.order[p], float((err / np.maximum(mag, 1e-300)).max()))
         empty = np.diff(G.pat[p][0]) == 0
         assert not u[G.xs(p)][empty].any() and not np.signbit(u[G.xs(p)][empty]).any(), (p, "an empty row of N is not an exact 0")
         worst = max(worst, float((err / np.maximum(mag, 1e-300)).max()))
@@ -173,18 +111,18 @@ def test_gram_mul_against_scipy_on_the_same_matrices():
 # ---------------------------------------------------------------- 3. the solve against a direct solve and the restatement
 
 def test_solve_against_a_dense_solve_on_the_oracle_jacobian():
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     cases = [case_of(name) for name, _ in DEVICE_INPUTS]
-    G = _Gram([c.S for c in cases], range(len(cases)))
+    G = GramBatch([c.S for c in cases], range(len(cases)))
     sys_ = [gc.first_system(c, seed) for c, (_, seed) in zip(cases, DEVICE_INPUTS)]   # (A, w, N, z, cf, b) on the oracle's J
-    jac = _dev(np.concatenate([q[0].data for q in sys_]))
-    w = _dev(np.concatenate([q[1] for q in sys_]))
-    wb = _dev(np.concatenate([q[1] * q[5] for q in sys_]))
-    c = _dev(np.concatenate([q[4] for q in sys_]))
+    jac = dev(np.concatenate([q[0].data for q in sys_]))
+    w = dev(np.concatenate([q[1] for q in sys_]))
+    wb = dev(np.concatenate([q[1] * q[5] for q in sys_]))
+    c = dev(np.concatenate([q[4] for q in sys_]))
     mu_h = [gc.mu_of(q[2], q[4]) for q in sys_]
     N = G.form(jac, w)
     z = G.tmul(jac, wb)
-    d, info = G.solve(N, z, _dev(mu_h), c)
+    d, info = G.solve(N, z, dev(mu_h), c)
     for p, (q, (name, seed)) in enumerate(zip(sys_, DEVICE_INPUTS)):
         dd = gc.dense_step(q[2], q[3], mu_h[p], q[4])
         err = np.linalg.norm(d[G.xs(p)] - dd) / np.linalg.norm(dd)
@@ -205,29 +143,29 @@ def test_iteration_counts_equal_the_restatement_on_the_ragged_batch():
     why the kernel has no fused multiply-add and the restatement follows its order.  With the same arithmetic the two agree
     in every bit: counts, |s| / |s0|, |s0| and d.  d is also held to plain numpy's, to 1e-6."""
     G, jac, b, wa = _ragged_gram()
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     N = G.form(jac, wa)
     z = G.tmul(jac, wa * b)
     N_h, z_h = N.cpu().numpy(), z.cpu().numpy()
-    colsq = _nan(G.xo[-1])
-    c = _nan(G.xo[-1])
+    colsq = nan(G.xo[-1])
+    c = nan(G.xo[-1])
     G.ops.col_sqnorms_device(jac.data_ptr(), colsq.data_ptr(), d_w=wa.data_ptr(), stream=st)
     G.lsq.col_scale_device(colsq.data_ptr(), c.data_ptr(), 1e-12, stream=st)
     torch.cuda.synchronize()
     c_h = c.cpu().numpy()
     mats = [G.csr(p, N_h) for p in range(G.P)]
     mu_h = np.array([_mu_of(mats[p], c_h[G.xs(p)]) for p in range(G.P)])
-    d, info = G.solve(N, z, _dev(mu_h), c)
+    d, info = G.solve(N, z, dev(mu_h), c)
     off, other_bits, plain_off = [], [], 0
     for p in range(G.P):
         k, d_np, rel, status = gc.gram_cg_device(mats[p], z_h[G.xs(p)], mu_h[p], c_h[G.xs(p)], ITERS, TOL)
         k_plain, d_plain, _, _ = gc.gram_cg(mats[p], z_h[G.xs(p)], mu_h[p], c_h[G.xs(p)], ITERS, TOL)
-        assert status == 0 and info[p, 3] == 0 and info[p, 1] <= TOL, (p, G.B.order[p], info[p], k, rel)
+        assert status == 0 and info[p, 3] == 0 and info[p, 1] <= TOL, (p, G.order[p], info[p], k, rel)
         assert np.linalg.norm(d[G.xs(p)] - d_plain) <= 1e-6 * np.linalg.norm(d_plain), p   # the same iterates up to rounding
         plain_off += int(info[p, 0] != k_plain)
         if info[p, 0] != k:
-            off.append((p, G.B.order[p], int(info[p, 0]), k, float(info[p, 1]), float(rel)))
-        if not (_same_bits(d[G.xs(p)], d_np) and info[p, 1] == rel):
+            off.append((p, G.order[p], int(info[p, 0]), k, float(info[p, 1]), float(rel)))
+        if not (same_bits(d[G.xs(p)], d_np) and info[p, 1] == rel):
             other_bits.append(p)
     print("iteration counts: %d of %d problems differ from the restatement in the device's order (problem, structure, device, numpy, "
           "|s|/|s0| device, numpy): %s; %d differ in the bits of d or |s|/|s0|; %d differ from plain numpy's count"
@@ -247,11 +185,11 @@ def test_iteration_counts_equal_the_restatement_under_heavy_damping():
     N_h, z_h = N.cpu().numpy(), z.cpu().numpy()
     mats = [G.csr(p, N_h) for p in range(G.P)]
     mu_h = np.array([1e3 * _mu_of(mats[p], np.ones(G.xo[p + 1] - G.xo[p])) for p in range(G.P)])
-    d, info = G.solve(N, z, _dev(mu_h))
+    d, info = G.solve(N, z, dev(mu_h))
     counts = set()
     for p in range(G.P):
         k, d_np, rel, status = gc.gram_cg(mats[p], z_h[G.xs(p)], mu_h[p], np.ones(G.xo[p + 1] - G.xo[p]), ITERS, TOL)
-        assert status == 0 and info[p, 3] == 0 and info[p, 0] == k and k < 12, (p, G.B.order[p], info[p], k, rel)
+        assert status == 0 and info[p, 3] == 0 and info[p, 0] == k and k < 12, (p, G.order[p], info[p], k, rel)
         assert np.linalg.norm(d[G.xs(p)] - d_np) <= 1e-12 * np.linalg.norm(d_np), p
         counts.add(k)
     print("iteration counts under heavy damping: %s" % sorted(counts))
@@ -264,7 +202,7 @@ def _small():
     """The first 12 ragged problems as a batch of their own, with N, z, a scale with zeros in it and mu: shared, never changed."""
     G0, jac0, b0, wa0 = _ragged_gram()
     P = 12
-    G = _Gram(G0.structs, G0.B.order[:P])
+    G = GramBatch(G0.structs, G0.order[:P])
     jac, b, wa = jac0[:int(G.jo[-1])].clone(), b0[:int(G.go[-1])].clone(), wa0[:int(G.go[-1])].clone()
     N = G.form(jac, wa)
     z = G.tmul(jac, wa * b)
@@ -279,7 +217,7 @@ def _small():
 def test_masked_and_scaled_rules():
     G, jac, wa, N, z, c_h, mu_h = _small()
     N_h, z_h = N.cpu().numpy(), z.cpu().numpy()
-    d, info = G.solve(N, z, _dev(mu_h), _dev(c_h))
+    d, info = G.solve(N, z, dev(mu_h), dev(c_h))
     assert (info[:, 3] == 0).all() and (c_h == 0).sum() > 100
     assert not d[c_h == 0].any() and not np.signbit(d[c_h == 0]).any(), "a masked variable is not an exact +0"
     for p in range(G.P):   # the columns taken out by hand, a dense solve
@@ -291,10 +229,10 @@ def test_masked_and_scaled_rules():
         s0 = np.linalg.norm(np.where(free, c * z_h[G.xs(p)], 0.0))
         assert abs(info[p, 2] - s0) <= 1e-12 * s0, (p, "|s0| is not taken over the free space")
     # c = 1 gives the bits of d_scale = NULL
-    mu1 = _dev(np.array([_mu_of(G.csr(p, N_h), np.ones(G.xo[p + 1] - G.xo[p])) for p in range(G.P)]))
+    mu1 = dev(np.array([_mu_of(G.csr(p, N_h), np.ones(G.xo[p + 1] - G.xo[p])) for p in range(G.P)]))
     d1, i1 = G.solve(N, z, mu1, None)
-    d2, i2 = G.solve(N, z, mu1, _dev(np.ones(int(G.xo[-1]))))
-    assert _same_bits(d1, d2) and _same_bits(i1, i2) and (i1[:, 3] == 0).all()
+    d2, i2 = G.solve(N, z, mu1, dev(np.ones(int(G.xo[-1]))))
+    assert same_bits(d1, d2) and same_bits(i1, i2) and (i1[:, 3] == 0).all()
     # bad input: status 2 and d = 0 for that problem alone
     for what, val in (("c", -1.0), ("c", np.nan), ("c", np.inf), ("mu", -1.0), ("mu", np.nan), ("mu", np.inf)):
         cb, mb = c_h.copy(), mu_h.copy()
@@ -302,27 +240,27 @@ def test_masked_and_scaled_rules():
             cb[G.xo[5] + 7] = val
         else:
             mb[5] = val
-        db, ib = G.solve(N, z, _dev(mb), _dev(cb))
+        db, ib = G.solve(N, z, dev(mb), dev(cb))
         assert ib[5, 3] == 2 and ib[5, 0] == 0 and not db[G.xs(5)].any(), (what, val, ib[5])
         assert np.isnan(ib[5, 1]) if what == "c" and not val < 0 else ib[5, 1] == 1.0, (what, val, ib[5])   # NaN where |s0| is not finite
         rest = np.ones(d.size, dtype=bool)
         rest[G.xs(5)] = False
-        assert _same_bits(db[rest], d[rest]) and _same_bits(np.delete(ib, 5, axis=0), np.delete(info, 5, axis=0)), (what, val)
+        assert same_bits(db[rest], d[rest]) and same_bits(np.delete(ib, 5, axis=0), np.delete(info, 5, axis=0)), (what, val)
 
 
 # ---------------------------------------------------------------- 5. bits
 
 def test_bits_do_not_depend_on_the_batch_the_call_the_stream_or_the_cap():
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     G, jac, wa, N, z, c_h, mu_h = _small()
-    c, mu = _dev(c_h), _dev(mu_h)
-    v = _dev(np.random.default_rng(44).normal(size=int(G.xo[-1])))
+    c, mu = dev(c_h), dev(mu_h)
+    v = dev(np.random.default_rng(44).normal(size=int(G.xo[-1])))
     N_h, u = N.cpu().numpy(), G.mul(N, v)
     d, info = G.solve(N, z, mu, c)
     # repeated calls
-    assert _same_bits(G.form(jac, wa).cpu().numpy(), N_h) and _same_bits(G.mul(N, v), u)
+    assert same_bits(G.form(jac, wa).cpu().numpy(), N_h) and same_bits(G.mul(N, v), u)
     d2, i2 = G.solve(N, z, mu, c)
-    assert _same_bits(d2, d) and _same_bits(i2, info), "two calls differ"
+    assert same_bits(d2, d) and same_bits(i2, info), "two calls differ"
     # another stream
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
@@ -330,39 +268,39 @@ def test_bits_do_not_depend_on_the_batch_the_call_the_stream_or_the_cap():
         N3 = G.form(jac, wa, stream=side.cuda_stream)
         u3 = G.mul(N3, v, stream=side.cuda_stream)
         d3, i3 = G.solve(N3, z, mu, c, stream=side.cuda_stream)
-    assert _same_bits(N3.cpu().numpy(), N_h) and _same_bits(u3, u) and _same_bits(d3, d) and _same_bits(i3, info), "another stream differs"
+    assert same_bits(N3.cpu().numpy(), N_h) and same_bits(u3, u) and same_bits(d3, d) and same_bits(i3, info), "another stream differs"
     # a larger cap; a smaller one stops the rest at the cap and leaves the finished ones alone
     d4, i4 = G.solve(N, z, mu, c, iters=5 * ITERS)
-    assert _same_bits(d4, d) and _same_bits(i4, info)
+    assert same_bits(d4, d) and same_bits(i4, info)
     assert info[:, 0].max() > info[:, 0].min()
     k = int(info[:, 0].min())
     dk, ik = G.solve(N, z, mu, c, iters=k)
     for p in range(G.P):
         if info[p, 0] <= k:
-            assert _same_bits(dk[G.xs(p)], d[G.xs(p)]) and _same_bits(ik[p], info[p]), p
+            assert same_bits(dk[G.xs(p)], d[G.xs(p)]) and same_bits(ik[p], info[p]), p
         else:
             assert ik[p, 3] == 1 and ik[p, 0] == k, ik[p]
     assert len(set(info[:, 0] <= k)) == 2
     # the same problems at other positions of another batch (reversed order, two of them twice)
     perm = list(range(G.P))[::-1] + [3, 0]
-    H = _Gram(G.structs, [G.B.order[p] for p in perm])
+    H = GramBatch(G.structs, [G.order[p] for p in perm])
     cat = lambda t, off: torch.cat([t[int(off[p]):int(off[p + 1])] for p in perm])   # noqa: E731
     jac_h, wa_h, z_h, c_q, v_h = cat(jac, G.jo), cat(wa, G.go), cat(z, G.xo), cat(c, G.xo), cat(v, G.xo)
     NH = H.form(jac_h, wa_h)
     uH = H.mul(NH, v_h)
-    dH, iH = H.solve(NH, z_h, _dev(mu_h[perm]), c_q)
+    dH, iH = H.solve(NH, z_h, dev(mu_h[perm]), c_q)
     NH_h = NH.cpu().numpy()
     for q, p in enumerate(perm):
         nn = len(G.pat[p][1])
-        assert _same_bits(NH_h[H.no[q]:H.no[q] + nn], N_h[G.no[p]:G.no[p] + nn]), (q, p, "N")
-        assert _same_bits(uH[H.xs(q)], u[G.xs(p)]) and _same_bits(dH[H.xs(q)], d[G.xs(p)]) and _same_bits(iH[q], info[p]), (q, p)
+        assert same_bits(NH_h[H.no[q]:H.no[q] + nn], N_h[G.no[p]:G.no[p] + nn]), (q, p, "N")
+        assert same_bits(uH[H.xs(q)], u[G.xs(p)]) and same_bits(dH[H.xs(q)], d[G.xs(p)]) and same_bits(iH[q], info[p]), (q, p)
 
 
 # ---------------------------------------------------------------- 6. poison and edge cases
 
 def test_poison_stays_in_its_problem():
     G, jac, wa, N, z, c_h, mu_h = _small()
-    c, mu = _dev(c_h), _dev(mu_h)
+    c, mu = dev(c_h), dev(mu_h)
     N_h = N.cpu().numpy()
     d, info = G.solve(N, z, mu, c)
     bad, nn = 4, len(G.pat[4][1])
@@ -382,7 +320,7 @@ def test_poison_stays_in_its_problem():
             cp[int(G.xo[bad]) + 1] = float("nan")
         Np = G.form(jp, wp)
         Np_h = Np.cpu().numpy()
-        assert _same_bits(Np_h[rest_n], N_h[rest_n]), (what, "N of another problem changed")
+        assert same_bits(Np_h[rest_n], N_h[rest_n]), (what, "N of another problem changed")
         assert np.isnan(Np_h[G.no[bad]:G.no[bad] + nn]).any() == (what in "Jw"), what
         dp, ip = G.solve(Np, zp, mu, cp)
         assert ip[bad, 3] == 2 and not dp[G.xs(bad)].any(), (what, ip[bad])   # nothing of it was usable: d = 0
@@ -391,9 +329,9 @@ def test_poison_stays_in_its_problem():
         k_np, _, rel_np, st_np = gc.gram_cg(G.csr(bad, Np_h), zp.cpu().numpy()[G.xs(bad)], mu_h[bad], cp.cpu().numpy()[G.xs(bad)], ITERS, TOL)
         k_dv, _, rel_dv, st_dv = gc.gram_cg_device(G.csr(bad, Np_h), zp.cpu().numpy()[G.xs(bad)], mu_h[bad], cp.cpu().numpy()[G.xs(bad)], ITERS, TOL)
         assert (k_np, st_np) == (k_dv, st_dv) == (0, 2) and np.array_equal([rel_np, rel_dv], [ip[bad, 1]] * 2, equal_nan=True), (what, rel_np, rel_dv)
-        assert _same_bits(dp[rest_x], d[rest_x]) and _same_bits(np.delete(ip, bad, axis=0), np.delete(info, bad, axis=0)), what
+        assert same_bits(dp[rest_x], d[rest_x]) and same_bits(np.delete(ip, bad, axis=0), np.delete(info, bad, axis=0)), what
         if what in "Jw":
-            up = G.mul(Np, _dev(np.ones(d.size)))
+            up = G.mul(Np, dev(np.ones(d.size)))
             assert np.isnan(up[G.xs(bad)]).any() and not np.isnan(up[rest_x]).any(), what
 
 
@@ -401,17 +339,17 @@ def test_edge_cases():
     rng = np.random.default_rng(45)
     norows, hopper = random_case(5111).S, baseline_cases()["C1_hopper"]().S
     assert norows.m == 0 and hopper.n % 2 == 1
-    G = _Gram([hopper, norows], [0, 1, 0, 1, 1])
+    G = GramBatch([hopper, norows], [0, 1, 0, 1, 1])
     assert [int(v) for v in np.diff(G.no)] == [len(G.pat[p][1]) + len(G.pat[p][1]) % 2 for p in range(G.P)] and G.no[2] == G.no[1]
-    jac = _dev(rng.normal(size=int(G.jo[-1])))
-    w = _dev(rng.uniform(0.5, 2.0, size=int(G.go[-1])))
+    jac = dev(rng.normal(size=int(G.jo[-1])))
+    w = dev(rng.uniform(0.5, 2.0, size=int(G.go[-1])))
     N = G.form(jac, w)
     N_h = N.cpu().numpy()
     z_h = rng.normal(size=int(G.xo[-1]))
     z_h[G.xs(2)] = 0.0   # z = 0: converged at the start
-    z = _dev(z_h)
+    z = dev(z_h)
     mu_h = np.array([_mu_of(G.csr(p, N_h), np.ones(G.xo[p + 1] - G.xo[p])) for p in range(G.P)])
-    d, info = G.solve(N, z, _dev(mu_h))
+    d, info = G.solve(N, z, dev(mu_h))
     u = G.mul(N, z)
     for p in (1, 3, 4):   # no rows: N = 0, so N v = 0 and (0 + mu I) d = z converges in one iteration to z / mu
         assert not u[G.xs(p)].any() and info[p, 3] == 0 and info[p, 0] == 1
@@ -420,34 +358,34 @@ def test_edge_cases():
     dd = gc.dense_step(G.csr(0, N_h), z_h[G.xs(0)], mu_h[0], np.ones(hopper.n))
     assert info[0, 3] == 0 and np.linalg.norm(d[G.xs(0)] - dd) <= 2 * COND * TOL * np.linalg.norm(dd)
     # z = 0 everywhere on a structure without rows: d = 0, status 0, no iterations
-    d0, i0 = G.solve(N, _dev(np.zeros(int(G.xo[-1]))), _dev(mu_h))
+    d0, i0 = G.solve(N, dev(np.zeros(int(G.xo[-1]))), dev(mu_h))
     assert not d0.any() and (i0 == 0).all()
     # iters = 0: d = 0, |s0|, status 1 where there is something to do
-    dz, iz = G.solve(N, z, _dev(mu_h), iters=0)
+    dz, iz = G.solve(N, z, dev(mu_h), iters=0)
     assert not dz.any() and (iz[:, 0] == 0).all() and list(iz[:, 3]) == [1, 1, 0, 1, 1]
     assert all(abs(iz[p, 2] - np.linalg.norm(z_h[G.xs(p)])) <= 1e-14 * np.linalg.norm(z_h[G.xs(p)]) for p in range(G.P))
     # a batch of one problem: the bits of the same problem in the batch above
-    one = _Gram([hopper], [0])
+    one = GramBatch([hopper], [0])
     j1, w1 = jac[:int(G.jo[1])].clone(), w[:int(G.go[1])].clone()
     N1 = one.form(j1, w1)
-    assert _same_bits(N1.cpu().numpy()[:len(one.pat[0][1])], N_h[:len(one.pat[0][1])])
-    d1, i1 = one.solve(N1, z[:hopper.n].clone(), _dev(mu_h[:1]))
-    assert _same_bits(d1, d[G.xs(0)]) and _same_bits(i1[0], info[0])
+    assert same_bits(N1.cpu().numpy()[:len(one.pat[0][1])], N_h[:len(one.pat[0][1])])
+    d1, i1 = one.solve(N1, z[:hopper.n].clone(), dev(mu_h[:1]))
+    assert same_bits(d1, d[G.xs(0)]) and same_bits(i1[0], info[0])
     # a handle of structures without rows only
-    E = _Gram([norows], [0, 0])
+    E = GramBatch([norows], [0, 0])
     assert E.no[-1] == 0
-    NE = E.form(_dev(np.zeros(1)), None)
-    dE, iE = E.solve(NE, _dev(np.ones(2 * norows.n)), _dev(np.array([2.0, 4.0])))
+    NE = E.form(dev(np.zeros(1)), None)
+    dE, iE = E.solve(NE, dev(np.ones(2 * norows.n)), dev(np.array([2.0, 4.0])))
     assert (iE[:, 3] == 0).all() and np.array_equal(dE, np.repeat([0.5, 0.25], norows.n))
 
 
 # ---------------------------------------------------------------- 7. capture, and what the handles hold
 
 def test_capture_eval_violation_tmul_gram_solve_as_one_graph():
-    torch, dev, _ = _torch()
-    cases, order = _ragged()
+    torch, device, _ = torch_ctx()
+    cases, order = ragged()
     order = [s for s in order if s != 3][:24]
-    B = _Batch([c.S for c in cases], order)
+    B = JacBatch([c.S for c in cases], order)
     ops0 = B.ops.bytes()["resident"]
     B.ops.reserve_gram()
     ops1 = B.ops.bytes()["resident"]
@@ -455,11 +393,10 @@ def test_capture_eval_violation_tmul_gram_solve_as_one_graph():
     B.ops.reserve_gram()
     assert B.ops.bytes()["resident"] == ops1, "the Gram tables are made once"
     X, G_, J, NN = int(B.xo[-1]), int(B.go[-1]), int(B.jo[-1]), int(B.ops.gram_layout()[-1])
-    x0 = np.concatenate([cases[s].x_perturbed(i) for i, s in enumerate(order)])
-    x = _dev(x0)
-    z64 = lambda n: torch.zeros(n, dtype=torch.float64, device=dev)   # noqa: E731
+    x = dev(ragged_x(cases, order))
+    z64 = lambda n: torch.zeros(n, dtype=torch.float64, device=device)   # noqa: E731
     g, jac, r, t, wa, merit, z, N, d, info = z64(G_), z64(J), z64(G_), z64(G_), z64(G_), z64(B.P), z64(X), z64(NN), z64(X), z64(4 * B.P)
-    mu = _dev(np.full(B.P, 50.0))
+    mu = dev(np.full(B.P, 50.0))
     outs = (g, jac, r, t, wa, merit, z, N, d, info)
     lsq0 = B.lsq.bytes()["resident"]
 
@@ -473,29 +410,15 @@ def test_capture_eval_violation_tmul_gram_solve_as_one_graph():
         B.lsq.solve_gram_device(N.data_ptr(), z.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), 25, 1e-6, stream=stream)
         x.add_(d)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):   # warm-up outside the capture (module load)
-        step(side.cuda_stream)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):   # captures on a non-default stream of its own
-        step(torch.cuda.current_stream().cuda_stream)
-    x1 = np.concatenate([cases[s].x_perturbed(100 + i) for i, s in enumerate(order)])
-    x.copy_(torch.from_numpy(x1))
-    for o in outs:
-        o.zero_()
-    graph.replay()
-    torch.cuda.synchronize()
-    got = [o.clone() for o in outs] + [x.clone()]
-    x.copy_(torch.from_numpy(x1))
-    for o in outs:
-        o.zero_()
-    step(torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    for a, e in zip(got, list(outs) + [x]):
-        assert _same_bits(a.cpu().numpy(), e.cpu().numpy())
+    graph = capture(step)
+    x1 = ragged_x(cases, order, seed0=100)
+
+    def reset():
+        x.copy_(torch.from_numpy(x1))
+        for t in outs:
+            t.zero_()
+
+    assert_replay_equals_eager(step, graph, reset, outs + (x,))
     assert info.cpu().numpy().reshape(-1, 4)[:, 0].max() > 3 and d.abs().max().item() > 0
     assert B.ops.bytes()["resident"] == ops1 and B.lsq.bytes()["resident"] == lsq0, "a call after the reserve changed what the handles hold"
 
@@ -504,13 +427,13 @@ def test_capture_eval_violation_tmul_gram_solve_as_one_graph():
 
 @functools.lru_cache(maxsize=None)
 def _gram_run(group):
-    B = _Lm(GROUPS[group], solver="gram")
+    B = LmBatch(GROUPS[group], solver="gram")
     return B, B.run()
 
 
 @functools.lru_cache(maxsize=None)
 def _cpu(name, seed):
-    case, (lo, up) = _case(name)
+    case, (lo, up) = lm_case(name)
     return gc.lm_gram(case, case.x_perturbed(seed), lo, up, steps=STEPS)
 
 
@@ -542,9 +465,9 @@ def test_driver_with_the_gram_solve_against_the_restatement(group):
 
 @groups
 def test_driver_eight_gram_steps_as_one_graph_give_the_eager_bits(group):
-    torch, dev, _ = _torch()
+    torch, device, _ = torch_ctx()
     ref, hist = _gram_run(group)
-    B = _Lm(GROUPS[group], solver="gram")
+    B = LmBatch(GROUPS[group], solver="gram")
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
@@ -559,16 +482,16 @@ def test_driver_eight_gram_steps_as_one_graph_give_the_eager_bits(group):
     torch.cuda.synchronize()
     graph.replay()
     x, rec = B.read()
-    assert _same_bits(x, hist[-1][0]) and _same_bits(rec, hist[-1][1])
+    assert same_bits(x, hist[-1][0]) and same_bits(rec, hist[-1][1])
 
 
 @groups
 def test_driver_left_at_cgls_is_unchanged_and_bytes_grow_at_set_solver(group):
-    a, b = _Lm(GROUPS[group]), _Lm(GROUPS[group], solver="cgls")
+    a, b = LmBatch(GROUPS[group]), LmBatch(GROUPS[group], solver="cgls")
     ops0, lm0 = a.ops.bytes()["resident"], a.lm.bytes()["resident"]
     ha, hb = a.run(), b.run()
     for (xa, ra), (xb, rb) in zip(ha, hb):
-        assert _same_bits(xa, xb) and _same_bits(ra, rb)
+        assert same_bits(xa, xb) and same_bits(ra, rb)
     assert a.ops.bytes()["resident"] == ops0 and a.lm.bytes()["resident"] == lm0, "a CGLS driver holds what it held"
     g, hist = _gram_run(group)
     n_gram = int(g.ops.gram_layout()[-1])

@@ -3,12 +3,12 @@
 biped with TWR_SETS_ALL (optimised timings: box bounds on every phase duration), ANYmal at towr's default grids (n = 640 > 512:
 the lanes of a workgroup loop), a structure without rows (a biped, n = 315); x = x_perturbed(seed), the bounds of
 twr_structure_variable_bounds for the start and goal the guess interpolates (scripts/lm_box_cpu.py::case_bounds).  A twr_batch
-holds structures of one foot count only, so the problems make three ragged batches (GROUPS), one per robot; every test runs on
-each of them.
+holds structures of one foot count only, so the problems make three ragged batches (GROUPS of tests/jac_ref.py, which the CPU
+tests share), one per robot; every test runs on each of them.
 
 Bounds of the comparisons:
   * the masked step against a dense direct solve on the free columns of the ORACLE's Jacobian: those of
-    tests/test_jac_scaled.py::_check_scaled_step (tol 1e-10, mu = 1e-2 lambda_max; true residual <= 2 tol, |e - direct| <= 101 * 2 tol
+    tests/jac_ref.py::check_scaled_step (tol 1e-10, mu = 1e-2 lambda_max; true residual <= 2 tol, |e - direct| <= 101 * 2 tol
     |direct|, under 200 iterations): the same iteration on fewer columns.
   * against scripts/lm_box_cpu.py (numpy on the CPU oracle) on the same inputs: the merit after one step within 1e-6 relative (the
     CPU run moves by up to 1.3e-7 under a 2e-8 relative jitter of its steps on these inputs), the final merit after 8 steps within
@@ -27,107 +27,28 @@ import scipy.sparse as sp
 
 import towr_amd as ta
 
-from .common import random_case
-from .test_jac_scaled import ITERS, REL_FLOOR, TOL, _bits, _check_scaled_step, _dev, _lam_max, _nan, _same_bits, _torch
+from .jac_device import F, LmBatch, dev, lm_inputs, nan, torch_ctx
+from .jac_ref import GROUPS, ITERS, REJECTS_FIRST, ROOT, STEPS, TOL, bits, check_scaled_step, lam_max, lm_case, same_bits
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 import lm_box_cpu as lb  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-GROUPS = {"hopper": (("C1_hopper", 0), ("hopper_all", 0), ("C1_hopper", 1), ("hopper_all", 1), ("C1_hopper", 2), ("hopper_all", 2)),
-          "biped": (("biped_all", 1), ("norows", 0), ("biped_all", 2), ("biped_all", 3)),
-          "anymal": (("anymal", 0), ("anymal", 2))}
-REJECTS_FIRST = ("biped_all", 1)   # rejects its first step on the CPU (tests/test_lm_box_cpu.py)
-STEPS = 8
 groups = pytest.mark.parametrize("group", list(GROUPS))
-F = {k: i for i, k in enumerate(ta.JacLm.FIELDS)}
-
-
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    case = random_case(5111) if name == "norows" else lb.cases()[name]()
-    return case, lb.case_bounds(case)
-
-
-def _inputs(problems):
-    """(structures, order, x0, lo, up) of a batch of (name, seed) problems."""
-    names = []
-    for name, _ in problems:
-        if name not in names:
-            names.append(name)
-    order = [names.index(name) for name, _ in problems]
-    x0 = np.concatenate([_case(name)[0].x_perturbed(seed) for name, seed in problems])
-    lo = np.concatenate([_case(name)[1][0] for name, _ in problems])
-    up = np.concatenate([_case(name)[1][1] for name, _ in problems])
-    return [_case(n)[0].S for n in names], order, x0, lo, up
 
 
 @functools.lru_cache(maxsize=None)
 def _cpu(name, seed):
-    case, (lo, up) = _case(name)
+    case, (lo, up) = lm_case(name)
     return lb.lm_box(case, case.x_perturbed(seed), lo, up, steps=STEPS)
-
-
-class _Lm:
-    """Batch + JacOps + JacLsq + JacLm of one batch, and the caller's buffers."""
-
-    def __init__(self, problems, **params):
-        torch, dev, st = _torch()
-        self.problems = tuple(problems)
-        self.structs, self.order, self.x0, self.lo_h, self.up_h = _inputs(problems)
-        self.batch = ta.Batch(self.structs, self.order, device=0)
-        self.ops = ta.JacOps(self.structs, self.order, device=0)
-        self.lsq = ta.JacLsq(self.ops)
-        self.lm = ta.JacLm(self.batch, self.lsq, **params)
-        self.xo, self.go, self.jo = self.ops.layout()
-        self.P = len(self.order)
-        self.X, self.G, self.J = int(self.xo[-1]), int(self.go[-1]), int(self.jo[-1])
-        self.x, self.lo, self.up = _nan(self.X), _nan(self.X), _nan(self.X)
-        self.g, self.jac, self.rec = _nan(self.G), _nan(self.J), _nan(ta.JacLm.REC * self.P)
-
-    def start(self, x_h=None, lo_h=None, up_h=None, stream=None):
-        torch, dev, st = _torch()
-        self.x[:self.X].copy_(torch.from_numpy(np.ascontiguousarray(self.x0 if x_h is None else x_h)))
-        self.lo[:self.X].copy_(torch.from_numpy(np.ascontiguousarray(self.lo_h if lo_h is None else lo_h)))
-        self.up[:self.X].copy_(torch.from_numpy(np.ascontiguousarray(self.up_h if up_h is None else up_h)))
-        self.lm.start_device(self.x.data_ptr(), self.lo.data_ptr(), self.up.data_ptr(), self.g.data_ptr(), self.jac.data_ptr(),
-                             stream or st)
-
-    def step(self, k=1, stream=None):
-        torch, dev, st = _torch()
-        for _ in range(k):
-            self.lm.step_device(stream or st)
-
-    def read(self, stream=None):
-        """(x, state records [P, 8]) on the host."""
-        torch, dev, st = _torch()
-        self.lm.state_device(self.rec.data_ptr(), stream or st)
-        torch.cuda.synchronize()
-        return self.x.cpu().numpy()[:self.X].copy(), self.rec.cpu().numpy()[:ta.JacLm.REC * self.P].reshape(self.P, -1).copy()
-
-    def run(self, steps=STEPS, **start):
-        """[(x, records)] after the start and after every step."""
-        self.start(**start)
-        hist = [self.read()]
-        for _ in range(steps):
-            self.step()
-            hist.append(self.read())
-        return hist
-
-    def xs(self, p):
-        return slice(self.xo[p], self.xo[p + 1])
-
-    def gs(self, p):
-        return slice(self.go[p], self.go[p + 1])
 
 
 @functools.lru_cache(maxsize=None)
 def _main(group):
     """The batch of a group and its eager run of STEPS steps: shared, never changed."""
-    B = _Lm(GROUPS[group])
+    B = LmBatch(GROUPS[group])
     return B, B.run()
 
 
@@ -136,16 +57,14 @@ def _norows(B, p):
 
 
 def _linearise(B, x_h):
-    """The chain of a step up to the free set with the public calls, at x_h: host copies and device tensors."""
-    torch, dev, st = _torch()
-    x = _dev(x_h)
-    g, jac, r, wa, q, c, z, cf, nf = _nan(B.G), _nan(B.J), _nan(B.G), _nan(B.G), _nan(B.X), _nan(B.X), _nan(B.X), _nan(B.X), _nan(B.P)
-    lo, up = _dev(B.lo_h), _dev(B.up_h)
-    B.batch.eval_device(x.data_ptr(), g.data_ptr(), jac.data_ptr(), ta.EVAL_BOTH, st)
-    B.lsq.violation_device(g.data_ptr(), r.data_ptr(), d_w_active=wa.data_ptr(), stream=st)
+    """The chain of a step up to the free set with the public calls, at x_h: device tensors."""
+    torch, _, st = torch_ctx()
+    x, lo, up = dev(x_h), dev(B.lo_h), dev(B.up_h)
+    g, jac = B.eval(x)
+    r, wa, _ = B.violation(g, merit=False)
     b = -r
-    B.ops.col_sqnorms_device(jac.data_ptr(), q.data_ptr(), d_w=wa.data_ptr(), stream=st)
-    B.lsq.col_scale_device(q.data_ptr(), c.data_ptr(), REL_FLOOR, stream=st)
+    q, c = B.col_scale(jac, wa)
+    z, cf, nf = nan(B.X), nan(B.X), nan(B.P)
     t = wa * b
     B.ops.tmul_device(jac.data_ptr(), t.data_ptr(), z.data_ptr(), st)
     B.lsq.free_set_device(x.data_ptr(), lo.data_ptr(), up.data_ptr(), z.data_ptr(), cf.data_ptr(), nf.data_ptr(), d_scale_in=c.data_ptr(),
@@ -156,7 +75,7 @@ def _linearise(B, x_h):
 
 def _oracle(B, p, x_h):
     """(A, r, w) of problem p at x_h from the CPU oracle."""
-    case = _case(B.problems[p][0])[0]
+    case = lm_case(B.problems[p][0])[0]
     S = case.S
     out = case.P.eval(x_h[B.xs(p)])
     glo, ghi = S.bounds()
@@ -166,7 +85,7 @@ def _oracle(B, p, x_h):
 
 def _oracle_z(problems, xo, p, x_h):
     """z = J^T(w o b) of problem p at x_h from the CPU oracle."""
-    case = _case(problems[p][0])[0]
+    case = lm_case(problems[p][0])[0]
     out = case.P.eval(x_h[xo[p]:xo[p + 1]])
     glo, ghi = case.S.bounds()
     r = out[0] - np.clip(out[0], glo, ghi)
@@ -194,16 +113,6 @@ def _place_on_bounds(problems, xo, x, lo, up, count):
     return np.array(hand, dtype=np.int64)
 
 
-def _solve(B, L, mu, c, masked, iters=ITERS, tol=TOL):
-    torch, dev, st = _torch()
-    d, info = _nan(B.X), _nan(4 * B.P)
-    f = B.lsq.solve_masked_device if masked else B.lsq.solve_scaled_device
-    f(L["jac"].data_ptr(), L["b"].data_ptr(), mu.data_ptr(), c.data_ptr(), d.data_ptr(), info.data_ptr(), iters, tol,
-      d_w=L["wa"].data_ptr(), stream=st)
-    torch.cuda.synchronize()
-    return d.cpu().numpy()[:B.X], info.cpu().numpy()[:4 * B.P].reshape(-1, 4)
-
-
 # ---------------------------------------------------------------- 1. the masked step
 
 @groups
@@ -214,15 +123,15 @@ def test_masked_step_against_a_direct_solve_on_the_free_columns(group):
     b_h, w_h, c_h, cf_h, jac_h, q_h = (L[k].cpu().numpy() for k in ("b", "wa", "c", "cf", "jac", "q"))
     assert np.isfinite(c_h[:B.X]).all() and (c_h[:B.X] > 0).all()
     free = cf_h[:B.X] != 0
-    assert _same_bits(cf_h[:B.X][free], c_h[:B.X][free]) and not np.signbit(cf_h[:B.X][~free]).any()
+    assert same_bits(cf_h[:B.X][free], c_h[:B.X][free]) and not np.signbit(cf_h[:B.X][~free]).any()
     mu_h = np.zeros(B.P)
     for p in range(B.P):
         S = B.structs[B.order[p]]
         A = sp.csr_matrix((jac_h[B.jo[p]:B.jo[p + 1]], S.col_idx, S.row_ptr), shape=(S.m, S.n))
-        mu_h[p] = 1e-2 * _lam_max((A @ sp.diags(cf_h[B.xs(p)])).tocsr(), w_h[B.gs(p)])
-    d, info = _solve(B, L, _dev(mu_h), L["cf"], True)
+        mu_h[p] = 1e-2 * lam_max((A @ sp.diags(cf_h[B.xs(p)])).tocsr(), w_h[B.gs(p)])
+    d, info = B.solve(L["jac"], L["b"], L["wa"], dev(mu_h), L["cf"], "masked")
     assert np.isfinite(d).all()
-    assert not _bits(d[~free]).any(), "a masked variable did not get an exact +0"
+    assert not bits(d[~free]).any(), "a masked variable did not get an exact +0"
     for p in range(B.P):
         fp = free[B.xs(p)]
         fixed = B.lo_h[B.xs(p)] == B.up_h[B.xs(p)]
@@ -234,13 +143,13 @@ def test_masked_step_against_a_direct_solve_on_the_free_columns(group):
         Af = A[:, np.nonzero(fp)[0]].tocsr()
         w = w_h[B.gs(p)]
         zero = q_h[B.xs(p)][fp] == 0   # the device's column norms, as tests/test_jac_scaled.py takes them
-        _check_scaled_step(Af, b_h[B.gs(p)], w, mu_h[p], c_h[B.xs(p)][fp], d[B.xs(p)][fp], info[p], zero,
-                           "problem %d %s, %d free of %d" % (p, B.problems[p], fp.sum(), fp.size))
+        check_scaled_step(Af, b_h[B.gs(p)], w, mu_h[p], c_h[B.xs(p)][fp], d[B.xs(p)][fp], info[p], zero,
+                          "problem %d %s, %d free of %d" % (p, B.problems[p], fp.sum(), fp.size))
     # no zero in c: the bits of twr_jac_lsq_solve_scaled, d and info, under the cap and converged
     for iters, tol in ((ITERS, TOL), (7, 0.0)):
-        d0, i0 = _solve(B, L, _dev(np.maximum(mu_h, 1e-3)), L["c"], False, iters, tol)
-        d1, i1 = _solve(B, L, _dev(np.maximum(mu_h, 1e-3)), L["c"], True, iters, tol)
-        assert _same_bits(d0, d1) and _same_bits(i0, i1) and d0.any()
+        d0, i0 = B.solve(L["jac"], L["b"], L["wa"], dev(np.maximum(mu_h, 1e-3)), L["c"], "scaled", iters, tol)
+        d1, i1 = B.solve(L["jac"], L["b"], L["wa"], dev(np.maximum(mu_h, 1e-3)), L["c"], "masked", iters, tol)
+        assert same_bits(d0, d1) and same_bits(i0, i1) and d0.any()
     # a negative, NaN or Inf c_k stays bad input, in its problem alone; an all-zero c converges at once with d = 0
     cbad = L["cf"].clone()
     values = (-1.0, float("nan"), float("inf"))
@@ -248,21 +157,21 @@ def test_masked_step_against_a_direct_solve_on_the_free_columns(group):
     for p, v in bad.items():
         cbad[int(B.xo[p]) + int(np.nonzero(free[B.xs(p)])[0][5])] = v
     cbad[B.xs(0)] = 0.0
-    d2, i2 = _solve(B, L, _dev(mu_h), cbad, True)
+    d2, i2 = B.solve(L["jac"], L["b"], L["wa"], dev(mu_h), cbad, "masked")
     for p in range(B.P):
         if p in bad:
             assert i2[p, 3] == 2 and not d2[B.xs(p)].any(), (p, i2[p])
         elif p == 0:
-            assert np.array_equal(i2[p], [0, 0, 0, 0]) and not _bits(d2[B.xs(p)]).any()
+            assert np.array_equal(i2[p], [0, 0, 0, 0]) and not bits(d2[B.xs(p)]).any()
         else:
-            assert _same_bits(d2[B.xs(p)], d[B.xs(p)]) and _same_bits(i2[p], info[p]), p
+            assert same_bits(d2[B.xs(p)], d[B.xs(p)]) and same_bits(i2[p], info[p]), p
 
 
 # ---------------------------------------------------------------- 2. the free set
 
 @groups
 def test_free_set_against_numpy(group):
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     B, _ = _main(group)
     x = np.clip(B.x0, B.lo_h, B.up_h)
     fixed = B.lo_h == B.up_h
@@ -292,13 +201,13 @@ def test_free_set_against_numpy(group):
     assert compared[hand].all(), "a hand-placed variable was left out of the comparison"
     outcomes = int(ref_blocked[hand].sum())
     assert 0 < outcomes or group == "anymal", "no hand-placed variable is blocked: the comparison is vacuous"
-    assert _same_bits(cf[:B.X][~got_blocked], c[:B.X][~got_blocked]) and not _bits(cf[:B.X][got_blocked]).any()
+    assert same_bits(cf[:B.X][~got_blocked], c[:B.X][~got_blocked]) and not bits(cf[:B.X][got_blocked]).any()
     # without a scale: ones
-    ones, nf1 = _nan(B.X), _nan(B.P)
+    ones, nf1 = nan(B.X), nan(B.P)
     B.lsq.free_set_device(L["x"].data_ptr(), L["lo"].data_ptr(), L["up"].data_ptr(), L["z"].data_ptr(), ones.data_ptr(), nf1.data_ptr(),
                           stream=st)
     torch.cuda.synchronize()
-    assert np.array_equal(ones.cpu().numpy()[:B.X], (~got_blocked).astype(np.float64)) and _same_bits(nf1.cpu().numpy(), nf)
+    assert np.array_equal(ones.cpu().numpy()[:B.X], (~got_blocked).astype(np.float64)) and same_bits(nf1.cpu().numpy(), nf)
     print("free set %s: %d hand-placed on a bound, %d of them blocked; %d variables compared, free counts %s"
           % (group, len(hand), outcomes, compared.sum(), nf[:B.P]))
 
@@ -311,11 +220,11 @@ def test_steps_honour_the_box_and_keep_their_books(group):
     fixed = B.lo_h == B.up_h
     par = B.lm.params
     x_start, rec_start = hist[0]
-    assert _same_bits(x_start, np.clip(B.x0, B.lo_h, B.up_h)), "start does not project x onto the box"
+    assert same_bits(x_start, np.clip(B.x0, B.lo_h, B.up_h)), "start does not project x onto the box"
     rejected = 0
     for k in range(1, STEPS + 1):
         (x0, r0), (x1, r1) = hist[k - 1], hist[k]
-        assert _same_bits(x1[fixed], B.lo_h[fixed]), (k, "a fixed variable lost the bits of its bound")
+        assert same_bits(x1[fixed], B.lo_h[fixed]), (k, "a fixed variable lost the bits of its bound")
         assert ((x1 >= B.lo_h) & (x1 <= B.up_h)).all(), k
         for p in range(B.P):
             a, b = r0[p], r1[p]
@@ -327,12 +236,12 @@ def test_steps_honour_the_box_and_keep_their_books(group):
             ok = b[F["accepted"]] - a[F["accepted"]]
             assert ok in (0.0, 1.0)
             if ok:
-                assert b[F["merit"]] < a[F["merit"]] and not _same_bits(x1[B.xs(p)], x0[B.xs(p)]), (k, p)
+                assert b[F["merit"]] < a[F["merit"]] and not same_bits(x1[B.xs(p)], x0[B.xs(p)]), (k, p)
                 assert b[F["mu"]] == min(max(a[F["mu"]] * par.mu_down, par.mu_min), par.mu_max), (k, p)
             else:
                 rejected += 1
-                assert _same_bits(b[F["merit"]:F["merit"] + 1], a[F["merit"]:F["merit"] + 1]), (k, p)
-                assert _same_bits(x1[B.xs(p)], x0[B.xs(p)]), (k, p, "a rejected step moved x")
+                assert same_bits(b[F["merit"]:F["merit"] + 1], a[F["merit"]:F["merit"] + 1]), (k, p)
+                assert same_bits(x1[B.xs(p)], x0[B.xs(p)]), (k, p, "a rejected step moved x")
                 assert b[F["mu"]] == min(max(a[F["mu"]] * par.mu_up, par.mu_min), par.mu_max), (k, p)
             assert 0 < b[F["free"]] <= B.xo[p + 1] - B.xo[p] - n_fixed and b[F["free"]] == int(b[F["free"]])
             assert 0 < b[F["cg_iters"]] <= par.cg_iters
@@ -347,7 +256,7 @@ def test_steps_honour_the_box_and_keep_their_books(group):
 
 
 def test_mu_is_clamped():
-    B = _Lm(GROUPS["hopper"][:4], mu_min=0.5, mu_max=2.0)
+    B = LmBatch(GROUPS["hopper"][:4], mu_min=0.5, mu_max=2.0)
     hist = B.run(3)
     par = B.lm.params
     for k in range(len(hist)):
@@ -356,7 +265,7 @@ def test_mu_is_clamped():
         if k:
             ok = hist[k][1][:, F["accepted"]] - hist[k - 1][1][:, F["accepted"]]
             want = np.clip(hist[k - 1][1][:, F["mu"]] * np.where(ok == 1, par.mu_down, par.mu_up), 0.5, 2.0)
-            assert _same_bits(mu, want), (k, mu, want)
+            assert same_bits(mu, want), (k, mu, want)
     assert (hist[-1][1][:, F["mu"]] == 0.5).any() or (hist[-1][1][:, F["mu"]] == 2.0).any(), "the clamp never bound"
 
 
@@ -390,7 +299,7 @@ def test_merits_against_the_cpu_restatement(group):
 
 @groups
 def test_bits_do_not_depend_on_the_batch_the_stream_or_the_graph(group):
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     B, hist = _main(group)
     PROBLEMS = GROUPS[group]
     xA, rA = hist[-1]
@@ -399,15 +308,15 @@ def test_bits_do_not_depend_on_the_batch_the_stream_or_the_graph(group):
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
-        C = _Lm([PROBLEMS[i] for i in perm])
+        C = LmBatch([PROBLEMS[i] for i in perm])
         C.start(stream=side.cuda_stream)
         C.step(STEPS, stream=side.cuda_stream)
         xC, rC = C.read(stream=side.cuda_stream)
     torch.cuda.current_stream().wait_stream(side)
     for q, i in enumerate(perm):
-        assert _same_bits(xC[C.xs(q)], xA[B.xs(i)]) and _same_bits(rC[q], rA[i]), (q, i, rC[q], rA[i])
+        assert same_bits(xC[C.xs(q)], xA[B.xs(i)]) and same_bits(rC[q], rA[i]), (q, i, rC[q], rA[i])
     # eager against captured-and-replayed steps, then the replay on a fresh x after a new start
-    D = _Lm(PROBLEMS)
+    D = LmBatch(PROBLEMS)
     with torch.cuda.stream(side):   # warm-up outside the capture (module load)
         D.start(stream=side.cuda_stream)
         D.step(stream=side.cuda_stream)
@@ -421,18 +330,18 @@ def test_bits_do_not_depend_on_the_batch_the_stream_or_the_graph(group):
     for _ in range(STEPS // 2):
         graph.replay()
     xD, rD = D.read()
-    assert _same_bits(xD, xA) and _same_bits(rD, rA), "captured steps differ from eager ones"
-    x1 = np.concatenate([_case(name)[0].x_perturbed(100 + seed) for name, seed in PROBLEMS])
+    assert same_bits(xD, xA) and same_bits(rD, rA), "captured steps differ from eager ones"
+    x1 = np.concatenate([lm_case(name)[0].x_perturbed(100 + seed) for name, seed in PROBLEMS])
     D.start(x_h=x1)
     for _ in range(2):
         graph.replay()
     xD1, rD1 = D.read()
-    E = _Lm(PROBLEMS)
+    E = LmBatch(PROBLEMS)
     E.start(x_h=x1)
     E.step(4)
     xE, rE = E.read()
-    assert _same_bits(xD1, xE) and _same_bits(rD1, rE), "the replay on a fresh x differs from eager steps"
-    assert not _same_bits(xD1, xA) and (rE[:, F["accepted"]] > 0).any()
+    assert same_bits(xD1, xE) and same_bits(rD1, rE), "the replay on a fresh x differs from eager steps"
+    assert not same_bits(xD1, xA) and (rE[:, F["accepted"]] > 0).any()
     print("%s: %d problems at other places on another stream, 4 replays of a 2-step graph, 2 more on a fresh x: same bits" % (group, len(perm)))
 
 
@@ -460,25 +369,25 @@ def test_hostile_inputs_stay_in_their_problem(group):
         elif what == "nan bound":
             up[k] = float("nan")
         else:   # the first phase duration; outside a box, so that the projection cannot repair it
-            case = _case(B.problems[p][0])[0]
+            case = lm_case(B.problems[p][0])[0]
             k = int(B.xo[p]) + [v for v in case.S.var_sets if v["name"].startswith("ee-schedule")][0]["offset"]
             x[k], lo[k], up[k] = 0.0, -1e20, 1e20
             late.append(p)
-    H = _Lm(GROUPS[group])
+    H = LmBatch(GROUPS[group])
     got = H.run(x_h=x, lo_h=lo, up_h=up)
     for p in range(B.P):
         s = B.xs(p)
         if p not in hostile:
             for k in (0, 1, STEPS):
-                assert _same_bits(got[k][0][s], hist[k][0][s]) and _same_bits(got[k][1][p], hist[k][1][p]), (p, k)
+                assert same_bits(got[k][0][s], hist[k][0][s]) and same_bits(got[k][1][p], hist[k][1][p]), (p, k)
             continue
         assert got[-1][1][p, F["state"]] == ta.JacLm.BAD and got[1][1][p, F["state"]] == ta.JacLm.BAD, (p, hostile[p], got[-1][1][p])
         for k in range(1, STEPS + 1):
-            assert _same_bits(got[k][0][s], got[0][0][s]), (p, hostile[p], k, "x of a bad problem changed after the start")
+            assert same_bits(got[k][0][s], got[0][0][s]), (p, hostile[p], k, "x of a bad problem changed after the start")
         if p not in late:   # bad from the start: not even projected
-            assert got[0][1][p, F["state"]] == ta.JacLm.BAD and _same_bits(got[0][0][s], x[s]), (p, hostile[p])
+            assert got[0][1][p, F["state"]] == ta.JacLm.BAD and same_bits(got[0][0][s], x[s]), (p, hostile[p])
         else:
-            assert _same_bits(got[0][0][s], np.clip(x[s], lo[s], up[s]))
+            assert same_bits(got[0][0][s], np.clip(x[s], lo[s], up[s]))
         assert got[-1][1][p, F["steps"]] == 0 and got[-1][1][p, F["accepted"]] == 0
 
 
@@ -493,14 +402,14 @@ def test_done_problems_are_frozen(group):
         for k in range(STEPS + 1):
             x, rec = hist[k]
             assert rec[p, F["state"]] == ta.JacLm.DONE and rec[p, F["merit"]] == 0.0 and rec[p, F["steps"]] == 0
-            assert _same_bits(x[B.xs(p)], hist[0][0][B.xs(p)]) and _same_bits(rec[p], hist[0][1][p])
+            assert same_bits(x[B.xs(p)], hist[0][0][B.xs(p)]) and same_bits(rec[p], hist[0][1][p])
     # every problem done at its first linearisation: nothing moves, whatever the solve and the trial do
-    D = _Lm(GROUPS[group], merit_done=1e300)
+    D = LmBatch(GROUPS[group], merit_done=1e300)
     got = D.run()
     assert (got[0][1][:, F["state"]] == ta.JacLm.DONE).all()
     for k in range(1, STEPS + 1):
-        assert _same_bits(got[k][0], got[0][0]) and _same_bits(got[k][1], got[0][1]), k
-    assert _same_bits(got[0][0], hist[0][0]) and _same_bits(got[0][1][:, F["mu"]], hist[0][1][:, F["mu"]])
+        assert same_bits(got[k][0], got[0][0]) and same_bits(got[k][1], got[0][1]), k
+    assert same_bits(got[0][0], hist[0][0]) and same_bits(got[0][1][:, F["mu"]], hist[0][1][:, F["mu"]])
     assert (got[0][1][:, F["merit"]] > 0).sum() == B.P - len(feasible)
 
 
@@ -508,7 +417,7 @@ def test_done_problems_are_frozen(group):
 
 def test_create_refuses_a_batch_of_another_layout():
     B, _ = _main("hopper")
-    structs, order, _, _, _ = _inputs(GROUPS["hopper"][:5])
+    structs, order, _, _, _ = lm_inputs(GROUPS["hopper"][:5])
     other = ta.Batch(structs, order, device=0)
     with pytest.raises(ta.TowrError, match="layout"):
         ta.JacLm(other, B.lsq)

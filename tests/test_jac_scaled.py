@@ -4,11 +4,8 @@ of twr_jac_lsq_solve, the Marquardt-scaled step against a direct solve of its no
 of the variables' units, containment of NaN / Inf and bad c / mu, the edge cases, hipGraph capture, the Levenberg-Marquardt
 loop with both dampings, and a full C3 batch.
 
-The bounds of the solve tests are those of tests/test_jac_lsq.py, in the scaled variables e = d / c, with tol = 1e-10 and
-mu = 1e-2 lambda_max(C J^T W J C):
-  * true relative residual |C (H d - J^T W b)| / |C J^T W b| <= 2 tol, H = J^T W J + mu C^-2;
-  * |e - e_direct| <= cond 2 tol |e_direct| with cond <= (lambda_max + mu) / mu = 101;
-  * iterations under the cap of 200 (CG on cond 101 contracts by 0.819 per iteration: converged from k = 131).
+The bounds of the solve tests are those of check_scaled_step, derived in tests/jac_ref.py: the bounds of the unscaled solve in the
+scaled variables e = d / c, with tol = 1e-10 and mu = 1e-2 lambda_max(C J^T W J C).
 The column norms: a sum of non-negative terms, at most a few thousand per column, against the same sum in another order:
 1e-12 relative leaves three orders over len 2^-53.
 
@@ -21,166 +18,25 @@ import sys
 import numpy as np
 import pytest
 import scipy.sparse as sp
-import scipy.sparse.linalg as spl
 
 import towr_amd as ta
 
 from .common import Case, baseline_cases, k_params, random_case
+from .jac_device import JacBatch, assert_replay_equals_eager, c3_batch, capture, dev, nan, ragged, ragged_x, torch_ctx
+from .jac_ref import COND, ITERS, REL_FLOOR, ROOT, TOL, check_scaled_step, csr, lam_max, same_bits
 
 pytestmark = pytest.mark.gpu
 
-TOL, ITERS, COND, REL_FLOOR = 1e-10, 200, 101.0, 1e-12
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _torch():
-    import torch
-
-    return torch, torch.device("cuda", 0), torch.cuda.current_stream().cuda_stream
-
-
-def _csr(S, vals):
-    return sp.csr_matrix((vals, S.col_idx, S.row_ptr), shape=(S.m, S.n))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
-
-
-def _lam_max(A, w):
-    """lambda_max(A^T W A) on the CPU; 0 for a problem without active rows."""
-    if not np.any(w):
-        return 0.0
-    return float(spl.svds(sp.diags(np.sqrt(w)) @ A, k=1, return_singular_vectors=False)[0] ** 2)
-
-
-def _dev(a):
-    torch, dev, _ = _torch()
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-
-
-def _nan(n):
-    torch, dev, _ = _torch()
-    return torch.full((max(1, int(n)),), float("nan"), dtype=torch.float64, device=dev)
-
-
-def _ragged():
-    """The batch of tests/test_jac_lsq.py: about 300 problems of quadruped structures: random ones, optimised timings, a grid
-    map, one too wide for the LDS copy of s; struct 0 is C3, struct 1 the gap with every constraint set."""
-    cases = [Case("anymal", "flat", ta.gait_combo(4, 1, 2.0), **k_params(2.0, 200)),
-             Case("anymal", "gap", ta.gait_combo(4, 0, 2.4, 0.9), constraint_sets=127),
-             Case("anymal", "grid_map", ta.gait_combo(4, 1, 2.0),
-                  grid=(np.random.default_rng(3).uniform(-0.05, 0.3, size=(40, 30)).astype(np.float32), 0.06, (0.8, -0.2))),
-             Case("anymal", "flat", ta.gait_combo(4, 1, 2.0), duration_base_poly=0.003)]
-    assert cases[3].S.n > 6144
-    seed = 0
-    while len(cases) < 8:
-        c = random_case(seed)
-        if c.S.n_ee == 4:
-            cases.append(c)
-        seed += 1
-    order = [0, 1, 2, 3] + list(np.random.default_rng(5).integers(0, len(cases), size=296))
-    return cases, order
-
-
-class _Batch:
-    """Batch + JacOps + JacLsq of the same arguments, and the calls under test on device tensors (outputs start as NaN)."""
-
-    def __init__(self, structs, order):
-        self.structs, self.order = structs, list(order)
-        self._batch = None
-        self.ops = ta.JacOps(structs, self.order, device=0)
-        self.lsq = ta.JacLsq(self.ops)
-        self.xo, self.go, self.jo = self.ops.layout()
-        self.P = len(self.order)
-        self.X, self.G, self.J = int(self.xo[-1]), int(self.go[-1]), int(self.jo[-1])
-
-    @property
-    def batch(self):
-        if self._batch is None:
-            self._batch = ta.Batch(self.structs, self.order, device=0)
-        return self._batch
-
-    def eval(self, x):
-        torch, dev, st = _torch()
-        g, jac = _nan(self.G), _nan(self.J)
-        self.batch.eval_device(x.data_ptr(), g.data_ptr(), jac.data_ptr(), ta.EVAL_BOTH, st)
-        torch.cuda.synchronize()
-        return g, jac
-
-    def violation(self, g):
-        torch, dev, st = _torch()
-        r, wa = _nan(self.G), _nan(self.G)
-        self.lsq.violation_device(g.data_ptr(), r.data_ptr(), d_w_active=wa.data_ptr(), stream=st)
-        torch.cuda.synchronize()
-        return r, wa
-
-    def linearise(self, x):
-        """(jac, b = -viol, active-set weights) at x."""
-        g, jac = self.eval(x)
-        r, wa = self.violation(g)
-        return jac, -r, wa
-
-    def colsq(self, jac, w, stream=None):
-        torch, dev, st = _torch()
-        out = _nan(self.X)
-        self.ops.col_sqnorms_device(jac.data_ptr(), out.data_ptr(), d_w=0 if w is None else w.data_ptr(), stream=stream or st)
-        torch.cuda.synchronize()
-        return out
-
-    def scale(self, colsq, rel_floor=REL_FLOOR, colmax=None, stream=None):
-        torch, dev, st = _torch()
-        c = _nan(self.X)
-        self.lsq.col_scale_device(colsq.data_ptr(), c.data_ptr(), rel_floor, d_colsq_max=0 if colmax is None else colmax.data_ptr(),
-                                  stream=stream or st)
-        torch.cuda.synchronize()
-        return c
-
-    def solve(self, jac, b, w, mu, c, iters=ITERS, tol=TOL, stream=None):
-        """(d, info[n_problems, 4]) on the host; c None: twr_jac_lsq_solve."""
-        torch, dev, st = _torch()
-        d, info = _nan(self.X), _nan(4 * self.P)
-        wp = 0 if w is None else w.data_ptr()
-        if c is None:
-            self.lsq.solve_device(jac.data_ptr(), b.data_ptr(), mu.data_ptr(), d.data_ptr(), info.data_ptr(), iters, tol, d_w=wp,
-                                  stream=stream or st)
-        else:
-            self.lsq.solve_scaled_device(jac.data_ptr(), b.data_ptr(), mu.data_ptr(), c.data_ptr(), d.data_ptr(), info.data_ptr(), iters,
-                                         tol, d_w=wp, stream=stream or st)
-        torch.cuda.synchronize()
-        return d.cpu().numpy()[:self.X], info.cpu().numpy().reshape(-1, 4)
-
-    def A(self, p, jac_h):
-        return _csr(self.structs[self.order[p]], jac_h[self.jo[p]:self.jo[p + 1]])
-
-    def xs(self, p):
-        return slice(self.xo[p], self.xo[p + 1])
-
-    def gs(self, p):
-        return slice(self.go[p], self.go[p + 1])
-
 
 def _ragged_batch(n=None, point="x_perturbed"):
-    cases, order = _ragged()
+    cases, order = ragged()
     order = order[:n]
-    B = _Batch([c.S for c in cases], order)
-    x = _dev(np.concatenate([getattr(cases[s], point)(i) for i, s in enumerate(order)]))
-    return cases, order, B, x
-
-
-def _c3_batch(n):
-    c = Case("anymal", "flat", ta.gait_combo(4, 1, 2.0), **k_params(2.0, 200))
-    B = _Batch([c.S], [0] * n)
-    x = _dev(np.concatenate([c.x_perturbed(i) for i in range(n)]))
-    return (c, B) + B.linearise(x)
+    B = JacBatch([c.S for c in cases], order)
+    return cases, order, B, dev(ragged_x(cases, order, point))
 
 
 def _scaled_lam_max(B, p, jac_h, w_h, c_h):
-    return _lam_max((B.A(p, jac_h) @ sp.diags(c_h[B.xs(p)])).tocsr(), w_h[B.gs(p)])
+    return lam_max((B.A(p, jac_h) @ sp.diags(c_h[B.xs(p)])).tocsr(), w_h[B.gs(p)])
 
 
 # ---------------------------------------------------------------- 1. column norms against scipy
@@ -189,10 +45,10 @@ def _scaled_lam_max(B, p, jac_h, w_h, c_h):
 def test_col_sqnorms_against_scipy_on_a_ragged_batch(point):
     cases, order, B, x = _ragged_batch(point=point)
     g, jac = B.eval(x)
-    _, wa = B.violation(g)
+    _, wa, _ = B.violation(g, merit=False)
     jac_h = jac.cpu().numpy()
     assert np.isfinite(jac_h[:B.J]).all()
-    w_rand = _dev(np.random.default_rng(21).uniform(0.1, 3.0, size=B.G))
+    w_rand = dev(np.random.default_rng(21).uniform(0.1, 3.0, size=B.G))
     sq = [B.A(p, jac_h).multiply(B.A(p, jac_h)).T.tocsr() for p in range(B.P)]
     for name, w in (("random", w_rand), ("active", wa), ("unit", None)):
         got = B.colsq(jac, w).cpu().numpy()[:B.X]
@@ -215,95 +71,77 @@ def test_col_sqnorms_against_scipy_on_a_ragged_batch(point):
 # ---------------------------------------------------------------- 2. bit-reproducibility
 
 def test_bits_do_not_depend_on_the_batch_the_call_or_the_cap():
-    torch, dev, st = _torch()
-    c, B, jac, b, wa = _c3_batch(512)
+    torch, device, st = torch_ctx()
+    c, B, _, _, jac, b, wa = c3_batch(512, merit=False)
     jac_h, w_h = jac.cpu().numpy(), wa.cpu().numpy()
     q1, q2 = B.colsq(jac, wa), B.colsq(jac, wa)
-    assert _same_bits(q1.cpu().numpy(), q2.cpu().numpy()), "two col_sqnorms calls differ"
+    assert same_bits(q1.cpu().numpy(), q2.cpu().numpy()), "two col_sqnorms calls differ"
     c1, c2 = B.scale(q1), B.scale(q1)
-    assert _same_bits(c1.cpu().numpy(), c2.cpu().numpy()), "two col_scale calls differ"
+    assert same_bits(c1.cpu().numpy(), c2.cpu().numpy()), "two col_scale calls differ"
     q_h, c_h = q1.cpu().numpy()[:B.X], c1.cpu().numpy()[:B.X]
     assert np.isfinite(c_h).all() and (c_h > 0).all()
     lam = _scaled_lam_max(B, 0, jac_h, w_h, c_h)
-    mu = _dev(np.full(B.P, 1e-2 * lam))
-    d1, i1 = B.solve(jac, b, wa, mu, c1)
-    d2, i2 = B.solve(jac, b, wa, mu, c1)
-    assert _same_bits(d1, d2) and _same_bits(i1, i2), "two calls differ"
+    mu = dev(np.full(B.P, 1e-2 * lam))
+    d1, i1 = B.solve(jac, b, wa, mu, c1, "scaled")
+    d2, i2 = B.solve(jac, b, wa, mu, c1, "scaled")
+    assert same_bits(d1, d2) and same_bits(i1, i2), "two calls differ"
     assert (i1[:, 3] == 0).all(), i1[:, 3]
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         q3 = B.colsq(jac, wa, stream=side.cuda_stream)
         c3 = B.scale(q3, stream=side.cuda_stream)
-        d3, i3 = B.solve(jac, b, wa, mu, c3, stream=side.cuda_stream)
-    assert _same_bits(q3.cpu().numpy()[:B.X], q_h) and _same_bits(c3.cpu().numpy()[:B.X], c_h), "another stream differs"
-    assert _same_bits(d1, d3) and _same_bits(i1, i3), "another stream differs"
-    one = _Batch([c.S], [0])
+        d3, i3 = B.solve(jac, b, wa, mu, c3, "scaled", stream=side.cuda_stream)
+    assert same_bits(q3.cpu().numpy()[:B.X], q_h) and same_bits(c3.cpu().numpy()[:B.X], c_h), "another stream differs"
+    assert same_bits(d1, d3) and same_bits(i1, i3), "another stream differs"
+    one = JacBatch([c.S], [0])
     for p in (0, 201, 511):   # alone in a one-problem handle, its values copied to fresh buffers
         jp, bp, wp = jac[B.jo[p]:B.jo[p + 1]].clone(), b[B.gs(p)].clone(), wa[B.gs(p)].clone()
         qo = one.colsq(jp, wp)
         co = one.scale(qo)
-        do, io = one.solve(jp, bp, wp, mu[p:p + 1].clone(), co)
-        assert _same_bits(qo.cpu().numpy()[:one.X], q_h[B.xs(p)]) and _same_bits(co.cpu().numpy()[:one.X], c_h[B.xs(p)]), p
-        assert _same_bits(do, d1[B.xs(p)]) and _same_bits(io[0], i1[p]), p
+        do, io = one.solve(jp, bp, wp, mu[p:p + 1].clone(), co, "scaled")
+        assert same_bits(qo.cpu().numpy()[:one.X], q_h[B.xs(p)]) and same_bits(co.cpu().numpy()[:one.X], c_h[B.xs(p)]), p
+        assert same_bits(do, d1[B.xs(p)]) and same_bits(io[0], i1[p]), p
     # mu from 1e-2 to 10 lambda_max: every problem converges, at different counts; a problem that has converged does not move
     # while the others go on
     P = 16
-    S16 = _Batch([c.S], [0] * P)
-    mus = _dev(lam * np.logspace(-2, 1, P))
+    S16 = JacBatch([c.S], [0] * P)
+    mus = dev(lam * np.logspace(-2, 1, P))
     sl = lambda t, off: t[:int(off[P])]   # noqa: E731  (one structure: the first 16 problems are a batch of their own)
     args = (sl(jac, B.jo), sl(b, B.go), sl(wa, B.go), mus, sl(c1, B.xo))
-    d200, i200 = S16.solve(*args)
+    d200, i200 = S16.solve(*args, "scaled")
     assert (i200[:, 3] == 0).all() and (i200[:, 0] < ITERS).all() and len(set(i200[:, 0])) > 4, i200[:, 0]
     for k in sorted(set(int(v) for v in i200[:, 0])):
-        dk, ik = S16.solve(*args, iters=k)
+        dk, ik = S16.solve(*args, "scaled", iters=k)
         for p in np.nonzero(i200[:, 0] <= k)[0]:
-            assert _same_bits(dk[S16.xs(p)], d200[S16.xs(p)]) and _same_bits(ik[p], i200[p]), (k, p)
+            assert same_bits(dk[S16.xs(p)], d200[S16.xs(p)]) and same_bits(ik[p], i200[p]), (k, p)
         assert (ik[i200[:, 0] > k, 3] == 1).all() and (ik[i200[:, 0] > k, 0] == k).all()   # the others: the cap
 
 
 # ---------------------------------------------------------------- 3. c = 1 is the unscaled solve
 
 def test_a_scale_of_ones_gives_the_bits_of_the_unscaled_solve():
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     cases, order, B, x = _ragged_batch()
-    jac, b, wa = B.linearise(x)
+    jac, b, wa = B.linearise(x, merit=False)
     q = B.colsq(jac, wa).cpu().numpy()[:B.X]
     # any mu > 0 serves: 1e-2 of the largest diagonal entry of J^T W J (a lower bound of lambda_max), from the device's norms
-    mu = _dev([1e-2 * max(q[B.xs(p)].max(), 1e-300) for p in range(B.P)])
-    ones = torch.ones(B.X, dtype=torch.float64, device=dev)
+    mu = dev([1e-2 * max(q[B.xs(p)].max(), 1e-300) for p in range(B.P)])
+    ones = torch.ones(B.X, dtype=torch.float64, device=device)
     for w in (wa, None):
         for iters, tol in ((60, TOL), (7, 0.0)):
             d0, i0 = B.solve(jac, b, w, mu, None, iters=iters, tol=tol)
-            d1, i1 = B.solve(jac, b, w, mu, ones, iters=iters, tol=tol)
+            d1, i1 = B.solve(jac, b, w, mu, ones, "scaled", iters=iters, tol=tol)
             assert np.isfinite(d0).all() and (i0[:, 0] > 0).all()
-            assert _same_bits(d0, d1), "d differs"
-            assert _same_bits(i0, i1), "info differs"
+            assert same_bits(d0, d1), "d differs"
+            assert same_bits(i0, i1), "info differs"
 
 
 # ---------------------------------------------------------------- 4. the scaled step against a direct solve
 
-def _check_scaled_step(A, b, w, mu, c, d, info, zero, what):
-    n = A.shape[1]
-    rhs = A.T @ (w * b)
-    msg = "%s: %d iterations, |s|/|s0| %.3e, status %d" % (what, info[0], info[1], info[3])
-    assert info[3] == 0, msg
-    assert 0 < info[0] < ITERS, msg
-    res = c * (A.T @ (w * (A @ d))) + mu * d / c - c * rhs
-    true = np.linalg.norm(res) / np.linalg.norm(c * rhs)
-    assert true <= 2 * TOL, (msg, "true residual", true)
-    AC = (A @ sp.diags(c)).tocsr()
-    Hs = (AC.T @ sp.diags(w) @ AC + mu * sp.identity(n)).tocsc()
-    ed = np.linalg.solve(Hs.toarray(), c * rhs) if n <= 1500 else spl.splu(Hs).solve(c * rhs)
-    err = np.linalg.norm(d / c - ed) / np.linalg.norm(ed)
-    assert err <= COND * 2 * TOL, (msg, "|e - direct| / |direct|", err)
-    assert not d[zero].any(), (msg, "a column of norm 0 moved")
-    print("%s; true residual %.2e, |e - direct| / |direct| %.2e, %d columns of norm 0" % (msg, true, err, zero.sum()))
-
-
 def test_scaled_step_against_a_direct_solve():
     cases, order, B, x = _ragged_batch()
-    jac, b, wa = B.linearise(x)
+    jac, b, wa = B.linearise(x, merit=False)
     q = B.colsq(jac, wa)
     c = B.scale(q)
     jac_h, b_h, w_h, q_h, c_h = (t.cpu().numpy() for t in (jac, b, wa, q, c))
@@ -315,14 +153,14 @@ def test_scaled_step_against_a_direct_solve():
     for p in sample:
         mu_h[p] = 1e-2 * _scaled_lam_max(B, p, jac_h, w_h, c_h)
     assert (mu_h[sample] > 0).all()
-    d, info = B.solve(jac, b, wa, _dev(mu_h), c)
+    d, info = B.solve(jac, b, wa, dev(mu_h), c, "scaled")
     assert np.isfinite(d).all() and (info[:, 3] != 2).all()
     zeros = 0
     for p in sample:
         zero = q_h[B.xs(p)] == 0
         zeros += int(zero.sum())
-        _check_scaled_step(B.A(p, jac_h), b_h[B.gs(p)], w_h[B.gs(p)], mu_h[p], c_h[B.xs(p)], d[B.xs(p)], info[p], zero,
-                           "ragged problem %d (struct %d)" % (p, order[p]))
+        check_scaled_step(B.A(p, jac_h), b_h[B.gs(p)], w_h[B.gs(p)], mu_h[p], c_h[B.xs(p)], d[B.xs(p)], info[p], zero,
+                          "ragged problem %d (struct %d)" % (p, order[p]))
     assert zeros > 0
 
 
@@ -332,28 +170,28 @@ def _unit_invariance(rel_floor, all_columns):
     """The same problems in other units, J' = J diag(2^j): (relative difference of the scaled steps in e over the columns
     that are at the floor in neither run, per problem; the same for the unscaled steps over all columns)."""
     cases, order, B, x = _ragged_batch(12)
-    jac, b, wa = B.linearise(x)
+    jac, b, wa = B.linearise(x, merit=False)
     jac_h, w_h = jac.cpu().numpy(), wa.cpu().numpy()
     rng = np.random.default_rng(77)
     j = rng.integers(-20, 21, size=B.X)
     f_h = np.ones(max(1, B.J))
     for p in range(B.P):
         f_h[B.jo[p]:B.jo[p + 1]] = np.ldexp(1.0, j[B.xs(p)])[B.structs[order[p]].col_idx]
-    jac2 = jac * _dev(f_h)   # exact: a power of two each
+    jac2 = jac * dev(f_h)   # exact: a power of two each
     two_j = np.ldexp(1.0, j)
     q1, q2 = B.colsq(jac, wa), B.colsq(jac2, wa)
     c1, c2 = B.scale(q1, rel_floor), B.scale(q2, rel_floor)
     q1_h, q2_h, c1_h, c2_h = (t.cpu().numpy()[:B.X] for t in (q1, q2, c1, c2))
-    assert _same_bits(q2_h, q1_h * two_j ** 2), "the norms of the rescaled columns are not the rescaled norms"
+    assert same_bits(q2_h, q1_h * two_j ** 2), "the norms of the rescaled columns are not the rescaled norms"
     mu_s = np.array([1e-2 * _scaled_lam_max(B, p, jac_h, w_h, c1_h) for p in range(B.P)])
-    d1, i1 = B.solve(jac, b, wa, _dev(mu_s), c1)
-    d2, i2 = B.solve(jac2, b, wa, _dev(mu_s), c2)
+    d1, i1 = B.solve(jac, b, wa, dev(mu_s), c1, "scaled")
+    d2, i2 = B.solve(jac2, b, wa, dev(mu_s), c2, "scaled")
     assert (i1[:, 3] == 0).all() and (i2[:, 3] == 0).all(), (i1[:, 3], i2[:, 3])
     jac2_h = jac2.cpu().numpy()
-    mu_1 = np.array([1e-2 * _lam_max(B.A(p, jac_h), w_h[B.gs(p)]) for p in range(B.P)])
-    mu_2 = np.array([1e-2 * _lam_max(B.A(p, jac2_h), w_h[B.gs(p)]) for p in range(B.P)])
-    u1, k1 = B.solve(jac, b, wa, _dev(mu_1), None)
-    u2, k2 = B.solve(jac2, b, wa, _dev(mu_2), None)
+    mu_1 = np.array([1e-2 * lam_max(B.A(p, jac_h), w_h[B.gs(p)]) for p in range(B.P)])
+    mu_2 = np.array([1e-2 * lam_max(B.A(p, jac2_h), w_h[B.gs(p)]) for p in range(B.P)])
+    u1, k1 = B.solve(jac, b, wa, dev(mu_1), None)
+    u2, k2 = B.solve(jac2, b, wa, dev(mu_2), None)
     assert (k1[:, 3] == 0).all() and (k2[:, 3] == 0).all()
     scaled, unscaled, checked = [], [], 0
     for p in range(B.P):
@@ -392,7 +230,7 @@ def test_the_scaled_step_does_not_depend_on_the_units_of_x():
 
 def test_poison_stays_in_its_problem():
     cases, order, B, x = _ragged_batch(40)
-    jac, b, wa = B.linearise(x)
+    jac, b, wa = B.linearise(x, merit=False)
     jac_h, b_h, w_h = jac.cpu().numpy(), b.cpu().numpy(), wa.cpu().numpy()
 
     def run(jv, bv, wv, mu_h, c_over):
@@ -401,7 +239,7 @@ def test_poison_stays_in_its_problem():
         c_h = c.cpu().numpy()
         for p, val in c_over.items():
             c_h[B.xo[p]:B.xo[p + 1]:3] = val
-        d, info = B.solve(jv, bv, wv, _dev(mu_h), _dev(c_h), iters=60)
+        d, info = B.solve(jv, bv, wv, dev(mu_h), dev(c_h), "scaled", iters=60)
         return q.cpu().numpy()[:B.X], c.cpu().numpy()[:B.X], d, info
 
     q0, c0, _, _ = run(jac, b, wa, np.ones(B.P), {})
@@ -420,13 +258,13 @@ def test_poison_stays_in_its_problem():
         else:
             arr, off = {"jac": (jb, B.jo), "b": (bb, B.go), "w": (wb, B.go)}[where]
             arr[off[p]:off[p + 1]:3] = val
-    q1, c1, d1, i1 = run(_dev(jb), _dev(bb), _dev(wb), mb, cb)
+    q1, c1, d1, i1 = run(dev(jb), dev(bb), dev(wb), mb, cb)
     for p in range(B.P):
         s = B.xs(p)
         if p not in bad or bad[p][0] in ("b", "mu", "c"):   # the norms and the scale read J and w only
-            assert _same_bits(q1[s], q0[s]) and _same_bits(c1[s], c0[s]), p
+            assert same_bits(q1[s], q0[s]) and same_bits(c1[s], c0[s]), p
         if p not in bad:
-            assert _same_bits(d1[s], d0[s]) and _same_bits(i1[p], i0[p]), p
+            assert same_bits(d1[s], d0[s]) and same_bits(i1[p], i0[p]), p
         elif bad[p][0] in ("mu", "c"):
             assert i1[p, 3] == 2 and i1[p, 0] == 0 and not d1[s].any(), (p, i1[p])
         else:
@@ -438,24 +276,24 @@ def test_poison_stays_in_its_problem():
 
 
 def test_edge_cases():
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     # a structure without rows: norms 0, c = 1, d = 0, status 0, no iterations
     case = random_case(5111)
     assert case.S.m == 0 and case.S.nnz == 0
-    B = _Batch([case.S], [0, 0, 0])
-    one = torch.zeros(8, dtype=torch.float64, device=dev)
+    B = JacBatch([case.S], [0, 0, 0])
+    one = torch.zeros(8, dtype=torch.float64, device=device)
     q = B.colsq(one, None)
     c = B.scale(q)
     assert not q.cpu().numpy()[:B.X].any() and (c.cpu().numpy()[:B.X] == 1.0).all()
-    d, info = B.solve(one, one, None, _dev([0.0, 1.0, 2.0]), c)
+    d, info = B.solve(one, one, None, dev([0.0, 1.0, 2.0]), c, "scaled")
     assert not d.any() and (info[:, 0] == 0).all() and (info[:, 3] == 0).all() and not info[:, 1:3].any()
     # a problem with no active row: top == 0 -> c = 1, d = 0, status 0; its neighbours keep their bits
-    c3, B, jac, b, wa = _c3_batch(3)
+    c3, B, _, _, jac, b, wa = c3_batch(3, merit=False)
     q0 = B.colsq(jac, wa)
     cc0 = B.scale(q0)
     lam = _scaled_lam_max(B, 0, jac.cpu().numpy(), wa.cpu().numpy(), cc0.cpu().numpy())
-    mu = _dev(np.full(3, 1e-2 * lam))
-    dref, iref = B.solve(jac, b, wa, mu, cc0)
+    mu = dev(np.full(3, 1e-2 * lam))
+    dref, iref = B.solve(jac, b, wa, mu, cc0, "scaled")
     assert (iref[:, 3] == 0).all()
     wz = wa.clone()
     wz[B.gs(1)] = 0.0
@@ -463,17 +301,17 @@ def test_edge_cases():
     cc = B.scale(q)
     q_h, c_h = q.cpu().numpy(), cc.cpu().numpy()
     assert not q_h[B.xs(1)].any() and (c_h[B.xs(1)] == 1.0).all()
-    d, info = B.solve(jac, b, wz, mu, cc)
+    d, info = B.solve(jac, b, wz, mu, cc, "scaled")
     assert not d[B.xs(1)].any() and np.array_equal(info[1], [0, 0, 0, 0])
     for p in (0, 2):
-        assert _same_bits(c_h[B.xs(p)], cc0.cpu().numpy()[B.xs(p)]) and _same_bits(d[B.xs(p)], dref[B.xs(p)]) and _same_bits(info[p], iref[p])
+        assert same_bits(c_h[B.xs(p)], cc0.cpu().numpy()[B.xs(p)]) and same_bits(d[B.xs(p)], dref[B.xs(p)]) and same_bits(info[p], iref[p])
     # the running maximum: max(colsq_max, colsq) in / out, and the scale of it
     rng = np.random.default_rng(4)
     m_h = q0.cpu().numpy()[:B.X] * rng.choice([0.25, 4.0], size=B.X)
-    cmax = _dev(m_h)
+    cmax = dev(m_h)
     cm = B.scale(q0, colmax=cmax).cpu().numpy()[:B.X]
     a_h = np.maximum(m_h, q0.cpu().numpy()[:B.X])
-    assert _same_bits(cmax.cpu().numpy(), a_h)
+    assert same_bits(cmax.cpu().numpy(), a_h)
     for p in range(3):
         a = a_h[B.xs(p)]
         assert np.allclose(cm[B.xs(p)], 1.0 / np.sqrt(np.maximum(a, REL_FLOOR * a.max())), rtol=1e-15, atol=0), p
@@ -481,14 +319,14 @@ def test_edge_cases():
     c1 = B.scale(q0, rel_floor=1.0).cpu().numpy()
     for p in range(3):
         assert len(set(c1[B.xs(p)])) == 1
-    cbuf = _nan(B.X)
+    cbuf = nan(B.X)
     for rf in (0.0, -1e-12, 1.0000001, float("nan"), float("inf")):
         with pytest.raises(ta.TowrError, match="error -1"):
             B.lsq.col_scale_device(q0.data_ptr(), cbuf.data_ptr(), rf, stream=st)
     # iters = 0: zeros and the scaled |s0|
-    d, info = B.solve(jac, b, wa, mu, cc0, iters=0)
+    d, info = B.solve(jac, b, wa, mu, cc0, "scaled", iters=0)
     assert not d.any() and (info[:, 0] == 0).all() and (info[:, 3] == 1).all() and (info[:, 1] == 1).all()
-    assert _same_bits(info[:, 2], iref[:, 2])
+    assert same_bits(info[:, 2], iref[:, 2])
     jac_h, w_h, b_h, c0_h = jac.cpu().numpy(), wa.cpu().numpy(), b.cpu().numpy(), cc0.cpu().numpy()
     for p in range(3):
         s0 = np.linalg.norm(c0_h[B.xs(p)] * (B.A(p, jac_h).T @ (w_h[B.gs(p)] * b_h[B.gs(p)])))
@@ -496,14 +334,14 @@ def test_edge_cases():
     # w NULL is w = 1
     ones = torch.ones_like(b)
     qn, q1 = B.colsq(jac, None), B.colsq(jac, ones)
-    assert _same_bits(qn.cpu().numpy(), q1.cpu().numpy())
+    assert same_bits(qn.cpu().numpy(), q1.cpu().numpy())
     cn = B.scale(qn)
-    dn, inn = B.solve(jac, b, None, mu, cn, iters=30)
-    d1, i1 = B.solve(jac, b, ones, mu, cn, iters=30)
-    assert _same_bits(dn, d1) and _same_bits(inn, i1) and (inn[:, 0] > 0).all()
+    dn, inn = B.solve(jac, b, None, mu, cn, "scaled", iters=30)
+    d1, i1 = B.solve(jac, b, ones, mu, cn, "scaled", iters=30)
+    assert same_bits(dn, d1) and same_bits(inn, i1) and (inn[:, 0] > 0).all()
     # NULL and misaligned buffers, negative iters, a NaN tol
-    out = torch.zeros(4 * 3, dtype=torch.float64, device=dev)
-    dd = torch.zeros(B.X, dtype=torch.float64, device=dev)
+    out = torch.zeros(4 * 3, dtype=torch.float64, device=device)
+    dd = torch.zeros(B.X, dtype=torch.float64, device=device)
     a = (jac.data_ptr(), b.data_ptr(), mu.data_ptr(), cc0.data_ptr(), dd.data_ptr(), out.data_ptr())
     for i in range(6):
         for badptr in (0, a[i] + 4):
@@ -533,16 +371,15 @@ def test_edge_cases():
 # ---------------------------------------------------------------- 7. hipGraph
 
 def test_capture_eval_violation_norms_scale_solve_update_as_one_graph():
-    torch, dev, _ = _torch()
-    cases, order = _ragged()
+    torch, device, _ = torch_ctx()
+    cases, order = ragged()
     order = order[:24]
-    B = _Batch([c.S for c in cases], order)
-    x0 = np.concatenate([cases[s].x_perturbed(i) for i, s in enumerate(order)])
-    x = _dev(x0)
-    z64 = lambda n: torch.zeros(n, dtype=torch.float64, device=dev)   # noqa: E731
+    B = JacBatch([c.S for c in cases], order)
+    x = dev(ragged_x(cases, order))
+    z64 = lambda n: torch.zeros(n, dtype=torch.float64, device=device)   # noqa: E731
     g, jac, r, b, wa, merit, q, c, d, info = (z64(B.G), z64(B.J), z64(B.G), z64(B.G), z64(B.G), z64(B.P), z64(B.X), z64(B.X), z64(B.X),
                                               z64(4 * B.P))
-    mu = _dev(np.full(B.P, 1e-2))
+    mu = dev(np.full(B.P, 1e-2))
     outs = (g, jac, r, b, wa, merit, q, c, d, info)
     before = B.lsq.bytes()["resident"]
     B.lsq.reserve_scaled()   # the one allocation, outside the capture
@@ -558,31 +395,17 @@ def test_capture_eval_violation_norms_scale_solve_update_as_one_graph():
                                   d_w=wa.data_ptr(), stream=stream)
         x.add_(d)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):   # warm-up outside the capture (module load)
-        step(side.cuda_stream)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):   # captures on a non-default stream of its own
-        step(torch.cuda.current_stream().cuda_stream)
-    x1 = np.concatenate([cases[s].x_perturbed(100 + i) for i, s in enumerate(order)])
-    x.copy_(torch.from_numpy(x1))
-    for t in outs:
-        t.zero_()
-    graph.replay()
-    torch.cuda.synchronize()
-    got = [t.clone() for t in outs] + [x.clone()]
-    x.copy_(torch.from_numpy(x1))
-    for t in outs:
-        t.zero_()
-    step(torch.cuda.current_stream().cuda_stream)
-    torch.cuda.synchronize()
-    for a, e in zip(got, list(outs) + [x]):
-        assert _same_bits(a.cpu().numpy(), e.cpu().numpy())
+    graph = capture(step)
+    x1 = ragged_x(cases, order, seed0=100)
+
+    def reset():
+        x.copy_(torch.from_numpy(x1))
+        for t in outs:
+            t.zero_()
+
+    assert_replay_equals_eager(step, graph, reset, outs + (x,))
     assert info.cpu().numpy().reshape(-1, 4)[:, 0].max() > 3 and d.abs().max().item() > 0 and (c > 0).all().item()
-    assert not torch.equal(x, torch.from_numpy(x1).to(dev))
+    assert not torch.equal(x, torch.from_numpy(x1).to(device))
 
 
 # ---------------------------------------------------------------- 8. the LM loop with both dampings
@@ -592,7 +415,7 @@ def test_lm_loop_marquardt_against_identity(name):
     """64 problems at x_perturbed(seed), 8 steps of 60 CG iterations, the loop and accept rule of scripts/jac_lsq.py: for every
     problem the final merit with mu C^-2 is at most half of the one with mu I (the CPU restatement on these inputs, module
     docstring: at most 0.138)."""
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     sys.path.insert(0, os.path.join(ROOT, "scripts"))
     try:
         import jac_lsq
@@ -605,7 +428,7 @@ def test_lm_loop_marquardt_against_identity(name):
     Q = jac_lsq.Problem(torch, [case.S], [0] * n, x0)
     final = {}
     for damping in ("identity", "marquardt"):
-        Q.x = torch.from_numpy(x0).to(dev)
+        Q.x = torch.from_numpy(x0).to(device)
         mu = None
         if damping == "identity":
             g, r, wa = Q.vec(Q.G), Q.vec(Q.G), Q.vec(Q.G)
@@ -625,20 +448,20 @@ def test_lm_loop_marquardt_against_identity(name):
 # ---------------------------------------------------------------- 9. a full C3 batch
 
 def test_c3_full_batch():
-    torch, dev, st = _torch()
+    torch, device, st = torch_ctx()
     c = Case("anymal", "flat", ta.gait_combo(4, 1, 2.0), **k_params(2.0, 200))
     S = c.S
     n = 8192
-    B = _Batch([S], [0] * n)
+    B = JacBatch([S], [0] * n)
     # before the scaled solve is reserved: the formula tests/test_jac_lsq.py pins
     want = 8 * (2 * S.n * n + 3 * S.m * n + 4 * n) + 2 * 8 * S.m + 40 * n
     assert S.n % 2 == 0 and S.m % 2 == 0 and B.lsq.bytes()["resident"] == want
-    gen = torch.Generator(device=dev)
+    gen = torch.Generator(device=device)
     gen.manual_seed(5)
-    x0 = _dev(c.x_guess())
-    scale = _dev((c.x_perturbed(0) - c.x_guess()) / np.random.default_rng(1234).normal(size=S.n))   # 0.05 * the per-variable scale
-    x = (x0[None, :] + scale[None, :] * torch.randn((n, S.n), generator=gen, dtype=torch.float64, device=dev)).reshape(-1).contiguous()
-    jac, b, wa = B.linearise(x)
+    x0 = dev(c.x_guess())
+    scale = dev((c.x_perturbed(0) - c.x_guess()) / np.random.default_rng(1234).normal(size=S.n))   # 0.05 * the per-variable scale
+    x = (x0[None, :] + scale[None, :] * torch.randn((n, S.n), generator=gen, dtype=torch.float64, device=device)).reshape(-1).contiguous()
+    jac, b, wa = B.linearise(x, merit=False)
     q = B.colsq(jac, wa)
     cc = B.scale(q)
     assert B.lsq.bytes()["resident"] == want, "the norms and the scale need no workspace"
@@ -648,8 +471,8 @@ def test_c3_full_batch():
     assert B.lsq.bytes()["resident"] == want + 8 * 2 * S.n * n   # once
     q_h, c_h = q.cpu().numpy()[:B.X], cc.cpu().numpy()[:B.X]
     assert np.isfinite(q_h).all() and (q_h >= 0).all() and np.isfinite(c_h).all() and (c_h > 0).all()
-    lam = _lam_max((_csr(S, jac[:B.jo[1]].cpu().numpy()) @ sp.diags(c_h[:S.n])).tocsr(), wa[:S.m].cpu().numpy())
-    mu = _dev(np.full(n, 1e-2 * lam))
-    d, info = B.solve(jac, b, wa, mu, cc, iters=20)
+    lam = lam_max((csr(S, jac[:B.jo[1]].cpu().numpy()) @ sp.diags(c_h[:S.n])).tocsr(), wa[:S.m].cpu().numpy())
+    mu = dev(np.full(n, 1e-2 * lam))
+    d, info = B.solve(jac, b, wa, mu, cc, "scaled", iters=20)
     assert np.isfinite(d).all() and np.isfinite(info).all()
     assert (info[:, 0] == 20).all() and (info[:, 3] == 1).all()

@@ -2,7 +2,7 @@
 the hopper and the biped with every constraint set of TWR_SETS_ALL (optimised timings: every phase duration boxed), seeds 0 .. 3,
   * the fixed variables (lo == up) keep the bits of their bound, every x stays inside its box, the recorded merit never rises;
   * the masked CGLS step agrees with a dense direct solve on the free columns, under the bounds of
-    tests/test_jac_scaled.py::_check_scaled_step (tol 1e-10, mu = 1e-2 lambda_max: true residual <= 2 tol, |e - direct| <= 101 * 2
+    tests/jac_ref.py::check_scaled_step (tol 1e-10, mu = 1e-2 lambda_max: true residual <= 2 tol, |e - direct| <= 101 * 2
     tol |direct|, converged under 200 iterations): it is that iteration on fewer columns; masked variables get an exact +0;
   * the free loop on the same inputs moves every fixed variable off its value, and with optimised timings leaves durations
     outside their box: what the driver is for."""
@@ -14,27 +14,20 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from .jac_ref import ITERS, ROOT, TOL, check_scaled_step, lam_max, lm_case
+
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
 
 import lm_box_cpu as lb  # noqa: E402
 from lm_damping_cpu import cgls  # noqa: E402
-
-from .test_jac_scaled import ITERS, TOL, _check_scaled_step, _lam_max  # noqa: E402
 
 CASES = ("C1_hopper", "hopper_all", "biped_all")
 SEEDS = (0, 1, 2, 3)
 
 
 @functools.lru_cache(maxsize=None)
-def _case(name):
-    case = lb.cases()[name]()
-    return case, lb.case_bounds(case)
-
-
-@functools.lru_cache(maxsize=None)
 def _run(name, seed, bounded):
-    case, (lo, up) = _case(name)
+    case, (lo, up) = lm_case(name)
     return lb.lm_box(case, case.x_perturbed(seed), lo, up, bounded=bounded, keep=True)
 
 
@@ -54,7 +47,7 @@ def test_start_vector_is_the_drivers():
 
 @pytest.mark.parametrize("name", CASES)
 def test_bounds_are_what_the_issue_counts(name):
-    case, (lo, up) = _case(name)
+    case, (lo, up) = lm_case(name)
     fixed = lo == up
     assert fixed.sum() == 23 + 3 * case.S.n_ee
     assert (lo <= up).all()
@@ -68,7 +61,7 @@ def test_bounds_are_what_the_issue_counts(name):
 @pytest.mark.parametrize("seed", SEEDS)
 @pytest.mark.parametrize("name", CASES)
 def test_bounded_loop_honours_the_box(name, seed):
-    case, (lo, up) = _case(name)
+    case, (lo, up) = lm_case(name)
     R = _run(name, seed, True)
     x, fixed = R["x"], lo == up
     assert np.array_equal(x[fixed].view(np.int64), lo[fixed].view(np.int64)), "a fixed variable lost the bits of its bound"
@@ -88,7 +81,7 @@ def test_bounded_loop_honours_the_box(name, seed):
 @pytest.mark.parametrize("name", CASES[1:])
 def test_the_active_set_is_exercised(name):
     """With optimised timings some run blocks a duration on its bound: the free count falls below n - fixed, and moves."""
-    case, (lo, up) = _case(name)
+    case, (lo, up) = lm_case(name)
     most = case.S.n - int((lo == up).sum())
     counts = set(v for seed in SEEDS for v in _run(name, seed, True)["nfree"])
     assert min(counts) < most and len(counts) > 1, counts
@@ -101,12 +94,12 @@ def test_the_biped_with_all_sets_rejects_its_first_step_at_seed_1():
 @pytest.mark.parametrize("seed", SEEDS)
 @pytest.mark.parametrize("name", CASES)
 def test_masked_step_against_a_dense_direct_solve(name, seed):
-    case, (lo, up) = _case(name)
+    case, (lo, up) = lm_case(name)
     L = _run(name, seed, True)["lin"][0]
     free = L.cf != 0
     assert np.array_equal(L.cf[free], L.c[free]) and (~free).sum() >= (lo == up).sum()
     ACf = (L.A @ sp.diags(L.cf)).tocsr()
-    mu = 1e-2 * _lam_max(ACf, L.w)
+    mu = 1e-2 * lam_max(ACf, L.w)
     k, e = cgls(ACf, L.b, L.w, mu, ITERS, TOL)
     d = L.cf * e
     assert not d[~free].any() and not np.signbit(d[~free]).any()
@@ -116,13 +109,13 @@ def test_masked_step_against_a_dense_direct_solve(name, seed):
     s = cfree * (Af.T @ (L.w * (L.b - Af @ d[free]))) - mu * d[free] / cfree
     info = [k, np.linalg.norm(s) / np.linalg.norm(s0), np.linalg.norm(s0), 0 if k < ITERS else 1]
     zero = np.asarray(Af.multiply(Af).T @ L.w).ravel() == 0
-    _check_scaled_step(Af, L.b, L.w, mu, cfree, d[free], info, zero, "%s seed %d, %d free of %d" % (name, seed, free.sum(), case.S.n))
+    check_scaled_step(Af, L.b, L.w, mu, cfree, d[free], info, zero, "%s seed %d, %d free of %d" % (name, seed, free.sum(), case.S.n))
 
 
 @pytest.mark.parametrize("seed", SEEDS)
 @pytest.mark.parametrize("name", CASES)
 def test_free_loop_leaves_every_fixed_variable_off_its_value(name, seed):
-    case, (lo, up) = _case(name)
+    case, (lo, up) = lm_case(name)
     x = _run(name, seed, False)["x"]
     fixed = lo == up
     off = np.abs(x[fixed] - lo[fixed])
