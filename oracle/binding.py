@@ -80,6 +80,7 @@ def lib():
         L.orc_set_grid_map.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_double, C.c_double, C.c_double]
         L.orc_set_grid_map.restype = C.c_int
         L.orc_terrain_probe.argtypes = [C.c_void_p, C.c_double, C.c_double, _dp]
+        L.orc_terrain_probe_full.argtypes = [C.c_void_p, C.c_double, C.c_double, _dp]
         L.orc_hermite_dpos_dT.argtypes = [C.c_double] * 6
         L.orc_hermite_dpos_dT.restype = C.c_double
         L.orc_euler_probe.argtypes = [_dp, C.c_double, C.c_double, _dp]
@@ -223,6 +224,13 @@ class OracleProblem:
         """(height, dh/dx, dh/dy) of the problem's terrain."""
         o = np.zeros(3)
         lib().orc_terrain_probe(self._h, float(x), float(y), _d(o))
+        return o
+
+    def terrain_probe_full(self, x, y):
+        """(h, hx, hy, hxx | normalised normal, tangent 1, tangent 2 (9) | their derivatives, basis-major, dim x then y (18)) of
+        the problem's terrain."""
+        o = np.zeros(31)
+        lib().orc_terrain_probe_full(self._h, float(x), float(y), _d(o))
         return o
 
     def bounds(self):

@@ -274,16 +274,26 @@ class GridMapTerrain:
         for a in (0, 1):
             v = (p[a] - 0.5 * self.length[a] - self.pos[a]) / self.res
             idx.append(int(-v))                       # Eigen cast<int>: truncation towards zero
-            t = -(p[a] - self.pos[a] - 0.5 * self.length[a])
+            # The published algorithm does not say in which order the border and centre expressions are rounded, and a point
+            # within an ulp of a border or of a cell centre is decided by exactly that (tests/test_terrain_probe.py found 5 %
+            # of its on-the-line points answered differently here and in the oracle, FLT_MAX against a height).  Both models
+            # and the device now round them in ONE stated order, a convention of this project, not grid_map's:
+            #   border: (pos + length / 2) - p        centre: ((pos + length / 2) - res / 2) - res * index
+            t = self.pos[a] + 0.5 * self.length[a] - p[a]
             inside = inside and (0.0 <= t < self.length[a])
             inside = inside and (0 <= idx[a] < self.size[a])
         return idx, inside
 
     def _centre(self, idx):
-        return [self.pos[a] + 0.5 * self.length[a] - (idx[a] + 0.5) * self.res for a in (0, 1)]
+        return [self.pos[a] + 0.5 * self.length[a] - 0.5 * self.res - self.res * float(idx[a]) for a in (0, 1)]   # (see _index)
 
     def at_position(self, x, y):
         """float32 value of atPosition(INTER_LINEAR), or None for std::out_of_range."""
+        v = self.at_position_exact(x, y)
+        return v if v is None or isinstance(v, np.float32) else np.float32(float(v))
+
+    def at_position_exact(self, x, y):
+        """at_position before its rounding to float: the bilinear value as an mpf (a float32 from the nearest-cell fall-back)"""
         p = (float(x), float(y))
         i0, inside = self._index(p)
         c0 = self._centre(i0)
@@ -301,7 +311,7 @@ class GridMapTerrain:
             v = (mpf(top[1]) - mpf(p[1])) / mpf(self.res)
             f = lambda di, dj: mpf(float(self.e[lo[0] + di, lo[1] + dj]))
             val = f(0, 0) * (1 - u) * (1 - v) + f(1, 0) * u * (1 - v) + f(0, 1) * (1 - u) * v + f(1, 1) * u * v
-            return np.float32(float(val))
+            return val
         if inside:
             return self.e[i0[0], i0[1]]               # INTER_NEAREST fall-back
         return None

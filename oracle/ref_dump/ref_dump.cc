@@ -43,6 +43,8 @@
 //                        regions in FILE (one line per region: position x y z, orientation x y z w, number of boundary
 //                        points, then their local x y) and the time horizon: per footstep state one line, the
 //                        duration, then the contact_set (plane index per foot, -1 = in the air)
+//   ref_dump --terrain-points IN OUT [--csv FILE]   the terrains alone at given points, see TerrainPoints() below
+//                        (oracle/ref_golden.py --terrain records it as tests/golden/refterrain_*.npz)
 #include <ifopt/problem.h>
 #include <towr/initialization/gait_generator.h>
 #include <towr/nlp_formulation.h>
@@ -82,7 +84,82 @@ static bool SampleTimesDefined(double T, double dt) {
 }
 #endif
 
+// ref_dump --terrain-points IN OUT [--csv FILE]: the reference's terrains alone, no NLP.  IN holds raw doubles, four per
+// point: terrain id (HeightMap::TerrainID 0..6, 7 = HeightMapFromCSV(FILE)), x, y, and a flag.  OUT receives raw doubles:
+// per point GetHeight, GetDerivativeOfHeightWrt(X_), (Y_) and the second derivative wrt x twice -- Gap's public
+// GetHeightDerivWrtXX; no other terrain overrides the base class's (private) zero, written here as 0 -- and, where the flag
+// is set, 27 more: GetNormalizedBasis(Normal | Tangent1 | Tangent2) (3 x 3), then GetDerivativeOfNormalizedBasisWrt(basis,
+// dim) for basis = Normal, Tangent1, Tangent2 and dim = X_, Y_ in that order (6 x 3), which carry every second derivative
+static int TerrainPoints(int argc, char** argv) {
+  if (argc < 4) {
+    std::fprintf(stderr, "usage: ref_dump --terrain-points IN OUT [--csv FILE]\n");
+    return 2;
+  }
+  std::string csv_file;
+  for (int i = 4; i < argc; ++i) {
+    if (std::string(argv[i]) == "--csv" && i + 1 < argc) csv_file = argv[++i];
+    else {
+      std::fprintf(stderr, "unknown option %s\n", argv[i]);
+      return 2;
+    }
+  }
+  std::vector<double> in;
+  {
+    std::FILE* f = std::fopen(argv[2], "rb");
+    if (!f) {
+      std::fprintf(stderr, "cannot read %s\n", argv[2]);
+      return 2;
+    }
+    double buf[4096];
+    size_t got;
+    while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) in.insert(in.end(), buf, buf + got);
+    std::fclose(f);
+  }
+  if (in.empty() || in.size() % 4) {
+    std::fprintf(stderr, "%s: %zu doubles do not make whole points\n", argv[2], in.size());
+    return 2;
+  }
+  std::vector<towr::HeightMap::Ptr> maps;
+  for (int id = 0; id < towr::HeightMap::TERRAIN_COUNT; ++id) maps.push_back(towr::HeightMap::MakeTerrain(static_cast<towr::HeightMap::TerrainID>(id)));
+  if (!csv_file.empty()) maps.push_back(std::make_shared<HeightMapFromCSV>(csv_file));
+  const towr::Gap gap;
+  std::vector<double> out;
+  using H = towr::HeightMap;
+  for (size_t k = 0; k < in.size(); k += 4) {
+    const int id = static_cast<int>(in[k]);
+    if (id < 0 || id >= static_cast<int>(maps.size())) {
+      std::fprintf(stderr, "%s: point %zu names terrain %d\n", argv[2], k / 4, id);
+      return 2;
+    }
+    const H& t = *maps[id];
+    const double x = in[k + 1], y = in[k + 2];
+    out.push_back(t.GetHeight(x, y));
+    out.push_back(t.GetDerivativeOfHeightWrt(towr::X_, x, y));
+    out.push_back(t.GetDerivativeOfHeightWrt(towr::Y_, x, y));
+    out.push_back(id == H::GapID ? gap.GetHeightDerivWrtXX(x, y) : 0.0);
+    if (in[k + 3] != 0.0) {
+      for (H::Direction b : {H::Normal, H::Tangent1, H::Tangent2}) {
+        const Eigen::Vector3d v = t.GetNormalizedBasis(b, x, y);
+        for (int i = 0; i < 3; ++i) out.push_back(v(i));
+      }
+      for (H::Direction b : {H::Normal, H::Tangent1, H::Tangent2})
+        for (towr::Dim2D dim : {towr::X_, towr::Y_}) {
+          const Eigen::Vector3d v = t.GetDerivativeOfNormalizedBasisWrt(b, dim, x, y);
+          for (int i = 0; i < 3; ++i) out.push_back(v(i));
+        }
+    }
+  }
+  std::FILE* f = std::fopen(argv[3], "wb");
+  if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size() || std::fclose(f) != 0) {
+    std::fprintf(stderr, "cannot write %s\n", argv[3]);
+    return 2;
+  }
+  std::printf("ref_dump: %zu terrain points, %zu values\n", in.size() / 4, out.size());
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc >= 2 && std::string(argv[1]) == "--terrain-points") return TerrainPoints(argc, argv);
   if (argc < 9) {
     std::fprintf(stderr, "usage: see the header of ref_dump.cc\n");
     return 2;

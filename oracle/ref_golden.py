@@ -9,6 +9,7 @@ recorded outputs of the reference's programs, nothing else.  tests/test_ref_gold
 the structure builder (CPU) and the device (GPU) on boxes that do not have the reference.
 
     python -m oracle.ref_golden --traj [names...]   (the fixtures tests/golden/reftraj_*.npz, see TRAJ_CASES below)
+    python -m oracle.ref_golden --terrain [names...]   (tests/golden/refterrain_*.npz, see TERRAIN_FIXTURES below)
 
 The cases are chosen for what the mpmath fixtures and the hand known-answers cannot reach: entries the reference DEFINES
 rather than derives (force rows x footholds on curved terrain, terrain rows of gridded terrain, explicit zeros), bounds,
@@ -310,12 +311,63 @@ def record_traj(name, workdir):
     return path, os.path.getsize(path), out["traj"].shape[1], int(out["plan_steps"].max())
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/golden/refterrain_<analytic|csv>.npz: the reference's terrain classes (ref_dump --terrain-points) at the points of
+# tests/terrain_points.py -- every breakpoint, its neighbouring doubles, the slope-band thresholds of the CSV steps in both
+# roundings.  Per file: terrain_id (n), xy (n, 2), values (n, 4) [h, hx, hy, hxx], force_index (k) = the points of the
+# force subset and basis (k, 27) = their three normalised basis vectors and six derivatives; the CSV file adds its heights.
+# tests/test_terrain_probe.py regenerates the points, compares the oracle bit for bit (CPU) and the device (GPU).
+TERRAIN_FIXTURES = ("analytic", "csv")
+
+
+def terrain_fixture_points(name):
+    """(terrain_id (n,), xy (n, 2), force_index (k,), csv heights or None) of one refterrain fixture"""
+    from tests import terrain_points as tp
+
+    keys = tp.ANALYTIC if name == "analytic" else ("csv",)
+    sub = tp.force_subset()
+    ids, xy, fi, at = [], [], [], 0
+    for key in keys:
+        p = tp.points(key)
+        ids.append(np.full(len(p), tp.TERRAIN_ID[key], dtype=np.int32))
+        xy.append(p)
+        fi.append(at + np.asarray(sub[key][0], dtype=np.int64))
+        at += len(p)
+    return np.concatenate(ids), np.concatenate(xy), np.concatenate(fi), (tp.CSV_HEIGHTS if name == "csv" else None)
+
+
+def record_terrain(name, workdir):
+    from oracle import ref_run
+
+    ids, xy, fi, heights = terrain_fixture_points(name)
+    flags = np.zeros(len(ids), dtype=bool)
+    flags[fi] = True
+    values, basis = ref_run.terrain_points(os.path.join(workdir, "terrain_" + name), ids, xy, flags, csv_heights=heights)
+    order = np.argsort(fi, kind="stable")              # ref_dump answers in point order
+    b = np.empty_like(basis)
+    b[order] = basis
+    out = dict(terrain_id=ids, xy=xy, values=values, force_index=fi, basis=b, reference_deps=ref_run.deps())
+    if heights is not None:
+        out["csv_heights"] = heights
+    path = os.path.join(GOLDEN, "refterrain_%s.npz" % name)
+    save_npz_lzma(path, out)
+    return path, os.path.getsize(path), len(ids), len(fi)
+
+
 def main(names):
     from oracle import ref_run
 
     if not ref_run.available():
         raise SystemExit("oracle/_ref/ref_dump is not built: run oracle/ref_dump/build.sh where the reference sources are")
     total = 0
+    if names and names[0] == "--terrain":
+        with tempfile.TemporaryDirectory() as work:
+            for name in names[1:] or list(TERRAIN_FIXTURES):
+                path, size, n, k = record_terrain(name, work)
+                total += size
+                print("%-40s points=%6d force=%4d %8d bytes" % (os.path.basename(path), n, k, size))
+        print("total %d bytes" % total)
+        return
     if names and names[0] == "--traj":
         with tempfile.TemporaryDirectory() as work:
             for name in names[1:] or list(TRAJ_CASES):

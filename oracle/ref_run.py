@@ -120,6 +120,33 @@ def run(prefix, *args, timeout=600, **kw):
     return out
 
 
+TERRAIN_BASIS_VALUES = 27   # ref_dump --terrain-points: three normalised basis vectors, then their six derivatives
+
+
+def terrain_points(prefix, terrain_ids, xy, with_basis, csv_heights=None, timeout=600):
+    """ref_dump --terrain-points: the reference's terrains at the points xy (n, 2) of terrain_ids (n,) (HeightMap::TerrainID,
+    7 = HeightMapFromCSV over csv_heights).  Returns (values (n, 4) [h, hx, hy, hxx], basis (k, 27) for the k points whose
+    with_basis flag is set, in their order)."""
+    xy = np.asarray(xy, dtype=np.float64).reshape(-1, 2)
+    flags = np.asarray(with_basis, dtype=bool)
+    rec = np.column_stack([np.asarray(terrain_ids, dtype=np.float64), xy, flags.astype(np.float64)])
+    np.ascontiguousarray(rec).tofile(prefix + "_points.bin")
+    cmd = [os.path.join(REF, "ref_dump"), "--terrain-points", prefix + "_points.bin", prefix + "_terrain.bin"]
+    if csv_heights is not None:
+        np.savetxt(prefix + "_heights.csv", np.asarray(csv_heights), fmt="%.17g", delimiter=",")
+        cmd += ["--csv", prefix + "_heights.csv"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    if r.returncode != 0:
+        raise RuntimeError("ref_dump exit %d: %s\n%s" % (r.returncode, " ".join(cmd), (r.stdout + r.stderr)[-2000:]))
+    out = np.fromfile(prefix + "_terrain.bin", dtype=np.float64)
+    width = 4 + TERRAIN_BASIS_VALUES * flags.astype(np.int64)
+    start = np.concatenate([[0], np.cumsum(width)])
+    assert out.size == start[-1], (out.size, start[-1])
+    values = out[start[:-1, None] + np.arange(4)[None, :]]
+    basis = out[start[:-1][flags][:, None] + 4 + np.arange(TERRAIN_BASIS_VALUES)[None, :]] if flags.any() else np.zeros((0, TERRAIN_BASIS_VALUES))
+    return values, basis
+
+
 def case_args(case):
     """(args, kwargs) of command() / run() for a tests.common.Case (every field a Case can set reaches the reference)."""
     p = case.params

@@ -2210,6 +2210,23 @@ void orc_terrain_probe(const orc_problem* P, double x, double y, double out[3]) 
   out[1] = P->terrain->GetDerivativeOfHeightWrt(X, x, y);
   out[2] = P->terrain->GetDerivativeOfHeightWrt(Y, x, y);
 }
+// everything the force rows take from the problem's terrain at one foothold: h, hx, hy, hxx | GetNormalizedBasis of the
+// normal and the two tangents (9) | GetDerivativeOfNormalizedBasisWrt, basis-major, dim x then y (18)
+void orc_terrain_probe_full(const orc_problem* P, double x, double y, double out[31]) {
+  const HeightMap& t = *P->terrain;
+  out[0] = t.GetHeight(x, y);
+  out[1] = t.GetDerivativeOfHeightWrt(X, x, y);
+  out[2] = t.GetDerivativeOfHeightWrt(Y, x, y);
+  out[3] = t.GetSecondDerivativeOfHeightWrt(X, X, x, y);
+  for (int b = 0; b < 3; ++b) {
+    V3 v = t.GetNormalizedBasis(b, x, y);
+    for (int i = 0; i < 3; ++i) out[4 + 3 * b + i] = v(i);
+    for (int dim = 0; dim < 2; ++dim) {
+      V3 d = t.GetDerivativeOfNormalizedBasisWrt(b, dim, x, y);
+      for (int i = 0; i < 3; ++i) out[13 + 3 * (2 * b + dim) + i] = d(i);
+    }
+  }
+}
 // --- probes for tests/test_oracle_symbolic.py (closed forms re-derived from the recipes of towr/matlab/*.m)
 // CubicHermitePolynomial::GetDerivativeOfPosWrtDuration (polynomial.cc:236-257) of one scalar polynomial
 double orc_hermite_dpos_dT(double t, double T, double p0, double v0, double p1, double v1) {

@@ -46,6 +46,7 @@ int orc_set_grid_map(orc_problem*, const float* elevation, int size_x, int size_
                      double pos_y);
 // height and the two slopes of the problem's terrain at (x, y)
 void orc_terrain_probe(const orc_problem*, double x, double y, double out[3]);
+void orc_terrain_probe_full(const orc_problem*, double x, double y, double out[31]);
 // constraint_sets: which of the default sets (parameters.cc:55-60) to build, in that order
 enum {
   ORC_SET_TERRAIN = 1, ORC_SET_DYNAMIC = 2, ORC_SET_BASE_ACC = 4, ORC_SET_ROM = 8, ORC_SET_FORCE = 16,

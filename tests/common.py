@@ -168,6 +168,32 @@ class Case:
         x[idx] = rng.choice([-1.0, 1.0], size=idx.shape) * np.where((node + axis) % 2 == 0, below, above)
         return x
 
+    def footholds(self):
+        """indices into x of the (x, y) of every ee-motion node, one row per node, in the order of the terrain rows: a terrain
+        row's Jacobian entries are (-hx, -hy, 1) at the node's x, y and z (the nodes of a stance phase share their variables)"""
+        S = self.S
+        pairs = []
+        for cs in S.con_sets:
+            if cs["name"].startswith("terrain-"):
+                for r in range(cs["offset"], cs["offset"] + cs["size"]):
+                    cols = S.col_idx[S.row_ptr[r]:S.row_ptr[r + 1]]
+                    assert len(cols) == 3   # (a swing node's velocities lie between its coordinates)
+                    pairs.append((int(cols[0]), int(cols[1])))
+        return np.array(list(dict.fromkeys(pairs)), dtype=np.int64).reshape(-1, 2)
+
+    def x_edges(self, seed):
+        """x_perturbed(seed) with the x and y of every ee-motion node on the breakpoints of the case's own terrain
+        (tests/terrain_points.py edge_footholds): a quarter on a breakpoint, a quarter on a neighbouring double, a quarter on a
+        slope-band threshold in either rounding (CSV), a cell centre (`Grid`) or two doubles from a breakpoint, the rest
+        inside a piece; which one cycles with node, foot and seed."""
+        from tests import terrain_points as tp
+        x = self.x_perturbed(seed)
+        idx = self.footholds()
+        grid_map = (self.grid.elevation, self.grid.resolution, self.grid.position) if isinstance(self.grid, ta.GridMap) else None
+        heights = self.grid.heights if self.grid is not None and grid_map is None else None
+        x[idx] = tp.edge_footholds(self.terrain, len(idx), seed, heights=heights, grid_map=grid_map)
+        return x
+
     def nudged(self, x, direction):
         """x with every base-ang variable moved one ulp up (direction > 0) or down: how far the reference's own output moves
         under it is the yardstick for points where the parity bar alone is below the conditioning of the problem"""

@@ -6,7 +6,8 @@
 // Built and run by tests/test_eval_matrix_plan.py (g++ against the host planner, no HIP); the matrix text comes in
 // as a file (argv[1]), the same text tests/test_eval_matrix.py builds its device batches from.  The device enters as 256 CUs
 // and a 256 MB memory-side cache (an MI355X); the GPU test holds the rows to the plan of the device it runs on.
-// With --print the plan of every call is listed (how the rows were found).
+// With --print the plan of every call is listed (how the rows were found).  With --partial the text is a set of rows of its own
+// (tests/test_eval_edges.py): every row must reach what it claims, and the rows need not cover every instantiation.
 #include <cstdio>
 #include <cstring>
 #include <fstream>
@@ -46,14 +47,24 @@ static std::string get(const Fields& f, const std::string& key, const std::strin
 }
 
 static const std::map<std::string, int> kRobots = {{"monoped", 0}, {"biped", 1}, {"hyq", 2}, {"anymal", 3}, {"go1", 4}};
-static const std::map<std::string, int> kTerrains = {{"flat", 0}, {"stairs", 2}, {"gap", 3}};
+static const std::map<std::string, int> kTerrains = {{"flat", 0}, {"block", 1}, {"stairs", 2}, {"gap", 3}, {"slope", 4}, {"chimney", 5},
+                                                    {"chimney_lr", 6}, {"csv", 7}, {"grid_map", 8}};
 
 // the structure of a `struct` line: the same fields, defaults and formulas as tests/eval_matrix.py make_case
 static twr::Structure build(const Fields& f) {
   twr::Structure S;
   const double T = std::stod(get(f, "T", "2.0"));
   const int K = std::stoi(get(f, "K", "40"));
-  twr::ModelPreset(kRobots.at(get(f, "robot", "anymal")), kTerrains.at(get(f, "terrain", "flat")), &S.model);
+  const int terrain = kTerrains.at(get(f, "terrain", "flat"));
+  twr::ModelPreset(kRobots.at(get(f, "robot", "anymal")), terrain, &S.model);
+  if (terrain >= 7) {   // gridded terrains: the plan depends on the map's presence, not on its cells
+    auto g = std::make_shared<twr::TerrainGrid>();
+    g->rows = 7, g->cols = 9;
+    g->grid_map = terrain == 8;
+    if (g->grid_map) g->elevation.assign(63, 0.0f), g->res = 0.05, g->eps = 0.05 / 6.0;
+    else g->heights.assign(63, 0.0);
+    S.grid = g;
+  }
   twr::GaitCombo(S.model.n_ee, std::stoi(get(f, "combo", "1")), T, std::stod(get(f, "swing", "1.0")), &S.schedule);
   twr_params& p = S.params;
   p.dt_dynamic = p.dt_rom = T / (K - 1.5);
@@ -105,10 +116,14 @@ static std::set<std::string> complete_set() {
 
 int main(int argc, char** argv) {
   if (argc < 2) {
-    std::fprintf(stderr, "usage: eval_matrix_driver MATRIX.txt [--print]\n");
+    std::fprintf(stderr, "usage: eval_matrix_driver MATRIX.txt [--print] [--partial]\n");
     return 2;
   }
-  const bool print = argc > 2 && std::string(argv[2]) == "--print";
+  bool print = false, partial = false;
+  for (int i = 2; i < argc; ++i) {
+    print = print || std::string(argv[i]) == "--print";
+    partial = partial || std::string(argv[i]) == "--partial";
+  }
   std::ifstream in(argv[1]);
   std::map<std::string, twr::Structure> structs;
   std::set<std::string> reached, excluded;
@@ -225,7 +240,8 @@ int main(int argc, char** argv) {
     CHECK(all.count(e), "exclusion %s is not an instantiation", e.c_str());
     CHECK(!reached.count(e), "exclusion %s is reached by a row", e.c_str());
   }
-  for (const std::string& a : all) CHECK(reached.count(a) || excluded.count(a), "no row reaches %s and no rule excludes it", a.c_str());
+  if (!partial)
+    for (const std::string& a : all) CHECK(reached.count(a) || excluded.count(a), "no row reaches %s and no rule excludes it", a.c_str());
   std::printf("eval_matrix_driver: %d rows, %zu of %zu instantiations reached, %zu excluded, %d failures\n", n_rows, reached.size(), all.size(),
               excluded.size(), fails);
   return fails ? 1 : 0;

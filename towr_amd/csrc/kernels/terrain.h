@@ -15,7 +15,11 @@ struct Terr {
 // HeightMapFromCSV (include/towr/terrain/height_map_from_csv.h:29-109): piecewise-constant heights per cell;
 // the "slope" is the step to the next / previous cell smeared over eps on the lower side of the step, checked
 // in the reference's order (next cell first); second derivatives are the base class's zeros.
+// Every threshold is the reference's: two separately rounded operations (x_end = cell * res, then x_end - eps).  A fused
+// multiply-add rounds (c + 1) res - eps once and lands on another double for about a quarter of the cells, which turns a slope
+// of diff / eps into 0 (or back) for a foothold on the threshold: no contraction in this function.
 TWR_DEV Terr grid_eval(const DevStruct* __restrict__ S, double x, double y) {
+#pragma clang fp contract(off)
   Terr t = {0.0, 0.0, 0.0, 0.0};
   const double* __restrict__ grid = reinterpret_cast<const double*>(S->grid_ptr);
   const int rows = S->grid_rows, cols = S->grid_cols;
@@ -53,7 +57,10 @@ TWR_DEV Terr grid_eval(const DevStruct* __restrict__ S, double x, double y) {
 // bilinear over the 2x2 cells around p evaluated in double and rounded to FLOAT; if one of the four cells lies outside
 // the map: the nearest cell when p is inside the map, otherwise std::out_of_range, which Grid::GetHeight turns into
 // numeric_limits<float>::max() (:41-45).
+// No contraction in this function either: the cell centres cx0 / px end in "- res * index", and on a centre line the +- eps
+// samples carry weights 1/6 and 5/6, so one exact value in six sits on a float rounding midpoint where the last bit of px decides.
 TWR_DEV float gridmap_sample(const DevStruct* __restrict__ S, double x, double y) {
+#pragma clang fp contract(off)
   const float* __restrict__ el = reinterpret_cast<const float*>(S->grid_ptr);
   const int sx = S->grid_rows, sy = S->grid_cols;
   const double res = S->grid_res, lx = sx * res, ly = sy * res, mx = S->grid_px, my = S->grid_py;
@@ -66,10 +73,10 @@ TWR_DEV float gridmap_sample(const DevStruct* __restrict__ S, double x, double y
     const double px = mx + 0.5 * lx - 0.5 * res - res * (double)ia, py = my + 0.5 * ly - 0.5 * res - res * (double)ja;
     const double rx = (x - px) / res, ry = (y - py) / res, fx = 1.0 - rx, fy = 1.0 - ry;
     const double f0 = el[ia + ja * (long)sx], f1 = el[ib + ja * (long)sx], f2 = el[ia + jb * (long)sx], f3 = el[ib + jb * (long)sx];
-    // no FMA contraction: the reference's products and sums are separately rounded doubles
-    return (float)__dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(__dmul_rn(f0, fx), fy), __dmul_rn(__dmul_rn(f1, rx), fy)),
-                                      __dmul_rn(__dmul_rn(f2, fx), ry)),
-                            __dmul_rn(__dmul_rn(f3, rx), ry));
+    // the reference's products and sums are separately rounded doubles: plain operators under the pragma above.  (HIP's
+    // __dmul_rn / __dadd_rn are inline `*` and `+` that carry the unit's own contraction: the sum written with them
+    // compiled to three fused multiply-adds.)
+    return (float)(f0 * fx * fy + f1 * rx * fy + f2 * fx * ry + f3 * rx * ry);
   }
   if (inside && i0 >= 0 && j0 >= 0 && i0 < sx && j0 < sy) return el[i0 + j0 * (long)sx];
   return 3.402823466e+38f;  // numeric_limits<float>::max()
@@ -83,7 +90,10 @@ TWR_DEV Terr gridmap_eval(const DevStruct* __restrict__ S, double x, double y) {
   t.hy = (double)(gridmap_sample(S, x, y + eps) - gridmap_sample(S, x, y - eps)) / (2 * eps);
   return t;
 }
+// The analytic maps round like the reference as well: Gap's 2a x + b cancels (62.8 - 60 at x = 1.31), so a fused slope differs from
+// the reference's by up to 11 ulp, which every force row on that foothold then carries.
 TWR_DEV Terr terrain_eval(const DevStruct* __restrict__ S, int id, double flat_height, double x, double y) {
+#pragma clang fp contract(off)
   Terr t = {0.0, 0.0, 0.0, 0.0};
   switch (id) {
     case 7: return grid_eval(S, x, y);
@@ -144,13 +154,14 @@ TWR_DEV void force_core(const DevStruct* __restrict__ S, const double f[3], doub
   const Terr t = terrain_eval(S, S->terrain_id, S->flat_height, px, py);
   const double mu = S->mu;
   const double vb[3][3] = {{-t.hx, -t.hy, 1.0}, {1.0, 0.0, t.hx}, {0.0, 1.0, t.hy}};  // n, t1, t2 (height_map.cc:93-139)
-  double nb[3][3], sq[3], nr[3];
+  double nb[3][3], sq[3], nr[3], inv_nr[3];
 #pragma unroll
   for (int b = 0; b < 3; ++b) {
     sq[b] = vb[b][0] * vb[b][0] + vb[b][1] * vb[b][1] + vb[b][2] * vb[b][2];
     nr[b] = sqrt(sq[b]);
 #pragma unroll
     for (int i = 0; i < 3; ++i) nb[b][i] = vb[b][i] / nr[b];
+    inv_nr[b] = nb[b][b == 0 ? 2 : b - 1];  // the component whose entry is 1: n.z, t1.x, t2.y
   }
   double rowv[5][3];  // the five pyramid directions
 #pragma unroll
@@ -178,8 +189,11 @@ TWR_DEV void force_core(const DevStruct* __restrict__ S, const double f[3], doub
     for (int b = 0; b < 3; ++b)
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        const double unit = i == dim ? 1.0 : 0.0;
-        const double outer = (1.0 / sq[b]) * (nr[b] * unit - vb[b][dim] * nb[b][i]);
+        // (1 / sq) (|v| unit - v[dim] v[i] / |v|).  On the diagonal that is |v| - v[dim]^2 / |v|, which cancels where the slope
+        // is steep (all but 1 / 145 of it at Gap's edges); written as the sum of the other two squares over |v| it does not
+        const double rest = vb[b][1 - dim] * vb[b][1 - dim] + vb[b][2] * vb[b][2];
+        const double inner = i == dim ? rest * inv_nr[b] : 0.0 - vb[b][dim] * nb[b][i];
+        const double outer = (1.0 / sq[b]) * inner;
         db[b][i] = outer * dv[b][i];
       }
     double dr[5][3];
