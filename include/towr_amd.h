@@ -167,6 +167,20 @@ int twr_terrain_grid_create(const double* heights, int rows, int cols, twr_terra
  * border band, std::out_of_range (-> FLT_MAX in Grid::GetHeight) outside the map. */
 int twr_terrain_grid_map_create(const float* elevation, int size_x, int size_y, double resolution, double pos_x,
                                 double pos_y, twr_terrain_grid** out);
+/* A new map in an existing grid_map handle (fpowr builds a fresh Grid from the request's map on every plan request,
+ * footstep_plan_server.cc:155): new content and centre, same size and resolution.  `elevation` is a layer of the handle's size
+ * as grid_map keeps it after GridMap::move, a circular buffer with start index (start_x, start_y) (GridMap::getStartIndex(); (0,0)
+ * for a map that was never moved); the handle keeps its own form, start index (0,0):
+ *   stored[i, j] = elevation[(i + start_x) mod size_x, (j + start_y) mod size_y]      (grid_map's getBufferIndexFromIndex)
+ * column-major like twr_terrain_grid_map_create; cells are copied bit for bit (a NaN cell stays that NaN).  Every structure that
+ * shares the handle sees the new map in its host-side calls from then on (twr_structure_initial_guess,
+ * twr_structure_variable_bounds; twr_terrain_grid_info: the `data` address stays the same), and a batch created afterwards
+ * uploads it.  A batch that already holds the map keeps its device copy until twr_batch_grid_map_sync.
+ * NOT safe against a concurrent host call on the handle or on a structure created with it: the caller serialises them.
+ * TWR_ERR_INVALID, with twr_last_error naming the argument and the handle unchanged: g or elevation NULL, elevation not
+ * 4-byte aligned, g a CSV grid, a start index outside [0, size), a non-finite position. */
+int twr_terrain_grid_map_update(twr_terrain_grid* g, const float* elevation /* size_x * size_y */, int start_x, int start_y,
+                                double pos_x, double pos_y);
 void twr_terrain_grid_destroy(twr_terrain_grid* g);
 /* As twr_structure_create for model->terrain_id == TWR_TERRAIN_CSV_GRID / TWR_TERRAIN_GRID_MAP (the grid must be
  * of the matching kind). */
@@ -287,6 +301,31 @@ int twr_batch_eval_plan(const twr_batch* b, int request, int flags, int events, 
 /* Ragged layout of the batch arrays, each n_problems+1 prefix sums in units of doubles:
  * problem p owns x[x_off[p]..x_off[p+1]), g[g_off[p]..), jac[jac_off[p]..). */
 int twr_batch_layout(const twr_batch* b, int64_t* x_off, int64_t* g_off, int64_t* jac_off);
+/* A new map for a live batch, in place: the batch's device copy of the grid_map layer behind handle `g` (a handle at least one
+ * structure of the batch was created with) and the map centre in the header of every structure of the batch that reads it are
+ * overwritten; the tables, work lists and plans of the batch, and everything built on it (twr_jac_ops, twr_jac_lsq, twr_jac_lm,
+ * the Gram tables) depend on the schedules alone and stay.  The device copy keeps its ADDRESS, so an evaluation captured in a
+ * hipGraph before the update sees the new map when it is replayed after it.  Structures of the batch on another map are not
+ * touched.  Same size and resolution only: another size is a new handle and a new batch.
+ *   twr_batch_grid_map_sync:          to the handle's current content and centre (twr_terrain_grid_map_update).  The host layer
+ *                                     goes to a staging buffer the batch owns (allocated by the first call) and from there into
+ *                                     the map by the same kernel.  Stream-ordered on hip_stream; NOT capturable (it reads
+ *                                     host memory, and its first call allocates).
+ *   twr_batch_grid_map_update_device: from a layer on the batch's device, as an elevation-mapping node leaves it: d_elevation
+ *                                     float[size_x * size_y], column-major, circular with start index (start_x, start_y) as in
+ *                                     twr_terrain_grid_map_update, and the centre (pos_x, pos_y).  One kernel launch and nothing
+ *                                     else: asynchronous on hip_stream, capturable in a hipGraph.  d_elevation is only read, and
+ *                                     read when the launch runs: keep it unchanged until then.  The HOST handle is NOT touched: a
+ *                                     caller that also uses the host-side structure calls (twr_structure_initial_guess,
+ *                                     twr_structure_variable_bounds) on the new map calls twr_terrain_grid_map_update as well.
+ * Both count as a call on the batch: at most ONE update or evaluation of a batch in flight at a time (serialise them on one
+ * stream; an evaluation enqueued before the update reads the old map, one enqueued after it the new one).  Device scope and sticky
+ * error as twr_batch_eval.  TWR_ERR_INVALID, with twr_last_error naming the argument, before any device is touched: b, g or
+ * d_elevation NULL, d_elevation not 4-byte aligned, g a CSV grid, g not a map of this batch, a start index outside [0, size),
+ * a non-finite position; nothing is changed then. */
+int twr_batch_grid_map_sync(twr_batch* b, const twr_terrain_grid* g, void* hip_stream);
+int twr_batch_grid_map_update_device(twr_batch* b, const twr_terrain_grid* g, const float* d_elevation, int start_x, int start_y,
+                                     double pos_x, double pos_y, void* hip_stream);
 
 /* One full NLP callback for every problem of the batch, device pointers in, device pointers out:
  *   ifopt::Problem::EvaluateConstraints(x)        -> g     (TWR_EVAL_VALUES)

@@ -118,6 +118,10 @@ def lib():
         L.twr_terrain_grid_map_create.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_double, C.c_double, C.c_double,
                                                   C.POINTER(C.c_void_p)]
         L.twr_terrain_grid_destroy.argtypes = [C.c_void_p]
+        L.twr_terrain_grid_map_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double]
+        L.twr_batch_grid_map_sync.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_batch_grid_map_update_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double,
+                                                       C.c_void_p]
         L.twr_structure_create_with_grid.argtypes = [C.POINTER(Model), C.POINTER(Schedule), C.POINTER(Params), C.c_void_p,
                                                      C.POINTER(C.c_void_p)]
         L.twr_structure_destroy.restype = None
@@ -303,6 +307,24 @@ class GridMap(TerrainGrid):
                                                  C.byref(self._h)))
         self.elevation, self.resolution, self.position = a, float(resolution), (float(position[0]), float(position[1]))
         self.heights = None
+
+    def update(self, elevation, position, start_index=(0, 0)):
+        """twr_terrain_grid_map_update: a new map of the same size and resolution in this handle.  `elevation` is the layer as
+        grid_map keeps it, a circular buffer with `start_index` (GridMap::getStartIndex(); (0, 0) for a map that was never
+        moved).  Afterwards `elevation` is the handle's copy, with start index (0, 0) -- np.roll(elevation, (-start_x, -start_y),
+        axis=(0, 1)) -- and `position` the new centre; every Structure built on this GridMap uses them in initial_guess and
+        variable_bounds.  A Batch that holds the map keeps its device copy until Batch.sync_grid_map.  Not safe against a
+        concurrent host call on a Structure of this map."""
+        a = np.asfortranarray(elevation, dtype=np.float32)
+        if a.shape != self.elevation.shape:
+            raise TowrError("GridMap.update: the layer is %r, the map %r (another size is a new GridMap)" % (a.shape, self.elevation.shape))
+        _check(lib().twr_terrain_grid_map_update(self._h, a.ctypes.data, int(start_index[0]), int(start_index[1]),
+                                                 float(position[0]), float(position[1])))
+        px, py, data = C.c_double(), C.c_double(), C.c_void_p()
+        _check(lib().twr_terrain_grid_info(self._h, None, None, None, None, C.byref(px), C.byref(py), C.byref(data)))
+        stored = np.ctypeslib.as_array(C.cast(data, C.POINTER(C.c_float)), shape=(a.size,))
+        self.elevation = np.array(stored.reshape(a.shape, order="F"), dtype=np.float32, order="F")
+        self.position = (px.value, py.value)
 
 
 class Planes:
@@ -502,6 +524,29 @@ class Batch:
         """Asynchronous launch on raw device pointers (ints), e.g. torch tensors' data_ptr()."""
         _check(lib().twr_batch_eval(self._h, C.c_void_p(d_x), C.c_void_p(d_g), C.c_void_p(d_jac), flags,
                                     C.c_void_p(stream)))
+
+    def sync_grid_map(self, gm, stream=None):
+        """twr_batch_grid_map_sync: the batch's device copy of GridMap `gm` (one its structures were built on) brought to gm's
+        current content and centre (GridMap.update), in place; stream-ordered on `stream` (a raw stream, None: the default
+        stream), not capturable.  At most one update or evaluation of the batch in flight."""
+        _check(lib().twr_batch_grid_map_sync(self._h, gm._h, C.c_void_p(stream or 0)))
+
+    def update_grid_map_device(self, gm, d_elevation, start_index, position, stream=None):
+        """twr_batch_grid_map_update_device: the same from a float32 layer on the batch's device -- a torch tensor in grid_map's
+        column-major storage order (1-D of size_x * size_y, or 2-D [size_x, size_y] with stride (1, size_x), e.g.
+        torch.empty(size_y, size_x).t()), or a raw device pointer -- with its start index and the new centre.  One kernel
+        launch, asynchronous on `stream`, capturable; the layer is only read.  gm itself (the host handle) is NOT updated."""
+        sx, sy = gm.elevation.shape
+        if hasattr(d_elevation, "data_ptr"):
+            t = d_elevation
+            flat = t.dim() == 1 and t.is_contiguous()
+            column_major = t.dim() == 2 and tuple(t.shape) == (sx, sy) and t.t().is_contiguous()
+            if str(t.dtype) != "torch.float32" or t.numel() != sx * sy or not (flat or column_major):
+                raise TowrError("update_grid_map_device: d_elevation must hold %d x %d float32 cells in column-major order" % (sx, sy))
+            d_elevation = t.data_ptr()
+        _check(lib().twr_batch_grid_map_update_device(self._h, gm._h, C.c_void_p(int(d_elevation)), int(start_index[0]),
+                                                      int(start_index[1]), float(position[0]), float(position[1]),
+                                                      C.c_void_p(stream or 0)))
 
     def table_bytes(self):
         """Device bytes of the batch's tables: resident, layout tables of the dynamic set as built, and what is left of them

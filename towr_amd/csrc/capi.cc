@@ -127,6 +127,47 @@ int twr_terrain_grid_map_create(const float* elevation, int size_x, int size_y, 
     return fail(TWR_ERR_INVALID, e.what());
   }
 }
+namespace {
+// What the map-update calls check of a layer, its start index and the map centre: false with the reason in `why`.
+bool layer_ok(const twr::TerrainGrid& t, const void* layer, const char* layer_name, int start_x, int start_y, double pos_x, double pos_y,
+              std::string& why) {
+  if (!layer) why = std::string(layer_name) + " is NULL";
+  else if (reinterpret_cast<uintptr_t>(layer) & 3) why = std::string(layer_name) + " is not 4-byte aligned";
+  else if (start_x < 0 || start_x >= t.rows) why = "start_x " + std::to_string(start_x) + " is outside [0, size_x = " + std::to_string(t.rows) + ")";
+  else if (start_y < 0 || start_y >= t.cols) why = "start_y " + std::to_string(start_y) + " is outside [0, size_y = " + std::to_string(t.cols) + ")";
+  else if (!std::isfinite(pos_x)) why = "pos_x is not finite";
+  else if (!std::isfinite(pos_y)) why = "pos_y is not finite";
+  else return true;
+  return false;
+}
+}  // namespace
+
+int twr_terrain_grid_map_update(twr_terrain_grid* g, const float* elevation, int start_x, int start_y, double pos_x, double pos_y) {
+  if (!g || !g->g) return fail(TWR_ERR_INVALID, "g is NULL");
+  twr::TerrainGrid& t = *g->g;
+  if (!t.grid_map) return fail(TWR_ERR_INVALID, "g is not a grid_map layer (a CSV grid cannot be updated)");
+  std::string why;
+  if (!layer_ok(t, elevation, "elevation", start_x, start_y, pos_x, pos_y, why)) return fail(TWR_ERR_INVALID, why);
+  try {
+    // stored[i, j] = elevation[(i + start_x) mod size_x, (j + start_y) mod size_y], column by column as two runs; built aside
+    // (`elevation` may be the handle's own data) and copied in, so that the address twr_terrain_grid_info gave out stays
+    // valid: cells as they are, NaN included
+    const size_t sx = (size_t)t.rows, sy = (size_t)t.cols, head = sx - (size_t)start_x;
+    std::vector<float> next(sx * sy);
+    for (size_t j = 0; j < sy; ++j) {
+      const float* s = elevation + ((j + (size_t)start_y) % sy) * sx;
+      float* d = next.data() + j * sx;
+      std::memcpy(d, s + start_x, head * sizeof(float));
+      std::memcpy(d + head, s, (size_t)start_x * sizeof(float));
+    }
+    std::memcpy(t.elevation.data(), next.data(), next.size() * sizeof(float));
+    t.pos_x = pos_x;
+    t.pos_y = pos_y;
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+}
 void twr_terrain_grid_destroy(twr_terrain_grid* g) { delete g; }
 
 int twr_structure_create(const twr_model* model, const twr_schedule* schedule, const twr_params* params,
@@ -376,6 +417,7 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
     std::vector<char> host_arena(blob_off[n_structs], 0);
     std::vector<uint64_t> blob_at(n_structs);
     std::vector<const twr::TerrainGrid*> host_grids;
+    std::vector<std::vector<uint64_t>> hdr_of_grid;   // per distinct `Grid` map: where its readers keep the map centre
     for (int i = 0; i < n_structs; ++i) {
       blob_at[i] = reinterpret_cast<uint64_t>(b->arena.get()) + blob_off[i];
       std::memcpy(host_arena.data() + blob_off[i], sp[i]->blob.data(), sp[i]->blob.size());
@@ -388,8 +430,27 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
         b->grids.push_back(dev_alloc<void>(bytes));
         TWR_HIP(hipMemcpy(b->grids[q].get(), src, bytes, hipMemcpyHostToDevice));
         host_grids.push_back(tg);
+        b->grid_of.push_back(sp[i]->grid);
+        hdr_of_grid.emplace_back();
       }
-      reinterpret_cast<twr::DevStruct*>(host_arena.data() + blob_off[i])->grid_ptr = reinterpret_cast<uint64_t>(b->grids[q].get());
+      twr::DevStruct* H = reinterpret_cast<twr::DevStruct*>(host_arena.data() + blob_off[i]);
+      H->grid_ptr = reinterpret_cast<uint64_t>(b->grids[q].get());
+      if (tg->grid_map) {
+        // the centre as the handle has it now (twr_terrain_grid_map_update may have moved it since the structure was built)
+        H->grid_px = tg->pos_x;
+        H->grid_py = tg->pos_y;
+        hdr_of_grid[q].push_back(blob_off[i] + offsetof(twr::DevStruct, grid_px));
+      }
+    }
+    static_assert(offsetof(twr::DevStruct, grid_py) == offsetof(twr::DevStruct, grid_px) + sizeof(double), "grid_py follows grid_px");
+    {
+      std::vector<uint64_t> all;
+      b->grid_hdr_first.assign(1, 0);
+      for (const std::vector<uint64_t>& h : hdr_of_grid) {
+        all.insert(all.end(), h.begin(), h.end());
+        b->grid_hdr_first.push_back((int32_t)all.size());
+      }
+      b->grid_hdr = upload_nonempty(all);
     }
     TWR_HIP(hipMemcpy(b->arena.get(), host_arena.data(), host_arena.size(), hipMemcpyHostToDevice));
     b->table_bytes = (int64_t)host_arena.size();
@@ -464,6 +525,60 @@ int twr_batch_layout(const twr_batch* b, int64_t* x_off, int64_t* g_off, int64_t
   if (g_off) std::memcpy(g_off, b->plan.g_off.data(), bytes);
   if (jac_off) std::memcpy(jac_off, b->plan.j_off.data(), bytes);
   return TWR_OK;
+}
+
+namespace {
+// The batch's copy of the map behind handle g: its index in twr_batch::grids, or -1 with the reason in `why`.
+int held_grid_map(const twr_batch* b, const twr_terrain_grid* g, std::string& why) {
+  if (!b) return why = "b is NULL", -1;
+  if (!g || !g->g) return why = "g is NULL", -1;
+  if (!g->g->grid_map) return why = "g is not a grid_map layer (a CSV grid cannot be updated)", -1;
+  for (size_t q = 0; q < b->grid_of.size(); ++q)
+    if (b->grid_of[q].get() == g->g.get()) return (int)q;
+  return why = "g is not a map of this batch (no structure of the batch was created with it)", -1;
+}
+// The one launch of both update calls: layer `src` on the device (start index (start_x, start_y)) into the batch's map q
+int update_held_map(twr_batch* b, int q, const float* d_src, int start_x, int start_y, double pos_x, double pos_y, hipStream_t stream) {
+  const twr::TerrainGrid& t = *b->grid_of[q];
+  const int first = b->grid_hdr_first[q], n_hdr = b->grid_hdr_first[q + 1] - first;
+  return launched(twr::launch_grid_map_update(d_src, static_cast<float*>(b->grids[q].get()), t.rows, t.cols, start_x, start_y, pos_x, pos_y,
+                                              b->arena.get(), n_hdr ? b->grid_hdr.d.get() + first : nullptr, n_hdr, stream));
+}
+}  // namespace
+
+int twr_batch_grid_map_sync(twr_batch* b, const twr_terrain_grid* g, void* hip_stream) {
+  std::string why;
+  const int q = held_grid_map(b, g, why);
+  if (q < 0) return fail(TWR_ERR_INVALID, why);
+  try {
+    DeviceScope on(b->device);
+    TWR_HIP(on.status);
+    hipStream_t stream = static_cast<hipStream_t>(hip_stream);
+    const twr::TerrainGrid& t = *g->g;
+    if (!b->grid_stage) {   // one staging buffer for every map of the batch
+      size_t cells = 0;
+      for (const auto& m : b->grid_of)
+        if (m->grid_map) cells = std::max(cells, m->elevation.size());
+      b->grid_stage = dev_alloc<float>(cells * sizeof(float));
+    }
+    // host layer -> staging (ordered behind what the stream holds; the map an evaluation in front of it reads is not touched),
+    // staging -> the map and the headers: the same launch as twr_batch_grid_map_update_device, with start index (0,0)
+    TWR_HIP(hipMemcpyAsync(b->grid_stage.get(), t.elevation.data(), t.elevation.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    return update_held_map(b, q, b->grid_stage.get(), 0, 0, t.pos_x, t.pos_y, stream);
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+int twr_batch_grid_map_update_device(twr_batch* b, const twr_terrain_grid* g, const float* d_elevation, int start_x, int start_y,
+                                     double pos_x, double pos_y, void* hip_stream) {
+  std::string why;
+  const int q = held_grid_map(b, g, why);
+  if (q < 0) return fail(TWR_ERR_INVALID, why);
+  if (!layer_ok(*g->g, d_elevation, "d_elevation", start_x, start_y, pos_x, pos_y, why)) return fail(TWR_ERR_INVALID, why);
+  DeviceScope on(b->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  return update_held_map(b, q, d_elevation, start_x, start_y, pos_x, pos_y, static_cast<hipStream_t>(hip_stream));
 }
 
 // Tuning knobs of the launches (include/towr_amd.h): a TUNING=1 build reads them on every evaluation; the default build reads

@@ -89,6 +89,13 @@ struct twr_batch {
                                              // one upload instead of a thousand)
   int64_t table_bytes = 0;                   // arena bytes
   std::vector<DevPtr<void>> grids;           // device copies of the distinct gridded terrains
+  // twr_batch_grid_map_sync / _update_device: the handle behind grids[q] (kept alive: it is how a caller names the map), and
+  // for a `Grid` map the headers that read it -- entries [grid_hdr_first[q], grid_hdr_first[q + 1]) of grid_hdr, each the
+  // byte offset of a DevStruct::grid_px in the arena.  Built once by twr_batch_create; a CSV grid has no entries.
+  std::vector<std::shared_ptr<const twr::TerrainGrid>> grid_of;
+  std::vector<int32_t> grid_hdr_first;
+  DevList<uint64_t> grid_hdr;
+  DevPtr<float> grid_stage;                  // twr_batch_grid_map_sync: where the host layer lands (first call; the largest map)
   DevList<twr::DynWork> dyn;
   DevList<twr::RomWork> rom;
   DevList<twr::NodeWork> node;               // (+ the end entry, not counted)

@@ -48,5 +48,9 @@ hipError_t launch_planes(const double* plan, const int32_t* counts, const double
                          int n_problems, int max_steps, int n_ee, int32_t* plane_index, hipStream_t stream);
 hipError_t launch_sample(const SampleWork* work, int n_work, const double* x, double* out, double dt, const double* times,
                          hipStream_t stream);
+// dst (a batch's copy of a `Grid` layer, start index (0,0)) from src (the same sizes, start index (start_x, start_y)), and the map
+// centre into the n_hdr headers whose DevStruct::grid_px lies hdr_off[k] bytes into arena (kernels/grid_map_update.h).  One launch.
+hipError_t launch_grid_map_update(const float* src, float* dst, int size_x, int size_y, int start_x, int start_y, double pos_x,
+                                  double pos_y, void* arena, const uint64_t* hdr_off, int n_hdr, hipStream_t stream);
 
 }  // namespace twr

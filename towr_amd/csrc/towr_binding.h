@@ -120,6 +120,18 @@ inline DeviceTerrain GridTerrain(grid_map::GridMap map) {
   d.grid = OwnGrid(g);
   return d;
 }
+// The next plan request's map in the same handle (same size and resolution): the layer goes over as grid_map holds it, start
+// index included -- no convertToDefaultStartIndex() copy.  A batch that holds the map follows with twr_batch_grid_map_sync.
+inline void UpdateGridTerrain(const DeviceTerrain& d, const grid_map::GridMap& map) {
+  int32_t size_x = 0, size_y = 0;
+  double res = 0.0;
+  if (twr_terrain_grid_info(d.grid.get(), nullptr, &size_x, &size_y, &res, nullptr, nullptr, nullptr) != TWR_OK ||
+      map.getSize()(0) != size_x || map.getSize()(1) != size_y || map.getResolution() != res)
+    throw std::runtime_error("towr_amd: UpdateGridTerrain needs a map of the handle's size and resolution (else: GridTerrain, new structures)");
+  if (twr_terrain_grid_map_update(d.grid.get(), map["elevation"].data(), map.getStartIndex()(0), map.getStartIndex()(1),
+                                  map.getPosition().x(), map.getPosition().y()) != TWR_OK)
+    throw std::runtime_error(std::string("towr_amd: ") + twr_last_error());
+}
 #endif
 
 #ifdef TOWR_AMD_HAVE_RAPIDCSV

@@ -1,7 +1,9 @@
 // Third translation unit of the kernels, plain flags: the utility kernels -- trajectory sampling, scoring from g, the planner's arg-min,
-// contact plan, nearest plane, TWR_EVAL_CHECK -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
+// contact plan, nearest plane, TWR_EVAL_CHECK, the grid_map layer update -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <algorithm>
 
 #include "launch.h"
 
@@ -9,6 +11,7 @@
 #include "kernels/host_launch.h"
 #include "kernels/spline_math.h"
 #include "kernels/phase_durations.h"
+#include "kernels/grid_map_update.h"
 
 namespace twr {
 
@@ -549,6 +552,28 @@ hipError_t launch_check(int n_problems, const int64_t* g_off, const int64_t* j_o
   hipError_t e = hipMemsetAsync(status, 0, sizeof(int32_t) * (size_t)n_problems, stream);
   if (e != hipSuccess) return e;
   return twr_launch(check_kernel, dim3(n_problems * kCheckParts), dim3(256), 0, stream, g_off, j_off, g, jac, status, flags);
+}
+
+// ---------------------------------------------------------------- a new grid_map layer (kernels/grid_map_update.h)
+// One launch: wave w of the grid copies columns w, w + waves, ... of the layer (un-rolling the circular buffer), and thread t
+// of the grid writes the new map centre into headers t, t + threads, ... of the map's list.  Every index comes from the sizes,
+// the start index and that list; src is only read.
+__global__ __launch_bounds__(256) void grid_map_update_kernel(const uint32_t* __restrict__ src, uint32_t* __restrict__ dst, int size_x,
+                                                              int size_y, int start_x, int start_y, double pos_x, double pos_y,
+                                                              char* __restrict__ arena, const uint64_t* __restrict__ hdr_off, int n_hdr) {
+  const int lane = threadIdx.x & 63, wave = blockIdx.x * 4 + (threadIdx.x >> 6), n_waves = gridDim.x * 4;
+  for (int j = wave; j < size_y; j += n_waves) grid_map_unroll_column(src, dst, size_x, size_y, start_x, start_y, j, lane);
+  for (int k = blockIdx.x * 256 + threadIdx.x; k < n_hdr; k += gridDim.x * 256) grid_map_put_centre(arena, hdr_off, k, pos_x, pos_y);
+}
+hipError_t launch_grid_map_update(const float* src, float* dst, int size_x, int size_y, int start_x, int start_y, double pos_x,
+                                  double pos_y, void* arena, const uint64_t* hdr_off, int n_hdr, hipStream_t stream) {
+  if (size_x < 1 || size_y < 1 || start_x < 0 || start_x >= size_x || start_y < 0 || start_y >= size_y || n_hdr < 0)
+    return hipErrorInvalidValue;   // (the C ABI has checked all of it: nothing out of range reaches the device)
+  const int want = std::max((size_y + 3) / 4, (n_hdr + 255) / 256);   // a wave per column, a thread per header
+  const int blocks = std::min(std::max(want, 1), 1024);
+  return twr_launch(grid_map_update_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const uint32_t*>(src),
+                    reinterpret_cast<uint32_t*>(dst), size_x, size_y, start_x, start_y, pos_x, pos_y, static_cast<char*>(arena), hdr_off,
+                    n_hdr);
 }
 
 }  // namespace twr
