@@ -85,6 +85,10 @@ def lib():
         L.orc_hermite_dpos_dT.restype = C.c_double
         L.orc_euler_probe.argtypes = [_dp, C.c_double, C.c_double, _dp]
         L.orc_hermite_weights.argtypes = [C.c_double, C.c_double, _dp]
+        L.orc_locate.argtypes = [_dp, C.c_int, _dp, C.c_int, _ip, _dp]
+        L.orc_locate.restype = C.c_int
+        L.orc_phase_poly_durations.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]
+        L.orc_phase_poly_durations.restype = C.c_int
         L.orc_terrain_height.argtypes = [C.c_int, C.c_double, C.c_double]
         L.orc_terrain_height.restype = C.c_double
         L.orc_terrain_basis.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, _dp]
@@ -247,6 +251,26 @@ def hermite_weights(t, T):
     w = np.zeros(12)
     lib().orc_hermite_weights(t, T, _d(w))
     return w.reshape(3, 4)
+
+
+def locate(durations, times):
+    """NodeSpline::GetLocalTime (Spline::GetSegmentID / GetLocalTime) on one duration list: (id (n,) int32, t_local (n,)); a
+    time for which no segment is found has id -1 and t_local NaN."""
+    d = np.ascontiguousarray(durations, dtype=np.float64)
+    t = np.ascontiguousarray(times, dtype=np.float64)
+    ids, tl = np.zeros(len(t), dtype=np.int32), np.zeros(len(t))
+    lib().orc_locate(_d(d), len(d), _d(t), len(t), _i(ids), _d(tl))
+    return ids, tl
+
+
+def phase_poly_durations(n, contact_at_start, pps, ppf, given, variables):
+    """PhaseDurations::SetVariables, then the polynomial durations of the ee-motion and ee-force nodes: (ph, md, fd)"""
+    g = np.ascontiguousarray(given, dtype=np.float64)
+    v = np.ascontiguousarray(variables, dtype=np.float64)
+    assert len(g) == n and len(v) == n - 1
+    ph, md, fd = np.zeros(n), np.zeros(n * max(pps, ppf, 1)), np.zeros(n * max(pps, ppf, 1))
+    c = lib().orc_phase_poly_durations(n, int(bool(contact_at_start)), pps, ppf, _d(g), _d(v), _d(ph), _d(md), _d(fd))
+    return ph, md[:c & 0xFFFF].copy(), fd[:c >> 16].copy()
 
 
 def hermite_dpos_dT(t, T, p0, v0, p1, v1):

@@ -45,11 +45,18 @@
 //                        duration, then the contact_set (plane index per foot, -1 = in the air)
 //   ref_dump --terrain-points IN OUT [--csv FILE]   the terrains alone at given points, see TerrainPoints() below
 //                        (oracle/ref_golden.py --terrain records it as tests/golden/refterrain_*.npz)
+//   ref_dump --segment-points IN OUT   Spline::GetSegmentID / GetLocalTime on given duration lists and times, or
+//                        PhaseDurations::SetVariables + ConvertPhaseToPolyDurations on given schedule variables, see
+//                        SegmentPoints() below (oracle/ref_golden.py --segments records it as tests/golden/refsegment.npz);
+//                        exit code 5 for a time the lookup is not defined for
 #include <ifopt/problem.h>
 #include <towr/initialization/gait_generator.h>
 #include <towr/nlp_formulation.h>
 #include <towr/terrain/examples/height_map_examples.h>
 #include <towr/terrain/height_map_from_csv.h>
+#include <towr/variables/nodes_variables_phase_based.h>
+#include <towr/variables/phase_durations.h>
+#include <towr/variables/spline.h>
 #if __has_include(<grid_map_ros/grid_map_ros.hpp>) && __has_include(<convex_plane_decomposition_msgs/PlanarTerrain.h>)
 #include <towr/terrain/grid_height_map.h>
 #define TWR_REF_HAVE_GRID_MAP 1
@@ -158,8 +165,123 @@ static int TerrainPoints(int argc, char** argv) {
   return 0;
 }
 
+// the protected Spline::GetLocalTime, made callable
+struct SegmentSpline : towr::Spline {
+  SegmentSpline() : towr::Spline({1.0}, 1) {}
+  using towr::Spline::GetLocalTime;
+};
+
+// ref_dump --segment-points IN OUT: the segment lookup and the duration conversion alone, no NLP.  IN holds raw doubles, the
+// first one the mode.
+//   mode 0: the number of lists; per list its length n and n durations; the number of points; per point the index of its
+//           list and t.  OUT: per point Spline::GetSegmentID(t, list) and the id and local time of Spline::GetLocalTime(t,
+//           list) -- three doubles.  A point with t < 0, or for which no accumulated sum reaches t - 1e-10, is outside what
+//           spline.cc:48-66 defines (its asserts): nothing is written and the exit code is 5.
+//   mode 1: the number of cases; per case the number of phases n, whether the foot starts in contact, the polynomials per
+//           swing phase and per stance phase of the force, the n given durations and the n - 1 schedule variables (their sum
+//           below the given total, phase_durations.cc:91).  OUT: per case PhaseDurations::GetPhaseDurations() after
+//           SetVariables (n), then the count and the values of ConvertPhaseToPolyDurations of NodesVariablesEEMotion and of
+//           NodesVariablesEEForce on them.
+static int SegmentPoints(int argc, char** argv) {
+  if (argc != 4) {
+    std::fprintf(stderr, "usage: ref_dump --segment-points IN OUT\n");
+    return 2;
+  }
+  std::vector<double> in;
+  {
+    std::FILE* f = std::fopen(argv[2], "rb");
+    if (!f) {
+      std::fprintf(stderr, "cannot read %s\n", argv[2]);
+      return 2;
+    }
+    double buf[4096];
+    size_t got;
+    while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) in.insert(in.end(), buf, buf + got);
+    std::fclose(f);
+  }
+  size_t at = 0;
+  auto have = [&](size_t k) { return at + k <= in.size(); };
+  auto bad = [&](const char* what) {
+    std::fprintf(stderr, "%s: %s\n", argv[2], what);
+    return 2;
+  };
+  if (!have(2)) return bad("empty");
+  const int mode = static_cast<int>(in[at++]);
+  std::vector<double> out;
+  if (mode == 0) {
+    const long n_lists = static_cast<long>(in[at++]);
+    std::vector<std::vector<double>> lists;
+    for (long l = 0; l < n_lists; ++l) {
+      if (!have(1)) return bad("truncated list");
+      const long n = static_cast<long>(in[at++]);
+      if (n < 1 || !have(n)) return bad("truncated list");
+      lists.emplace_back(in.begin() + at, in.begin() + at + n);
+      at += n;
+    }
+    if (!have(1)) return bad("no points");
+    const long n_points = static_cast<long>(in[at++]);
+    if (n_points < 0 || at + 2 * static_cast<size_t>(n_points) != in.size()) return bad("point count");
+    const SegmentSpline spline;
+    for (long k = 0; k < n_points; ++k, at += 2) {
+      const long l = static_cast<long>(in[at]);
+      const double t = in[at + 1];
+      if (l < 0 || l >= n_lists) return bad("list index");
+      bool found = false;
+      double acc = 0.0;
+      for (double d : lists[l]) {
+        acc += d;
+        if (acc >= t - 1e-10) found = true;
+      }
+      if (!(t >= 0.0) || !found) {
+        std::fprintf(stderr, "--segment-points: point %ld (list %ld, t = %.17g) is outside what Spline::GetSegmentID defines\n", k, l, t);
+        return 5;
+      }
+      const auto lt = spline.GetLocalTime(t, lists[l]);
+      out.push_back(towr::Spline::GetSegmentID(t, lists[l]));
+      out.push_back(lt.first);
+      out.push_back(lt.second);
+    }
+  } else if (mode == 1) {
+    const long n_cases = static_cast<long>(in[at++]);
+    for (long c = 0; c < n_cases; ++c) {
+      if (!have(4)) return bad("truncated case");
+      const long n = static_cast<long>(in[at]);
+      const bool contact = in[at + 1] != 0.0;
+      const int pps = static_cast<int>(in[at + 2]), ppf = static_cast<int>(in[at + 3]);
+      at += 4;
+      if (n < 1 || pps < 1 || ppf < 1 || !have(2 * n - 1)) return bad("truncated case");
+      const std::vector<double> given(in.begin() + at, in.begin() + at + n);
+      Eigen::VectorXd x(n - 1);
+      for (long i = 0; i < n - 1; ++i) x(i) = in[at + n + i];
+      at += 2 * n - 1;
+      towr::PhaseDurations pd(0, given, contact, 0.0, 1e20);
+      pd.SetVariables(x);
+      const std::vector<double> ph = pd.GetPhaseDurations();
+      const towr::NodesVariablesEEMotion motion(n, contact, "m", pps);
+      const towr::NodesVariablesEEForce force(n, contact, "f", ppf);
+      const std::vector<double> md = motion.ConvertPhaseToPolyDurations(ph), fd = force.ConvertPhaseToPolyDurations(ph);
+      out.insert(out.end(), ph.begin(), ph.end());
+      out.push_back(md.size());
+      out.insert(out.end(), md.begin(), md.end());
+      out.push_back(fd.size());
+      out.insert(out.end(), fd.begin(), fd.end());
+    }
+    if (at != in.size()) return bad("trailing data");
+  } else {
+    return bad("unknown mode");
+  }
+  std::FILE* f = std::fopen(argv[3], "wb");
+  if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size() || std::fclose(f) != 0) {
+    std::fprintf(stderr, "cannot write %s\n", argv[3]);
+    return 2;
+  }
+  std::printf("ref_dump: segment mode %d, %zu values\n", mode, out.size());
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--terrain-points") return TerrainPoints(argc, argv);
+  if (argc >= 2 && std::string(argv[1]) == "--segment-points") return SegmentPoints(argc, argv);
   if (argc < 9) {
     std::fprintf(stderr, "usage: see the header of ref_dump.cc\n");
     return 2;

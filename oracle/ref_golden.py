@@ -10,6 +10,7 @@ the structure builder (CPU) and the device (GPU) on boxes that do not have the r
 
     python -m oracle.ref_golden --traj [names...]   (the fixtures tests/golden/reftraj_*.npz, see TRAJ_CASES below)
     python -m oracle.ref_golden --terrain [names...]   (tests/golden/refterrain_*.npz, see TERRAIN_FIXTURES below)
+    python -m oracle.ref_golden --segments          (tests/golden/refsegment.npz, see record_segments below)
 
 The cases are chosen for what the mpmath fixtures and the hand known-answers cannot reach: entries the reference DEFINES
 rather than derives (force rows x footholds on curved terrain, terrain rows of gridded terrain, explicit zeros), bounds,
@@ -62,7 +63,7 @@ def _phases(n_ee, n_ph, T, start_contact, seed):
     return _sched(durs, [int(start_contact)] * n_ee)
 
 
-# name -> (robot, terrain, schedule builder, params, x families); an x family is ("guess" | "perturbed" | "wild" | "snapped", seed)
+# name -> (robot, terrain, schedule builder, params, x families); an x family is ("guess" | "perturbed" | "wild" | "snapped" | "junctions", seed)
 W2 = (("wild", 1), ("wild", 2))
 P1 = (("perturbed", 1),)
 W1 = (("wild", 1),)
@@ -87,6 +88,10 @@ CASES = {
     "every_go1": ("go1", "block", lambda: _combo("go1", 0, 1.2), dict(constraint_sets=255, base_z_init=0.3, **COARSE), P1),
     "timings_63_monoped": ("monoped", "stairs", lambda: _combo("monoped", 1, 1.2), dict(constraint_sets=63, dt_dynamic=0.2, dt_rom=0.2), W1),
     "timings_127_biped": ("biped", "gap", lambda: _combo("biped", 0, 1.2), dict(constraint_sets=127, **COARSE), P1),
+    # junctions of the optimised phases on the thresholds of the segment lookup (Case.x_junctions: an accumulated sum on
+    # fl(t - 1e-10) of a time node t, on its neighbours, on t itself); K = 12 and one x: what the size budget of this set leaves
+    "timings_junctions_biped": ("biped", "gap", lambda: _combo("biped", 0, 1.2), dict(constraint_sets=127, duration_base_poly=0.2, **_k(1.2, 12)),
+                                (("junctions", 1),)),
     "timings_rom_only": ("biped", "flat", lambda: _combo("biped", 2, 1.2), dict(constraint_sets=64 | 8, dt_rom=0.21), W1),
     "timings_dynamic_only": ("biped", "block", lambda: _combo("biped", 2, 1.2), dict(constraint_sets=64 | 2, dt_dynamic=0.23), P1),
     "timings_terrain_force": ("hyq", "slope", lambda: _combo("hyq", 1, 1.2), dict(constraint_sets=64 | 16 | 1), W1),
@@ -126,6 +131,8 @@ def make_x(case, family, seed):
         return case.x_guess()
     if family == "perturbed":
         return case.x_perturbed(seed)
+    if family == "junctions":
+        return case.x_junctions(seed)
     x = case.x_wild(seed)
     if family == "snapped":   # a third of the foothold coordinates next to the edges of the 0.17 m cells (inside and outside
         # the slope window), a tenth of them exactly ON an edge (k * 0.17 as the double product: the tie of the cell index)
@@ -208,6 +215,10 @@ TRAJ_CASES = {
     "biped_timings": ("biped", "flat", lambda: _combo("biped", 0, 1.2), dict(constraint_sets=127, polys_per_stance_force=2), 0.01, (5,), 4.0),
     "anymal_stairs": ("anymal", "stairs", lambda: _combo("anymal", 1, 2.0), dict(constraint_sets=63), 0.025, (6,), 5.0),
     "anymal_gap_timings": ("anymal", "gap", lambda: _combo("anymal", 0, 2.0), dict(constraint_sets=127), 0.03, (7,), 5.0),
+    # an eighth field: the schedule variables are those of Case.x_junctions(seed, times = the accumulated sample times), and
+    # the guess times add the threshold doubles of every junction of that x with their neighbouring doubles
+    "biped_junctions": ("biped", "stairs", lambda: _combo("biped", 0, 1.2), dict(constraint_sets=127, polys_per_swing=3, **_k(1.2, 32)), 0.01, (8, 3),
+                        4.0, "junctions"),
 }
 
 
@@ -260,18 +271,61 @@ def make_traj_x(case, seed, ang_scale):
     return x
 
 
+def junction_schedules(case, x):
+    """per foot of a case with optimised timings at x: (phase, ee-motion polynomial, ee-force polynomial) durations"""
+    from tests import segment_points as sp
+
+    out, p = [], case.params
+    for vs in case.S.var_sets:
+        if vs["name"].startswith("ee-schedule"):
+            e = int(vs["name"][len("ee-schedule"):])
+            ph = sp.set_variables(case.sched.durations()[e], x[vs["offset"]:vs["offset"] + vs["size"]])
+            contact = bool(case.sched.contact()[e])
+            out.append((ph, sp.poly_durations(ph, contact, p.polys_per_swing), sp.poly_durations(ph, not contact, p.polys_per_stance_force)))
+    return out
+
+
+def make_junction_traj(case, seeds, ang_scale, dt, T):
+    """(the x of a junction fixture, the guess times on their thresholds)"""
+    from tests import segment_points as sp
+
+    t, samples = 0.0, []
+    while t <= T + 1e-5:
+        samples.append(t)
+        t += dt
+    xs, extra = [], []
+    for seed in seeds:
+        x = make_traj_x(case, seed, ang_scale)
+        xj = case.x_junctions(seed, times=samples)
+        for vs in case.S.var_sets:
+            if vs["name"].startswith("ee-schedule"):
+                x[vs["offset"]:vs["offset"] + vs["size"]] = xj[vs["offset"]:vs["offset"] + vs["size"]]
+        xs.append(x)
+        for lists in junction_schedules(case, x):
+            for d in lists:
+                for acc in sp.sums(d)[:-1]:
+                    thr = sp.threshold(acc)
+                    extra += [thr, float(np.nextafter(thr, -np.inf)), float(np.nextafter(thr, np.inf))]
+    return xs, np.array(sorted(set(extra)))[::-1]
+
+
 def compute_traj(name, workdir):
     """the arrays of reftraj_<name>.npz, from a run of the reference's code"""
     from oracle import ref_run
     from tests.common import Case
 
-    robot, terrain, sched, params, dt, seeds, ang_scale = TRAJ_CASES[name]
+    robot, terrain, sched, params, dt, seeds, ang_scale = TRAJ_CASES[name][:7]
+    junctions = len(TRAJ_CASES[name]) > 7
     case = Case(robot, terrain, sched(), **params)
     n_ee, p = N_EE[robot], case.params
     T = float(np.sum(case.sched.durations()[0]))
     rng = np.random.default_rng(len(name))
     times = np.concatenate([[0.0, T, p.duration_base_poly, 2 * p.duration_base_poly, case.sched.durations()[0][0], 0.5 * T],
                             rng.uniform(0.0, T, 66)])
+    junction_x = None
+    if junctions:
+        junction_x, extra = make_junction_traj(case, seeds, ang_scale, dt, T)
+        times = np.concatenate([times[:16], extra])
     assert len(times) > 64 and np.any(np.diff(times) < 0)
     for step in (dt, PLAN_DT):
         if not sample_times_defined(T, step, times):
@@ -279,8 +333,8 @@ def compute_traj(name, workdir):
     regions, bounds = traj_regions()
     args, kw = ref_run.case_args(case)
     xs, trajs, guesses, durs, sets, states = [], [], [], [], [], []
-    for seed in seeds:
-        x = make_traj_x(case, seed, ang_scale)
+    for k, seed in enumerate(seeds):
+        x = junction_x[k] if junctions else make_traj_x(case, seed, ang_scale)
         d = ref_run.run(os.path.join(workdir, "%s_%d" % (name, seed)), *args, x=x, sample_dt=dt, guess_times=times,
                         planes=(regions, bounds, PLAN_HORIZON), **kw)
         fine = ref_run.run(os.path.join(workdir, "%s_%d_fine" % (name, seed)), *args, x=x, sample_dt=PLAN_DT, **kw)["traj"]
@@ -354,6 +408,45 @@ def record_terrain(name, workdir):
     return path, os.path.getsize(path), len(ids), len(fi)
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/golden/refsegment.npz: Spline::GetSegmentID / GetLocalTime (ref_dump --segment-points) at the defined points of
+# tests/segment_points.py -- every junction threshold of every list and its neighbouring doubles -- and
+# PhaseDurations::SetVariables + ConvertPhaseToPolyDurations on its duration cases.  The file holds the lists (list_start,
+# durations) and per point point_list, point_t, seg_id (uint8) and t_local; per duration case its inputs (case_head
+# [n_phases, contact, pps, ppf], case_given, case_vars) and the reference's case_ph, case_md, case_fd with their starts.
+# tests/test_segment_probe.py regenerates the points, compares the oracle and mp_ref bit for bit (CPU) and the device (GPU).
+def compute_segments(workdir):
+    from oracle import ref_run
+    from tests import segment_points as sp
+
+    p = sp.points()
+    sel = np.nonzero(p["defined"])[0]
+    lists = [sp.list_of(k) for k in range(len(p["list_start"]) - 1)]
+    for k, t in zip(p["point_list"][sel], p["point_t"][sel]):   # (ref_dump refuses them as well, with exit code 5)
+        if not (t >= 0.0 and sp.reaches(sp.sums(lists[k])[-1], float(t))):
+            raise SystemExit("list %d, t = %.17g lies outside what Spline::GetSegmentID defines" % (k, t))
+    ids, tl = ref_run.segment_points(os.path.join(workdir, "segments"), lists, p["point_list"][sel], p["point_t"][sel])
+    assert ids.min() >= 0 and ids.max() < 256
+    cases = sp.duration_cases()
+    res = ref_run.segment_durations(os.path.join(workdir, "durations"), cases)
+    starts = lambda arrs: np.concatenate([[0], np.cumsum([len(a) for a in arrs])]).astype(np.int32)
+    out = dict(list_start=p["list_start"], durations=p["durations"], point_list=p["point_list"][sel].astype(np.uint8), point_t=p["point_t"][sel],
+               seg_id=ids.astype(np.uint8), t_local=tl,
+               case_head=np.array([c[:4] for c in cases], dtype=np.int32), case_given=np.concatenate([c[4] for c in cases]),
+               case_vars=np.concatenate([c[5] for c in cases]), case_ph=np.concatenate([r[0] for r in res]),
+               case_md=np.concatenate([r[1] for r in res]), case_md_start=starts([r[1] for r in res]),
+               case_fd=np.concatenate([r[2] for r in res]), case_fd_start=starts([r[2] for r in res]), reference_deps=ref_run.deps())
+    assert len(p["list_start"]) - 1 < 256
+    return out
+
+
+def record_segments(workdir):
+    out = compute_segments(workdir)
+    path = os.path.join(GOLDEN, "refsegment.npz")
+    save_npz_lzma(path, out)
+    return path, os.path.getsize(path), len(out["point_t"]), len(out["case_head"])
+
+
 def main(names):
     from oracle import ref_run
 
@@ -367,6 +460,11 @@ def main(names):
                 total += size
                 print("%-40s points=%6d force=%4d %8d bytes" % (os.path.basename(path), n, k, size))
         print("total %d bytes" % total)
+        return
+    if names and names[0] == "--segments":
+        with tempfile.TemporaryDirectory() as work:
+            path, size, n, k = record_segments(work)
+        print("%-40s points=%6d duration cases=%3d %8d bytes" % (os.path.basename(path), n, k, size))
         return
     if names and names[0] == "--traj":
         with tempfile.TemporaryDirectory() as work:

@@ -147,6 +147,50 @@ def terrain_points(prefix, terrain_ids, xy, with_basis, csv_heights=None, timeou
     return values, basis
 
 
+def _segment_run(prefix, doubles, timeout):
+    np.ascontiguousarray(doubles, dtype=np.float64).tofile(prefix + "_segments_in.bin")
+    cmd = [os.path.join(REF, "ref_dump"), "--segment-points", prefix + "_segments_in.bin", prefix + "_segments_out.bin"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    if r.returncode != 0:
+        raise RuntimeError("ref_dump exit %d: %s\n%s" % (r.returncode, " ".join(cmd), (r.stdout + r.stderr)[-2000:]))
+    return np.fromfile(prefix + "_segments_out.bin", dtype=np.float64)
+
+
+def segment_points(prefix, lists, point_list, point_t, timeout=600):
+    """ref_dump --segment-points, mode 0: Spline::GetSegmentID and GetLocalTime at the times point_t (n,) on the duration lists
+    lists[point_list[k]].  Returns (id (n,) int32, t_local (n,)); ref_dump refuses (exit code 5) a time for which the lookup
+    is not defined."""
+    parts = [[0.0, float(len(lists))]]
+    for d in lists:
+        parts += [[float(len(d))], np.asarray(d, dtype=np.float64)]
+    parts += [[float(len(point_t))], np.column_stack([np.asarray(point_list, dtype=np.float64), np.asarray(point_t, dtype=np.float64)]).ravel()]
+    out = _segment_run(prefix, np.concatenate([np.asarray(p, dtype=np.float64) for p in parts]), timeout).reshape(-1, 3)
+    assert len(out) == len(point_t) and np.array_equal(out[:, 0], out[:, 1]), "GetLocalTime's id is GetSegmentID's"
+    return out[:, 0].astype(np.int32), out[:, 2].copy()
+
+
+def segment_durations(prefix, cases, timeout=600):
+    """ref_dump --segment-points, mode 1: per case (n_phases, in contact at start, polynomials per swing phase, per stance phase
+    of the force, given durations, schedule variables) the reference's (phase durations after PhaseDurations::SetVariables,
+    ConvertPhaseToPolyDurations of the ee-motion nodes, of the ee-force nodes)."""
+    parts = [[1.0, float(len(cases))]]
+    for n, contact, pps, ppf, given, variables in cases:
+        assert len(given) == n and len(variables) == n - 1
+        parts += [[float(n), float(bool(contact)), float(pps), float(ppf)], given, variables]
+    out = _segment_run(prefix, np.concatenate([np.asarray(p, dtype=np.float64) for p in parts]), timeout)
+    res, at = [], 0
+    for n, *_ in cases:
+        ph = out[at:at + n]
+        nm = int(out[at + n])
+        md = out[at + n + 1:at + n + 1 + nm]
+        nf = int(out[at + n + 1 + nm])
+        fd = out[at + n + 2 + nm:at + n + 2 + nm + nf]
+        at += n + 2 + nm + nf
+        res.append((ph.copy(), md.copy(), fd.copy()))
+    assert at == out.size
+    return res
+
+
 def case_args(case):
     """(args, kwargs) of command() / run() for a tests.common.Case (every field a Case can set reaches the reference)."""
     p = case.params

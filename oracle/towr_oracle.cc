@@ -2184,6 +2184,34 @@ int orc_gait(int n_ee, int combo, double t_total, int* n_phases, int* contact_at
   }
 }
 
+int orc_locate(const double* durations, int n, const double* t, int n_t, int* id, double* t_local) {
+  const std::vector<double> d(durations, durations + n);
+  int missed = 0;
+  for (int k = 0; k < n_t; ++k) {
+    try {
+      const auto lt = NodeSpline::GetLocalTime(t[k], d);
+      id[k] = lt.first;
+      t_local[k] = lt.second;
+    } catch (const std::runtime_error&) {   // GetSegmentID: t beyond the spline
+      id[k] = -1;
+      t_local[k] = std::nan("");
+      ++missed;
+    }
+  }
+  return missed;
+}
+int orc_phase_poly_durations(int n, int contact_at_start, int pps, int ppf, const double* given, const double* vars, double* ph,
+                             double* md, double* fd) {
+  PhaseDurations pd(0, std::vector<double>(given, given + n), contact_at_start != 0, 0.0, 1e20);
+  pd.SetVariables(vars);
+  const NodesVars motion = MakeNodesEEMotion(n, contact_at_start != 0, "m", pps);
+  const NodesVars force = MakeNodesEEForce(n, contact_at_start != 0, "f", ppf);
+  const std::vector<double> m = motion.PhaseToPolyDurations(pd.durations), f = force.PhaseToPolyDurations(pd.durations);
+  std::copy(pd.durations.begin(), pd.durations.end(), ph);
+  std::copy(m.begin(), m.end(), md);
+  std::copy(f.begin(), f.end(), fd);
+  return (int)m.size() | ((int)f.size() << 16);
+}
 void orc_hermite_weights(double t, double T, double w[12]) {
   CubicHermite p;
   p.T = T;

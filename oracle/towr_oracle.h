@@ -116,6 +116,13 @@ void orc_euler_probe(const double nodes[12], double T, double t, double* out /* 
 
 // small probes used by known-answer tests
 void orc_hermite_weights(double t, double T, double w[12]);   // d{p,v,a}/d{p0,v0,p1,v1}
+// NodeSpline::GetLocalTime on n durations at each of n_t times: id[k], t_local[k]; returns the number of times for which no
+// segment is found (id -1, t_local NaN)
+int orc_locate(const double* durations, int n, const double* t, int n_t, int* id, double* t_local);
+// PhaseDurations::SetVariables on n - 1 variables of n given durations, then NodesVars::PhaseToPolyDurations of the ee-motion and the
+// ee-force nodes: ph[n], md / fd (room for n * max(pps, ppf) each); returns n_md | n_fd << 16
+int orc_phase_poly_durations(int n, int contact_at_start, int pps, int ppf, const double* given, const double* vars, double* ph,
+                             double* md, double* fd);
 double orc_terrain_height(int terrain, double x, double y);
 void orc_terrain_basis(int terrain, int which, double x, double y, double out[3]);
 void orc_terrain_dbasis(int terrain, int which, int dim, double x, double y, double out[3]);

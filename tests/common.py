@@ -194,6 +194,84 @@ class Case:
         x[idx] = tp.edge_footholds(self.terrain, len(idx), seed, heights=heights, grid_map=grid_map)
         return x
 
+    def x_junctions(self, seed, times=None):
+        """x_perturbed(seed) with the ee-schedule variables re-solved foot by foot, phase after phase, so that accumulated sums
+        of durations land on chosen doubles next to a time node: of the dynamic grid or of the range-of-motion grid in turn, or
+        of `times` when given.  With t the time node nearest to where the perturbed junction lies and fl(t - 1e-10) the sum
+        that just reaches it (t is then the threshold double of tests/segment_points.py), the kind cycles with phase, foot and
+        seed: 0 the end of the phase on fl(t - 1e-10); 1 on the double one ulp below or above it; 2 on t itself or a neighbour;
+        3 a polynomial junction INSIDE the phase on fl(t' - 1e-10) of its own nearest node t', through the ee-motion
+        accumulation where the phase has several ee-motion polynomials and through the ee-force accumulation otherwise (the
+        phase's end then stays where the solved duration puts it; the junction chosen is the one that moves the duration least,
+        and a phase whose duration would move by more than 40 ms, or with one polynomial in both lists, stays as perturbed).
+        The end of a phase is aimed through the phase, the ee-motion or the ee-force accumulation in turn: their sums differ by
+        rounding.  A duration d_j = (target - acc) * n / j is searched 16 ulp either way for fl(acc + d_j/n + ... ) == target;
+        a target that cannot be met, or would leave a duration below 20 ms (the last phase: below 5 ms), stays as perturbed."""
+        from tests import segment_points as sp
+        x = self.x_perturbed(seed)
+        perturbed = x.copy()
+        p = self.params
+        durs, contact = self.sched.durations(), self.sched.contact()
+        T = sp.sums(durs[0])[-1]
+        if times is not None:
+            grids = [np.sort(np.asarray(times, dtype=np.float64))]
+        else:
+            grids = [np.array(sp.time_nodes(T, p.dt_dynamic)), np.array(sp.time_nodes(T, p.dt_rom))]
+
+        def end_of(acc, d, n, j):
+            h = d / n
+            for _ in range(j):
+                acc += h
+            return acc
+
+        def solve(acc, n, j, target):
+            d0 = (target - acc) * n / j
+            for towards in (np.inf, -np.inf):
+                d = d0
+                for _ in range(17):
+                    if end_of(acc, d, n, j) == target:
+                        return d
+                    d = float(np.nextafter(d, towards))
+            return None
+
+        for vs in self.S.var_sets:
+            if not vs["name"].startswith("ee-schedule"):
+                continue
+            e = int(vs["name"][len("ee-schedule"):])
+            a = vs["offset"]
+            acc = {"phase": 0.0, "motion": 0.0, "force": 0.0}
+            for i in range(vs["size"]):
+                stance = bool(contact[e]) == (i % 2 == 0)
+                count = {"phase": 1, "motion": 1 if stance else p.polys_per_swing, "force": p.polys_per_stance_force if stance else 1}
+                d = float(x[a + i])
+                kind = (i + e + seed) % 4
+                grid = grids[(i + seed) % len(grids)]
+                nearest = lambda v: float(grid[np.argmin(np.abs(grid - v))])
+                new = None
+                if kind == 3:
+                    which = "motion" if count["motion"] > 1 else "force"
+                    n = count[which]
+                    # (moving junction j of n by delta moves the duration by delta * n / j: the j that moves it least)
+                    found = [solve(acc[which], n, j, nearest(end_of(acc[which], d, n, j)) - sp.EPS) for j in range(1, n)]
+                    found = [v for v in found if v is not None and abs(v - d) <= 0.04]
+                    if found:
+                        new = min(found, key=lambda v: abs(v - d))
+                else:
+                    which = ("phase", "motion", "force")[(i // 4 + e + seed) % 3]
+                    t = nearest(acc["phase"] + d)
+                    side = np.inf if (i // 4 + seed) % 2 else -np.inf
+                    target = (t - sp.EPS, float(np.nextafter(t - sp.EPS, side)), t if (i // 2 + seed) % 2 else float(np.nextafter(t, side)))[kind]
+                    new = solve(acc[which], count[which], count[which], target)
+                if new is not None and new >= 0.02 and (i < vs["size"] - 1 or T - (acc["phase"] + new) >= 0.005):
+                    d = new
+                x[a + i] = d
+                for name in acc:
+                    acc[name] = end_of(acc[name], d, count[name], count[name])
+            if T - acc["phase"] < 0.005:      # the moves added up to more than the last phase holds: this foot stays as perturbed
+                x[a:a + vs["size"]] = perturbed[a:a + vs["size"]]
+            assert T - sp.sums(x[a:a + vs["size"]])[-1] > 0.0, "the last phase keeps a positive duration"
+        return x
+
     def nudged(self, x, direction):
         """x with every base-ang variable moved one ulp up (direction > 0) or down: how far the reference's own output moves
         under it is the yardstick for points where the parity bar alone is below the conditioning of the problem"""

@@ -132,7 +132,7 @@ def accumulated_times_defined(T, dt):
 # ---------------------------------------------------------------------------------------------------------------- CPU tier
 def test_the_fixture_set_covers_what_it_is_there_for():
     """Asserted on the recorded reference data alone (no oracle, no device)."""
-    assert 5 <= len(FIXTURES) <= 6
+    assert 5 <= len(FIXTURES) <= 7
     sizes = [os.path.getsize(p) for p in FIXTURES]
     assert max(sizes) <= 1 << 20 and sum(sizes) <= 1500000, sizes
     for p in FIXTURES:   # the globs (and the budget test) of the other fixture families must not pick these up
