@@ -464,6 +464,62 @@ int twr_planes_world_xy(const twr_planes* planes, double* world_xy);
 int twr_batch_contact_planes(twr_batch* b, const twr_planes* planes, const double* d_plan, const int32_t* d_counts,
                              int32_t max_steps, int32_t* d_plane_index, void* hip_stream);
 
+/* Joint-space trajectories and reachability scores: the reference's Go1 leg inverse kinematics
+ * (towr/src/go1/go1leg_inverse_kinematics.cc:16-115, inverse_kinematics_go1.cc:8-47), which it runs on the RobotStateCartesian
+ * records of GetTrajectory (footstep_plan_server.cc:118-129), for every sample of every problem of a batch.
+ *
+ * twr_leg_kinematics describes one leg chain (HAA about x, HFE and KFE about y) and how the legs map onto the front-left one.
+ * twr_leg_kinematics_preset fills the reference's Go1 constants as the doubles its expressions yield; every other robot is
+ * TWR_ERR_UNSUPPORTED (the reference has no IK for them) -- a caller may fill the struct for their own robot.  Every call below
+ * validates the descriptor before any device is touched, twr_last_error naming the field: n_ee in 1..4, mirrors exactly +-1,
+ * bends 0/1, lengths finite and > 0, offsets finite, q_min <= q_max and neither NaN.
+ *
+ * Foot e in the base frame is R(q)^T (p_ee - p_base), R(q) = Eigen's toRotationMatrix of the normalised quaternion of the
+ * sample record (xpp_vis CartesianJointConverter's frame change); then foot * mirror[e] - base_to_hip goes through
+ * GetJointAngles + EnforceLimits restated operation for operation, the reference's quirks included: -atan2(y, -z) with its
+ * signed zeros, the clamp std::max(lo, std::min(hi, v)) that turns a NaN cosine into +1, limits that leave a NaN alone.
+ *
+ * Joint record of a sample, TWR_JOINT_REC(n_ee) doubles:  [ t | per leg: q_HAA q_HFE q_KFE flags over_reach ]
+ *   flags (an integer as a double): 1 the HFE cosine was clamped (!(-1 <= c && c <= 1), so a NaN counts), 2 the KFE cosine was,
+ *     4 / 8 / 16 the HAA / HFE / KFE limit was enforced, 32 an angle is NaN
+ *   over_reach: max(r - (thigh + shank), |thigh - shank| - r, 0) in metres, r the HFE-to-foot distance (NaN if r is): what the
+ *     clamp hides and twr_batch_joint_scores reports, which the angles alone no longer tell
+ * Scores of a problem, TWR_JOINT_SCORE_REC doubles:
+ *   [0] samples   [1] leg-samples with flag 1 or 2 (unreachable)   [2] leg-samples with a limit enforced
+ *   [3] max over_reach   [4] max over joints and samples s >= 1 of |q(s) - q(s-1)| / dt, raw, no unwrapping (0 with one sample)
+ *   [5] min distance of an angle to its nearer limit over leg-samples with no flag set (1e20 if there are none)
+ *   [6] leg-samples with flag 32   [7] index of the first sample with an unreachable leg, -1 if none
+ *   [3], [4], [5] are NaN if a contributing value is NaN (twr_batch_score's rule).  Maxima, minima and counts only, folded in a
+ *   fixed order without atomics: the same bits wherever the problem sits in a batch, on every call and stream.
+ *
+ * twr_batch_joints: the records of twr_batch_sample (same dt, hence the same sample counts; d_traj / traj_stride as given
+ *   there) -> joint records at d_joints + p * joint_stride.
+ * twr_batch_joint_scores: joint records -> scores at d_jscores + 8 p.
+ * twr_batch_eval_joint_scores: x -> scores, bit-identical to the three calls in a row, without a trajectory buffer.  It counts as
+ *   an evaluation of the batch (at most one in flight).
+ * All three are asynchronous and stream-ordered on hip_stream and consist of kernel launches only (twr_batch_joints builds the
+ * sample work list on its first call per dt / stride like twr_batch_sample: capture after one warm call).  TWR_ERR_INVALID before
+ * any device is touched: NULL arguments, pointers not 8-byte aligned, traj_stride < n_samples * (20 + 13 n_ee) or joint_stride <
+ * n_samples * TWR_JOINT_REC(n_ee) for some problem, kin->n_ee != the batch's, dt not finite or <= 0, a bad descriptor. */
+typedef struct twr_leg_kinematics {
+  int32_t n_ee;             /* 1..4, must equal the batch's n_ee */
+  int32_t knee_bend[4];     /* 0 forward, 1 backward */
+  double  mirror[4][3];     /* +-1: foot_B * mirror[e] maps leg e onto the front-left leg */
+  double  base_to_hip[3];   /* of the front-left leg, subtracted after mirroring */
+  double  hfe_to_haa[3];    /* added after the HAA rotation */
+  double  length_thigh, length_shank;
+  double  q_min[3], q_max[3];  /* HAA, HFE, KFE, radians */
+} twr_leg_kinematics;
+#define TWR_JOINT_REC(n_ee)  (1 + 5 * (n_ee))
+#define TWR_JOINT_SCORE_REC  8
+int twr_leg_kinematics_preset(int robot, twr_leg_kinematics* out);
+int twr_batch_joints(twr_batch* b, const twr_leg_kinematics* kin, const double* d_traj, int64_t traj_stride, double dt,
+                     double* d_joints, int64_t joint_stride, void* hip_stream);
+int twr_batch_joint_scores(twr_batch* b, const twr_leg_kinematics* kin, const double* d_joints, int64_t joint_stride,
+                           double dt, double* d_jscores /* 8 * n_problems */, void* hip_stream);
+int twr_batch_eval_joint_scores(twr_batch* b, const twr_leg_kinematics* kin, const double* d_x, double dt,
+                                double* d_jscores /* 8 * n_problems */, void* hip_stream);
+
 /* Convenience for single-problem / adapter use: host buffers, synchronous (H2D, eval, D2H).  Runs on a NON-BLOCKING
  * stream the batch owns (created on first use), not on the NULL stream: it neither waits for nor holds up work the host
  * application has in flight on the NULL stream or on its own blocking streams; the call returns when its own chain is

@@ -65,6 +65,22 @@ class LaunchStep(C.Structure):
                 ("xc", C.c_int32), ("grid", C.c_int32), ("block", C.c_int32), ("lds_bytes", C.c_int32), ("uniform_kinds", C.c_int32)]
 
 
+class LegKinematics(C.Structure):
+    """twr_leg_kinematics: one leg chain and how the legs map onto the front-left one (leg_kinematics_preset)."""
+    _fields_ = [("n_ee", C.c_int32), ("knee_bend", C.c_int32 * 4), ("mirror", (C.c_double * 3) * 4), ("base_to_hip", C.c_double * 3),
+                ("hfe_to_haa", C.c_double * 3), ("length_thigh", C.c_double), ("length_shank", C.c_double),
+                ("q_min", C.c_double * 3), ("q_max", C.c_double * 3)]
+
+
+JOINT_SCORE_REC = 8   # TWR_JOINT_SCORE_REC
+IK_FLAGS = dict(beta_clamped=1, gamma_clamped=2, haa_limit=4, hfe_limit=8, kfe_limit=16, nan=32)
+
+
+def joint_rec(n_ee):
+    """TWR_JOINT_REC(n_ee): doubles per joint record, [t | per leg: q_HAA q_HFE q_KFE flags over_reach]"""
+    return 1 + 5 * n_ee
+
+
 class JacLmParams(C.Structure):
     """twr_jac_lm_params"""
     _fields_ = [("cg_iters", C.c_int32), ("power_iters", C.c_int32), ("cg_tol", C.c_double), ("mu_down", C.c_double),
@@ -226,6 +242,12 @@ def lib():
         L.twr_jac_lsq_solve_gram.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double,
                                              C.c_void_p, C.c_void_p, C.c_void_p]
         L.twr_jac_lm_set_solver.argtypes = [C.c_void_p, C.c_int]
+        L.twr_leg_kinematics_preset.argtypes = [C.c_int, C.POINTER(LegKinematics)]
+        L.twr_batch_joints.argtypes = [C.c_void_p, C.POINTER(LegKinematics), C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64,
+                                       C.c_void_p]
+        L.twr_batch_joint_scores.argtypes = [C.c_void_p, C.POINTER(LegKinematics), C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
+                                             C.c_void_p]
+        L.twr_batch_eval_joint_scores.argtypes = [C.c_void_p, C.POINTER(LegKinematics), C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -250,6 +272,14 @@ def model_preset(robot, terrain):
     t = TERRAINS[terrain] if isinstance(terrain, str) else terrain
     _check(lib().twr_model_preset(r, t, C.byref(m)))
     return m
+
+
+def leg_kinematics_preset(robot):
+    """twr_leg_kinematics_preset: the reference's Go1 leg inverse-kinematics constants (any other robot raises: the reference
+    has no IK for them; fill a LegKinematics yourself)."""
+    k = LegKinematics()
+    _check(lib().twr_leg_kinematics_preset(ROBOTS[robot] if isinstance(robot, str) else robot, C.byref(k)))
+    return k
 
 
 def params_default(**kw):
@@ -671,6 +701,24 @@ class Batch:
         contact_plan_device(); d_plane_index int32[n_problems, max_steps, n_ee], -1 = in the air / no such state."""
         _check(lib().twr_batch_contact_planes(self._h, planes._h, C.c_void_p(d_plan), C.c_void_p(d_counts), int(max_steps),
                                               C.c_void_p(d_plane_index), C.c_void_p(stream)))
+
+    def joints_device(self, kin, d_traj, traj_stride, dt, d_joints, joint_stride, stream=0):
+        """twr_batch_joints: the records of sample_device (same dt and stride) -> joint records
+        d_joints[p * joint_stride + sample * joint_rec(n_ee) + field] (device pointers)."""
+        _check(lib().twr_batch_joints(self._h, C.byref(kin), C.c_void_p(d_traj), int(traj_stride), float(dt), C.c_void_p(d_joints),
+                                      int(joint_stride), C.c_void_p(stream)))
+
+    def joint_scores_device(self, kin, d_joints, joint_stride, dt, d_jscores, stream=0):
+        """twr_batch_joint_scores: joint records -> d_jscores[JOINT_SCORE_REC * p + slot]: samples, unreachable leg-samples,
+        limit-enforced leg-samples, max over-reach [m], max |dq| / dt, min margin to a limit, NaN leg-samples, first
+        unreachable sample (-1: none)."""
+        _check(lib().twr_batch_joint_scores(self._h, C.byref(kin), C.c_void_p(d_joints), int(joint_stride), float(dt),
+                                            C.c_void_p(d_jscores), C.c_void_p(stream)))
+
+    def eval_joint_scores_device(self, kin, d_x, dt, d_jscores, stream=0):
+        """twr_batch_eval_joint_scores: the scores of joint_scores_device straight from x, bit for bit, without a trajectory."""
+        _check(lib().twr_batch_eval_joint_scores(self._h, C.byref(kin), C.c_void_p(d_x), float(dt), C.c_void_p(d_jscores),
+                                                 C.c_void_p(stream)))
 
     def host_buffers(self):
         """Page-locked x / g / jac arrays owned by the batch (numpy views); eval_host_pinned() uses them."""

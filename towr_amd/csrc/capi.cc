@@ -33,6 +33,18 @@ void build_sample_work(twr_batch& b, DevList<twr::SampleWork>& list, int64_t str
   list = upload(work);
 }
 
+// the work list of twr_batch_sample for (dt, stride), (re)built where the last call's was another (twr_batch_joints walks it too)
+void sample_work_for(twr_batch& b, double dt, int64_t problem_stride) {
+  if (b.swork.d && b.swork_dt == dt && b.swork_stride == problem_stride) return;
+  build_sample_work(b, b.swork, problem_stride, [&](int p) {
+    const int n = twr::SampleCount(b.plan.t_total[p], dt);
+    if ((int64_t)n * (20 + 13 * b.n_ee) > problem_stride) throw std::runtime_error("problem_stride too small for the samples");
+    return n;
+  });
+  b.swork_dt = dt;
+  b.swork_stride = problem_stride;
+}
+
 void check_params(const twr_params& p) {   // throws: what twr_structure_create rejects before it builds anything
   if (p.polys_per_swing < 1 || p.polys_per_stance_force < 1) throw std::runtime_error("polynomials per phase must be >= 1");
   if (p.constraint_sets <= 0 || (p.constraint_sets & ~TWR_SETS_EVERY))
@@ -801,15 +813,7 @@ int twr_batch_sample(twr_batch* b, const double* d_x, double dt, double* d_out, 
   try {
     DeviceScope on(b->device);
     TWR_HIP(on.status);
-    if (!b->swork.d || b->swork_dt != dt || b->swork_stride != problem_stride) {  // (re)build the work list
-      build_sample_work(*b, b->swork, problem_stride, [&](int p) {
-        const int n = twr::SampleCount(b->plan.t_total[p], dt);
-        if ((int64_t)n * (20 + 13 * b->n_ee) > problem_stride) throw std::runtime_error("problem_stride too small for the samples");
-        return n;
-      });
-      b->swork_dt = dt;
-      b->swork_stride = problem_stride;
-    }
+    sample_work_for(*b, dt, problem_stride);
     hipError_t e = twr::launch_sample(b->swork.d.get(), b->swork.n, d_x, d_out, dt, nullptr, static_cast<hipStream_t>(hip_stream));
     return launched(e);
   } catch (const std::exception& e) {
@@ -1012,6 +1016,89 @@ int twr_batch_contact_plan(twr_batch* b, const double* d_x, double dt, double ti
   } catch (const std::exception& e) {
     return fail(TWR_ERR_HIP, e.what());
   }
+}
+
+int twr_leg_kinematics_preset(int robot, twr_leg_kinematics* out) {
+  if (!out) return fail(TWR_ERR_INVALID, "null output");
+  if (robot < TWR_ROBOT_MONOPED || robot > TWR_ROBOT_GO1) return fail(TWR_ERR_INVALID, "unknown robot id");
+  if (!twr::LegKinematicsPreset(robot, out)) return fail(TWR_ERR_UNSUPPORTED, "the reference has inverse kinematics for Go1 only");
+  return TWR_OK;
+}
+
+namespace {
+// What the three joint calls check before any device is touched; *n_max: the largest sample count of a problem.  Strides are
+// checked against every problem's own count (a stride of -1: that buffer is not part of the call).
+int check_joint_call(const twr_batch* b, const twr_leg_kinematics* kin, std::initializer_list<const void*> buffers, double dt,
+                     int64_t traj_stride, int64_t joint_stride, int* n_max) {
+  if (!kin) return fail(TWR_ERR_INVALID, "null kin");
+  try {   // (the descriptor first: it can be judged without a batch)
+    twr::CheckLegKinematics(*kin);
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+  if (!b) return fail(TWR_ERR_INVALID, "null batch");
+  for (const void* p : buffers)
+    if (!p) return fail(TWR_ERR_INVALID, "null device buffer");
+  if (misaligned(buffers)) return fail(TWR_ERR_INVALID, "device buffers must be 8-byte aligned");
+  if (!std::isfinite(dt) || !(dt > 0)) return fail(TWR_ERR_INVALID, "dt must be finite and > 0");
+  try {
+    if (kin->n_ee != b->n_ee) throw std::runtime_error("twr_leg_kinematics: n_ee differs from the batch's");
+    *n_max = 0;
+    for (int p = 0; p < b->n_problems; ++p) {
+      if (!b->plan.sample_ok[p]) throw std::runtime_error("too many polynomials per spline for trajectory sampling");
+      const int n = twr::SampleCount(b->plan.t_total[p], dt);
+      if (traj_stride >= 0 && (int64_t)n * (20 + 13 * b->n_ee) > traj_stride) throw std::runtime_error("traj_stride too small for the samples");
+      if (joint_stride >= 0 && (int64_t)n * TWR_JOINT_REC(b->n_ee) > joint_stride) throw std::runtime_error("joint_stride too small for the samples");
+      *n_max = std::max(*n_max, n);
+    }
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+  return TWR_OK;
+}
+}  // namespace
+
+int twr_batch_joints(twr_batch* b, const twr_leg_kinematics* kin, const double* d_traj, int64_t traj_stride, double dt, double* d_joints,
+                     int64_t joint_stride, void* hip_stream) {
+  int n_max = 0;
+  if (traj_stride < 0 || joint_stride < 0) return fail(TWR_ERR_INVALID, "negative stride");
+  const int rc = check_joint_call(b, kin, {d_traj, d_joints}, dt, traj_stride, joint_stride, &n_max);
+  if (rc != TWR_OK) return rc;
+  try {
+    DeviceScope on(b->device);
+    TWR_HIP(on.status);
+    sample_work_for(*b, dt, traj_stride);
+    hipError_t e = twr::launch_joints(b->swork.d.get(), b->swork.n, d_traj, traj_stride, d_joints, joint_stride, b->n_ee, *kin,
+                                      static_cast<hipStream_t>(hip_stream));
+    return launched(e);
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+int twr_batch_joint_scores(twr_batch* b, const twr_leg_kinematics* kin, const double* d_joints, int64_t joint_stride, double dt,
+                           double* d_jscores, void* hip_stream) {
+  int n_max = 0;
+  if (joint_stride < 0) return fail(TWR_ERR_INVALID, "negative stride");
+  const int rc = check_joint_call(b, kin, {d_joints, d_jscores}, dt, -1, joint_stride, &n_max);
+  if (rc != TWR_OK) return rc;
+  DeviceScope on(b->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipError_t e = twr::launch_joint_scores(b->node.d.get(), b->n_problems, d_joints, joint_stride, dt, n_max, d_jscores, *kin,
+                                          static_cast<hipStream_t>(hip_stream));
+  return launched(e);
+}
+
+int twr_batch_eval_joint_scores(twr_batch* b, const twr_leg_kinematics* kin, const double* d_x, double dt, double* d_jscores,
+                                void* hip_stream) {
+  int n_max = 0;
+  const int rc = check_joint_call(b, kin, {d_x, d_jscores}, dt, -1, -1, &n_max);
+  if (rc != TWR_OK) return rc;
+  DeviceScope on(b->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipError_t e = twr::launch_eval_joint_scores(b->node.d.get(), b->n_problems, d_x, dt, n_max, d_jscores, *kin,
+                                               static_cast<hipStream_t>(hip_stream));
+  return launched(e);
 }
 
 int twr_batch_host_buffers(twr_batch* b, double** h_x, double** h_g, double** h_jac) {

@@ -48,6 +48,14 @@ hipError_t launch_planes(const double* plan, const int32_t* counts, const double
                          int n_problems, int max_steps, int n_ee, int32_t* plane_index, hipStream_t stream);
 hipError_t launch_sample(const SampleWork* work, int n_work, const double* x, double* out, double dt, const double* times,
                          hipStream_t stream);
+// Joint-space trajectories (kernels/joints.h): sample records -> joint records over sample_kernel's work list; joint records
+// -> eight scores per problem; x -> the same scores without a trajectory.  n_samples_max: the largest sample count of a problem.
+hipError_t launch_joints(const SampleWork* work, int n_work, const double* traj, int64_t traj_stride, double* out, int64_t joint_stride,
+                         int n_ee, const twr_leg_kinematics& kin, hipStream_t stream);
+hipError_t launch_joint_scores(const NodeWork* work, int n_problems, const double* joints, int64_t joint_stride, double dt,
+                               int n_samples_max, double* scores, const twr_leg_kinematics& kin, hipStream_t stream);
+hipError_t launch_eval_joint_scores(const NodeWork* work, int n_problems, const double* x, double dt, int n_samples_max, double* scores,
+                                    const twr_leg_kinematics& kin, hipStream_t stream);
 // dst (a batch's copy of a `Grid` layer, start index (0,0)) from src (the same sizes, start index (start_x, start_y)), and the map
 // centre into the n_hdr headers whose DevStruct::grid_px lies hdr_off[k] bytes into arena (kernels/grid_map_update.h).  One launch.
 hipError_t launch_grid_map_update(const float* src, float* dst, int size_x, int size_y, int start_x, int start_y, double pos_x,

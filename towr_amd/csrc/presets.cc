@@ -1,8 +1,10 @@
 // Robot and terrain presets and the gait generator: the reference's RobotModel and GaitGenerator as tables.
 // Citations are file:line of the reference's towr/ tree, as in structure.cc.
+#include <cmath>
 #include <cstring>
 #include <numeric>
 #include <stdexcept>
+#include <string>
 #include <vector>
 
 #include "structure.h"
@@ -56,6 +58,46 @@ void ModelPreset(int robot, int terrain, twr_model* m) {
   m->friction = 0.5;        // height_map.h:136
   m->force_limit = 1000.0;  // parameters.cc:48
   m->flat_height = 0.0;
+}
+
+// Go1legInverseKinematics / InverseKinematicsGo1 (include/towr/models/go1/go1leg_inverse_kinematics.h:47-49,
+// inverse_kinematics_go1.h:34, src/go1/go1leg_inverse_kinematics.cc:86-108, src/go1/inverse_kinematics_go1.cc:23-37): every
+// constant as the double the reference's expression yields.  Returns false for a robot the reference has no IK for.
+bool LegKinematicsPreset(int robot, twr_leg_kinematics* k) {
+  if (robot != TWR_ROBOT_GO1) return false;
+  std::memset(k, 0, sizeof(*k));
+  const double pi = 3.14159265358979323846;   // M_PI
+  k->n_ee = 4;
+  const double mirror[4][3] = {{1, 1, 1}, {1, -1, 1}, {-1, 1, 1}, {-1, -1, 1}};   // LF RF LH RH
+  std::memcpy(k->mirror, mirror, sizeof(mirror));
+  k->knee_bend[2] = k->knee_bend[3] = 1;   // hind legs: Backward
+  k->base_to_hip[0] = 0.1881;
+  k->base_to_hip[1] = 0.04675 + 0.08;
+  k->length_thigh = k->length_shank = 0.213;
+  const double lo[3] = {-180, -90, -180}, hi[3] = {90, 90, 0};
+  for (int j = 0; j < 3; ++j) {
+    k->q_min[j] = lo[j] / 180.0 * pi;
+    k->q_max[j] = hi[j] / 180.0 * pi;
+  }
+  return true;
+}
+// What every joint call requires of a descriptor; throws naming the field.
+void CheckLegKinematics(const twr_leg_kinematics& k) {
+  auto bad = [](const std::string& what) { throw std::runtime_error("twr_leg_kinematics: " + what); };
+  if (k.n_ee < 1 || k.n_ee > 4) bad("n_ee must be 1..4");
+  for (int e = 0; e < k.n_ee; ++e) {
+    if (k.knee_bend[e] != 0 && k.knee_bend[e] != 1) bad("knee_bend must be 0 or 1");
+    for (int d = 0; d < 3; ++d)
+      if (k.mirror[e][d] != 1.0 && k.mirror[e][d] != -1.0) bad("mirror must be +1 or -1");
+  }
+  for (int d = 0; d < 3; ++d) {
+    if (!std::isfinite(k.base_to_hip[d])) bad("base_to_hip must be finite");
+    if (!std::isfinite(k.hfe_to_haa[d])) bad("hfe_to_haa must be finite");
+  }
+  if (!std::isfinite(k.length_thigh) || !(k.length_thigh > 0)) bad("length_thigh must be finite and > 0");
+  if (!std::isfinite(k.length_shank) || !(k.length_shank > 0)) bad("length_shank must be finite and > 0");
+  for (int j = 0; j < 3; ++j)
+    if (!(k.q_min[j] <= k.q_max[j])) bad("q_min <= q_max is required, neither NaN");
 }
 
 // ------------------------------------------------------------------ gait generator

@@ -135,6 +135,8 @@ struct Structure {
 int SampleCount(double t_total, double dt);
 void GaitCombo(int n_ee, int combo, double t_total, double swing_scale, twr_schedule* out);
 void ModelPreset(int robot, int terrain, twr_model* out);
+bool LegKinematicsPreset(int robot, twr_leg_kinematics* out);   // false: the reference has no IK for this robot
+void CheckLegKinematics(const twr_leg_kinematics& k);          // throws naming the field
 double TerrainHeightHost(const twr_model& m, const TerrainGrid* grid, double x, double y);
 
 }  // namespace twr

@@ -1,5 +1,5 @@
 // Third translation unit of the kernels, plain flags: the utility kernels -- trajectory sampling, scoring from g, the planner's arg-min,
-// contact plan, nearest plane, TWR_EVAL_CHECK, the grid_map layer update -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
+// contact plan, nearest plane, joint-space trajectories and their scores, TWR_EVAL_CHECK, the grid_map layer update -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -12,6 +12,7 @@
 #include "kernels/spline_math.h"
 #include "kernels/phase_durations.h"
 #include "kernels/grid_map_update.h"
+#include "kernels/joints.h"
 
 namespace twr {
 
@@ -33,6 +34,53 @@ TWR_DEV void sample_spline(const double* __restrict__ xp, const PolyDesc& pd, do
     a[d] = wa[0] * nv[0][d] + wa[1] * nv[1][d] + wa[2] * nv[2][d] + wa[3] * nv[3][d];
   }
 }
+// The base of a sample at time t, shared by sample_kernel and eval_joint_scores_kernel (which must form the very same doubles:
+// the compiler's choice of fused operations depends on what else uses a product, so that kernel keeps every result alive).
+struct BaseSample {
+  double p[3], v[3], a[3];       // base-lin
+  double e3[3], ed[3], edd[3];   // base-ang: Euler angles, rates, accelerations
+};
+struct BaseAngular {
+  double q[4];                   // x y z w
+  double omega[3], omega_dot[3];
+};
+// base-lin / base-ang (NodesVariablesAll: [p0 v0 p1 v1] x 3 of polynomial q at 6 q)
+TWR_DEV void sample_base(const double* __restrict__ xp, const SampleTables* ST, const double* s_bd, double t, BaseSample& B) {
+  double tl;
+  const int qb = locate_segment(s_bd, ST->n_base, t, tl);
+  double wp[4], wv[4], wa[4];
+  hermite_all(tl, 1.0 / s_bd[qb], wp, wv, wa);
+  const double* xl = xp + ST->off_lin + 6 * qb;
+  const double* xa = xp + ST->off_ang + 6 * qb;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    B.p[d] = wp[0] * xl[d] + wp[1] * xl[3 + d] + wp[2] * xl[6 + d] + wp[3] * xl[9 + d];
+    B.v[d] = wv[0] * xl[d] + wv[1] * xl[3 + d] + wv[2] * xl[6 + d] + wv[3] * xl[9 + d];
+    B.a[d] = wa[0] * xl[d] + wa[1] * xl[3 + d] + wa[2] * xl[6 + d] + wa[3] * xl[9 + d];
+    B.e3[d] = wp[0] * xa[d] + wp[1] * xa[3 + d] + wp[2] * xa[6 + d] + wp[3] * xa[9 + d];
+    B.ed[d] = wv[0] * xa[d] + wv[1] * xa[3 + d] + wv[2] * xa[6 + d] + wv[3] * xa[9 + d];
+    B.edd[d] = wa[0] * xa[d] + wa[1] * xa[3 + d] + wa[2] * xa[6 + d] + wa[3] * xa[9 + d];
+  }
+}
+TWR_DEV void sample_angular(const BaseSample& B, BaseAngular& A) {
+  Rot ro;
+  rotation(B.e3, ro);
+  quat_of_rotation(ro.R, A.q);
+  {  // omega = M edot, omega_dot = Mdot edot + M eddot (euler_converter.cc:58-83,133-166)
+    const double sy = ro.sy, cy = ro.cy, sz = ro.sz, cz = ro.cz;
+    const double xd = B.ed[0], yd = B.ed[1], zd = B.ed[2];
+    const double Mx[3] = {cy * cz, cy * sz, -sy}, My[3] = {-sz, cz, 0.0};
+    const double Mdx[3] = {-cz * sy * yd - cy * sz * zd, cy * cz * zd - sy * sz * yd, -cy * yd};
+    const double Mdy[3] = {-cz * zd, -sz * zd, 0.0};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      A.omega[i] = Mx[i] * xd + My[i] * yd + (i == 2 ? zd : 0.0);
+      A.omega_dot[i] = Mdx[i] * xd + Mdy[i] * yd + Mx[i] * B.edd[0] + My[i] * B.edd[1] + (i == 2 ? B.edd[2] : 0.0);
+    }
+  }
+}
+// keeps a value computed where nothing stores it
+TWR_DEV void keep_alive(double v) { asm volatile("" ::"v"(v)); }
 // With `times` set the kernel is fpowr::ExtractInitialGuess (fpowr/include/fpowr/initial_guess_extractor.h:17-34)
 // instead: sample s of every problem is taken at times[s] and the record is [ t | state: base-lin p, base-ang p (Euler
 // angles), base-lin v, base-ang v (Euler rates) | controls (36): ee-motion acceleration of ee i at 3 i, twelve zeros
@@ -69,22 +117,14 @@ __global__ __launch_bounds__(64) void sample_kernel(const SampleWork* __restrict
   const int rec = times ? 49 : 20 + 13 * n_ee;
   double* o = out + sw.out_off + (int64_t)s_idx * rec;
   o[0] = t;
-  // base-lin / base-ang (NodesVariablesAll: [p0 v0 p1 v1] x 3 of polynomial q at 6 q)
-  double tl;
-  const int qb = locate_segment(s_bd, ST->n_base, t, tl);
-  double wp[4], wv[4], wa[4];
-  hermite_all(tl, 1.0 / s_bd[qb], wp, wv, wa);
-  const double* xl = xp + ST->off_lin + 6 * qb;
-  const double* xa = xp + ST->off_ang + 6 * qb;
-  double e3[3], ed[3], edd[3];
+  BaseSample B;
+  sample_base(xp, ST, s_bd, t, B);
+  const double (&e3)[3] = B.e3, (&ed)[3] = B.ed;
 #pragma unroll
   for (int d = 0; d < 3; ++d) {
-    o[1 + d] = wp[0] * xl[d] + wp[1] * xl[3 + d] + wp[2] * xl[6 + d] + wp[3] * xl[9 + d];
-    o[4 + d] = wv[0] * xl[d] + wv[1] * xl[3 + d] + wv[2] * xl[6 + d] + wv[3] * xl[9 + d];
-    o[7 + d] = wa[0] * xl[d] + wa[1] * xl[3 + d] + wa[2] * xl[6 + d] + wa[3] * xl[9 + d];
-    e3[d] = wp[0] * xa[d] + wp[1] * xa[3 + d] + wp[2] * xa[6 + d] + wp[3] * xa[9 + d];
-    ed[d] = wv[0] * xa[d] + wv[1] * xa[3 + d] + wv[2] * xa[6 + d] + wv[3] * xa[9 + d];
-    edd[d] = wa[0] * xa[d] + wa[1] * xa[3 + d] + wa[2] * xa[6 + d] + wa[3] * xa[9 + d];
+    o[1 + d] = B.p[d];
+    o[4 + d] = B.v[d];
+    o[7 + d] = B.a[d];
   }
   if (times) {   // ExtractInitialGuess record
 #pragma unroll
@@ -108,48 +148,13 @@ __global__ __launch_bounds__(64) void sample_kernel(const SampleWork* __restrict
     }
     return;
   }
-  Rot ro;
-  rotation(e3, ro);
-  {  // Eigen::Quaterniond(R) (euler_converter.cc:51-56; Eigen 3.3 Quaternion.h, quaternionbase_assign_impl)
-    const double (&m)[3][3] = ro.R;
-    double q[4];  // x y z w
-    double tr = m[0][0] + m[1][1] + m[2][2];
-    if (tr > 0) {
-      tr = sqrt(tr + 1.0);
-      q[3] = 0.5 * tr;
-      tr = 0.5 / tr;
-      q[0] = (m[2][1] - m[1][2]) * tr;
-      q[1] = (m[0][2] - m[2][0]) * tr;
-      q[2] = (m[1][0] - m[0][1]) * tr;
-    } else {
-      int i = 0;
-      if (m[1][1] > m[0][0]) i = 1;
-      if (m[2][2] > (i == 0 ? m[0][0] : m[1][1])) i = 2;
-      const int j = (i + 1) % 3, k = (j + 1) % 3;
-      auto M = [&](int r, int c) { return sel3(r, sel3(c, m[0][0], m[0][1], m[0][2]), sel3(c, m[1][0], m[1][1], m[1][2]),
-                                               sel3(c, m[2][0], m[2][1], m[2][2])); };
-      tr = sqrt(M(i, i) - M(j, j) - M(k, k) + 1.0);
-      const double qi = 0.5 * tr;
-      tr = 0.5 / tr;
-      const double qw = (M(k, j) - M(j, k)) * tr, qj = (M(j, i) + M(i, j)) * tr, qk = (M(k, i) + M(i, k)) * tr;
-      q[3] = qw;
-      q[0] = i == 0 ? qi : (j == 0 ? qj : qk);
-      q[1] = i == 1 ? qi : (j == 1 ? qj : qk);
-      q[2] = i == 2 ? qi : (j == 2 ? qj : qk);
-    }
-    o[10] = q[3]; o[11] = q[0]; o[12] = q[1]; o[13] = q[2];
-  }
-  {  // omega = M edot, omega_dot = Mdot edot + M eddot (euler_converter.cc:58-83,133-166)
-    const double sy = ro.sy, cy = ro.cy, sz = ro.sz, cz = ro.cz;
-    const double xd = ed[0], yd = ed[1], zd = ed[2];
-    const double Mx[3] = {cy * cz, cy * sz, -sy}, My[3] = {-sz, cz, 0.0};
-    const double Mdx[3] = {-cz * sy * yd - cy * sz * zd, cy * cz * zd - sy * sz * yd, -cy * yd};
-    const double Mdy[3] = {-cz * zd, -sz * zd, 0.0};
+  BaseAngular A;
+  sample_angular(B, A);
+  o[10] = A.q[3]; o[11] = A.q[0]; o[12] = A.q[1]; o[13] = A.q[2];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      o[14 + i] = Mx[i] * xd + My[i] * yd + (i == 2 ? zd : 0.0);
-      o[17 + i] = Mdx[i] * xd + Mdy[i] * yd + Mx[i] * edd[0] + My[i] * edd[1] + (i == 2 ? edd[2] : 0.0);
-    }
+  for (int i = 0; i < 3; ++i) {
+    o[14 + i] = A.omega[i];
+    o[17 + i] = A.omega_dot[i];
   }
   for (int e = 0; e < n_ee; ++e) {
     double* oe = o + 20 + 13 * e;
@@ -522,6 +527,156 @@ hipError_t launch_planes(const double* plan, const int32_t* counts, const double
   if (n <= 0) return hipSuccess;
   return twr_launch(plane_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, plan, counts, poly_xy, poly_start, n_polys,
                     n_problems, max_steps, n_ee, plane_index);
+}
+
+// ---------------------------------------------------------------- joint-space trajectories (kernels/joints.h)
+// twr_batch_joints: records of sample_kernel -> joint records, lane = sample over the same work list (the problem is the
+// item's record offset over the trajectory stride).  Only the records are read: no table, no x.
+__global__ __launch_bounds__(64) void joints_kernel(const SampleWork* __restrict__ work, const double* __restrict__ traj,
+                                                    int64_t traj_stride, double* __restrict__ out, int64_t joint_stride, int n_ee,
+                                                    twr_leg_kinematics K) {
+  const SampleWork sw = work[blockIdx.x];
+  const int lane = threadIdx.x;
+  if (lane >= sw.cnt) return;
+  const int s_idx = sw.s0 + lane;
+  const int64_t p = sw.out_off / traj_stride;
+  const double* r = traj + sw.out_off + (int64_t)s_idx * (20 + 13 * n_ee);
+  double* o = out + p * joint_stride + (int64_t)s_idx * TWR_JOINT_REC(n_ee);
+  o[0] = r[0];
+  double R[3][3];
+  base_frame_rotation(r[10], r[11], r[12], r[13], R);
+  const double pb[3] = {r[1], r[2], r[3]};
+  for (int e = 0; e < n_ee; ++e) {
+    const double pe[3] = {r[21 + 13 * e], r[22 + 13 * e], r[23 + 13 * e]};
+    double foot[3];
+    base_frame(R, pb, pe, foot);
+    LegIk k;
+    leg_ik_of_foot(foot, e, K, k);
+    put_leg(o + 1 + kJointLeg * e, k, K);
+  }
+}
+hipError_t launch_joints(const SampleWork* work, int n_work, const double* traj, int64_t traj_stride, double* out, int64_t joint_stride,
+                         int n_ee, const twr_leg_kinematics& kin, hipStream_t stream) {
+  if (n_work <= 0) return hipSuccess;
+  return twr_launch(joints_kernel, dim3(n_work), dim3(64), 0, stream, work, traj, traj_stride, out, joint_stride, n_ee, kin);
+}
+
+// twr_batch_joint_scores: one wave per problem folds its joint records, 64 samples per round (JointFold).  The sample count is
+// GetTrajectory's: while (t <= T + 1e-5) with t accumulated.
+__global__ __launch_bounds__(64) void joint_scores_kernel(const NodeWork* __restrict__ work, const double* __restrict__ joints,
+                                                          int64_t joint_stride, double dt, int n_samples_max,
+                                                          double* __restrict__ scores, twr_leg_kinematics K) {
+  const char* blob = reinterpret_cast<const char*>(work[blockIdx.x].blob);
+  const DevStruct* H = reinterpret_cast<const DevStruct*>(blob);
+  const double T = tbl<SampleTables>(blob, H->o_sample)->t_total;
+  const int lane = threadIdx.x, n_ee = H->n_ee, rec = TWR_JOINT_REC(n_ee);
+  const double* jp = joints + (int64_t)blockIdx.x * joint_stride;
+  JointFold F;
+  F.init();
+  for (int s0 = 0; s0 < n_samples_max; s0 += 64) {
+    const int s_idx = s0 + lane;
+    double t = 0.0;
+    for (int i = 0; i < s_idx; ++i) t += dt;
+    const bool live = t <= T + 1e-5;
+    if (!__any(live)) break;
+    double q[kMaxEE][3] = {};
+    double ov[kMaxEE] = {};
+    int fl[kMaxEE] = {};
+#pragma unroll
+    for (int e = 0; e < kMaxEE; ++e)
+      if (live && e < n_ee) {
+        const double* l = jp + (int64_t)s_idx * rec + 1 + kJointLeg * e;
+        q[e][0] = l[0]; q[e][1] = l[1]; q[e][2] = l[2];
+        fl[e] = (int)l[3];
+        ov[e] = l[4];
+      }
+    F.round(lane, s_idx, live, n_ee, q, fl, ov, dt, K);
+  }
+  F.finish(lane, scores + TWR_JOINT_SCORE_REC * (size_t)blockIdx.x);
+}
+hipError_t launch_joint_scores(const NodeWork* work, int n_problems, const double* joints, int64_t joint_stride, double dt,
+                               int n_samples_max, double* scores, const twr_leg_kinematics& kin, hipStream_t stream) {
+  return twr_launch(joint_scores_kernel, dim3(n_problems), dim3(64), 0, stream, work, joints, joint_stride, dt, n_samples_max, scores, kin);
+}
+
+// twr_batch_eval_joint_scores: x -> the same eight doubles without a trajectory.  One wave per problem like
+// contact_plan_kernel: durations to LDS, then per round the lane's sample as sample_kernel takes it (sample_base, sample_angular,
+// sample_spline with every result kept alive: the same bits), the frame change and the leg IK as joints_kernel, the fold as
+// joint_scores_kernel.
+__global__ __launch_bounds__(64) void eval_joint_scores_kernel(const NodeWork* __restrict__ work, const double* __restrict__ x, double dt,
+                                                               int n_samples_max, double* __restrict__ scores, twr_leg_kinematics K) {
+  __shared__ double s_bd[2 * kMaxPhasePolys], s_ph[kMaxEE][TWR_MAX_PHASES_DEV], s_md[kMaxEE][kMaxPhasePolys];
+  const NodeWork w = work[blockIdx.x];
+  const char* blob = reinterpret_cast<const char*>(w.blob);
+  const DevStruct* H = reinterpret_cast<const DevStruct*>(blob);
+  const SampleTables* ST = tbl<SampleTables>(blob, H->o_sample);
+  const double* xp = x + w.x_off;
+  const int lane = threadIdx.x, n_ee = H->n_ee;
+  for (int q = lane; q < ST->n_base; q += 64) s_bd[q] = tbl<double>(blob, ST->o_bdur)[q];
+  for (int e = 0; e < n_ee; ++e) {
+    if (H->timings) {
+      phase_poly_durations_wave(tbl<PhaseTables>(blob, H->o_phase), blob, xp, e, s_ph[e], s_md[e], lane);
+    } else {
+      for (int q = lane; q < ST->n_mpoly[e]; q += 64) s_md[e][q] = tbl<double>(blob, ST->o_mdur[e])[q];
+    }
+  }
+  __syncthreads();
+  const double T = ST->t_total;
+  JointFold F;
+  F.init();
+  for (int s0 = 0; s0 < n_samples_max; s0 += 64) {
+    const int s_idx = s0 + lane;
+    double t = 0.0;
+    for (int i = 0; i < s_idx; ++i) t += dt;
+    const bool live = t <= T + 1e-5;
+    if (!__any(live)) break;
+    double q[kMaxEE][3] = {};
+    double ov[kMaxEE] = {};
+    int fl[kMaxEE] = {};
+    if (live) {
+      BaseSample B;
+      BaseAngular A;
+      sample_base(xp, ST, s_bd, t, B);
+      sample_angular(B, A);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {   // (what sample_kernel stores and this kernel has no use for)
+        keep_alive(B.v[d]);
+        keep_alive(B.a[d]);
+        keep_alive(A.omega[d]);
+        keep_alive(A.omega_dot[d]);
+      }
+      const double (&pb)[3] = B.p;
+      double R[3][3];
+      base_frame_rotation(A.q[3], A.q[0], A.q[1], A.q[2], R);
+      for (int e = 0; e < n_ee; ++e) {
+        double tlm, pe[3], v[3], a[3], foot[3];
+        const int qm = locate_segment(s_md[e], ST->n_mpoly[e], t, tlm);
+        sample_spline(xp, tbl<PolyDesc>(blob, ST->o_mdesc[e])[qm], tlm, s_md[e][qm], pe, v, a);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+          keep_alive(v[d]);
+          keep_alive(a[d]);
+        }
+        base_frame(R, pb, pe, foot);
+        LegIk k;
+        leg_ik_of_foot(foot, e, K, k);
+        const double over = over_reach(k.r, K);
+#pragma unroll
+        for (int j = 0; j < kMaxEE; ++j)   // (a rolled loop over the legs, its results selected into registers)
+          if (j == e) {
+            q[j][0] = k.q[0]; q[j][1] = k.q[1]; q[j][2] = k.q[2];
+            fl[j] = k.flags;
+            ov[j] = over;
+          }
+      }
+    }
+    F.round(lane, s_idx, live, n_ee, q, fl, ov, dt, K);
+  }
+  F.finish(lane, scores + TWR_JOINT_SCORE_REC * (size_t)blockIdx.x);
+}
+hipError_t launch_eval_joint_scores(const NodeWork* work, int n_problems, const double* x, double dt, int n_samples_max, double* scores,
+                                    const twr_leg_kinematics& kin, hipStream_t stream) {
+  return twr_launch(eval_joint_scores_kernel, dim3(n_problems), dim3(64), 0, stream, work, x, dt, n_samples_max, scores, kin);
 }
 
 // ---------------------------------------------------------------- TWR_EVAL_CHECK
