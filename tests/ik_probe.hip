@@ -8,12 +8,15 @@
 // hfe_to_haa[3], length_thigh, length_shank, q_min[3], q_max[3].  OUT (raw doubles), per leg: q_HAA q_HFE q_KFE flags
 // cos_beta cos_gamma r over_reach.
 //
-// Exit status: 0 done, 2 usage / file error, 3 no HIP device, 4 a HIP call failed.
+// Exit status: see probe_host.h.
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "kernels/joints.h"
+
+#define PROBE_NAME "ik_probe"
+#include "probe_host.h"
 
 namespace {
 constexpr int BLOCK = 64, OUT = 8, KIN = 31;
@@ -42,79 +45,44 @@ __global__ __launch_bounds__(BLOCK) void body_probe(const double* __restrict__ p
     put(out + OUT * (4 * i + e), k, K);
   }
 }
-
-bool ok(hipError_t err, const char* what) {
-  if (err == hipSuccess) return true;
-  std::fprintf(stderr, "ik_probe: %s: %s\n", what, hipGetErrorString(err));
-  return false;
-}
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc != 4 || (std::strcmp(argv[1], "leg") && std::strcmp(argv[1], "body"))) {
     std::fprintf(stderr, "usage: ik_probe leg|body IN OUT\n");
-    return 2;
+    return probe::REFUSED;
   }
   const bool body = !std::strcmp(argv[1], "body");
-  std::vector<double> in;
-  {
-    std::FILE* f = std::fopen(argv[2], "rb");
-    if (!f) {
-      std::fprintf(stderr, "ik_probe: cannot read %s\n", argv[2]);
-      return 2;
-    }
-    double buf[4096];
-    size_t got;
-    while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) in.insert(in.end(), buf, buf + got);
-    std::fclose(f);
-  }
+  probe::Input in;
+  if (!in.read(argv[2])) return probe::REFUSED;
   // parse on the host first: the count is checked against what the file holds before anything reaches the device
-  auto bad = [&](const char* what) {
-    std::fprintf(stderr, "ik_probe: %s: %s\n", argv[2], what);
-    return 2;
-  };
-  if (in.size() < (size_t)KIN + 1) return bad("truncated descriptor");
+  if (!in.have((size_t)KIN + 1)) return in.bad("truncated descriptor");
   twr_leg_kinematics K;
   std::memset(&K, 0, sizeof K);
-  size_t at = 0;
-  K.n_ee = (int32_t)in[at++];
-  for (int e = 0; e < 4; ++e) K.knee_bend[e] = (int32_t)in[at++];
+  K.n_ee = (int32_t)in.next();
+  for (int e = 0; e < 4; ++e) K.knee_bend[e] = (int32_t)in.next();
   for (int e = 0; e < 4; ++e)
-    for (int d = 0; d < 3; ++d) K.mirror[e][d] = in[at++];
-  for (int d = 0; d < 3; ++d) K.base_to_hip[d] = in[at++];
-  for (int d = 0; d < 3; ++d) K.hfe_to_haa[d] = in[at++];
-  K.length_thigh = in[at++];
-  K.length_shank = in[at++];
-  for (int j = 0; j < 3; ++j) K.q_min[j] = in[at++];
-  for (int j = 0; j < 3; ++j) K.q_max[j] = in[at++];
-  const long n = (long)in[at++];
+    for (int d = 0; d < 3; ++d) K.mirror[e][d] = in.next();
+  for (int d = 0; d < 3; ++d) K.base_to_hip[d] = in.next();
+  for (int d = 0; d < 3; ++d) K.hfe_to_haa[d] = in.next();
+  K.length_thigh = in.next();
+  K.length_shank = in.next();
+  for (int j = 0; j < 3; ++j) K.q_min[j] = in.next();
+  for (int j = 0; j < 3; ++j) K.q_max[j] = in.next();
+  const long n = (long)in.next();
   const size_t per = body ? 12 : 4;
-  if (n < 1 || n > (1L << 22)) return bad("point count");
-  if (in.size() < at + per * (size_t)n) return bad("truncated points");
-  if (in.size() != at + per * (size_t)n) return bad("trailing data");
-  if (body && K.n_ee != 4) return bad("body mode needs four legs");
-  int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
-    std::fprintf(stderr, "ik_probe: no HIP device\n");
-    return 3;
-  }
+  if (n < 1 || n > (1L << 22)) return in.bad("point count");
+  if (!in.have(per * (size_t)n)) return in.bad("truncated points");
+  if (in.at + per * (size_t)n != in.v.size()) return in.bad("trailing data");
+  if (body && K.n_ee != 4) return in.bad("body mode needs four legs");
+  if (!probe::have_device()) return probe::NO_DEVICE;
   std::vector<double> out((size_t)OUT * (body ? 4 : 1) * (size_t)n);
+  probe::Device dev;
   double *d_p = nullptr, *d_out = nullptr;
-  if (!ok(hipMalloc(reinterpret_cast<void**>(&d_p), per * (size_t)n * sizeof(double)), "hipMalloc") ||
-      !ok(hipMemcpy(d_p, in.data() + at, per * (size_t)n * sizeof(double), hipMemcpyHostToDevice), "copy in") ||
-      !ok(hipMalloc(reinterpret_cast<void**>(&d_out), out.size() * sizeof(double)), "hipMalloc") ||
-      !ok(hipMemset(d_out, 0xFF, out.size() * sizeof(double)), "hipMemset"))   // unwritten results read back as NaN
-    return 4;
+  if (!dev.upload(&d_p, in.here(), per * (size_t)n) || !dev.results(&d_out, out.size())) return probe::HIP_FAILED;
   const unsigned blocks = (unsigned)((n + BLOCK - 1) / BLOCK);
   if (body) body_probe<<<blocks, BLOCK>>>(d_p, n, d_out, K);
   else leg_probe<<<blocks, BLOCK>>>(d_p, n, d_out, K);
-  if (!ok(hipGetLastError(), "launch") || !ok(hipDeviceSynchronize(), "kernel")) return 4;
-  if (!ok(hipMemcpy(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost), "copy out")) return 4;
-  if (!ok(hipFree(d_p), "hipFree") || !ok(hipFree(d_out), "hipFree")) return 4;
-  std::FILE* f = std::fopen(argv[3], "wb");
-  if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size() || std::fclose(f) != 0) {
-    std::fprintf(stderr, "ik_probe: cannot write %s\n", argv[3]);
-    return 2;
-  }
-  return 0;
+  if (!probe::collect(out.data(), d_out, out.size()) || !dev.release()) return probe::HIP_FAILED;
+  return probe::write_out(argv[3], out);
 }

@@ -23,6 +23,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spl
 
 from .common import baseline_cases, random_case
+from .probe import bits
 
 TOL, ITERS, COND, REL_FLOOR = 1e-10, 200, 101.0, 1e-12
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,10 +35,6 @@ def csr(S, vals):
 
 def viol(g, lo, hi):
     return g - np.clip(g, lo, hi)
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def same_bits(a, b):

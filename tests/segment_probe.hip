@@ -17,13 +17,16 @@
 //              slot e = case mod 4 describes the ee-motion polynomials and whose slot (e + 1) mod 4 the ee-force polynomials.
 //   hermite    the number of points; per point t and iT.
 //
-// Exit status: 0 done, 2 usage / file error, 3 no HIP device, 4 a HIP call failed.
+// Exit status: see probe_host.h.
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "kernels/phase_durations.h"
 #include "kernels/spline_math.h"
+
+#define PROBE_NAME "segment_probe"
+#include "probe_host.h"
 
 namespace {
 constexpr int BLOCK = 256;
@@ -83,19 +86,6 @@ __global__ __launch_bounds__(BLOCK) void hermite_probe(const double* __restrict_
   }
 }
 
-bool ok(hipError_t err, const char* what) {
-  if (err == hipSuccess) return true;
-  std::fprintf(stderr, "segment_probe: %s: %s\n", what, hipGetErrorString(err));
-  return false;
-}
-
-template <class T>
-bool upload(T** dev, const std::vector<T>& host) {
-  const size_t bytes = (host.empty() ? 1 : host.size()) * sizeof(T);
-  return ok(hipMalloc(reinterpret_cast<void**>(dev), bytes), "hipMalloc") &&
-         (host.empty() || ok(hipMemcpy(*dev, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice), "copy in"));
-}
-
 // ee-motion (constant = contact) or ee-force (constant = !contact) polynomials of n phases: BuildPolyInfos
 // (nodes_variables_phase_based.cc:38-58)
 std::vector<twr::PhasePoly> poly_infos(int n, bool first_constant, int n_changing) {
@@ -120,122 +110,89 @@ std::vector<twr::PhasePoly> poly_infos(int n, bool first_constant, int n_changin
 int main(int argc, char** argv) {
   if (argc != 4) {
     std::fprintf(stderr, "usage: segment_probe locate|durations64|durations256|hermite IN OUT\n");
-    return 2;
+    return probe::REFUSED;
   }
   const bool m_locate = !std::strcmp(argv[1], "locate"), m_d64 = !std::strcmp(argv[1], "durations64"),
              m_d256 = !std::strcmp(argv[1], "durations256"), m_hermite = !std::strcmp(argv[1], "hermite");
   if (!m_locate && !m_d64 && !m_d256 && !m_hermite) {
     std::fprintf(stderr, "segment_probe: unknown mode %s\n", argv[1]);
-    return 2;
+    return probe::REFUSED;
   }
-  std::vector<double> in;
-  {
-    std::FILE* f = std::fopen(argv[2], "rb");
-    if (!f) {
-      std::fprintf(stderr, "segment_probe: cannot read %s\n", argv[2]);
-      return 2;
-    }
-    double buf[4096];
-    size_t got;
-    while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) in.insert(in.end(), buf, buf + got);
-    std::fclose(f);
-  }
+  probe::Input in;
+  if (!in.read(argv[2])) return probe::REFUSED;
   // parse on the host first: every count and index is checked against what the file holds before anything reaches the device
-  size_t at = 0;
-  auto have = [&](size_t k) { return at + k <= in.size(); };
-  auto bad = [&](const char* what) {
-    std::fprintf(stderr, "segment_probe: %s: %s\n", argv[2], what);
-    return 2;
-  };
-  if (!have(1)) return bad("empty");
+  if (!in.have(1)) return in.bad("empty");
+  // every mode parses, asks for a device, uploads, sizes `out` and launches; the results of all three are collected below
   std::vector<double> out;
+  probe::Device dev;
+  double* d_out = nullptr;
 
   if (m_locate) {
-    const long n_lists = (long)in[at++];
-    if (n_lists < 1 || n_lists > (1L << 20)) return bad("list count");
+    const long n_lists = (long)in.next();
+    if (n_lists < 1 || n_lists > (1L << 20)) return in.bad("list count");
     std::vector<double> durations;
     std::vector<int32_t> d_at, d_n;
     for (long l = 0; l < n_lists; ++l) {
-      if (!have(1)) return bad("truncated list header");
-      const long n = (long)in[at++];
-      if (n < 1 || n > twr::kMaxPhasePolys) return bad("list length");
-      if (!have((size_t)n)) return bad("truncated list");
+      if (!in.have(1)) return in.bad("truncated list header");
+      const long n = (long)in.next();
+      if (n < 1 || n > twr::kMaxPhasePolys) return in.bad("list length");
+      if (!in.have((size_t)n)) return in.bad("truncated list");
       d_at.push_back((int32_t)durations.size());
       d_n.push_back((int32_t)n);
-      durations.insert(durations.end(), in.begin() + at, in.begin() + at + n);
-      at += (size_t)n;
+      durations.insert(durations.end(), in.here(), in.here() + n);
+      in.at += (size_t)n;
     }
-    if (!have(1)) return bad("no points");
-    const long n_points = (long)in[at++];
-    if (n_points < 1 || n_points > (1L << 24)) return bad("point count");
-    if (!have(2 * (size_t)n_points)) return bad("truncated points");
-    if (at + 2 * (size_t)n_points != in.size()) return bad("trailing data");
+    if (!in.have(1)) return in.bad("no points");
+    const long n_points = (long)in.next();
+    if (n_points < 1 || n_points > (1L << 24)) return in.bad("point count");
+    if (!in.have(2 * (size_t)n_points)) return in.bad("truncated points");
+    if (in.at + 2 * (size_t)n_points != in.v.size()) return in.bad("trailing data");
     std::vector<double> t((size_t)n_points);
     std::vector<LocateWork> work;
     long prev = -1;
     for (long k = 0; k < n_points; ++k) {
-      const long l = (long)in[at + 2 * k];
-      if (l < 0 || l >= n_lists || l < prev) return bad("list index (the points are ordered by list)");
-      t[k] = in[at + 2 * k + 1];
+      const long l = (long)in[2 * k];
+      if (l < 0 || l >= n_lists || l < prev) return in.bad("list index (the points are ordered by list)");
+      t[k] = in[2 * k + 1];
       if (l != prev || work.back().count == BLOCK) work.push_back({d_at[l], d_n[l], (int32_t)k, 0});
       ++work.back().count;
       prev = l;
     }
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
-      std::fprintf(stderr, "segment_probe: no HIP device\n");
-      return 3;
-    }
+    if (!probe::have_device()) return probe::NO_DEVICE;
     LocateWork* d_work = nullptr;
-    double *d_dur = nullptr, *d_t = nullptr, *d_out = nullptr;
+    double *d_dur = nullptr, *d_t = nullptr;
     out.resize(2 * (size_t)n_points);
-    if (!upload(&d_work, work) || !upload(&d_dur, durations) || !upload(&d_t, t) ||
-        !ok(hipMalloc(reinterpret_cast<void**>(&d_out), out.size() * sizeof(double)), "hipMalloc") ||
-        !ok(hipMemset(d_out, 0xFF, out.size() * sizeof(double)), "hipMemset"))   // unwritten results read back as NaN
-      return 4;
+    if (!dev.upload(&d_work, work) || !dev.upload(&d_dur, durations) || !dev.upload(&d_t, t) || !dev.results(&d_out, out.size()))
+      return probe::HIP_FAILED;
     locate_probe<<<(unsigned)work.size(), BLOCK>>>(d_work, d_dur, d_t, d_out);
-    if (!ok(hipGetLastError(), "launch") || !ok(hipDeviceSynchronize(), "kernel")) return 4;
-    if (!ok(hipMemcpy(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost), "copy out")) return 4;
-    if (!ok(hipFree(d_work), "hipFree") || !ok(hipFree(d_dur), "hipFree") || !ok(hipFree(d_t), "hipFree") || !ok(hipFree(d_out), "hipFree"))
-      return 4;
   } else if (m_hermite) {
-    const long n = (long)in[at++];
-    if (n < 1 || n > (1L << 24)) return bad("point count");
-    if (!have(2 * (size_t)n)) return bad("truncated points");
-    if (at + 2 * (size_t)n != in.size()) return bad("trailing data");
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
-      std::fprintf(stderr, "segment_probe: no HIP device\n");
-      return 3;
-    }
-    const std::vector<double> p(in.begin() + at, in.end());
-    double *d_p = nullptr, *d_out = nullptr;
+    const long n = (long)in.next();
+    if (n < 1 || n > (1L << 24)) return in.bad("point count");
+    if (!in.have(2 * (size_t)n)) return in.bad("truncated points");
+    if (in.at + 2 * (size_t)n != in.v.size()) return in.bad("trailing data");
+    if (!probe::have_device()) return probe::NO_DEVICE;
+    double* d_p = nullptr;
     out.resize(12 * (size_t)n);
-    if (!upload(&d_p, p) || !ok(hipMalloc(reinterpret_cast<void**>(&d_out), out.size() * sizeof(double)), "hipMalloc") ||
-        !ok(hipMemset(d_out, 0xFF, out.size() * sizeof(double)), "hipMemset"))
-      return 4;
+    if (!dev.upload(&d_p, in.here(), 2 * (size_t)n) || !dev.results(&d_out, out.size())) return probe::HIP_FAILED;
     hermite_probe<<<(unsigned)((n + BLOCK - 1) / BLOCK), BLOCK>>>(d_p, n, d_out);
-    if (!ok(hipGetLastError(), "launch") || !ok(hipDeviceSynchronize(), "kernel")) return 4;
-    if (!ok(hipMemcpy(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost), "copy out")) return 4;
-    if (!ok(hipFree(d_p), "hipFree") || !ok(hipFree(d_out), "hipFree")) return 4;
   } else {
-    const long n_cases = (long)in[at++];
-    if (n_cases < 1 || n_cases > 4096) return bad("case count");
+    const long n_cases = (long)in.next();
+    if (n_cases < 1 || n_cases > 4096) return in.bad("case count");
     // one blob per case: PhaseTables, then the ee-motion PhasePoly array, then the ee-force one; one x per case
     std::vector<std::vector<char>> blobs;
     std::vector<std::vector<double>> xs;
     std::vector<int> ee;
     for (long c = 0; c < n_cases; ++c) {
-      if (!have(5)) return bad("truncated case header");
-      const long n = (long)in[at];
-      const bool contact = in[at + 1] != 0.0;
-      const long pps = (long)in[at + 2], ppf = (long)in[at + 3];
-      const double t_total = in[at + 4];
-      at += 5;
-      if (n < 1 || n > twr::TWR_MAX_PHASES_DEV || pps < 1 || pps > 16 || ppf < 1 || ppf > 16) return bad("case header");
-      if (!have((size_t)(n - 1))) return bad("truncated case");
+      if (!in.have(5)) return in.bad("truncated case header");
+      const long n = (long)in[0];
+      const bool contact = in[1] != 0.0;
+      const long pps = (long)in[2], ppf = (long)in[3];
+      const double t_total = in[4];
+      in.at += 5;
+      if (n < 1 || n > twr::TWR_MAX_PHASES_DEV || pps < 1 || pps > 16 || ppf < 1 || ppf > 16) return in.bad("case header");
+      if (!in.have((size_t)(n - 1))) return in.bad("truncated case");
       const std::vector<twr::PhasePoly> mp = poly_infos((int)n, contact, (int)pps), fp = poly_infos((int)n, !contact, (int)ppf);
-      if (mp.size() > (size_t)twr::kMaxPhasePolys || fp.size() > (size_t)twr::kMaxPhasePolys) return bad("more than 64 polynomials");
+      if (mp.size() > (size_t)twr::kMaxPhasePolys || fp.size() > (size_t)twr::kMaxPhasePolys) return in.bad("more than 64 polynomials");
       const int e = (int)(c % twr::kMaxEE), f = (e + 1) % twr::kMaxEE;
       twr::PhaseTables PT;
       std::memset(&PT, 0, sizeof PT);
@@ -253,43 +210,25 @@ int main(int argc, char** argv) {
       std::memcpy(blob.data() + PT.o_mpoly[e], mp.data(), mp.size() * sizeof(twr::PhasePoly));
       std::memcpy(blob.data() + PT.o_mpoly[f], fp.data(), fp.size() * sizeof(twr::PhasePoly));
       std::vector<double> x((size_t)X_PAD, -1.0);
-      x.insert(x.end(), in.begin() + at, in.begin() + at + (n - 1));
-      at += (size_t)(n - 1);
+      x.insert(x.end(), in.here(), in.here() + (n - 1));
+      in.at += (size_t)(n - 1);
       blobs.push_back(blob), xs.push_back(x), ee.push_back(e);
     }
-    if (at != in.size()) return bad("trailing data");
-    int devices = 0;
-    if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
-      std::fprintf(stderr, "segment_probe: no HIP device\n");
-      return 3;
-    }
+    if (!in.at_end()) return in.bad("trailing data");
+    if (!probe::have_device()) return probe::NO_DEVICE;
     std::vector<DurWork> work;
-    std::vector<void*> owned;
     for (long c = 0; c < n_cases; ++c) {
       char* d_blob = nullptr;
       double* d_x = nullptr;
-      if (!upload(&d_blob, blobs[c]) || !upload(&d_x, xs[c])) return 4;
-      owned.push_back(d_blob), owned.push_back(d_x);
+      if (!dev.upload(&d_blob, blobs[c]) || !dev.upload(&d_x, xs[c])) return probe::HIP_FAILED;
       work.push_back({(uint64_t)(uintptr_t)d_blob, (uint64_t)(uintptr_t)d_x, ee[c], 0});
     }
     DurWork* d_work = nullptr;
-    double* d_out = nullptr;
     out.resize((size_t)DUR_OUT * n_cases);
-    if (!upload(&d_work, work) || !ok(hipMalloc(reinterpret_cast<void**>(&d_out), out.size() * sizeof(double)), "hipMalloc") ||
-        !ok(hipMemset(d_out, 0xFF, out.size() * sizeof(double)), "hipMemset"))
-      return 4;
+    if (!dev.upload(&d_work, work) || !dev.results(&d_out, out.size())) return probe::HIP_FAILED;
     const int nthreads = m_d64 ? 64 : 256;
     durations_probe<<<(unsigned)n_cases, nthreads>>>(d_work, d_out, nthreads);
-    if (!ok(hipGetLastError(), "launch") || !ok(hipDeviceSynchronize(), "kernel")) return 4;
-    if (!ok(hipMemcpy(out.data(), d_out, out.size() * sizeof(double), hipMemcpyDeviceToHost), "copy out")) return 4;
-    for (void* p : owned)
-      if (!ok(hipFree(p), "hipFree")) return 4;
-    if (!ok(hipFree(d_work), "hipFree") || !ok(hipFree(d_out), "hipFree")) return 4;
   }
-  std::FILE* f = std::fopen(argv[3], "wb");
-  if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size() || std::fclose(f) != 0) {
-    std::fprintf(stderr, "segment_probe: cannot write %s\n", argv[3]);
-    return 2;
-  }
-  return 0;
+  if (!probe::collect(out.data(), d_out, out.size()) || !dev.release()) return probe::HIP_FAILED;
+  return probe::write_out(argv[3], out);
 }

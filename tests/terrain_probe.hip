@@ -10,12 +10,15 @@
 // terrain_id, map index (-1: none), mu, flat_height, n, then n points -- (x, y) for eval, (fx, fy, fz, x, y) for the
 // force modes.  Each group runs on a DevStruct of its own, filled by hand with the fields the terrain reads.
 //
-// Exit status: 0 done, 2 usage / file error, 3 no HIP device, 4 a HIP call failed.
+// Exit status: see probe_host.h.
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "kernels/terrain.h"
+
+#define PROBE_NAME "terrain_probe"
+#include "probe_host.h"
 
 namespace {
 constexpr int BLOCK = 256;
@@ -47,12 +50,6 @@ __global__ void force_probe(const twr::DevStruct* __restrict__ S, const double* 
   }
 }
 
-bool ok(hipError_t err, const char* what) {
-  if (err == hipSuccess) return true;
-  std::fprintf(stderr, "terrain_probe: %s: %s\n", what, hipGetErrorString(err));
-  return false;
-}
-
 struct Map {
   int kind, rows, cols;
   double res, eps, px, py;
@@ -63,46 +60,30 @@ struct Map {
 int main(int argc, char** argv) {
   if (argc != 4) {
     std::fprintf(stderr, "usage: terrain_probe eval|force|force_g IN OUT\n");
-    return 2;
+    return probe::REFUSED;
   }
   const bool m_eval = !std::strcmp(argv[1], "eval"), m_force = !std::strcmp(argv[1], "force"), m_g = !std::strcmp(argv[1], "force_g");
   if (!m_eval && !m_force && !m_g) {
     std::fprintf(stderr, "terrain_probe: unknown mode %s\n", argv[1]);
-    return 2;
+    return probe::REFUSED;
   }
-  std::vector<double> in;
-  {
-    std::FILE* f = std::fopen(argv[2], "rb");
-    if (!f) {
-      std::fprintf(stderr, "terrain_probe: cannot read %s\n", argv[2]);
-      return 2;
-    }
-    double buf[4096];
-    size_t got;
-    while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) in.insert(in.end(), buf, buf + got);
-    std::fclose(f);
-  }
+  probe::Input in;
+  if (!in.read(argv[2])) return probe::REFUSED;
   // parse on the host first: every count is checked against what the file holds before anything reaches the device
-  size_t at = 0;
-  auto have = [&](size_t k) { return at + k <= in.size(); };
-  auto bad = [&](const char* what) {
-    std::fprintf(stderr, "terrain_probe: %s: %s\n", argv[2], what);
-    return 2;
-  };
-  if (!have(1)) return bad("empty");
-  const long n_maps = (long)in[at++];
-  if (n_maps < 0 || n_maps > 64) return bad("map count");
+  if (!in.have(1)) return in.bad("empty");
+  const long n_maps = (long)in.next();
+  if (n_maps < 0 || n_maps > 64) return in.bad("map count");
   std::vector<Map> maps;
   std::vector<size_t> map_at;
   for (long m = 0; m < n_maps; ++m) {
-    if (!have(7)) return bad("truncated map header");
-    Map mp = {(int)in[at], (int)in[at + 1], (int)in[at + 2], in[at + 3], in[at + 4], in[at + 5], in[at + 6], nullptr};
-    at += 7;
+    if (!in.have(7)) return in.bad("truncated map header");
+    Map mp = {(int)in[0], (int)in[1], (int)in[2], in[3], in[4], in[5], in[6], nullptr};
+    in.at += 7;
     if ((mp.kind != 7 && mp.kind != 8) || mp.rows < 1 || mp.cols < 1 || mp.rows > 4096 || mp.cols > 4096 || !(mp.res > 0) || !(mp.eps > 0))
-      return bad("map header");
-    if (!have((size_t)mp.rows * mp.cols)) return bad("truncated map");
-    map_at.push_back(at);
-    at += (size_t)mp.rows * mp.cols;
+      return in.bad("map header");
+    if (!in.have((size_t)mp.rows * mp.cols)) return in.bad("truncated map");
+    map_at.push_back(in.at);
+    in.at += (size_t)mp.rows * mp.cols;
     maps.push_back(mp);
   }
   struct Group {
@@ -112,43 +93,40 @@ int main(int argc, char** argv) {
     size_t at;
   };
   const long per_in = m_eval ? 2 : 5, per_out = m_eval ? 4 : m_force ? FORCE_OUT : 5;
-  if (!have(1)) return bad("no groups");
-  const long n_groups = (long)in[at++];
-  if (n_groups < 1 || n_groups > 4096) return bad("group count");
+  if (!in.have(1)) return in.bad("no groups");
+  const long n_groups = (long)in.next();
+  if (n_groups < 1 || n_groups > 4096) return in.bad("group count");
   std::vector<Group> groups;
   long total = 0;
   for (long g = 0; g < n_groups; ++g) {
-    if (!have(5)) return bad("truncated group header");
-    Group gr = {(int)in[at], (int)in[at + 1], in[at + 2], in[at + 3], (long)in[at + 4], at + 5};
-    at += 5;
-    if (gr.terrain_id < 0 || gr.terrain_id > 8 || gr.n < 1 || gr.n > (1L << 24)) return bad("group header");
-    if ((gr.terrain_id >= 7) != (gr.map >= 0) || gr.map >= n_maps) return bad("group map index");
-    if (gr.map >= 0 && maps[gr.map].kind != gr.terrain_id) return bad("group map kind");
-    if (!have((size_t)gr.n * per_in)) return bad("truncated group");
-    at += (size_t)gr.n * per_in;
+    if (!in.have(5)) return in.bad("truncated group header");
+    Group gr = {(int)in[0], (int)in[1], in[2], in[3], (long)in[4], in.at + 5};
+    in.at += 5;
+    if (gr.terrain_id < 0 || gr.terrain_id > 8 || gr.n < 1 || gr.n > (1L << 24)) return in.bad("group header");
+    if ((gr.terrain_id >= 7) != (gr.map >= 0) || gr.map >= n_maps) return in.bad("group map index");
+    if (gr.map >= 0 && maps[gr.map].kind != gr.terrain_id) return in.bad("group map kind");
+    if (!in.have((size_t)gr.n * per_in)) return in.bad("truncated group");
+    in.at += (size_t)gr.n * per_in;
     total += gr.n;
     groups.push_back(gr);
   }
-  if (at != in.size()) return bad("trailing data");
+  if (!in.at_end()) return in.bad("trailing data");
 
-  int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
-    std::fprintf(stderr, "terrain_probe: no HIP device\n");
-    return 3;
-  }
+  if (!probe::have_device()) return probe::NO_DEVICE;
+  probe::Device map_dev;   // the maps live as long as the groups; a kind-8 map goes up as floats
   for (size_t m = 0; m < maps.size(); ++m) {
     Map& mp = maps[m];
     const size_t cells = (size_t)mp.rows * mp.cols;
     if (mp.kind == 7) {
-      if (!ok(hipMalloc(&mp.dev, cells * sizeof(double)), "hipMalloc") ||
-          !ok(hipMemcpy(mp.dev, in.data() + map_at[m], cells * sizeof(double), hipMemcpyHostToDevice), "copy map"))
-        return 4;
+      double* d = nullptr;
+      if (!map_dev.upload(&d, in.v.data() + map_at[m], cells)) return probe::HIP_FAILED;
+      mp.dev = d;
     } else {
       std::vector<float> el(cells);
-      for (size_t k = 0; k < cells; ++k) el[k] = (float)in[map_at[m] + k];
-      if (!ok(hipMalloc(&mp.dev, cells * sizeof(float)), "hipMalloc") ||
-          !ok(hipMemcpy(mp.dev, el.data(), cells * sizeof(float), hipMemcpyHostToDevice), "copy map"))
-        return 4;
+      for (size_t k = 0; k < cells; ++k) el[k] = (float)in.v[map_at[m] + k];
+      float* d = nullptr;
+      if (!map_dev.upload(&d, el)) return probe::HIP_FAILED;
+      mp.dev = d;
     }
   }
   std::vector<double> out((size_t)total * per_out);
@@ -169,31 +147,18 @@ int main(int argc, char** argv) {
       S.grid_px = mp.px;
       S.grid_py = mp.py;
     }
+    probe::Device dev;   // this group's header, points and results, freed before the next group
     twr::DevStruct* d_S = nullptr;
     double *d_in = nullptr, *d_out = nullptr;
     const size_t n_in = (size_t)gr.n * per_in, n_out = (size_t)gr.n * per_out;
-    if (!ok(hipMalloc(&d_S, sizeof S), "hipMalloc") || !ok(hipMalloc(&d_in, n_in * sizeof(double)), "hipMalloc") ||
-        !ok(hipMalloc(&d_out, n_out * sizeof(double)), "hipMalloc"))
-      return 4;
-    if (!ok(hipMemcpy(d_S, &S, sizeof S, hipMemcpyHostToDevice), "copy header") ||
-        !ok(hipMemcpy(d_in, in.data() + gr.at, n_in * sizeof(double), hipMemcpyHostToDevice), "copy in") ||
-        !ok(hipMemset(d_out, 0xFF, n_out * sizeof(double)), "hipMemset"))   // unwritten results read back as NaN
-      return 4;
+    if (!dev.upload(&d_S, &S, 1) || !dev.upload(&d_in, in.v.data() + gr.at, n_in) || !dev.results(&d_out, n_out)) return probe::HIP_FAILED;
     const unsigned blocks = (unsigned)((gr.n + BLOCK - 1) / BLOCK);
     if (m_eval) eval_probe<<<blocks, BLOCK>>>(d_S, d_in, gr.n, d_out);
     else if (m_force) force_probe<true><<<blocks, BLOCK>>>(d_S, d_in, gr.n, d_out);
     else force_probe<false><<<blocks, BLOCK>>>(d_S, d_in, gr.n, d_out);
-    if (!ok(hipGetLastError(), "launch") || !ok(hipDeviceSynchronize(), "kernel")) return 4;
-    if (!ok(hipMemcpy(out.data() + out_at, d_out, n_out * sizeof(double), hipMemcpyDeviceToHost), "copy out")) return 4;
+    if (!probe::collect(out.data() + out_at, d_out, n_out) || !dev.release()) return probe::HIP_FAILED;
     out_at += n_out;
-    if (!ok(hipFree(d_S), "hipFree") || !ok(hipFree(d_in), "hipFree") || !ok(hipFree(d_out), "hipFree")) return 4;
   }
-  for (Map& mp : maps)
-    if (!ok(hipFree(mp.dev), "hipFree")) return 4;
-  std::FILE* f = std::fopen(argv[3], "wb");
-  if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size() || std::fclose(f) != 0) {
-    std::fprintf(stderr, "terrain_probe: cannot write %s\n", argv[3]);
-    return 2;
-  }
-  return 0;
+  if (!map_dev.release()) return probe::HIP_FAILED;
+  return probe::write_out(argv[3], out);
 }

@@ -21,42 +21,16 @@ no acos takes an unclamped argument.
 
 The GPU tests print the worst case they measured as a fraction of the bound (run with -s); DESIGN section 5 "Leg inverse
 kinematics" quotes them."""
-import functools
-import os
-import shutil
-import subprocess
-import tempfile
-
 import numpy as np
 import pytest
 
 import towr_amd as ta
 
 from . import ik_points as ip
-from .test_ik_ref import C_IK, PI, U, acos_factor, angle_bounds, bits, fixture, mp_leg_ik, same_bits
-from .test_terrain_probe import HIPCC, ROOT, product_cxxflags
+from .probe import Probe, bits
+from .test_ik_ref import C_IK, PI, U, acos_factor, angle_bounds, fixture, mp_leg_ik, same_bits
 
-_dir = None
-
-
-def _workdir():
-    global _dir
-    if _dir is None:
-        import atexit
-        _dir = tempfile.mkdtemp(prefix="twr_ik_probe_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
-
-
-@functools.lru_cache(maxsize=None)
-def _build():
-    exe = os.path.join(_workdir(), "ik_probe")
-    cmd = [HIPCC, "--offload-arch=gfx950"] + product_cxxflags() + ["-Wextra", "-I", os.path.join(ROOT, "towr_amd", "csrc"),
-                                                                    os.path.join(ROOT, "tests", "ik_probe.hip"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "warning" not in (r.stdout + r.stderr), r.stdout + r.stderr
-    return exe
+PROBE = Probe("ik_probe")
 
 
 def descriptor_doubles(k):
@@ -73,28 +47,16 @@ def probe_input(mode):
     return np.concatenate([k, [float(len(body))], body.ravel()])
 
 
-@functools.lru_cache(maxsize=None)
 def _probe(mode):
     """[n, 8] per leg: q_HAA q_HFE q_KFE flags cos_beta cos_gamma r over_reach, from a child process of its own"""
-    fin, fout = os.path.join(_workdir(), mode + ".in"), os.path.join(_workdir(), mode + ".out")
-    probe_input(mode).tofile(fin)
-    r = subprocess.run([_build(), mode, fin, fout], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, "ik_probe %s: exit %d\n%s%s" % (mode, r.returncode, r.stdout, r.stderr)
-    out = np.fromfile(fout, dtype=np.float64).reshape(-1, 8)
-    out.flags.writeable = False
-    return out
+    return PROBE.run(mode, probe_input(mode)).reshape(-1, 8)
 
 
 def test_probe_compiles_without_warning():
     """(CPU tier) hipcc compiles and links the probe for gfx950 with the product's flags, without a GPU and without a warning;
     the input parser refuses a file whose count does not add up before anything reaches a device"""
-    exe = _build()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
-    fin = os.path.join(_workdir(), "short.in")
-    probe_input("leg")[:-1].tofile(fin)
-    r = subprocess.run([exe, "leg", fin, os.path.join(_workdir(), "short.out")], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "truncated" in r.stderr
+    PROBE.refuses([], None, "usage")
+    PROBE.refuses(["leg"], probe_input("leg")[:-1], "truncated")
 
 
 def _reference():

@@ -27,7 +27,6 @@ What does not pass through an acos -- alpha = atan2(-z', +-x) - pi/2 (2.5 L + 4)
 addition or subtraction (1) -- stays below 3.5 L + 6 per side = 47 together and is covered by the "1 +" of the bound.  On the
 interior class (|c| <= 0.999, so 1 / sqrt <= 22.4) the bound stays below 121 * 2^-53 * 23.4 * pi = 9.9e-13 rad."""
 import ctypes as C
-import functools
 import os
 
 import numpy as np
@@ -37,15 +36,12 @@ import towr_amd as ta
 
 from . import ik_points as ip
 from .ik_ref import record
+from .probe import bits, load_fixture
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "refik_go1.npz")
 U = 2.0 ** -53
 C_IK = 121.0
 PI = ip.PI
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
 
 
 def same_bits(a, b):
@@ -54,13 +50,8 @@ def same_bits(a, b):
     return (bits(a) == bits(b)) | (np.isnan(a) & np.isnan(b))
 
 
-@functools.lru_cache(maxsize=None)
 def fixture():
-    d = np.load(GOLDEN)
-    out = {k: d[k] for k in d.files}
-    for v in out.values():
-        v.flags.writeable = False
-    return out
+    return load_fixture("refik_go1")
 
 
 def acos_factor(c):

@@ -31,8 +31,6 @@ The GPU tests print the worst case they measured as a fraction of the bound (run
 quotes it."""
 import functools
 import os
-import shutil
-import subprocess
 import tempfile
 
 import numpy as np
@@ -42,26 +40,16 @@ from oracle import binding as ob
 from oracle import mp_ref, ref_golden, ref_run
 
 from . import segment_points as sp
-from .test_terrain_probe import HIPCC, ROOT, product_cxxflags
+from .probe import GOLDEN, Probe, load_fixture, bits as _bits    # (the assertions below keep the name they were written with)
 
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 U = 2.0 ** -53
 C_HERMITE = 10.0     # the roundings of the longest chain of hermite_all (w_p0), counted in the docstring
 MAX_PHASES, MAX_POLYS = 32, 64
 DUR_OUT = MAX_PHASES + 2 * MAX_POLYS
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
-@functools.lru_cache(maxsize=None)
 def fixture():
-    d = np.load(os.path.join(GOLDEN, "refsegment.npz"))
-    out = {k: d[k] for k in d.files}
-    for v in out.values():
-        v.flags.writeable = False
-    return out
+    return load_fixture("refsegment")
 
 
 def fixture_case(k):
@@ -73,28 +61,8 @@ def fixture_case(k):
             f["case_fd"][f["case_fd_start"][k]:f["case_fd_start"][k + 1]])
 
 
-# ------------------------------------------------------------------ building and running the probe
-_dir = None
-
-
-def _workdir():
-    global _dir
-    if _dir is None:
-        import atexit
-        _dir = tempfile.mkdtemp(prefix="twr_segment_probe_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
-
-
-@functools.lru_cache(maxsize=None)
-def _build():
-    exe = os.path.join(_workdir(), "segment_probe")
-    cmd = [HIPCC, "--offload-arch=gfx950"] + product_cxxflags() + ["-Wextra", "-I", os.path.join(ROOT, "towr_amd", "csrc"),
-                                                                    os.path.join(ROOT, "tests", "segment_probe.hip"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "warning" not in (r.stdout + r.stderr), r.stdout + r.stderr
-    return exe
+# ------------------------------------------------------------------ running the probe (tests/probe.py)
+PROBE = Probe("segment_probe")
 
 
 @functools.lru_cache(maxsize=None)
@@ -160,36 +128,21 @@ def hermite_input():
     return np.concatenate([[float(len(h))], np.column_stack([h[:, 0], 1.0 / h[:, 1]]).ravel()])
 
 
-@functools.lru_cache(maxsize=None)
 def _probe(mode):
-    """the probe's raw output for `mode`, from a child process of its own; a non-zero exit fails the test and is not retried"""
+    """the probe's raw output for `mode`, from a child process of its own; a failed run is remembered and not started again,
+    and after a device failure no probe is (the failure rule of tests/probe.py)"""
     data = {"locate": locate_input, "durations64": durations_input, "durations256": durations_input, "hermite": hermite_input}[mode]()
-    fin, fout = os.path.join(_workdir(), mode + ".in"), os.path.join(_workdir(), mode + ".out")
-    data.tofile(fin)
-    r = subprocess.run([_build(), mode, fin, fout], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, "segment_probe %s: exit %d\n%s%s" % (mode, r.returncode, r.stdout, r.stderr)
-    raw = np.fromfile(fout, dtype=np.float64)
-    raw.flags.writeable = False
-    return raw
+    return PROBE.run(mode, data)
 
 
 # ------------------------------------------------------------------ CPU tier
 def test_probe_compiles_without_warning():
     """(CPU tier) hipcc compiles and links the probe for gfx950 with the product's flags, without a GPU and without a warning;
     the input parser refuses a file whose counts do not add up before anything reaches a device"""
-    exe = _build()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    PROBE.refuses([], None, "usage")
     for mode, data in (("locate", locate_input()), ("durations64", durations_input()), ("hermite", hermite_input())):
-        fin = os.path.join(_workdir(), "short.in")
-        data[:-1].tofile(fin)
-        r = subprocess.run([exe, mode, fin, os.path.join(_workdir(), "short.out")], capture_output=True, text=True, timeout=60)
-        assert r.returncode == 2 and "truncated" in r.stderr, (mode, r.stderr)
-    fin = os.path.join(_workdir(), "long.in")
-    long_list = np.concatenate([[1.0, 65.0], np.full(65, 0.1), [1.0, 0.0, 0.05]])
-    long_list.tofile(fin)
-    r = subprocess.run([exe, "locate", fin, os.path.join(_workdir(), "long.out")], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "list length" in r.stderr
+        PROBE.refuses([mode], data[:-1], "truncated")
+    PROBE.refuses(["locate"], np.concatenate([[1.0, 65.0], np.full(65, 0.1), [1.0, 0.0, 0.05]]), "list length")
 
 
 def test_points_cover_what_they_claim():

@@ -36,10 +36,6 @@ The GPU tests print the worst case they measured as a fraction of the bound (run
 breakpoints" quotes them."""
 import functools
 import os
-import re
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -48,10 +44,8 @@ from oracle import binding as ob
 from oracle import mp_ref, ref_golden
 
 from . import terrain_points as tp
+from .probe import GOLDEN, Probe, bits, load_fixture
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-GOLDEN = os.path.join(ROOT, "tests", "golden")
 U = 2.0 ** -53
 C_FUSED = 3.0        # analytic pieces the device may fuse: at most three roundings against exact terms
 C_FORCE = 20.0       # the roundings of the longest chain of force_core (the derivative column), counted in the docstring
@@ -65,22 +59,13 @@ def _mp():
     return mpmath.mp
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.int64)
-
-
 def _same_bits(a, b):
     """element-wise: the same double, taking +0 and -0 for different"""
-    return _bits(a) == _bits(b)
+    return bits(a) == bits(b)
 
 
-@functools.lru_cache(maxsize=None)
 def fixture(name):
-    d = np.load(os.path.join(GOLDEN, "refterrain_%s.npz" % name))
-    out = {k: d[k] for k in d.files}
-    for v in out.values():
-        v.flags.writeable = False
-    return out
+    return load_fixture("refterrain_%s" % name)
 
 
 def fixture_rows(key):
@@ -121,36 +106,8 @@ def reference_values(key):
     return fixture(name)["values"][rows]
 
 
-# ------------------------------------------------------------------ building and running the probe
-_dir = None
-
-
-def _workdir():
-    global _dir
-    if _dir is None:
-        import atexit
-        _dir = tempfile.mkdtemp(prefix="twr_terrain_probe_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
-
-
-def product_cxxflags():
-    """CXXFLAGS of towr_amd/csrc/Makefile, the flags kernels.o is compiled with"""
-    text = open(os.path.join(ROOT, "towr_amd", "csrc", "Makefile")).read()
-    m = re.search(r"^CXXFLAGS \?= (.*)$", text, re.M)
-    assert m, "CXXFLAGS ?= ... not found in towr_amd/csrc/Makefile"
-    return m.group(1).split()
-
-
-@functools.lru_cache(maxsize=None)
-def _build():
-    exe = os.path.join(_workdir(), "terrain_probe")
-    cmd = [HIPCC, "--offload-arch=gfx950"] + product_cxxflags() + ["-Wextra", "-I", os.path.join(ROOT, "towr_amd", "csrc"),
-                                                                    os.path.join(ROOT, "tests", "terrain_probe.hip"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "warning" not in (r.stdout + r.stderr), r.stdout + r.stderr
-    return exe
+# ------------------------------------------------------------------ running the probe (tests/probe.py)
+PROBE = Probe("terrain_probe")
 
 
 def _maps_block():
@@ -197,11 +154,7 @@ def _probe(mode):
     force_subset()[key] (force modes)"""
     data, groups = probe_input(mode)
     width = {"eval": 4, "force": 30, "force_g": 5}[mode]
-    fin, fout = os.path.join(_workdir(), mode + ".in"), os.path.join(_workdir(), mode + ".out")
-    data.tofile(fin)
-    r = subprocess.run([_build(), mode, fin, fout], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, "terrain_probe %s: exit %d\n%s%s" % (mode, r.returncode, r.stdout, r.stderr)
-    raw = np.fromfile(fout, dtype=np.float64).reshape(-1, width)
+    raw = PROBE.run(mode, data).reshape(-1, width)
     assert raw.shape[0] == sum(len(sel) for _, _, sel in groups)
     out, at = {}, 0
     for key, _mu, sel in groups:
@@ -217,14 +170,8 @@ def _probe(mode):
 def test_probe_compiles_without_warning():
     """(CPU tier) hipcc compiles and links the probe for gfx950 with the product's flags, without a GPU and without a warning;
     the input parser refuses a file whose counts do not add up before anything reaches a device"""
-    exe = _build()
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
-    data, _ = probe_input("eval")
-    fin = os.path.join(_workdir(), "short.in")
-    data[:-1].tofile(fin)
-    r = subprocess.run([exe, "eval", fin, os.path.join(_workdir(), "short.out")], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "truncated" in r.stderr
+    PROBE.refuses([], None, "usage")
+    PROBE.refuses(["eval"], probe_input("eval")[0][:-1], "truncated")
 
 
 @pytest.mark.parametrize("name", ref_golden.TERRAIN_FIXTURES)

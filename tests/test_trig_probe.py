@@ -21,15 +21,12 @@ The GPU tests print the worst case they measured (run with -s); DESIGN section 5
 import functools
 import math
 import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+from .probe import Probe
+
 SWITCH = 1.0e5               # sincos_fast hands |x| >= SWITCH to sincos_far
 K_FAST = 63661               # the largest k with k * pi/2 < SWITCH
 HARD_CASE = math.ldexp(6381956970095103.0, 797)   # the double closest to a multiple of pi/2 (relative to its size)
@@ -129,50 +126,21 @@ def _ulp_error(got, ref):
     return float(abs(mp.mpf(float(got)) - ref) / _ulp_of(ref))
 
 
-# ------------------------------------------------------------------ building and running the probe
-_dir = None
+# ------------------------------------------------------------------ running the probe (tests/probe.py)
+# (plain flags of its own, not the product's CXXFLAGS as the other probes: other flags would change what it measures)
+PROBE = Probe("trig_probe", flags=["-O3", "-std=c++17", "-Wall", "-Wextra"])
 
 
-def _workdir():
-    global _dir
-    if _dir is None:
-        import atexit
-        _dir = tempfile.mkdtemp(prefix="twr_trig_probe_")
-        atexit.register(shutil.rmtree, _dir, ignore_errors=True)
-    return _dir
-
-
-@functools.lru_cache(maxsize=None)
-def _build():
-    exe = os.path.join(_workdir(), "trig_probe")
-    cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "towr_amd", "csrc"),
-           os.path.join(ROOT, "tests", "trig_probe.hip"), "-o", exe]
-    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "warning" not in (r.stdout + r.stderr), r.stdout + r.stderr
-    return exe
-
-
-@functools.lru_cache(maxsize=None)
 def _probe(mode):
     """the probe's output for `mode` on this file's inputs, from a child process of its own"""
-    x = np.concatenate(list(sincos_inputs().values())) if mode == "sincos" else triple_inputs()[0]
-    fin, fout = os.path.join(_workdir(), mode + ".in"), os.path.join(_workdir(), mode + ".out")
-    np.ascontiguousarray(x, dtype=np.float64).tofile(fin)
-    r = subprocess.run([_build(), mode, fin, fout], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, "trig_probe %s: exit %d\n%s%s" % (mode, r.returncode, r.stdout, r.stderr)
-    out = np.fromfile(fout, dtype=np.float64)
-    out.flags.writeable = False
-    return out
+    return PROBE.run(mode, np.concatenate(list(sincos_inputs().values())) if mode == "sincos" else triple_inputs()[0])
 
 
 # ------------------------------------------------------------------ CPU tier
 def test_probe_compiles_without_warning():
     """(CPU tier) hipcc compiles and links the probe for gfx950 without a GPU and without a warning"""
-    exe = _build()
-    assert os.path.exists(exe)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 2 and "usage" in r.stderr
+    assert os.path.exists(PROBE.build())
+    PROBE.refuses([], None, "usage")
 
 
 def test_inputs_cover_every_family():

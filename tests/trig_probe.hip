@@ -7,12 +7,15 @@
 //   trig_probe rotquad IN OUT   IN: n x 3 Euler angles OUT: n x 4 x the same 15 values, four lanes per triple calling
 //                                                           rotation_quad(lane & 3, ...); every lane writes what it holds
 //
-// Exit status: 0 done, 2 usage / file error, 3 no HIP device, 4 a HIP call failed.
+// Exit status: see probe_host.h.
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "kernels/spline_math.h"
+
+#define PROBE_NAME "trig_probe"
+#include "probe_host.h"
 
 namespace {
 constexpr int ROT_VALUES = 15;
@@ -54,66 +57,38 @@ __global__ void rotquad_probe(const double* __restrict__ e, long n, double* __re
   twr::rotation_quad((int)(lane & 3), ang, ro);
   if (quad < n) put_rot(ro, out + ROT_VALUES * lane);
 }
-
-bool ok(hipError_t err, const char* what) {
-  if (err == hipSuccess) return true;
-  std::fprintf(stderr, "trig_probe: %s: %s\n", what, hipGetErrorString(err));
-  return false;
-}
 }  // namespace
 
 int main(int argc, char** argv) {
   if (argc != 4) {
     std::fprintf(stderr, "usage: trig_probe sincos|rot|rotquad IN OUT\n");
-    return 2;
+    return probe::REFUSED;
   }
   const bool m_sincos = !std::strcmp(argv[1], "sincos"), m_rot = !std::strcmp(argv[1], "rot"), m_quad = !std::strcmp(argv[1], "rotquad");
   if (!m_sincos && !m_rot && !m_quad) {
     std::fprintf(stderr, "trig_probe: unknown mode %s\n", argv[1]);
-    return 2;
+    return probe::REFUSED;
   }
-  std::vector<double> in;
-  {
-    std::FILE* f = std::fopen(argv[2], "rb");
-    if (!f) {
-      std::fprintf(stderr, "trig_probe: cannot read %s\n", argv[2]);
-      return 2;
-    }
-    double buf[4096];
-    size_t got;
-    while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) in.insert(in.end(), buf, buf + got);
-    std::fclose(f);
-  }
+  probe::Input in;
+  if (!in.read(argv[2])) return probe::REFUSED;
   const long per_item = m_sincos ? 1 : 3;
-  if (in.empty() || in.size() % per_item) {
-    std::fprintf(stderr, "trig_probe: %zu doubles in %s do not make whole inputs\n", in.size(), argv[2]);
-    return 2;
+  if (in.v.empty() || in.v.size() % per_item) {
+    std::fprintf(stderr, "trig_probe: %zu doubles in %s do not make whole inputs\n", in.v.size(), argv[2]);
+    return probe::REFUSED;
   }
-  const long n = (long)in.size() / per_item;
+  const long n = (long)in.v.size() / per_item;
   const long lanes = m_quad ? 4 * n : n;
-  const long n_out = m_sincos ? 2 * n : ROT_VALUES * lanes;
+  std::vector<double> out(m_sincos ? 2 * n : ROT_VALUES * lanes);
 
-  int devices = 0;
-  if (hipGetDeviceCount(&devices) != hipSuccess || devices == 0) {
-    std::fprintf(stderr, "trig_probe: no HIP device\n");
-    return 3;
-  }
+  if (!probe::have_device()) return probe::NO_DEVICE;
+  probe::Device dev;
   double *d_in = nullptr, *d_out = nullptr;
-  if (!ok(hipMalloc(&d_in, in.size() * sizeof(double)), "hipMalloc") || !ok(hipMalloc(&d_out, n_out * sizeof(double)), "hipMalloc")) return 4;
-  if (!ok(hipMemcpy(d_in, in.data(), in.size() * sizeof(double), hipMemcpyHostToDevice), "copy in")) return 4;
-  if (!ok(hipMemset(d_out, 0xFF, n_out * sizeof(double)), "hipMemset")) return 4;   // unwritten results read back as NaN
+  if (!dev.upload(&d_in, in.v) || !dev.results(&d_out, out.size())) return probe::HIP_FAILED;
   const unsigned blocks = (unsigned)((lanes + BLOCK - 1) / BLOCK);
   if (m_sincos) sincos_probe<<<blocks, BLOCK>>>(d_in, n, d_out);
   else if (m_rot) rot_probe<<<blocks, BLOCK>>>(d_in, n, d_out);
   else rotquad_probe<<<blocks, BLOCK>>>(d_in, n, d_out);
-  if (!ok(hipGetLastError(), "launch") || !ok(hipDeviceSynchronize(), "kernel")) return 4;
-  std::vector<double> out(n_out);
-  if (!ok(hipMemcpy(out.data(), d_out, n_out * sizeof(double), hipMemcpyDeviceToHost), "copy out")) return 4;
-  if (!ok(hipFree(d_in), "hipFree") || !ok(hipFree(d_out), "hipFree")) return 4;
-  std::FILE* f = std::fopen(argv[3], "wb");
-  if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size() || std::fclose(f) != 0) {
-    std::fprintf(stderr, "trig_probe: cannot write %s\n", argv[3]);
-    return 2;
-  }
-  return 0;
+  if (!probe::collect(out.data(), d_out, out.size()) || !dev.release()) return probe::HIP_FAILED;
+  return probe::write_out(argv[3], out);
 }
+
