@@ -449,7 +449,8 @@ int twr_batch_contact_plan(twr_batch* b, const double* d_x, double dt, double ti
  * first polygon with the smallest boost::geometry::distance to the foot's x, y (0 inside or on the boundary, else the
  * distance to the nearest boundary segment; the boundary points are walked as given, no closing edge is added -- what
  * boost does with the reference's uncorrected polygons); -1 for a foot in the air, for footstep states past d_counts[p]
- * and when there are no regions.
+ * and when there are no regions -- or when no distance is below DBL_MAX, the reference's start value: a NaN, infinite or
+ * overflowing (1e300) foothold over closed polygons.  Every product and sum is rounded on its own, as in the reference's build.
  *   regions:        n_regions x 7 doubles  [position x y z | orientation x y z w]   (plane_parameters)
  *   boundary_xy:    the outer_boundary points of all regions, x y each, region r = points [boundary_start[r],
  *                   boundary_start[r+1])

@@ -72,6 +72,10 @@ def lib():
         L.orc_planes_world_xy.restype = None
         L.orc_nearest_plane.argtypes = [_dp, _ip, C.c_int, C.c_double, C.c_double]
         L.orc_nearest_plane.restype = C.c_int
+        L.orc_ring_side.argtypes = [_dp, C.c_int, _dp, C.c_int, _ip]
+        L.orc_ring_side.restype = None
+        L.orc_ring_distance.argtypes = [_dp, C.c_int, _dp, C.c_int, _dp]
+        L.orc_ring_distance.restype = None
         L.orc_initial_guess_samples.restype = None
         L.orc_time_callbacks.argtypes = [C.c_void_p, _dp, C.c_int]
         L.orc_time_callbacks.restype = C.c_double
@@ -312,6 +316,24 @@ def planes_world_xy(regions, local_xy, start):
     start = np.ascontiguousarray(start, dtype=np.int32)
     out = np.zeros_like(local_xy)
     lib().orc_planes_world_xy(_d(regions), _d(local_xy), start.ctypes.data_as(C.POINTER(C.c_int)), len(regions), _d(out))
+    return out
+
+
+def ring_side(ring_xy, points):
+    """covered_by of bg::distance(point, polygon) on one ring (n, 2) at points (k, 2): 1 inside, 0 on the boundary, -1 outside"""
+    ring = np.ascontiguousarray(ring_xy, dtype=np.float64).reshape(-1, 2)
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros(len(pts), dtype=np.int32)
+    lib().orc_ring_side(_d(ring), len(ring), _d(pts), len(pts), _i(out))
+    return out
+
+
+def ring_distance(ring_xy, points):
+    """the distance from points (k, 2) to the consecutive points of one ring (n, 2), whether they are inside or not"""
+    ring = np.ascontiguousarray(ring_xy, dtype=np.float64).reshape(-1, 2)
+    pts = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 2)
+    out = np.zeros(len(pts))
+    lib().orc_ring_distance(_d(ring), len(ring), _d(pts), len(pts), _d(out))
     return out
 
 

@@ -49,6 +49,9 @@
 //                        PhaseDurations::SetVariables + ConvertPhaseToPolyDurations on given schedule variables, see
 //                        SegmentPoints() below (oracle/ref_golden.py --segments records it as tests/golden/refsegment.npz);
 //                        exit code 5 for a time the lookup is not defined for
+//   ref_dump --plane-points IN OUT   PlanarRegionsToPolygons and NearestPlaneLookup::GetNearestPlaneIndex on given regions and
+//                        points, with bg::distance per region, see PlanePoints() below (oracle/ref_golden.py --planes records
+//                        it as tests/golden/refplane.npz)
 #include <ifopt/problem.h>
 #include <towr/initialization/gait_generator.h>
 #include <towr/nlp_formulation.h>
@@ -279,9 +282,103 @@ static int SegmentPoints(int argc, char** argv) {
   return 0;
 }
 
+// ref_dump --plane-points IN OUT: the nearest-plane lookup alone, no NLP.  IN holds raw doubles: the number of scenes; per scene
+// the number of regions, per region position x y z, orientation x y z w, the number k of boundary points and their k local
+// (x, y), then the number of query points and their (x, y).  A scene becomes a convex_plane_decomposition_msgs::PlanarTerrain.
+// OUT per scene: the world (x, y) of every boundary point as fpowr::PlanarRegionsToPolygons made them, region after region;
+// per query point fpowr::NearestPlaneLookup::GetNearestPlaneIndex; per query point and region bg::distance(point, polygon)
+// (point-major).  Exit code 4 where the build has the fpowr extractors compiled out.
+static int PlanePoints(int argc, char** argv) {
+  if (argc != 4) {
+    std::fprintf(stderr, "usage: ref_dump --plane-points IN OUT\n");
+    return 2;
+  }
+#ifdef TWR_REF_EXTRACTORS
+  std::vector<double> in;
+  {
+    std::FILE* f = std::fopen(argv[2], "rb");
+    if (!f) {
+      std::fprintf(stderr, "cannot read %s\n", argv[2]);
+      return 2;
+    }
+    double buf[4096];
+    size_t got;
+    while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) in.insert(in.end(), buf, buf + got);
+    std::fclose(f);
+  }
+  size_t at = 0;
+  auto have = [&](size_t k) { return at + k <= in.size(); };
+  auto bad = [&](const char* what) {
+    std::fprintf(stderr, "%s: %s\n", argv[2], what);
+    return 2;
+  };
+  if (!have(1)) return bad("empty");
+  const long n_scenes = static_cast<long>(in[at++]);
+  std::vector<double> out;
+  size_t n_pairs = 0;
+  for (long s = 0; s < n_scenes; ++s) {
+    if (!have(1)) return bad("truncated scene");
+    const long n_regions = static_cast<long>(in[at++]);
+    if (n_regions < 0) return bad("region count");
+    convex_plane_decomposition_msgs::PlanarTerrain terrain;
+    for (long r = 0; r < n_regions; ++r) {
+      if (!have(8)) return bad("truncated region");
+      convex_plane_decomposition_msgs::PlanarRegion region;
+      auto& pp = region.plane_parameters;
+      pp.position.x = in[at], pp.position.y = in[at + 1], pp.position.z = in[at + 2];
+      pp.orientation.x = in[at + 3], pp.orientation.y = in[at + 4], pp.orientation.z = in[at + 5], pp.orientation.w = in[at + 6];
+      const long k = static_cast<long>(in[at + 7]);
+      at += 8;
+      if (k < 0 || !have(2 * static_cast<size_t>(k))) return bad("truncated boundary");
+      for (long i = 0; i < k; ++i, at += 2) {
+        convex_plane_decomposition_msgs::Point2d pt;
+        pt.x = in[at];
+        pt.y = in[at + 1];
+        if (static_cast<double>(pt.x) != in[at] || static_cast<double>(pt.y) != in[at + 1])
+          return bad("a boundary point the message's number format does not hold exactly");
+        region.boundary.outer_boundary.points.push_back(pt);
+      }
+      terrain.planarRegions.push_back(region);
+    }
+    if (!have(1)) return bad("no points");
+    const long n_points = static_cast<long>(in[at++]);
+    if (n_points < 0 || !have(2 * static_cast<size_t>(n_points))) return bad("truncated points");
+    const std::vector<polygon_t> polygons = fpowr::PlanarRegionsToPolygons(terrain);
+    for (const polygon_t& poly : polygons)
+      for (const point_t& p : poly.outer()) {
+        out.push_back(p.x());
+        out.push_back(p.y());
+      }
+    const fpowr::NearestPlaneLookup lookup(terrain);
+    Eigen::VectorXd position(2);
+    for (long k = 0; k < n_points; ++k) {
+      position(0) = in[at + 2 * k];
+      position(1) = in[at + 2 * k + 1];
+      out.push_back(lookup.GetNearestPlaneIndex(position));
+    }
+    for (long k = 0; k < n_points; ++k)
+      for (const polygon_t& poly : polygons) out.push_back(bg::distance(point_t(in[at + 2 * k], in[at + 2 * k + 1]), poly));
+    n_pairs += static_cast<size_t>(n_points) * polygons.size();
+    at += 2 * static_cast<size_t>(n_points);
+  }
+  if (at != in.size()) return bad("trailing data");
+  std::FILE* f = std::fopen(argv[3], "wb");
+  if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size() || std::fclose(f) != 0) {
+    std::fprintf(stderr, "cannot write %s\n", argv[3]);
+    return 2;
+  }
+  std::printf("ref_dump: %ld plane scenes, %zu (ring, point) pairs\n", n_scenes, n_pairs);
+  return 0;
+#else
+  std::fprintf(stderr, "--plane-points: this build has the fpowr extractors compiled out\n");
+  return 4;
+#endif
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--terrain-points") return TerrainPoints(argc, argv);
   if (argc >= 2 && std::string(argv[1]) == "--segment-points") return SegmentPoints(argc, argv);
+  if (argc >= 2 && std::string(argv[1]) == "--plane-points") return PlanePoints(argc, argv);
   if (argc < 9) {
     std::fprintf(stderr, "usage: see the header of ref_dump.cc\n");
     return 2;

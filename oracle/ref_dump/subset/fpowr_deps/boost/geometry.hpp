@@ -105,7 +105,7 @@ double squared_to_edge(const Point& a, const Point& b, const Point& p) {
   const double vx = b.x() - a.x(), vy = b.y() - a.y(), wx = p.x() - a.x(), wy = p.y() - a.y();
   const double c1 = wx * vx + wy * vy;
   double qx = a.x(), qy = a.y();
-  if (c1 > 0.0) {
+  if (!(c1 <= 0.0)) {   // (as published: `c1 <= 0` takes a, so a NaN c1 -- an infinite coordinate -- goes on to the projection)
     const double c2 = vx * vx + vy * vy;
     if (c2 <= c1) {
       qx = b.x();

@@ -447,6 +447,43 @@ def record_segments(workdir):
     return path, os.path.getsize(path), len(out["point_t"]), len(out["case_head"])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/golden/refplane.npz: fpowr::PlanarRegionsToPolygons and NearestPlaneLookup::GetNearestPlaneIndex (ref_dump
+# --plane-points) on the scenes of tests/plane_points.py.  What it pins: the reference's own loop -- the DBL_MAX start, the
+# strict `<`, -1 where nothing is below DBL_MAX, the first of equal distances wins -- and the tf transform of the boundary
+# points (quaternion -> matrix -> world), both compiled from the reference's header.  The polygon geometry under them
+# (bg::distance: covered_by and the distance to the ring) is the stand-in's of oracle/ref_dump/subset/fpowr_deps/boost, written
+# from Boost 1.71's published algorithm: Boost itself is not executed.  The file holds per scene its regions and local rings
+# (scene_region_start, regions, ring_start, local_xy), world_xy (the reference's polygons), the query points (scene_point_start,
+# points) with index (int8) per point, and distance per (point, region) point-major (scene_pair_start, distance).
+# tests/test_plane_probe.py regenerates the scenes and compares the oracle (CPU) and the device (GPU); tests/test_planes_edges.py
+# runs them through twr_batch_contact_planes.
+def compute_planes(workdir):
+    from oracle import ref_run
+    from tests import plane_points as pp
+
+    scenes = pp.scenes()
+    res = ref_run.plane_points(os.path.join(workdir, "planes"), [(s["regions"], s["rings"], s["points"]) for s in scenes])
+    starts = lambda counts: np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
+    rings = [r for s in scenes for r in s["rings"]]
+    index = np.concatenate([r[1] for r in res])
+    assert index.min() >= -1 and index.max() < 127
+    return dict(scene_region_start=starts([len(s["rings"]) for s in scenes]),
+                regions=np.concatenate([s["regions"].reshape(-1, 7) for s in scenes]), ring_start=starts([len(r) for r in rings]),
+                local_xy=np.concatenate([r.reshape(-1, 2) for r in rings]).astype(np.float32),
+                world_xy=np.concatenate([w.reshape(-1, 2) for r in res for w in r[0]] + [np.zeros((0, 2))]),
+                scene_point_start=starts([len(s["points"]) for s in scenes]), points=np.concatenate([s["points"] for s in scenes]),
+                index=index.astype(np.int8), scene_pair_start=starts([r[2].size for r in res]),
+                distance=np.concatenate([r[2].ravel() for r in res]), reference_deps=ref_run.deps())
+
+
+def record_planes(workdir):
+    out = compute_planes(workdir)
+    path = os.path.join(GOLDEN, "refplane.npz")
+    save_npz_lzma(path, out)
+    return path, os.path.getsize(path), len(out["points"]), len(out["distance"])
+
+
 def main(names):
     from oracle import ref_run
 
@@ -465,6 +502,11 @@ def main(names):
         with tempfile.TemporaryDirectory() as work:
             path, size, n, k = record_segments(work)
         print("%-40s points=%6d duration cases=%3d %8d bytes" % (os.path.basename(path), n, k, size))
+        return
+    if names and names[0] == "--planes":
+        with tempfile.TemporaryDirectory() as work:
+            path, size, n, k = record_planes(work)
+        print("%-40s points=%6d (ring, point) pairs=%6d %8d bytes" % (os.path.basename(path), n, k, size))
         return
     if names and names[0] == "--traj":
         with tempfile.TemporaryDirectory() as work:

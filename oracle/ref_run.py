@@ -191,6 +191,43 @@ def segment_durations(prefix, cases, timeout=600):
     return res
 
 
+def plane_points(prefix, scenes, timeout=600):
+    """ref_dump --plane-points: per scene (regions (n, 7) [position xyz, orientation xyzw], local boundary rings [(k, 2)], query
+    points (m, 2)) the reference's (world rings as PlanarRegionsToPolygons made them [(k, 2)], GetNearestPlaneIndex per point (m,)
+    int32, bg::distance per point and region (m, n))."""
+    parts = [[float(len(scenes))]]
+    for regions, rings, points in scenes:
+        regions = np.asarray(regions, dtype=np.float64).reshape(-1, 7)
+        assert len(regions) == len(rings)
+        parts.append([float(len(rings))])
+        for pose, ring in zip(regions, rings):
+            ring = np.asarray(ring, dtype=np.float64).reshape(-1, 2)
+            parts += [pose, [float(len(ring))], ring.ravel()]
+        points = np.asarray(points, dtype=np.float64).reshape(-1, 2)
+        parts += [[float(len(points))], points.ravel()]
+    np.concatenate([np.asarray(p, dtype=np.float64) for p in parts]).tofile(prefix + "_planes_in.bin")
+    cmd = [os.path.join(REF, "ref_dump"), "--plane-points", prefix + "_planes_in.bin", prefix + "_planes_out.bin"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    if r.returncode != 0:
+        raise RuntimeError("ref_dump exit %d: %s\n%s" % (r.returncode, " ".join(cmd), (r.stdout + r.stderr)[-2000:]))
+    out = np.fromfile(prefix + "_planes_out.bin", dtype=np.float64)
+    res, at = [], 0
+    for regions, rings, points in scenes:
+        world = []
+        for ring in rings:
+            k = len(np.asarray(ring).reshape(-1, 2))
+            world.append(out[at:at + 2 * k].reshape(k, 2).copy())
+            at += 2 * k
+        m, n = len(np.asarray(points).reshape(-1, 2)), len(rings)
+        index = out[at:at + m].astype(np.int32)
+        assert np.array_equal(index, out[at:at + m])
+        at += m
+        res.append((world, index, out[at:at + m * n].reshape(m, n).copy()))
+        at += m * n
+    assert at == out.size, (at, out.size)
+    return res
+
+
 def case_args(case):
     """(args, kwargs) of command() / run() for a tests.common.Case (every field a Case can set reaches the reference)."""
     p = case.params

@@ -1861,9 +1861,10 @@ int RingSide(const double* xy, int n, double px, double py) {
       int side;
       if (c == 1 || c == -1) {
         const double sey = eq1 ? s1y : s2y;
-        side = py == sey ? 0 : (py < sey ? -c : c);
+        side = py == sey ? 0 : (py > sey ? c : -c);   // (a NaN py is neither on the end nor above it)
       } else {
         const double det = (s2x - s1x) * (py - s1y) - (s2y - s1y) * (px - s1x);   // side_by_triangle: > 0 left
+        if (det != det) continue;                     // a NaN py: neither on the edge nor on a side of it
         side = det > 0 ? 1 : (det < 0 ? -1 : 0);
       }
       if (side == 0) return 0;
@@ -1893,6 +1894,15 @@ double RingDistance(const double* xy, int n, double px, double py) {   // point_
   return std::sqrt(best);
 }
 }  // namespace
+// the two parts of bg::distance(point, polygon) on one ring at n_points points (x, y), for the tests that compare them per ring:
+// covered_by's answer (1 inside, 0 on the boundary, -1 outside) and the distance to the ring's consecutive points, which
+// bg::distance takes only where the first is -1
+void orc_ring_side(const double* xy, int n, const double* points, int n_points, int* side) {
+  for (int k = 0; k < n_points; ++k) side[k] = RingSide(xy, n, points[2 * k], points[2 * k + 1]);
+}
+void orc_ring_distance(const double* xy, int n, const double* points, int n_points, double* distance) {
+  for (int k = 0; k < n_points; ++k) distance[k] = RingDistance(xy, n, points[2 * k], points[2 * k + 1]);
+}
 // NearestPlaneLookup::GetNearestPlaneIndex (:62-84): first polygon with the smallest bg::distance, -1 without polygons
 int orc_nearest_plane(const double* world_xy, const int* start, int n_polys, double px, double py) {
   double min_distance = std::numeric_limits<double>::max();

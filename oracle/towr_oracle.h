@@ -91,6 +91,9 @@ int orc_sample_trajectory(orc_problem*, const double* x, double dt, double* out,
 // boost::geometry restated from their published algorithms (notes in towr_oracle.cc)
 void orc_planes_world_xy(const double* regions, const double* local_xy, const int* start, int n, double* out_xy);
 int orc_nearest_plane(const double* world_xy, const int* start, int n_polys, double px, double py);
+// per ring and point: covered_by (1 inside, 0 boundary, -1 outside) and the distance to the ring itself (n_points points x, y)
+void orc_ring_side(const double* xy, int n, const double* points, int n_points, int* side);
+void orc_ring_distance(const double* xy, int n, const double* points, int n_points, double* distance);
 
 // fpowr::ExtractInitialGuess (initial_guess_extractor.h:17-34) at the given times: 49 doubles per time
 // [t | state 12 | controls 36], layout in towr_oracle.cc
