@@ -246,6 +246,19 @@ int twr_structure_initial_guess(const twr_structure* s, const double init_base_l
 int twr_structure_variable_bounds(const twr_structure* s, const double init_base[12], const double final_base[12],
                                   const double* init_ee_pos /* n_ee*3 */, double* lower /* n_vars */,
                                   double* upper /* n_vars */);
+/* A planning request as ONE record of TWR_START_REC doubles -- what twr_structure_initial_guess and twr_structure_variable_bounds
+ * take as five arrays:
+ *   [0, 12)   init_base   {lin pos, lin vel, ang pos, ang vel}
+ *   [12, 24)  final_base  (the same order)
+ *   [24, 36)  init_ee_pos, 3 per end-effector (entries of feet the structure does not have are not read)
+ * twr_structure_start_host gives x = twr_structure_initial_guess and lower / upper = twr_structure_variable_bounds of that
+ * request, bit for bit, from the structure's START TABLE: one 8-byte record per variable that names where its value comes from
+ * (a node of a spline -- the later one where two share the variable --, a phase duration, or zero) and where its bounds come
+ * from (a slot of the request, the phase-duration box [0.2, 1.0], or ifopt::NoBound).  It is the host executor of the table
+ * twr_batch_start runs on the device; each of x / lower / upper may be NULL. */
+#define TWR_START_REC 36
+int twr_structure_start_host(const twr_structure* s, const double request[TWR_START_REC], double* x /* n_vars or NULL */,
+                             double* lower /* n_vars or NULL */, double* upper /* n_vars or NULL */);
 
 /* Upload the tables of a batch: problem p uses structs[struct_of_problem[p]].  device is the HIP
  * device ordinal of this process (one process per GPU).  All structures of one batch must have the same
@@ -315,9 +328,11 @@ int twr_batch_layout(const twr_batch* b, int64_t* x_off, int64_t* g_off, int64_t
  *                                     float[size_x * size_y], column-major, circular with start index (start_x, start_y) as in
  *                                     twr_terrain_grid_map_update, and the centre (pos_x, pos_y).  One kernel launch and nothing
  *                                     else: asynchronous on hip_stream, capturable in a hipGraph.  d_elevation is only read, and
- *                                     read when the launch runs: keep it unchanged until then.  The HOST handle is NOT touched: a
- *                                     caller that also uses the host-side structure calls (twr_structure_initial_guess,
- *                                     twr_structure_variable_bounds) on the new map calls twr_terrain_grid_map_update as well.
+ *                                     read when the launch runs: keep it unchanged until then.  The HOST handle is NOT touched:
+ *                                     twr_batch_start (below) makes x0 and the variable bounds of a request from the new map on
+ *                                     the device; only a caller that also uses the host-side structure calls
+ *                                     (twr_structure_initial_guess, twr_structure_variable_bounds, twr_structure_start_host) on
+ *                                     the new map calls twr_terrain_grid_map_update as well.
  * Both count as a call on the batch: at most ONE update or evaluation of a batch in flight at a time (serialise them on one
  * stream; an evaluation enqueued before the update reads the old map, one enqueued after it the new one).  Device scope and sticky
  * error as twr_batch_eval.  TWR_ERR_INVALID, with twr_last_error naming the argument, before any device is touched: b, g or
@@ -326,6 +341,28 @@ int twr_batch_layout(const twr_batch* b, int64_t* x_off, int64_t* g_off, int64_t
 int twr_batch_grid_map_sync(twr_batch* b, const twr_terrain_grid* g, void* hip_stream);
 int twr_batch_grid_map_update_device(twr_batch* b, const twr_terrain_grid* g, const float* d_elevation, int start_x, int start_y,
                                      double pos_x, double pos_y, void* hip_stream);
+/* Start of a planning request for the whole batch, on the device: x0 (twr_structure_initial_guess) and x_l / x_u
+ * (twr_structure_variable_bounds) of every problem from request records in device memory (TWR_START_REC doubles each, layout
+ * above).  Problem p reads the record at d_request + p * request_stride; request_stride = 0: one record for all problems.
+ * The outputs are in the layout of twr_batch_layout (x_off); each of d_x / d_xlo / d_xup may be NULL, not all three.
+ * The terrain heights of the guess (the goal and every final foothold) are evaluated through the batch's tables, i.e. on the
+ * map the batch holds NOW: after twr_batch_grid_map_update_device that is the new map, without the host handle.
+ * Results: a request whose final yaw is 0 gives the bits of the host functions.  With a turn the device's sine and cosine are
+ * its own (within 1.5 ulp of libm's), so the variables that descend from a final foothold (ee-motion positions and
+ * velocities) differ from the host's by rounding, everything else is bit-identical.  A non-finite or huge entry of a record
+ * reaches the variables that are made from it and nothing else (no index is computed from a request without a range check).
+ *   twr_batch_reserve_start: plans the call and uploads the start tables of the batch's structures (byte-identical ones once)
+ *                            and the work list, into device memory of their own (twr_batch_table_bytes does not count it).
+ *   twr_batch_start:         ONE kernel launch, asynchronous on hip_stream, no host synchronisation.  After
+ *                            twr_batch_reserve_start it allocates nothing and is capturable in a hipGraph; without it the
+ *                            first call reserves (allocates and uploads) and is NOT capturable.
+ * twr_batch_start counts as a call on the batch: at most ONE update, start or evaluation of a batch in flight at a time (a map
+ * update enqueued before it is seen, one enqueued after it is not).  Device scope and sticky error as twr_batch_eval.
+ * TWR_ERR_INVALID, with twr_last_error naming the argument, before any device is touched: b or d_request NULL, all three
+ * outputs NULL, a request_stride that is neither 0 nor >= TWR_START_REC, a pointer that is not 8-byte aligned. */
+int twr_batch_reserve_start(twr_batch* b);
+int twr_batch_start(twr_batch* b, const double* d_request, int64_t request_stride, double* d_x, double* d_xlo, double* d_xup,
+                    void* hip_stream);
 
 /* One full NLP callback for every problem of the batch, device pointers in, device pointers out:
  *   ifopt::Problem::EvaluateConstraints(x)        -> g     (TWR_EVAL_VALUES)

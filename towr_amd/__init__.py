@@ -160,6 +160,9 @@ def lib():
         L.twr_structure_bounds.argtypes = [C.c_void_p, _dp, _dp]
         L.twr_structure_initial_guess.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp]
         L.twr_structure_variable_bounds.argtypes = [C.c_void_p, _dp, _dp, _dp, _dp, _dp]
+        L.twr_structure_start_host.argtypes = [C.c_void_p, _dp, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.twr_batch_reserve_start.argtypes = [C.c_void_p]
+        L.twr_batch_start.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.twr_batch_create.argtypes = [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_int32), C.c_int, C.c_int,
                                        C.POINTER(C.c_void_p)]
         L.twr_batch_destroy.argtypes = [C.c_void_p]
@@ -305,6 +308,22 @@ def schedule(phase_durations, contact_at_start):
         for i, d in enumerate(pd):
             s.phase_durations[e][i] = float(d)
     return s
+
+
+START_REC = 36  # TWR_START_REC
+
+
+def start_request(init_base, final_base, ee_pos0):
+    """The request record of twr_structure_start_host / twr_batch_start: START_REC doubles [init_base (12: lin p, lin v, ang p,
+    ang v) | final_base (12) | initial foot positions (3 per end-effector, zero padded to four feet)]."""
+    a = np.asarray(init_base, dtype=np.float64).reshape(-1)
+    b = np.asarray(final_base, dtype=np.float64).reshape(-1)
+    ee = np.asarray(ee_pos0, dtype=np.float64).reshape(-1)
+    if a.size != 12 or b.size != 12 or ee.size % 3 or ee.size > 12:
+        raise TowrError("start_request: init_base and final_base are 12 doubles, ee_pos0 at most four feet of 3")
+    rec = np.zeros(START_REC)
+    rec[0:12], rec[12:24], rec[24:24 + ee.size] = a, b, ee
+    return rec
 
 
 class TerrainGrid:
@@ -523,6 +542,15 @@ class Structure:
         _check(lib().twr_structure_variable_bounds(self._h, _d(a), _d(b), _d(ee), _d(lo), _d(up)))
         return lo, up
 
+    def start_host(self, request):
+        """twr_structure_start_host: (x0, x_l, x_u) of one request record (start_request) from the structure's start table --
+        the bits of initial_guess and variable_bounds; the host executor of Batch.start_device."""
+        rq = np.ascontiguousarray(request, dtype=np.float64).reshape(-1)
+        assert rq.size == START_REC
+        x, lo, up = np.zeros(self.n), np.zeros(self.n), np.zeros(self.n)
+        _check(lib().twr_structure_start_host(self._h, _d(rq), x.ctypes.data, lo.ctypes.data, up.ctypes.data))
+        return x, lo, up
+
 
 class Batch:
     """Device tables of a batch of candidates; problem p uses structures[struct_of_problem[p]]."""
@@ -577,6 +605,18 @@ class Batch:
         _check(lib().twr_batch_grid_map_update_device(self._h, gm._h, C.c_void_p(int(d_elevation)), int(start_index[0]),
                                                       int(start_index[1]), float(position[0]), float(position[1]),
                                                       C.c_void_p(stream or 0)))
+
+    def reserve_start(self):
+        """twr_batch_reserve_start: plans start_device and uploads its tables; afterwards start_device allocates nothing and
+        can be captured in a graph."""
+        _check(lib().twr_batch_reserve_start(self._h))
+
+    def start_device(self, d_request, request_stride, d_x, d_xlo, d_xup, stream=0):
+        """twr_batch_start: x0 / x_l / x_u of every problem (layout x_off; raw device pointers, 0 leaves one out) from request
+        records on the device (start_request; problem p reads d_request + p * request_stride doubles, stride 0: one record
+        for all).  One launch, asynchronous on `stream`; the terrain is the map the batch holds now."""
+        _check(lib().twr_batch_start(self._h, C.c_void_p(int(d_request)), int(request_stride), C.c_void_p(int(d_x)),
+                                     C.c_void_p(int(d_xlo)), C.c_void_p(int(d_xup)), C.c_void_p(stream or 0)))
 
     def table_bytes(self):
         """Device bytes of the batch's tables: resident, layout tables of the dynamic set as built, and what is left of them

@@ -518,6 +518,41 @@ BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vec
   return b;
 }
 
+// ---------------------------------------------------------------- twr_batch_start (start_table.h)
+StartPlan PlanStart(const std::vector<const std::vector<char>*>& table_of_struct, const std::vector<int32_t>& struct_of_problem,
+                    const std::vector<int64_t>& x_off, const std::vector<uint64_t>& blob_of_problem) {
+  const size_t n_problems = struct_of_problem.size();
+  if (x_off.size() != n_problems + 1 || blob_of_problem.size() != n_problems) throw std::runtime_error("PlanStart: list sizes");
+  StartPlan plan;
+  // every distinct table once, on a 256-byte line (a bucket per size and first words: equality is decided by memcmp)
+  std::unordered_map<std::string, uint64_t> placed;
+  std::vector<uint64_t> off_of_struct(table_of_struct.size());
+  for (size_t i = 0; i < table_of_struct.size(); ++i) {
+    if (!table_of_struct[i] || table_of_struct[i]->size() < sizeof(StartHeader)) throw std::runtime_error("PlanStart: structure without a start table");
+    const std::vector<char>& t = *table_of_struct[i];
+    plan.bytes_built += (int64_t)t.size();
+    const auto at = placed.emplace(std::string(t.data(), t.size()), (uint64_t)plan.tables.size());
+    if (at.second) {
+      plan.tables.insert(plan.tables.end(), t.begin(), t.end());
+      plan.tables.resize((plan.tables.size() + 255) / 256 * 256, 0);
+      plan.bytes_distinct += (int64_t)t.size();
+    }
+    off_of_struct[i] = at.first->second;
+  }
+  for (size_t p = 0; p < n_problems; ++p) {
+    const int32_t s = struct_of_problem[p];
+    if (s < 0 || (size_t)s >= table_of_struct.size()) throw std::runtime_error("PlanStart: structure index out of range");
+    const StartHeader& h = *reinterpret_cast<const StartHeader*>(plan.tables.data() + off_of_struct[s]);
+    if (x_off[p + 1] - x_off[p] != h.n_vars) throw std::runtime_error("PlanStart: x offsets do not match the structure's variables");
+    for (int v0 = 0; v0 < h.n_vars; v0 += kStartItem)
+      plan.work.push_back({off_of_struct[s], blob_of_problem[p], x_off[p], v0, std::min(kStartItem, h.n_vars - v0), (int32_t)p, 0});
+  }
+  return plan;
+}
+void StartPlan::Place(uint64_t base) {
+  for (StartWork& w : work) w.table += base;
+}
+
 EvalCounts CountsOf(const BatchPlan& P) {
   const BatchPlan::Lists& L = P.lists;
   EvalCounts c;

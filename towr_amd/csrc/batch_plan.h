@@ -91,6 +91,20 @@ std::vector<size_t> BlobOffsets(const std::vector<const Structure*>& structs);  
 BatchPlan PlanBatch(const std::vector<const Structure*>& structs, const std::vector<int32_t>& struct_of_problem,
                     const std::vector<uint64_t>& blob, int n_cu, int64_t cache_bytes, int force_chunk);
 
+// twr_batch_start planned on the host (no HIP): the start tables of the batch's structures, byte-identical ones stored once,
+// each on a 256-byte line of `tables` (device memory of its own: the blobs and the arena are not touched), and the work list --
+// per problem, in problem order, its variables cut into runs of kStartItem; no item crosses a problem.  The list depends on the
+// structures (table_of_struct[i]: Structure::start_table of structure i), the x offsets and the blob addresses only.
+// StartWork::table holds the byte offset inside `tables` until Place(device address of tables).
+struct StartPlan {
+  std::vector<char> tables;
+  std::vector<StartWork> work;
+  int64_t bytes_built = 0, bytes_distinct = 0;   // start tables as the structures hold them / as stored
+  void Place(uint64_t base);
+};
+StartPlan PlanStart(const std::vector<const std::vector<char>*>& table_of_struct, const std::vector<int32_t>& struct_of_problem,
+                    const std::vector<int64_t>& x_off, const std::vector<uint64_t>& blob_of_problem);
+
 // The shape of one call, assembled in ONE place for twr_batch_eval, the scoring entry points and twr_batch_eval_plan (and the
 // host checks of the plans): the list counts as the batch holds them on the device, the policy PlanBatch decided, the request.
 // `flags`: TWR_EVAL_* bits of an evaluation, or kEvalScores (| kEvalBest).  A scoring request records no per-kernel events and

@@ -405,6 +405,16 @@ int twr_structure_variable_bounds(const twr_structure* s, const double init_base
   }
 }
 
+int twr_structure_start_host(const twr_structure* s, const double request[TWR_START_REC], double* x, double* lower, double* upper) {
+  if (!s || !request) return fail(TWR_ERR_INVALID, "null argument");
+  try {
+    s->s.StartHost(request, x, lower, upper);
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_INVALID, e.what());
+  }
+}
+
 int twr_batch_create(const twr_structure* const* structs, int n_structs, const int32_t* struct_of_problem,
                      int n_problems, int device, twr_batch** out) {
   if (!structs || !struct_of_problem || !out || n_structs < 1 || n_problems < 1)
@@ -423,6 +433,8 @@ int twr_batch_create(const twr_structure* const* structs, int n_structs, const i
     b->device = device;
     b->n_problems = n_problems;
     b->n_ee = sp[0]->n_ee;
+    for (const twr::Structure* s : sp) b->start_tables.push_back(s->start_table);   // (twr_batch_reserve_start)
+    b->struct_of_problem.assign(struct_of_problem, struct_of_problem + n_problems);
     // the arena; every distinct gridded terrain is uploaded once and its address patched into the headers that use it
     const std::vector<size_t> blob_off = twr::BlobOffsets(sp);
     b->arena = dev_alloc<void>(blob_off[n_structs]);
@@ -591,6 +603,56 @@ int twr_batch_grid_map_update_device(twr_batch* b, const twr_terrain_grid* g, co
   DeviceScope on(b->device);
   if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
   return update_held_map(b, q, d_elevation, start_x, start_y, pos_x, pos_y, static_cast<hipStream_t>(hip_stream));
+}
+
+namespace {
+// Plans and uploads what twr_batch_start reads (once; under the caller's DeviceScope).  Throws.
+void reserve_start(twr_batch& b) {
+  if (b.start_work.d) return;
+  std::vector<const std::vector<char>*> tables;
+  for (const auto& t : b.start_tables) tables.push_back(t.get());
+  twr::StartPlan plan = twr::PlanStart(tables, b.struct_of_problem, b.plan.x_off, b.plan.blob_of_problem);
+  DevPtr<char> dev = dev_alloc<char>(plan.tables.size());
+  TWR_HIP(hipMemcpy(dev.get(), plan.tables.data(), plan.tables.size(), hipMemcpyHostToDevice));
+  plan.Place(reinterpret_cast<uint64_t>(dev.get()));
+  DevList<twr::StartWork> work = upload(plan.work);
+  b.start_dev = std::move(dev);
+  b.start_work = std::move(work);
+}
+}  // namespace
+
+int twr_batch_reserve_start(twr_batch* b) {
+  if (!b) return fail(TWR_ERR_INVALID, "b is NULL");
+  try {
+    DeviceScope on(b->device);
+    TWR_HIP(on.status);
+    reserve_start(*b);
+    return TWR_OK;
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+int twr_batch_start(twr_batch* b, const double* d_request, int64_t request_stride, double* d_x, double* d_xlo, double* d_xup,
+                    void* hip_stream) {
+  if (!b) return fail(TWR_ERR_INVALID, "b is NULL");
+  if (!d_request) return fail(TWR_ERR_INVALID, "d_request is NULL");
+  if (!d_x && !d_xlo && !d_xup) return fail(TWR_ERR_INVALID, "d_x, d_xlo and d_xup are all NULL");
+  if (request_stride != 0 && request_stride < TWR_START_REC)
+    return fail(TWR_ERR_INVALID, "request_stride must be 0 (one record for all problems) or >= TWR_START_REC");
+  if (misaligned({d_request})) return fail(TWR_ERR_INVALID, "d_request is not 8-byte aligned");
+  if (misaligned({d_x})) return fail(TWR_ERR_INVALID, "d_x is not 8-byte aligned");
+  if (misaligned({d_xlo})) return fail(TWR_ERR_INVALID, "d_xlo is not 8-byte aligned");
+  if (misaligned({d_xup})) return fail(TWR_ERR_INVALID, "d_xup is not 8-byte aligned");
+  try {
+    DeviceScope on(b->device);
+    TWR_HIP(on.status);
+    reserve_start(*b);   // (a no-op after twr_batch_reserve_start; otherwise the first call allocates and uploads)
+    return launched(twr::launch_start(b->start_work.d.get(), b->start_work.n, d_request, request_stride, d_x, d_xlo, d_xup,
+                                      static_cast<hipStream_t>(hip_stream)));
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
 }
 
 // Tuning knobs of the launches (include/towr_amd.h): a TUNING=1 build reads them on every evaluation; the default build reads

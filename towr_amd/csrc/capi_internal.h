@@ -119,6 +119,13 @@ struct twr_batch {
   DevList<twr::SampleWork> gwork;            // work list of the last twr_batch_initial_guess call (cached per count / stride)
   int gwork_times = -1;
   int64_t gwork_stride = -1;
+  // twr_batch_start: the start tables of the batch's structures as the structures hold them (shared, not copied) and the
+  // structure of every problem, kept by twr_batch_create; twr_batch_reserve_start plans from them (twr::PlanStart) and uploads
+  // the distinct tables and the work list into device memory of their own
+  std::vector<std::shared_ptr<const std::vector<char>>> start_tables;
+  std::vector<int32_t> struct_of_problem;
+  DevPtr<char> start_dev;
+  DevList<twr::StartWork> start_work;
   // lazily sized scratch for twr_batch_eval_host
   DevPtr<double> d_x, d_g, d_j;
   PinnedPtr<double> p_x, p_g, p_j;           // page-locked host buffers (twr_batch_host_buffers)

@@ -60,5 +60,9 @@ hipError_t launch_eval_joint_scores(const NodeWork* work, int n_problems, const 
 // centre into the n_hdr headers whose DevStruct::grid_px lies hdr_off[k] bytes into arena (kernels/grid_map_update.h).  One launch.
 hipError_t launch_grid_map_update(const float* src, float* dst, int size_x, int size_y, int start_x, int start_y, double pos_x,
                                   double pos_y, void* arena, const uint64_t* hdr_off, int n_hdr, hipStream_t stream);
+// x0 / x_l / x_u of the batch from request records on the device (kernels/start.h): work list of PlanStart, `stride` doubles
+// between two problems' records (0: one record for all); x / lower / upper in the layout of x_off, each may be null (not all).
+hipError_t launch_start(const StartWork* work, int n_work, const double* request, int64_t stride, double* x, double* lower, double* upper,
+                        hipStream_t stream);
 
 }  // namespace twr

@@ -1377,6 +1377,7 @@ void Structure::Build() {
   BuildTimeTables();
   BuildPattern();
   PackBlob();
+  BuildStartTable();
 }
 void Structure::BuildSizes() {
   BuildVariables();
@@ -1560,6 +1561,107 @@ void Structure::VariableBounds(const double* init_base, const double* final_base
         lower[off_schedule[e] + i] = 0.2;
         upper[off_schedule[e] + i] = 1.0;
       }
+}
+
+// ------------------------------------------------------------------ start table (start_table.h)
+// InitialGuess and VariableBounds above as ONE record per variable: the loops are theirs, in their order, writing records where
+// they write numbers -- so a variable shared by two nodes keeps the record of the later node, as it keeps that node's value, and
+// a bound on a node value that is no variable leaves no trace.
+void Structure::BuildStartTable() {
+  std::vector<StartRec> rec(n_vars, StartRec{0, 0, 0, kStartZero, kStartNoBound, 0, 0});
+  std::vector<double> dur;
+  StartHeader h{};
+  h.n_vars = n_vars;
+  h.n_ee = n_ee;
+  h.T = T;
+  h.mass = model.mass;
+  h.gravity = model.gravity;
+  for (int e = 0; e < n_ee; ++e)
+    for (int d = 0; d < 3; ++d) h.stance[e][d] = model.nominal_stance[e][d];
+  auto values = [&](const SplineLayout& s, int delta, int spline) {   // `interpolate` of InitialGuess
+    if (s.n_nodes - 1 > 0xFFFF) throw std::runtime_error("too many nodes per spline for the start table");
+    h.nm1[spline] = s.n_nodes - 1;
+    for (int n = 0; n < s.n_nodes; ++n)
+      for (int d = 0; d < 3; ++d)
+        for (int dv = 0; dv < 2; ++dv) {
+          const int i = s.at(n, dv, d);
+          if (i < 0) continue;
+          StartRec& r = rec[i + delta];
+          r.node = (uint16_t)n;
+          r.spline = (uint8_t)spline;
+          r.comp = (uint8_t)(3 * dv + d);
+          r.value = kStartNode;
+        }
+  };
+  values(base, off_base_lin, 0);
+  values(base, off_base_ang, 1);
+  for (int e = 0; e < n_ee; ++e) values(motion[e], 0, 2 + e);
+  for (int e = 0; e < n_ee; ++e) values(force[e], 0, 2 + kMaxEE + e);
+  auto fix = [&](const SplineLayout& s, int delta, int node, int deriv, int dim, int slot) {   // `fix` of VariableBounds
+    const int i = s.at(node, deriv, dim);
+    if (i < 0) return;
+    rec[i + delta].bound = kStartFixed;
+    rec[i + delta].slot = (uint8_t)slot;
+  };
+  const int last = base.n_nodes - 1;
+  for (int d = 0; d < 3; ++d) {
+    fix(base, off_base_lin, 0, 0, d, d);
+    fix(base, off_base_lin, 0, 1, d, 3 + d);
+    if (d != 2) fix(base, off_base_lin, last, 0, d, 12 + d);
+    fix(base, off_base_lin, last, 1, d, 12 + 3 + d);
+    fix(base, off_base_ang, 0, 0, d, 6 + d);
+    fix(base, off_base_ang, 0, 1, d, 9 + d);
+    fix(base, off_base_ang, last, 0, d, 12 + 6 + d);
+    fix(base, off_base_ang, last, 1, d, 12 + 9 + d);
+    for (int e = 0; e < n_ee; ++e) fix(motion[e], 0, 0, 0, d, 24 + 3 * e + d);
+  }
+  if (timings)
+    for (int e = 0; e < n_ee; ++e)
+      for (int i = 0; i < schedule.n_phases[e] - 1; ++i) {
+        StartRec& r = rec[off_schedule[e] + i];
+        r = StartRec{(uint16_t)dur.size(), 0, 0, kStartDuration, kStartDurationBox, 0, 0};
+        dur.push_back(schedule.phase_durations[e][i]);
+      }
+  h.n_dur = (int32_t)dur.size();
+  h.o_dur = (uint32_t)sizeof(StartHeader);
+  h.o_rec = h.o_dur + (uint32_t)(dur.size() * sizeof(double));
+  auto table = std::make_shared<std::vector<char>>(h.o_rec + rec.size() * sizeof(StartRec));
+  std::memcpy(table->data(), &h, sizeof(h));
+  if (!dur.empty()) std::memcpy(table->data() + h.o_dur, dur.data(), dur.size() * sizeof(double));
+  if (!rec.empty()) std::memcpy(table->data() + h.o_rec, rec.data(), rec.size() * sizeof(StartRec));
+  start_table = std::move(table);
+}
+
+void Structure::StartHost(const double* request, double* x, double* lower, double* upper) const {
+  if (!start_table) throw std::runtime_error("structure without a start table");
+  const char* t = start_table->data();
+  const StartHeader& h = *reinterpret_cast<const StartHeader*>(t);
+  const double* dur = reinterpret_cast<const double*>(t + h.o_dur);
+  const StartRec* rec = reinterpret_cast<const StartRec*>(t + h.o_rec);
+  StartEnd ends[kStartSplines] = {};
+  if (x) {   // the per-spline endpoints: 1 + n_ee terrain heights, one sine and one cosine
+    const double *lin0 = request, *ang0 = request + 6, *lin1 = request + 12, *ang1 = request + 18, *ee0 = request + 24;
+    double fl[3], f[3];
+    start_final_base(lin1, TerrainHeightHost(model, grid.get(), lin1[0], lin1[1]), h.stance[0], fl);
+    start_end(lin0, fl, h.T, ends[0]);
+    start_end(ang0, ang1, h.T, ends[1]);
+    const double cz = std::cos(ang1[2]), sz = std::sin(ang1[2]);
+    start_force(h.mass, h.gravity, h.n_ee, f);
+    for (int e = 0; e < h.n_ee; ++e) {
+      double fe[3];
+      start_foothold(lin1, sz, cz, h.stance[e], fe);
+      fe[2] = TerrainHeightHost(model, grid.get(), fe[0], fe[1]);
+      start_end(ee0 + 3 * e, fe, h.T, ends[2 + e]);
+      start_end(f, f, h.T, ends[2 + kMaxEE + e]);
+    }
+  }
+  for (int i = 0; i < h.n_vars; ++i) {
+    if (x) x[i] = start_value(rec[i], ends, h.nm1, dur);
+    double lo, up;
+    start_bounds(rec[i], request, lo, up);
+    if (lower) lower[i] = lo;
+    if (upper) upper[i] = up;
+  }
 }
 
 }  // namespace twr

@@ -12,6 +12,7 @@
 
 #include "../../include/towr_amd.h"
 #include "device_tables.h"
+#include "start_table.h"
 
 namespace twr {
 
@@ -76,6 +77,9 @@ struct Structure {
   std::vector<double> lower, upper;
 
   std::vector<char> blob;  // packed DevStruct + tables (device_tables.h)
+  // StartHeader | dur[] | StartRec[n_vars] (start_table.h): where x0 / x_l / x_u of a request come from.  Not part of the blob;
+  // shared, so that a batch keeps the tables of its structures without copying them (twr_batch_reserve_start).
+  std::shared_ptr<const std::vector<char>> start_table;
   // byte offsets of the per-lane record arrays inside the blob
   uint32_t off_dyn_shared = 0, off_dyn_lanes = 0;   // optimised timings: DynShared[k] (base-spline part)
   // fixed timings: slices of the dynamic set and their tables (device_tables.h DynNodeT / DynNodeL / DynSel / DynPolyT / DynPolyL / DynTile)
@@ -123,12 +127,16 @@ struct Structure {
   int SampleCount(double dt) const;  // twr::SampleCount of the base spline's total time
   void VariableBounds(const double* init_base, const double* final_base, const double* ee0, double* lower,
                       double* upper) const;
+  // The start table run on the host: InitialGuess (x) and VariableBounds (lower, upper) of one request record; each output
+  // may be null.
+  void StartHost(const double* request, double* x, double* lower, double* upper) const;
 
  private:
   void BuildVariables();
   void BuildTimeTables();
   void BuildPattern();
   void PackBlob();
+  void BuildStartTable();
 };
 
 // fpowr GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53): samples while t <= t_total + 1e-5, t accumulated

@@ -1,5 +1,5 @@
 // Third translation unit of the kernels, plain flags: the utility kernels -- trajectory sampling, scoring from g, the planner's arg-min,
-// contact plan, nearest plane, joint-space trajectories and their scores, TWR_EVAL_CHECK, the grid_map layer update -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
+// contact plan, nearest plane, joint-space trajectories and their scores, TWR_EVAL_CHECK, the grid_map layer update, the start of a request (x0 and variable bounds) -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -14,6 +14,7 @@
 #include "kernels/grid_map_update.h"
 #include "kernels/joints.h"
 #include "kernels/planes.h"
+#include "kernels/start.h"
 
 namespace twr {
 
@@ -671,6 +672,35 @@ hipError_t launch_grid_map_update(const float* src, float* dst, int size_x, int 
   return twr_launch(grid_map_update_kernel, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const uint32_t*>(src),
                     reinterpret_cast<uint32_t*>(dst), size_x, size_y, start_x, start_y, pos_x, pos_y, static_cast<char*>(arena), hdr_off,
                     n_hdr);
+}
+
+// ---------------------------------------------------------------- x0 and variable bounds of a request (kernels/start.h)
+// One workgroup per work item.  stride: doubles between two problems' request records (0: one record for all).
+__global__ __launch_bounds__(kStartItem) void start_kernel(const StartWork* __restrict__ work, const double* __restrict__ request,
+                                                           int64_t stride, double* __restrict__ x, double* __restrict__ lower,
+                                                           double* __restrict__ upper) {
+  __shared__ double s_rq[kStartRequest];
+  __shared__ StartEnd s_end[kStartSplines];
+  const StartWork w = work[blockIdx.x];
+  const char* table = reinterpret_cast<const char*>(w.table);
+  const StartHeader* H = reinterpret_cast<const StartHeader*>(table);
+  const DevStruct* S = reinterpret_cast<const DevStruct*>(w.blob);
+  const int t = threadIdx.x;
+  if (t < kStartRequest) s_rq[t] = request[(int64_t)w.problem * stride + t];
+  __syncthreads();
+  if (x) {   // (the bounds need no endpoints)
+    if (t < H->n_ee) start_foot_ends(H, S, s_rq, t, s_end);
+    else if (t == 64) start_base_ends(H, S, s_rq, s_end);
+    __syncthreads();
+  }
+  if (t < w.cnt)
+    start_put(H, table, s_end, H->nm1, s_rq, w.v0 + t, x ? x + w.x_off : nullptr, lower ? lower + w.x_off : nullptr,
+              upper ? upper + w.x_off : nullptr);
+}
+hipError_t launch_start(const StartWork* work, int n_work, const double* request, int64_t stride, double* x, double* lower, double* upper,
+                        hipStream_t stream) {
+  if (n_work < 1 || !work || !request || (!x && !lower && !upper) || stride < 0) return hipErrorInvalidValue;
+  return twr_launch(start_kernel, dim3(n_work), dim3(kStartItem), 0, stream, work, request, stride, x, lower, upper);
 }
 
 }  // namespace twr
