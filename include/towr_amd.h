@@ -513,7 +513,8 @@ int twr_batch_contact_planes(twr_batch* b, const twr_planes* planes, const doubl
  * bends 0/1, lengths finite and > 0, offsets finite, q_min <= q_max and neither NaN.
  *
  * Foot e in the base frame is R(q)^T (p_ee - p_base), R(q) = Eigen's toRotationMatrix of the normalised quaternion of the
- * sample record (xpp_vis CartesianJointConverter's frame change); then foot * mirror[e] - base_to_hip goes through
+ * sample record (xpp_vis CartesianJointConverter's frame change; a quaternion whose norm in doubles is 0, Inf or NaN cannot be
+ * normalised and gives NaN angles with flag 32); then foot * mirror[e] - base_to_hip goes through
  * GetJointAngles + EnforceLimits restated operation for operation, the reference's quirks included: -atan2(y, -z) with its
  * signed zeros, the clamp std::max(lo, std::min(hi, v)) that turns a NaN cosine into +1, limits that leave a NaN alone.
  *

@@ -52,11 +52,17 @@
 //   ref_dump --plane-points IN OUT   PlanarRegionsToPolygons and NearestPlaneLookup::GetNearestPlaneIndex on given regions and
 //                        points, with bg::distance per region, see PlanePoints() below (oracle/ref_golden.py --planes records
 //                        it as tests/golden/refplane.npz)
+//   ref_dump --attitude-points IN OUT   Eigen::Quaterniond(R) on given matrices, or EulerConverter's rotation matrix, quaternion,
+//                        angular velocity and acceleration on given states of the Euler-angle spline, see AttitudePoints() below
+//                        (oracle/ref_golden.py --attitude records it as tests/golden/refattitude.npz)
 #include <ifopt/problem.h>
 #include <towr/initialization/gait_generator.h>
 #include <towr/nlp_formulation.h>
 #include <towr/terrain/examples/height_map_examples.h>
 #include <towr/terrain/height_map_from_csv.h>
+#include <towr/variables/euler_converter.h>
+#include <towr/variables/node_spline.h>
+#include <towr/variables/nodes_variables_all.h>
 #include <towr/variables/nodes_variables_phase_based.h>
 #include <towr/variables/phase_durations.h>
 #include <towr/variables/spline.h>
@@ -375,10 +381,89 @@ static int PlanePoints(int argc, char** argv) {
 #endif
 }
 
+// ref_dump --attitude-points IN OUT: the attitude of the base alone, no NLP.  IN holds raw doubles, the first one the mode, the
+// second the number of points n.
+//   mode 0: per point a 3 x 3 matrix, row-major.  OUT per point: Eigen::Quaterniond(R) as x y z w -- of the Eigen this build
+//           uses (oracle/_ref/DEPS), the statement of euler_converter.cc:55.
+//   mode 1: per point the 12 values [p0 v0 p1 v1] of a NodesVariablesAll with two nodes of three dimensions.  A NodeSpline of one
+//           polynomial of duration 1 on them is the Euler-angle spline of an EulerConverter.  OUT per point, 28 doubles: the state
+//           NodeSpline::GetPoint(0) returns (angles, rates, accelerations: the input of everything that follows), the matrix of
+//           the static GetRotationMatrixBaseToWorld(angles) row-major, the static GetQuaternionBaseToWorld(angles) as x y z w,
+//           GetAngularVelocityInWorld(0.0) and GetAngularAccelerationInWorld(0.0) (the static ones are private).
+static int AttitudePoints(int argc, char** argv) {
+  if (argc != 4) {
+    std::fprintf(stderr, "usage: ref_dump --attitude-points IN OUT\n");
+    return 2;
+  }
+  std::vector<double> in;
+  {
+    std::FILE* f = std::fopen(argv[2], "rb");
+    if (!f) {
+      std::fprintf(stderr, "cannot read %s\n", argv[2]);
+      return 2;
+    }
+    double buf[4096];
+    size_t got;
+    while ((got = std::fread(buf, sizeof(double), 4096, f)) > 0) in.insert(in.end(), buf, buf + got);
+    std::fclose(f);
+  }
+  auto bad = [&](const char* what) {
+    std::fprintf(stderr, "%s: %s\n", argv[2], what);
+    return 2;
+  };
+  if (in.size() < 2) return bad("empty");
+  const int mode = static_cast<int>(in[0]);
+  const long n = static_cast<long>(in[1]);
+  if (mode != 0 && mode != 1) return bad("unknown mode");
+  const size_t per = mode == 0 ? 9 : 12;
+  if (n < 0 || 2 + per * static_cast<size_t>(n) != in.size()) return bad("point count");
+  std::vector<double> out;
+  const double* p = in.data() + 2;
+  if (mode == 0) {
+    for (long k = 0; k < n; ++k, p += 9) {
+      Eigen::Matrix3d R;
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) R(r, c) = p[3 * r + c];
+      const Eigen::Quaterniond q(R);
+      out.insert(out.end(), {q.x(), q.y(), q.z(), q.w()});
+    }
+  } else {
+    auto nodes = std::make_shared<towr::NodesVariablesAll>(2, 3, "attitude");
+    auto spline = std::make_shared<towr::NodeSpline>(nodes.get(), std::vector<double>{1.0});
+    const towr::EulerConverter converter(spline);
+    Eigen::VectorXd x(12);
+    for (long k = 0; k < n; ++k, p += 12) {
+      for (int i = 0; i < 12; ++i) x(i) = p[i];
+      nodes->SetVariables(x);
+      const towr::State s = spline->GetPoint(0.0);
+      const Eigen::Vector3d angles = s.p();
+      for (int i = 0; i < 3; ++i) out.push_back(s.p()(i));
+      for (int i = 0; i < 3; ++i) out.push_back(s.v()(i));
+      for (int i = 0; i < 3; ++i) out.push_back(s.a()(i));
+      const auto R = towr::EulerConverter::GetRotationMatrixBaseToWorld(angles);
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) out.push_back(R.coeff(r, c));
+      const Eigen::Quaterniond q = towr::EulerConverter::GetQuaternionBaseToWorld(angles);
+      out.insert(out.end(), {q.x(), q.y(), q.z(), q.w()});
+      const Eigen::Vector3d w = converter.GetAngularVelocityInWorld(0.0), wd = converter.GetAngularAccelerationInWorld(0.0);
+      for (int i = 0; i < 3; ++i) out.push_back(w(i));
+      for (int i = 0; i < 3; ++i) out.push_back(wd(i));
+    }
+  }
+  std::FILE* f = std::fopen(argv[3], "wb");
+  if (!f || std::fwrite(out.data(), sizeof(double), out.size(), f) != out.size() || std::fclose(f) != 0) {
+    std::fprintf(stderr, "cannot write %s\n", argv[3]);
+    return 2;
+  }
+  std::printf("ref_dump: attitude mode %d, %ld points, %zu values\n", mode, n, out.size());
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && std::string(argv[1]) == "--terrain-points") return TerrainPoints(argc, argv);
   if (argc >= 2 && std::string(argv[1]) == "--segment-points") return SegmentPoints(argc, argv);
   if (argc >= 2 && std::string(argv[1]) == "--plane-points") return PlanePoints(argc, argv);
+  if (argc >= 2 && std::string(argv[1]) == "--attitude-points") return AttitudePoints(argc, argv);
   if (argc < 9) {
     std::fprintf(stderr, "usage: see the header of ref_dump.cc\n");
     return 2;

@@ -11,6 +11,9 @@ the structure builder (CPU) and the device (GPU) on boxes that do not have the r
     python -m oracle.ref_golden --traj [names...]   (the fixtures tests/golden/reftraj_*.npz, see TRAJ_CASES below)
     python -m oracle.ref_golden --terrain [names...]   (tests/golden/refterrain_*.npz, see TERRAIN_FIXTURES below)
     python -m oracle.ref_golden --segments          (tests/golden/refsegment.npz, see record_segments below)
+    python -m oracle.ref_golden --planes            (tests/golden/refplane.npz, see record_planes below)
+    python -m oracle.ref_golden --attitude          (tests/golden/refattitude.npz, see record_attitude below)
+    python -m oracle.ref_golden --attitude --check  (records afresh and compares with the committed file, writes nothing)
 
 The cases are chosen for what the mpmath fixtures and the hand known-answers cannot reach: entries the reference DEFINES
 rather than derives (force rows x footholds on curved terrain, terrain rows of gridded terrain, explicit zeros), bounds,
@@ -484,6 +487,64 @@ def record_planes(workdir):
     return path, os.path.getsize(path), len(out["points"]), len(out["distance"])
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# tests/golden/refattitude.npz: the attitude of the base (ref_dump --attitude-points) at the points of tests/attitude_points.py.
+# quat_R (n, 9) and quat_q (n, 4, x y z w) = Eigen::Quaterniond(R) of the Eigen the build uses -- reference_deps names it; with
+# the subset that is this project's own statement of the conversion, so these rows pin the device to a restatement, not to Eigen.
+# euler_state (n, 9) = what the reference's one-polynomial NodeSpline returns at t = 0 for the nodes of attitude_points.spline_nodes
+# (the input of the rows that follow, and of the probe), euler_R, euler_q, euler_omega, euler_omega_dot = EulerConverter's
+# GetRotationMatrixBaseToWorld, GetQuaternionBaseToWorld, GetAngularVelocityInWorld, GetAngularAccelerationInWorld: the
+# reference's own statements.  There is no reference code for the frame change, so the file holds nothing for it.
+# tests/test_attitude_probe.py regenerates the points and compares the restatement (CPU) and the device (GPU).
+def compute_attitude(workdir):
+    from oracle import ref_run
+    from tests import attitude_points as ap
+
+    p = ap.points()
+    q = ref_run.attitude_quaternions(os.path.join(workdir, "quat"), p["quat"])
+    nodes = np.array([ap.spline_nodes(s) for s in p["euler"]])
+    state, R, eq, w, wd = ref_run.attitude_states(os.path.join(workdir, "euler"), nodes)
+    return dict(quat_R=p["quat"], quat_group=p["quat_group"], quat_q=q, euler_group=p["euler_group"], euler_state=state, euler_R=R,
+                euler_q=eq, euler_omega=w, euler_omega_dot=wd, reference_deps=ref_run.deps())
+
+
+ATTITUDE_LIBM_FREE = ("quat_R", "quat_group", "quat_q", "euler_group", "euler_state")   # keys that no sin / cos of the host feeds
+
+
+def check_attitude(workdir):
+    """python -m oracle.ref_golden --attitude --check: a fresh recording against the committed refattitude.npz, key by key.
+    Returns the lines of the report and whether the recipe reproduced the file: byte for byte in ATTITUDE_LIBM_FREE; the other
+    keys pass through the host's libm, which need not be the same function everywhere, and may differ by its rounding (an entry
+    of R by 36 * 2^-53: twice the 9 roundings counted in tests/test_attitude_probe.py on a sum of terms of at most 2).
+    This is run by hand where the reference is present; it is not part of the test suite."""
+    out, f = compute_attitude(workdir), np.load(os.path.join(GOLDEN, "refattitude.npz"))
+    lines, ok = [], set(out) == set(f.files)
+    for key in f.files:
+        if key == "reference_deps":
+            continue
+        a, b = np.asarray(out[key]), f[key]
+        if a.dtype != b.dtype or a.shape != b.shape:
+            lines.append("%-16s dtype or shape differ: %s %s against %s %s" % (key, a.dtype, a.shape, b.dtype, b.shape))
+            ok = False
+            continue
+        rows = np.nonzero((a.view(np.uint8).reshape(len(a), -1) != b.view(np.uint8).reshape(len(b), -1)).any(axis=1))[0]
+        if len(rows) == 0:
+            lines.append("%-16s equal" % key)
+            continue
+        worst = float(np.nanmax(np.abs(a.astype(np.float64) - b.astype(np.float64))))
+        lines.append("%-16s %d rows differ, first %s, largest |difference| %.3e" % (key, len(rows), rows[:8].tolist(), worst))
+        if key in ATTITUDE_LIBM_FREE or (key == "euler_R" and worst > 36 * 2.0 ** -53):
+            ok = False
+    return lines, ok
+
+
+def record_attitude(workdir):
+    out = compute_attitude(workdir)
+    path = os.path.join(GOLDEN, "refattitude.npz")
+    save_npz_lzma(path, out)
+    return path, os.path.getsize(path), len(out["quat_q"]), len(out["euler_q"])
+
+
 def main(names):
     from oracle import ref_run
 
@@ -507,6 +568,19 @@ def main(names):
         with tempfile.TemporaryDirectory() as work:
             path, size, n, k = record_planes(work)
         print("%-40s points=%6d (ring, point) pairs=%6d %8d bytes" % (os.path.basename(path), n, k, size))
+        return
+    if names[:2] == ["--attitude", "--check"]:
+        with tempfile.TemporaryDirectory() as work:
+            lines, ok = check_attitude(work)
+        print("\n".join(lines))
+        if not ok:
+            raise SystemExit("refattitude.npz is NOT reproduced by this build of the reference")
+        print("refattitude.npz is reproduced")
+        return
+    if names and names[0] == "--attitude":
+        with tempfile.TemporaryDirectory() as work:
+            path, size, n, k = record_attitude(work)
+        print("%-40s matrices=%6d states=%6d %8d bytes" % (os.path.basename(path), n, k, size))
         return
     if names and names[0] == "--traj":
         with tempfile.TemporaryDirectory() as work:

@@ -228,6 +228,33 @@ def plane_points(prefix, scenes, timeout=600):
     return res
 
 
+def _attitude_run(prefix, mode, rows, timeout):
+    rows = np.ascontiguousarray(rows, dtype=np.float64)
+    np.concatenate([[float(mode), float(len(rows))], rows.ravel()]).tofile(prefix + "_attitude_in.bin")
+    cmd = [os.path.join(REF, "ref_dump"), "--attitude-points", prefix + "_attitude_in.bin", prefix + "_attitude_out.bin"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout)
+    if r.returncode != 0:
+        raise RuntimeError("ref_dump exit %d: %s\n%s" % (r.returncode, " ".join(cmd), (r.stdout + r.stderr)[-2000:]))
+    return np.fromfile(prefix + "_attitude_out.bin", dtype=np.float64)
+
+
+def attitude_quaternions(prefix, R, timeout=600):
+    """ref_dump --attitude-points, mode 0: Eigen::Quaterniond(R) of the build's Eigen (deps()) on matrices R (n, 9) row-major, as
+    (n, 4) x y z w"""
+    out = _attitude_run(prefix, 0, np.asarray(R, dtype=np.float64).reshape(-1, 9), timeout).reshape(-1, 4)
+    assert len(out) == len(R)
+    return out
+
+
+def attitude_states(prefix, nodes, timeout=600):
+    """ref_dump --attitude-points, mode 1: per row of nodes (n, 12) [p0 v0 p1 v1] of a one-polynomial Euler-angle spline of
+    duration 1 the reference's (state (9) GetPoint(0) returned, GetRotationMatrixBaseToWorld (9), GetQuaternionBaseToWorld (4,
+    x y z w), GetAngularVelocityInWorld (3), GetAngularAccelerationInWorld (3)) of that state"""
+    out = _attitude_run(prefix, 1, np.asarray(nodes, dtype=np.float64).reshape(-1, 12), timeout).reshape(-1, 28)
+    assert len(out) == len(nodes)
+    return out[:, :9].copy(), out[:, 9:18].copy(), out[:, 18:22].copy(), out[:, 22:25].copy(), out[:, 25:28].copy()
+
+
 def case_args(case):
     """(args, kwargs) of command() / run() for a tests.common.Case (every field a Case can set reaches the reference)."""
     p = case.params

@@ -143,20 +143,33 @@ def run(name):
     return Run(names, dt([case(n) for n in names])).both()
 
 
+def frame_rotation(q):
+    """R[3][3] of arrays (n,): base_frame_rotation (kernels/joints.h) on quaternions q (n, 4) w x y z, in the device's order of
+    plainly rounded operations; a norm that is not finite gives NaN like a norm of 0"""
+    with np.errstate(all="ignore"):
+        w, x, y, z = (np.array(q[:, i], dtype=np.float64) for i in range(4))
+        n = np.sqrt(x * x + y * y + z * z + w * w)
+        n = np.where(n < np.inf, n, n - n)
+        w, x, y, z = w / n, x / n, y / n, z / n
+        tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
+        twx, twy, twz, txx, txy, txz, tyy, tyz, tzz = tx * w, ty * w, tz * w, tx * x, ty * x, tz * x, ty * y, tz * y, tz * z
+        return [[1.0 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1.0 - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, 1.0 - (txx + tyy)]]
+
+
+def frame_vector(R, p_base, p_ee):
+    """(n, 3): base_frame (kernels/joints.h) on frame_rotation's R and points (n, 3)"""
+    with np.errstate(all="ignore"):
+        d = p_ee - p_base
+        return np.column_stack([R[0][i] * d[:, 0] + R[1][i] * d[:, 1] + R[2][i] * d[:, 2] for i in range(3)])
+
+
 def hip_feet(traj):
     """[n, 4, 3] hip-frame feet of trajectory records, in the device's order of operations (kernels/joints.h base_frame_rotation,
     base_frame, leg_ik_of_foot)"""
-    w, x, y, z = (traj[:, 10 + i].copy() for i in range(4))
-    n = np.sqrt(x * x + y * y + z * z + w * w)
-    w, x, y, z = w / n, x / n, y / n, z / n
-    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
-    twx, twy, twz, txx, txy, txz, tyy, tyz, tzz = tx * w, ty * w, tz * w, tx * x, ty * x, tz * x, ty * y, tz * y, tz * z
-    R = np.array([[1.0 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1.0 - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, 1.0 - (txx + tyy)]])
+    R = frame_rotation(traj[:, 10:14])
     out = np.empty((len(traj), 4, 3))
     for e in range(4):
-        d = traj[:, 21 + 13 * e:24 + 13 * e] - traj[:, 1:4]
-        for i in range(3):
-            out[:, e, i] = R[0][i] * d[:, 0] + R[1][i] * d[:, 1] + R[2][i] * d[:, 2]
+        out[:, e] = frame_vector(R, traj[:, 1:4], traj[:, 21 + 13 * e:24 + 13 * e])
     return out * ip.MIRROR[None] - ip.BASE_TO_HIP[None, None]
 
 
@@ -318,6 +331,76 @@ def test_hostile_x_is_contained_in_its_problem():
             # reference's own rules and the bad number surfaces as an infinite over-reach of unreachable legs
             assert got[1][3] == np.inf and got[1][1] > 0 and got[1][7] >= 0, got[1].tolist()
         assert same_bits(got[1], fold(r.joints_of(1), r.dt)).all()
+
+
+# ------------------------------------------------------------------ the quaternion of the records
+def joints_of_edited_records(clean, edit):
+    """(a Run on clean's batch shape whose trajectory records are clean's with `edit(records of problem p, p)` applied, after
+    twr_batch_joints and twr_batch_joint_scores on them)"""
+    torch = _torch()
+    r = Run(BATCHES["i_64"][0], clean.dt, xs=clean.xs)
+    traj = clean.traj.cpu().numpy().copy()
+    for p, n in enumerate(clean.counts):
+        edit(traj[p * clean.tstride:p * clean.tstride + n * clean.trec].reshape(n, clean.trec), p)
+    r.traj.copy_(torch.from_numpy(traj))
+    st = torch.cuda.current_stream().cuda_stream
+    r.batch.joints_device(kin(), r.traj.data_ptr(), r.tstride, r.dt, r.joints.data_ptr(), r.jstride, st)
+    r.batch.joint_scores_device(kin(), r.joints.data_ptr(), r.jstride, r.dt, r.scores.data_ptr(), st)
+    torch.cuda.synchronize()
+    return r
+
+
+@pytest.mark.gpu
+def test_joints_ignore_the_sign_and_a_power_of_two_of_the_quaternion():
+    """q and -q are one rotation and every product of the frame change is even in q; the normalisation is exact under a power of
+    two (the squares, their sum, the root and the quotients scale without rounding): the joint records keep every bit"""
+    clean = run("i_64")
+
+    def edit(rec, p):
+        s = np.arange(len(rec))
+        rec[s % 2 == 1, 10:14] *= -1.0
+        rec[(s // 2) % 3 == 1, 10:14] *= 2.0
+        rec[(s // 2) % 3 == 2, 10:14] *= 0.5
+        assert (s % 2 == 1).sum() == len(rec) // 2
+
+    r = joints_of_edited_records(clean, edit)
+    assert not same_bits(r.traj.cpu().numpy(), clean.traj.cpu().numpy()).all()
+    assert same_bits(r.joints.cpu().numpy(), clean.joints.cpu().numpy()).all()
+    assert same_bits(r.scores.cpu().numpy(), clean.scores.cpu().numpy()).all()
+
+
+HOSTILE_Q = {3: (0.0, 0.0, 0.0, 0.0), 17: (np.nan, 0.1, 0.2, 0.3), 18: (0.9, 0.1, np.nan, 0.3), 31: (np.inf, 0.1, 0.2, 0.3),
+             32: (0.9, -np.inf, 0.2, 0.3), 45: (1e200, 1e200, 1e200, 1e200), 46: (0.9, 0.1, 0.2, 1e200), 62: (1e-200, 1e-200, 1e-200, 1e-200),
+             63: (0.0, 1e-200, 0.0, 0.0)}
+
+
+@pytest.mark.gpu
+def test_a_quaternion_that_cannot_be_normalised_is_flagged_and_stays_in_its_sample():
+    """zero, NaN, Inf, 1e200 (the squares overflow) and 1e-200 (they underflow to a norm of 0) in the quaternion of some records
+    of problem 1: every leg of those samples carries the NaN flag and NaN angles, every other sample and problem 0 keep the bits
+    of the clean run, and nothing is written behind a problem's records"""
+    clean = run("i_64")
+
+    def edit(rec, p):
+        if p == 1:
+            for s, q in HOSTILE_Q.items():
+                rec[s, 10:14] = q
+
+    r = joints_of_edited_records(clean, edit)
+    assert same_bits(r.joints_of(0), clean.joints_of(0)).all()
+    got, was = r.joints_of(1), clean.joints_of(1)
+    hit = np.zeros(len(got), dtype=bool)
+    hit[list(HOSTILE_Q)] = True
+    assert same_bits(got[~hit], was[~hit]).all() and same_bits(got[:, 0], was[:, 0]).all()
+    legs = got[hit][:, 1:].reshape(-1, 5)
+    assert ((legs[:, 3].astype(np.int64) & 32) != 0).all(), legs[:, 3].tolist()
+    assert np.isnan(legs[:, :3]).any(axis=1).all()
+    pad = r.joints.cpu().numpy().reshape(len(r.cases), r.jstride)
+    for p, n in enumerate(r.counts):
+        assert np.isnan(pad[p, n * r.jrec:]).all(), "nothing is written behind a problem's records"
+    sc, sc0 = r.scores.cpu().numpy(), clean.scores.cpu().numpy()
+    assert same_bits(sc[0], sc0[0]).all()
+    assert sc[1][6] == 4 * len(HOSTILE_Q) and same_bits(sc[1], fold(got, r.dt)).all(), sc[1].tolist()
 
 
 # ------------------------------------------------------------------ argument checks

@@ -16,7 +16,12 @@ static_assert(TWR_JOINT_REC(4) == 1 + kJointLeg * 4, "joint record layout");
 enum : int { kIkBeta = 1, kIkGamma = 2, kIkHaa = 4, kIkHfe = 8, kIkKfe = 16, kIkNan = 32 };
 
 // Eigen::Quaterniond(R) (euler_converter.cc:51-56; Eigen 3.3 Quaternion.h, quaternionbase_assign_impl); q = x y z w
+// The trace is summed as (m00 + m11) + m22, like the oracle's and the Eigen subset's statement of it (DESIGN 5 "Base attitude").
+// No contraction: the reference converts the ROUNDED entries of R.  Inlined behind rotation(), whose entries are products, the
+// sums and differences below were otherwise fused with those products, so that q was not a function of R (tests/attitude_probe.hip
+// found q one ulp off the conversion of the very R the same thread had stored) and depended on what else used the products.
 TWR_DEV void quat_of_rotation(const double (&m)[3][3], double q[4]) {
+#pragma clang fp contract(off)
   double tr = m[0][0] + m[1][1] + m[2][2];
   if (tr > 0) {
     tr = sqrt(tr + 1.0);
@@ -48,7 +53,11 @@ TWR_DEV void quat_of_rotation(const double (&m)[3][3], double q[4]) {
 // (no contraction in either: the fused kernel and the kernel that reads records must round alike whatever surrounds the call)
 TWR_DEV void base_frame_rotation(double w, double x, double y, double z, double R[3][3]) {
 #pragma clang fp contract(off)
-  const double n = sqrt(x * x + y * y + z * z + w * w);
+  double n = sqrt(x * x + y * y + z * z + w * w);
+  // A quaternion that cannot be normalised is NaN, not a rotation: |q| = 0 and a NaN component give NaN by themselves (0 / 0),
+  // but a norm of Inf (an Inf component, or squares that overflow from 1e155 on) would divide every finite component to 0 and
+  // R to the identity.
+  if (!(n < __builtin_inf())) n = n - n;
   w /= n; x /= n; y /= n; z /= n;
   const double tx = 2.0 * x, ty = 2.0 * y, tz = 2.0 * z;
   const double twx = tx * w, twy = ty * w, twz = tz * w, txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;

@@ -14,75 +14,12 @@
 #include "kernels/grid_map_update.h"
 #include "kernels/joints.h"
 #include "kernels/planes.h"
+#include "kernels/sample.h"
 #include "kernels/start.h"
 
 namespace twr {
 
-// ---------------------------------------------------------------- trajectory sampling
-// fpowr::GetTrajectory (fpowr/include/fpowr/footstep_plan_extractor.h:19-53) for a batch of solutions: lane =
-// sample.  Durations (constants of the structure, or recomputed from x with optimised timings) go to LDS once
-// per workgroup; every lane accumulates its sample time like the reference (t += dt), locates the active
-// polynomial of every spline and evaluates position / velocity / acceleration in Hermite basis form.
-TWR_DEV void sample_spline(const double* __restrict__ xp, const PolyDesc& pd, double tl, double T, double p[3], double v[3],
-                           double a[3]) {
-  double X[12], nv[4][3], wp[4], wv[4], wa[4];
-  gather12c(xp, pd.xbase, pd.cand, X);
-  node_values(slots_of(pd.cand), meta_shared(pd.meta), X, nv);
-  hermite_all(tl, 1.0 / T, wp, wv, wa);
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    p[d] = wp[0] * nv[0][d] + wp[1] * nv[1][d] + wp[2] * nv[2][d] + wp[3] * nv[3][d];
-    v[d] = wv[0] * nv[0][d] + wv[1] * nv[1][d] + wv[2] * nv[2][d] + wv[3] * nv[3][d];
-    a[d] = wa[0] * nv[0][d] + wa[1] * nv[1][d] + wa[2] * nv[2][d] + wa[3] * nv[3][d];
-  }
-}
-// The base of a sample at time t, shared by sample_kernel and eval_joint_scores_kernel (which must form the very same doubles:
-// the compiler's choice of fused operations depends on what else uses a product, so that kernel keeps every result alive).
-struct BaseSample {
-  double p[3], v[3], a[3];       // base-lin
-  double e3[3], ed[3], edd[3];   // base-ang: Euler angles, rates, accelerations
-};
-struct BaseAngular {
-  double q[4];                   // x y z w
-  double omega[3], omega_dot[3];
-};
-// base-lin / base-ang (NodesVariablesAll: [p0 v0 p1 v1] x 3 of polynomial q at 6 q)
-TWR_DEV void sample_base(const double* __restrict__ xp, const SampleTables* ST, const double* s_bd, double t, BaseSample& B) {
-  double tl;
-  const int qb = locate_segment(s_bd, ST->n_base, t, tl);
-  double wp[4], wv[4], wa[4];
-  hermite_all(tl, 1.0 / s_bd[qb], wp, wv, wa);
-  const double* xl = xp + ST->off_lin + 6 * qb;
-  const double* xa = xp + ST->off_ang + 6 * qb;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    B.p[d] = wp[0] * xl[d] + wp[1] * xl[3 + d] + wp[2] * xl[6 + d] + wp[3] * xl[9 + d];
-    B.v[d] = wv[0] * xl[d] + wv[1] * xl[3 + d] + wv[2] * xl[6 + d] + wv[3] * xl[9 + d];
-    B.a[d] = wa[0] * xl[d] + wa[1] * xl[3 + d] + wa[2] * xl[6 + d] + wa[3] * xl[9 + d];
-    B.e3[d] = wp[0] * xa[d] + wp[1] * xa[3 + d] + wp[2] * xa[6 + d] + wp[3] * xa[9 + d];
-    B.ed[d] = wv[0] * xa[d] + wv[1] * xa[3 + d] + wv[2] * xa[6 + d] + wv[3] * xa[9 + d];
-    B.edd[d] = wa[0] * xa[d] + wa[1] * xa[3 + d] + wa[2] * xa[6 + d] + wa[3] * xa[9 + d];
-  }
-}
-TWR_DEV void sample_angular(const BaseSample& B, BaseAngular& A) {
-  Rot ro;
-  rotation(B.e3, ro);
-  quat_of_rotation(ro.R, A.q);
-  {  // omega = M edot, omega_dot = Mdot edot + M eddot (euler_converter.cc:58-83,133-166)
-    const double sy = ro.sy, cy = ro.cy, sz = ro.sz, cz = ro.cz;
-    const double xd = B.ed[0], yd = B.ed[1], zd = B.ed[2];
-    const double Mx[3] = {cy * cz, cy * sz, -sy}, My[3] = {-sz, cz, 0.0};
-    const double Mdx[3] = {-cz * sy * yd - cy * sz * zd, cy * cz * zd - sy * sz * yd, -cy * yd};
-    const double Mdy[3] = {-cz * zd, -sz * zd, 0.0};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      A.omega[i] = Mx[i] * xd + My[i] * yd + (i == 2 ? zd : 0.0);
-      A.omega_dot[i] = Mdx[i] * xd + Mdy[i] * yd + Mx[i] * B.edd[0] + My[i] * B.edd[1] + (i == 2 ? B.edd[2] : 0.0);
-    }
-  }
-}
-// keeps a value computed where nothing stores it
-TWR_DEV void keep_alive(double v) { asm volatile("" ::"v"(v)); }
+// ---------------------------------------------------------------- trajectory sampling (the device functions: kernels/sample.h)
 // With `times` set the kernel is fpowr::ExtractInitialGuess (fpowr/include/fpowr/initial_guess_extractor.h:17-34)
 // instead: sample s of every problem is taken at times[s] and the record is [ t | state: base-lin p, base-ang p (Euler
 // angles), base-lin v, base-ang v (Euler rates) | controls (36): ee-motion acceleration of ee i at 3 i, twelve zeros
