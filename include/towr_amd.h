@@ -559,6 +559,64 @@ int twr_batch_joint_scores(twr_batch* b, const twr_leg_kinematics* kin, const do
 int twr_batch_eval_joint_scores(twr_batch* b, const twr_leg_kinematics* kin, const double* d_x, double dt,
                                 double* d_jscores /* 8 * n_problems */, void* hip_stream);
 
+/* Checks of a sampled trajectory BETWEEN the constraint nodes.  The constraints hold where towr places them (dynamics and range of
+ * motion on their dt grids, terrain height and the friction pyramid at the spline nodes); these two calls evaluate the same
+ * quantities at every sample record of twr_batch_sample, i.e. on the trajectory a planner publishes
+ * (footstep_plan_server.cc:118-129, 286-294), and fold them per problem.
+ *
+ * twr_batch_checks reads the sample record [ t | base p v a | q wxyz | omega | omega_dot | per ee: contact, p v a, f ] and nothing
+ * else of the trajectory, and writes one check record per sample, TWR_CHECK_REC(n_ee) doubles:
+ *   [ t | dynamics residual: angular (3), linear (3) | per ee: contact, clearance, f_n, cone, rom ]
+ *   t, contact  the sample record's own doubles (the contact flag is carried along because the scores below tell stance from swing
+ *               and are folded from check records alone; with optimised timings only the trajectory knows the phase)
+ *   residual    SingleRigidBodyDynamics::GetDynamicViolation (single_rigid_body_dynamics.cc:76-103) in its order:
+ *                 angular  I_w omega_dot + omega x (I_w omega) - sum_e f_e x (p_base - p_e),   I_w = R I_b R^T
+ *                 linear   m a - sum_e f_e, + m g on z
+ *               R = the rotation of the record's normalised quaternion (as twr_batch_joints forms it); m, g and I_b are those of the
+ *               problem's structure, the constants its constraints were built with
+ *   clearance   p_e.z - h(p_e.x, p_e.y), h the terrain of the problem's structure; for a `Grid` batch the map the batch holds when
+ *               the launch runs
+ *   f_n         f_e . n
+ *   cone        mu f_n - max(|f_e . t1|, |f_e . t2|): >= 0 inside the friction pyramid.  n, t1, t2: the normalised terrain basis at
+ *               (p_e.x, p_e.y) as the force constraint forms it (height_map.cc:93-139), mu the structure's friction coefficient
+ *   rom         max_d (|foot_B[d] - nominal_stance[e][d]| - max_dev[d]), foot_B = R^T (p_e - p_base): <= 0 inside the box of
+ *               range_of_motion_constraint.cc:71-81
+ * Of `model` only n_ee, nominal_stance, max_dev and force_limit are read.  force_limit enters nowhere but the validation: the
+ * caller compares score [5] and the f_n of the records with it.
+ * Order of operations: no operation is contracted, sums over the end-effectors run left to right from 0, I_w is formed as
+ * (R I_b) R^T row by row, every dot product left to right (the header of csrc/kernels/checks.h lists every expression).  A check
+ * record is thus a function of its sample record alone, the same bits in every batch, slot, call and stream, and a restatement in
+ * plainly rounded doubles reproduces it bit for bit (tests/check_points.py).
+ *
+ * twr_batch_check_scores folds a problem's check records into TWR_CHECK_SCORE_REC doubles at d_cscores + 8 p:
+ *   [0] samples   [1] max |linear residual component|   [2] max |angular residual component|
+ *   [3] min clearance over leg-samples with contact 0 (1e20 if none)   [4] max |clearance| over leg-samples in contact (0 if none)
+ *   [5] min f_n over leg-samples in contact (1e20 if none)   [6] min cone over leg-samples in contact (1e20 if none)
+ *   [7] max rom over all leg-samples
+ *   A leg-sample is in contact when its flag is not 0.  [1] - [7] are NaN if a contributing value is NaN (twr_batch_score's rule).
+ *   Maxima, minima and counts only, one wave per problem in rounds of 64 samples, no atomics: the same bits wherever the problem
+ *   sits in a batch.
+ *
+ * Both calls are asynchronous and stream-ordered on hip_stream and consist of kernel launches only.  twr_batch_checks walks the
+ * sample work list of twr_batch_sample (same dt and traj_stride as given there, built on the first call per dt / stride): capturable
+ * in a hipGraph after one warm call; twr_batch_check_scores is always capturable.  twr_batch_checks counts as a call on the batch,
+ * because it reads the live map: a twr_batch_grid_map_update_device enqueued before it on the stream is seen, one enqueued after it
+ * is not.  Device scope and sticky error as twr_batch_eval.
+ * TWR_ERR_INVALID, with twr_last_error naming the argument or field, before any device is touched: a NULL argument, a pointer
+ * that is not 8-byte aligned, traj_stride < n_samples * (20 + 13 n_ee) or check_stride < n_samples * TWR_CHECK_REC(n_ee) for some
+ * problem, dt not finite or <= 0, model->n_ee != the batch's, a nominal_stance, max_dev or force_limit that is not finite,
+ * a max_dev < 0.
+ * Hostile records are contained: the only index computed from a record is the cell lookup of the terrain, behind its range checks;
+ * a NaN / Inf / 1e300 foot or force reaches the fields of its own sample that are made from it (its leg's fields and the residual)
+ * and nothing else; a quaternion that cannot be normalised (norm 0, Inf or NaN in doubles) gives a NaN angular residual and NaN
+ * rom for that sample. */
+#define TWR_CHECK_REC(n_ee)  (7 + 5 * (n_ee))
+#define TWR_CHECK_SCORE_REC  8
+int twr_batch_checks(twr_batch* b, const twr_model* model, const double* d_traj, int64_t traj_stride, double dt, double* d_checks,
+                     int64_t check_stride, void* hip_stream);
+int twr_batch_check_scores(twr_batch* b, const double* d_checks, int64_t check_stride, double dt,
+                           double* d_cscores /* 8 * n_problems */, void* hip_stream);
+
 /* Convenience for single-problem / adapter use: host buffers, synchronous (H2D, eval, D2H).  Runs on a NON-BLOCKING
  * stream the batch owns (created on first use), not on the NULL stream: it neither waits for nor holds up work the host
  * application has in flight on the NULL stream or on its own blocking streams; the call returns when its own chain is

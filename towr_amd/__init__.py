@@ -81,6 +81,14 @@ def joint_rec(n_ee):
     return 1 + 5 * n_ee
 
 
+CHECK_SCORE_REC = 8   # TWR_CHECK_SCORE_REC
+
+
+def check_rec(n_ee):
+    """TWR_CHECK_REC(n_ee): doubles per check record, [t | residual: angular 3, linear 3 | per ee: contact clearance f_n cone rom]"""
+    return 7 + 5 * n_ee
+
+
 class JacLmParams(C.Structure):
     """twr_jac_lm_params"""
     _fields_ = [("cg_iters", C.c_int32), ("power_iters", C.c_int32), ("cg_tol", C.c_double), ("mu_down", C.c_double),
@@ -251,6 +259,8 @@ def lib():
         L.twr_batch_joint_scores.argtypes = [C.c_void_p, C.POINTER(LegKinematics), C.c_void_p, C.c_int64, C.c_double, C.c_void_p,
                                              C.c_void_p]
         L.twr_batch_eval_joint_scores.argtypes = [C.c_void_p, C.POINTER(LegKinematics), C.c_void_p, C.c_double, C.c_void_p, C.c_void_p]
+        L.twr_batch_checks.argtypes = [C.c_void_p, C.POINTER(Model), C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]
+        L.twr_batch_check_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_void_p, C.c_void_p]
         _lib = L
     return _lib
 
@@ -759,6 +769,19 @@ class Batch:
         """twr_batch_eval_joint_scores: the scores of joint_scores_device straight from x, bit for bit, without a trajectory."""
         _check(lib().twr_batch_eval_joint_scores(self._h, C.byref(kin), C.c_void_p(d_x), float(dt), C.c_void_p(d_jscores),
                                                  C.c_void_p(stream)))
+
+    def checks_device(self, model, d_traj, traj_stride, dt, d_checks, check_stride, stream=0):
+        """twr_batch_checks: the records of sample_device (same dt and stride) -> check records
+        d_checks[p * check_stride + sample * check_rec(n_ee) + field] (device pointers); `model`: the Model whose nominal stance
+        and maximum deviation bound the range of motion."""
+        _check(lib().twr_batch_checks(self._h, C.byref(model), C.c_void_p(d_traj), int(traj_stride), float(dt), C.c_void_p(d_checks),
+                                      int(check_stride), C.c_void_p(stream)))
+
+    def check_scores_device(self, d_checks, check_stride, dt, d_cscores, stream=0):
+        """twr_batch_check_scores: check records -> d_cscores[CHECK_SCORE_REC * p + slot]: samples, max |linear residual|, max
+        |angular residual|, min swing clearance, max |stance clearance|, min f_n in contact, min cone in contact, max rom."""
+        _check(lib().twr_batch_check_scores(self._h, C.c_void_p(d_checks), int(check_stride), float(dt), C.c_void_p(d_cscores),
+                                            C.c_void_p(stream)))
 
     def host_buffers(self):
         """Page-locked x / g / jac arrays owned by the batch (numpy views); eval_host_pinned() uses them."""

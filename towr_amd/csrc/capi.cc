@@ -1163,6 +1163,66 @@ int twr_batch_eval_joint_scores(twr_batch* b, const twr_leg_kinematics* kin, con
   return launched(e);
 }
 
+namespace {
+// What the two check calls check before any device is touched (strides as check_joint_call); *n_max: the largest sample count.
+int check_checks_call(const twr_batch* b, std::initializer_list<const void*> buffers, double dt, int64_t traj_stride, int64_t check_stride,
+                      int* n_max) {
+  if (!b) return fail(TWR_ERR_INVALID, "null batch");
+  for (const void* p : buffers)
+    if (!p) return fail(TWR_ERR_INVALID, "null device buffer");
+  if (misaligned(buffers)) return fail(TWR_ERR_INVALID, "device buffers must be 8-byte aligned");
+  if (!std::isfinite(dt) || !(dt > 0)) return fail(TWR_ERR_INVALID, "dt must be finite and > 0");
+  *n_max = 0;
+  for (int p = 0; p < b->n_problems; ++p) {
+    if (!b->plan.sample_ok[p]) return fail(TWR_ERR_INVALID, "too many polynomials per spline for trajectory sampling");
+    const int n = twr::SampleCount(b->plan.t_total[p], dt);
+    if (traj_stride >= 0 && (int64_t)n * (20 + 13 * b->n_ee) > traj_stride) return fail(TWR_ERR_INVALID, "traj_stride too small for the samples");
+    if ((int64_t)n * TWR_CHECK_REC(b->n_ee) > check_stride) return fail(TWR_ERR_INVALID, "check_stride too small for the samples");
+    *n_max = std::max(*n_max, n);
+  }
+  return TWR_OK;
+}
+}  // namespace
+
+int twr_batch_checks(twr_batch* b, const twr_model* model, const double* d_traj, int64_t traj_stride, double dt, double* d_checks,
+                     int64_t check_stride, void* hip_stream) {
+  int n_max = 0;
+  if (!model) return fail(TWR_ERR_INVALID, "null model");
+  if (model->n_ee < 1 || model->n_ee > TWR_MAX_EE) return fail(TWR_ERR_INVALID, "twr_model: n_ee must be 1..4");
+  for (int e = 0; e < model->n_ee; ++e)
+    for (int d = 0; d < 3; ++d)
+      if (!std::isfinite(model->nominal_stance[e][d])) return fail(TWR_ERR_INVALID, "twr_model: nominal_stance must be finite");
+  for (int d = 0; d < 3; ++d)
+    if (!std::isfinite(model->max_dev[d]) || !(model->max_dev[d] >= 0)) return fail(TWR_ERR_INVALID, "twr_model: max_dev must be finite and >= 0");
+  if (!std::isfinite(model->force_limit)) return fail(TWR_ERR_INVALID, "twr_model: force_limit must be finite");
+  if (traj_stride < 0 || check_stride < 0) return fail(TWR_ERR_INVALID, "negative stride");
+  const int rc = check_checks_call(b, {d_traj, d_checks}, dt, traj_stride, check_stride, &n_max);
+  if (rc != TWR_OK) return rc;
+  if (model->n_ee != b->n_ee) return fail(TWR_ERR_INVALID, "twr_model: n_ee differs from the batch's");
+  try {
+    DeviceScope on(b->device);
+    TWR_HIP(on.status);
+    sample_work_for(*b, dt, traj_stride);
+    hipError_t e = twr::launch_checks(b->swork.d.get(), b->swork.n, d_traj, traj_stride, d_checks, check_stride, *model,
+                                      static_cast<hipStream_t>(hip_stream));
+    return launched(e);
+  } catch (const std::exception& e) {
+    return fail(TWR_ERR_HIP, e.what());
+  }
+}
+
+int twr_batch_check_scores(twr_batch* b, const double* d_checks, int64_t check_stride, double dt, double* d_cscores, void* hip_stream) {
+  int n_max = 0;
+  if (check_stride < 0) return fail(TWR_ERR_INVALID, "negative stride");
+  const int rc = check_checks_call(b, {d_checks, d_cscores}, dt, -1, check_stride, &n_max);
+  if (rc != TWR_OK) return rc;
+  DeviceScope on(b->device);
+  if (on.status != hipSuccess) return fail(TWR_ERR_HIP, "hipSetDevice failed");
+  hipError_t e = twr::launch_check_scores(b->node.d.get(), b->n_problems, d_checks, check_stride, dt, n_max, d_cscores,
+                                          static_cast<hipStream_t>(hip_stream));
+  return launched(e);
+}
+
 int twr_batch_host_buffers(twr_batch* b, double** h_x, double** h_g, double** h_jac) {
   if (!b) return fail(TWR_ERR_INVALID, "null batch");
   try {

@@ -56,6 +56,12 @@ hipError_t launch_joint_scores(const NodeWork* work, int n_problems, const doubl
                                int n_samples_max, double* scores, const twr_leg_kinematics& kin, hipStream_t stream);
 hipError_t launch_eval_joint_scores(const NodeWork* work, int n_problems, const double* x, double dt, int n_samples_max, double* scores,
                                     const twr_leg_kinematics& kin, hipStream_t stream);
+// Trajectory checks (kernels/checks.h): sample records -> check records over sample_kernel's work list (model: n_ee, nominal_stance
+// and max_dev are read; n_ee in 1..4); check records -> eight scores per problem.
+hipError_t launch_checks(const SampleWork* work, int n_work, const double* traj, int64_t traj_stride, double* out, int64_t check_stride,
+                         const twr_model& model, hipStream_t stream);
+hipError_t launch_check_scores(const NodeWork* work, int n_problems, const double* checks, int64_t check_stride, double dt,
+                               int n_samples_max, double* scores, hipStream_t stream);
 // dst (a batch's copy of a `Grid` layer, start index (0,0)) from src (the same sizes, start index (start_x, start_y)), and the map
 // centre into the n_hdr headers whose DevStruct::grid_px lies hdr_off[k] bytes into arena (kernels/grid_map_update.h).  One launch.
 hipError_t launch_grid_map_update(const float* src, float* dst, int size_x, int size_y, int start_x, int start_y, double pos_x,

@@ -1,5 +1,5 @@
 // Third translation unit of the kernels, plain flags: the utility kernels -- trajectory sampling, scoring from g, the planner's arg-min,
-// contact plan, nearest plane, joint-space trajectories and their scores, TWR_EVAL_CHECK, the grid_map layer update, the start of a request (x0 and variable bounds) -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
+// contact plan, nearest plane, joint-space trajectories and their scores, the trajectory checks and their scores, TWR_EVAL_CHECK, the grid_map layer update, the start of a request (x0 and variable bounds) -- each followed by its launch_* function (launch.h); none is used by an evaluation kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -11,6 +11,7 @@
 #include "kernels/host_launch.h"
 #include "kernels/spline_math.h"
 #include "kernels/phase_durations.h"
+#include "kernels/checks.h"
 #include "kernels/grid_map_update.h"
 #include "kernels/joints.h"
 #include "kernels/planes.h"
@@ -557,6 +558,139 @@ __global__ __launch_bounds__(64) void eval_joint_scores_kernel(const NodeWork* _
 hipError_t launch_eval_joint_scores(const NodeWork* work, int n_problems, const double* x, double dt, int n_samples_max, double* scores,
                                     const twr_leg_kinematics& kin, hipStream_t stream) {
   return twr_launch(eval_joint_scores_kernel, dim3(n_problems), dim3(64), 0, stream, work, x, dt, n_samples_max, scores, kin);
+}
+
+// ---------------------------------------------------------------- trajectory checks (kernels/checks.h)
+// twr_batch_checks: records of sample_kernel -> check records over the same work list, one wave per item, lane = sample.
+// An item's records are contiguous (64 x 576 B at four feet) but a lane's own record is 576 B from its neighbour's.  STAGED: the wave
+// copies the item into LDS with coalesced loads (lane l takes doubles l, l + 64, ...), each record at an odd number of doubles from
+// the next (a lane's ds_read_b64 then lands on its own bank pair), does the per-lane math from there, puts its check record into
+// the same image and copies the item's check records out the same way.  One workgroup holds 64 x 73 doubles = 37,376 B at four
+// feet: four waves per CU by LDS.  !STAGED: every lane reads its record from and writes its check record to global memory,
+// occupancy by registers alone.  Both run check_record, so they give the same bits (tests/test_checks.py runs on either build: one,
+// two and four feet against the numpy restatement; no robot of the presets has three).  Measured: the direct reads are the
+// faster form on both sweeps, 0.126 against 0.216 ms and 0.019 against 0.029 ms -- at one wave per SIMD the staged wave waits for
+// its own loads, its barrier and its stores in turn with nothing else to run -- so they are the default;
+// make DIAG=-DTWR_CHECKS_STAGED builds the other.
+#ifdef TWR_CHECKS_STAGED
+constexpr bool kChecksStaged = true;
+#else
+constexpr bool kChecksStaged = false;
+#endif
+// the wave's copy between `n` contiguous doubles at g and records of kRec doubles, kPad apart, in the image: double k of the
+// item is double k % kRec of record k / kRec.  A lane walks k = lane, lane + 64, ... with a running (row, col) instead of a
+// division per element; check_image_walk proves at compile time, for the record sizes in use, that the walk is that map.
+struct CheckImageWalk {
+  int row, col;
+  template <int kRec>
+  __host__ __device__ constexpr void start(int lane) {
+    row = lane / kRec;
+    col = lane % kRec;
+  }
+  template <int kRec>
+  __host__ __device__ constexpr void step() {
+    col += 64;
+    while (col >= kRec) {
+      col -= kRec;
+      ++row;
+    }
+  }
+};
+template <int kRec>
+constexpr bool check_image_walk() {
+  for (int lane = 0; lane < 64; ++lane) {
+    CheckImageWalk w{0, 0};
+    w.start<kRec>(lane);
+    for (int k = lane; k < 64 * kRec; k += 64) {
+      if (w.row != k / kRec || w.col != k % kRec) return false;
+      w.step<kRec>();
+    }
+  }
+  return true;
+}
+template <int kRec, int kPad, bool kIn>
+TWR_DEV void check_image_copy(double* __restrict__ img, double* __restrict__ g, int n, int lane) {
+  static_assert(kRec > 0 && kPad >= kRec && check_image_walk<kRec>(), "the running (row, col) of every lane is (k / kRec, k % kRec)");
+  CheckImageWalk w{0, 0};
+  w.start<kRec>(lane);
+#pragma unroll 8
+  for (int k = lane; k < n; k += 64) {
+    if (kIn) img[w.row * kPad + w.col] = g[k];
+    else g[k] = img[w.row * kPad + w.col];
+    w.step<kRec>();
+  }
+}
+template <int N_EE, bool STAGED>
+__global__ __launch_bounds__(64) void checks_kernel(const SampleWork* __restrict__ work, const double* __restrict__ traj,
+                                                    int64_t traj_stride, double* __restrict__ out, int64_t check_stride, CheckModel M) {
+  constexpr int kRec = 20 + 13 * N_EE, kRecPad = kRec | 1, kOut = TWR_CHECK_REC(N_EE), kOutPad = kOut | 1;
+  static_assert(kOutPad <= kRecPad, "the check records fit the image of the sample records");
+  const SampleWork sw = work[blockIdx.x];
+  const DevStruct* H = reinterpret_cast<const DevStruct*>(sw.blob);
+  const int lane = threadIdx.x;
+  const int64_t p = sw.out_off / traj_stride;
+  const double* src = traj + sw.out_off + (int64_t)sw.s0 * kRec;      // the item's cnt records, and where its check records go
+  double* dst = out + p * check_stride + (int64_t)sw.s0 * kOut;
+  double o[kOut];
+  if constexpr (STAGED) {
+    __shared__ double img[64 * kRecPad];
+    check_image_copy<kRec, kRecPad, true>(img, const_cast<double*>(src), sw.cnt * kRec, lane);
+    __syncthreads();
+    if (lane < sw.cnt) check_record<N_EE>(static_cast<const double*>(img + lane * kRecPad), H, M, o);
+    __syncthreads();
+    if (lane < sw.cnt) {
+#pragma unroll
+      for (int j = 0; j < kOut; ++j) img[lane * kOutPad + j] = o[j];
+    }
+    __syncthreads();
+    check_image_copy<kOut, kOutPad, false>(img, dst, sw.cnt * kOut, lane);
+  } else {
+    if (lane >= sw.cnt) return;
+    check_record<N_EE>(src + (int64_t)lane * kRec, H, M, o);
+#pragma unroll
+    for (int j = 0; j < kOut; ++j) dst[(int64_t)lane * kOut + j] = o[j];
+  }
+}
+hipError_t launch_checks(const SampleWork* work, int n_work, const double* traj, int64_t traj_stride, double* out, int64_t check_stride,
+                         const twr_model& model, hipStream_t stream) {
+  if (n_work <= 0) return hipSuccess;
+  CheckModel M;
+  for (int e = 0; e < kMaxEE; ++e)
+    for (int d = 0; d < 3; ++d) M.nominal[e][d] = e < model.n_ee ? model.nominal_stance[e][d] : 0.0;
+  for (int d = 0; d < 3; ++d) M.max_dev[d] = model.max_dev[d];
+  switch (model.n_ee) {
+    case 1: return twr_launch(checks_kernel<1, kChecksStaged>, dim3(n_work), dim3(64), 0, stream, work, traj, traj_stride, out, check_stride, M);
+    case 2: return twr_launch(checks_kernel<2, kChecksStaged>, dim3(n_work), dim3(64), 0, stream, work, traj, traj_stride, out, check_stride, M);
+    case 3: return twr_launch(checks_kernel<3, kChecksStaged>, dim3(n_work), dim3(64), 0, stream, work, traj, traj_stride, out, check_stride, M);
+    case 4: return twr_launch(checks_kernel<4, kChecksStaged>, dim3(n_work), dim3(64), 0, stream, work, traj, traj_stride, out, check_stride, M);
+  }
+  return hipErrorInvalidValue;
+}
+
+// twr_batch_check_scores: one wave per problem folds its check records, 64 samples per round (CheckFold); the sample count is
+// GetTrajectory's, as in joint_scores_kernel.
+__global__ __launch_bounds__(64) void check_scores_kernel(const NodeWork* __restrict__ work, const double* __restrict__ checks,
+                                                          int64_t check_stride, double dt, int n_samples_max, double* __restrict__ scores) {
+  const char* blob = reinterpret_cast<const char*>(work[blockIdx.x].blob);
+  const DevStruct* H = reinterpret_cast<const DevStruct*>(blob);
+  const double T = tbl<SampleTables>(blob, H->o_sample)->t_total;
+  const int lane = threadIdx.x, n_ee = H->n_ee, rec = TWR_CHECK_REC(n_ee);
+  const double* cp = checks + (int64_t)blockIdx.x * check_stride;
+  CheckFold F;
+  F.init();
+  for (int s0 = 0; s0 < n_samples_max; s0 += 64) {
+    const int s_idx = s0 + lane;
+    double t = 0.0;
+    for (int i = 0; i < s_idx; ++i) t += dt;
+    const bool live = t <= T + 1e-5;
+    if (!__any(live)) break;
+    if (live) F.take(cp + (int64_t)s_idx * rec, n_ee);
+  }
+  F.finish(lane, scores + TWR_CHECK_SCORE_REC * (size_t)blockIdx.x);
+}
+hipError_t launch_check_scores(const NodeWork* work, int n_problems, const double* checks, int64_t check_stride, double dt,
+                               int n_samples_max, double* scores, hipStream_t stream) {
+  return twr_launch(check_scores_kernel, dim3(n_problems), dim3(64), 0, stream, work, checks, check_stride, dt, n_samples_max, scores);
 }
 
 // ---------------------------------------------------------------- TWR_EVAL_CHECK
